@@ -6,10 +6,20 @@
 One "step" = one full optimisation step of scheme s4 (5 task losses over 4 domains x 8 graphs,
 5 per-task backwards, PCGrad, clip 0.5, AdamW) == run_training's loop body
 (reference src/pretrain/pretrain.py:113-155).  Prints ONE JSON line (rank 0) with
-  value      graphs/s over all ranks (weak scaling: every rank runs its own 32-graph step),
-  roofline   the GIN aggregation kernel on the 65,536-graph rung (x = 2.2 GB, streams from HBM),
-             algorithmic bytes / live HIP-event time, against the 8 TB/s HBM3E peak,
-  cpu_baseline  the CPU oracle's s4 step on this box's host cores (rank 0, N=1 only).
+  value        graphs/s over all ranks (weak scaling: every rank runs its own 32-graph step),
+  ms_per_step  milliseconds per timed step (exactly --steps of them, after the set-up and --warmup steps).
+With --full (rank 0) the line also carries the legs beside the headline, each timed on its own after the timed steps:
+  roofline     the GIN aggregation kernel on the 65,536-graph rung (x = 2.2 GB, streams from HBM),
+               algorithmic bytes / live HIP-event time, against the 8 TB/s HBM3E peak (+ roofline_bwd, roofline_gemm),
+  cora_finetune  the Cora_NC fine-tune step (N=1 only),
+  cpu_baseline   the CPU oracle's s4 step on the host's cores (N=1 only);
+without it these keys are null.  --no-roofline / --no-cora / --no-cpu-baseline drop single legs of a --full run.
+
+--dump-outputs DIR (rank 0) writes what the last timed step left for its caller, after the timing: the five task losses
+(DIR/loss.<task>.npy, float64 scalars), every floating-point tensor of the model's state_dict -- parameters and BatchNorm
+running statistics -- (DIR/model.<name>.npy, float32) and the AdamW moments in the engine's flat parameter layout
+(DIR/optimizer.exp_avg.npy, DIR/optimizer.exp_avg_sq.npy, float32): ~42 MB.  Seeds are fixed, so the same arguments give
+the same inputs on every run.
 """
 from __future__ import annotations
 
@@ -36,16 +46,24 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=400)
     ap.add_argument("--warmup", type=int, default=50)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the legs beside the headline: aggregation / GEMM rooflines, the Cora_NC "
+                         "fine-tune step (BASELINE.json configs[4]) and the CPU oracle baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's losses, model state and AdamW moments to DIR/<name>.npy (rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the aggregation / GEMM rooflines")
     ap.add_argument("--roofline-only", action="store_true", help="only the aggregation-kernel leg (used for the PMC passes)")
-    ap.add_argument("--no-cora", action="store_true", help="skip the Cora_NC fine-tune leg (BASELINE.json configs[4]) of the result line")
+    ap.add_argument("--no-cora", action="store_true", help="with --full: skip the Cora_NC fine-tune leg of the result line")
     ap.add_argument("--rng", choices=["reference", "vectorized", "device"], default=None,
                     help="how the step's augmentation/mask/negative indices are drawn: 'reference' = the exact "
                          "per-graph draw sequence of the reference from the CPU torch.Generator; 'vectorized' = same "
                          "distributions, all graphs of a domain at once (numpy); 'device' = masks and views built on the GPU "
                          "(csrc/augment.hip, Philox).  Default: reference when the native host module is built, else vectorized")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
 
 
 if __name__ == "__main__" and "WORLD_SIZE" not in os.environ:
@@ -334,6 +352,24 @@ def cpu_baseline(seed: int, budget_s: float = 20.0):
                            "sample": f"{n1} steps of the same workload (median {med1 * 1e3:.1f} ms/step), torch.set_num_threads(1)"}}
 
 
+def dump_outputs(engine, model, out_dir: str, limit_bytes: int = 64 << 20) -> int:
+    """What the last step left for its caller (see the module docstring), as DIR/<name>.npy; returns the bytes written."""
+    import numpy as np
+    arrays = {f"loss.{t}": np.asarray(v, dtype=np.float64) for t, v in engine.losses().items()}
+    for n, v in model.state_dict().items():
+        if v.is_floating_point():
+            arrays[f"model.{n}"] = v.detach().float().cpu().numpy()
+    arrays["optimizer.exp_avg"] = engine.exp_avg.detach().float().cpu().numpy()
+    arrays["optimizer.exp_avg_sq"] = engine.exp_avg_sq.detach().float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > limit_bytes:
+        raise SystemExit(f"--dump-outputs: {total} bytes of outputs, more than the {limit_bytes} allowed")
+    os.makedirs(out_dir, exist_ok=True)
+    for n, arr in arrays.items():
+        np.save(os.path.join(out_dir, n + ".npy"), arr)
+    return total
+
+
 def main() -> None:
     a = parse_args()
     # Only the result line may reach stdout: RCCL prints a banner (HIP / ROCm version, hostname, library path) on stdout when a
@@ -437,17 +473,20 @@ def main() -> None:
     log(f"{a.steps} steps in {elapsed:.3f} s; last-step losses {engine.losses()}")
     log("host ms/step: " + ", ".join(f"{k} {hm[k] / max(hm['steps'], 1):.2f}" for k in ("draw", "plan", "upload", "launch")) +
         f"; prefetch threads busy: draws {pf.draw_s / max(a.steps, 1) * 1e3:.2f}, layout {pf.busy_s / max(a.steps, 1) * 1e3:.2f}, launcher waited for them {pf.wait_s / max(a.steps, 1) * 1e3:.2f}")
+    if rank == 0 and a.dump_outputs:
+        nbytes = dump_outputs(engine, model, a.dump_outputs)
+        log(f"last step's outputs ({nbytes / 2**20:.1f} MiB) written to {a.dump_outputs}")
     roof = roof_gemm = cpu = None
-    if rank == 0 and not a.no_roofline:
+    if rank == 0 and a.full and not a.no_roofline:
         roof = aggregation_roofline(device)
         log(f"roofline {roof['achieved']} GB/s")
         roof_gemm = gemm_roofline(device)
         log(f"gemm {roof_gemm['achieved']} TFLOP/s")
     cora = None
-    if rank == 0 and world == 1 and not a.no_cora:
+    if rank == 0 and world == 1 and a.full and not a.no_cora:
         cora = cora_finetune(device, seed)
         log(f"cora fine-tune step {cora['ms_per_step']} ms (CPU oracle {cora['cpu_baseline']['value']} steps/s)")
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
         log("cpu baseline ...")
         cpu = cpu_baseline(seed)
     if rank == 0:
@@ -458,7 +497,7 @@ def main() -> None:
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "fp32", "data": "synthetic",
             "config": {"workload": "s4 (NFM+LP+NC+GC+GP) pre-training step, 4 domains x 8 synthetic ENZYMES-shaped graphs "
                                    "per rank (input dims 7/4/37/21, hidden 256, 5 GIN layers), PCGrad + clip + AdamW",
-                       "global_batch_graphs": GRAPHS_PER_STEP * world, "parallelism": f"dp{world}", "setup_steps": PRIME_STEPS, "index_rng": a.rng,
+                       "global_batch_graphs": GRAPHS_PER_STEP * world, "parallelism": f"dp{world}", "setup_steps": PRIME_STEPS, "full": a.full, "index_rng": a.rng,
                        "index_draws": ("native (csrc_host/hostdraw.cpp)" if (a.rng == "reference" and hostdraw() is not None) else
                                        "device (csrc/augment.hip; negatives on the host)" if a.rng == "device" else "python/numpy"),
                        "cross_stream_sync": "gates" if engine.use_gates else "events",
