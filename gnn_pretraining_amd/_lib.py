@@ -88,6 +88,11 @@ _SIGS: Dict[str, tuple] = {
     "gmp_group_sum_1d": (C.c_int, [p, i32, p, p, p, p]),
     "gmp_colsum_workspace_bytes": (sz, [i64, i64]),
     "gmp_colsum": (C.c_int, [p, p, i64, i64, i64, i32, p, sz, p]),
+    "gmp_sparse_linear_workspace_bytes": (sz, [i64, i32]),
+    "gmp_sparse_linear_fwd": (C.c_int, [p, p, p, i64, i64, p, i64, p, p, i32, i64, p, p, sz, p]),
+    "gmp_sparse_linear_wgrad": (C.c_int, [p, p, p, i64, i64, p, i32, p, i64, p, p]),
+    "gmp_sparse_csc_workspace_bytes": (sz, [i64, i64, i64]),
+    "gmp_sparse_csc_build": (C.c_int, [p, p, p, i64, i64, i64, p, p, p, p, p, sz, p]),
     "gmp_bn_workspace_bytes": (sz, [i64, i32, i32, i64]),
     "gmp_bn_sync_bytes": (sz, [i32, i32]),
     "gmp_bn_fwd": (C.c_int, [p, p, p, p, i32, i64, i64, i32, p, p, p, p, p, p, p, C.POINTER(BnConfig), p, sz, p]),

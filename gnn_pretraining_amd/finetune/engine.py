@@ -22,7 +22,11 @@ round 2 believed -- its kernels add up to 1.43 ms (BatchNorm 0.58, GEMMs 0.56) -
 a parallel graph branch for the weight-gradient GEMMs (GMP_FINETUNE_FORK=1) makes the replay itself cost 1.45 ms of host time.
 Second half of round 3: BatchNorm as slabs over the whole chip in one launch (gmp_bn_config.sync: 34 -> 12 us per backward launch) brought the
 kernels to 1.0 ms; the eager step with the weight-gradient GEMMs on the side stream then beats the replay (0.88 against 0.95 ms) and is the
-default; the capture stays available (GMP_FINETUNE_GRAPH=1) and tested."""
+default; the capture stays available (GMP_FINETUNE_GRAPH=1) and tested.
+
+Sparse features (opt-in, `x` a graph.SparseFeatures): the encoder GEMM becomes gmp_sparse_linear_fwd (W transposed into a workspace, one wave
+per node gathering the rows of W^T its non-zeros name) and its weight gradient gmp_sparse_linear_wgrad over the CSC form built once here, plus
+gmp_colsum for the bias.  The flat-buffer layout, the padded [256, dpad] slot and every other launch are the dense path's."""
 from __future__ import annotations
 
 import ctypes as C
@@ -33,6 +37,7 @@ import torch
 from torch import Tensor
 
 from .. import _lib as L, ops
+from ..graph import SparseFeatures
 from ..models.finetune_model import LR_BACKBONE, LR_FINETUNE, FinetuneGNN
 from ..models.gnn import DROPOUT_RATE, GNN_HIDDEN_DIM, GNN_NUM_LAYERS
 
@@ -56,8 +61,18 @@ class NodeClassificationEngine:
         dev = self.device
         self.N, self.d_in = int(x.size(0)), int(x.size(1))
         self.dpad = (self.d_in + 31) // 32 * 32
-        self.x = torch.zeros(self.N, self.dpad, device=dev)
-        self.x[:, :self.d_in] = x.to(dev)
+        # sparse (CSR) features: the encoder is gmp_sparse_linear_fwd / _wgrad on the same [256, dpad] weight slot; the CSC form the
+        # weight gradient reads is built here, once (the features never change)
+        self.sparse = isinstance(x, SparseFeatures)
+        if self.sparse:
+            self.x, self.xs = None, x.to(dev)
+            self.x_csc = self.xs.csc()
+            self.sp_wt = torch.empty(self.lib.gmp_sparse_linear_workspace_bytes(self.d_in, H), dtype=torch.uint8, device=dev)
+            self.sp_status = torch.zeros(1, dtype=torch.int32, device=dev)          # skipped indices (none once csc() has passed): loss()
+            self.colsum_ws = torch.empty(max(self.lib.gmp_colsum_workspace_bytes(self.N, H), 16), dtype=torch.uint8, device=dev)
+        else:
+            self.x = torch.zeros(self.N, self.dpad, device=dev)
+            self.x[:, :self.d_in] = x.to(dev)
         self.csr = ops.csr_build(edge_index.to(dev).contiguous(), self.N)
         self.classes = int(model.classification_head.mlp[0].weight.size(0))
         self._flatten()
@@ -188,8 +203,14 @@ class NodeClassificationEngine:
         enc, sp = self.model.input_encoder, self.seg_ptr.data_ptr()
         # 2,708 x 1,440 -> 256 is 172 output tiles for 256 CUs; unsliced since round 3 (three K-slices + their reduction: 38 us, one launch: 33 --
         # gmp_gemm_f32_workspace_bytes now slices NT / NN only below ~100 tiles)
-        self._gemm(st, NT, self.x.data_ptr(), P("input_encoder.linear.weight"), P("input_encoder.linear.bias"), self.z0.data_ptr(), N, H, self.dpad,
-                   self.dpad, self.dpad, H, ws=self.gemm_ws)
+        if self.sparse:
+            xs = self.xs
+            self._chk(lib.gmp_sparse_linear_fwd(xs.rowptr.data_ptr(), xs.col.data_ptr(), xs.val.data_ptr(), N, self.d_in, P("input_encoder.linear.weight"),
+                                                self.dpad, P("input_encoder.linear.bias"), self.z0.data_ptr(), H, H, self.sp_status.data_ptr(),
+                                                self.sp_wt.data_ptr(), self.sp_wt.numel(), st), "sparse encoder")
+        else:
+            self._gemm(st, NT, self.x.data_ptr(), P("input_encoder.linear.weight"), P("input_encoder.linear.bias"), self.z0.data_ptr(), N, H, self.dpad,
+                       self.dpad, self.dpad, H, ws=self.gemm_ws)
         cfg = self._cfg(True, True, 1)
         self._chk(lib.gmp_bn_fwd(self.z0.data_ptr(), None, sp, None, 1, N, N, H, P("input_encoder.batch_norm.weight"), P("input_encoder.batch_norm.bias"),
                                  enc.batch_norm.running_mean.data_ptr(), enc.batch_norm.running_var.data_ptr(), self.enc_mean.data_ptr(),
@@ -354,7 +375,14 @@ class NodeClassificationEngine:
                                  P("input_encoder.batch_norm.bias"), enc.batch_norm.running_mean.data_ptr(), enc.batch_norm.running_var.data_ptr(),
                                  self.enc_mean.data_ptr(), self.enc_rstd.data_ptr(), gu.data_ptr(), g, g, one, _i64([self._G("input_encoder.batch_norm.weight")]),
                                  _i64([self._G("input_encoder.batch_norm.bias")]), 1, C.byref(cfg), self.bn_ws.data_ptr(), self.bn_ws.numel(), st), "bn encoder bwd")
-        self._wgrad(st, gu.data_ptr(), self.x.data_ptr(), "input_encoder.linear.weight", "input_encoder.linear.bias", H, self.dpad, self.dpad)
+        if self.sparse:                                             # dW over the whole [256, dpad] slot (padding columns 0.0), db = colsum
+            colptr, row, val_t = self.x_csc
+            self._chk(lib.gmp_sparse_linear_wgrad(colptr.data_ptr(), row.data_ptr(), val_t.data_ptr(), N, self.d_in, gu.data_ptr(), H,
+                                                  g + 4 * self._G("input_encoder.linear.weight"), self.dpad, self.sp_status.data_ptr(), st), "sparse wgrad")
+            self._chk(lib.gmp_colsum(gu.data_ptr(), g + 4 * self._G("input_encoder.linear.bias"), N, H, H, 0, self.colsum_ws.data_ptr(),
+                                     self.colsum_ws.numel(), st), "encoder bias grad")
+        else:
+            self._wgrad(st, gu.data_ptr(), self.x.data_ptr(), "input_encoder.linear.weight", "input_encoder.linear.bias", H, self.dpad, self.dpad)
         if side is not None:                                        # every weight gradient is in the buffer
             if gates:
                 self._chk(lib.gmp_gate_open(flags + 4 * 40, epoch, sst), "gate open")
@@ -376,6 +404,8 @@ class NodeClassificationEngine:
         """Mean cross-entropy of the last step (a read-back: the one place the loop synchronises, so the gates' time-out word and the slab
         BatchNorm's are looked at here too)."""
         v = float(self.loss_sum.item())
+        if self.sparse and int(self.sp_status.item()) != 0:
+            raise L.GnnmpError(f"fine-tune engine: the sparse encoder skipped {int(self.sp_status.item())} out-of-range feature indices")
         if int(self.sync_flags[63].item()) != 0 or (self.bn_sync is not None and int(self.bn_sync[0].item()) != 0):
             raise L.GnnmpError("fine-tune engine: a cross-stream gate or a BatchNorm slab wait timed out (streams sharing a hardware queue, "
                                "a tool serialising kernels, or a sync buffer shared between streams): results since then are not to be trusted")

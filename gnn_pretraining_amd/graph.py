@@ -16,6 +16,105 @@ import torch
 from torch import Tensor
 
 
+class SparseFeatures:
+    """A node-feature matrix [N, K] in CSR form (int32 ``rowptr`` / ``col``, fp32 ``val``): the bag-of-words features of the
+    Planetoid domains (Cora, CiteSeer) keep ~1 % of their entries after NormalizeFeatures (src/data/data_setup.py:154).
+    Stands in for a dense ``x`` wherever the input encoder reads it (models/gnn.Linear, finetune/engine.py); ``Data.to`` /
+    ``Batch.to`` carry it.  Columns are sorted and unique within a row.  The CSC form the weight gradient reads is built
+    once, on first use, and cached (``csc()``); moving the container moves the cached form with it."""
+
+    def __init__(self, rowptr: Tensor, col: Tensor, val: Tensor, shape, csc=None) -> None:
+        self.rowptr, self.col, self.val = rowptr, col, val
+        self.shape = torch.Size((int(shape[0]), int(shape[1])))
+        self._csc = csc                   # (colptr [K+1], row [nnz], val_t [nnz]) once built
+        if rowptr.dtype != torch.int32 or col.dtype != torch.int32 or val.dtype != torch.float32:
+            raise TypeError(f"SparseFeatures: int32 rowptr / col and fp32 val expected, got {rowptr.dtype}, {col.dtype}, {val.dtype}")
+        if rowptr.numel() != self.shape[0] + 1 or col.numel() != val.numel():
+            raise ValueError(f"SparseFeatures: rowptr has {rowptr.numel()} entries for {self.shape[0]} rows, col / val {col.numel()} / {val.numel()}")
+
+    @staticmethod
+    def _from_coo(row: Tensor, col: Tensor, val: Tensor, shape) -> "SparseFeatures":
+        """(row, col) already in row-major order without duplicates."""
+        n = int(shape[0])
+        counts = torch.bincount(row, minlength=n) if row.numel() else torch.zeros(n, dtype=torch.long, device=row.device)
+        rowptr = torch.zeros(n + 1, dtype=torch.int64, device=row.device)
+        rowptr[1:] = counts.cumsum(0)
+        return SparseFeatures(rowptr.to(torch.int32), col.to(torch.int32), val.to(torch.float32).contiguous(), shape)
+
+    @staticmethod
+    def from_dense(x: Tensor) -> "SparseFeatures":
+        if x.dim() != 2:
+            raise ValueError(f"SparseFeatures.from_dense: 2-D tensor expected, got {tuple(x.shape)}")
+        row, col = (x != 0).nonzero(as_tuple=True)           # row-major order: columns ascending within a row
+        return SparseFeatures._from_coo(row, col, x[row, col], x.shape)
+
+    @staticmethod
+    def from_torch(t: Tensor) -> "SparseFeatures":
+        """From a torch sparse CSR or COO tensor (duplicates summed, columns sorted; stored zeros are kept)."""
+        if t.layout not in (torch.sparse_csr, torch.sparse_coo) or t.dim() != 2:
+            raise ValueError(f"SparseFeatures.from_torch: a 2-D sparse CSR / COO tensor expected, got {t.layout} {tuple(t.shape)}")
+        c = t.to_sparse_coo().coalesce()
+        idx = c.indices()
+        return SparseFeatures._from_coo(idx[0], idx[1], c.values(), t.shape)
+
+    def to_dense(self) -> Tensor:
+        out = torch.zeros(self.shape, dtype=torch.float32, device=self.device)
+        rows = torch.repeat_interleave(torch.arange(self.shape[0], device=self.device), self.rowptr[1:].long() - self.rowptr[:-1].long())
+        out[rows, self.col.long()] = self.val
+        return out
+
+    @property
+    def device(self) -> torch.device:
+        return self.val.device
+
+    @property
+    def nnz(self) -> int:
+        return int(self.val.numel())
+
+    def size(self, dim: Optional[int] = None):
+        return self.shape if dim is None else self.shape[dim]
+
+    def dim(self) -> int:
+        return 2
+
+    def to(self, device, non_blocking: bool = False) -> "SparseFeatures":
+        m = lambda t: t.to(device, non_blocking=non_blocking)
+        csc = None if self._csc is None else tuple(m(t) for t in self._csc)
+        return SparseFeatures(m(self.rowptr), m(self.col), m(self.val), self.shape, csc)
+
+    def cpu(self) -> "SparseFeatures":
+        return self.to("cpu")
+
+    def clone(self) -> "SparseFeatures":
+        csc = None if self._csc is None else tuple(t.clone() for t in self._csc)
+        return SparseFeatures(self.rowptr.clone(), self.col.clone(), self.val.clone(), self.shape, csc)
+
+    def csc(self):
+        """(colptr int32 [K+1], row int32 [nnz], val_t fp32 [nnz]): X by columns, ascending row within a column.  Built once:
+        on the GPU by gmp_sparse_csc_build (which raises if a column index lies outside [0, K)), on the host by a stable sort."""
+        if self._csc is None:
+            if self.device.type == "cuda":
+                from . import ops
+                colptr, row, val_t, status = ops.sparse_csc_build(self)
+                if int(status.item()) != 0:
+                    raise ValueError(f"SparseFeatures: {int(status.item())} column indices outside [0, {self.shape[1]})")
+                self._csc = (colptr, row, val_t)
+            else:
+                K = self.shape[1]
+                col = self.col.long()
+                if col.numel() and (int(col.min()) < 0 or int(col.max()) >= K):
+                    raise ValueError(f"SparseFeatures: column indices outside [0, {K})")
+                rows = torch.repeat_interleave(torch.arange(self.shape[0]), self.rowptr[1:].long() - self.rowptr[:-1].long())
+                order = torch.sort(col, stable=True).indices
+                colptr = torch.zeros(K + 1, dtype=torch.int64)
+                colptr[1:] = torch.bincount(col, minlength=K).cumsum(0)
+                self._csc = (colptr.to(torch.int32), rows[order].to(torch.int32), self.val[order].contiguous())
+        return self._csc
+
+    def __repr__(self) -> str:
+        return f"SparseFeatures(shape={tuple(self.shape)}, nnz={self.nnz}, device={self.device})"
+
+
 class Data:
     def __init__(self, x: Tensor, edge_index: Tensor, y: Optional[Tensor] = None,
                  graph_properties: Optional[Tensor] = None) -> None:

@@ -17,6 +17,7 @@ import torch.nn as nn
 from torch import Tensor
 
 from .. import operators as O
+from ..graph import SparseFeatures
 
 DROPOUT_RATE = 0.2
 GNN_HIDDEN_DIM = 256
@@ -24,9 +25,14 @@ GNN_NUM_LAYERS = 5
 
 
 class Linear(nn.Linear):
-    """nn.Linear whose forward runs the f32-MFMA GEMM (parameters/keys unchanged)."""
+    """nn.Linear whose forward runs the f32-MFMA GEMM (parameters/keys unchanged); a SparseFeatures input (CSR node features,
+    graph.SparseFeatures) takes the sparse gather-sum kernels instead."""
 
     def forward(self, x: Tensor, relu: bool = False) -> Tensor:
+        if isinstance(x, SparseFeatures):
+            if relu:
+                raise ValueError("Linear: no fused ReLU on sparse input")
+            return O.sparse_linear(x, self.weight, self.bias)
         return O.linear(x, self.weight, self.bias, relu)
 
 

@@ -4,6 +4,7 @@ re-implemented as autograd Functions over libgnnmp (SURVEY.md section 8b "operat
     gin_aggregate(x, edge_index, eps)      GINConv's propagate + (1+eps) x       gnn.py:29-41
     global_mean_pool / global_max_pool     PyG read-out pooling                  tasks.py:241-246,299
     linear(x, W, b)                        nn.Linear on the f32 MFMA             gnn.py:14,31,34 heads.py:42
+    sparse_linear(x, W, b)                 nn.Linear on CSR features (gather-sum)  gnn.py:17-22 (Planetoid inputs)
     batch_norm_act(...)                    BatchNorm1d (+residual,+ReLU,+dropout) gnn.py:19-22,42-43
     take_rows(h, idx)                      h[idx]                                tasks.py:80
     lp_edge_features(h, edges)             [hs+hd | hs*hd | |hs-hd|]             heads.py:58-66
@@ -162,6 +163,29 @@ class _Linear(torch.autograd.Function):
 def linear(x: Tensor, weight: Tensor, bias: Optional[Tensor], relu: bool = False) -> Tensor:
     """x W^T + b (torch.nn.Linear layout: weight [out,in]); optional fused ReLU."""
     return _Linear.apply(x, weight, bias, relu)
+
+
+class _SparseLinear(torch.autograd.Function):
+    """x W^T + b with x a SparseFeatures (CSR).  x is a constant of the graph: only dW (= G^T X, from x's cached CSC form) and db flow back."""
+
+    @staticmethod
+    def forward(ctx, weight, bias, x):
+        ctx.x = x
+        return ops.sparse_linear_fwd(x, weight, bias)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, g = ctx.x, g.contiguous()
+        gw = ops.sparse_linear_wgrad(x.csc(), x.shape[0], g) if ctx.needs_input_grad[0] else None
+        gb = ops.colsum(g) if ctx.needs_input_grad[1] else None
+        return gw, gb, None
+
+
+def sparse_linear(x, weight: Tensor, bias: Optional[Tensor]) -> Tensor:
+    """x W^T + b for a SparseFeatures x [N, K] (gmp_sparse_linear_fwd); the weight may be a row-strided view."""
+    if x.val.requires_grad:
+        raise GnnmpError("sparse_linear: SparseFeatures carry no gradient (the input features are constants)")
+    return _SparseLinear.apply(weight, bias, x)
 
 
 # --------------------------------------------------------------------------- #

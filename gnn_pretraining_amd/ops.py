@@ -223,6 +223,83 @@ def colsum(A: Tensor, out: Optional[Tensor] = None, accumulate: bool = False) ->
     return out
 
 
+def _sparse_ok(x, K_needed: bool = True) -> None:
+    from .graph import SparseFeatures
+    if not isinstance(x, SparseFeatures):
+        raise L.GnnmpError(f"expected SparseFeatures, got {type(x).__name__}")
+    _need(x.rowptr, torch.int32, "x.rowptr", 1); _need(x.col, torch.int32, "x.col", 1); _need(x.val, torch.float32, "x.val", 1)
+    if x.rowptr.numel() != x.shape[0] + 1:
+        raise L.GnnmpError(f"x.rowptr has {x.rowptr.numel()} entries for {x.shape[0]} rows")
+
+
+def sparse_linear_fwd(x, weight: Tensor, bias: Optional[Tensor] = None, out: Optional[Tensor] = None,
+                      status: Optional[Tensor] = None) -> Tensor:
+    """out[N, H] = X W^T + b with X a SparseFeatures [N, K] and W [H, >= K] (a row-strided view such as the fine-tune engine's [256, 1433]
+    view of its [256, 1440] slot is read in place).  status (int32[1], nullable): skipped column indices are ADDED to it."""
+    _sparse_ok(x)
+    _need_rows(weight, "weight")
+    N, K = x.shape
+    H = weight.size(0)
+    if weight.size(1) != K:
+        raise L.GnnmpError(f"sparse_linear: weight has {weight.size(1)} columns for {K} features")
+    ldw = weight.stride(0) if H > 1 else K
+    if bias is not None:
+        _need(bias, torch.float32, "bias", 1)
+        if bias.numel() != H:
+            raise L.GnnmpError("sparse_linear: bias length")
+    if out is None:
+        out = torch.empty(N, H, dtype=torch.float32, device=weight.device)
+    else:
+        _need(out, torch.float32, "out", 2)
+        if tuple(out.shape) != (N, H):
+            raise L.GnnmpError("sparse_linear: out shape")
+    if status is not None:
+        _need(status, torch.int32, "status", 1)
+    l = L.lib()
+    ws = _ws(l.gmp_sparse_linear_workspace_bytes(K, H), weight.device)
+    L.check(l.gmp_sparse_linear_fwd(_ptr(x.rowptr), _ptr(x.col), _ptr(x.val), N, K, _ptr(weight), ldw, _ptr(bias), _ptr(out), H, H,
+                                    _ptr(status), _ptr(ws), ws.numel(), _stream(weight)), "gmp_sparse_linear_fwd")
+    return out
+
+
+def sparse_csc_build(x) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """(colptr int32 [K+1], row int32 [nnz], val_t fp32 [nnz], status int32[1]) of a SparseFeatures on the GPU; status = column
+    indices outside [0, K) (left out; the first colptr[K] slots of row / val_t are valid)."""
+    _sparse_ok(x)
+    N, K = x.shape
+    nnz, dev = x.nnz, x.device
+    colptr, row = torch.empty(K + 1, dtype=torch.int32, device=dev), torch.zeros(nnz, dtype=torch.int32, device=dev)
+    val_t, status = torch.zeros(nnz, dtype=torch.float32, device=dev), torch.empty(1, dtype=torch.int32, device=dev)
+    l = L.lib()
+    ws = _ws(l.gmp_sparse_csc_workspace_bytes(N, K, nnz), dev)
+    L.check(l.gmp_sparse_csc_build(_ptr(x.rowptr), _ptr(x.col), _ptr(x.val), N, K, nnz, _ptr(colptr), _ptr(row), _ptr(val_t), _ptr(status),
+                                   _ptr(ws), ws.numel(), _stream(x.val)), "gmp_sparse_csc_build")
+    return colptr, row, val_t, status
+
+
+def sparse_linear_wgrad(csc, num_rows: int, g: Tensor, out: Optional[Tensor] = None, status: Optional[Tensor] = None) -> Tensor:
+    """dW [H, ldw] = G^T X from the CSC form (colptr, row, val_t) of X [num_rows, K]; out (nullable) may be wider than K (its padding
+    columns are overwritten with 0.0, like every column without entries)."""
+    colptr, row, val_t = csc
+    _need(colptr, torch.int32, "colptr", 1); _need(row, torch.int32, "row", 1); _need(val_t, torch.float32, "val_t", 1)
+    _need(g, torch.float32, "g", 2)
+    K, H = colptr.numel() - 1, g.size(1)
+    if g.size(0) != num_rows:
+        raise L.GnnmpError(f"sparse_linear_wgrad: g has {g.size(0)} rows for {num_rows}")
+    if out is None:
+        out = torch.empty(H, K, dtype=torch.float32, device=g.device)
+    else:
+        _need_rows(out, "out")
+        if out.size(0) != H or out.size(1) < K:
+            raise L.GnnmpError(f"sparse_linear_wgrad: out {tuple(out.shape)} for [{H}, >= {K}]")
+    ldw = out.stride(0) if H > 1 else out.size(1)
+    if status is not None:
+        _need(status, torch.int32, "status", 1)
+    L.check(L.lib().gmp_sparse_linear_wgrad(_ptr(colptr), _ptr(row), _ptr(val_t), num_rows, K, _ptr(g), H, _ptr(out), ldw, _ptr(status),
+                                            _stream(g)), "gmp_sparse_linear_wgrad")
+    return out
+
+
 def make_bn_config(training: bool, relu: bool, dropout_p: float = 0.0, seed: int = 0, stream_id: int = 0,
                    eps: float = 1e-5, momentum: float = 0.1, sync: Optional[Tensor] = None) -> L.BnConfig:
     """sync: zero-filled int32 device tensor of bn_sync_words(channels, segments) words (gmp_bn_config.sync): segments of 1,025-4,096

@@ -15,8 +15,10 @@
  *   - all pointers are DEVICE pointers unless a parameter says "host";
  *   - all work is enqueued asynchronously on `stream` (a hipStream_t passed as
  *     void*); no call synchronises;
- *   - feature matrices are row-major fp32; graph indices handed over by the caller
- *     are int64 (the reference's dtype), CSR arrays produced here are int32;
+ *   - feature matrices are row-major fp32 -- except the sparse input of
+ *     gmp_sparse_linear_*, which is CSR (int32 rowptr / col, fp32 values); graph
+ *     indices handed over by the caller are int64 (the reference's dtype), CSR
+ *     arrays produced here are int32;
  *   - F (feature width) must be a multiple of 4 and rows must be 16-byte aligned.
  */
 #ifndef GNNMP_H
@@ -449,6 +451,39 @@ int gmp_encoder_bwd(const float* x_all, int64_t num_x_rows, int64_t num_rows, in
                     int dpad, int groups, const int32_t* group_seg_host, const int64_t* off_w_host,
                     const int64_t* off_b_host, float* grad_out, void* workspace, size_t workspace_bytes,
                     gmp_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
+ * Sparse (CSR) input for InputEncoder.linear (gnn.py:17-22) on the Planetoid domains, whose bag-of-words
+ * features keep ~1 % of their entries after NormalizeFeatures (data_setup.py:154).  Opt-in; the dense GEMM
+ * path is untouched.
+ *   X [N, K]: CSR rowptr int32 [N+1], col int32 [nnz], val fp32 [nnz] (columns need not be sorted).
+ *   W [H, ldw] row-major (nn.Linear layout), ldw >= K: the fine-tune engine's K-padded slot works as is.
+ *   H (out_features) must be a multiple of 64 and <= 1024, else GMP_ERR_UNSUPPORTED (256 is the model's).
+ *   status: device int32[1], nullable; the forward and the weight gradient ADD the number of indices they
+ *   skipped (column outside [0,K), resp. CSC row outside [0,N)) -- the caller zeroes it.
+ *
+ * fwd:   out[r, :] = sum_{k in rowptr[r]..rowptr[r+1]} val[k] * W[:, col[k]] + bias   (empty row -> bias)
+ *        out [N, ldo] fp32, ldo >= H and a multiple of 4; bias [H] nullable.  Two launches: W transposed into
+ *        the workspace (gmp_sparse_linear_workspace_bytes(K, H) bytes), then one wave per row gathering rows
+ *        of W^T.  Each output is one sum in non-zero order: bitwise reproducible.
+ * wgrad: dW[h, k] = sum over column k of val_t * g[row, h]   (G^T X; g [N, H] contiguous, 16-byte aligned)
+ *        from the CSC form (colptr int32 [K+1], row int32, val_t fp32) of gmp_sparse_csc_build.  OVERWRITES
+ *        every column of [0, ldw): columns without entries and the padding [K, ldw) get exactly 0.0.  No
+ *        atomics: each element is one fixed-order sum.  The bias gradient is gmp_colsum(g).
+ * csc:   the CSC form of X, stable (ascending row within a column; gmp_csr_build over the (row, col)
+ *        pairs).  status is ZEROED, then counts the non-zeros whose column lies outside [0,K): those are
+ *        left out, colptr[K] = the non-zeros kept.  row / val_t need nnz slots.  Once per feature matrix.
+ * ------------------------------------------------------------------------- */
+size_t gmp_sparse_linear_workspace_bytes(int64_t in_features, int out_features);
+int gmp_sparse_linear_fwd(const int32_t* rowptr, const int32_t* col, const float* val, int64_t num_rows, int64_t in_features,
+                          const float* weight, int64_t ldw, const float* bias, float* out, int out_features, int64_t ldo,
+                          int32_t* status, void* workspace, size_t workspace_bytes, gmp_stream_t stream);
+int gmp_sparse_linear_wgrad(const int32_t* colptr, const int32_t* row, const float* val_t, int64_t num_rows, int64_t in_features,
+                            const float* g, int out_features, float* dW, int64_t ldw, int32_t* status, gmp_stream_t stream);
+size_t gmp_sparse_csc_workspace_bytes(int64_t num_rows, int64_t in_features, int64_t nnz);
+int gmp_sparse_csc_build(const int32_t* rowptr, const int32_t* col, const float* val, int64_t num_rows, int64_t in_features,
+                         int64_t nnz, int32_t* colptr, int32_t* row, float* val_t, int32_t* status, void* workspace,
+                         size_t workspace_bytes, gmp_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
  * Multi-tensor PCGrad + clip_grad_norm_ + AdamW over flat buffers (gradient_surgery.py:41-103,
