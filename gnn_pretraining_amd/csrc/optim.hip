@@ -201,7 +201,10 @@ __global__ __launch_bounds__(64) void solve_kernel(const MtArgs a) {
             hp[i] = i < a.n_order && has[a.order[i]];
             nh += hp[i];
         }
-        if (hp[0]) {
+        // the reference projects (and counts the pairs of) every tensor two tasks hold, also the ones it then does not emit because the
+        // first-shuffled task lacks them (gradient_surgery.py _project_gradient runs over all of task i's tensors): the counts come from
+        // every such tensor, the weights are used only where hp[0]
+        if (nh > 1 || hp[0]) {
             double Gp[MAXT][MAXT];
 #pragma unroll
             for (int i = 0; i < MAXT; ++i)
@@ -242,7 +245,7 @@ __global__ __launch_bounds__(64) void solve_kernel(const MtArgs a) {
 #pragma unroll
                     for (int b = 0; b < MAXT; ++b) wout[b] += (float)(alpha[i][b] / nh);
                 }
-            flag = 1;
+            flag = hp[0] ? 1 : 0;
         }
         float* w = a.weights + k * MAXT;
         for (int t = 0; t < MAXT; ++t) w[t] = 0.f;
