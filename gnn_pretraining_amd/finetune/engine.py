@@ -74,7 +74,8 @@ class NodeClassificationEngine:
             self.x = torch.zeros(self.N, self.dpad, device=dev)
             self.x[:, :self.d_in] = x.to(dev)
         self.csr = ops.csr_build(edge_index.to(dev).contiguous(), self.N)
-        self.classes = int(model.classification_head.mlp[0].weight.size(0))
+        head = model.classification_head                  # (the link-prediction head has no class logits: LinkPredictionEngine)
+        self.classes = int(head.mlp[0].weight.size(0)) if hasattr(head, "mlp") else 0
         self._flatten()
         f = lambda *s: torch.empty(*s, device=dev)
         N, Lr = self.N, GNN_NUM_LAYERS
@@ -181,10 +182,11 @@ class NodeClassificationEngine:
         base = self.seed * 1000003
         sync = (self.bn_sync.data_ptr(), self.bn_sync.numel()) if self.bn_sync is not None else (None, 0)
         if self._seed_dev:
-            return L.BnConfig(int(self.model.training), int(relu), 1e-5, 0.1, p, base & (2 ** 64 - 1), site, self._seed_dev, *sync)
-        return L.BnConfig(int(self.model.training), int(relu), 1e-5, 0.1, p, (base + self.step_count) & (2 ** 64 - 1), site, None, *sync)
+            return L.BnConfig(int(self.model.training), int(relu), 1e-5, 0.1, p, base & (2 ** 64 - 1), site + self._site_base, self._seed_dev, *sync)
+        return L.BnConfig(int(self.model.training), int(relu), 1e-5, 0.1, p, (base + self.step_count) & (2 ** 64 - 1), site + self._site_base, None, *sync)
 
     _seed_dev = None
+    _site_base = 0                      # added to every dropout site of a forward (LinkPredictionEngine.mining_forward: a second pass per step)
 
     def _gemm(self, st, mode, A, B, bias, Cc, M, N, K, lda, ldb, ldc, ws: Optional[Tensor] = None):
         self._chk(self.lib.gmp_gemm_f32(mode, A, B, bias, Cc, M, N, K, lda, ldb, ldc, 1.0, 0, 0, None if ws is None else ws.data_ptr(),
@@ -198,6 +200,15 @@ class NodeClassificationEngine:
 
     # ------------------------------------------------------------------ forward (finetune_model.py:68-80, message passing on the full graph)
     def forward(self) -> Tensor:
+        self._backbone_forward()
+        self._gemm(torch.cuda.current_stream(self.device).cuda_stream, NT, self.h[GNN_NUM_LAYERS].data_ptr(), self._P("classification_head.mlp.0.weight"),
+                   self._P("classification_head.mlp.0.bias"), self.logits.data_ptr(), self.N, self.classes, H, H, H, self.classes)
+        if self.model.training:
+            self._bn_calls += 1             # num_batches_tracked only matters for a saved state_dict (momentum is fixed): flush_counters()
+        return self.logits
+
+    def _backbone_forward(self) -> None:
+        """Encoder + the GIN layers into h[GNN_NUM_LAYERS]; every activation the backward reads stays in the engine's buffers."""
         lib, N, P, c = self.lib, self.N, self._P, self.csr
         st = torch.cuda.current_stream(self.device).cuda_stream
         enc, sp = self.model.input_encoder, self.seg_ptr.data_ptr()
@@ -228,11 +239,6 @@ class NodeClassificationEngine:
             self._chk(lib.gmp_bn_fwd(self.z2[l].data_ptr(), self.h[l].data_ptr(), sp, None, 1, N, N, H, P(pre + "batch_norm.weight"), P(pre + "batch_norm.bias"),
                                      bn2.running_mean.data_ptr(), bn2.running_var.data_ptr(), self.stat["m2"][l].data_ptr(), self.stat["s2"][l].data_ptr(),
                                      self.h[l + 1].data_ptr(), C.byref(cfg), self.bn_ws.data_ptr(), self.bn_ws.numel(), st), "bn2")
-        self._gemm(st, NT, self.h[GNN_NUM_LAYERS].data_ptr(), P("classification_head.mlp.0.weight"), P("classification_head.mlp.0.bias"), self.logits.data_ptr(),
-                   N, self.classes, H, H, H, self.classes)
-        if self.model.training:
-            self._bn_calls += 1             # num_batches_tracked only matters for a saved state_dict (momentum is fixed): flush_counters()
-        return self.logits
 
     def flush_counters(self) -> None:
         if self._bn_calls:
@@ -283,7 +289,7 @@ class NodeClassificationEngine:
     def _enqueue(self, node_indices: Tensor, targets: Tensor, apply_update: bool, forked: bool = False) -> None:
         """The step's launches on the current stream.  forked: the weight-gradient GEMMs (they only feed the gradient buffer) go to the
         side stream behind an event of the main one -- inside a capture a parallel branch of the graph -- and are joined before AdamW."""
-        lib, N, P, c, Cn = self.lib, self.N, self._P, self.csr, self.classes
+        lib, N, P, c = self.lib, self.N, self._P, self.csr
         main = torch.cuda.current_stream(self.device)
         st = main.cuda_stream
         side = self.side if (forked and self.side is not None) else None
@@ -317,27 +323,9 @@ class NodeClassificationEngine:
                 self._chk(lib.gmp_gate_open(flags + 4 * (nfork[0] - 1), epoch, st), "gate open")
 
         self.forward()
-        M = int(node_indices.numel())
-        if self._train_idx is None or self._train_idx.numel() != M:
-            f = lambda *s: torch.empty(*s, device=self.device)
-            self._rows_logits, self._rows_g, self._rows_h = f(M, Cn), f(M, Cn), f(M, H)
-            self._rows_gh = f(M, H)
-        self._train_idx, self.num_targets = node_indices, M
-        self.g_scale.fill_(1.0 / M)
-        idx, tgt, g = node_indices.data_ptr(), targets.data_ptr(), self.grad.data_ptr()
-        hL = self.h[GNN_NUM_LAYERS]
-        self._chk(lib.gmp_row_gather(self.logits.data_ptr(), idx, None, self._rows_logits.data_ptr(), M, N, Cn, st), "logit rows")
-        self._chk(lib.gmp_cross_entropy_sum_fwd(self._rows_logits.data_ptr(), tgt, M, Cn, self.loss_sum.data_ptr(), self.loss_ws.data_ptr(), self.loss_ws.numel(), st), "ce")
-        self._chk(lib.gmp_cross_entropy_sum_bwd(self._rows_logits.data_ptr(), tgt, M, Cn, self.g_scale.data_ptr(), self._rows_g.data_ptr(), st), "ce bwd")
-        # head: dW = g^T h[idx], db = colsum(g), g_h[idx] = g W  (only the M training rows carry a gradient)
-        self._chk(lib.gmp_row_gather(hL.data_ptr(), idx, None, self._rows_h.data_ptr(), M, N, H, st), "h rows")
-        self._chk(lib.gmp_gemm_f32_grouped(TN, self._rows_g.data_ptr(), self._rows_h.data_ptr(), None, g, 1, _i32([0, M]), None, None,
-                                           _i64([self._G("classification_head.mlp.0.weight")]), g, _i64([self._G("classification_head.mlp.0.bias")]),
-                                           Cn, H, 0, Cn, H, H, 1.0, 0, 0, None, 0, st), "head wgrad")
-        self._gemm(st, NN, self._rows_g.data_ptr(), P("classification_head.mlp.0.weight"), None, self._rows_gh.data_ptr(), M, H, Cn, Cn, H, H)
+        self._head_backward(node_indices, targets, st)
+        g = self.grad.data_ptr()
         gcur, ga = self.gA, self.ga
-        gcur.zero_()
-        self._chk(lib.gmp_row_fill(gcur.data_ptr(), idx, self._rows_gh.data_ptr(), M, N, H, 0, st), "scatter g_h")
         sp, one = self.seg_ptr.data_ptr(), _i32([0, 1])
         pending_eps = None
         for l in reversed(range(GNN_NUM_LAYERS)):
@@ -396,6 +384,31 @@ class NodeClassificationEngine:
                                                self.final_grad.data_ptr(), self.normsq.data_ptr(), self.metrics.data_ptr(), self.flags.data_ptr(),
                                                self.mt_ws.data_ptr(), self.mt_ws.numel(), int(apply_update), st), "adamw")
 
+    def _head_backward(self, node_indices: Tensor, targets: Tensor, st: int) -> None:
+        """Loss and head of the step after forward(): d loss / d h[GNN_NUM_LAYERS] into gA (the backbone backward starts from it)."""
+        lib, N, P, Cn = self.lib, self.N, self._P, self.classes
+        M = int(node_indices.numel())
+        if self._train_idx is None or self._train_idx.numel() != M:
+            f = lambda *s: torch.empty(*s, device=self.device)
+            self._rows_logits, self._rows_g, self._rows_h = f(M, Cn), f(M, Cn), f(M, H)
+            self._rows_gh = f(M, H)
+        self._train_idx, self.num_targets = node_indices, M
+        self.g_scale.fill_(1.0 / M)
+        idx, tgt, g = node_indices.data_ptr(), targets.data_ptr(), self.grad.data_ptr()
+        hL = self.h[GNN_NUM_LAYERS]
+        self._chk(lib.gmp_row_gather(self.logits.data_ptr(), idx, None, self._rows_logits.data_ptr(), M, N, Cn, st), "logit rows")
+        self._chk(lib.gmp_cross_entropy_sum_fwd(self._rows_logits.data_ptr(), tgt, M, Cn, self.loss_sum.data_ptr(), self.loss_ws.data_ptr(), self.loss_ws.numel(), st), "ce")
+        self._chk(lib.gmp_cross_entropy_sum_bwd(self._rows_logits.data_ptr(), tgt, M, Cn, self.g_scale.data_ptr(), self._rows_g.data_ptr(), st), "ce bwd")
+        # head: dW = g^T h[idx], db = colsum(g), g_h[idx] = g W  (only the M training rows carry a gradient)
+        self._chk(lib.gmp_row_gather(hL.data_ptr(), idx, None, self._rows_h.data_ptr(), M, N, H, st), "h rows")
+        self._chk(lib.gmp_gemm_f32_grouped(TN, self._rows_g.data_ptr(), self._rows_h.data_ptr(), None, g, 1, _i32([0, M]), None, None,
+                                           _i64([self._G("classification_head.mlp.0.weight")]), g, _i64([self._G("classification_head.mlp.0.bias")]),
+                                           Cn, H, 0, Cn, H, H, 1.0, 0, 0, None, 0, st), "head wgrad")
+        self._gemm(st, NN, self._rows_g.data_ptr(), P("classification_head.mlp.0.weight"), None, self._rows_gh.data_ptr(), M, H, Cn, Cn, H, H)
+        gcur = self.gA
+        gcur.zero_()
+        self._chk(lib.gmp_row_fill(gcur.data_ptr(), idx, self._rows_gh.data_ptr(), M, N, H, 0, st), "scatter g_h")
+
     def _eps_grad(self, stream: int, l: int) -> None:
         self._chk(self.lib.gmp_group_sum_1d(self.rowdot[l].data_ptr(), 1, _i32([0, self.N]), _i64([self._G(f"gnn_backbone.layers.{l}.gin_conv.eps")]),
                                             self.grad.data_ptr(), stream), "eps grad")
@@ -417,3 +430,121 @@ class NodeClassificationEngine:
             return self.final_grad[o:o + H * self.dpad].view(H, self.dpad)[:, :self.d_in]
         p = dict(self.model.named_parameters())[name]
         return self.final_grad[o:o + p.numel()].view_as(p)
+
+
+LP_SCORER_SITE = 40                 # dropout site of the scorer's hidden layer (the backbone's: 1 and 10-14)
+MINING_SITE_BASE = 100              # added to the backbone's sites in the mining pass: masks independent of the training forward's
+_LP_HEAD = "classification_head.predictor.mlp."
+
+
+class LinkPredictionEngine(NodeClassificationEngine):
+    """One link-prediction fine-tune step (Cora_LP / CiteSeer_LP, src/finetune/finetune.py:181-211) as an explicit kernel sequence.
+
+    The reference's training batch is: a no-grad train-mode embedding pass over the message-passing graph (train_pos) to mine hard
+    negatives, a second full forward, the MLPLinkPredictor over [pos | neg], BCE (mean), backward, AdamW.  Here:
+      mining_forward()   the first pass -- the node engine's encoder + backbone launches with dropout sites MINING_SITE_BASE higher,
+                         BatchNorm in batch statistics updating the running ones, counted in num_batches_tracked (twice per step, as on
+                         the module path); LinkPredictionHardNegativeMiner runs on its output unchanged
+      step(pos, neg)     the pairs into a preallocated buffer, the training forward, the fused scorer (gmp_lp_score_fwd: the [K, 768]
+                         features never leave LDS), gmp_sigmoid_bce_sum_fwd_bwd, gmp_lp_score_bwd (head gradients straight into the flat
+                         buffer, per-pair g_hs / g_hd), csr_build + two segment_sums onto the nodes, then the node engine's backbone
+                         backward (side-stream fork, gates) and AdamW with the reference's groups.  Nothing is read back.
+    The module stays the owner of the parameters (views into the flat buffer), so evaluation and checkpoints go through it."""
+
+    def __init__(self, model: FinetuneGNN, x: Tensor, message_passing_edges: Tensor, device, seed: int = 0, max_pairs: int = 512) -> None:
+        super().__init__(model, x, message_passing_edges, device, seed)
+        self.use_graph = False              # the pair list changes every step: no captured replay
+        self.kmax, self.num_targets = 0, 0
+        self._pairs: Optional[Tensor] = None
+        self._grow(max_pairs)
+
+    def _grow(self, kmax: int) -> None:
+        dev, lib, N = self.device, self.lib, self.N
+        ws = lambda n: torch.empty(max(int(n), 16), dtype=torch.uint8, device=dev)
+        i32 = lambda n: torch.empty(n, dtype=torch.int32, device=dev)
+        self.kmax = kmax
+        self.pair_buf = torch.empty(2 * kmax, dtype=torch.int64, device=dev)      # step k's pairs: the first 2 K words, viewed [2, K]
+        self.labels = torch.empty(kmax, device=dev)
+        self.act = torch.empty(kmax, H, device=dev)
+        self.logit, self.probs, self.g_logit = (torch.empty(kmax, device=dev) for _ in range(3))
+        self.g_hs, self.g_hd = torch.empty(kmax, H, device=dev), torch.empty(kmax, H, device=dev)
+        self.score_fwd_ws = ws(lib.gmp_lp_score_fwd_workspace_bytes(kmax))
+        self.score_bwd_ws = ws(lib.gmp_lp_score_bwd_workspace_bytes(kmax))
+        self.pair_loss_ws = ws(lib.gmp_loss_workspace_bytes(kmax))
+        self.pair_csr = [i32(N + 1), i32(kmax), i32(kmax), i32(N + 1), i32(kmax), i32(kmax), i32(1)]
+        self.pair_csr_ws = ws(lib.gmp_csr_build_workspace_bytes(N, kmax))
+
+    # ------------------------------------------------------------------ forward: encoder + backbone only (the scorer runs in the step)
+    def forward(self) -> Tensor:
+        self._backbone_forward()
+        if self.model.training:
+            self._bn_calls += 1
+        return self.h[GNN_NUM_LAYERS]
+
+    def mining_forward(self) -> Tensor:
+        """The reference's no-grad embedding pass (finetune.py:181-190) in the model's mode.  Returns the engine's own [N, 256] buffer: the
+        next forward overwrites it."""
+        self._site_base = MINING_SITE_BASE
+        try:
+            return self.forward()
+        finally:
+            self._site_base = 0
+
+    # ------------------------------------------------------------------ one optimisation step
+    def step(self, pos_edges: Tensor, neg_edges: Tensor, apply_update: bool = True) -> None:
+        """loss = BCE(scorer(h, [pos | neg]), [1 | 0]) (mean); backward; AdamW.  pos / neg int64 [2, *] on the device."""
+        P_, Q = int(pos_edges.size(1)), int(neg_edges.size(1))
+        K = P_ + Q
+        if K == 0:
+            raise ValueError("LinkPredictionEngine.step: no pairs")
+        if K > self.kmax:
+            self._grow(max(K, 2 * self.kmax))
+        pairs = self.pair_buf[:2 * K].view(2, K)
+        pairs[:, :P_].copy_(pos_edges)
+        if Q:
+            pairs[:, P_:].copy_(neg_edges)
+        self.labels[:P_].fill_(1.0)
+        if Q:
+            self.labels[P_:K].fill_(0.0)
+        self._pairs, self.num_targets = pairs, K
+        self._enqueue(pairs, self.labels, apply_update, forked=self.fork_wgrads)
+        self.step_count += 1
+
+    def _head_backward(self, pairs: Tensor, labels: Tensor, st: int) -> None:
+        """Scorer, loss and their backward after forward(): d loss / d h[GNN_NUM_LAYERS] into gA."""
+        lib, N, P, g = self.lib, self.N, self._P, self.grad.data_ptr()
+        K = int(pairs.size(1))
+        src, dst = pairs.data_ptr(), pairs.data_ptr() + 8 * K
+        p = self.dropout_p if self.model.training else 0.0
+        seed = (self.seed * 1000003 + self.step_count) & (2 ** 64 - 1)
+        hL = self.h[GNN_NUM_LAYERS].data_ptr()
+        self.g_scale.fill_(1.0 / K)
+        self._chk(lib.gmp_lp_score_fwd(hL, src, dst, N, K, H, H, P(_LP_HEAD + "0.weight"), P(_LP_HEAD + "0.bias"), P(_LP_HEAD + "3.weight"),
+                                       P(_LP_HEAD + "3.bias"), self.act.data_ptr(), self.logit.data_ptr(), p, seed, LP_SCORER_SITE,
+                                       self.score_fwd_ws.data_ptr(), self.score_fwd_ws.numel(), st), "lp score")
+        self._chk(lib.gmp_sigmoid_bce_sum_fwd_bwd(self.logit.data_ptr(), labels.data_ptr(), K, self.g_scale.data_ptr(), self.loss_sum.data_ptr(),
+                                                  self.probs.data_ptr(), self.g_logit.data_ptr(), self.pair_loss_ws.data_ptr(), self.pair_loss_ws.numel(), st),
+                  "lp bce")
+        self._chk(lib.gmp_lp_score_bwd(hL, src, dst, N, K, H, H, P(_LP_HEAD + "0.weight"), P(_LP_HEAD + "3.weight"), self.act.data_ptr(),
+                                       self.g_logit.data_ptr(), p, seed, LP_SCORER_SITE, g + 4 * self._G(_LP_HEAD + "0.weight"),
+                                       g + 4 * self._G(_LP_HEAD + "0.bias"), g + 4 * self._G(_LP_HEAD + "3.weight"), g + 4 * self._G(_LP_HEAD + "3.bias"),
+                                       0, self.g_hs.data_ptr(), self.g_hd.data_ptr(), self.score_bwd_ws.data_ptr(), self.score_bwd_ws.numel(), st),
+                  "lp score bwd")
+        # the pair scatter: g_h[i] = sum of g_hs over pairs from i + sum of g_hd over pairs to i (fixed order, operators.lp_edge_features)
+        rowptr, col, perm, rowptr_t, col_t, perm_t, status = (t.data_ptr() for t in self.pair_csr)
+        self._chk(lib.gmp_csr_build(pairs.data_ptr(), N, K, rowptr, col, perm, rowptr_t, col_t, perm_t, status, self.pair_csr_ws.data_ptr(),
+                                    self.pair_csr_ws.numel(), st), "pair csr")
+        self._chk(lib.gmp_segment_sum(self.g_hs.data_ptr(), rowptr_t, perm_t, self.gA.data_ptr(), N, H, 0, 0, st), "g_h from sources")
+        self._chk(lib.gmp_segment_sum(self.g_hd.data_ptr(), rowptr, perm, self.gA.data_ptr(), N, H, 0, 1, st), "g_h from destinations")
+
+    # ------------------------------------------------------------------ read-backs
+    def loss(self) -> float:
+        """Mean BCE of the last step (synchronises; checks the gate and slab time-out words like the node engine)."""
+        return super().loss()
+
+    def probabilities(self) -> Tensor:
+        """sigmoid(logit) of the last step's pairs, [pos | neg] order."""
+        return self.probs[:self.num_targets]
+
+    def labels_of_step(self) -> Tensor:
+        return self.labels[:self.num_targets]

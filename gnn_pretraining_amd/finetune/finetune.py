@@ -2,7 +2,7 @@
 miner, process_batch per task type, one AdamW step per batch over FinetuneGNN.param_groups, best-validation checkpoint,
 test metrics from the best checkpoint.  Data come from the loaders of gnn_pretraining_amd/data (processed datasets in
 data/processed; synthetic stand-ins are generated when none were exported).  wandb is replaced by a JSONL logger with the
-same metric keys.  Build-only flags: --epochs, --device, --data-root, --data-scale, --log, --sparse-features."""
+same metric keys.  Build-only flags: --epochs, --device, --data-root, --data-scale, --log, --sparse-features, --lp-engine."""
 from __future__ import annotations
 
 import argparse
@@ -89,10 +89,13 @@ class FinetuneConfig:
     epochs: int = None
     patience: int = None
     sparse_features: bool = False       # Planetoid domains: node features as CSR (graph.SparseFeatures) -- the sparse encoder kernels
+    lp_engine: bool = False             # link-prediction domains: the explicit-kernel step (finetune/engine.py LinkPredictionEngine)
 
     def __post_init__(self) -> None:
         if self.sparse_features and TASK_TYPES[self.domain_name] == "graph_classification":
             raise ValueError(f"sparse_features applies to the Planetoid domains (Cora / CiteSeer), not to {self.domain_name}")
+        if self.lp_engine and TASK_TYPES[self.domain_name] != "link_prediction":
+            raise ValueError(f"lp_engine applies to the link-prediction domains (Cora_LP / CiteSeer_LP), not to {self.domain_name}")
         self.exp_name = f"{self.domain_name}_{self.finetune_strategy}_{self.pretrained_scheme}"
         self.task_type = TASK_TYPES[self.domain_name]
         self.batch_size = BATCH_SIZES[self.domain_name]
@@ -225,6 +228,33 @@ def run_training_node_engine(engine, train_loader, device, epoch: int, global_st
             logger.log(m, global_step[0])
 
 
+def run_training_lp_engine(engine, train_loader, device, epoch: int, global_step: List[int], cfg: FinetuneConfig, miner,
+                           logger: JsonlLogger) -> None:
+    """run_training for the link-prediction domains on the explicit-kernel step (finetune/engine.py LinkPredictionEngine): per batch the
+    mining pass, the hard-negative miner on its output, then engine.step -- training forward, fused scorer, BCE, backward, AdamW with the
+    reference's parameter groups -- with no autograd graph and nothing read back unless a log is being written."""
+    model = engine.model
+    model.train()
+    edges = _train_edges(train_loader, device)
+    for (_, pos_edges, _) in train_loader:
+        t0 = time.time()
+        global_step[0] += 1
+        pos = pos_edges.to(device).contiguous()
+        emb = engine.mining_forward()
+        neg = miner.mine_hard_negatives_for_edges(node_embeddings=emb, positive_edges=pos, num_negatives=pos.size(1), existing_edges=edges)
+        engine.step(pos, neg)
+        if logger.f:
+            p, labels = engine.probabilities().detach(), engine.labels_of_step()
+            loss = torch.tensor(engine.loss())
+            m = compute_batch_metrics(cfg.domain_name, labels.long(), (p > 0.5).long(), torch.stack([1 - p, p], dim=1), loss, "train")
+            for pg in model.param_groups:
+                m[f'train/lr/{pg["name"]}'] = pg["lr"]
+            m["train/gradients/model_grad_norm"] = float(engine.normsq.sqrt())
+            m["train/progress/epoch"], m["train/progress/step"] = epoch, global_step[0]
+            m["train/system/time_per_step"] = time.time() - t0
+            logger.log(m, global_step[0])
+
+
 def evaluate(model: FinetuneGNN, loader, device, cfg: FinetuneConfig, prefix: str, miner, train_edges) -> List[Dict[str, float]]:
     return [compute_loss_and_metrics(model, b, device, cfg.task_type, cfg.domain_name, prefix, miner, train_edges) for b in loader]
 
@@ -269,10 +299,18 @@ def finetune(cfg: FinetuneConfig, epochs: Optional[int] = None, device: Optional
         from .engine import NodeClassificationEngine
         data = train_loader.dataset.data
         node_engine = NodeClassificationEngine(model, data.x, data.edge_index, dev, seed=cfg.seed)
+    lp_engine = None
+    if cfg.lp_engine:
+        from .engine import LinkPredictionEngine
+        lp_engine = LinkPredictionEngine(model, train_loader.dataset.data.x, _train_edges(train_loader, dev), dev, seed=cfg.seed,
+                                         max_pairs=2 * cfg.batch_size)
     for epoch in range(1, (epochs or cfg.epochs) + 1):
         if node_engine is not None:
             run_training_node_engine(node_engine, train_loader, dev, epoch, global_step, cfg, logger)
             node_engine.flush_counters()
+        elif lp_engine is not None:
+            run_training_lp_engine(lp_engine, train_loader, dev, epoch, global_step, cfg, miner, logger)
+            lp_engine.flush_counters()
         else:
             run_training(model, optimizer, train_loader, dev, epoch, global_step, cfg, miner, logger)
         edges = _train_edges(train_loader, dev)
@@ -306,11 +344,13 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--data-scale", type=float, default=1.0)
     p.add_argument("--log", type=str, default=None)
     p.add_argument("--sparse-features", action="store_true", help="Cora / CiteSeer node features as CSR (sparse encoder kernels)")
+    p.add_argument("--lp-engine", action="store_true", help="Cora_LP / CiteSeer_LP: the explicit-kernel fine-tune step (LinkPredictionEngine)")
     return p
 
 
 def config_from_args(a: argparse.Namespace) -> FinetuneConfig:
-    return FinetuneConfig(a.domain_name, a.finetune_strategy, a.pretrained_scheme, a.seed, sparse_features=a.sparse_features)
+    return FinetuneConfig(a.domain_name, a.finetune_strategy, a.pretrained_scheme, a.seed, sparse_features=a.sparse_features,
+                          lp_engine=getattr(a, "lp_engine", False))
 
 
 def main() -> None:

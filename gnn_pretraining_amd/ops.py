@@ -723,3 +723,46 @@ def lp_pair_head(y1: Tensor, w: Tensor, bias: Tensor, pos: Tensor, sign: Tensor,
     L.check(l.gmp_lp_pair_weighted_colsum(_ptr(g_y2), _ptr(y1), _ptr(pos), _ptr(g_w), _ptr(g_b), K, F, float(p), sd, stream_id, _ptr(ws), ws.numel(), st),
             "gmp_lp_pair_weighted_colsum")
     return y2, loss, g_y2, g_y1, g_w, g_b
+
+
+def lp_score_fwd(h: Tensor, src: Tensor, dst: Tensor, w0: Tensor, b0: Tensor, w3: Tensor, b3: Tensor, p: float = 0.0, seed: int = 0,
+                 site: int = 0) -> Tuple[Tensor, Tensor]:
+    """The fused link-prediction scorer up to the logit (gnnmp.h gmp_lp_score_fwd): h [N, 256], src / dst int64 [K], w0 [256, 768],
+    b0 [256], w3 [1, 256] or [256], b3 [1].  Returns (act [K, 256] = the pre-dropout ReLU output, logit [K])."""
+    _need(h, torch.float32, "h", 2)
+    _need(src, torch.int64, "src", 1); _need(dst, torch.int64, "dst", 1)
+    for t, n in ((w0, "w0"), (b0, "b0"), (w3, "w3"), (b3, "b3")):
+        _need(t, torch.float32, n)
+    K, dev, l = src.numel(), h.device, L.lib()
+    if dst.numel() != K:
+        raise L.GnnmpError("lp_score_fwd: src and dst differ in length")
+    act, logit = torch.empty(K, w0.size(0), device=dev), torch.empty(K, device=dev)
+    ws = _ws(l.gmp_lp_score_fwd_workspace_bytes(K), dev)
+    L.check(l.gmp_lp_score_fwd(_ptr(h), _ptr(src), _ptr(dst), h.size(0), K, h.size(1), w0.size(0), _ptr(w0), _ptr(b0), _ptr(w3), _ptr(b3),
+                               _ptr(act), _ptr(logit), float(p), seed & (2 ** 64 - 1), site, _ptr(ws), ws.numel(), _stream(h)), "gmp_lp_score_fwd")
+    return act, logit
+
+
+def lp_score_bwd(h: Tensor, src: Tensor, dst: Tensor, w0: Tensor, w3: Tensor, act: Tensor, g_logit: Tensor, p: float = 0.0, seed: int = 0,
+                 site: int = 0) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """Backward of lp_score_fwd from d loss / d logit (gnnmp.h gmp_lp_score_bwd).  Returns (g_w0 [256, 768], g_b0 [256], g_w3 [256],
+    g_b3 [1], g_hs [K, 256], g_hd [K, 256]); lp_score_node_grad reduces the last two onto nodes."""
+    _need(act, torch.float32, "act", 2); _need(g_logit, torch.float32, "g_logit", 1)
+    K, dev, l = src.numel(), h.device, L.lib()
+    Hd, F = w0.size(0), h.size(1)
+    g_w0, g_b0, g_w3, g_b3 = torch.empty_like(w0), torch.empty(Hd, device=dev), torch.empty(Hd, device=dev), torch.empty(1, device=dev)
+    g_hs, g_hd = torch.empty(K, F, device=dev), torch.empty(K, F, device=dev)
+    ws = _ws(l.gmp_lp_score_bwd_workspace_bytes(K), dev)
+    L.check(l.gmp_lp_score_bwd(_ptr(h), _ptr(src), _ptr(dst), h.size(0), K, F, Hd, _ptr(w0), _ptr(w3), _ptr(act), _ptr(g_logit), float(p),
+                               seed & (2 ** 64 - 1), site, _ptr(g_w0), _ptr(g_b0), _ptr(g_w3), _ptr(g_b3), 0, _ptr(g_hs), _ptr(g_hd),
+                               _ptr(ws), ws.numel(), _stream(h)), "gmp_lp_score_bwd")
+    return g_w0, g_b0, g_w3, g_b3, g_hs, g_hd
+
+
+def lp_score_node_grad(g_hs: Tensor, g_hd: Tensor, pairs: Tensor, num_nodes: int) -> Tensor:
+    """g_h[i] = sum of g_hs over the pairs whose source is i + sum of g_hd over those whose destination is i (fixed order: csr_build +
+    two segment_sums, the backward of operators.lp_edge_features).  pairs int64 [2, K] contiguous; a pair with an endpoint outside
+    [0, num_nodes) is dropped by csr_build and gives no node gradient."""
+    csr = csr_build(pairs, num_nodes)
+    gh = segment_sum(g_hs, csr.rowptr_t, csr.perm_t)
+    return segment_sum(g_hd, csr.rowptr, csr.perm, out=gh, accumulate=True)

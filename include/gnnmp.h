@@ -252,6 +252,27 @@ int gmp_lp_edge_features_bwd(const float* g_feat, const float* h, const int64_t*
                              gmp_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
+ * The fused link-prediction scorer (MLPLinkPredictor, heads.py:57-67) over a pair list src[k], dst[k] (int64, k < K):
+ *   feat = [hs+hd | hs*hd | |hs-hd|] (never written to memory), z = feat w0^T + b0 (w0 [hidden, 3 feat] row-major),
+ *   act = relu(z) [K, hidden] (the pre-dropout activation, kept for the backward), logit = <dropout(act), w3> + b3.
+ * Dropout is the mask gmp_dropout_fwd(act, p, seed, site) draws over the contiguous [K, hidden] activation; p == 0: no mask.
+ * The sigmoid / BCE / d loss / d logit that follow are gmp_sigmoid_bce_sum_fwd_bwd.
+ * bwd from g_logit [K]: g_w0 [hidden, 3 feat], g_b0 [hidden], g_w3 [hidden], g_b3 [1] written (accumulate = 0) or added to,
+ * per-pair g_hs / g_hd [K, feat] (torch.abs' subgradient: 0 at hs == hd; reduce them onto nodes with gmp_segment_sum).
+ * feat == hidden == 256 (GMP_ERR_UNSUPPORTED otherwise).  Every sum over pairs is in a fixed order (no atomics): bitwise
+ * reproducible.  An index outside [0, num_nodes) reads as a zero row.  h, w0, b0, w3, act 16-byte aligned.
+ * ------------------------------------------------------------------------- */
+size_t gmp_lp_score_fwd_workspace_bytes(int64_t num_pairs);
+size_t gmp_lp_score_bwd_workspace_bytes(int64_t num_pairs);
+int gmp_lp_score_fwd(const float* h, const int64_t* src, const int64_t* dst, int64_t num_nodes, int64_t num_pairs, int feat_dim,
+                     int hidden, const float* w0, const float* b0, const float* w3, const float* b3, float* act, float* logit,
+                     float p, uint64_t seed, uint32_t site, void* workspace, size_t workspace_bytes, gmp_stream_t stream);
+int gmp_lp_score_bwd(const float* h, const int64_t* src, const int64_t* dst, int64_t num_nodes, int64_t num_pairs, int feat_dim,
+                     int hidden, const float* w0, const float* w3, const float* act, const float* g_logit, float p, uint64_t seed,
+                     uint32_t site, float* g_w0, float* g_b0, float* g_w3, float* g_b3, int accumulate, float* g_hs, float* g_hd,
+                     void* workspace, size_t workspace_bytes, gmp_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
  * NT-Xent / InfoNCE (tasks.py:192-213, 265-287).
  *   z = [normalize(z1); normalize(z2)]  (eps 1e-12), sim = z z^T / T, diag = -inf,
  *   loss_sum = sum_i CE(sim[i,:], pos_i),  pos_i = (i + n) mod 2n.
