@@ -8,7 +8,7 @@ re-implemented as autograd Functions over libgnnmp (SURVEY.md section 8b "operat
     batch_norm_act(...)                    BatchNorm1d (+residual,+ReLU,+dropout) gnn.py:19-22,42-43
     take_rows(h, idx)                      h[idx]                                tasks.py:80
     lp_edge_features(h, edges)             [hs+hd | hs*hd | |hs-hd|]             heads.py:58-66
-    nt_xent(z1, z2, T)                     SimCLR loss                           tasks.py:192-213
+    nt_xent(z1, z2, T, impl="auto")        SimCLR loss (matrix or streaming form) tasks.py:192-213
     relu_dropout(x, p, training)           the ReLU->Dropout pair of MLPHead     heads.py:43-45
 
 Everything raises GnnmpError on CPU tensors -- there is no eager fallback.
@@ -313,9 +313,35 @@ class _NtXent(torch.autograd.Function):
         return g1, g2, None
 
 
-def nt_xent(z1: Tensor, z2: Tensor, temperature: float) -> Tuple[Tensor, int]:
-    """(sum of the 2n cross-entropies, 2n)."""
-    return _NtXent.apply(z1, z2, float(temperature)), 2 * z1.size(0)
+class _NtXentStream(torch.autograd.Function):
+    """The streaming form: what is kept from forward to backward is z1, z2 and the O(n d) workspace."""
+    @staticmethod
+    def forward(ctx, z1, z2, temperature: float):
+        z1, z2 = z1.contiguous(), z2.contiguous()
+        loss, ws = ops.nt_xent_stream_fwd(z1, z2, temperature)
+        ctx.t = temperature
+        ctx.save_for_backward(z1, z2, ws)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        z1, z2, ws = ctx.saved_tensors
+        g1, g2 = ops.nt_xent_stream_bwd(z1, z2, ctx.t, g.reshape(1).contiguous().float(), ws)
+        return g1, g2, None
+
+
+NT_XENT_MATRIX_MAX_N = 8192         # what gmp_nt_xent_fwd accepts
+
+
+def nt_xent(z1: Tensor, z2: Tensor, temperature: float, impl: str = "auto") -> Tuple[Tensor, int]:
+    """(sum of the 2n cross-entropies, 2n).  impl: "matrix" = the [2n, 2n] similarity matrix in the workspace (n <= 8192),
+    "stream" = similarity tiles in registers only (O(n d) memory, any n), "auto" = matrix where it is accepted, stream above."""
+    if impl not in ("auto", "matrix", "stream"):
+        raise ValueError(f"nt_xent: impl must be 'auto', 'matrix' or 'stream', not {impl!r}")
+    if impl == "auto":
+        impl = "matrix" if z1.size(0) <= NT_XENT_MATRIX_MAX_N else "stream"
+    fn = _NtXent if impl == "matrix" else _NtXentStream
+    return fn.apply(z1, z2, float(temperature)), 2 * z1.size(0)
 
 
 # --------------------------------------------------------------------------- #

@@ -410,6 +410,30 @@ def nt_xent_bwd(z1: Tensor, z2: Tensor, temperature: float, g_scale: Tensor, ws:
     return g1, g2
 
 
+def nt_xent_stream_fwd(z1: Tensor, z2: Tensor, temperature: float) -> Tuple[Tensor, Tensor]:
+    """The streaming form (no [2n, 2n] matrix, O(n d) workspace, any n).  Returns (loss_sum [1], workspace) -- the workspace
+    feeds nt_xent_stream_bwd."""
+    _need(z1, torch.float32, "z1", 2); _need(z2, torch.float32, "z2", 2)
+    if z1.shape != z2.shape:
+        raise L.GnnmpError("nt_xent_stream: z1/z2 shapes differ")
+    n, d = z1.shape
+    l = L.lib()
+    ws = _ws(l.gmp_nt_xent_stream_workspace_bytes(n, d), z1.device)
+    loss = torch.empty(1, dtype=torch.float32, device=z1.device)
+    L.check(l.gmp_nt_xent_stream_fwd(_ptr(z1), _ptr(z2), n, d, float(temperature), _ptr(loss), _ptr(ws), ws.numel(),
+                                     _stream(z1)), "gmp_nt_xent_stream_fwd")
+    return loss, ws
+
+
+def nt_xent_stream_bwd(z1: Tensor, z2: Tensor, temperature: float, g_scale: Tensor, ws: Tensor) -> Tuple[Tensor, Tensor]:
+    n, d = z1.shape
+    _need(g_scale, torch.float32, "g_scale")
+    g1, g2 = torch.empty_like(z1), torch.empty_like(z2)
+    L.check(L.lib().gmp_nt_xent_stream_bwd(_ptr(z1), _ptr(z2), n, d, float(temperature), _ptr(g_scale), _ptr(g1), _ptr(g2),
+                                           _ptr(ws), ws.numel(), _stream(z1)), "gmp_nt_xent_stream_bwd")
+    return g1, g2
+
+
 def hard_negative_topk(emb: Tensor, existing_edges: Tensor, k: int, return_scores: bool = False,
                        return_matrix: bool = False):
     """Top-k cosine-similarity non-edges (finetune.py:45-75).  Returns edges [2,k] int64 (score-descending), and

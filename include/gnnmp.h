@@ -288,6 +288,18 @@ int gmp_nt_xent_bwd(const float* z1, const float* z2, int64_t n, int dim, float 
                     const float* g_scale, float* g_z1, float* g_z2,
                     void* workspace /* the one fwd filled */, size_t workspace_bytes, gmp_stream_t stream);
 
+/* The same loss and gradient without the [2n, 2n] similarity matrix (flash-attention style: similarity tiles live in registers /
+ * LDS only, the workspace is O(n * dim)).  Arguments and conventions are those of gmp_nt_xent_fwd / _bwd; the backward reads the
+ * normalised rows and the per-row log-sum-exp the forward left in the workspace.  dim: a multiple of 4 in [4, 256];
+ * 1 <= n <= (INT32_MAX - 128) / 2 (int32 row indexing of the 2n rows).  Bad arguments and a short workspace are refused before
+ * any launch.  Fixed-order reductions: bitwise reproducible.  Results agree with the matrix form to fp32 rounding, not bit for bit. */
+size_t gmp_nt_xent_stream_workspace_bytes(int64_t n, int dim);
+int gmp_nt_xent_stream_fwd(const float* z1, const float* z2, int64_t n, int dim, float temperature,
+                           float* loss_sum, void* workspace, size_t workspace_bytes, gmp_stream_t stream);
+int gmp_nt_xent_stream_bwd(const float* z1, const float* z2, int64_t n, int dim, float temperature,
+                           const float* g_scale, float* g_z1, float* g_z2,
+                           void* workspace /* the one fwd filled */, size_t workspace_bytes, gmp_stream_t stream);
+
 /* ------------------------------------------------------------------------- *
  * MLPHead pieces (heads.py:42-45): Linear -> ReLU -> Dropout.  The ReLU rides in the
  * GEMM epilogue; these two handle the dropout and the fused backward
