@@ -150,10 +150,11 @@ __global__ __launch_bounds__(BLOCK) void lp_feat_fwd_kernel(const float4* __rest
     const int lane = threadIdx.x % GMP_WAVE;
     for (int64_t k = wave_id(); k < K; k += wave_count()) {
         const int64_t a = edges[k], b = edges[K + k];
-        const bool ok = a >= 0 && a < N && b >= 0 && b < N;
+        const bool oka = a >= 0 && a < N, okb = b >= 0 && b < N;   // each endpoint on its own: an index out of range reads as a zero row
         for (int c = lane; c < F4; c += GMP_WAVE) {
             float4 s = make_float4(0.f, 0.f, 0.f, 0.f), d = s;
-            if (ok) { s = h[a * F4 + c]; d = h[b * F4 + c]; }
+            if (oka) s = h[a * F4 + c];
+            if (okb) d = h[b * F4 + c];
             float4* o = feat + k * 3 * F4;
             o[c] = make_float4(s.x + d.x, s.y + d.y, s.z + d.z, s.w + d.w);
             o[F4 + c] = make_float4(s.x * d.x, s.y * d.y, s.z * d.z, s.w * d.w);
@@ -170,10 +171,11 @@ __global__ __launch_bounds__(BLOCK) void lp_feat_bwd_kernel(const float4* __rest
     const int lane = threadIdx.x % GMP_WAVE;
     for (int64_t k = wave_id(); k < K; k += wave_count()) {
         const int64_t a = edges[k], b = edges[K + k];
-        const bool ok = a >= 0 && a < N && b >= 0 && b < N;
+        const bool oka = a >= 0 && a < N, okb = b >= 0 && b < N;   // each endpoint on its own: an index out of range reads as a zero row
         for (int c = lane; c < F4; c += GMP_WAVE) {
             float4 s = make_float4(0.f, 0.f, 0.f, 0.f), d = s;
-            if (ok) { s = h[a * F4 + c]; d = h[b * F4 + c]; }
+            if (oka) s = h[a * F4 + c];
+            if (okb) d = h[b * F4 + c];
             const float4* g = gf + k * 3 * F4;
             const float4 gs = g[c], gp = g[F4 + c], ga = g[2 * F4 + c];
             float4 t = make_float4(ga.x * sgn(s.x - d.x), ga.y * sgn(s.y - d.y), ga.z * sgn(s.z - d.z), ga.w * sgn(s.w - d.w));

@@ -121,6 +121,60 @@ def gin_aggregate_bwd(g_out: Tensor, rowptr_t: Tensor, col_t: Tensor, eps: Tenso
     return g_x, g_eps
 
 
+def gin_aggregate_fwd_rows(x: Tensor, rowptr: Tensor, col: Tensor, eps: Tensor, out: Tensor, row0: int, row1: int) -> Tensor:
+    """Rows [row0, row1) of gin_aggregate_fwd written into `out` [N, F] (the other rows are left as they are); col keeps the whole
+    batch's numbering."""
+    F = _feat_ok(x, "x")
+    _need(rowptr, torch.int32, "rowptr", 1); _need(col, torch.int32, "col", 1); _need(eps, torch.float32, "eps")
+    _need(out, torch.float32, "out", 2)
+    if rowptr.numel() != x.size(0) + 1 or out.shape != x.shape:
+        raise L.GnnmpError("gin_aggregate_fwd_rows: rowptr / out do not match x")
+    if not 0 <= row0 <= row1 <= x.size(0):
+        raise L.GnnmpError(f"gin_aggregate_fwd_rows: rows [{row0}, {row1}) of {x.size(0)}")
+    L.check(L.lib().gmp_gin_aggregate_fwd_rows(_ptr(x), _ptr(rowptr), _ptr(col), _ptr(eps), _ptr(out), row0, row1, F, _stream(x)),
+            "gmp_gin_aggregate_fwd_rows")
+    return out
+
+
+def gin_aggregate_bwd_ex(g_out: Tensor, rowptr_t: Tensor, col_t: Tensor, eps: Tensor, x: Optional[Tensor] = None,
+                         addend: Optional[Tensor] = None) -> Tuple[Tensor, Optional[Tensor]]:
+    """The stacked step's backward: g_x = (1 + eps) g + sum over the transposed CSR of g (+ addend), and, when x is given,
+    rowdot [N] = <g[r], x[r]> per row (gmp_group_sum_1d reduces it to the eps gradient of a task)."""
+    F = _feat_ok(g_out, "g_out")
+    _need(rowptr_t, torch.int32, "rowptr_t", 1); _need(col_t, torch.int32, "col_t", 1); _need(eps, torch.float32, "eps")
+    if rowptr_t.numel() != g_out.size(0) + 1:
+        raise L.GnnmpError("rowptr_t / g_out row mismatch")
+    for t, n in ((x, "x"), (addend, "addend")):
+        if t is not None:
+            _feat_ok(t, n)
+            if t.shape != g_out.shape:
+                raise L.GnnmpError(f"{n} / g_out shape mismatch")
+    g_x = torch.empty_like(g_out)
+    rowdot = torch.empty(g_out.size(0), dtype=torch.float32, device=g_out.device) if x is not None else None
+    L.check(L.lib().gmp_gin_aggregate_bwd_ex(_ptr(g_out), _ptr(rowptr_t), _ptr(col_t), _ptr(eps), _ptr(x), _ptr(addend), _ptr(g_x),
+                                             _ptr(rowdot), g_out.size(0), F, _stream(g_out)), "gmp_gin_aggregate_bwd_ex")
+    return g_x, rowdot
+
+
+def group_sum_1d(vals: Tensor, group_rows, out: Optional[Tensor] = None, out_off=None) -> Tensor:
+    """out[out_off[g]] = sum of vals[group_rows[g] : group_rows[g + 1]] (out_off default g; group_rows / out_off: host lists).  Slots
+    of `out` that no group names are left as they are."""
+    _need(vals, torch.float32, "vals", 1)
+    rows = [int(r) for r in group_rows]
+    G = len(rows) - 1
+    if G < 1 or rows[0] < 0 or rows[-1] > vals.numel() or any(a > b for a, b in zip(rows[:-1], rows[1:])):
+        raise L.GnnmpError(f"group_sum_1d: group rows {rows} for {vals.numel()} values")
+    off = list(range(G)) if out_off is None else [int(o) for o in out_off]
+    if out is None:
+        out = torch.empty(max(off) + 1 if off else 0, dtype=torch.float32, device=vals.device)
+    _need(out, torch.float32, "out", 1)
+    if len(off) != G or min(off) < 0 or max(off) >= out.numel():
+        raise L.GnnmpError(f"group_sum_1d: output slots {off} for {out.numel()} entries")
+    L.check(L.lib().gmp_group_sum_1d(_ptr(vals), G, (C.c_int32 * (G + 1))(*rows), None if out_off is None else (C.c_int64 * G)(*off),
+                                     _ptr(out), _stream(vals)), "gmp_group_sum_1d")
+    return out
+
+
 def segment_sum(src: Tensor, ptr: Tensor, idx: Optional[Tensor], mean: bool = False,
                 out: Optional[Tensor] = None, accumulate: bool = False) -> Tensor:
     _need(src, torch.float32, "src", 2)
@@ -160,13 +214,22 @@ def segment_max_fwd(x: Tensor, ptr: Tensor) -> Tensor:
     return out
 
 
-def segment_max_bwd(g_out: Tensor, x: Tensor, out: Tensor, ptr: Tensor) -> Tensor:
+def segment_max_bwd(g_out: Tensor, x: Tensor, out: Tensor, ptr: Tensor, g_x: Optional[Tensor] = None,
+                    accumulate: bool = False) -> Tensor:
+    """g_x (nullable: a fresh buffer): rows of a segment are overwritten, or added to when `accumulate`; rows outside every segment
+    are left as they are."""
     F = _feat_ok(x, "x")
     _need(g_out, torch.float32, "g_out", 2); _need(out, torch.float32, "out", 2); _need(ptr, torch.int32, "ptr", 1)
     if g_out.shape != out.shape or out.size(0) != ptr.numel() - 1 or out.size(1) != F:
         raise L.GnnmpError("segment_max_bwd: shape mismatch")
-    g_x = torch.empty_like(x)
-    L.check(L.lib().gmp_segment_max_bwd(_ptr(g_out), _ptr(x), _ptr(out), _ptr(ptr), _ptr(g_x), ptr.numel() - 1, F, 0,
+    if g_x is None:
+        g_x = torch.empty_like(x)
+        accumulate = False
+    else:
+        _need(g_x, torch.float32, "g_x", 2)
+        if g_x.shape != x.shape:
+            raise L.GnnmpError("segment_max_bwd: g_x shape")
+    L.check(L.lib().gmp_segment_max_bwd(_ptr(g_out), _ptr(x), _ptr(out), _ptr(ptr), _ptr(g_x), ptr.numel() - 1, F, int(accumulate),
                                         _stream(x)), "gmp_segment_max_bwd")
     return g_x
 
@@ -542,6 +605,28 @@ def bce_sum_bwd(p: Tensor, labels: Tensor, g_scale: Tensor) -> Tensor:
     gp = torch.empty_like(p)
     L.check(L.lib().gmp_bce_sum_bwd(_ptr(p), _ptr(labels), _ptr(g_scale), _ptr(gp), p.numel(), _stream(p)), "gmp_bce_sum_bwd")
     return gp
+
+
+def _sigmoid_bce(fn: str, x: Tensor, y: Tensor, g_scale: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+    _need(x, torch.float32, "x", 1); _need(y, torch.float32, "labels", 1); _need(g_scale, torch.float32, "g_scale")
+    if x.shape != y.shape:
+        raise L.GnnmpError(f"{fn}: shapes {tuple(x.shape)} vs {tuple(y.shape)}")
+    loss = torch.empty(1, dtype=torch.float32, device=x.device)
+    p, gx = torch.empty_like(x), torch.empty_like(x)
+    ws = _loss_ws(x.numel(), x.device)
+    L.check(getattr(L.lib(), fn)(_ptr(x), _ptr(y), x.numel(), _ptr(g_scale), _ptr(loss), _ptr(p), _ptr(gx), _ptr(ws), ws.numel(),
+                                 _stream(x)), fn)
+    return loss, p, gx
+
+
+def sigmoid_bce_sum_fwd_bwd(x: Tensor, labels: Tensor, g_scale: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+    """(loss_sum [1], sigmoid(x), d (g_scale * loss_sum) / d x) in one pass (gmp_sigmoid_bce_sum_fwd_bwd)."""
+    return _sigmoid_bce("gmp_sigmoid_bce_sum_fwd_bwd", x, labels, g_scale)
+
+
+def sigmoid_bce_signed_sum_fwd_bwd(x: Tensor, signed_weight: Tensor, g_scale: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+    """The same pass with signed_weight[i] = +w (positive pair) / -w (negative pair): loss term and gradient scaled by w."""
+    return _sigmoid_bce("gmp_sigmoid_bce_signed_sum_fwd_bwd", x, signed_weight, g_scale)
 
 
 def cross_entropy_sum_fwd(logits: Tensor, target: Tensor) -> Tensor:

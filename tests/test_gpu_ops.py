@@ -428,6 +428,15 @@ def test_fused_sigmoid_bce_equals_the_four_separate_kernels():
     assert bool(torch.isfinite(gx).all()) and bool(torch.isfinite(loss).all())
     want = torch.nn.functional.binary_cross_entropy(torch.sigmoid(x.cpu()), y.cpu(), reduction="sum")
     close(loss, want.reshape(1), what="sigmoid+bce loss")
+    # ... and against float64, so that the five kernels cannot share one wrong formula: p against sigmoid, the gradient against autograd
+    # through torch's BCE at the kernel's own p (x reaches +-120, where float32 p is exactly 0 or 1 and the clamps decide) pushed through
+    # torch's sigmoid backward; bars and their measurements: tests/test_gpu_kernel_edges_losses.py
+    close(p, torch.sigmoid(x.cpu().double()), rtol=4e-7, what="p against float64 sigmoid")
+    p64 = p.cpu().double().requires_grad_()
+    loss64 = torch.nn.functional.binary_cross_entropy(p64, y.cpu().double(), reduction="sum")
+    gp64, = torch.autograd.grad(loss64 * gs.cpu().double(), p64)
+    close(loss, loss64.detach().reshape(1), rtol=6e-7, what="loss against float64 BCE at the kernel's p")
+    close(gx, torch.ops.aten.sigmoid_backward(gp64, p64.detach()), rtol=2e-6, what="g_x against float64 autograd at the kernel's p")
 
 
 def test_bn_split_entry_points_equal_the_inline_ones():
