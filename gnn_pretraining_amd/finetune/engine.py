@@ -548,3 +548,154 @@ class LinkPredictionEngine(NodeClassificationEngine):
 
     def labels_of_step(self) -> Tensor:
         return self.labels[:self.num_targets]
+
+
+GC_HEAD_SITE = 41                   # dropout site of the graph-classification head's hidden layer (the backbone's: 1 and 10-14, the scorer's: 40)
+_GC_HEAD = "classification_head.mlp."
+
+
+class GraphClassificationEngine(NodeClassificationEngine):
+    """One graph-classification fine-tune step (ENZYMES / PTC_MR, src/finetune/finetune.py:136-158 + 283-331) as an explicit kernel sequence.
+
+    The reference's training batch is 32 graphs (about 1,000 rows for ENZYMES, 450 for PTC_MR): forward, global_mean_pool, the
+    256 -> 128 -> C head, cross-entropy (C > 2) or BCE-with-logits on logits[:, 1] (C == 2), backward, AdamW.  The batch -- and with it the
+    number of rows, edges and graphs -- changes every step, so unlike the node engine this one works on CAPACITIES:
+      buffers            activations, gradients, the CSR and the workspaces are sized for max_nodes / max_edges / max_graphs and regrown by
+                         doubling when a batch exceeds them (_alloc); every row-major buffer has leading dimension 256 / 512, so a step
+                         uses its first N rows and rows a larger previous batch left behind are never read
+      step(batch)        the batch's x into the padded [N, dpad] input (the padding columns stay zero), gmp_csr_build on the device into the
+                         preallocated CSR, seg_ptr = [0, N], the node engine's backbone forward, the fused head (gmp_gc_head_fwd: pooling,
+                         both layers, the loss and d loss / d logits in one kernel + the loss sum), gmp_gc_head_bwd (head gradients straight
+                         into the flat buffer, every row of d loss / d h written), then the node engine's backbone backward (side-stream
+                         fork, gates) and AdamW.  Nothing is read back; no captured replay (shapes change every step).
+    Which tensors train comes from the model (requires_grad as FinetuneGNN set it: the encoder is frozen for ENZYMES, the backbone for
+    linear_probe), the learning rates are those of FinetuneGNN.param_groups.  A frozen tensor is never touched by the optimizer -- no update,
+    no weight decay -- and stays bitwise what it was.  The backward still runs through frozen layers (no launch is skipped);
+    gradient(name) of a frozen tensor returns zeros.
+    The module stays the owner of the parameters (views into the flat buffer), so evaluation and checkpoints go through it.
+    Measured (MI355X, scripts/bench_gc_finetune.py, profiles/README.md GC fine-tune): 0.80 ms per 32-graph ENZYMES-shaped step against 3.28 on the
+    module path, 0.88 against 2.98 at the PTC_MR shape; about 120 launches per step, host-bound."""
+
+    def __init__(self, model: FinetuneGNN, device, seed: int = 0, max_nodes: int = 2048, max_edges: int = 8192, max_graphs: int = 64) -> None:
+        d_in = int(model.input_encoder.linear.weight.size(1))
+        # the node engine's set-up (flat buffer, streams, gates, optimizer state) on a one-row placeholder graph; _alloc sizes the rest
+        super().__init__(model, torch.zeros(1, d_in), torch.zeros(2, 1, dtype=torch.long), device, seed)
+        self.use_graph = False              # N, E and B change every step: no captured replay
+        del self.logits                     # (the node engine's [N, classes] buffer: here logits() is the last step's [B, C])
+        self.classes = int(model.classification_head.mlp[3].weight.size(0))
+        self.B, self.num_targets = 0, 0
+        self._ptr32: Optional[Tensor] = None
+        self._y: Optional[Tensor] = None
+        self._alloc(max(int(max_nodes), 1), max(int(max_edges), 1), max(int(max_graphs), 1))
+
+    def _alloc(self, cap_n: int, cap_e: int, cap_b: int) -> None:
+        dev, lib, Lr = self.device, self.lib, GNN_NUM_LAYERS
+        f = lambda *s: torch.empty(*s, device=dev)
+        i32 = lambda n: torch.empty(n, dtype=torch.int32, device=dev)
+        ws = lambda n: torch.empty(max(int(n), 16), dtype=torch.uint8, device=dev)
+        self.cap_n, self.cap_e, self.cap_b = cap_n, cap_e, cap_b
+        self.x = torch.zeros(cap_n, self.dpad, device=dev)
+        self.z0, self.h = f(cap_n, H), [f(cap_n, H) for _ in range(Lr + 1)]
+        self.a, self.z1 = [f(cap_n, H) for _ in range(Lr)], [f(cap_n, 2 * H) for _ in range(Lr)]
+        self.r1, self.z2 = [f(cap_n, 2 * H) for _ in range(Lr)], [f(cap_n, H) for _ in range(Lr)]
+        self.gA, self.gB, self.ga, self.gW, self.gW2 = f(cap_n, H), f(cap_n, H), f(cap_n, H), f(cap_n, 2 * H), f(cap_n, 2 * H)
+        self.gu_l, self.gz1_l = [f(cap_n, H) for _ in range(Lr + 1)], [f(cap_n, 2 * H) for _ in range(Lr)]
+        self.rowdot = f(Lr, cap_n)
+        self.bn_ws = ws(lib.gmp_bn_workspace_bytes(cap_n, 2 * H, 1, cap_n))
+        self.csr = ops.CSR(i32(cap_n + 1), i32(cap_e), i32(cap_e), i32(cap_n + 1), i32(cap_e), i32(cap_e), cap_n, torch.zeros(1, dtype=torch.int32, device=dev))
+        self.csr_ws = ws(lib.gmp_csr_build_workspace_bytes(cap_n, cap_e))
+        self.pooled, self.act = f(cap_b, H), f(cap_b, self.model.classification_head.mlp[0].weight.size(0))
+        self.logits_b, self.g_logits = f(cap_b, self.classes), f(cap_b, self.classes)
+        self.head_ws = ws(lib.gmp_gc_head_fwd_workspace_bytes(cap_b))
+
+    # ------------------------------------------------------------------ this step's batch into the engine's buffers
+    def _load(self, batch) -> None:
+        if batch.x.device.type != self.device.type:
+            batch = batch.to(self.device)
+        N, E, B = batch.num_nodes, batch.num_edges, batch.num_graphs
+        if N < 1 or B < 1:
+            raise ValueError("GraphClassificationEngine: an empty batch")
+        if batch.x.size(1) != self.d_in:
+            raise ValueError(f"GraphClassificationEngine: the batch has {batch.x.size(1)} features, the encoder {self.d_in}")
+        if batch.y is None or batch.y.numel() != B:
+            raise ValueError("GraphClassificationEngine: the batch needs one label per graph")
+        if N > self.cap_n or E > self.cap_e or B > self.cap_b:
+            grown = lambda need, cap: max(need, 2 * cap) if need > cap else cap
+            self._alloc(grown(N, self.cap_n), grown(E, self.cap_e), grown(B, self.cap_b))
+        self.N, self.B, self.num_targets = N, B, B
+        self.seg_ptr[1:].fill_(N)                                # the one BatchNorm segment [0, N)
+        self.x[:N, :self.d_in].copy_(batch.x)
+        ei, c = batch.edge_index.contiguous(), self.csr
+        st = torch.cuda.current_stream(self.device).cuda_stream
+        self._chk(self.lib.gmp_csr_build(ei.data_ptr() if E else None, N, E, c.rowptr.data_ptr(), c.col.data_ptr(), c.perm.data_ptr(),
+                                         c.rowptr_t.data_ptr(), c.col_t.data_ptr(), c.perm_t.data_ptr(), c.status.data_ptr(),
+                                         self.csr_ws.data_ptr(), self.csr_ws.numel(), st), "batch csr")
+        # (a cast on the device: Batch.ptr32 would upload the host offsets again, one blocking copy per step)
+        self._ptr32, self._y = batch.ptr.to(torch.int32), batch.y.to(torch.int64).contiguous()
+
+    # ------------------------------------------------------------------ forward: encoder + backbone (the head runs in the step)
+    def forward(self, batch=None) -> Tensor:
+        """The backbone's output for `batch` (or for the batch already loaded) in the model's mode: the first N rows of the engine's own
+        buffer, which the next forward overwrites."""
+        if batch is not None:
+            self._load(batch)
+        self._backbone_forward()
+        if self.model.training:
+            self._bn_calls += 1
+        return self.h[GNN_NUM_LAYERS][:self.N]
+
+    def evaluate(self, batch) -> Tensor:
+        """logits [B, C] of `batch` in the model's mode (forward + the fused head; loss() then holds the batch's mean loss)."""
+        self.forward(batch)
+        self._head_forward(torch.cuda.current_stream(self.device).cuda_stream)
+        return self.logits()
+
+    # ------------------------------------------------------------------ one optimisation step
+    def step(self, batch, apply_update: bool = True) -> None:
+        """loss = classification_loss(model(batch), batch.y) (mean over the batch's graphs); backward; AdamW.  `batch` is the loader's Batch
+        (x, edge_index, ptr32, y), moved to the device if it is not there yet."""
+        self._load(batch)
+        self._enqueue(None, None, apply_update, forked=self.fork_wgrads)
+        self.step_count += 1
+
+    def _head_args(self):
+        p = self.dropout_p if self.model.training else 0.0
+        return p, (self.seed * 1000003 + self.step_count) & (2 ** 64 - 1)
+
+    def _head_forward(self, st: int) -> None:
+        lib, P = self.lib, self._P
+        p, seed = self._head_args()
+        self.g_scale.fill_(1.0 / self.B)
+        self._chk(lib.gmp_gc_head_fwd(self.h[GNN_NUM_LAYERS].data_ptr(), H, self._ptr32.data_ptr(), self.N, self.B, H, self.act.size(1), self.classes,
+                                      P(_GC_HEAD + "0.weight"), P(_GC_HEAD + "0.bias"), P(_GC_HEAD + "3.weight"), P(_GC_HEAD + "3.bias"),
+                                      self._y.data_ptr(), self.g_scale.data_ptr(), self.pooled.data_ptr(), self.act.data_ptr(),
+                                      self.logits_b.data_ptr(), self.loss_sum.data_ptr(), self.g_logits.data_ptr(), p, seed, GC_HEAD_SITE,
+                                      self.head_ws.data_ptr(), self.head_ws.numel(), st), "gc head")
+
+    def _head_backward(self, _unused_a, _unused_b, st: int) -> None:
+        """Head, loss and their backward after forward(): d loss / d h[GNN_NUM_LAYERS] into every row of gA."""
+        lib, P, g = self.lib, self._P, self.grad.data_ptr()
+        p, seed = self._head_args()
+        self._head_forward(st)
+        self._chk(lib.gmp_gc_head_bwd(self._ptr32.data_ptr(), self.N, self.B, H, self.act.size(1), self.classes, P(_GC_HEAD + "0.weight"),
+                                      P(_GC_HEAD + "3.weight"), self.pooled.data_ptr(), self.act.data_ptr(), self.g_logits.data_ptr(), p, seed,
+                                      GC_HEAD_SITE, g + 4 * self._G(_GC_HEAD + "0.weight"), g + 4 * self._G(_GC_HEAD + "0.bias"),
+                                      g + 4 * self._G(_GC_HEAD + "3.weight"), g + 4 * self._G(_GC_HEAD + "3.bias"), self.gA.data_ptr(), H, st),
+                  "gc head bwd")
+
+    # ------------------------------------------------------------------ read-backs
+    def loss(self) -> float:
+        """Mean loss of the last step (synchronises; checks the gate and slab time-out words like the node engine, and the CSR build's
+        count of edge endpoints outside the batch)."""
+        v = super().loss()
+        if int(self.csr.status.item()) != 0:
+            raise L.GnnmpError(f"fine-tune engine: {int(self.csr.status.item())} edge endpoints outside the batch's nodes")
+        return v
+
+    def logits(self) -> Tensor:
+        """The last step's logits [B, C] (a view of the engine's buffer: the next step overwrites it)."""
+        return self.logits_b[:self.B]
+
+    def gradient(self, name: str) -> Tensor:
+        g = super().gradient(name)
+        return g if dict(self.model.named_parameters())[name].requires_grad else torch.zeros_like(g)

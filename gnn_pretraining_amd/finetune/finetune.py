@@ -2,7 +2,7 @@
 miner, process_batch per task type, one AdamW step per batch over FinetuneGNN.param_groups, best-validation checkpoint,
 test metrics from the best checkpoint.  Data come from the loaders of gnn_pretraining_amd/data (processed datasets in
 data/processed; synthetic stand-ins are generated when none were exported).  wandb is replaced by a JSONL logger with the
-same metric keys.  Build-only flags: --epochs, --device, --data-root, --data-scale, --log, --sparse-features, --lp-engine."""
+same metric keys.  Build-only flags: --epochs, --device, --data-root, --data-scale, --log, --sparse-features, --lp-engine, --gc-engine."""
 from __future__ import annotations
 
 import argparse
@@ -90,12 +90,15 @@ class FinetuneConfig:
     patience: int = None
     sparse_features: bool = False       # Planetoid domains: node features as CSR (graph.SparseFeatures) -- the sparse encoder kernels
     lp_engine: bool = False             # link-prediction domains: the explicit-kernel step (finetune/engine.py LinkPredictionEngine)
+    gc_engine: bool = False             # graph-classification domains: the explicit-kernel step (finetune/engine.py GraphClassificationEngine)
 
     def __post_init__(self) -> None:
         if self.sparse_features and TASK_TYPES[self.domain_name] == "graph_classification":
             raise ValueError(f"sparse_features applies to the Planetoid domains (Cora / CiteSeer), not to {self.domain_name}")
         if self.lp_engine and TASK_TYPES[self.domain_name] != "link_prediction":
             raise ValueError(f"lp_engine applies to the link-prediction domains (Cora_LP / CiteSeer_LP), not to {self.domain_name}")
+        if self.gc_engine and TASK_TYPES[self.domain_name] != "graph_classification":
+            raise ValueError(f"gc_engine applies to the graph-classification domains (ENZYMES / PTC_MR), not to {self.domain_name}")
         self.exp_name = f"{self.domain_name}_{self.finetune_strategy}_{self.pretrained_scheme}"
         self.task_type = TASK_TYPES[self.domain_name]
         self.batch_size = BATCH_SIZES[self.domain_name]
@@ -255,6 +258,29 @@ def run_training_lp_engine(engine, train_loader, device, epoch: int, global_step
             logger.log(m, global_step[0])
 
 
+def run_training_gc_engine(engine, train_loader, device, epoch: int, global_step: List[int], cfg: FinetuneConfig, logger: JsonlLogger) -> None:
+    """run_training for the graph-classification domains on the explicit-kernel step (finetune/engine.py GraphClassificationEngine): one
+    engine.step per batch -- the batch's CSR, forward, fused pooling + head + loss, backward, AdamW with the reference's parameter groups --
+    with no autograd graph and nothing read back unless a log is being written."""
+    model = engine.model
+    model.train()
+    for batch in train_loader:
+        t0 = time.time()
+        global_step[0] += 1
+        b = batch.to(device)
+        engine.step(b)
+        if logger.f:
+            lg = engine.logits().detach()
+            loss = torch.tensor(engine.loss())
+            m = compute_batch_metrics(cfg.domain_name, b.y, lg.argmax(dim=1), torch.softmax(lg, dim=1), loss, "train")
+            for pg in model.param_groups:
+                m[f'train/lr/{pg["name"]}'] = pg["lr"]
+            m["train/gradients/model_grad_norm"] = float(engine.normsq.sqrt())
+            m["train/progress/epoch"], m["train/progress/step"] = epoch, global_step[0]
+            m["train/system/time_per_step"] = time.time() - t0
+            logger.log(m, global_step[0])
+
+
 def evaluate(model: FinetuneGNN, loader, device, cfg: FinetuneConfig, prefix: str, miner, train_edges) -> List[Dict[str, float]]:
     return [compute_loss_and_metrics(model, b, device, cfg.task_type, cfg.domain_name, prefix, miner, train_edges) for b in loader]
 
@@ -304,6 +330,10 @@ def finetune(cfg: FinetuneConfig, epochs: Optional[int] = None, device: Optional
         from .engine import LinkPredictionEngine
         lp_engine = LinkPredictionEngine(model, train_loader.dataset.data.x, _train_edges(train_loader, dev), dev, seed=cfg.seed,
                                          max_pairs=2 * cfg.batch_size)
+    gc_engine = None
+    if cfg.gc_engine:
+        from .engine import GraphClassificationEngine
+        gc_engine = GraphClassificationEngine(model, dev, seed=cfg.seed, max_graphs=max(cfg.batch_size, 1))
     for epoch in range(1, (epochs or cfg.epochs) + 1):
         if node_engine is not None:
             run_training_node_engine(node_engine, train_loader, dev, epoch, global_step, cfg, logger)
@@ -311,6 +341,9 @@ def finetune(cfg: FinetuneConfig, epochs: Optional[int] = None, device: Optional
         elif lp_engine is not None:
             run_training_lp_engine(lp_engine, train_loader, dev, epoch, global_step, cfg, miner, logger)
             lp_engine.flush_counters()
+        elif gc_engine is not None:
+            run_training_gc_engine(gc_engine, train_loader, dev, epoch, global_step, cfg, logger)
+            gc_engine.flush_counters()
         else:
             run_training(model, optimizer, train_loader, dev, epoch, global_step, cfg, miner, logger)
         edges = _train_edges(train_loader, dev)
@@ -345,12 +378,13 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--log", type=str, default=None)
     p.add_argument("--sparse-features", action="store_true", help="Cora / CiteSeer node features as CSR (sparse encoder kernels)")
     p.add_argument("--lp-engine", action="store_true", help="Cora_LP / CiteSeer_LP: the explicit-kernel fine-tune step (LinkPredictionEngine)")
+    p.add_argument("--gc-engine", action="store_true", help="ENZYMES / PTC_MR: the explicit-kernel fine-tune step (GraphClassificationEngine)")
     return p
 
 
 def config_from_args(a: argparse.Namespace) -> FinetuneConfig:
     return FinetuneConfig(a.domain_name, a.finetune_strategy, a.pretrained_scheme, a.seed, sparse_features=a.sparse_features,
-                          lp_engine=getattr(a, "lp_engine", False))
+                          lp_engine=getattr(a, "lp_engine", False), gc_engine=getattr(a, "gc_engine", False))
 
 
 def main() -> None:

@@ -875,3 +875,47 @@ def lp_score_node_grad(g_hs: Tensor, g_hd: Tensor, pairs: Tensor, num_nodes: int
     csr = csr_build(pairs, num_nodes)
     gh = segment_sum(g_hs, csr.rowptr_t, csr.perm_t)
     return segment_sum(g_hd, csr.rowptr, csr.perm, out=gh, accumulate=True)
+
+
+def gc_head_fwd(h: Tensor, ptr: Tensor, w0: Tensor, b0: Tensor, w3: Tensor, b3: Tensor, target: Tensor, g_scale: Tensor, p: float = 0.0,
+                seed: int = 0, site: int = 0) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """The fused graph-classification head up to the loss (gnnmp.h gmp_gc_head_fwd): h [N, 256] (rows contiguous, any leading dimension),
+    ptr int32 [B + 1], w0 [128, 256], b0 [128], w3 [C, 128], b3 [C], target int64 [B], g_scale fp32 [1].  Returns (pooled [B, 256],
+    act [B, 128] = the pre-dropout ReLU output, logits [B, C], loss [1] = the sum over the batch, g_logits [B, C] scaled by g_scale)."""
+    _need_rows(h, "h")
+    _need(ptr, torch.int32, "ptr", 1); _need(target, torch.int64, "target", 1); _need(g_scale, torch.float32, "g_scale")
+    for t, n in ((w0, "w0"), (b0, "b0"), (w3, "w3"), (b3, "b3")):
+        _need(t, torch.float32, n)
+    B, dev, l = ptr.numel() - 1, h.device, L.lib()
+    if B < 1 or target.numel() != B:
+        raise L.GnnmpError(f"gc_head_fwd: ptr has {ptr.numel()} entries for {target.numel()} targets")
+    Cn, Hd = w3.size(0), w0.size(0)
+    if w3.dim() != 2 or w3.size(1) != Hd or b0.numel() != Hd or b3.numel() != Cn or w0.size(1) != h.size(1):
+        raise L.GnnmpError("gc_head_fwd: weight shapes")
+    pooled, act, logits = torch.empty(B, h.size(1), device=dev), torch.empty(B, Hd, device=dev), torch.empty(B, Cn, device=dev)
+    loss, g_logits = torch.empty(1, device=dev), torch.empty(B, Cn, device=dev)
+    ws = _ws(l.gmp_gc_head_fwd_workspace_bytes(B), dev)
+    ldh = h.stride(0) if h.size(0) > 1 else h.size(1)
+    L.check(l.gmp_gc_head_fwd(_ptr(h), ldh, _ptr(ptr), h.size(0), B, h.size(1), Hd, Cn, _ptr(w0), _ptr(b0), _ptr(w3), _ptr(b3), _ptr(target),
+                              _ptr(g_scale), _ptr(pooled), _ptr(act), _ptr(logits), _ptr(loss), _ptr(g_logits), float(p), seed & (2 ** 64 - 1),
+                              site, _ptr(ws), ws.numel(), _stream(h)), "gmp_gc_head_fwd")
+    return pooled, act, logits, loss, g_logits
+
+
+def gc_head_bwd(ptr: Tensor, num_nodes: int, w0: Tensor, w3: Tensor, pooled: Tensor, act: Tensor, g_logits: Tensor, p: float = 0.0,
+                seed: int = 0, site: int = 0) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """Backward of gc_head_fwd from its g_logits (gnnmp.h gmp_gc_head_bwd).  Returns (g_w0 [128, 256], g_b0 [128], g_w3 [C, 128], g_b3 [C],
+    g_h [num_nodes, 256]: every row written, g_pooled[graph(i)] / max(count, 1))."""
+    _need(ptr, torch.int32, "ptr", 1)
+    for t, n in ((w0, "w0"), (w3, "w3"), (pooled, "pooled"), (act, "act"), (g_logits, "g_logits")):
+        _need(t, torch.float32, n, 2)
+    B, dev = ptr.numel() - 1, w0.device
+    Cn, Hd, F = w3.size(0), w0.size(0), w0.size(1)
+    if B < 1 or pooled.shape != (B, F) or act.shape != (B, Hd) or g_logits.shape != (B, Cn) or w3.size(1) != Hd:
+        raise L.GnnmpError("gc_head_bwd: shapes")
+    g_w0, g_b0, g_w3, g_b3 = torch.empty_like(w0), torch.empty(Hd, device=dev), torch.empty_like(w3), torch.empty(Cn, device=dev)
+    g_h = torch.empty(num_nodes, F, device=dev)
+    L.check(L.lib().gmp_gc_head_bwd(_ptr(ptr), num_nodes, B, F, Hd, Cn, _ptr(w0), _ptr(w3), _ptr(pooled), _ptr(act), _ptr(g_logits), float(p),
+                                    seed & (2 ** 64 - 1), site, _ptr(g_w0), _ptr(g_b0), _ptr(g_w3), _ptr(g_b3), _ptr(g_h), F, _stream(w0)),
+            "gmp_gc_head_bwd")
+    return g_w0, g_b0, g_w3, g_b3, g_h

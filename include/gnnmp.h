@@ -273,6 +273,32 @@ int gmp_lp_score_bwd(const float* h, const int64_t* src, const int64_t* dst, int
                      void* workspace, size_t workspace_bytes, gmp_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
+ * The fused graph-classification head of fine-tuning (finetune_model.py:68-80, finetune.py:110-114) over one batch of
+ * num_graphs graphs; graph b owns the rows ptr[b] .. ptr[b+1] of h (ptr: device int32 [num_graphs + 1]):
+ *   pooled[b] = mean of the graph's rows, divisor max(count, 1) (gmp_segment_sum(mean = 1); an empty graph pools to zero),
+ *   act = relu(pooled w0^T + b0) [B, hidden] (the pre-dropout activation, kept for the backward; w0 [hidden, feat] row-major),
+ *   logits = dropout(act) w3^T + b3 [B, classes] (w3 [classes, hidden]),
+ *   loss (device float[1]) = cross-entropy sum over the batch (classes > 2; target int64 [B], a label outside [0, classes) adds
+ *   nothing) or the BCE-with-logits sum on logits[:, 1] (classes == 2: target 0 / 1, logits[:, 0] gets a zero gradient),
+ *   g_logits [B, classes] = d loss / d logits scaled by the device word g_scale (1 / B for the mean).
+ * Dropout is the mask gmp_dropout_fwd(act, p, seed, site) draws over the contiguous [B, hidden] activation; p == 0: no mask.
+ * bwd (the mask is regenerated) writes g_w0 [hidden, feat], g_b0 [hidden], g_w3 [classes, hidden], g_b3 [classes] (pointers into
+ * the caller's gradient buffer) and EVERY row of g_h [num_nodes, feat] (leading dimension ldg): g_pooled[graph(i)] / max(count, 1),
+ * zero for a row no graph owns -- no zero-fill, no scatter.
+ * feat == 256, hidden == 128, 2 <= classes <= 16 (GMP_ERR_UNSUPPORTED otherwise), num_graphs >= 1.  fp32; every sum in a fixed
+ * order (no atomics): bitwise reproducible.  Three launches in all (fwd two, bwd one), nothing read back.  ptr entries are
+ * clamped into [0, num_nodes].  h, w0, w3, pooled, act, g_h 16-byte aligned, ldh / ldg multiples of 4.
+ * ------------------------------------------------------------------------- */
+size_t gmp_gc_head_fwd_workspace_bytes(int64_t num_graphs);
+int gmp_gc_head_fwd(const float* h, int64_t ldh, const int32_t* ptr, int64_t num_nodes, int64_t num_graphs, int feat_dim, int hidden,
+                    int classes, const float* w0, const float* b0, const float* w3, const float* b3, const int64_t* target,
+                    const float* g_scale, float* pooled, float* act, float* logits, float* loss, float* g_logits, float p,
+                    uint64_t seed, uint32_t site, void* workspace, size_t workspace_bytes, gmp_stream_t stream);
+int gmp_gc_head_bwd(const int32_t* ptr, int64_t num_nodes, int64_t num_graphs, int feat_dim, int hidden, int classes, const float* w0,
+                    const float* w3, const float* pooled, const float* act, const float* g_logits, float p, uint64_t seed,
+                    uint32_t site, float* g_w0, float* g_b0, float* g_w3, float* g_b3, float* g_h, int64_t ldg, gmp_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
  * NT-Xent / InfoNCE (tasks.py:192-213, 265-287).
  *   z = [normalize(z1); normalize(z2)]  (eps 1e-12), sim = z z^T / T, diag = -inf,
  *   loss_sum = sum_i CE(sim[i,:], pos_i),  pos_i = (i + n) mod 2n.

@@ -1,0 +1,144 @@
+"""Graph-classification fine-tune step: the module path (finetune.py process_batch on autograd + torch.optim.AdamW) against the explicit-kernel
+GraphClassificationEngine (finetune/engine.py), on synthetic batches of the ENZYMES shape (32 graphs, 21 features, 33 nodes / 62 edges per
+graph) and of the PTC_MR shape (32 graphs, 18 features, 14 nodes / 15 edges, labels in {0, 1}), in one process.  Real ENZYMES / PTC_MR data
+are not available offline: the shapes are the public dataset statistics.
+
+    python scripts/bench_gc_finetune.py [--steps 200] [--warmup 30] [--repeats 3] [--head-reps 200] [--out profiles/gc_finetune.json]
+
+Both paths cycle through the same pre-built list of --batches (default 12) different device batches.  Per path and shape: wall ms per
+training step (synchronised at the end of the timed run) and the same span between device events, --repeats times; the head alone (the
+fused gmp_gc_head_fwd + _bwd against the module head's pool / Linear / ReLU / dropout / Linear / loss launches, forward + backward) between
+device events.  Kernels per step: run it under `rocprofv3 --kernel-trace --stats -- python scripts/bench_gc_finetune.py --steps 20
+--warmup 5 --repeats 1 --head-reps 0 --shapes ENZYMES --paths engine` and divide the calls by the 25 steps."""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+from gnn_pretraining_amd import operators as O, ops, synthetic as S  # noqa: E402
+from gnn_pretraining_amd.finetune import finetune as FT  # noqa: E402
+from gnn_pretraining_amd.finetune.engine import GC_HEAD_SITE, GraphClassificationEngine  # noqa: E402
+from gnn_pretraining_amd.graph import Batch  # noqa: E402
+from gnn_pretraining_amd.models import FinetuneGNN  # noqa: E402
+
+DEV = torch.device("cuda")
+SHAPES = {"ENZYMES": (21, 33.0, 62.0, 6), "PTC_MR": (18, 14.0, 15.0, 2)}
+
+
+def timed(fn, steps: int, warmup: int):
+    for i in range(warmup):
+        fn(i)
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0 = time.perf_counter()
+    e0.record()
+    for i in range(steps):
+        fn(warmup + i)
+    e1.record()
+    torch.cuda.synchronize()
+    return 1e3 * (time.perf_counter() - t0) / steps, e0.elapsed_time(e1) / steps
+
+
+def bench_shape(domain: str, a) -> dict:
+    dim, mn, me, C = SHAPES[domain]
+    gen = torch.Generator().manual_seed(0)
+    torch.manual_seed(0)
+    if domain == "ENZYMES":
+        host = [S.domain_batch(gen, dim, 32) for _ in range(a.batches)]
+    else:
+        host = [Batch.from_data_list([S.random_graph(gen, dim, mn, me, num_classes=C) for _ in range(32)]) for _ in range(a.batches)]
+    batches = [b.to(DEV) for b in host]
+
+    model = FinetuneGNN(DEV, domain, "full_finetune")
+    opt = torch.optim.AdamW(model.param_groups)
+    model.train()
+
+    def module_step(i):
+        loss, *_ = FT.process_batch(model, batches[i % len(batches)], DEV, "graph_classification", domain, None, None)
+        opt.zero_grad()
+        loss.backward()
+        opt.step()
+
+    emodel = FinetuneGNN(DEV, domain, "full_finetune")
+    emodel.train()
+    eng = GraphClassificationEngine(emodel, DEV, seed=0)
+
+    def engine_step(i):
+        eng.step(batches[i % len(batches)].to(DEV))            # (.to as in run_training_gc_engine: a fresh Batch object per step, like the module path's)
+
+    res = {"rows_per_batch": round(sum(b.num_nodes for b in batches) / len(batches), 1),
+           "edges_per_batch": round(sum(b.num_edges for b in batches) / len(batches), 1), "module_ms_per_step": [], "module_event_ms_per_step": [],
+           "engine_ms_per_step": [], "engine_event_ms_per_step": []}
+    for r in range(a.repeats):                                  # module, engine, module, engine, ...: the order of the legs does not decide the result
+        for path, fn in (("module", module_step), ("engine", engine_step)):
+            if path in a.paths:
+                w, g = timed(fn, a.steps, a.warmup if r == 0 else 5)
+                res[path + "_ms_per_step"].append(round(w, 4)); res[path + "_event_ms_per_step"].append(round(g, 4))
+    if "engine" in a.paths:
+        res["engine_loss_finite"] = bool(torch.isfinite(torch.tensor(eng.loss())).item())
+    if "engine" in a.paths and "module" in a.paths:
+        res["speedup_median"] = round(sorted(res["module_ms_per_step"])[a.repeats // 2] / sorted(res["engine_ms_per_step"])[a.repeats // 2], 2)
+
+    if a.head_reps > 0:                                         # the head alone on one batch's backbone output
+        b = batches[0]
+        h = torch.randn(b.num_nodes, 256, device=DEV)
+        p = dict(emodel.named_parameters())
+        hd = "classification_head.mlp."
+        w0, b0, w3, b3 = (p[hd + k].detach() for k in ("0.weight", "0.bias", "3.weight", "3.bias"))
+        g_scale = torch.full((1,), 1.0 / b.num_graphs, device=DEV)
+
+        def fused(i):
+            pooled, act, logits, loss, g_logits = ops.gc_head_fwd(h, b.ptr32, w0, b0, w3, b3, b.y, g_scale, 0.2, i, GC_HEAD_SITE)
+            ops.gc_head_bwd(b.ptr32, b.num_nodes, w0, w3, pooled, act, g_logits, 0.2, i, GC_HEAD_SITE)
+
+        head = model.classification_head
+        hm = h.clone().requires_grad_(True)
+
+        def module_head(i):
+            loss = FT.classification_loss(head(O.global_mean_pool(hm, b.batch, ptr32=b.ptr32)), b.y, C)
+            loss.backward()
+            hm.grad = None
+            for q in head.parameters():
+                q.grad = None
+
+        fw, fg = timed(fused, a.head_reps, 10)
+        mw, mg = timed(module_head, a.head_reps, 10)
+        res["head_fused_event_ms"], res["head_fused_wall_ms"] = round(fg, 4), round(fw, 4)
+        res["head_module_event_ms"], res["head_module_wall_ms"] = round(mg, 4), round(mw, 4)
+    return res
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=30)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--batches", type=int, default=12)
+    ap.add_argument("--head-reps", type=int, default=200)
+    ap.add_argument("--shapes", default="ENZYMES,PTC_MR")
+    ap.add_argument("--paths", default="module,engine", help="which legs to time (a kernel trace of one path alone: --paths engine)")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if a.batches < 8:
+        ap.error("--batches: at least 8 different batches are cycled")
+    res = {"workload": "32 graphs per step, full_finetune, dropout 0.2, synthetic batches (public ENZYMES / PTC_MR size statistics)",
+           "steps": a.steps, "warmup": a.warmup, "repeats": a.repeats, "batches": a.batches}
+    for domain in a.shapes.split(","):
+        res[domain] = bench_shape(domain, a)
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+
+
+if __name__ == "__main__":
+    main()
