@@ -99,6 +99,9 @@ _SIGS: Dict[str, tuple] = {
     "gmp_bn_param_grads": (C.c_int, [p, i32, i32, p, p, p, p, p, i32, p]),
     "gmp_bn_running_update_batch": (C.c_int, [i32, p, i32, p, p, p, p, p, p, p, p]),
     "gmp_bn_running_update": (C.c_int, [p, p, i32, i32, p, p, p, p, p, p]),
+    "gmp_bn_fold": (C.c_int, [i32, p, p, p, p, p, f32, p, p]),
+    "gmp_linear_affine_workspace_bytes": (sz, [i64, i64, i64]),
+    "gmp_linear_affine_fwd": (C.c_int, [p, p, p, p, p, p, p, i64, i64, i64, i64, i64, i64, i64, i32, p, sz, p]),
     "gmp_bn_bwd": (C.c_int, [p, p, p, p, p, i32, i64, i64, i32, p, p, p, p, p, p, p, p, p, p, p, p, i32,
                              C.POINTER(BnConfig), p, sz, p]),
     "gmp_lp_edge_features_fwd": (C.c_int, [p, p, p, i64, i64, i32, p]),

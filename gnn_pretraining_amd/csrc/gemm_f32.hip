@@ -148,6 +148,12 @@ struct GemmArgs {
     int* sig_flag;
     int sig_value;
     int vecC;             // C (+ every group's coff) 16-byte aligned and ldc % 4 == 0: the pipelined kernel stores float4 row pieces
+    // affine epilogue (gmp_linear_affine_fwd, the EPI instances of the NT kernels only): C = act(((alpha A B^T + bias) + resid) * scale + shift),
+    // in that order; scale / shift [N] (both or neither), resid [M, N] with leading dimension ldr (nullable)
+    const float* scale;
+    const float* shift;
+    const float* resid;
+    int64_t ldr;
 };
 
 thread_local int* t_sig_flag = nullptr;
@@ -160,7 +166,8 @@ inline void take_signal(GemmArgs& g) {
 
 #include "gemm_pipe.h"      // namespace g2, nested in this anonymous namespace (its kernels take GemmArgs: internal linkage throughout)
 
-template <int BM, int BN, bool A_KMAJOR, bool B_KMAJOR, int BK, bool FAST>
+// EPI: the affine epilogue of GemmArgs (scale / shift / resid); false = the kernel as it always was
+template <int BM, int BN, bool A_KMAJOR, bool B_KMAJOR, int BK, bool FAST, bool EPI = false>
 __global__ __launch_bounds__(THREADS) void gemm_kernel(const GemmArgs g) {
     using LA = TileLoader<BM, A_KMAJOR, BK>;
     using LB = TileLoader<BN, B_KMAJOR, BK>;
@@ -284,6 +291,7 @@ __global__ __launch_bounds__(THREADS) void gemm_kernel(const GemmArgs g) {
             const int64_t col = n0 + wn * (BN / 2) + j * 32 + l31;
             if (col >= g.N) continue;
             const float bv = (!partial && biasp) ? biasp[col] : 0.f;
+            const float sc = (EPI && !partial && g.scale) ? g.scale[col] : 1.f, sh = (EPI && !partial && g.scale) ? g.shift[col] : 0.f;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int64_t row = m0 + wm * (BM / 2) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
@@ -292,6 +300,10 @@ __global__ __launch_bounds__(THREADS) void gemm_kernel(const GemmArgs g) {
                 if (!partial) {
                     v = g.alpha * v + bv;
                     if (g.accumulate) v += out[row * ldo + col];
+                    if (EPI) {
+                        if (g.resid) v += g.resid[row * g.ldr + col];
+                        if (g.scale) v = v * sc + sh;
+                    }
                     if (g.relu) v = fmaxf(v, 0.f);
                 }
                 out[row * ldo + col] = v;
@@ -308,6 +320,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(GemmArgs g) {
         const int64_t row = i / g.N, col = i % g.N;
         float v = g.alpha * s + (g.bias ? g.bias[col] : 0.f);
         if (g.accumulate) v += g.C[row * g.ldc + col];
+        if (g.resid) v += g.resid[row * g.ldr + col];
+        if (g.scale) v = v * g.scale[col] + g.shift[col];
         if (g.relu) v = fmaxf(v, 0.f);
         g.C[row * g.ldc + col] = v;
     }
@@ -418,7 +432,14 @@ void launch_mode(int mode, const GemmArgs& g, dim3 grid, hipStream_t st, bool fa
         else hipLaunchKernelGGL((gemm_kernel<BM, BN, AK, BKM, BK, false>), grid, dim3(THREADS), 0, st, g);          \
     } while (0)
     switch (mode) {
-        case GMP_GEMM_NT: GMP_GEMM_LAUNCH(false, false); break;
+        case GMP_GEMM_NT:
+            if (g.scale || g.resid) {          // the affine epilogue exists for the Linear forward only
+                if (fast) hipLaunchKernelGGL((gemm_kernel<BM, BN, false, false, BK, true, true>), grid, dim3(THREADS), 0, st, g);
+                else hipLaunchKernelGGL((gemm_kernel<BM, BN, false, false, BK, false, true>), grid, dim3(THREADS), 0, st, g);
+                break;
+            }
+            GMP_GEMM_LAUNCH(false, false);
+            break;
         case GMP_GEMM_NN: GMP_GEMM_LAUNCH(false, true); break;
         default:          GMP_GEMM_LAUNCH(true, true); break;
     }
@@ -429,10 +450,14 @@ void launch_mode(int mode, const GemmArgs& g, dim3 grid, hipStream_t st, bool fa
 // GMP_GEMM_IMPL=old keeps every problem on gemm_kernel (A/B aid); GMP_GEMM_PIPE_TILE=0..3 forces 128x128 / 64x128 / 128x64 / 64x64.
 constexpr int PIPE_TILES[4][2] = {{2, 2}, {1, 2}, {2, 1}, {1, 1}};
 
-template <int TM, int TN, bool A_KC, bool B_KC, int STAGES, int BUFS = STAGES>
+template <int TM, int TN, bool A_KC, bool B_KC, int STAGES, int BUFS = STAGES, bool EPI = false>
 int launch_pipe_cfg(const GemmArgs& g, int tiles_m, int tiles_n, int z, hipStream_t st) {
+    // the affine epilogue (NT only) is an instance of its own: every other launch runs the kernel it always ran
+    if constexpr (!EPI && A_KC && B_KC) {
+        if (g.scale || g.resid) return launch_pipe_cfg<TM, TN, A_KC, B_KC, STAGES, BUFS, true>(g, tiles_m, tiles_n, z, st);
+    }
     using C = g2::Cfg<TM, TN, A_KC, B_KC, STAGES, BUFS>;
-    auto kern = g2::gemm_pipe_kernel<TM, TN, A_KC, B_KC, STAGES, BUFS>;
+    auto kern = g2::gemm_pipe_kernel<TM, TN, A_KC, B_KC, STAGES, BUFS, EPI>;
     // a workgroup may ask for up to 160 KiB of LDS once the function says so -- per DEVICE (the attribute belongs to the device's copy of
     // the function): one bit per device ordinal, set after the call succeeded there; racing threads at worst both make the (idempotent) call
     static std::atomic<uint64_t> attr_set{0};
@@ -548,6 +573,18 @@ extern "C" size_t gmp_gemm_f32_workspace_bytes(int mode, int64_t M, int64_t N, i
 extern "C" int gmp_gemm_f32(int mode, const float* A, const float* B, const float* bias, float* C, int64_t M, int64_t N,
                             int64_t K, int64_t lda, int64_t ldb, int64_t ldc, float alpha, int accumulate, int relu,
                             void* workspace, size_t workspace_bytes, gmp_stream_t stream) {
+    return gmp::gemm_f32_epilogue(mode, A, B, bias, C, M, N, K, lda, ldb, ldc, alpha, accumulate, relu, nullptr, nullptr, nullptr, 0, workspace,
+                                  workspace_bytes, stream);
+}
+
+// gmp_gemm_f32 with the affine epilogue operands (all NULL: gmp_gemm_f32 itself).  One dispatch rule for both: tile, kernel family and
+// K-slices depend on the shape, the alignment and the workspace only, so with scale = 1, shift = 0 and no residual gmp_linear_affine_fwd
+// (infer.hip) accumulates in the order gmp_gemm_f32 does.  A pending gate signal belongs to gmp_gemm_f32 alone.
+int gmp::gemm_f32_epilogue(int mode, const float* A, const float* B, const float* bias, float* C, int64_t M, int64_t N, int64_t K, int64_t lda,
+                           int64_t ldb, int64_t ldc, float alpha, int accumulate, int relu, const float* scale, const float* shift,
+                           const float* resid, int64_t ldr, void* workspace, size_t workspace_bytes, gmp_stream_t stream) {
+    const bool epi = scale || shift || resid;
+    if (epi && (mode != GMP_GEMM_NT || !scale != !shift || (resid && ldr < N))) return gmp::fail(GMP_ERR_ARG, "gemm: affine epilogue operands");
     if (mode < 0 || mode > 2) return gmp::fail(GMP_ERR_ARG, "gemm: mode %d", mode);
     if (M < 0 || N < 0 || K < 0) return gmp::fail(GMP_ERR_ARG, "gemm: negative size");
     if (M == 0 || N == 0) return GMP_OK;
@@ -559,8 +596,13 @@ extern "C" int gmp_gemm_f32(int mode, const float* A, const float* B, const floa
     hipStream_t st = (hipStream_t)stream;
     GemmArgs g{A, B, bias, C, M, N, K, lda, ldb, ldc, alpha, accumulate, relu, 1, nullptr,
                (lda % 4 == 0) && aligned16(A), (ldb % 4 == 0) && aligned16(B)};
-    take_signal(g);
+    if (!epi) take_signal(g);
     g.vecC = (ldc % 4 == 0) && aligned16(C);
+    if (epi) {
+        g.scale = scale; g.shift = shift; g.resid = resid; g.ldr = ldr;
+        // float4 epilogue of the pipelined kernel: every per-column / per-element operand 16-byte addressable, whole quads of columns
+        if (N % 4 || !aligned16(bias) || !aligned16(scale) || !aligned16(shift) || !aligned16(resid) || ldr % 4) g.vecC = 0;
+    }
     const size_t want = gmp_gemm_f32_workspace_bytes(mode, M, N, K);
     if (want && workspace && workspace_bytes >= want) {
         g.splitk = (int)(want / ((size_t)M * N * sizeof(float)));

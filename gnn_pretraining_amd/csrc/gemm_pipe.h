@@ -183,7 +183,8 @@ __device__ __forceinline__ void sched_sub() {
 #endif
 }
 
-template <int TM, int TN, bool A_KC, bool B_KC, int STAGES, int BUFS = STAGES>
+// EPI: the affine epilogue of GemmArgs (scale / shift / resid, NT only); false = the kernel as it always was
+template <int TM, int TN, bool A_KC, bool B_KC, int STAGES, int BUFS = STAGES, bool EPI = false>
 __global__ __launch_bounds__(THREADS) void gemm_pipe_kernel(const GemmArgs g, int tiles_m, int tiles_n) {
     using C = Cfg<TM, TN, A_KC, B_KC, STAGES, BUFS>;
     constexpr bool EARLY = BUFS < STAGES;
@@ -387,6 +388,12 @@ __global__ __launch_bounds__(THREADS) void gemm_pipe_kernel(const GemmArgs g, in
                 if (col + 2 < g.N) bv.z = biasp[col + 2];
             }
         }
+        // affine epilogue: the launcher sends operands that are not 16-byte addressable (or N % 4 != 0) to the scalar form below
+        float4 sc = make_float4(1.f, 1.f, 1.f, 1.f), sh = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (EPI && !partial && g.scale && col + 3 < g.N) {
+            sc = *reinterpret_cast<const float4*>(g.scale + col);
+            sh = *reinterpret_cast<const float4*>(g.shift + col);
+        }
 #pragma unroll
         for (int q = 0; q < WR / RPI; ++q) {
             const int rl = q * RPI + rsub;
@@ -406,6 +413,13 @@ __global__ __launch_bounds__(THREADS) void gemm_pipe_kernel(const GemmArgs g, in
                         if (col + 1 < g.N) v.y += o[1];
                         if (col + 2 < g.N) v.z += o[2];
                     }
+                }
+                if (EPI) {
+                    if (g.resid) {
+                        const float4 c = *reinterpret_cast<const float4*>(g.resid + row * g.ldr + col);
+                        v.x += c.x; v.y += c.y; v.z += c.z; v.w += c.w;
+                    }
+                    if (g.scale) { v.x = v.x * sc.x + sh.x; v.y = v.y * sc.y + sh.y; v.z = v.z * sc.z + sh.z; v.w = v.w * sc.w + sh.w; }
                 }
                 if (g.relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
             }
@@ -430,12 +444,17 @@ __global__ __launch_bounds__(THREADS) void gemm_pipe_kernel(const GemmArgs g, in
             const int64_t col = col0 + j * 32 + l31;
             if (col >= g.N) continue;
             const float bv = (!partial && biasp) ? biasp[col] : 0.f;
+            const float sc = (EPI && g.scale) ? g.scale[col] : 1.f, sh = (EPI && g.scale) ? g.shift[col] : 0.f;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int64_t row = row0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
                 if (row >= Mrows) continue;
                 float v = g.alpha * acc[i][j][r] + bv;
                 if (g.accumulate) v += out[row * ldo + col];
+                if (EPI) {
+                    if (g.resid) v += g.resid[row * g.ldr + col];
+                    if (g.scale) v = v * sc + sh;
+                }
                 if (g.relu) v = fmaxf(v, 0.f);
                 out[row * ldo + col] = v;
             }

@@ -24,6 +24,12 @@ int fail(int code, const char* fmt, ...);
 void signal_on_next_gemm(int32_t* flag, int value);
 bool signal_pending();
 
+// gmp_gemm_f32 with an affine epilogue (GMP_GEMM_NT only): C = act(((alpha A B^T + bias) + resid) * scale + shift), in that order; scale and
+// shift [N] (both or neither), resid [M, N] with leading dimension ldr; all three NULL = gmp_gemm_f32.  Same dispatch, same accumulation order.
+int gemm_f32_epilogue(int mode, const float* A, const float* B, const float* bias, float* C, int64_t M, int64_t N, int64_t K, int64_t lda,
+                      int64_t ldb, int64_t ldc, float alpha, int accumulate, int relu, const float* scale, const float* shift,
+                      const float* resid, int64_t ldr, void* workspace, size_t workspace_bytes, gmp_stream_t stream);
+
 // Two-lane enqueue (step.hip): the pre-training step's launch sequence is walked by TWO host threads at once -- the caller takes the main
 // stream's launches, a worker thread everything else -- because one thread needs ~4 us per launch and a step has ~250 (the launcher was the
 // limiter on slower hosts; two threads launching on different streams scale 1.7x on this runtime, scripts/probe_two_threads.hip).  Both

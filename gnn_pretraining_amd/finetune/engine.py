@@ -26,7 +26,14 @@ default; the capture stays available (GMP_FINETUNE_GRAPH=1) and tested.
 
 Sparse features (opt-in, `x` a graph.SparseFeatures): the encoder GEMM becomes gmp_sparse_linear_fwd (W transposed into a workspace, one wave
 per node gathering the rows of W^T its non-zeros name) and its weight gradient gmp_sparse_linear_wgrad over the CSC form built once here, plus
-gmp_colsum for the bias.  The flat-buffer layout, the padded [256, dpad] slot and every other launch are the dense path's."""
+gmp_colsum for the bias.  The flat-buffer layout, the padded [256, dpad] slot and every other launch are the dense path's.
+
+Inference (embed / predict on all three engines): always eval mode, whatever model.training is.  With running statistics BatchNorm is a
+per-channel affine map, so one gmp_bn_fold turns the eleven BatchNorms into (scale, shift) rows as the parameters and running statistics
+stand at the call, and every Linear + BatchNorm (+ residual) + ReLU of the backbone is ONE gmp_linear_affine_fwd: a GIN layer is three
+launches (aggregate, GEMM, GEMM) instead of the five forward() runs under model.eval().  One stream, no gates, no capture, no dropout, no
+saved statistics; it writes activation buffers only, which every training step rewrites before it reads them, so a step after a predict is
+bitwise the step without it."""
 from __future__ import annotations
 
 import ctypes as C
@@ -125,6 +132,12 @@ class NodeClassificationEngine:
         self.normsq, self.metrics, self.flags = torch.zeros(1, device=dev), torch.zeros(2, dtype=torch.int32, device=dev), torch.zeros(self.K, dtype=torch.int32, device=dev)
         self._train_idx: Optional[Tensor] = None
         self._bn_calls = 0
+        # inference path: the (scale, shift) table of the 11 BatchNorms (encoder, then inner / outer of each layer), refilled per pass
+        self._fold_ch = [H] + [2 * H, H] * GNN_NUM_LAYERS
+        self._fold_off = [2 * sum(self._fold_ch[:i]) for i in range(len(self._fold_ch))]
+        self._fold_table = torch.empty(2 * sum(self._fold_ch), device=dev)
+        self._infer_loss: Optional[Tuple[Tensor, int]] = None     # (loss sum, count) of the last predict with targets; a step clears it
+        self._fwd_gen, self._embed_gen = 0, -1                    # forwards that wrote h[] so far / the one whose output embed() last returned
 
     # ------------------------------------------------------------------ parameters: one flat buffer, the module's tensors view into it
     def _flatten(self) -> None:
@@ -210,6 +223,7 @@ class NodeClassificationEngine:
     def _backbone_forward(self) -> None:
         """Encoder + the GIN layers into h[GNN_NUM_LAYERS]; every activation the backward reads stays in the engine's buffers."""
         lib, N, P, c = self.lib, self.N, self._P, self.csr
+        self._fwd_gen += 1
         st = torch.cuda.current_stream(self.device).cuda_stream
         enc, sp = self.model.input_encoder, self.seg_ptr.data_ptr()
         # 2,708 x 1,440 -> 256 is 172 output tiles for 256 CUs; unsliced since round 3 (three K-slices + their reduction: 38 us, one launch: 33 --
@@ -240,6 +254,72 @@ class NodeClassificationEngine:
                                      bn2.running_mean.data_ptr(), bn2.running_var.data_ptr(), self.stat["m2"][l].data_ptr(), self.stat["s2"][l].data_ptr(),
                                      self.h[l + 1].data_ptr(), C.byref(cfg), self.bn_ws.data_ptr(), self.bn_ws.numel(), st), "bn2")
 
+    # ------------------------------------------------------------------ inference: eval mode, BatchNorm folded into the GEMM epilogues
+    def _bn_modules(self):
+        enc = self.model.input_encoder
+        return [enc.batch_norm] + [b for l in self.model.gnn_backbone.layers for b in (l.gin_conv.nn[1], l.batch_norm)]
+
+    def _bn_names(self) -> List[str]:
+        return ["input_encoder.batch_norm."] + [f"gnn_backbone.layers.{l}.{n}" for l in range(GNN_NUM_LAYERS) for n in ("gin_conv.nn.1.", "batch_norm.")]
+
+    def _infer_forward(self) -> Tensor:
+        """Encoder + the GIN layers in eval mode into h[GNN_NUM_LAYERS], on the current stream: gmp_bn_fold, the encoder as one
+        gmp_linear_affine_fwd (sparse features: gmp_sparse_linear_fwd + the eval-mode gmp_bn_fwd), then aggregate, GEMM, GEMM per layer."""
+        lib, N, P, c = self.lib, self.N, self._P, self.csr
+        self._fwd_gen += 1
+        st = torch.cuda.current_stream(self.device).cuda_stream
+        bns, names = self._bn_modules(), self._bn_names()
+        tbl = lambda xs: (C.c_void_p * len(xs))(*xs)
+        self._chk(lib.gmp_bn_fold(len(bns), tbl([P(n + "weight") for n in names]), tbl([P(n + "bias") for n in names]),
+                                  tbl([b.running_mean.data_ptr() for b in bns]), tbl([b.running_var.data_ptr() for b in bns]),
+                                  _i32(self._fold_ch), 1e-5, self._fold_table.data_ptr(), st), "bn fold")
+        sc = lambda i: self._fold_table.data_ptr() + 4 * self._fold_off[i]
+        sh = lambda i: sc(i) + 4 * self._fold_ch[i]
+        ws = self.gemm_ws
+
+        def lin(A, w_name, b_name, resid, i, out, M, Nout, K, lda, ldw):
+            self._chk(lib.gmp_linear_affine_fwd(A, P(w_name), P(b_name), resid, sc(i), sh(i), out, M, Nout, K, lda, ldw, Nout if resid else 0, Nout, 1,
+                                                ws.data_ptr(), ws.numel(), st), "linear affine")
+
+        if self.sparse:
+            xs, enc = self.xs, self.model.input_encoder
+            self._chk(lib.gmp_sparse_linear_fwd(xs.rowptr.data_ptr(), xs.col.data_ptr(), xs.val.data_ptr(), N, self.d_in, P("input_encoder.linear.weight"),
+                                                self.dpad, P("input_encoder.linear.bias"), self.z0.data_ptr(), H, H, self.sp_status.data_ptr(),
+                                                self.sp_wt.data_ptr(), self.sp_wt.numel(), st), "sparse encoder")
+            cfg = L.BnConfig(0, 1, 1e-5, 0.1, 0.0, 0, 0, None, None, 0)
+            self._chk(lib.gmp_bn_fwd(self.z0.data_ptr(), None, self.seg_ptr.data_ptr(), None, 1, N, N, H, P("input_encoder.batch_norm.weight"),
+                                     P("input_encoder.batch_norm.bias"), enc.batch_norm.running_mean.data_ptr(), enc.batch_norm.running_var.data_ptr(),
+                                     None, None, self.h[0].data_ptr(), C.byref(cfg), self.bn_ws.data_ptr(), self.bn_ws.numel(), st), "bn encoder (eval)")
+        else:
+            lin(self.x.data_ptr(), "input_encoder.linear.weight", "input_encoder.linear.bias", None, 0, self.h[0].data_ptr(), N, H, self.dpad, self.dpad, self.dpad)
+        for l in range(GNN_NUM_LAYERS):
+            pre = f"gnn_backbone.layers.{l}."
+            self._chk(lib.gmp_gin_aggregate_fwd(self.h[l].data_ptr(), c.rowptr.data_ptr(), c.col.data_ptr(), P(pre + "gin_conv.eps"), self.a[l].data_ptr(), N, H, st), "aggregate")
+            lin(self.a[l].data_ptr(), pre + "gin_conv.nn.0.weight", pre + "gin_conv.nn.0.bias", None, 1 + 2 * l, self.r1[l].data_ptr(), N, 2 * H, H, H, H)
+            lin(self.r1[l].data_ptr(), pre + "gin_conv.nn.3.weight", pre + "gin_conv.nn.3.bias", self.h[l].data_ptr(), 2 + 2 * l, self.h[l + 1].data_ptr(), N, H, 2 * H, 2 * H, 2 * H)
+        return self.h[GNN_NUM_LAYERS]
+
+    def embed(self) -> Tensor:
+        """The backbone's output rows [N, 256] in eval mode (whatever model.training is), from the parameters and running statistics as
+        they stand now.  The engine's own buffer: the next forward, step, embed or predict overwrites it."""
+        out = self._infer_forward()[:self.N]
+        self._embed_gen = self._fwd_gen
+        return out
+
+    def predict(self, node_indices: Tensor, targets: Optional[Tensor] = None) -> Tensor:
+        """Eval-mode logits [len(node_indices), C] of the given nodes; with targets, loss() then returns their mean cross-entropy.
+        Changes nothing a training step reads: parameters, optimizer state, running statistics, counters and the captured step stay as they are."""
+        from .. import operators as O
+        hL = self._infer_forward()
+        self._gemm(torch.cuda.current_stream(self.device).cuda_stream, NT, hL.data_ptr(), self._P("classification_head.mlp.0.weight"),
+                   self._P("classification_head.mlp.0.bias"), self.logits.data_ptr(), self.N, self.classes, H, H, H, self.classes)
+        with torch.no_grad():
+            rows = O.take_rows(self.logits, node_indices)
+            self._infer_loss = None
+            if targets is not None:
+                self._infer_loss = (ops.cross_entropy_sum_fwd(rows, targets.contiguous()), int(node_indices.numel()))
+        return rows
+
     def flush_counters(self) -> None:
         if self._bn_calls:
             enc = self.model.input_encoder
@@ -251,6 +331,7 @@ class NodeClassificationEngine:
     def step(self, node_indices: Tensor, targets: Tensor, apply_update: bool = True) -> None:
         """loss = cross_entropy(model(data)[node_indices], targets) (mean); backward; AdamW.  Nothing is read back: loss().
         Training steps with an update are replayed from a hipGraph captured at the first such call for these index tensors."""
+        self._infer_loss = None
         if not (self.use_graph and apply_update and self.model.training):
             self._enqueue(node_indices, targets, apply_update, forked=self.fork_wgrads)
             self.step_count += 1
@@ -282,6 +363,7 @@ class NodeClassificationEngine:
         if self._graph_step != self.step_count:                    # eager steps ran in between (evaluation does not count): resynchronise
             self.seed_word.fill_(self.step_count)
         self._graph.replay()
+        self._fwd_gen += 1
         self.step_count += 1
         self._graph_step = self.step_count
         self._bn_calls += 1
@@ -416,13 +498,14 @@ class NodeClassificationEngine:
     def loss(self) -> float:
         """Mean cross-entropy of the last step (a read-back: the one place the loop synchronises, so the gates' time-out word and the slab
         BatchNorm's are looked at here too)."""
-        v = float(self.loss_sum.item())
+        infer = self._infer_loss
+        v = float((self.loss_sum if infer is None else infer[0]).item())
         if self.sparse and int(self.sp_status.item()) != 0:
             raise L.GnnmpError(f"fine-tune engine: the sparse encoder skipped {int(self.sp_status.item())} out-of-range feature indices")
         if int(self.sync_flags[63].item()) != 0 or (self.bn_sync is not None and int(self.bn_sync[0].item()) != 0):
             raise L.GnnmpError("fine-tune engine: a cross-stream gate or a BatchNorm slab wait timed out (streams sharing a hardware queue, "
                                "a tool serialising kernels, or a sync buffer shared between streams): results since then are not to be trusted")
-        return v / max(self.num_targets, 1)
+        return v / max(self.num_targets if infer is None else infer[1], 1)
 
     def gradient(self, name: str) -> Tensor:
         o = self.off[name]
@@ -495,6 +578,7 @@ class LinkPredictionEngine(NodeClassificationEngine):
         """loss = BCE(scorer(h, [pos | neg]), [1 | 0]) (mean); backward; AdamW.  pos / neg int64 [2, *] on the device."""
         P_, Q = int(pos_edges.size(1)), int(neg_edges.size(1))
         K = P_ + Q
+        self._infer_loss = None
         if K == 0:
             raise ValueError("LinkPredictionEngine.step: no pairs")
         if K > self.kmax:
@@ -536,6 +620,37 @@ class LinkPredictionEngine(NodeClassificationEngine):
                                     self.pair_csr_ws.numel(), st), "pair csr")
         self._chk(lib.gmp_segment_sum(self.g_hs.data_ptr(), rowptr_t, perm_t, self.gA.data_ptr(), N, H, 0, 0, st), "g_h from sources")
         self._chk(lib.gmp_segment_sum(self.g_hd.data_ptr(), rowptr, perm, self.gA.data_ptr(), N, H, 0, 1, st), "g_h from destinations")
+
+    # ------------------------------------------------------------------ inference
+    def predict(self, edges: Tensor, labels: Optional[Tensor] = None, embeddings: Optional[Tensor] = None) -> Tensor:
+        """Eval-mode probabilities [K] of the pairs edges [2, K] (int64, on the device): the fused scorer with p = 0 over the backbone's
+        eval-mode output.  embeddings: the result of an embed() no forward has overwritten since -- an evaluation pass embeds once and scores
+        every batch of pairs against it (the parameters do not change within a pass); an embedding that a later forward or step has overwritten
+        is refused.  None: embed() first.  With labels, loss() then returns the mean BCE.  Changes nothing a training step reads."""
+        K = int(edges.size(1))
+        if K == 0:
+            raise ValueError("LinkPredictionEngine.predict: no pairs")
+        hL = self.embed() if embeddings is None else embeddings
+        if hL.data_ptr() != self.h[GNN_NUM_LAYERS].data_ptr() or hL.size(0) != self.N:
+            raise ValueError("LinkPredictionEngine.predict: embeddings must be the result of this engine's embed()")
+        if self._embed_gen != self._fwd_gen:
+            raise ValueError("LinkPredictionEngine.predict: a forward or a step has overwritten these embeddings since embed() returned them")
+        if K > self.kmax:
+            self._grow(max(K, 2 * self.kmax))
+        lib, P, st = self.lib, self._P, torch.cuda.current_stream(self.device).cuda_stream
+        pairs = edges.contiguous()
+        self._chk(lib.gmp_lp_score_fwd(hL.data_ptr(), pairs.data_ptr(), pairs.data_ptr() + 8 * K, self.N, K, H, H, P(_LP_HEAD + "0.weight"),
+                                       P(_LP_HEAD + "0.bias"), P(_LP_HEAD + "3.weight"), P(_LP_HEAD + "3.bias"), self.act.data_ptr(), self.logit.data_ptr(),
+                                       0.0, 0, LP_SCORER_SITE, self.score_fwd_ws.data_ptr(), self.score_fwd_ws.numel(), st), "lp score (eval)")
+        self._infer_loss = None
+        if labels is None:
+            return ops.sigmoid_fwd(self.logit[:K])
+        probs, loss_sum, g_scale = torch.empty(K, device=self.device), torch.zeros(1, device=self.device), torch.ones(1, device=self.device)
+        lab = labels.to(torch.float32).contiguous()
+        self._chk(lib.gmp_sigmoid_bce_sum_fwd_bwd(self.logit.data_ptr(), lab.data_ptr(), K, g_scale.data_ptr(), loss_sum.data_ptr(), probs.data_ptr(),
+                                                  self.g_logit.data_ptr(), self.pair_loss_ws.data_ptr(), self.pair_loss_ws.numel(), st), "lp bce (eval)")
+        self._infer_loss = (loss_sum, K)
+        return probs
 
     # ------------------------------------------------------------------ read-backs
     def loss(self) -> float:
@@ -609,7 +724,7 @@ class GraphClassificationEngine(NodeClassificationEngine):
         self.head_ws = ws(lib.gmp_gc_head_fwd_workspace_bytes(cap_b))
 
     # ------------------------------------------------------------------ this step's batch into the engine's buffers
-    def _load(self, batch) -> None:
+    def _load(self, batch, need_y: bool = True) -> None:
         if batch.x.device.type != self.device.type:
             batch = batch.to(self.device)
         N, E, B = batch.num_nodes, batch.num_edges, batch.num_graphs
@@ -617,12 +732,13 @@ class GraphClassificationEngine(NodeClassificationEngine):
             raise ValueError("GraphClassificationEngine: an empty batch")
         if batch.x.size(1) != self.d_in:
             raise ValueError(f"GraphClassificationEngine: the batch has {batch.x.size(1)} features, the encoder {self.d_in}")
-        if batch.y is None or batch.y.numel() != B:
+        if need_y and (batch.y is None or batch.y.numel() != B):
             raise ValueError("GraphClassificationEngine: the batch needs one label per graph")
         if N > self.cap_n or E > self.cap_e or B > self.cap_b:
             grown = lambda need, cap: max(need, 2 * cap) if need > cap else cap
             self._alloc(grown(N, self.cap_n), grown(E, self.cap_e), grown(B, self.cap_b))
         self.N, self.B, self.num_targets = N, B, B
+        self._unlabelled = False
         self.seg_ptr[1:].fill_(N)                                # the one BatchNorm segment [0, N)
         self.x[:N, :self.d_in].copy_(batch.x)
         ei, c = batch.edge_index.contiguous(), self.csr
@@ -631,7 +747,8 @@ class GraphClassificationEngine(NodeClassificationEngine):
                                          c.rowptr_t.data_ptr(), c.col_t.data_ptr(), c.perm_t.data_ptr(), c.status.data_ptr(),
                                          self.csr_ws.data_ptr(), self.csr_ws.numel(), st), "batch csr")
         # (a cast on the device: Batch.ptr32 would upload the host offsets again, one blocking copy per step)
-        self._ptr32, self._y = batch.ptr.to(torch.int32), batch.y.to(torch.int64).contiguous()
+        self._ptr32 = batch.ptr.to(torch.int32)
+        self._y = batch.y.to(torch.int64).contiguous() if (need_y or (batch.y is not None and batch.y.numel() == B)) else None
 
     # ------------------------------------------------------------------ forward: encoder + backbone (the head runs in the step)
     def forward(self, batch=None) -> Tensor:
@@ -650,6 +767,28 @@ class GraphClassificationEngine(NodeClassificationEngine):
         self._head_forward(torch.cuda.current_stream(self.device).cuda_stream)
         return self.logits()
 
+    # ------------------------------------------------------------------ inference
+    def embed(self, batch=None) -> Tensor:
+        """The backbone's eval-mode output rows [N, 256] for `batch` (or for the batch already loaded), whatever model.training is.  Loads the
+        batch and regrows the capacities as step does; labels are not needed.  The engine's own buffer: the next forward overwrites it."""
+        if batch is not None:
+            self._load(batch, need_y=False)
+        out = self._infer_forward()[:self.N]
+        self._embed_gen = self._fwd_gen
+        return out
+
+    def predict(self, batch) -> Tensor:
+        """Eval-mode logits [B, C] of `batch` (the folded backbone + the fused head with p = 0).  With labels (batch.y) loss() then holds the
+        batch's mean loss; without, the fused head runs against zero labels and loss() raises until a labelled batch has been loaded.  Like evaluate(), it replaces the loaded
+        batch (N, B, the CSR: forward() / embed() without an argument then act on this one) and the last loss; parameters, optimizer state,
+        running statistics and counters stay as they are, and a step reloads its own batch, so training is unaffected."""
+        self._load(batch, need_y=False)
+        if self._y is None:
+            self._y, self._unlabelled = torch.zeros(self.B, dtype=torch.int64, device=self.device), True
+        self._infer_forward()
+        self._head_forward(torch.cuda.current_stream(self.device).cuda_stream, p=0.0)
+        return self.logits()
+
     # ------------------------------------------------------------------ one optimisation step
     def step(self, batch, apply_update: bool = True) -> None:
         """loss = classification_loss(model(batch), batch.y) (mean over the batch's graphs); backward; AdamW.  `batch` is the loader's Batch
@@ -662,9 +801,10 @@ class GraphClassificationEngine(NodeClassificationEngine):
         p = self.dropout_p if self.model.training else 0.0
         return p, (self.seed * 1000003 + self.step_count) & (2 ** 64 - 1)
 
-    def _head_forward(self, st: int) -> None:
+    def _head_forward(self, st: int, p: Optional[float] = None) -> None:
         lib, P = self.lib, self._P
-        p, seed = self._head_args()
+        p_step, seed = self._head_args()
+        p = p_step if p is None else p
         self.g_scale.fill_(1.0 / self.B)
         self._chk(lib.gmp_gc_head_fwd(self.h[GNN_NUM_LAYERS].data_ptr(), H, self._ptr32.data_ptr(), self.N, self.B, H, self.act.size(1), self.classes,
                                       P(_GC_HEAD + "0.weight"), P(_GC_HEAD + "0.bias"), P(_GC_HEAD + "3.weight"), P(_GC_HEAD + "3.bias"),
@@ -687,6 +827,8 @@ class GraphClassificationEngine(NodeClassificationEngine):
     def loss(self) -> float:
         """Mean loss of the last step (synchronises; checks the gate and slab time-out words like the node engine, and the CSR build's
         count of edge endpoints outside the batch)."""
+        if getattr(self, "_unlabelled", False):
+            raise L.GnnmpError("fine-tune engine: the last predict had no labels (batch.y): there is no loss to report")
         v = super().loss()
         if int(self.csr.status.item()) != 0:
             raise L.GnnmpError(f"fine-tune engine: {int(self.csr.status.item())} edge endpoints outside the batch's nodes")

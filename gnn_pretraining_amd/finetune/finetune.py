@@ -2,7 +2,8 @@
 miner, process_batch per task type, one AdamW step per batch over FinetuneGNN.param_groups, best-validation checkpoint,
 test metrics from the best checkpoint.  Data come from the loaders of gnn_pretraining_amd/data (processed datasets in
 data/processed; synthetic stand-ins are generated when none were exported).  wandb is replaced by a JSONL logger with the
-same metric keys.  Build-only flags: --epochs, --device, --data-root, --data-scale, --log, --sparse-features, --lp-engine, --gc-engine."""
+same metric keys.  Build-only flags: --epochs, --device, --data-root, --data-scale, --log, --sparse-features, --lp-engine, --gc-engine,
+--engine-eval."""
 from __future__ import annotations
 
 import argparse
@@ -91,6 +92,7 @@ class FinetuneConfig:
     sparse_features: bool = False       # Planetoid domains: node features as CSR (graph.SparseFeatures) -- the sparse encoder kernels
     lp_engine: bool = False             # link-prediction domains: the explicit-kernel step (finetune/engine.py LinkPredictionEngine)
     gc_engine: bool = False             # graph-classification domains: the explicit-kernel step (finetune/engine.py GraphClassificationEngine)
+    engine_eval: bool = False           # validation / test through the active engine's predict (BatchNorm folded into the GEMMs), not the module
 
     def __post_init__(self) -> None:
         if self.sparse_features and TASK_TYPES[self.domain_name] == "graph_classification":
@@ -99,11 +101,24 @@ class FinetuneConfig:
             raise ValueError(f"lp_engine applies to the link-prediction domains (Cora_LP / CiteSeer_LP), not to {self.domain_name}")
         if self.gc_engine and TASK_TYPES[self.domain_name] != "graph_classification":
             raise ValueError(f"gc_engine applies to the graph-classification domains (ENZYMES / PTC_MR), not to {self.domain_name}")
+        if self.engine_eval and not engine_active(self):
+            raise ValueError(f"engine_eval needs an active fine-tune engine for {self.domain_name}: "
+                             + {"node_classification": "the node engine is switched off (GMP_FINETUNE_ENGINE=0)",
+                                "link_prediction": "pass lp_engine (--lp-engine)",
+                                "graph_classification": "pass gc_engine (--gc-engine)"}[TASK_TYPES[self.domain_name]])
         self.exp_name = f"{self.domain_name}_{self.finetune_strategy}_{self.pretrained_scheme}"
         self.task_type = TASK_TYPES[self.domain_name]
         self.batch_size = BATCH_SIZES[self.domain_name]
         self.epochs = EPOCHS[self.domain_name]
         self.patience = int(self.epochs * PATIENCE_FRACTION)
+
+
+def engine_active(cfg: FinetuneConfig) -> bool:
+    """Whether finetune() trains this configuration on an explicit-kernel engine (finetune/engine.py)."""
+    kind = TASK_TYPES[cfg.domain_name]
+    if kind == "node_classification":
+        return os.environ.get("GMP_FINETUNE_ENGINE", "1") != "0"
+    return cfg.lp_engine if kind == "link_prediction" else cfg.gc_engine
 
 
 def set_global_seed(seed: int) -> None:
@@ -285,6 +300,30 @@ def evaluate(model: FinetuneGNN, loader, device, cfg: FinetuneConfig, prefix: st
     return [compute_loss_and_metrics(model, b, device, cfg.task_type, cfg.domain_name, prefix, miner, train_edges) for b in loader]
 
 
+def evaluate_engine(engine, loader, device, cfg: FinetuneConfig, prefix: str) -> List[Dict[str, float]]:
+    """evaluate() on the engine's inference path (cfg.engine_eval): predict per batch, the same compute_batch_metrics.  Link prediction embeds
+    once for the whole pass -- the parameters do not change within it -- and scores every batch of pairs against that."""
+    out = []
+    emb = engine.embed() if cfg.task_type == "link_prediction" else None
+    for batch in loader:
+        if cfg.task_type == "graph_classification":
+            b = batch.to(device)
+            logits, targets = engine.predict(b), b.y
+        elif cfg.task_type == "node_classification":
+            _, node_indices, targets = batch
+            node_indices, targets = node_indices.to(device), targets.to(device)
+            logits = engine.predict(node_indices, targets)
+        else:
+            _, all_edges, edge_labels = batch
+            all_edges, edge_labels = all_edges.to(device).contiguous(), edge_labels.to(device)
+            p = engine.predict(all_edges, edge_labels, embeddings=emb)
+            out.append(compute_batch_metrics(cfg.domain_name, edge_labels.long(), (p > 0.5).long(), torch.stack([1 - p, p], dim=1),
+                                             torch.tensor(engine.loss()), prefix))
+            continue
+        out.append(compute_batch_metrics(cfg.domain_name, targets, logits.argmax(dim=1), torch.softmax(logits, dim=1), torch.tensor(engine.loss()), prefix))
+    return out
+
+
 def finetune(cfg: FinetuneConfig, epochs: Optional[int] = None, device: Optional[str] = None,
              data_root: Optional[str] = None, data_scale: float = 1.0, log_path: Optional[str] = None) -> Dict[str, float]:
     """finetune.py:334-445.  Returns the test metrics of the best-validation checkpoint."""
@@ -334,6 +373,11 @@ def finetune(cfg: FinetuneConfig, epochs: Optional[int] = None, device: Optional
     if cfg.gc_engine:
         from .engine import GraphClassificationEngine
         gc_engine = GraphClassificationEngine(model, dev, seed=cfg.seed, max_graphs=max(cfg.batch_size, 1))
+    eval_engine = None
+    if cfg.engine_eval:
+        eval_engine = node_engine or lp_engine or gc_engine
+        if eval_engine is None:
+            raise ValueError(f"engine_eval needs an active fine-tune engine for {cfg.domain_name}")
     for epoch in range(1, (epochs or cfg.epochs) + 1):
         if node_engine is not None:
             run_training_node_engine(node_engine, train_loader, dev, epoch, global_step, cfg, logger)
@@ -347,7 +391,10 @@ def finetune(cfg: FinetuneConfig, epochs: Optional[int] = None, device: Optional
         else:
             run_training(model, optimizer, train_loader, dev, epoch, global_step, cfg, miner, logger)
         edges = _train_edges(train_loader, dev)
-        val = compute_validation_metrics(evaluate(model, val_loader, dev, cfg, "val", miner, edges), epoch)
+        if eval_engine is not None:
+            val = compute_validation_metrics(evaluate_engine(eval_engine, val_loader, dev, cfg, "val"), epoch)
+        else:
+            val = compute_validation_metrics(evaluate(model, val_loader, dev, cfg, "val", miner, edges), epoch)
         if val[key] > best:
             best, stale = val[key], 0
             torch.save({"epoch": epoch, "model_state_dict": model.state_dict(), "val_metrics": val}, path)
@@ -357,8 +404,11 @@ def finetune(cfg: FinetuneConfig, epochs: Optional[int] = None, device: Optional
         if stale >= cfg.patience:
             break
     model.load_state_dict(torch.load(path, map_location=dev, weights_only=True)["model_state_dict"])
-    test = compute_test_metrics(evaluate(model, test_loader, dev, cfg, "test", miner, _train_edges(train_loader, dev)),
-                                epoch, stale, start, model)
+    if eval_engine is not None:                              # (predict reads the parameters and running statistics just loaded)
+        test_batches = evaluate_engine(eval_engine, test_loader, dev, cfg, "test")
+    else:
+        test_batches = evaluate(model, test_loader, dev, cfg, "test", miner, _train_edges(train_loader, dev))
+    test = compute_test_metrics(test_batches, epoch, stale, start, model)
     logger.log(test, global_step[0])
     print(f"{cfg.exp_name}: best {key} {best:.4f}, test/accuracy {test['test/accuracy']:.4f}, test/auc {test['test/auc']:.4f}, "
           f"training_time {test['test/training_time']:.2f}s, saved {path}")
@@ -379,12 +429,14 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--sparse-features", action="store_true", help="Cora / CiteSeer node features as CSR (sparse encoder kernels)")
     p.add_argument("--lp-engine", action="store_true", help="Cora_LP / CiteSeer_LP: the explicit-kernel fine-tune step (LinkPredictionEngine)")
     p.add_argument("--gc-engine", action="store_true", help="ENZYMES / PTC_MR: the explicit-kernel fine-tune step (GraphClassificationEngine)")
+    p.add_argument("--engine-eval", action="store_true", help="validation / test through the active engine's predict (needs the node engine, --lp-engine or --gc-engine)")
     return p
 
 
 def config_from_args(a: argparse.Namespace) -> FinetuneConfig:
     return FinetuneConfig(a.domain_name, a.finetune_strategy, a.pretrained_scheme, a.seed, sparse_features=a.sparse_features,
-                          lp_engine=getattr(a, "lp_engine", False), gc_engine=getattr(a, "gc_engine", False))
+                          lp_engine=getattr(a, "lp_engine", False), gc_engine=getattr(a, "gc_engine", False),
+                          engine_eval=getattr(a, "engine_eval", False))
 
 
 def main() -> None:

@@ -406,6 +406,80 @@ def bn_fwd(x: Tensor, residual: Optional[Tensor], seg_ptr: Tensor, max_seg_rows:
     return y, sm, sr
 
 
+def _ptr_table(ts):
+    return (C.c_void_p * len(ts))(*[None if t is None else t.data_ptr() for t in ts])
+
+
+def bn_fold(layers, eps: float = 1e-5, out: Optional[Tensor] = None):
+    """Eval-mode BatchNorm as per-channel (scale, shift) rows, all `layers` in one launch (gmp_bn_fold).  layers: a sequence of
+    (gamma, beta, running_mean, running_var) -- gamma / beta may be None (1 / 0).  Returns (table, [(scale, shift), ...]): the pairs are
+    views into `table` (2 * sum of the channel counts floats; pass `out` to reuse one)."""
+    layers = list(layers)
+    if not 1 <= len(layers) <= 16:
+        raise L.GnnmpError(f"bn_fold: {len(layers)} layers (1 .. 16)")
+    chans = []
+    for i, (g, b, m, v) in enumerate(layers):
+        _need(m, torch.float32, f"running_mean[{i}]", 1); _need(v, torch.float32, f"running_var[{i}]", 1)
+        for t, n in ((g, "gamma"), (b, "beta"), (v, "running_var")):
+            if t is not None:
+                _need(t, torch.float32, f"{n}[{i}]", 1)
+                if t.numel() != m.numel():
+                    raise L.GnnmpError(f"bn_fold: {n}[{i}] length")
+        if m.numel() < 1:
+            raise L.GnnmpError(f"bn_fold: layer {i} has no channels")
+        chans.append(m.numel())
+    total = 2 * sum(chans)
+    dev = layers[0][2].device
+    if out is None:
+        out = torch.empty(total, dtype=torch.float32, device=dev)
+    else:
+        _need(out, torch.float32, "out", 1)
+        if out.numel() < total:
+            raise L.GnnmpError(f"bn_fold: out has {out.numel()} floats, {total} needed")
+    cols = list(zip(*layers))
+    L.check(L.lib().gmp_bn_fold(len(layers), _ptr_table(cols[0]), _ptr_table(cols[1]), _ptr_table(cols[2]), _ptr_table(cols[3]),
+                                (C.c_int32 * len(chans))(*chans), float(eps), _ptr(out), _stream(out)), "gmp_bn_fold")
+    pairs, o = [], 0
+    for c in chans:
+        pairs.append((out[o:o + c], out[o + c:o + 2 * c]))
+        o += 2 * c
+    return out, pairs
+
+
+def linear_affine(A: Tensor, W: Tensor, bias: Optional[Tensor], scale: Tensor, shift: Tensor, residual: Optional[Tensor] = None,
+                  relu: bool = False, out: Optional[Tensor] = None) -> Tensor:
+    """act(((A W^T + bias) + residual) * scale + shift), in that order (gmp_linear_affine_fwd): a Linear with the eval-mode BatchNorm that
+    follows it (ops.bn_fold) in the GEMM epilogue.  A [M, K], W [N, K], residual [M, N] and out [M, N] may be row-strided views."""
+    _need_rows(A, "A"); _need_rows(W, "W")
+    M, K, N = A.size(0), A.size(1), W.size(0)
+    if W.size(1) != K or K < 1:
+        raise L.GnnmpError(f"linear_affine: A has {K} columns, W {W.size(1)}")
+    for t, n in ((bias, "bias"), (scale, "scale"), (shift, "shift")):
+        if t is None and n == "bias":
+            continue
+        _need(t, torch.float32, n, 1)
+        if t.numel() != N:
+            raise L.GnnmpError(f"linear_affine: {n} length")
+    ld = lambda t: t.stride(0) if t.size(0) > 1 else t.size(1)
+    if residual is not None:
+        _need_rows(residual, "residual")
+        if tuple(residual.shape) != (M, N):
+            raise L.GnnmpError("linear_affine: residual shape")
+    if out is None:
+        out = torch.empty(M, N, dtype=torch.float32, device=A.device)
+    else:
+        _need_rows(out, "out")
+        if tuple(out.shape) != (M, N):
+            raise L.GnnmpError("linear_affine: out shape")
+    l = L.lib()
+    wsb = l.gmp_linear_affine_workspace_bytes(M, N, K)
+    ws = _ws(wsb, A.device) if wsb else None
+    L.check(l.gmp_linear_affine_fwd(_ptr(A), _ptr(W), _ptr(bias), _ptr(residual), _ptr(scale), _ptr(shift), _ptr(out), M, N, K, ld(A), ld(W),
+                                    0 if residual is None else ld(residual), ld(out), int(relu), _ptr(ws), wsb, _stream(A)),
+            "gmp_linear_affine_fwd")
+    return out
+
+
 def bn_bwd(g_y: Tensor, x: Tensor, residual: Optional[Tensor], seg_ptr: Tensor, max_seg_rows: int, gamma: Tensor,
            beta: Tensor, running_mean, running_var, save_mean, save_rstd, cfg: L.BnConfig, group_seg_ptr=None):
     """Returns (g_u, g_gamma [G,C], g_beta [G,C]); group_seg_ptr: python list of segment offsets (default one group)."""

@@ -240,6 +240,29 @@ int gmp_bn_param_grads(const void* bwd_workspace, int num_segments, int channels
                        int num_groups, gmp_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
+ * Inference: eval-mode BatchNorm1d folded into the Linear that feeds it.  With running statistics the norm is the per-channel
+ * affine map y = scale * u + shift, scale = gamma / sqrt(running_var + eps), shift = beta - scale * running_mean.
+ *
+ * gmp_bn_fold: the (scale, shift) rows of `count` (<= 16) BatchNorms in ONE launch.  gamma / beta / running_mean / running_var are HOST
+ *   arrays of `count` device pointers, channels a HOST int32 array (gamma / beta, or single entries of them, may be NULL: 1 / 0).
+ *   `table` is the caller's: entry e's scale row starts at float offset 2 * (channels[0] + .. + channels[e-1]), its shift row follows
+ *   at + channels[e]; 2 * sum(channels) floats in all.  Asynchronous on `stream`, allocates nothing.
+ *
+ * gmp_linear_affine_fwd: C[M,N] = act(((A W^T + bias) + residual) * scale + shift), evaluated in exactly that order (fp32, no fused
+ *   multiply-add).  A [M,K] (lda), W [N,K] as nn.Linear stores it (ldw), bias [N] or NULL, residual [M,N] (ldr) or NULL, scale and
+ *   shift [N] (rows of gmp_bn_fold's table), relu != 0 -> max(., 0).  Any M >= 1, K >= 1.  The product runs on gmp_gemm_f32's kernels
+ *   under its dispatch rule (GMP_GEMM_NT, alpha 1): with scale = 1, shift = 0 and no residual the result equals gmp_gemm_f32's given
+ *   the same workspace -- the same accumulation order, so the same bits, except that an element gmp_gemm_f32 leaves at -0.0 becomes +0.0.  Rows beyond M are never written.  No atomics: bitwise reproducible.  The workspace is optional, as for
+ *   gmp_gemm_f32 (K-slices when the output alone cannot fill the chip).
+ * ------------------------------------------------------------------------- */
+int gmp_bn_fold(int count, const float* const* gamma, const float* const* beta, const float* const* running_mean,
+                const float* const* running_var, const int32_t* channels, float eps, float* table, gmp_stream_t stream);
+size_t gmp_linear_affine_workspace_bytes(int64_t M, int64_t N, int64_t K);
+int gmp_linear_affine_fwd(const float* A, const float* W, const float* bias, const float* residual, const float* scale,
+                          const float* shift, float* C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw, int64_t ldr,
+                          int64_t ldc, int relu, void* workspace, size_t workspace_bytes, gmp_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
  * Link-prediction edge features (the per-edge MLP input, heads.py:58-66):
  *   feat[k,:] = [ hs+hd | hs*hd | |hs-hd| ],  hs = h[edges[0,k]], hd = h[edges[1,k]]
  * bwd produces per-edge gradients g_hs, g_hd [K,F]; the caller reduces them onto
