@@ -38,12 +38,12 @@ from __future__ import annotations
 
 import ctypes as C
 import os as _os_mod
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 from torch import Tensor
 
-from .. import _lib as L, ops
+from .. import _lib as L, operators as OP, ops
 from ..graph import SparseFeatures
 from ..models.finetune_model import LR_BACKBONE, LR_FINETUNE, FinetuneGNN
 from ..models.gnn import DROPOUT_RATE, GNN_HIDDEN_DIM, GNN_NUM_LAYERS
@@ -520,6 +520,14 @@ MINING_SITE_BASE = 100              # added to the backbone's sites in the minin
 _LP_HEAD = "classification_head.predictor.mlp."
 
 
+class LinkRanks(NamedTuple):
+    """LinkPredictionEngine.rank(): per true pair, over its filtered candidates."""
+    n_greater: Tensor   # [Q] int32: candidates scoring above the true pair
+    n_equal: Tensor     # [Q] int32: candidates scoring exactly the true pair's logit
+    rank: Tensor        # [Q] float32: 1 + n_greater + n_equal / 2
+    logit: Tensor       # [Q] the true pair's logit (sigmoid of it is predict()'s probability)
+
+
 class LinkPredictionEngine(NodeClassificationEngine):
     """One link-prediction fine-tune step (Cora_LP / CiteSeer_LP, src/finetune/finetune.py:181-211) as an explicit kernel sequence.
 
@@ -651,6 +659,37 @@ class LinkPredictionEngine(NodeClassificationEngine):
                                                   self.g_logit.data_ptr(), self.pair_loss_ws.data_ptr(), self.pair_loss_ws.numel(), st), "lp bce (eval)")
         self._infer_loss = (loss_sum, K)
         return probs
+
+    def _ranking_inputs(self, who: str, embeddings: Optional[Tensor], filter_edges: Optional[Tensor]):
+        """The embeddings under predict()'s rules, the scorer's weights and the filter's source-major CSR (cached per tensor)."""
+        hL = self.embed() if embeddings is None else embeddings
+        if hL.data_ptr() != self.h[GNN_NUM_LAYERS].data_ptr() or hL.size(0) != self.N:
+            raise ValueError(f"LinkPredictionEngine.{who}: embeddings must be the result of this engine's embed()")
+        if self._embed_gen != self._fwd_gen:
+            raise ValueError(f"LinkPredictionEngine.{who}: a forward or a step has overwritten these embeddings since embed() returned them")
+        mlp = self.model.classification_head.predictor.mlp
+        return hL, (mlp[0].weight, mlp[0].bias, mlp[3].weight, mlp[3].bias), None if filter_edges is None else filter_edges.to(self.device)
+
+    def rank(self, edges: Tensor, filter_edges: Optional[Tensor] = None, embeddings: Optional[Tensor] = None) -> "LinkRanks":
+        """Every true pair of edges [2, Q] (int64, on the device) ranked against all N nodes as destinations (gmp_lp_rank: no pair list,
+        no per-candidate logit in memory).  Left out of a pair's candidates: its source, its destination, and every c with (source, c) in
+        filter_edges [2, E] (the known positives; its CSR is built once per tensor).  embeddings: as for predict().  Eval mode; changes
+        nothing a training step reads."""
+        if int(edges.size(1)) == 0:
+            raise ValueError("LinkPredictionEngine.rank: no pairs")
+        hL, weights, filt = self._ranking_inputs("rank", embeddings, filter_edges)
+        logit, n_greater, n_equal = OP.lp_rank(hL, edges, *weights, filter_edges=filt)
+        return LinkRanks(n_greater, n_equal, 1.0 + n_greater.to(torch.float32) + 0.5 * n_equal.to(torch.float32), logit)
+
+    def top_k(self, sources: Tensor, k: int, filter_edges: Optional[Tensor] = None, embeddings: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+        """The k (1 <= k <= 64) most probable destinations of every node of sources [Q] (int64, on the device) among all N nodes
+        (gmp_lp_topk): (idx [Q, k] int64, probability [Q, k]), best first, ties to the lower index, the source itself and its
+        filter_edges destinations left out; -1 / probability 0 where a source has fewer than k candidates.  Otherwise as rank()."""
+        if int(sources.numel()) == 0:
+            raise ValueError("LinkPredictionEngine.top_k: no sources")
+        hL, weights, filt = self._ranking_inputs("top_k", embeddings, filter_edges)
+        idx, logit = OP.lp_topk(hL, sources, k, *weights, filter_edges=filt)
+        return idx, ops.sigmoid_fwd(logit.view(-1)).view_as(logit)
 
     # ------------------------------------------------------------------ read-backs
     def loss(self) -> float:

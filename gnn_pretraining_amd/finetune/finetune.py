@@ -21,7 +21,7 @@ from .. import operators as O, ops
 from ..constants import NUM_CLASSES, TASK_TYPES
 from ..graph import SparseFeatures
 from ..models.finetune_model import FinetuneGNN, create_finetune_model
-from .metrics import compute_batch_metrics, compute_test_metrics, compute_training_metrics, compute_validation_metrics
+from .metrics import compute_batch_metrics, compute_test_metrics, compute_training_metrics, compute_validation_metrics, ranking_metrics
 
 OUTPUT_DIR = Path(__file__).resolve().parents[2] / "outputs" / "finetune"
 BATCH_SIZES = {"ENZYMES": 32, "PTC_MR": 32, "Cora_NC": -1, "CiteSeer_NC": -1, "Cora_LP": 256, "CiteSeer_LP": 256}
@@ -93,6 +93,7 @@ class FinetuneConfig:
     lp_engine: bool = False             # link-prediction domains: the explicit-kernel step (finetune/engine.py LinkPredictionEngine)
     gc_engine: bool = False             # graph-classification domains: the explicit-kernel step (finetune/engine.py GraphClassificationEngine)
     engine_eval: bool = False           # validation / test through the active engine's predict (BatchNorm folded into the GEMMs), not the module
+    lp_ranking: bool = False            # link prediction on the engine: the test pass also ranks every true test edge against all nodes (MRR, Hits@K)
 
     def __post_init__(self) -> None:
         if self.sparse_features and TASK_TYPES[self.domain_name] == "graph_classification":
@@ -106,6 +107,8 @@ class FinetuneConfig:
                              + {"node_classification": "the node engine is switched off (GMP_FINETUNE_ENGINE=0)",
                                 "link_prediction": "pass lp_engine (--lp-engine)",
                                 "graph_classification": "pass gc_engine (--gc-engine)"}[TASK_TYPES[self.domain_name]])
+        if self.lp_ranking and not self.lp_engine:
+            raise ValueError("lp_ranking ranks with the link-prediction engine (gmp_lp_rank): pass lp_engine (--lp-engine)")
         self.exp_name = f"{self.domain_name}_{self.finetune_strategy}_{self.pretrained_scheme}"
         self.task_type = TASK_TYPES[self.domain_name]
         self.batch_size = BATCH_SIZES[self.domain_name]
@@ -324,6 +327,17 @@ def evaluate_engine(engine, loader, device, cfg: FinetuneConfig, prefix: str) ->
     return out
 
 
+def rank_test_edges(engine, train_loader, val_loader, test_loader, device) -> Dict[str, float]:
+    """The filtered ranking evaluation of link prediction (cfg.lp_ranking): every true test edge (s, d) is ranked among all nodes as
+    destinations of s, the known positives of the three splits (either direction: the graphs are undirected) filtered out; MRR and
+    Hits@K over those ranks.  One embed(), one LinkPredictionEngine.rank()."""
+    pos = test_loader.dataset.pos_edges.to(device).contiguous()
+    known = torch.cat([train_loader.dataset.train_edges, val_loader.dataset.pos_edges, test_loader.dataset.pos_edges], dim=1).to(device)
+    known = torch.cat([known, known.flip(0)], dim=1).contiguous()
+    ranks = engine.rank(pos, filter_edges=known).rank
+    return {f"test/{k}": v for k, v in ranking_metrics(ranks).items()}
+
+
 def finetune(cfg: FinetuneConfig, epochs: Optional[int] = None, device: Optional[str] = None,
              data_root: Optional[str] = None, data_scale: float = 1.0, log_path: Optional[str] = None) -> Dict[str, float]:
     """finetune.py:334-445.  Returns the test metrics of the best-validation checkpoint."""
@@ -409,6 +423,8 @@ def finetune(cfg: FinetuneConfig, epochs: Optional[int] = None, device: Optional
     else:
         test_batches = evaluate(model, test_loader, dev, cfg, "test", miner, _train_edges(train_loader, dev))
     test = compute_test_metrics(test_batches, epoch, stale, start, model)
+    if cfg.lp_ranking:
+        test.update(rank_test_edges(lp_engine, train_loader, val_loader, test_loader, dev))
     logger.log(test, global_step[0])
     print(f"{cfg.exp_name}: best {key} {best:.4f}, test/accuracy {test['test/accuracy']:.4f}, test/auc {test['test/auc']:.4f}, "
           f"training_time {test['test/training_time']:.2f}s, saved {path}")
@@ -430,13 +446,14 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--lp-engine", action="store_true", help="Cora_LP / CiteSeer_LP: the explicit-kernel fine-tune step (LinkPredictionEngine)")
     p.add_argument("--gc-engine", action="store_true", help="ENZYMES / PTC_MR: the explicit-kernel fine-tune step (GraphClassificationEngine)")
     p.add_argument("--engine-eval", action="store_true", help="validation / test through the active engine's predict (needs the node engine, --lp-engine or --gc-engine)")
+    p.add_argument("--lp-ranking", action="store_true", help="with --lp-engine: the test pass also logs test/mrr and test/hits@K (true test edges ranked against all nodes, known positives filtered)")
     return p
 
 
 def config_from_args(a: argparse.Namespace) -> FinetuneConfig:
     return FinetuneConfig(a.domain_name, a.finetune_strategy, a.pretrained_scheme, a.seed, sparse_features=a.sparse_features,
                           lp_engine=getattr(a, "lp_engine", False), gc_engine=getattr(a, "gc_engine", False),
-                          engine_eval=getattr(a, "engine_eval", False))
+                          engine_eval=getattr(a, "engine_eval", False), lp_ranking=getattr(a, "lp_ranking", False))
 
 
 def main() -> None:

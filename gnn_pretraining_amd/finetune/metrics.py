@@ -3,7 +3,7 @@ sample-weighted means over batches).  Reporting only: nothing here feeds back in
 from __future__ import annotations
 
 import time
-from typing import Dict, List
+from typing import Dict, List, Sequence
 
 import numpy as np
 import torch
@@ -75,3 +75,17 @@ def compute_test_metrics(batch_metrics: List[Dict[str, float]], epoch: int, epoc
     m["test/total_parameters"] = sum(p.numel() for p in model.parameters())
     m["test/trainable_parameters"] = sum(p.numel() for p in model.parameters() if p.requires_grad)
     return m
+
+
+def ranking_metrics(ranks, ks: Sequence[int] = (1, 10, 50)) -> Dict[str, float]:
+    """MRR and Hits@K of link-prediction ranks (1 = best).  A rank may be fractional: a true edge tied with n_equal candidates sits at
+    1 + n_greater + n_equal / 2, the mean over the orders of the tie (LinkPredictionEngine.rank).  hits@K counts rank <= K."""
+    r = torch.as_tensor(ranks, dtype=torch.float64).reshape(-1).cpu()
+    if r.numel() == 0:
+        raise ValueError("ranking_metrics: no ranks")
+    if bool((r < 1).any()):
+        raise ValueError("ranking_metrics: ranks start at 1")
+    out = {"mrr": float((1.0 / r).mean())}
+    for k in ks:
+        out[f"hits@{int(k)}"] = float((r <= k).to(torch.float64).mean())
+    return out

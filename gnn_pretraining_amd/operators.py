@@ -8,6 +8,7 @@ re-implemented as autograd Functions over libgnnmp (SURVEY.md section 8b "operat
     batch_norm_act(...)                    BatchNorm1d (+residual,+ReLU,+dropout) gnn.py:19-22,42-43
     take_rows(h, idx)                      h[idx]                                tasks.py:80
     lp_edge_features(h, edges)             [hs+hd | hs*hd | |hs-hd|]             heads.py:58-66
+    lp_rank / lp_topk(h, ..., weights)     one source against all nodes with MLPLinkPredictor (inference, no autograd)
     nt_xent(z1, z2, T, impl="auto")        SimCLR loss (matrix or streaming form) tasks.py:192-213
     relu_dropout(x, p, training)           the ReLU->Dropout pair of MLPHead     heads.py:43-45
 
@@ -294,6 +295,51 @@ class _LpEdgeFeatures(torch.autograd.Function):
 
 def lp_edge_features(h: Tensor, edges: Tensor) -> Tensor:
     return _LpEdgeFeatures.apply(h, edges.contiguous())
+
+
+def _lp_filter(who: str, filter_edges: Optional[Tensor], num_nodes: int) -> Tuple[Optional[Tensor], Optional[Tensor]]:
+    """The source-major CSR of the known edges (row = source, entries = destinations), built once per tensor (csr_of)."""
+    if filter_edges is None:
+        return None, None
+    if filter_edges.dtype != torch.int64 or filter_edges.dim() != 2 or filter_edges.size(0) != 2:
+        raise GnnmpError(f"{who}: filter_edges must be an int64 [2, E] tensor, got {filter_edges.dtype} {tuple(filter_edges.shape)}")
+    csr = csr_of(filter_edges, num_nodes)
+    return csr.rowptr_t, csr.col_t
+
+
+def _lp_inference_args(who: str, h: Tensor, weights) -> Tuple[Tensor, ...]:
+    if h.dim() != 2 or h.size(1) != 256:
+        raise GnnmpError(f"{who}: h must be [N, 256], got {tuple(h.shape)}")
+    w0, b0, w3, b3 = (w.detach().contiguous() for w in weights)
+    if tuple(w0.shape) != (256, 768) or b0.numel() != 256 or w3.numel() != 256 or b3.numel() != 1:
+        raise GnnmpError(f"{who}: scorer weights must be w0 [256, 768], b0 [256], w3 [256] or [1, 256], b3 [1]")
+    return h.detach().contiguous(), w0, b0, w3, b3
+
+
+def lp_rank(h: Tensor, edges: Tensor, w0: Tensor, b0: Tensor, w3: Tensor, b3: Tensor,
+            filter_edges: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
+    """Filtered ranking of the true pairs edges [2, Q] (int64) against every node of h (inference only, no autograd): returns
+    (logit_true [Q], n_greater [Q], n_equal [Q]); the rank of pair q is 1 + n_greater[q] + n_equal[q] / 2.  filter_edges [2, E]:
+    known edges, a candidate c with (src, c) among them is left out."""
+    if edges.dtype != torch.int64 or edges.dim() != 2 or edges.size(0) != 2:
+        raise GnnmpError(f"lp_rank: edges must be an int64 [2, Q] tensor, got {edges.dtype} {tuple(edges.shape)}")
+    h, w0, b0, w3, b3 = _lp_inference_args("lp_rank", h, (w0, b0, w3, b3))
+    rowptr, col = _lp_filter("lp_rank", filter_edges, h.size(0))
+    e = edges.contiguous()
+    return ops.lp_rank(h, e[0], e[1], w0, b0, w3, b3, rowptr, col)
+
+
+def lp_topk(h: Tensor, sources: Tensor, k: int, w0: Tensor, b0: Tensor, w3: Tensor, b3: Tensor,
+            filter_edges: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """The k best destinations of every source among all nodes of h (inference only, no autograd): (idx [Q, k], logit [Q, k]),
+    best first, ties to the lower index, -1 / -inf where a source has fewer than k candidates."""
+    if sources.dtype != torch.int64 or sources.dim() != 1:
+        raise GnnmpError(f"lp_topk: sources must be an int64 [Q] tensor, got {sources.dtype} {tuple(sources.shape)}")
+    if not 1 <= int(k) <= 64:
+        raise GnnmpError(f"lp_topk: k={k} (1 <= k <= 64)")
+    h, w0, b0, w3, b3 = _lp_inference_args("lp_topk", h, (w0, b0, w3, b3))
+    rowptr, col = _lp_filter("lp_topk", filter_edges, h.size(0))
+    return ops.lp_topk(h, sources.contiguous(), int(k), w0, b0, w3, b3, rowptr, col)
 
 
 # --------------------------------------------------------------------------- #

@@ -951,6 +951,57 @@ def lp_score_node_grad(g_hs: Tensor, g_hd: Tensor, pairs: Tensor, num_nodes: int
     return segment_sum(g_hd, csr.rowptr, csr.perm, out=gh, accumulate=True)
 
 
+def _lp_rank_args(who: str, h: Tensor, w0: Tensor, b0: Tensor, w3: Tensor, b3: Tensor, filter_rowptr: Optional[Tensor],
+                  filter_col: Optional[Tensor]) -> int:
+    _need(h, torch.float32, "h", 2)
+    for t, n in ((w0, "w0"), (b0, "b0"), (w3, "w3"), (b3, "b3")):
+        _need(t, torch.float32, n)
+    if (filter_rowptr is None) != (filter_col is None):
+        raise L.GnnmpError(f"{who}: filter_rowptr and filter_col go together")
+    if filter_rowptr is None:
+        return 0
+    _need(filter_rowptr, torch.int32, "filter_rowptr", 1); _need(filter_col, torch.int32, "filter_col", 1)
+    if filter_rowptr.numel() != h.size(0) + 1:
+        raise L.GnnmpError(f"{who}: filter_rowptr has {filter_rowptr.numel()} entries for {h.size(0)} nodes")
+    return filter_col.numel()
+
+
+def lp_rank(h: Tensor, src: Tensor, dst: Tensor, w0: Tensor, b0: Tensor, w3: Tensor, b3: Tensor, filter_rowptr: Optional[Tensor] = None,
+            filter_col: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
+    """Every true pair (src[q], dst[q]) ranked against all nodes of h [N, 256] (gnnmp.h gmp_lp_rank): returns (logit_true [Q],
+    n_greater [Q] int32, n_equal [Q] int32) over the candidates c other than src[q], dst[q] and the entries of src[q]'s row of the
+    optional filter CSR (int32 rowptr [N + 1] / col, row = source).  Logits are those of lp_score_fwd with p = 0, bit for bit."""
+    nnz = _lp_rank_args("lp_rank", h, w0, b0, w3, b3, filter_rowptr, filter_col)
+    _need(src, torch.int64, "src", 1); _need(dst, torch.int64, "dst", 1)
+    Q, N, dev, l = src.numel(), h.size(0), h.device, L.lib()
+    if dst.numel() != Q:
+        raise L.GnnmpError("lp_rank: src and dst differ in length")
+    logit = torch.empty(Q, device=dev)
+    n_greater, n_equal = torch.empty(Q, dtype=torch.int32, device=dev), torch.empty(Q, dtype=torch.int32, device=dev)
+    ws = _ws(l.gmp_lp_rank_workspace_bytes(Q, N), dev)
+    L.check(l.gmp_lp_rank(_ptr(h), _ptr(src), _ptr(dst), N, Q, h.size(1), w0.size(0), _ptr(w0), _ptr(b0), _ptr(w3), _ptr(b3),
+                          _ptr(filter_rowptr), _ptr(filter_col), nnz, _ptr(logit), _ptr(n_greater), _ptr(n_equal), _ptr(ws), ws.numel(),
+                          _stream(h)), "gmp_lp_rank")
+    return logit, n_greater, n_equal
+
+
+def lp_topk(h: Tensor, src: Tensor, k: int, w0: Tensor, b0: Tensor, w3: Tensor, b3: Tensor, filter_rowptr: Optional[Tensor] = None,
+            filter_col: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """The k (1 <= k <= 64) best destinations of every source over all nodes of h [N, 256] (gnnmp.h gmp_lp_topk): returns (idx [Q, k]
+    int64, logit [Q, k]), logit descending, ties to the lower node index, the source itself and its filter row left out; a row with
+    fewer than k candidates is padded with -1 / -inf."""
+    nnz = _lp_rank_args("lp_topk", h, w0, b0, w3, b3, filter_rowptr, filter_col)
+    _need(src, torch.int64, "src", 1)
+    if not 1 <= int(k) <= 64:
+        raise L.GnnmpError(f"lp_topk: k={k} (1 <= k <= 64)")
+    Q, N, dev, l = src.numel(), h.size(0), h.device, L.lib()
+    idx, logit = torch.empty(Q, k, dtype=torch.int64, device=dev), torch.empty(Q, k, device=dev)
+    ws = _ws(l.gmp_lp_topk_workspace_bytes(Q, N), dev)
+    L.check(l.gmp_lp_topk(_ptr(h), _ptr(src), N, Q, int(k), h.size(1), w0.size(0), _ptr(w0), _ptr(b0), _ptr(w3), _ptr(b3), _ptr(filter_rowptr),
+                          _ptr(filter_col), nnz, _ptr(idx), _ptr(logit), _ptr(ws), ws.numel(), _stream(h)), "gmp_lp_topk")
+    return idx, logit
+
+
 def gc_head_fwd(h: Tensor, ptr: Tensor, w0: Tensor, b0: Tensor, w3: Tensor, b3: Tensor, target: Tensor, g_scale: Tensor, p: float = 0.0,
                 seed: int = 0, site: int = 0) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
     """The fused graph-classification head up to the loss (gnnmp.h gmp_gc_head_fwd): h [N, 256] (rows contiguous, any leading dimension),

@@ -296,6 +296,34 @@ int gmp_lp_score_bwd(const float* h, const int64_t* src, const int64_t* dst, int
                      void* workspace, size_t workspace_bytes, gmp_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
+ * All-candidate link ranking with the scorer above (p = 0): one source against every node of h [num_nodes, feat], reduced on the fly.
+ * The logit of a pair (s, c) is bit for bit the one gmp_lp_score_fwd gives it with p = 0 (the same MFMA products, k-slices and partial
+ * dots in the same order), so ranks are exact integers that agree with scoring the explicit pair list.  No per-candidate logit, no
+ * [Q num_nodes, hidden] activation and no pair list is written to memory.
+ * The optional filter is a CSR of known edges, row = source: filter_rowptr int32 [num_nodes + 1], filter_col int32 [filter_nnz]
+ * (both NULL: no filter).  Rows need not be sorted and may hold duplicates; entries outside [0, num_nodes) are ignored.
+ * gmp_lp_rank, for Q true pairs (src[q], dst[q]): logit_true [Q], and over the candidates c in [0, num_nodes) except c == src[q],
+ *   c == dst[q] and the entries of src[q]'s filter row: n_greater [Q] = how many score greater than the true pair, n_equal [Q] = how
+ *   many score equal to it (int32; the filtered rank is 1 + n_greater + n_equal / 2).  Integer sums: independent of the block order.
+ *   Needs no workspace (gmp_lp_rank_workspace_bytes is 0; workspace may be NULL).
+ * gmp_lp_topk, for Q sources and 1 <= k <= 64: idx [Q, k] int64 and logit [Q, k], the k best candidates c != src[q] outside the
+ *   filter row, logit descending, ties to the lower node index; a row with fewer than k candidates is padded with -1 / -inf.
+ *   workspace >= gmp_lp_topk_workspace_bytes(Q, num_nodes): at most 16 partial lists of 64 entries per source, O(Q).
+ * src / dst outside [0, num_nodes) read as a zero row (and have an empty filter row).  feat == hidden == 256; num_nodes < 2^31;
+ * h, w0, b0, w3 16-byte aligned.
+ * ------------------------------------------------------------------------- */
+size_t gmp_lp_rank_workspace_bytes(int64_t num_queries, int64_t num_nodes);
+size_t gmp_lp_topk_workspace_bytes(int64_t num_queries, int64_t num_nodes);
+int gmp_lp_rank(const float* h, const int64_t* src, const int64_t* dst, int64_t num_nodes, int64_t num_queries, int feat_dim, int hidden,
+                const float* w0, const float* b0, const float* w3, const float* b3, const int32_t* filter_rowptr,
+                const int32_t* filter_col, int64_t filter_nnz, float* logit_true, int32_t* n_greater, int32_t* n_equal,
+                void* workspace, size_t workspace_bytes, gmp_stream_t stream);
+int gmp_lp_topk(const float* h, const int64_t* src, int64_t num_nodes, int64_t num_queries, int k, int feat_dim, int hidden,
+                const float* w0, const float* b0, const float* w3, const float* b3, const int32_t* filter_rowptr,
+                const int32_t* filter_col, int64_t filter_nnz, int64_t* idx, float* logit, void* workspace, size_t workspace_bytes,
+                gmp_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
  * The fused graph-classification head of fine-tuning (finetune_model.py:68-80, finetune.py:110-114) over one batch of
  * num_graphs graphs; graph b owns the rows ptr[b] .. ptr[b+1] of h (ptr: device int32 [num_graphs + 1]):
  *   pooled[b] = mean of the graph's rows, divisor max(count, 1) (gmp_segment_sum(mean = 1); an empty graph pools to zero),

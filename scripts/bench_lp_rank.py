@@ -1,0 +1,131 @@
+"""Filtered ranking of Q = 1,000 true edges against all nodes of a Cora-sized graph (2,708 x 1,433), two routes in one process:
+
+  rank      LinkPredictionEngine.rank(edges, filter_edges, embeddings): gmp_lp_rank, one call, no pair list
+  predict   what the engine offered before it: per chunk of queries the explicit [2, chunk N] pair list, LinkPredictionEngine.predict
+            over it (the fused scorer, which keeps a [pairs, 256] activation), then torch comparisons of the logits against the true
+            pair's, masked by a dense known-edge matrix
+
+    python scripts/bench_lp_rank.py [--queries 1000] [--chunk 64] [--reps 10] [--warmup 2] [--out profiles/lp_rank.json]
+
+Both routes share one embed() (not timed), run alternately, and are timed by a host clock around work that ends in a synchronise and
+by device events.  Peak memory is torch's allocator peak over a route's first call, above what was allocated before it.  The
+two routes' counts are compared and must be equal.  Also timed: top_k (k = 10) for the same sources."""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+from gnn_pretraining_amd import synthetic as S  # noqa: E402
+from gnn_pretraining_amd.data.data_setup import create_link_prediction_splits  # noqa: E402
+from gnn_pretraining_amd.finetune.engine import LinkPredictionEngine  # noqa: E402
+from gnn_pretraining_amd.models import FinetuneGNN  # noqa: E402
+
+DEV = torch.device("cuda")
+
+
+def timed(fn, reps: int):
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0 = time.perf_counter()
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return 1e3 * (time.perf_counter() - t0) / reps, e0.elapsed_time(e1) / reps
+
+
+def peak_mb(fn):
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    base = torch.cuda.memory_allocated()
+    torch.cuda.reset_peak_memory_stats()
+    out = fn()
+    torch.cuda.synchronize()
+    return (torch.cuda.max_memory_allocated() - base) / 2 ** 20, out
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--queries", type=int, default=1000)
+    ap.add_argument("--chunk", type=int, default=64)
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    gen = torch.Generator().manual_seed(0)
+    torch.manual_seed(0)
+    c = S.cora_like(gen)
+    N = c.num_nodes
+    splits = create_link_prediction_splits(c)
+    train_pos = splits["train_pos"].contiguous()
+    model = FinetuneGNN(DEV, "Cora_LP", "full_finetune")
+    eng = LinkPredictionEngine(model, c.x, train_pos, DEV, seed=0)
+    pos = torch.cat([splits["test_pos"], splits["val_pos"], train_pos], dim=1)[:, :a.queries].contiguous().to(DEV)
+    Q = pos.size(1)
+    known = torch.cat([train_pos, splits["val_pos"], splits["test_pos"]], dim=1)
+    known = torch.cat([known, known.flip(0)], dim=1).contiguous().to(DEV)
+    emb = eng.embed()
+
+    def route_rank():
+        r = eng.rank(pos, filter_edges=known, embeddings=emb)
+        return r.n_greater, r.n_equal
+
+    adj = torch.zeros(N, N, dtype=torch.bool, device=DEV)
+    adj[known[0], known[1]] = True
+    ar = torch.arange(N, device=DEV)
+
+    def route_predict():
+        ng, ne = [], []
+        for s0 in range(0, Q, a.chunk):
+            src, dst = pos[0, s0:s0 + a.chunk], pos[1, s0:s0 + a.chunk]
+            q = src.numel()
+            pairs = torch.stack([src[:, None].expand(q, N).reshape(-1), ar[None, :].expand(q, N).reshape(-1)])
+            eng.predict(pairs, embeddings=emb)
+            logit = eng.logit[:q * N].view(q, N)
+            lt = logit.gather(1, dst[:, None])
+            keep = ~(adj[src] | (ar[None, :] == src[:, None]) | (ar[None, :] == dst[:, None]))
+            ng.append(((logit > lt) & keep).sum(1))
+            ne.append(((logit == lt) & keep).sum(1))
+        return torch.cat(ng).to(torch.int32), torch.cat(ne).to(torch.int32)
+
+    sources = pos[0].contiguous()
+    route_topk = lambda: eng.top_k(sources, 10, filter_edges=known, embeddings=emb)
+
+    # each route's first call: everything it makes the engine allocate counts (predict grows the engine's pair buffers to the chunk)
+    (rank_peak, got), (pred_peak, want) = peak_mb(route_rank), peak_mb(route_predict)
+    for _ in range(a.warmup):
+        route_rank(), route_predict(), route_topk()
+    same = bool(torch.equal(got[0], want[0]) and torch.equal(got[1], want[1]))
+    rank_t, pred_t = [], []
+    for _ in range(3):                                          # alternate the routes: the order does not decide the result
+        rank_t.append(timed(route_rank, a.reps))
+        pred_t.append(timed(route_predict, max(a.reps // 5, 1)))
+    topk_t = timed(route_topk, a.reps)
+    best = lambda ts, i: round(min(t[i] for t in ts), 3)
+    res = {"shape": f"Cora-sized synthetic graph: N = {N}, Q = {Q} true edges, {known.size(1)} filter edges, predict route in chunks of {a.chunk} queries",
+           "counts_equal": same,
+           "rank_ms": best(rank_t, 0), "rank_event_ms": best(rank_t, 1), "rank_ms_runs": [round(t[0], 3) for t in rank_t],
+           "predict_route_ms": best(pred_t, 0), "predict_route_event_ms": best(pred_t, 1), "predict_route_ms_runs": [round(t[0], 3) for t in pred_t],
+           "rank_peak_mb": round(rank_peak, 2), "predict_route_peak_mb": round(pred_peak, 2),
+           "topk10_ms": round(topk_t[0], 3), "topk10_event_ms": round(topk_t[1], 3),
+           "pairs": Q * N, "reps": a.reps, "warmup": a.warmup}
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+    if not same:
+        raise SystemExit("the two routes disagree")
+
+
+if __name__ == "__main__":
+    main()
