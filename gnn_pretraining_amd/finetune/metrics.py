@@ -48,11 +48,76 @@ def compute_batch_metrics(domain_name: str, targets: Tensor, predictions: Tensor
     return m
 
 
+def metrics_from_counts(confusion, auc_counts, binary: bool, prefix: str) -> Dict[str, float]:
+    """The five scores of compute_batch_metrics and num_samples from integer counts alone, in float64 on the host (no GPU, no scikit-learn):
+    confusion [C, C] with [t, p] = rows of target t predicted p, auc_counts [C, 4] = (n_pos, n_neg, n_greater, n_equal) per class
+    (ops.cls_counts).  What the scikit-learn calls compute, spelled out:
+      accuracy                trace / n
+      precision, recall, f1   tp / (tp + fp), tp / (tp + fn), 2 tp / (2 tp + fp + fn), each 0 where its denominator is 0 (zero_division=0);
+                              binary: of label 1; otherwise the unweighted mean over the labels that occur as a target or as a prediction
+                              (average="macro" over scikit-learn's union of y_true and y_pred)
+      auc                     per class (n_greater + n_equal / 2) / (n_pos n_neg), the pair-count form of the area under the ROC curve;
+                              binary: of class 1, 0.0 with fewer than two distinct targets; otherwise the mean over all C classes, 0.0 when
+                              a class has no target (roc_auc_score raises there and compute_batch_metrics reports 0.0)"""
+    conf = np.asarray(confusion, dtype=np.int64)
+    auc = np.asarray(auc_counts, dtype=np.int64).reshape(-1, 4)
+    c = conf.shape[0]
+    if conf.shape != (c, c) or auc.shape != (c, 4):
+        raise ValueError(f"metrics_from_counts: confusion {conf.shape}, auc_counts {auc.shape}")
+    support, predicted, tp = conf.sum(axis=1), conf.sum(axis=0), np.diag(conf)
+    n = int(conf.sum())
+    if n == 0:
+        raise ValueError("metrics_from_counts: no samples")
+    labels = [1] if binary else [k for k in range(c) if support[k] > 0 or predicted[k] > 0]
+
+    def mean_ratio(num, den) -> float:
+        return float(np.mean([int(num[k]) / int(den[k]) if den[k] > 0 else 0.0 for k in labels]))
+
+    m = {f"{prefix}/accuracy": int(tp.sum()) / n,
+         f"{prefix}/f1": mean_ratio(2 * tp, support + predicted),              # 2 tp + fp + fn = support + predicted
+         f"{prefix}/precision": mean_ratio(tp, predicted),
+         f"{prefix}/recall": mean_ratio(tp, support)}
+    classes = [1] if binary else list(range(c))
+    if int((support > 0).sum()) < 2 or any(support[k] == 0 for k in classes):
+        m[f"{prefix}/auc"] = 0.0
+    else:
+        m[f"{prefix}/auc"] = float(np.mean([(int(auc[k, 2]) + 0.5 * int(auc[k, 3])) / (int(auc[k, 0]) * int(auc[k, 1])) for k in classes]))
+    m["num_samples"] = n
+    return m
+
+
+def compute_batch_metrics_device(domain_name: str, targets: Tensor, predictions: Tensor, probabilities: Tensor, loss: Tensor,
+                                 prefix: str) -> Dict[str, float]:
+    """compute_batch_metrics with the counting on the GPU (ops.cls_counts: csrc/cls_metrics.hip): the same keys and values from one
+    read-back of C C + 4 C + 1 integers (and the loss) and metrics_from_counts, with no copy of the inputs and no scikit-learn.
+    targets / predictions int64 [n] and probabilities fp32 [n, C] on the GPU, 1 <= n <= ops.CLS_MAX_ROWS (the pair count behind the AUC
+    is n^2 compares).  Raises ValueError when n is outside that range or a row has a target or prediction outside [0, C) or a non-finite
+    probability.  One difference on purpose: roc_auc_score refuses multi-class rows that do not sum to 1 (reported as auc 0.0); the
+    counts do not look at row sums -- the callers pass a softmax."""
+    from .. import ops
+    n, c = int(targets.numel()), int(probabilities.size(1))
+    if not 1 <= n <= ops.CLS_MAX_ROWS:
+        raise ValueError(f"compute_batch_metrics_device: {n} rows (1 <= n <= {ops.CLS_MAX_ROWS}: the AUC pair count is n^2 compares)")
+    buf = ops.cls_counts_packed(targets.detach().contiguous(), predictions.detach().contiguous(), probabilities.detach().contiguous())
+    host = buf.cpu().numpy()                                                    # the one read-back
+    k = c * c + 4 * c
+    counts, status = host[:2 * k].view(np.int64), int(host[2 * k])
+    if status != 0:
+        raise ValueError(f"compute_batch_metrics_device: {status} of {n} rows have a target or prediction outside [0, {c}) "
+                         "or a non-finite probability")
+    m = metrics_from_counts(counts[:c * c].reshape(c, c), counts[c * c:].reshape(c, 4), NUM_CLASSES[domain_name] == 2, prefix)
+    m.pop("num_samples")
+    m[f"{prefix}/loss"] = float(loss.item())
+    m["num_samples"] = n
+    return m
+
+
 def compute_training_metrics(epoch: int, step: int, loss: Tensor, optimizer: torch.optim.Optimizer, domain_name: str,
                              targets: Tensor, predictions: Tensor, probabilities: Tensor, step_start_time: float,
-                             model: torch.nn.Module) -> Dict[str, float]:
-    """metrics.py:85-118"""
-    m = compute_batch_metrics(domain_name, targets, predictions, probabilities, loss, "train")
+                             model: torch.nn.Module, device_metrics: bool = False) -> Dict[str, float]:
+    """metrics.py:85-118 (device_metrics: the batch scores from compute_batch_metrics_device)"""
+    batch_metrics = compute_batch_metrics_device if device_metrics else compute_batch_metrics
+    m = batch_metrics(domain_name, targets, predictions, probabilities, loss, "train")
     for pg in optimizer.param_groups:
         m[f'train/lr/{pg["name"]}'] = pg["lr"]
     sq = [p.grad.detach().pow(2).sum() for p in model.parameters() if p.grad is not None and p.requires_grad]

@@ -1002,6 +1002,39 @@ def lp_topk(h: Tensor, src: Tensor, k: int, w0: Tensor, b0: Tensor, w3: Tensor, 
     return idx, logit
 
 
+CLS_MAX_ROWS, CLS_MAX_CLASSES = 262144, 32        # gmp_cls_counts: the pair count is n^2 compares (gnnmp.h)
+
+
+def cls_counts_packed(targets: Tensor, predictions: Tensor, probabilities: Tensor) -> Tensor:
+    """gmp_cls_counts into ONE int32 device buffer of 2 (C C + 4 C) + 1 words, so that a caller reads everything back with one copy: words
+    [0, 2 C C) are confusion as int64, the next 8 C auc_counts as int64, the last word is status (cls_counts gives the three views)."""
+    _need(targets, torch.int64, "targets", 1); _need(predictions, torch.int64, "predictions", 1)
+    _need(probabilities, torch.float32, "probabilities", 2)
+    n, c, dev, l = targets.numel(), probabilities.size(1), targets.device, L.lib()
+    if predictions.numel() != n or probabilities.size(0) != n:
+        raise L.GnnmpError(f"cls_counts: {n} targets, {predictions.numel()} predictions, probabilities {tuple(probabilities.shape)}")
+    if predictions.device != dev or probabilities.device != dev:
+        raise L.GnnmpError("cls_counts: the three inputs must be on one device")
+    buf = torch.empty(2 * (c * c + 4 * c) + 1, dtype=torch.int32, device=dev)
+    ws = _ws(l.gmp_cls_counts_workspace_bytes(n, c), dev)
+    base = buf.data_ptr()
+    L.check(l.gmp_cls_counts(_ptr(targets), _ptr(predictions), _ptr(probabilities), n, c, C.c_void_p(base), C.c_void_p(base + 8 * c * c),
+                             C.c_void_p(base + 8 * (c * c + 4 * c)), _ptr(ws), ws.numel(), _stream(targets)), "gmp_cls_counts")
+    return buf
+
+
+def cls_counts(targets: Tensor, predictions: Tensor, probabilities: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+    """The integer counts behind the classification metrics (gnnmp.h gmp_cls_counts), as device tensors: (confusion [C, C] int64 with
+    [t, p] = rows of target t predicted p, auc_counts [C, 4] int64 = (n_pos, n_neg, n_greater, n_equal) per class, status [1] int32 =
+    rows left out for a target / prediction outside [0, C) or a non-finite probability).  targets, predictions int64 [n],
+    probabilities fp32 [n, C] contiguous; 1 <= n <= CLS_MAX_ROWS, 2 <= C <= CLS_MAX_CLASSES."""
+    buf = cls_counts_packed(targets, predictions, probabilities)
+    c = probabilities.size(1)
+    k = c * c + 4 * c
+    wide = buf[:2 * k].view(torch.int64)
+    return wide[:c * c].view(c, c), wide[c * c:].view(c, 4), buf[2 * k:]
+
+
 def gc_head_fwd(h: Tensor, ptr: Tensor, w0: Tensor, b0: Tensor, w3: Tensor, b3: Tensor, target: Tensor, g_scale: Tensor, p: float = 0.0,
                 seed: int = 0, site: int = 0) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
     """The fused graph-classification head up to the loss (gnnmp.h gmp_gc_head_fwd): h [N, 256] (rows contiguous, any leading dimension),

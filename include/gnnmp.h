@@ -324,6 +324,24 @@ int gmp_lp_topk(const float* h, const int64_t* src, int64_t num_nodes, int64_t n
                 gmp_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
+ * Integer counts for the classification metrics of fine-tuning (src/finetune/metrics.py:39-82: accuracy, F1, precision, recall and the
+ * one-vs-rest ROC AUC of scikit-learn), from targets [n] int64, predictions [n] int64 and probabilities [n, classes] fp32 contiguous:
+ *   confusion  int64 [classes * classes]  entry [t * classes + p] = rows with target t and prediction p
+ *   auc_counts int64 [classes * 4]        per class c: n_pos (rows with target c), n_neg (rows with another target), and over the pairs
+ *                                         (i, j) with target[i] == c != target[j]: n_greater = how many have prob[i, c] > prob[j, c],
+ *                                         n_equal = how many compare equal (AUC_c = (n_greater + n_equal / 2) / (n_pos n_neg))
+ *   status     int32 [1]                  rows with a target or prediction outside [0, classes) or a non-finite probability; such rows
+ *                                         are left out of every count
+ * The outputs are zeroed inside the call.  All sums are integer: the result does not depend on the block order.  The pair count is
+ * exhaustive, n^2 compares whatever `classes` is, hence 1 <= n <= 262144; 2 <= classes <= 32.  GMP_ERR_ARG outside those ranges,
+ * GMP_ERR_WORKSPACE when workspace_bytes < gmp_cls_counts_workspace_bytes(n, classes) (one int32 per row); nothing is launched then.
+ * ------------------------------------------------------------------------- */
+size_t gmp_cls_counts_workspace_bytes(int64_t n, int classes);
+int gmp_cls_counts(const int64_t* targets, const int64_t* predictions, const float* probabilities, int64_t n, int classes,
+                   int64_t* confusion, int64_t* auc_counts, int32_t* status, void* workspace, size_t workspace_bytes,
+                   gmp_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
  * The fused graph-classification head of fine-tuning (finetune_model.py:68-80, finetune.py:110-114) over one batch of
  * num_graphs graphs; graph b owns the rows ptr[b] .. ptr[b+1] of h (ptr: device int32 [num_graphs + 1]):
  *   pooled[b] = mean of the graph's rows, divisor max(count, 1) (gmp_segment_sum(mean = 1); an empty graph pools to zero),
