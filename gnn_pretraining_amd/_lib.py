@@ -116,6 +116,8 @@ _SIGS: Dict[str, tuple] = {
     "gmp_lp_topk": (C.c_int, [p, p, i64, i64, i32, i32, i32, p, p, p, p, p, p, i64, p, p, p, sz, p]),
     "gmp_cls_counts_workspace_bytes": (sz, [i64, i32]),
     "gmp_cls_counts": (C.c_int, [p, p, p, i64, i32, p, p, p, p, sz, p]),
+    "gmp_graph_props_workspace_bytes": (sz, [i32, i64]),
+    "gmp_graph_props": (C.c_int, [p, p, p, i64, i64, i32, i64, p, p, p, sz, p]),
     "gmp_gc_head_fwd_workspace_bytes": (sz, [i64]),
     "gmp_gc_head_fwd": (C.c_int, [p, i64, p, i64, i64, i32, i32, i32, p, p, p, p, p, p, p, p, p, p, p, f32, C.c_uint64, C.c_uint32, p, sz, p]),
     "gmp_gc_head_bwd": (C.c_int, [p, i64, i64, i32, i32, i32, p, p, p, p, p, f32, C.c_uint64, C.c_uint32, p, p, p, p, p, i64, p]),

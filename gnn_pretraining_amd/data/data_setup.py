@@ -81,8 +81,9 @@ def standardize_clip_features(store: GraphStore, train_idx: np.ndarray) -> None:
     store.x = torch.from_numpy(np.clip(standardize(x, rows), MIN_SCALE, MAX_SCALE)).to(store.x.dtype)
 
 
-def process_tu_store(name: str, store: GraphStore, root: Optional[Path] = None) -> Dict[str, Tensor]:
-    """process_tudatasets (:75-127) for one dataset whose raw graphs are already in `store`."""
+def process_tu_store(name: str, store: GraphStore, root: Optional[Path] = None, device_properties: bool = False) -> Dict[str, Tensor]:
+    """process_tudatasets (:75-127) for one dataset whose raw graphs are already in `store`.  device_properties: the graph-property
+    targets come from the GPU (GraphPropertyCalculator.compute_for_dataset(device="cuda")) instead of the per-graph host loop."""
     needs_pretrain, needs_downstream = name in PRETRAIN_TUDATASETS, name in DOWNSTREAM_TUDATASETS
     if needs_downstream:
         splits = downstream_splits(store.y.numpy())
@@ -92,7 +93,8 @@ def process_tu_store(name: str, store: GraphStore, root: Optional[Path] = None) 
         splits = pretrain_only_splits(len(store))
     if needs_pretrain:
         graphs = [store.graph(i) for i in range(len(store))]
-        store.graph_properties = GraphPropertyCalculator().compute_and_standardize_for_dataset(graphs, splits["train"].numpy())
+        store.graph_properties = GraphPropertyCalculator().compute_and_standardize_for_dataset(graphs, splits["train"].numpy(),
+                                                                                                device="cuda" if device_properties else None)
     store.save(processed_dir(name, root))
     save_splits(processed_dir(name, root), splits)
     return splits
@@ -187,11 +189,11 @@ def synthetic_planetoid(name: str, gen: torch.Generator, num_nodes: Optional[int
     return GraphStore.from_data_list([g]), splits
 
 
-def process_synthetic(root: Optional[Path] = None, seed: int = RANDOM_SEED, scale: float = 1.0) -> None:
+def process_synthetic(root: Optional[Path] = None, seed: int = RANDOM_SEED, scale: float = 1.0, device_properties: bool = False) -> None:
     gen = torch.Generator()
     gen.manual_seed(seed)
     for name in TUDATASETS:
-        process_tu_store(name, synthetic_tu_store(name, gen, max(120, int(TU_STATS[name][0] * scale))), root)
+        process_tu_store(name, synthetic_tu_store(name, gen, max(120, int(TU_STATS[name][0] * scale))), root, device_properties)
     for name in PLANETOID_DATASETS:
         store, splits = synthetic_planetoid(name, gen, None if scale >= 1.0 else max(200, int(PLANETOID_STATS[name][0] * scale)))
         process_planetoid_store(name, store, splits, root)
@@ -210,8 +212,10 @@ def main() -> None:
     p = argparse.ArgumentParser(description="write data/processed/* (synthetic stand-ins; there is no network)")
     p.add_argument("--root", type=str, default=None)
     p.add_argument("--scale", type=float, default=1.0, help="fraction of the public dataset sizes to generate")
+    p.add_argument("--device-properties", action="store_true",
+                   help="compute the graph-property targets on the GPU (csrc/graph_props.hip) instead of one graph at a time on the host")
     a = p.parse_args()
-    process_synthetic(Path(a.root) if a.root else None, scale=a.scale)
+    process_synthetic(Path(a.root) if a.root else None, scale=a.scale, device_properties=a.device_properties)
     print(f"wrote {Path(a.root) if a.root else PROCESSED_DIR}")
 
 

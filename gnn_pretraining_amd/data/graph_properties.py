@@ -4,7 +4,10 @@ sparse adjacency with numpy / scipy instead of a networkx object per graph.
 Order (graph_properties.py:62-75): N, E, density, mean degree, degree variance, max degree, average clustering,
 transitivity, #components, diameter of the largest component, degree assortativity, degree centralisation -- on the
 simple undirected graph (self loops removed, both directions merged, graph_properties.py:21-24).
-tests/test_data.py holds this against oracle/graph_properties.py (the networkx restatement of the reference)."""
+tests/test_data.py holds this against oracle/graph_properties.py (the networkx restatement of the reference).
+
+compute_for_dataset(..., device=...) makes the same targets for whole batches on the GPU: ops.graph_properties (csrc/graph_props.hip)
+returns exact integer counts per graph and properties_from_counts finishes them here, in the integer form of the formulas below."""
 from __future__ import annotations
 
 import math
@@ -19,6 +22,7 @@ from torch import Tensor
 from ..graph import Data
 
 GRAPH_PROPERTY_DIM = 12
+DEVICE_CHUNK_NODES = 65536      # nodes per collated chunk of compute_for_dataset(device=...): one launch and one read-back each
 
 
 def _simple_adjacency(edge_index: np.ndarray, n: int) -> sp.csr_matrix:
@@ -76,16 +80,74 @@ class GraphPropertyCalculator:
         return torch.tensor([float(n), e, density, deg_mean, deg_var, deg_max, clustering, transitivity, float(ncomp),
                              diameter, assort, central], dtype=torch.float32)
 
-    def compute_for_dataset(self, dataset_list: Sequence[Data]) -> Tensor:
+    def compute_for_dataset(self, dataset_list: Sequence[Data], device=None) -> Tensor:
+        """device=None: one graph at a time on the host.  With a device: the graphs are collated in chunks of at most
+        DEVICE_CHUNK_NODES nodes (a graph larger than that is a chunk of its own), one ops.graph_properties launch and one read-back of
+        [B, 16] integers per chunk, properties_from_counts on the host.  A graph the kernel refuses (status bit 0: more than 1024
+        nodes) is recomputed by __call__; an edge endpoint outside its graph raises."""
         out = torch.zeros((len(dataset_list), GRAPH_PROPERTY_DIM), dtype=torch.float32)
+        if device is not None:
+            return self._compute_on_device(dataset_list, torch.device(device), out)
         for i, g in enumerate(dataset_list):
             out[i] = self(g)
         return out
 
-    def compute_and_standardize_for_dataset(self, dataset_list: Sequence[Data], train_idx: np.ndarray) -> Tensor:
-        """graph_properties.py:88-96: StandardScaler fitted on the train split (population std; zero scale -> 1)."""
-        props = self.compute_for_dataset(dataset_list).numpy().astype(np.float64)
+    def _compute_on_device(self, dataset_list: Sequence[Data], device: torch.device, out: Tensor) -> Tensor:
+        from .. import ops
+        start, total = 0, len(dataset_list)
+        while start < total:
+            stop, nodes = start, 0
+            while stop < total and (stop == start or nodes + int(dataset_list[stop].num_nodes) <= DEVICE_CHUNK_NODES):
+                nodes += int(dataset_list[stop].num_nodes)
+                stop += 1
+            chunk = dataset_list[start:stop]
+            sizes = np.array([int(g.num_nodes) for g in chunk], dtype=np.int64)
+            esizes = np.array([int(g.edge_index.size(1)) for g in chunk], dtype=np.int64)
+            ptr = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+            eptr = np.concatenate([[0], np.cumsum(esizes)]).astype(np.int64)
+            ei = torch.cat([g.edge_index.cpu().to(torch.int64) + int(o) for g, o in zip(chunk, ptr[:-1])], dim=1).contiguous()
+            counts, csum = ops.graph_properties(torch.from_numpy(ptr).to(device), torch.from_numpy(eptr).to(device), ei.to(device),
+                                                max_graph_nodes=int(sizes.max()))
+            counts, csum = counts.cpu(), csum.cpu()
+            out[start:stop] = properties_from_counts(counts, csum)
+            status = counts[:, 12].tolist()
+            for k, st in enumerate(status):
+                if st >> 8:
+                    raise ValueError(f"graph {start + k}: {st >> 8} edge endpoint(s) outside its {int(sizes[k])} nodes")
+                if st & 1:
+                    out[start + k] = self(chunk[k])
+            start = stop
+        return out
+
+    def compute_and_standardize_for_dataset(self, dataset_list: Sequence[Data], train_idx: np.ndarray, device=None) -> Tensor:
+        """graph_properties.py:88-96: StandardScaler fitted on the train split (population std; zero scale -> 1).  Always on the host in
+        fp64; `device` only selects where compute_for_dataset makes the raw targets."""
+        props = self.compute_for_dataset(dataset_list, device).numpy().astype(np.float64)
         return torch.from_numpy(standardize(props, np.asarray(train_idx))).float()
+
+
+def properties_from_counts(counts, clustering_sum) -> Tensor:
+    """The 12 targets, float32 [B, 12], from the read-back of ops.graph_properties (counts int64 [B, 16] in the slot order of gnnmp.h
+    gmp_graph_props, clustering_sum float64 [B]); host tensors, arrays or nested lists.  Python integers throughout (no overflow), one
+    correctly rounded division per value, and the guards of GraphPropertyCalculator.__call__.  A row whose status bit 0 is set (the
+    kernel refused the graph) comes out as zeros: the caller recomputes it."""
+    rows = counts.tolist() if hasattr(counts, "tolist") else [list(r) for r in counts]
+    csum = clustering_sum.tolist() if hasattr(clustering_sum, "tolist") else list(clustering_sum)
+    out = np.zeros((len(rows), GRAPH_PROPERTY_DIM), dtype=np.float64)
+    for i, row in enumerate(rows):
+        n, e, dmax, s1, s2, t2, pr, ncomp, diam, sxy, sx, sxx, status = (int(v) for v in row[:13])
+        if status & 1 or n == 0:
+            continue
+        density = 0.0 if (n <= 1 or e == 0) else 2 * e / (n * (n - 1))
+        var_num = n * s2 - s1 * s1
+        transitivity = t2 / pr if (n > 2 and t2 > 0) else 0.0
+        m = 2 * e
+        assort = 0.0
+        if var_num != 0 and e != 0 and m * sxx != sx * sx:
+            assort = (m * sxy - sx * sx) / (m * sxx - sx * sx)
+        central = (n * dmax - s1) / ((n - 1) * (n - 2)) if n > 2 else 0.0
+        out[i] = [n, e, density, s1 / n, var_num / (n * n), dmax, float(csum[i]) / n, transitivity, ncomp, diam, assort, central]
+    return torch.from_numpy(out).to(torch.float32)
 
 
 def standardize(values: np.ndarray, fit_rows: np.ndarray) -> np.ndarray:

@@ -1035,6 +1035,33 @@ def cls_counts(targets: Tensor, predictions: Tensor, probabilities: Tensor) -> T
     return wide[:c * c].view(c, c), wide[c * c:].view(c, 4), buf[2 * k:]
 
 
+GRAPH_PROPS_SLOTS, GRAPH_PROPS_MAX_NODES = 16, 1024        # gmp_graph_props: counts per graph, largest graph the kernel takes (gnnmp.h)
+
+
+def graph_properties(ptr: Tensor, eptr: Tensor, edge_index: Tensor, max_graph_nodes: Optional[int] = None) -> Tuple[Tensor, Tensor]:
+    """The integer counts behind the 12 graph-property targets of a batch (gnnmp.h gmp_graph_props; the slot table is there): ptr int64
+    [B + 1] node offsets, eptr int64 [B + 1] edge offsets, edge_index int64 [2, E] batch-global ids grouped by graph.  Returns (counts
+    int64 [B, 16], clustering_sum float64 [B]) on the device; data.graph_properties.properties_from_counts turns them into the targets.
+    Both start as zeros, so a graph the kernel refuses (status bit 0: more than GRAPH_PROPS_MAX_NODES nodes) reads as zeros with slot 12
+    = 1.  max_graph_nodes: the largest ptr[g + 1] - ptr[g] when the caller knows it (None reads it back from ptr, one synchronisation)."""
+    _need(ptr, torch.int64, "ptr", 1); _need(eptr, torch.int64, "eptr", 1); _need(edge_index, torch.int64, "edge_index", 2)
+    B, dev = ptr.numel() - 1, ptr.device
+    if B < 0 or eptr.numel() != B + 1 or edge_index.size(0) != 2:
+        raise L.GnnmpError(f"graph_properties: ptr {tuple(ptr.shape)}, eptr {tuple(eptr.shape)}, edge_index {tuple(edge_index.shape)}")
+    if eptr.device != dev or edge_index.device != dev:
+        raise L.GnnmpError("graph_properties: the three inputs must be on one device")
+    counts = torch.zeros(B, GRAPH_PROPS_SLOTS, dtype=torch.int64, device=dev)
+    csum = torch.zeros(B, dtype=torch.float64, device=dev)
+    if B == 0:
+        return counts, csum
+    if max_graph_nodes is None:
+        max_graph_nodes = max(int((ptr[1:] - ptr[:-1]).max()), 0)
+    E = edge_index.size(1)
+    L.check(L.lib().gmp_graph_props(_ptr(ptr), _ptr(eptr), _ptr(edge_index) if E else None, 0, E, B, int(max_graph_nodes), _ptr(counts),
+                                    _ptr(csum), None, 0, _stream(ptr)), "gmp_graph_props")
+    return counts, csum
+
+
 def gc_head_fwd(h: Tensor, ptr: Tensor, w0: Tensor, b0: Tensor, w3: Tensor, b3: Tensor, target: Tensor, g_scale: Tensor, p: float = 0.0,
                 seed: int = 0, site: int = 0) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
     """The fused graph-classification head up to the loss (gnnmp.h gmp_gc_head_fwd): h [N, 256] (rows contiguous, any leading dimension),

@@ -342,6 +342,43 @@ int gmp_cls_counts(const int64_t* targets, const int64_t* predictions, const flo
                    gmp_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
+ * Integer counts behind the 12 structural targets of the graph-property task (src/data/graph_properties.py:17-96) for a batch of
+ * num_graphs graphs, one workgroup per graph.  The batch is described as for gmp_aug_two_views: ptr int64 [num_graphs + 1] node
+ * offsets, eptr int64 [num_graphs + 1] edge offsets, edge_index int64 [2, num_edges] with batch-global ids, grouped by graph.  The
+ * targets are those of the SIMPLE UNDIRECTED graph: self loops are dropped, duplicate and mirrored entries merge, in any order.
+ * An entry with an endpoint outside its own graph's [ptr[g], ptr[g+1]) is dropped and never dereferenced; every such endpoint is
+ * counted in the graph's status word.  eptr is clamped into [0, num_edges].  num_nodes is checked for its sign only (node ids are
+ * held against ptr, which lives on the device; a caller that does not know the total may pass 0).
+ * counts int64 [num_graphs, 16], per graph:
+ *    0  n
+ *    1  E, simple undirected edges = (sum of deg) / 2
+ *    2  max degree
+ *    3  sum of deg
+ *    4  sum of deg^2
+ *    5  T2 = sum over v of t2[v], t2[v] = sum over u in N(v) of |N(v) & N(u)| (= 2 x triangles through v)
+ *    6  Pr = sum of deg (deg - 1)
+ *    7  number of connected components
+ *    8  diameter of the largest component (ties in size: the component holding the smallest node id); 0 if its size <= 1
+ *    9  Sxy = sum over directed adjacency entries (u, v) of deg(u) deg(v)
+ *   10  Sx  = sum over directed entries of deg(u)   (= sum of deg^2)
+ *   11  Sxx = sum over directed entries of deg(u)^2 (= sum of deg^3)
+ *   12  status: bit 0 = the graph is too large for the kernel (n > min(max_graph_nodes, 1024), or ptr decreasing); bits 8.. = the
+ *       number of dropped endpoints (saturating at 2^54 - 1)
+ *   13-15  reserved, written as 0
+ * clustering_sum double [num_graphs]: sum over the nodes with deg >= 2 of t2[v] / (deg(v) (deg(v) - 1)), each term one fp64 division
+ * of integers, added in ascending node order by a fixed tree (no float atomic): bitwise reproducible.
+ * A graph with status bit 0 set gets ONLY slot 12 written (= 1): its other slots and its clustering_sum keep what the caller left
+ * there.  n = 0 and n = 1 are valid (all sums 0, components = n).  max_graph_nodes is the caller's bound on ptr[g+1] - ptr[g]; it
+ * selects the launch (n <= 256: an 8 KB bit matrix; n <= 1024: 128 KB, one workgroup per CU) and sizes the LDS.  Needs no workspace
+ * (gmp_graph_props_workspace_bytes is 0; workspace may be NULL).  num_graphs == 0 is a no-op; GMP_ERR_ARG on a negative size or a
+ * null pointer, before any launch.  All integer sums are order-independent.
+ * ------------------------------------------------------------------------- */
+size_t gmp_graph_props_workspace_bytes(int num_graphs, int64_t max_graph_nodes);
+int gmp_graph_props(const int64_t* ptr, const int64_t* eptr, const int64_t* edge_index, int64_t num_nodes, int64_t num_edges,
+                    int num_graphs, int64_t max_graph_nodes, int64_t* counts /* [B,16] */, double* clustering_sum /* [B] */,
+                    void* workspace, size_t workspace_bytes, gmp_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
  * The fused graph-classification head of fine-tuning (finetune_model.py:68-80, finetune.py:110-114) over one batch of
  * num_graphs graphs; graph b owns the rows ptr[b] .. ptr[b+1] of h (ptr: device int32 [num_graphs + 1]):
  *   pooled[b] = mean of the graph's rows, divisor max(count, 1) (gmp_segment_sum(mean = 1); an empty graph pools to zero),
