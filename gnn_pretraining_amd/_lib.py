@@ -106,6 +106,10 @@ _SIGS: Dict[str, tuple] = {
                              C.POINTER(BnConfig), p, sz, p]),
     "gmp_lp_edge_features_fwd": (C.c_int, [p, p, p, i64, i64, i32, p]),
     "gmp_lp_edge_features_bwd": (C.c_int, [p, p, p, p, p, i64, i64, i32, p]),
+    "gmp_lp_feat_gemm_bwd_fold": (C.c_int, [p, p, p, p, p, p, i64, i64, i32, p]),
+    "gmp_lp_feat_gemm_fwd": (C.c_int, [p, p, p, p, p, i64, i64, i32, p]),
+    "gmp_lp_feat_gemm_wgrad": (C.c_int, [p, p, p, p, p, i64, i64, i32, p, sz, p]),
+    "gmp_lp_feat_gemm_launch_count": (C.c_uint64, []),
     "gmp_lp_score_fwd_workspace_bytes": (sz, [i64]),
     "gmp_lp_score_bwd_workspace_bytes": (sz, [i64]),
     "gmp_lp_score_fwd": (C.c_int, [p, p, p, i64, i64, i32, i32, p, p, p, p, p, p, f32, C.c_uint64, C.c_uint32, p, sz, p]),

@@ -154,6 +154,11 @@ struct GemmArgs {
     const float* shift;
     const float* resid;
     int64_t ldr;
+    // generated operand (the GEN instances of gemm_pipe_kernel only): the link-prediction edge features of node rows h [gen_N, 256] over the
+    // pair list gen_edges [2, gen_K] stand in for A (NT) or B (TN), which is then never dereferenced
+    const float* gen_h;
+    const int64_t* gen_edges;
+    int64_t gen_N, gen_K;
 };
 
 thread_local int* t_sig_flag = nullptr;
@@ -470,6 +475,22 @@ int launch_pipe_cfg(const GemmArgs& g, int tiles_m, int tiles_n, int z, hipStrea
     return gmp::check_launch("gemm_pipe_kernel");
 }
 
+// the generated-operand instances (64 x 64 tile, 4 stages: the step's default, and the accumulation order is the same for every tile)
+template <bool KC, int GEN>
+int launch_pipe_gen(const GemmArgs& g, int64_t rows, int z, hipStream_t st) {
+    using C = g2::Cfg<1, 1, KC, KC, 4, 4>;
+    auto kern = g2::gemm_pipe_kernel<1, 1, KC, KC, 4, 4, false, GEN>;
+    static std::atomic<uint64_t> attr_set{0};
+    if (!gmp::lds_attr_done(attr_set)) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES) != hipSuccess)
+            return gmp::fail(GMP_ERR_LAUNCH, "gemm_pipe (generated operand): cannot reserve %d bytes of LDS", C::LDS_BYTES);
+        gmp::lds_attr_mark(attr_set);
+    }
+    const int tiles_m = (int)((rows + 63) / 64), tiles_n = (int)((g.N + 63) / 64);
+    hipLaunchKernelGGL(kern, dim3((unsigned)(tiles_m * tiles_n), 1, (unsigned)z), dim3(g2::THREADS), C::LDS_BYTES, st, g, tiles_m, tiles_n);
+    return gmp::check_launch("gemm_pipe_kernel (generated operand)");
+}
+
 // LDS ring depth: 4 stages everywhere (128x128: 4 x 32 KB, one block per CU; 64x64: 4 x 16 KB, two blocks per CU).  A 3-stage 64x64
 // ring (three blocks per CU) is 1 us faster alone and slower inside the step (1.53 against 1.45 ms): GMP_GEMM_PIPE_STAGES=3.
 // Round 3, GMP_GEMM_PIPE_STAGES=32: the 3-stage schedule on TWO buffers (gemm_pipe.h "early free": 32 KB, four blocks per CU, all 928
@@ -534,6 +555,13 @@ bool pipe_ok(int mode, const GemmArgs& g) {
     if (mode == GMP_GEMM_NT) return g.K >= 64 && g.K % g2::BK == 0;
     if (mode == GMP_GEMM_NN) return g.K >= 64 && g.K % g2::BK == 0 && g.N % 4 == 0 && g.N >= 4;
     return g.M % 4 == 0 && g.M >= 4 && g.N % 4 == 0 && g.N >= 4;
+}
+
+// THE rule by which gmp_gemm_f32 sends an NT / NN problem to the pipelined kernel (large row counts: the backbone's layer GEMMs, the
+// link-prediction scorer).  One predicate: gmp::lp_fold_applies asks it too, so the fused launch exists exactly where the GEMM it replaces
+// would have accumulated in the same order.
+inline bool takes_pipe(int mode, const GemmArgs& g) {
+    return mode != GMP_GEMM_TN && g.M >= pipe_min_rows() && g.N >= 64 && pipe_ok(mode, g) && (g.splitk == 1 || g.N % 4 == 0);   // (slices are stored as float4 rows of N)
 }
 
 }  // namespace
@@ -617,7 +645,7 @@ int gmp::gemm_f32_epilogue(int mode, const float* A, const float* B, const float
     if (g.splitk == 1) tile = t128 >= 4096 ? 2 : 0;     // measured on MI355X: 64x64 wins until the grid is many waves deep
     if (forced >= 0 && forced <= 2 && g.splitk == 1) tile = forced;
     // large row counts (the backbone's layer GEMMs, the link-prediction scorer): the LDS-DMA pipelined kernel
-    if (mode != GMP_GEMM_TN && M >= pipe_min_rows() && N >= 64 && pipe_ok(mode, g) && (g.splitk == 1 || N % 4 == 0)) {   // (slices are stored as float4 rows of N)
+    if (takes_pipe(mode, g)) {
         if (g.splitk == 1) return launch_pipe(mode, pipe_pick_tile(M, N, 1), g, M, 1, st);
         // few output tiles and a long K (the caller handed over a workspace): K-slices of the pipelined kernel, summed in slice order
         if (int rc = launch_pipe(mode, pipe_pick_tile(M, N, 1), g, M, g.splitk, st)) return rc;
@@ -642,12 +670,31 @@ int gmp::gemm_f32_epilogue(int mode, const float* A, const float* B, const float
     return GMP_OK;
 }
 
+namespace {
+struct GenOperand { const float* h; const int64_t* edges; int64_t N, K; };
+int grouped_impl(int mode, const float* A, const float* B, const float* bias, float* C, int groups, const int32_t* group_rows_host,
+                 const int64_t* b_off_host, const int64_t* bias_off_host, const int64_t* c_off_host, float* a_colsum,
+                 const int64_t* a_colsum_off_host, int64_t M_tn, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, float alpha,
+                 int accumulate, int relu, void* workspace, size_t workspace_bytes, gmp_stream_t stream, const GenOperand* gen);
+}  // namespace
+
 extern "C" int gmp_gemm_f32_grouped(int mode, const float* A, const float* B, const float* bias, float* C, int groups,
                                     const int32_t* group_rows_host, const int64_t* b_off_host,
                                     const int64_t* bias_off_host, const int64_t* c_off_host, float* a_colsum,
                                     const int64_t* a_colsum_off_host, int64_t M_tn, int64_t N, int64_t K, int64_t lda,
                                     int64_t ldb, int64_t ldc, float alpha, int accumulate, int relu, void* workspace,
                                     size_t workspace_bytes, gmp_stream_t stream) {
+    return grouped_impl(mode, A, B, bias, C, groups, group_rows_host, b_off_host, bias_off_host, c_off_host, a_colsum, a_colsum_off_host, M_tn, N, K,
+                        lda, ldb, ldc, alpha, accumulate, relu, workspace, workspace_bytes, stream, nullptr);
+}
+
+namespace {
+// gen: B of the TN form is the generated edge-feature matrix (gmp_lp_feat_gemm_wgrad); every choice below -- tile, row slices -- is made as for a
+// fetched B, so the slices and their order are the materialised call's
+int grouped_impl(int mode, const float* A, const float* B, const float* bias, float* C, int groups, const int32_t* group_rows_host,
+                 const int64_t* b_off_host, const int64_t* bias_off_host, const int64_t* c_off_host, float* a_colsum,
+                 const int64_t* a_colsum_off_host, int64_t M_tn, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, float alpha,
+                 int accumulate, int relu, void* workspace, size_t workspace_bytes, gmp_stream_t stream, const GenOperand* gen) {
     if (mode < 0 || mode > 2) return gmp::fail(GMP_ERR_ARG, "gemm_grouped: mode %d", mode);
     if (groups < 1 || groups > MAXG || !group_rows_host) return gmp::fail(GMP_ERR_ARG, "gemm_grouped: %d groups (max %d)", groups, MAXG);
     if (N <= 0 || K < 0 || !A || !B || !C) return gmp::fail(GMP_ERR_ARG, "gemm_grouped: bad argument");
@@ -707,12 +754,17 @@ extern "C" int gmp_gemm_f32_grouped(int mode, const float* A, const float* B, co
                 g.gpart = (float*)workspace;
                 g.gasum_part = g.gpart + (size_t)groups * best_split * g.M * N;
             }
-            if (int rc = launch_pipe(mode, best_tile, g, g.M, groups * best_split, st)) return rc;
+            if (gen) {
+                if (best_tile != 3) return gmp::fail(GMP_ERR_UNSUPPORTED, "gemm_grouped: the generated operand exists for the 64 x 64 tile only");
+                g.gen_h = gen->h; g.gen_edges = gen->edges; g.gen_N = gen->N; g.gen_K = gen->K;
+                if (int rc = launch_pipe_gen<false, 2>(g, g.M, groups * best_split, st)) return rc;
+            } else if (int rc = launch_pipe(mode, best_tile, g, g.M, groups * best_split, st)) return rc;
             if (best_split > 1) {
                 launch_grouped_reduce(g, groups, st);
             }
             return gmp::check_launch("gemm_pipe_kernel (grouped)");
         }
+        if (gen) return gmp::fail(GMP_ERR_ARG, "gemm_grouped: the generated operand needs the pipelined kernel (a workspace, 256 rows and more)");
         // few output tiles x long reductions: slice every group's rows over several blocks when a workspace is given
         const int64_t tiles = ((N + 63) / 64) * ((g.M + 63) / 64) * groups;
         int split = 1;
@@ -745,6 +797,102 @@ extern "C" int gmp_gemm_f32_grouped(int mode, const float* A, const float* B, co
                             !nofast_g2 && fast_ok<BK_DEFAULT>(mode, g, 1));
     }
     return gmp::check_launch("gemm_kernel (grouped)");
+}
+}  // namespace
+
+// ---- link-prediction head: g_hs / g_hd straight from gy1 W0 (gemm_pipe.h lp_bwd_fold_kernel) --------------------------------------
+// Applies where gmp_gemm_f32 sends gfeat = gy1 W0 ([K, 768], no workspace, hence no K-slices) to the pipelined kernel -- asked of the same
+// predicate on the same GemmArgs -- and the fold's own operands are 16-byte addressable.
+namespace {
+GemmArgs lp_gfeat_problem(const float* gy1, const float* w0, int64_t K, int F) {
+    GemmArgs g{gy1, w0, nullptr, nullptr, K, 3 * (int64_t)F, F, F, 3 * (int64_t)F, 3 * (int64_t)F, 1.f, 0, 0, 1, nullptr,
+               (F % 4 == 0) && aligned16(gy1), (F % 4 == 0) && aligned16(w0)};
+    return g;
+}
+}  // namespace
+
+bool gmp::lp_fold_applies(const float* gy1, const float* w0, const float* h, const float* g_hs, const float* g_hd, int64_t K, int F) {
+    return F == 256 && takes_pipe(GMP_GEMM_NN, lp_gfeat_problem(gy1, w0, K, F)) && aligned16(h) && aligned16(g_hs) && aligned16(g_hd);
+}
+
+// y1 = relu(feat W0^T + b0) and dW0 = gy1^T feat (+ db0) with feat generated inside the GEMMs' loaders: the GemmArgs of the materialised calls
+// (step.hip GMP_TASK_LP) with the generated operand in place of lp_feat, sent through the same dispatch
+namespace {
+std::atomic<uint64_t> g_lp_fold_launches{0};
+GemmArgs lp_y1_problem(const float* w0, const float* b0, float* y1, int64_t K, int F) {
+    GemmArgs g{w0 /* A is generated: any aligned pointer */, w0, b0, y1, K, F, 3 * (int64_t)F, 3 * (int64_t)F, 3 * (int64_t)F, F, 1.f, 0, 1, 1, nullptr,
+               1, aligned16(w0) ? 1 : 0};
+    g.vecC = aligned16(y1);
+    return g;
+}
+}  // namespace
+
+bool gmp::lp_feat_gemm_applies(const float* h, const float* w0, const float* b0, const float* y1, const float* gy1, const float* dW0,
+                               const void* workspace, int64_t K, int F) {
+    if (F != 256 || !workspace || !aligned16(h) || !aligned16(b0) || !aligned16(gy1) || !aligned16(dW0)) return false;
+    if (!takes_pipe(GMP_GEMM_NT, lp_y1_problem(w0, b0, const_cast<float*>(y1), K, F))) return false;
+    GemmArgs t{};          // the weight-gradient problem as gmp_gemm_f32_grouped sees it
+    t.vecA = t.vecB = 1; t.M = F; t.N = 3 * F;
+    return K >= pipe_min_rows() && pipe_ok(GMP_GEMM_TN, t);
+}
+
+extern "C" int gmp_lp_feat_gemm_fwd(const float* h, const int64_t* edges, const float* w0, const float* b0, float* y1, int64_t num_nodes,
+                                    int64_t K, int F, gmp_stream_t stream) {
+    if (F != 256) return gmp::fail(GMP_ERR_UNSUPPORTED, "lp_feat_gemm_fwd: feature width %d (256 only)", F);
+    if (num_nodes < 0 || !h || !edges || !w0 || !b0 || !y1) return gmp::fail(GMP_ERR_ARG, "lp_feat_gemm_fwd: bad argument");
+    if (K < pipe_min_rows() || K > INT32_MAX / 4)
+        return gmp::fail(GMP_ERR_ARG, "lp_feat_gemm_fwd: %lld pairs (the pipelined kernel takes %lld and more)", (long long)K, (long long)pipe_min_rows());
+    if (!aligned16(h) || !aligned16(w0) || !aligned16(b0) || !aligned16(y1))
+        return gmp::fail(GMP_ERR_ARG, "lp_feat_gemm_fwd: operands must be 16-byte aligned");
+    GemmArgs g = lp_y1_problem(w0, b0, y1, K, F);
+    take_signal(g);
+    g.gen_h = h; g.gen_edges = edges; g.gen_N = num_nodes; g.gen_K = K;
+    if (gmp::lane_takes((hipStream_t)stream)) g_lp_fold_launches.fetch_add(1, std::memory_order_relaxed);
+    return launch_pipe_gen<true, 1>(g, K, 1, (hipStream_t)stream);
+}
+
+extern "C" int gmp_lp_feat_gemm_wgrad(const float* gy1, const float* h, const int64_t* edges, float* dW0, float* db0, int64_t num_nodes, int64_t K,
+                                      int F, void* workspace, size_t workspace_bytes, gmp_stream_t stream) {
+    if (F != 256) return gmp::fail(GMP_ERR_UNSUPPORTED, "lp_feat_gemm_wgrad: feature width %d (256 only)", F);
+    if (num_nodes < 0 || !gy1 || !h || !edges || !dW0) return gmp::fail(GMP_ERR_ARG, "lp_feat_gemm_wgrad: bad argument");
+    if (K < pipe_min_rows() || K > INT32_MAX / 4)
+        return gmp::fail(GMP_ERR_ARG, "lp_feat_gemm_wgrad: %lld pairs (the pipelined kernel takes %lld and more)", (long long)K, (long long)pipe_min_rows());
+    if (!aligned16(gy1) || !aligned16(h) || !aligned16(dW0)) return gmp::fail(GMP_ERR_ARG, "lp_feat_gemm_wgrad: operands must be 16-byte aligned");
+    if (!workspace) return gmp::fail(GMP_ERR_WORKSPACE, "lp_feat_gemm_wgrad: a workspace is required (without one the materialised GEMM does not run the pipelined kernel)");
+    const int32_t rows[2] = {0, (int32_t)K};
+    const int64_t zero[1] = {0};
+    const GenOperand gen{h, edges, num_nodes, K};
+    if (gmp::lane_takes((hipStream_t)stream)) g_lp_fold_launches.fetch_add(1, std::memory_order_relaxed);
+    return grouped_impl(GMP_GEMM_TN, gy1, h /* B is generated: any aligned pointer */, nullptr, dW0, 1, rows, nullptr, nullptr, zero, db0, zero, F, 3 * (int64_t)F, 0, F,
+                        3 * (int64_t)F, 3 * (int64_t)F, 1.f, 0, 0, workspace, workspace_bytes, stream, &gen);
+}
+
+extern "C" uint64_t gmp_lp_feat_gemm_launch_count(void) { return g_lp_fold_launches.load(std::memory_order_relaxed); }
+
+extern "C" int gmp_lp_feat_gemm_bwd_fold(const float* gy1, const float* w0, const float* h, const int64_t* edges, float* g_hs, float* g_hd,
+                                         int64_t num_nodes, int64_t K, int F, gmp_stream_t stream) {
+    if (F != 256) return gmp::fail(GMP_ERR_UNSUPPORTED, "lp_feat_gemm_bwd_fold: feature width %d (256 only)", F);
+    if (num_nodes < 0 || !gy1 || !w0 || !h || !edges || !g_hs || !g_hd) return gmp::fail(GMP_ERR_ARG, "lp_feat_gemm_bwd_fold: bad argument");
+    if (K < pipe_min_rows() || K > INT32_MAX / 4)
+        return gmp::fail(GMP_ERR_ARG, "lp_feat_gemm_bwd_fold: %lld pairs (the pipelined kernel takes %lld and more)", (long long)K, (long long)pipe_min_rows());
+    if (!aligned16(gy1) || !aligned16(w0) || !aligned16(h) || !aligned16(g_hs) || !aligned16(g_hd))
+        return gmp::fail(GMP_ERR_ARG, "lp_feat_gemm_bwd_fold: operands must be 16-byte aligned");
+    if (!gmp::lp_fold_applies(gy1, w0, h, g_hs, g_hd, K, F))
+        return gmp::fail(GMP_ERR_UNSUPPORTED, "lp_feat_gemm_bwd_fold: gmp_gemm_f32 would not run the pipelined kernel here (GMP_GEMM_IMPL)");
+    g2::LpFoldArgs a{gy1, w0, h, edges, g_hs, g_hd, num_nodes, K, 1.f, t_sig_flag, t_sig_value};
+    t_sig_flag = nullptr;
+    using C = g2::Cfg<1, 1, true, false, 4>;
+    auto kern = g2::lp_bwd_fold_kernel;
+    static std::atomic<uint64_t> attr_set{0};
+    if (!gmp::lds_attr_done(attr_set)) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES) != hipSuccess)
+            return gmp::fail(GMP_ERR_LAUNCH, "lp_feat_gemm_bwd_fold: cannot reserve %d bytes of LDS", C::LDS_BYTES);
+        gmp::lds_attr_mark(attr_set);
+    }
+    const int tiles_m = (int)((K + C::BM - 1) / C::BM);
+    if (gmp::lane_takes((hipStream_t)stream)) g_lp_fold_launches.fetch_add(1, std::memory_order_relaxed);      // (one count per launch, whichever lane makes it)
+    hipLaunchKernelGGL(kern, dim3((unsigned)(tiles_m * (256 / C::BN))), dim3(g2::THREADS), C::LDS_BYTES, (hipStream_t)stream, a, tiles_m);
+    return gmp::check_launch("lp_bwd_fold_kernel");
 }
 
 extern "C" size_t gmp_colsum_workspace_bytes(int64_t M, int64_t N) {

@@ -184,11 +184,34 @@ __device__ __forceinline__ void sched_sub() {
 }
 
 // EPI: the affine epilogue of GemmArgs (scale / shift / resid, NT only); false = the kernel as it always was
-template <int TM, int TN, bool A_KC, bool B_KC, int STAGES, int BUFS = STAGES, bool EPI = false>
+//
+// GEN: one operand is the link-prediction head's edge-feature matrix feat[k] = [hs+hd | hs*hd | |hs-hd|] ([K, 768], hs = h[edges[0][k]],
+// hd = h[edges[1][k]], an index out of range reads as a zero row) GENERATED into the ring instead of fetched from memory:
+//   GEN 1 (NT form, y1 = feat W0^T + b0): operand A, k-contiguous.  K-step s lies in third s / 8 at node-feature columns 32 (s % 8) .. +31; a thread
+//         owns the (row, 16-byte chunk) slots its lane addresses in the LDS-DMA instructions wave + 4 i, loads the hs / hd float4 of its pair
+//         row, forms the third's value with lp_feat_fwd_kernel's expressions and writes it where the DMA would have left it (lane-linear, the
+//         XOR swizzle is in the chunk it LOADS).  The row tile's indices are read once.
+//   GEN 2 (TN form, dW0 = gy1^T feat): operand B, k-major [32 pair rows][64 feature columns], one third per column tile; the pair indices of
+//         a stage are prefetched one hand-over before its node rows.  Rows at or beyond the reduction range are read from its last row and
+//         zeroed in the fragments by the TAIL step, as for a fetched operand.
+// The LDS image of a stage is the one the LDS-DMA leaves for a materialised feat, fragments and MFMA order are untouched: same bits.
+// Schedule and hazards.  The generated operand has a register prefetch depth of ONE stage (2 x 2 float4 per thread at 64 x 64: two blocks
+// per CU keep their registers): the loads of stage s + 2 are issued at the hand-over of step s, after the barrier and BEFORE the DMA of stage
+// s + 3, and are turned into ds_writes of stage s + 2 at the hand-over of step s + 1, before its barrier (that buffer's previous stage, s - 2,
+// was left by every wave two barriers ago).  vmcnt counts every vector load in issue order: at the hand-over of step s the outstanding ones
+// are DMA(s + 1); generated(s + 1) [+ indices(s + 2)], DMA(s + 2) -- so the counted wait for "stage s + 1 landed" is still "all but the DMA
+// instructions of ONE stage", with DMA_LOADS (the fetched operand's instructions only) in place of Cfg::LOADS; the generated loads are plain
+// C++ loads, hipcc adds its own wait in front of their first use (it may be stricter than needed -- it does not see the DMA -- never weaker).
+// The ds_writes are followed by s_waitcnt lgkmcnt(0) before the barrier, so every wave's part of stage s + 1 is visible behind it.
+template <int TM, int TN, bool A_KC, bool B_KC, int STAGES, int BUFS = STAGES, bool EPI = false, int GEN = 0>
 __global__ __launch_bounds__(THREADS) void gemm_pipe_kernel(const GemmArgs g, int tiles_m, int tiles_n) {
     using C = Cfg<TM, TN, A_KC, B_KC, STAGES, BUFS>;
     constexpr bool EARLY = BUFS < STAGES;
     constexpr bool IS_TN = !A_KC && !B_KC;
+    constexpr bool GEN_A = GEN == 1, GEN_B = GEN == 2;
+    static_assert(GEN == 0 || (GEN_A && A_KC && B_KC) || (GEN_B && IS_TN), "generated operand: A of the NT form or B of the TN form");
+    static_assert(GEN == 0 || (!EARLY && !EPI), "generated operand: one buffer per stage, plain epilogue");
+    constexpr int DMA_LOADS = (GEN_A ? 0 : C::OA::PER_WAVE) + (GEN_B ? 0 : C::OB::PER_WAVE);      // LDS-DMA instructions per wave per stage
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     const int t = threadIdx.x, lane = t & 63;
@@ -259,21 +282,85 @@ __global__ __launch_bounds__(THREADS) void gemm_pipe_kernel(const GemmArgs g, in
     typename C::OA la;
     typename C::OB lb;
     if (nsteps > 0) {
-        la.init(g.A, g.lda, m0, Mrows, kbeg, lane, wave);
-        lb.init(Bp, g.ldb, n0, g.N, kbeg, lane, wave);
+        if (!GEN_A) la.init(g.A, g.lda, m0, Mrows, kbeg, lane, wave);
+        if (!GEN_B) lb.init(Bp, g.ldb, n0, g.N, kbeg, lane, wave);
     }
     auto stage_ptr = [&](int s) -> char* { return smem + (s % BUFS) * C::STAGE_BYTES; };
     const unsigned lds0 = lds_address(smem);
     auto issue = [&](int s) {          // stage of K-step s; wave-uniform control flow
         const unsigned sp = lds0 + (s % BUFS) * C::STAGE_BYTES;
         if (IS_TN && ktail && s == nfull) {
-            la.issue_tail(sp, wave, lane, ktail, g.lda);
-            lb.issue_tail(sp + C::OA::BYTES, wave, lane, ktail, g.ldb);
+            if (!GEN_A) la.issue_tail(sp, wave, lane, ktail, g.lda);
+            if (!GEN_B) lb.issue_tail(sp + C::OA::BYTES, wave, lane, ktail, g.ldb);
         } else {
-            la.issue(sp, wave);
-            lb.issue(sp + C::OA::BYTES, wave);
+            if (!GEN_A) la.issue(sp, wave);
+            if (!GEN_B) lb.issue(sp + C::OA::BYTES, wave);
         }
     };
+    // ---- the generated operand (GEN): indices -> node rows -> the third's value -> the stage, one slot per DMA instruction of this wave
+    constexpr int NS = GEN_A ? C::OA::PER_WAVE : C::OB::PER_WAVE;
+    constexpr int LPRB = C::OB::LPR;
+    const float4* __restrict__ gh4 = reinterpret_cast<const float4*>(g.gen_h);
+    int64_t gia[NS], gib[NS];          // pair indices of the stage whose node rows are loaded next
+    float4 gvs[NS], gvd[NS];           // hs / hd pieces of the stage that is written next
+    auto gen_idx = [&](int s) {
+#pragma unroll
+        for (int i = 0; i < NS; ++i) {
+            const int ii = wave + 4 * i;
+            int64_t r;
+            if (GEN_A) {
+                r = m0 + ii * 8 + (lane >> 3);
+                r = r < Mrows ? r : Mrows - 1;
+            } else {
+                r = kbeg + (int64_t)s * BK + ii * (64 / LPRB) + lane / LPRB;
+                r = r < kend ? r : kend - 1;
+            }
+            gia[i] = g.gen_edges[r];
+            gib[i] = g.gen_edges[g.gen_K + r];
+        }
+    };
+    auto gen_load = [&](int s) {
+#pragma unroll
+        for (int i = 0; i < NS; ++i) {
+            const int ii = wave + 4 * i;
+            int cq;                    // float4 column of the 256-wide node row
+            if (GEN_A) {
+                const int row = ii * 8 + (lane >> 3);
+                cq = 8 * (s & 7) + ((lane & 7) ^ ((row >> 1) & 7));
+            } else {
+                cq = (int)(n0 & 255) / 4 + lane % LPRB;
+            }
+            const bool oka = gia[i] >= 0 && gia[i] < g.gen_N, okb = gib[i] >= 0 && gib[i] < g.gen_N;   // each endpoint on its own
+            float4 sv = make_float4(0.f, 0.f, 0.f, 0.f), dv = sv;
+            if (oka) sv = gh4[gia[i] * 64 + cq];
+            if (okb) dv = gh4[gib[i] * 64 + cq];
+            gvs[i] = sv;
+            gvd[i] = dv;
+        }
+    };
+    auto gen_store = [&](int s) {
+        const int third = GEN_A ? (s >> 3) : (int)(n0 >> 8);          // wave-uniform
+        char* dst = stage_ptr(s) + (GEN_B ? C::OA::BYTES : 0);
+#pragma unroll
+        for (int i = 0; i < NS; ++i) {
+            const float4 a = gvs[i], b = gvd[i];
+            float4 v;
+            if (third == 0) v = make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
+            else if (third == 1) v = make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w);
+            else v = make_float4(fabsf(a.x - b.x), fabsf(a.y - b.y), fabsf(a.z - b.z), fabsf(a.w - b.w));
+            *reinterpret_cast<float4*>(dst + (wave + 4 * i) * 1024 + lane * 16) = v;
+        }
+    };
+    if (GEN != 0 && nsteps > 0) {      // stage 0 into its buffer, stage 1 into registers, the indices of stage 2: all issued before the first DMA
+        gen_idx(0);
+        gen_load(0);
+        gen_store(0);
+        if (nsteps > 1) {
+            if (GEN_B) gen_idx(1);
+            gen_load(1);
+        }
+        if (GEN_B && nsteps > 2) gen_idx(2);
+    }
 #pragma unroll
     for (int s = 0; s < STAGES - 1; ++s)
         if (s < nsteps) issue(s);
@@ -293,12 +380,14 @@ __global__ __launch_bounds__(THREADS) void gemm_pipe_kernel(const GemmArgs g, in
     float fa0[TM][4], fa1[TM][4], fb0[TN][4], fb1[TN][4];
     constexpr int NREADS = (A_KC ? TM : 4 * TM) + (B_KC ? TN : 4 * TN), NMFMA = 4 * TM * TN;
     if (nsteps > 0) {          // stage 0: the prologue's younger stages (at most STAGES - 2 of them) may stay in flight
-        if (STAGES >= 4 && nsteps >= 3) wait_vmcnt<2 * C::LOADS>();
-        else if (STAGES >= 3 && nsteps >= 2) wait_vmcnt<C::LOADS>();
+        if (STAGES >= 4 && nsteps >= 3) wait_vmcnt<2 * DMA_LOADS>();
+        else if (STAGES >= 3 && nsteps >= 2) wait_vmcnt<DMA_LOADS>();
         else wait_vmcnt<0>();
+        if (GEN != 0) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // this wave's part of the generated stage 0 is in LDS
         __builtin_amdgcn_s_barrier();
         read_sub<TM, TN, A_KC, B_KC, STAGES>(stage_ptr(0), 0, wm, wn, l31, half, fa0, fb0);
     }
+    // (lp_bwd_fold_kernel below mirrors this step's sub-step schedule by hand; tests/test_gpu_lp_fused.py holds the two to the same bits)
     auto step = [&](int s, auto tailc) {
         constexpr bool TAIL = decltype(tailc)::value;
         const char* st = stage_ptr(s);
@@ -324,12 +413,20 @@ __global__ __launch_bounds__(THREADS) void gemm_pipe_kernel(const GemmArgs g, in
         mfma_sub<TM, TN, TAIL>(acc, fa0, fb0, 2, half, klen);
         sched_sub<NREADS, NMFMA>();
         if (s + 1 < nsteps) {
-            if (STAGES >= 4 && s + 2 < nsteps) wait_vmcnt<C::LOADS>();          // 4-stage schedule: stage s + 2 may stay in flight
+            if (STAGES >= 4 && s + 2 < nsteps) wait_vmcnt<DMA_LOADS>();          // 4-stage schedule: stage s + 2 may stay in flight
             else wait_vmcnt<0>();
             // early free: the DMA issued below lands in THIS stage's buffer -- this wave's reads of it (sub-step 3's were issued behind the
             // first MFMA of sub-step 2) must have returned before any wave may overwrite it; the barrier alone does not wait for them
             if (EARLY) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            if (GEN != 0) {            // the generated half of stage s + 1: out of the registers into its buffer, visible behind the barrier
+                gen_store(s + 1);
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            }
             __builtin_amdgcn_s_barrier();
+            if (GEN != 0 && s + 2 < nsteps) {          // before the DMA below: the counted waits rely on this order
+                gen_load(s + 2);
+                if (GEN_B && s + 3 < nsteps) gen_idx(s + 3);
+            }
             if (s + STAGES - 1 < nsteps) issue(s + STAGES - 1);
             read_sub<TM, TN, A_KC, B_KC, STAGES>(stage_ptr(s + 1), 0, wm, wn, l31, half, fa0, fb0);
         }
@@ -459,6 +556,144 @@ __global__ __launch_bounds__(THREADS) void gemm_pipe_kernel(const GemmArgs g, in
                 out[row * ldo + col] = v;
             }
         }
+}
+
+// ---- link-prediction head: input-gradient GEMM with the edge-feature fold in its epilogue ----------------------------------------
+// What it replaces: gfeat = gy1 W0 ([K, 768], the NN form above at its 64 x 64 / 4-stage default) followed by lp_feat_bwd_kernel, which reads
+// gfeat back only to fold its three column thirds (the gradients of hs+hd, hs*hd, |hs-hd|) into g_hs / g_hd [K, 256].  Here a block owns
+// 64 pair rows x 64 NODE-feature columns c .. c+63 and computes the three gfeat tiles at columns c, 256 + c, 512 + c itself: one ring, one
+// pipeline of 24 K-steps (third = s / 8; A = gy1 is re-read from L2 for every third, B = W0 moves 256 columns to the right), three accumulator
+// sets.  Each third starts from zero and sees its eight K-steps in ascending order with the sub-step / MFMA order of gemm_pipe_kernel, so
+// its tile is bit for bit the tile the NN GEMM stored; the epilogue applies the GEMM's alpha * v + 0 and then the expressions of
+// lp_feat_bwd_kernel.  gfeat (K x 768 fp32 written, then read) never exists, and the fold is not a launch of its own.
+// Hazards: as in gemm_pipe_kernel -- both operands are LDS-DMA, the counted vmcnt sees DMA instructions only (the epilogue's plain loads
+// are issued after the last stage was waited for with vmcnt(0)).
+struct LpFoldArgs {
+    const float* gy1;            // [K, 256]
+    const float* w0;             // [256, 768] row-major (Linear weight of the first layer)
+    const float* h;              // [N, 256]
+    const int64_t* edges;        // [2, K]
+    float* ghs;                  // [K, 256]
+    float* ghd;
+    int64_t N, K;
+    float alpha;                 // 1: kept as an operand so that the epilogue's alpha * v + 0 is the NN GEMM's
+    int* sig_flag;
+    int sig_value;
+};
+
+__device__ __forceinline__ float lp_sgn(float v) { return (float)((v > 0.f) - (v < 0.f)); }   // torch.abs' subgradient: 0 at 0
+
+__global__ __launch_bounds__(THREADS) void lp_bwd_fold_kernel(const LpFoldArgs g, int tiles_m) {
+    constexpr int STAGES = 4;          // the NN GEMM's default ring; the prologue and the hand-over waits below are written for it
+    using C = Cfg<1, 1, true, false, STAGES>;
+    constexpr int F = 256, KS = F / BK, NSTEPS = 3 * KS, TILES_N = F / C::BN;
+    static_assert(4 * 3 * 32 * 32 * 4 <= C::LDS_BYTES, "the epilogue turns three sub-tiles per wave through the ring");
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+
+    const int t = threadIdx.x, lane = t & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int wm = wave >> 1, wn = wave & 1, l31 = lane & 31, half = lane >> 5;
+    if (g.sig_flag && t == 0 && blockIdx.x == 0)
+        __hip_atomic_store(g.sig_flag, g.sig_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+
+    int bid = blockIdx.x;          // the four column tiles of one row tile on one XCD (gemm_pipe_kernel)
+    {
+        const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
+        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+    }
+    const int tile_m = bid / TILES_N, tile_n = bid - tile_m * TILES_N;
+    if (tile_m >= tiles_m) return;
+    const int64_t m0 = (int64_t)tile_m * C::BM;
+    const int c0 = tile_n * C::BN;
+
+    f32x16 acc[3][1][1];
+#pragma unroll
+    for (int th = 0; th < 3; ++th)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[th][0][0][r] = 0.f;
+
+    typename C::OA la;
+    typename C::OB lb;
+    la.init(g.gy1, F, m0, g.K, 0, lane, wave);
+    lb.init(g.w0, 3 * F, c0, 3 * F, 0, lane, wave);
+    auto stage_ptr = [&](int s) -> char* { return smem + (s % STAGES) * C::STAGE_BYTES; };
+    const unsigned lds0 = lds_address(smem);
+    auto issue = [&](int s) {          // called for s = 0, 1, 2, ... in order; wave-uniform control flow
+        const unsigned sp = lds0 + (s % STAGES) * C::STAGE_BYTES;
+        la.issue(sp, wave);
+        lb.issue(sp + C::OA::BYTES, wave);
+        if ((s & (KS - 1)) == KS - 1) {          // next third: A back to k = 0, B back to k = 0 and 256 columns on
+#pragma unroll
+            for (int i = 0; i < C::OA::PER_WAVE; ++i) la.p[i] -= F;
+#pragma unroll
+            for (int i = 0; i < C::OB::PER_WAVE; ++i) lb.p[i] += F - (int64_t)F * 3 * F;
+        }
+    };
+#pragma unroll
+    for (int s = 0; s < STAGES - 1; ++s) issue(s);
+
+    float fa0[1][4], fa1[1][4], fb0[1][4], fb1[1][4];
+    constexpr int NREADS = 1 + 4, NMFMA = 4;
+    wait_vmcnt<2 * C::LOADS>();
+    __builtin_amdgcn_s_barrier();
+    read_sub<1, 1, true, false, STAGES>(stage_ptr(0), 0, wm, wn, l31, half, fa0, fb0);
+    auto step = [&](int s, f32x16 (&a)[1][1]) {
+        const char* st = stage_ptr(s);
+        read_sub<1, 1, true, false, STAGES>(st, 1, wm, wn, l31, half, fa1, fb1);
+        mfma_sub<1, 1, false>(a, fa0, fb0, 0, half, BK);
+        sched_sub<NREADS, NMFMA>();
+        read_sub<1, 1, true, false, STAGES>(st, 2, wm, wn, l31, half, fa0, fb0);
+        mfma_sub<1, 1, false>(a, fa1, fb1, 1, half, BK);
+        sched_sub<NREADS, NMFMA>();
+        read_sub<1, 1, true, false, STAGES>(st, 3, wm, wn, l31, half, fa1, fb1);
+        mfma_sub<1, 1, false>(a, fa0, fb0, 2, half, BK);
+        sched_sub<NREADS, NMFMA>();
+        if (s + 1 < NSTEPS) {
+            if (s + 2 < NSTEPS) wait_vmcnt<C::LOADS>();          // stage s + 2 may stay in flight
+            else wait_vmcnt<0>();
+            __builtin_amdgcn_s_barrier();
+            if (s + STAGES - 1 < NSTEPS) issue(s + STAGES - 1);
+            read_sub<1, 1, true, false, STAGES>(stage_ptr(s + 1), 0, wm, wn, l31, half, fa0, fb0);
+        }
+        mfma_sub<1, 1, false>(a, fa1, fb1, 3, half, BK);
+    };
+#pragma unroll
+    for (int th = 0; th < 3; ++th)
+        for (int s = 0; s < KS; ++s) step(th * KS + s, acc[th]);
+
+    // ---- epilogue: each wave turns its three 32 x 32 sub-tiles through LDS (the ring is free) and folds whole float4 row pieces
+    __builtin_amdgcn_s_barrier();                         // every wave has finished reading the last stages
+    float* tile = reinterpret_cast<float*>(smem) + wave * (3 * 32 * 32);
+#pragma unroll
+    for (int th = 0; th < 3; ++th)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) tile[th * 1024 + ((r & 3) + 8 * (r >> 2) + 4 * half) * 32 + l31] = acc[th][0][0][r];
+    const int c4 = lane & 7, rsub = lane >> 3;
+    const int colq = (c0 + wn * 32) / 4 + c4;             // float4 column of the node-feature row
+    const float4* __restrict__ h4 = reinterpret_cast<const float4*>(g.h);
+    float4* ghs4 = reinterpret_cast<float4*>(g.ghs);
+    float4* ghd4 = reinterpret_cast<float4*>(g.ghd);
+    const float al = g.alpha;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int rl = q * 8 + rsub;
+        float4 gs = *reinterpret_cast<const float4*>(tile + rl * 32 + 4 * c4);
+        float4 gp = *reinterpret_cast<const float4*>(tile + 1024 + rl * 32 + 4 * c4);
+        float4 ga = *reinterpret_cast<const float4*>(tile + 2048 + rl * 32 + 4 * c4);
+        const int64_t row = m0 + wm * 32 + rl;
+        if (row >= g.K) continue;
+        gs = make_float4(al * gs.x + 0.f, al * gs.y + 0.f, al * gs.z + 0.f, al * gs.w + 0.f);
+        gp = make_float4(al * gp.x + 0.f, al * gp.y + 0.f, al * gp.z + 0.f, al * gp.w + 0.f);
+        ga = make_float4(al * ga.x + 0.f, al * ga.y + 0.f, al * ga.z + 0.f, al * ga.w + 0.f);
+        const int64_t a = g.edges[row], b = g.edges[g.K + row];
+        const bool oka = a >= 0 && a < g.N, okb = b >= 0 && b < g.N;   // each endpoint on its own: an index out of range reads as a zero row
+        float4 s = make_float4(0.f, 0.f, 0.f, 0.f), d = s;
+        if (oka) s = h4[a * (F / 4) + colq];
+        if (okb) d = h4[b * (F / 4) + colq];
+        const float4 tt = make_float4(ga.x * lp_sgn(s.x - d.x), ga.y * lp_sgn(s.y - d.y), ga.z * lp_sgn(s.z - d.z), ga.w * lp_sgn(s.w - d.w));
+        ghs4[row * (F / 4) + colq] = make_float4(gs.x + gp.x * d.x + tt.x, gs.y + gp.y * d.y + tt.y, gs.z + gp.z * d.z + tt.z, gs.w + gp.w * d.w + tt.w);
+        ghd4[row * (F / 4) + colq] = make_float4(gs.x + gp.x * s.x - tt.x, gs.y + gp.y * s.y - tt.y, gs.z + gp.z * s.z - tt.z, gs.w + gp.w * s.w - tt.w);
+    }
 }
 
 }  // namespace g2

@@ -30,6 +30,15 @@ int gemm_f32_epilogue(int mode, const float* A, const float* B, const float* bia
                       int64_t ldb, int64_t ldc, float alpha, int accumulate, int relu, const float* scale, const float* shift,
                       const float* resid, int64_t ldr, void* workspace, size_t workspace_bytes, gmp_stream_t stream);
 
+// The step's link-prediction head may take gmp_lp_feat_gemm_bwd_fold in place of gmp_gemm_f32 (NN) + gmp_lp_edge_features_bwd: true where that
+// GEMM would run on the pipelined kernel (same accumulation order, so the same bits) and every operand is 16-byte addressable.
+bool lp_fold_applies(const float* gy1, const float* w0, const float* h, const float* g_hs, const float* g_hd, int64_t K, int F);
+
+// Likewise gmp_lp_feat_gemm_fwd / gmp_lp_feat_gemm_wgrad in place of gmp_lp_edge_features_fwd + the NT GEMM and of the grouped TN GEMM over lp_feat:
+// true where both materialised GEMMs would run the pipelined kernel (the weight-gradient one needs a workspace for that).
+bool lp_feat_gemm_applies(const float* h, const float* w0, const float* b0, const float* y1, const float* gy1, const float* dW0,
+                          const void* workspace, int64_t K, int F);
+
 // Two-lane enqueue (step.hip): the pre-training step's launch sequence is walked by TWO host threads at once -- the caller takes the main
 // stream's launches, a worker thread everything else -- because one thread needs ~4 us per launch and a step has ~250 (the launcher was the
 // limiter on slower hosts; two threads launching on different streams scale 1.7x on this runtime, scripts/probe_two_threads.hip).  Both

@@ -125,6 +125,22 @@ int gemm(int mode, const float* A, const float* B, const float* bias, float* C, 
     return gmp_gemm_f32(mode, A, B, bias, C, M, N, K, lda, ldb, ldc, 1.f, 0, relu ? 1 : 0, nullptr, 0, st);
 }
 
+// GMP_LP_FUSED (read per call: one process can interleave A/B rounds): 0 = the link-prediction head keeps its materialised K x 768 matrices
+// everywhere; 1 (default) = the input gradient is folded inside its GEMM (lp_gfeat is not written: 1.335 -> 1.318 ms per step); 2 = the
+// forward and weight-gradient GEMMs generate lp_feat in their loaders as well (no K x 768 matrix at all, two launches less -- and, as
+// measured, SLOWER: 1.359 ms, the generated-operand GEMMs take 97 and 156 us against 66 + 14 and 88; profiles/README.md).  Same bits at every level.
+int lp_fused_level() {
+    const char* e = getenv("GMP_LP_FUSED");
+    return e ? atoi(e) : 1;
+}
+bool lp_fused() { return lp_fused_level() >= 1; }
+
+// one answer for the forward (task_head_inputs) and the weight gradient (task_head_params) of a step: both generate the features or neither does
+bool lp_feat_generated(const gmp_step_desc& d, const gmp_task_desc& t) {
+    return lp_fused_level() >= 2 && gmp::lp_feat_gemm_applies(d.h[GMP_STEP_LAYERS], d.flat + t.lp_off_w0, d.flat + t.lp_off_b0, t.lp_y1, t.lp_gy1,
+                                                   d.task_grads + t.lp_tg_w0, t.gemm_ws, t.lp_K, H);
+}
+
 // dropout(src) -> dst, or alias src when dropout is off; returns the buffer holding the result
 float* drop(const gmp_step_desc& d, float* src, float* dst, int64_t numel, uint32_t site, gmp_stream_t st, int* rc) {
     *rc = GMP_OK;
@@ -203,8 +219,14 @@ int task_head_inputs(const gmp_step_desc& d, int ti, gmp_stream_t st, float** d1
         case GMP_TASK_LP: {
             const int64_t K = t.lp_K;
             const float *w0 = d.flat + t.lp_off_w0, *b0 = d.flat + t.lp_off_b0, *w3 = d.flat + t.lp_off_w3, *b3 = d.flat + t.lp_off_b3;
-            GMP_TRY(gmp_lp_edge_features_fwd(hL, t.lp_edges, t.lp_feat, N, K, H, st));
-            GMP_TRY(gemm(GMP_GEMM_NT, t.lp_feat, w0, b0, t.lp_y1, K, H, 3 * H, 3 * H, 3 * H, H, true, st));
+            // the K x 768 edge features are generated inside the 768 -> 256 GEMM's loader where it and the weight-gradient GEMM (task_head_params asks
+            // the same question) run the pipelined kernel: same bits, lp_feat is not written; else the feature pass and the GEMM over it
+            if (lp_feat_generated(d, t)) {
+                GMP_TRY(gmp_lp_feat_gemm_fwd(hL, t.lp_edges, w0, b0, t.lp_y1, N, K, H, st));
+            } else {
+                GMP_TRY(gmp_lp_edge_features_fwd(hL, t.lp_edges, t.lp_feat, N, K, H, st));
+                GMP_TRY(gemm(GMP_GEMM_NT, t.lp_feat, w0, b0, t.lp_y1, K, H, 3 * H, 3 * H, 3 * H, H, true, st));
+            }
             // the 256 -> 1 layer: a dot product per row with the dropout in the same pass, and its input gradient as an outer product
             // pushed through the dropout and the ReLU (gmp_dropout_rowdot_fwd / gmp_outer_relu_dropout_bwd: no N = 1 GEMM launches)
             const float pdrop = d.training && d.dropout_p > 0.f ? d.dropout_p : 0.f;
@@ -220,8 +242,13 @@ int task_head_inputs(const gmp_step_desc& d, int ti, gmp_stream_t st, float** d1
                 *d1_out = ld1;
                 GMP_TRY(gmp_outer_relu_dropout_bwd(t.lp_gy2, w3, t.lp_y1, t.lp_gy1, K, H, pdrop, d.seed, t.lp_site, st));
             }
-            GMP_TRY(gemm(GMP_GEMM_NN, t.lp_gy1, w0, nullptr, t.lp_gfeat, K, 3 * H, H, H, 3 * H, 3 * H, false, st));
-            GMP_TRY(gmp_lp_edge_features_bwd(t.lp_gfeat, hL, t.lp_edges, t.lp_ghs, t.lp_ghd, N, K, H, st));
+            // g_hs / g_hd: one launch that never writes the K x 768 gradient where the pipelined GEMM applies (same bits), else the GEMM and the fold
+            if (lp_fused() && gmp::lp_fold_applies(t.lp_gy1, w0, hL, t.lp_ghs, t.lp_ghd, K, H)) {
+                GMP_TRY(gmp_lp_feat_gemm_bwd_fold(t.lp_gy1, w0, hL, t.lp_edges, t.lp_ghs, t.lp_ghd, N, K, H, st));
+            } else {
+                GMP_TRY(gemm(GMP_GEMM_NN, t.lp_gy1, w0, nullptr, t.lp_gfeat, K, 3 * H, H, H, 3 * H, 3 * H, false, st));
+                GMP_TRY(gmp_lp_edge_features_bwd(t.lp_gfeat, hL, t.lp_edges, t.lp_ghs, t.lp_ghd, N, K, H, st));
+            }
             float* g_rows = gH + (int64_t)H * t.row0;
             GMP_TRY(gmp_segment_sum(t.lp_ghs, d.lp_csr[3] + t.row0, d.lp_csr[5], g_rows, t.row1 - t.row0, H, 0, 1, st));
             return gmp_segment_sum(t.lp_ghd, d.lp_csr[0] + t.row0, d.lp_csr[2], g_rows, t.row1 - t.row0, H, 0, 1, st);
@@ -317,8 +344,12 @@ int task_head_params(const gmp_step_desc& d, int ti, gmp_stream_t st, float* d1)
             const int32_t one[2] = {0, (int32_t)K};
             const int64_t cw0[1] = {t.lp_tg_w0}, cb0[1] = {t.lp_tg_b0};
             // dW0 with db0 riding along (column sums of the A tile already in LDS); first: this GEMM carries the "input half done" signal
-            GMP_TRY(gmp_gemm_f32_grouped(GMP_GEMM_TN, t.lp_gy1, t.lp_feat, nullptr, tg, 1, one, nullptr, nullptr, cw0, tg, cb0, H, 3 * H, 0, H, 3 * H, 3 * H,
-                                         1.f, 0, 0, t.gemm_ws, t.gemm_ws_bytes, st));
+            // (with the features generated in its B loader where the forward did not write lp_feat: still "the next GEMM" of this thread for the signal)
+            if (lp_feat_generated(d, t))
+                GMP_TRY(gmp_lp_feat_gemm_wgrad(t.lp_gy1, d.h[GMP_STEP_LAYERS], t.lp_edges, tg + t.lp_tg_w0, tg + t.lp_tg_b0, d.N, K, H, t.gemm_ws, t.gemm_ws_bytes, st));
+            else
+                GMP_TRY(gmp_gemm_f32_grouped(GMP_GEMM_TN, t.lp_gy1, t.lp_feat, nullptr, tg, 1, one, nullptr, nullptr, cw0, tg, cb0, H, 3 * H, 0, H, 3 * H, 3 * H,
+                                             1.f, 0, 0, t.gemm_ws, t.gemm_ws_bytes, st));
             // dW3 [1, 256] and db3: a weighted column sum (the grouped GEMM path took 54 us for these 257 numbers)
             if (t.lp_pos)
                 return gmp_lp_pair_weighted_colsum(t.lp_gy2, t.lp_y1, t.lp_pos, tg + t.lp_tg_w3, tg + t.lp_tg_b3, K, H,

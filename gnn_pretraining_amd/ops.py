@@ -524,6 +524,44 @@ def lp_edge_features_bwd(g_feat: Tensor, h: Tensor, edges: Tensor) -> Tuple[Tens
     return ghs, ghd
 
 
+def lp_feat_gemm_fwd(h: Tensor, edges: Tensor, w0: Tensor, b0: Tensor) -> Tensor:
+    """relu(lp_edge_features(h, edges) @ w0.T + b0) [K, 256] with the features generated in the GEMM's loader (gmp_lp_feat_gemm_fwd)."""
+    F = _feat_ok(h, "h")
+    _need(edges, torch.int64, "edges", 2); _need(w0, torch.float32, "w0", 2); _need(b0, torch.float32, "b0", 1)
+    K = edges.size(1)
+    y1 = torch.empty(K, F, dtype=torch.float32, device=h.device)
+    L.check(L.lib().gmp_lp_feat_gemm_fwd(_ptr(h), _ptr(edges), _ptr(w0), _ptr(b0), _ptr(y1), h.size(0), K, F, _stream(h)), "gmp_lp_feat_gemm_fwd")
+    return y1
+
+
+def lp_feat_gemm_wgrad(gy1: Tensor, h: Tensor, edges: Tensor, workspace: Optional[Tensor]) -> Tuple[Tensor, Tensor]:
+    """dW0 [256, 768] = gy1.T @ lp_edge_features(h, edges) and db0 [256] = gy1.sum(0), features generated in the loader
+    (gmp_lp_feat_gemm_wgrad); the workspace (uint8) decides the row slices as it does for gmp_gemm_f32_grouped."""
+    F = _feat_ok(h, "h")
+    _need(gy1, torch.float32, "gy1", 2); _need(edges, torch.int64, "edges", 2)
+    K = edges.size(1)
+    dW0 = torch.empty(F, 3 * F, dtype=torch.float32, device=h.device)
+    db0 = torch.empty(F, dtype=torch.float32, device=h.device)
+    L.check(L.lib().gmp_lp_feat_gemm_wgrad(_ptr(gy1), _ptr(h), _ptr(edges), _ptr(dW0), _ptr(db0), h.size(0), K, F, _ptr(workspace),
+                                           0 if workspace is None else workspace.numel(), _stream(h)), "gmp_lp_feat_gemm_wgrad")
+    return dW0, db0
+
+
+def lp_feat_gemm_bwd_fold(gy1: Tensor, w0: Tensor, h: Tensor, edges: Tensor) -> Tuple[Tensor, Tensor]:
+    """g_hs, g_hd [K, 256] of lp_edge_features_bwd(gy1 @ w0, h, edges) without the [K, 768] matrix (gmp_lp_feat_gemm_bwd_fold:
+    K >= 1024, feature width 256; bit for bit the two-launch form)."""
+    F = _feat_ok(h, "h")
+    _need(gy1, torch.float32, "gy1", 2); _need(w0, torch.float32, "w0", 2); _need(edges, torch.int64, "edges", 2)
+    K = edges.size(1)
+    if tuple(gy1.shape) != (K, F) or tuple(w0.shape) != (F, 3 * F):
+        raise L.GnnmpError("lp_feat_gemm_bwd_fold: gy1 [K, F] and w0 [F, 3 F] expected")
+    ghs = torch.empty(K, F, dtype=torch.float32, device=h.device)
+    ghd = torch.empty_like(ghs)
+    L.check(L.lib().gmp_lp_feat_gemm_bwd_fold(_ptr(gy1), _ptr(w0), _ptr(h), _ptr(edges), _ptr(ghs), _ptr(ghd), h.size(0), K, F,
+                                              _stream(h)), "gmp_lp_feat_gemm_bwd_fold")
+    return ghs, ghd
+
+
 def nt_xent_fwd(z1: Tensor, z2: Tensor, temperature: float) -> Tuple[Tensor, Tensor]:
     """Returns (loss_sum [1], workspace) -- the workspace feeds nt_xent_bwd."""
     _need(z1, torch.float32, "z1", 2); _need(z2, torch.float32, "z2", 2)

@@ -273,6 +273,29 @@ int gmp_lp_edge_features_fwd(const float* h, const int64_t* edges, float* feat, 
 int gmp_lp_edge_features_bwd(const float* g_feat, const float* h, const int64_t* edges, float* g_hs,
                              float* g_hd, int64_t num_nodes, int64_t num_edges, int feat_dim,
                              gmp_stream_t stream);
+/* The input-gradient GEMM of the first head layer with gmp_lp_edge_features_bwd in its epilogue:
+ *   g_feat = gy1 w0 ([K, 3 feat], never written), folded per pair into g_hs, g_hd [K, feat] as gmp_lp_edge_features_bwd does.
+ * gy1 [K, 256], w0 [256, 768] row-major, h [num_nodes, 256], edges int64 [2, K].  Bit for bit what gmp_gemm_f32(GMP_GEMM_NN, gy1, w0,
+ * NULL, g_feat, K, 768, 256, ...) without a workspace followed by gmp_lp_edge_features_bwd gives where that GEMM runs on the pipelined
+ * kernel, hence: feat_dim == 256 (GMP_ERR_UNSUPPORTED otherwise), K >= 1024 and every float operand 16-byte aligned (GMP_ERR_ARG;
+ * nothing is launched).  Carries a pending gmp_gate_open_by_next_gemm signal like the GEMM it replaces. */
+int gmp_lp_feat_gemm_bwd_fold(const float* gy1, const float* w0, const float* h, const int64_t* edges, float* g_hs,
+                              float* g_hd, int64_t num_nodes, int64_t num_edges, int feat_dim, gmp_stream_t stream);
+/* The two GEMMs that read feat, with feat generated inside their operand loaders (never written):
+ *   fwd:   y1 = relu(feat w0^T + b0) [K, 256]       -- gmp_lp_edge_features_fwd + gmp_gemm_f32(GMP_GEMM_NT, feat, w0, b0, y1, ..., relu)
+ *   wgrad: dW0 = gy1^T feat [256, 768], db0 = column sums of gy1 [256] (NULL: skipped)
+ *                                                    -- gmp_gemm_f32_grouped(GMP_GEMM_TN, gy1, feat, ..., one group, WITH this workspace)
+ * bit for bit, where those GEMMs run on the pipelined kernel: feat_dim == 256 (GMP_ERR_UNSUPPORTED otherwise), K >= 1024, float operands
+ * 16-byte aligned (GMP_ERR_ARG); wgrad needs a workspace (GMP_ERR_WORKSPACE without: the materialised GEMM would not take the pipelined
+ * kernel) and slices the rows exactly as the materialised call with the same workspace size does.  Nothing is launched on an error.
+ * Both carry a pending gmp_gate_open_by_next_gemm signal. */
+int gmp_lp_feat_gemm_fwd(const float* h, const int64_t* edges, const float* w0, const float* b0, float* y1, int64_t num_nodes,
+                         int64_t num_edges, int feat_dim, gmp_stream_t stream);
+int gmp_lp_feat_gemm_wgrad(const float* gy1, const float* h, const int64_t* edges, float* dW0, float* db0, int64_t num_nodes,
+                           int64_t num_edges, int feat_dim, void* workspace, size_t workspace_bytes, gmp_stream_t stream);
+/* DIAGNOSTIC: how many gmp_lp_feat_gemm_fwd / _wgrad / _bwd_fold calls of this process have launched so far (the pre-training step counts here too); lets a
+ * test tell whether a step took the fused launches or its fallback. */
+uint64_t gmp_lp_feat_gemm_launch_count(void);
 
 /* ------------------------------------------------------------------------- *
  * The fused link-prediction scorer (MLPLinkPredictor, heads.py:57-67) over a pair list src[k], dst[k] (int64, k < K):
