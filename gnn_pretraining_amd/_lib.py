@@ -61,6 +61,12 @@ class AugViewsJob(C.Structure):          # gmp_aug_views_job
                 ("totals_and_flags", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
 
 
+class AugNegJob(C.Structure):            # gmp_aug_neg_job
+    _fields_ = [("ptr", C.c_void_p), ("eptr", C.c_void_p), ("edge_index", C.c_void_p), ("num_nodes", C.c_int64), ("num_edges", C.c_int64),
+                ("num_graphs", C.c_int32), ("stream_id", C.c_uint32), ("num_neg", C.c_int64), ("neg_out", C.c_void_p), ("capacity", C.c_int64),
+                ("counts", C.c_void_p), ("total", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
 class BnConfig(C.Structure):
     _fields_ = [("training", C.c_int), ("relu", C.c_int), ("eps", C.c_float), ("momentum", C.c_float),
                 ("dropout_p", C.c_float), ("seed", C.c_uint64), ("stream_id", C.c_uint32), ("seed_dev", C.c_void_p),
@@ -171,6 +177,9 @@ _SIGS: Dict[str, tuple] = {
     "gmp_aug_node_masks_batch": (C.c_int, [C.POINTER(AugMasksJob), i32, i64, C.c_uint64, p]),
     "gmp_aug_two_views_batch": (C.c_int, [C.POINTER(AugViewsJob), i32, i64, i64, C.c_uint64, p]),
     "gmp_aug_two_views": (C.c_int, [p, p, p, i64, i64, p, i32, i64, i64, i32, C.c_uint64, C.c_uint32, p, p, p, p, p, p, i64, p, p, p, p, p, sz, p]),
+    "gmp_aug_negative_edges_workspace_bytes": (sz, [i64, i64, i64]),
+    "gmp_aug_negative_edges": (C.c_int, [p, p, p, i64, i64, i32, i64, i64, C.c_uint64, C.c_uint32, p, i64, p, p, p, sz, p]),
+    "gmp_aug_negative_edges_batch": (C.c_int, [C.POINTER(AugNegJob), i32, i64, C.c_uint64, p]),
     "gmp_upload": (C.c_int, [i32, p, p, p, p]),
     "gmp_segments_pack": (C.c_int, [p, p, p, i32, i64, p]),
     "gmp_segments_unpack": (C.c_int, [p, p, p, i32, i64, f32, p]),

@@ -15,6 +15,21 @@
 // graph sizes alone, so `rows` is written at its final place; edge and common-node counts are random, so the first kernel leaves
 // every graph's survivors compacted at the start of the graph's own slot (its original edge / node range) and a second kernel
 // moves the slots to their final offsets (exclusive scan of the counts) in view-local numbering.
+//
+// Link-prediction negatives (gmp_aug_negative_edges, at the end of the file): torch_geometric's batched_negative_sampling(
+// to_undirected(edge_index), batch, num_neg) as pretrain/tasks.py restates it, one workgroup per graph.  The graph's undirected
+// adjacency (both directions, duplicates coalesced, self loops ignored) is a bitmap in the caller's workspace; cnt = its set bits,
+// pop = n (n - 1), M = pop - cnt non-edges (ordered pairs i != j, not adjacent).  n < 2 or cnt >= pop give nothing.  The host's
+// fp64 test pop <= int(1.1 * num_neg / (1.0 - cnt / pop)), in its evaluation order, decides between
+//   no draw : the first min(M, num_neg) non-edges in ascending code i * n + j -- what the host returns, bit for bit;
+//   sampled : every non-edge gets the key key32(seed, stream, S_NEG, (s + i) << 32 | (s + j)) (s = the graph's first node: the id is
+//             unique per ordered pair of the batch); the num_neg smallest keys are the sample, ties to the lower code, emitted in
+//             ascending code order.  A uniform num_neg-subset without replacement.
+// Two departures from PyG in the sampled case: the count is always exactly min(M, num_neg) (PyG may come back short after its three
+// tries), and the order within a graph is ascending, not random (the scorer's loss is a sum over pairs: order carries no meaning).
+// The k-th smallest key is found by a 4 x 8-bit radix select whose passes recompute the keys (no key array: a 1,024-node graph
+// has a million pairs); as for the views, a build kernel leaves each graph's codes in a slot of the workspace and an emit kernel
+// moves them to their final offsets.  LDS: two ints per node of the batch's largest graph + a 256-bin histogram (<= 10 KB).
 #include "gnnmp_internal.h"
 
 namespace {
@@ -23,7 +38,8 @@ constexpr int AB = 256;                 // threads per graph
 constexpr int MAX_NODES = 4096;         // per graph: keep flags / new ids / keys of both views live in LDS
 constexpr int EDGES_LDS = 4096;
 constexpr uint32_t S_NODE = 0x6e6f6465u, S_EDGE = 0x65646765u, S_ECOIN = 0x65636f69u, S_ACOIN = 0x61636f69u, S_ATTR = 0x61747472u,
-                   S_NFM = 0x6e666d6bu;
+                   S_NFM = 0x6e666d6bu, S_NEG = 0x6e656773u;
+constexpr int NEG_MAX_NODES = 1024;     // per graph, link-prediction negatives: codes i * n + j fit 2^20, rows of 32 bitmap words
 
 __device__ __forceinline__ uint32_t key32(uint64_t seed, uint32_t stream, uint32_t purpose, uint64_t idx) {
     return gmp::philox4x32(make_uint4((uint32_t)idx, (uint32_t)(idx >> 32), stream, purpose), make_uint2((uint32_t)seed, (uint32_t)(seed >> 32))).x;
@@ -438,4 +454,304 @@ extern "C" int gmp_aug_node_masks_batch(const gmp_aug_masks_job* jobs, int count
         hipLaunchKernelGGL(nfm_masks_batch_kernel, dim3(blocks), dim3(AB), 0, (hipStream_t)stream, mb);
     }
     return gmp::check_launch("nfm_masks_batch_kernel");
+}
+
+
+// ---- link-prediction negatives (rule and layout: header comment) -------------------------------------------------------------------
+namespace {
+
+struct NegArgs {
+    const int64_t *ptr, *eptr, *src, *dst;
+    int64_t N, E;
+    int G;
+    int64_t num_neg;
+    uint32_t stream;
+    uint32_t* bits;              // [N, W] adjacency rows (workspace): node s + i of the batch owns row s + i
+    int32_t* slot;               // [capacity] codes i * n + j; graph g's start at sum_{q < g} min(num_neg, n_q (n_q - 1))
+    int64_t capacity;
+    int64_t* neg;                // [2, capacity]
+    int32_t* counts;             // [G]
+    int32_t* total;              // [1]
+};
+
+// exclusive scan of a[0 .. n) in place by the first wave; *tot = the sum (the caller synchronises)
+__device__ __forceinline__ void neg_scan_rows(int* a, const int n, int* tot) {
+    const int t = threadIdx.x;
+    if (t >= 64) return;
+    int run = 0;
+    for (int c = 0; c < n; c += 64) {
+        const int i = c + t;
+        const int v = i < n ? a[i] : 0;
+        int inc = v;
+        for (int d = 1; d < 64; d <<= 1) {
+            const int u = __shfl_up(inc, d, 64);
+            if (t >= d) inc += u;
+        }
+        if (i < n) a[i] = run + inc - v;
+        run += __shfl(inc, 63, 64);
+    }
+    if (t == 0) *tot = run;
+}
+
+__device__ __forceinline__ uint32_t neg_key(uint64_t seed, uint32_t stream, int64_t s, int i, int j) {
+    return key32(seed, stream, S_NEG, ((uint64_t)(s + i) << 32) | (uint64_t)(uint32_t)(s + j));
+}
+
+__device__ __forceinline__ void negatives_body(const NegArgs& a, const int W, const uint64_t seed, const int g, unsigned char* dyn) {
+    const int ncap = W * 32;
+    unsigned long long* const s_off = reinterpret_cast<unsigned long long*>(dyn);      // slot offset of this graph
+    int* const s_misc = reinterpret_cast<int*>(dyn + 8);                                 // cnt | total below | total ties | prefix | remaining
+    uint32_t* const s_hist = reinterpret_cast<uint32_t*>(dyn + 32);                       // [256]
+    int* const s_less = reinterpret_cast<int*>(dyn + 32 + 1024);                           // [ncap] per row: selected below the threshold
+    int* const s_tie = s_less + ncap;                                                       // [ncap] per row: keys equal to the threshold
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    const int64_t s = a.ptr[g], es = a.eptr[g];
+    const int64_t n64 = a.ptr[g + 1] - s, ne64 = a.eptr[g + 1] - es;
+    // (a graph the arguments do not cover gives nothing rather than an access outside the workspace)
+    if (n64 < 2 || n64 > ncap || s < 0 || s + n64 > a.N || es < 0 || ne64 < 0 || es + ne64 > a.E) {
+        if (t == 0) a.counts[g] = 0;
+        return;
+    }
+    const int n = (int)n64, ne = (int)ne64;
+    if (t == 0) { *s_off = 0ull; s_misc[0] = 0; }
+    __syncthreads();
+    {
+        unsigned long long mine = 0ull;
+        for (int q = t; q < g; q += AB) {
+            const int64_t nq = a.ptr[q + 1] - a.ptr[q];
+            if (nq >= 2 && nq <= ncap) mine += (unsigned long long)(a.num_neg < nq * (nq - 1) ? a.num_neg : nq * (nq - 1));
+        }
+        if (mine) atomicAdd(s_off, mine);
+    }
+    uint32_t* const bits = a.bits + (size_t)s * W;
+    for (int q = t; q < n * W; q += AB) bits[q] = 0u;
+    __threadfence_block();
+    __syncthreads();
+    for (int e = t; e < ne; e += AB) {
+        const int64_t i = a.src[es + e] - s, j = a.dst[es + e] - s;
+        if (i < 0 || i >= n || j < 0 || j >= n || i == j) continue;
+        atomicOr(&bits[i * W + (j >> 5)], 1u << (j & 31));
+        atomicOr(&bits[j * W + (i >> 5)], 1u << (i & 31));
+    }
+    __threadfence_block();
+    __syncthreads();
+    const int wn = (n + 31) >> 5;
+    {
+        int deg_mine = 0;
+        for (int i = t; i < n; i += AB) {
+            int deg = 0;
+            for (int w = 0; w < wn; ++w) deg += __popc(bits[i * W + w]);
+            s_less[i] = n - 1 - deg;                 // non-edges of row i (the diagonal bit is never set)
+            s_tie[i] = 0;
+            deg_mine += deg;
+        }
+        if (deg_mine) atomicAdd(&s_misc[0], deg_mine);
+    }
+    __syncthreads();
+    const int cnt = s_misc[0], pop = n * (n - 1);
+    int64_t room = a.capacity - (int64_t)*s_off;
+    if (cnt >= pop || room <= 0) {
+        if (t == 0) a.counts[g] = 0;
+        return;
+    }
+    const int M = pop - cnt;
+    int k = a.num_neg < M ? (int)a.num_neg : M;
+    if (k > room) k = (int)room;                     // (never with the documented capacity: memory safety only)
+    // the host's rule, its fp64 arithmetic and evaluation order: prob = 1.0 - cnt / pop; size = int(1.1 * num_neg / prob)
+    const double prob = 1.0 - (double)cnt / (double)pop;
+    const double size = trunc(1.1 * (double)a.num_neg / prob);
+    const bool sampled = !((double)pop <= size) && k < M;
+    uint32_t T = 0xffffffffu;                        // no draw: every non-edge is "below the threshold", cut at k in code order
+    int take = 0;
+    if (sampled) {
+        // ---- the k-th smallest key: four 8-bit digits from the top; remaining = rank wanted inside the current prefix group
+        if (t == 0) { s_misc[3] = 0; s_misc[4] = k; }
+        for (int pass = 0; pass < 4; ++pass) {
+            const int shift = 24 - 8 * pass;
+            s_hist[t] = 0u;                          // (AB == 256 bins)
+            __syncthreads();
+            const uint32_t prefix = (uint32_t)s_misc[3];
+            for (int i = wave; i < n; i += AB / 64)
+                for (int c = 0; c < n; c += 64) {
+                    const int j = c + lane;
+                    if (j >= n || j == i || ((bits[i * W + (j >> 5)] >> (j & 31)) & 1u)) continue;
+                    const uint32_t key = neg_key(seed, a.stream, s, i, j);
+                    if (pass == 0 || (key >> (shift + 8)) == prefix) atomicAdd(&s_hist[(key >> shift) & 255u], 1u);
+                }
+            __syncthreads();
+            if (t == 0) {
+                int rem = s_misc[4], b = 0;
+                while (b < 255 && (int)s_hist[b] < rem) { rem -= (int)s_hist[b]; ++b; }
+                s_misc[3] = (int)((prefix << 8) | (uint32_t)b);
+                s_misc[4] = rem;
+            }
+            __syncthreads();
+        }
+        T = (uint32_t)s_misc[3];
+        take = s_misc[4];                            // how many of the keys equal to T belong to the sample (>= 1): the lowest codes
+        // ---- per row: keys below T, keys equal to T
+        for (int i = wave; i < n; i += AB / 64) {
+            int below = 0, equal = 0;
+            for (int c = 0; c < n; c += 64) {
+                const int j = c + lane;
+                const bool ne_ = j < n && j != i && !((bits[i * W + (j >> 5)] >> (j & 31)) & 1u);
+                const uint32_t key = ne_ ? neg_key(seed, a.stream, s, i, j) : 0u;
+                below += __popcll(__ballot(ne_ && key < T));
+                equal += __popcll(__ballot(ne_ && key == T));
+            }
+            if (lane == 0) { s_less[i] = below; s_tie[i] = equal; }
+        }
+        __syncthreads();
+    }
+    neg_scan_rows(s_less, n, &s_misc[1]);
+    __syncthreads();
+    if (sampled) {
+        neg_scan_rows(s_tie, n, &s_misc[2]);
+        __syncthreads();
+    }
+    // ---- emit in code order: position = selected pairs in front = keys below T in front + min(ties in front, take)
+    int32_t* const out = a.slot + *s_off;
+    for (int i = wave; i < n; i += AB / 64) {
+        int below = s_less[i], ties = s_tie[i];
+        if (below + (ties < take ? ties : take) >= k) continue;       // (wave-uniform) the row starts behind the cut
+        for (int c = 0; c < n; c += 64) {
+            const int j = c + lane;
+            const bool ne_ = j < n && j != i && !((bits[i * W + (j >> 5)] >> (j & 31)) & 1u);
+            bool lo = ne_, eq = false;
+            if (sampled) {
+                const uint32_t key = ne_ ? neg_key(seed, a.stream, s, i, j) : 0u;
+                lo = ne_ && key < T;
+                eq = ne_ && key == T;
+            }
+            const unsigned long long blo = __ballot(lo), beq = __ballot(eq);
+            const int tie_front = ties + __popcll(beq & lt);
+            const int pos = below + __popcll(blo & lt) + (tie_front < take ? tie_front : take);
+            if ((lo || (eq && tie_front < take)) && pos < k) out[pos] = i * n + j;
+            below += __popcll(blo);
+            ties += __popcll(beq);
+        }
+    }
+    if (t == 0) a.counts[g] = k;
+}
+
+// slots -> final offsets (exclusive scan of the counts), codes -> pairs in batch numbering
+__device__ __forceinline__ void emit_negatives_body(const NegArgs& a, const int W, const int g) {
+    __shared__ unsigned long long s_acc[2];          // counts in front | slot offset
+    const int t = threadIdx.x, ncap = W * 32;
+    if (t < 2) s_acc[t] = 0ull;
+    __syncthreads();
+    unsigned long long c_mine = 0ull, o_mine = 0ull;
+    for (int q = t; q < g; q += AB) {
+        c_mine += (unsigned long long)a.counts[q];
+        const int64_t nq = a.ptr[q + 1] - a.ptr[q];
+        if (nq >= 2 && nq <= ncap) o_mine += (unsigned long long)(a.num_neg < nq * (nq - 1) ? a.num_neg : nq * (nq - 1));
+    }
+    if (c_mine) atomicAdd(&s_acc[0], c_mine);
+    if (o_mine) atomicAdd(&s_acc[1], o_mine);
+    __syncthreads();
+    const int64_t off = (int64_t)s_acc[0];
+    const int k = a.counts[g];
+    if (k > 0) {
+        const int64_t s = a.ptr[g];
+        const int n = (int)(a.ptr[g + 1] - s);
+        const int32_t* const in = a.slot + s_acc[1];
+        for (int e = t; e < k; e += AB) {
+            const int code = in[e];
+            a.neg[off + e] = s + code / n;
+            a.neg[a.capacity + off + e] = s + code % n;
+        }
+    }
+    if (g == a.G - 1 && t == 0) *a.total = (int32_t)(off + k);
+}
+
+constexpr int NEG_MAXJ = 8;
+struct NegBatch { NegArgs job[NEG_MAXJ]; int first[NEG_MAXJ + 1]; int count; uint64_t seed; };
+__global__ __launch_bounds__(AB) void negatives_kernel(const NegArgs a, int W, uint64_t seed) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
+    negatives_body(a, W, seed, blockIdx.x, dyn);
+}
+__global__ __launch_bounds__(AB) void emit_negatives_kernel(const NegArgs a, int W) { emit_negatives_body(a, W, blockIdx.x); }
+__global__ __launch_bounds__(AB) void negatives_batch_kernel(const NegBatch b, int W) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
+    const int j = job_of(b.first, b.count, blockIdx.x);
+    negatives_body(b.job[j], W, b.seed, blockIdx.x - b.first[j], dyn);
+}
+__global__ __launch_bounds__(AB) void emit_negatives_batch_kernel(const NegBatch b, int W) {
+    const int j = job_of(b.first, b.count, blockIdx.x);
+    emit_negatives_body(b.job[j], W, blockIdx.x - b.first[j]);
+}
+
+int neg_words(int64_t max_graph_nodes) { return (int)((max_graph_nodes < 1 ? 1 : max_graph_nodes) + 31) / 32; }
+size_t neg_lds(int W) { return 32 + 1024 + (size_t)W * 32 * 2 * sizeof(int); }
+size_t neg_bitmap_bytes(int64_t num_nodes, int W) { return ((size_t)num_nodes * W * sizeof(uint32_t) + 255) / 256 * 256; }
+
+int neg_check(const gmp_aug_neg_job& q, int64_t max_graph_nodes) {
+    if (q.num_graphs < 0 || q.num_nodes < 0 || q.num_edges < 0 || q.num_neg < 0 || q.capacity < 0) return gmp::fail(GMP_ERR_ARG, "aug_negative_edges: bad sizes");
+    if (q.num_graphs == 0) return GMP_OK;
+    if (max_graph_nodes > NEG_MAX_NODES)
+        return gmp::fail(GMP_ERR_ARG, "aug_negative_edges: a graph of %lld nodes (limit %d)", (long long)max_graph_nodes, NEG_MAX_NODES);
+    if (!q.ptr || !q.eptr || !q.counts || !q.total || (q.num_edges > 0 && !q.edge_index) || (q.capacity > 0 && !q.neg_out))
+        return gmp::fail(GMP_ERR_ARG, "aug_negative_edges: null pointer");
+    if (!q.workspace || q.workspace_bytes < gmp_aug_negative_edges_workspace_bytes(q.num_nodes, max_graph_nodes, q.capacity))
+        return gmp::fail(GMP_ERR_WORKSPACE, "aug_negative_edges: workspace");
+    return GMP_OK;
+}
+NegArgs neg_args(const gmp_aug_neg_job& q, int W) {
+    NegArgs a{};
+    a.ptr = q.ptr; a.eptr = q.eptr; a.src = q.edge_index; a.dst = q.edge_index ? q.edge_index + q.num_edges : nullptr;
+    a.N = q.num_nodes; a.E = q.num_edges; a.G = q.num_graphs; a.num_neg = q.num_neg; a.stream = q.stream_id;
+    a.bits = (uint32_t*)q.workspace;
+    a.slot = (int32_t*)((unsigned char*)q.workspace + neg_bitmap_bytes(q.num_nodes, W));
+    a.capacity = q.capacity; a.neg = q.neg_out; a.counts = q.counts; a.total = q.total;
+    return a;
+}
+}  // namespace
+
+extern "C" size_t gmp_aug_negative_edges_workspace_bytes(int64_t num_nodes, int64_t max_graph_nodes, int64_t capacity) {
+    if (num_nodes < 0 || max_graph_nodes < 0 || capacity < 0) return 0;
+    return neg_bitmap_bytes(num_nodes, neg_words(max_graph_nodes)) + (size_t)capacity * sizeof(int32_t) + 256;
+}
+
+extern "C" int gmp_aug_negative_edges_batch(const gmp_aug_neg_job* jobs, int count, int64_t max_graph_nodes, uint64_t seed, gmp_stream_t stream) {
+    if (count < 0 || (count > 0 && !jobs)) return gmp::fail(GMP_ERR_ARG, "aug_negative_edges_batch: bad job list");
+    const int W = neg_words(max_graph_nodes);
+    hipStream_t st = (hipStream_t)stream;
+    for (int j0 = 0; j0 < count;) {
+        NegBatch nb{};
+        int n = 0, blocks = 0;
+        for (; j0 < count && n < NEG_MAXJ; ++j0) {
+            if (int rc = neg_check(jobs[j0], max_graph_nodes)) return rc;
+            if (jobs[j0].num_graphs == 0) continue;
+            nb.job[n] = neg_args(jobs[j0], W);
+            nb.first[n] = blocks;
+            blocks += jobs[j0].num_graphs;
+            ++n;
+        }
+        if (n == 0) continue;
+        nb.first[n] = blocks;
+        nb.count = n;
+        nb.seed = seed;
+        hipLaunchKernelGGL(negatives_batch_kernel, dim3(blocks), dim3(AB), neg_lds(W), st, nb, W);
+        hipLaunchKernelGGL(emit_negatives_batch_kernel, dim3(blocks), dim3(AB), 0, st, nb, W);
+    }
+    return gmp::check_launch("aug_negative_edges_batch kernels");
+}
+
+extern "C" int gmp_aug_negative_edges(const int64_t* ptr, const int64_t* eptr, const int64_t* edge_index, int64_t num_nodes, int64_t num_edges,
+                                      int num_graphs, int64_t max_graph_nodes, int64_t num_neg, uint64_t seed, uint32_t stream_id,
+                                      int64_t* neg_out, int64_t capacity, int32_t* counts, int32_t* total, void* workspace,
+                                      size_t workspace_bytes, gmp_stream_t stream) {
+    gmp_aug_neg_job q{};
+    q.ptr = ptr; q.eptr = eptr; q.edge_index = edge_index; q.num_nodes = num_nodes; q.num_edges = num_edges; q.num_graphs = num_graphs;
+    q.stream_id = stream_id; q.num_neg = num_neg; q.neg_out = neg_out; q.capacity = capacity; q.counts = counts; q.total = total;
+    q.workspace = workspace; q.workspace_bytes = workspace_bytes;
+    if (int rc = neg_check(q, max_graph_nodes)) return rc;
+    if (num_graphs == 0) return GMP_OK;
+    const int W = neg_words(max_graph_nodes);
+    const NegArgs a = neg_args(q, W);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(negatives_kernel, dim3(num_graphs), dim3(AB), neg_lds(W), st, a, W, seed);
+    hipLaunchKernelGGL(emit_negatives_kernel, dim3(num_graphs), dim3(AB), 0, st, a, W);
+    return gmp::check_launch("aug_negative_edges kernels");
 }

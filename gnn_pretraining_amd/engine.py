@@ -313,7 +313,7 @@ class StepEngine:
     def __init__(self, model: PretrainableGNN, tasks: Sequence[str], domains: Sequence[str], device,
                  max_rows: int = 16384, max_edges: int = 131072, seed: int = 0, shuffle_rng: Optional[random.Random] = None,
                  grad_sync=None, rng_mode: str = "reference", native: bool = True, neg_rng: Optional[random.Random] = None,
-                 dp_mode: Optional[str] = None) -> None:
+                 dp_mode: Optional[str] = None, device_negatives: bool = False) -> None:
         self.native = native       # True: csrc/step.hip enqueues the step; False: the same launches one by one from Python
         # data-parallel exchange: "allreduce" (every rank all-reduces all per-task gradients and runs the whole PCGrad: dist.OverlappedGradSync)
         # or "sharded" (reduce-scatter to the owner of each tensor, PCGrad on the owned tensors, all-gather of the combined gradient:
@@ -325,6 +325,10 @@ class StepEngine:
         if rng_mode not in ("reference", "vectorized", "device"):
             raise ValueError("rng_mode must be 'reference', 'vectorized' or 'device'")
         self.rng_mode, self._nprng = rng_mode, None
+        # link-prediction negatives drawn on the device too (csrc/augment.hip gmp_aug_negative_edges), riding the draw ticket: opt-in
+        if device_negatives and rng_mode != "device":
+            raise ValueError("device_negatives needs rng_mode='device'")
+        self.device_negatives = bool(device_negatives)
         # Link-prediction negatives: PyG's sampler draws from Python's `random` (the global, unseeded module in the reference), never
         # from the shared torch generator (pretrain/tasks.py sample_negative_edges).  The engine keeps a stream of its own.
         self.neg_rng = neg_rng if neg_rng is not None else random.Random(0x9E3779B1 * (seed + 1))
@@ -711,7 +715,8 @@ class StepEngine:
 
     def enqueue_draws(self, inp: StepInputs) -> "DrawTicket":
         """Enqueue the device-side draws of ONE step (rng_mode 'device'): node-feature-masking indices and the two augmented views
-        of every contrastive (task, domain) pair, by gmp_aug_node_masks / gmp_aug_two_views on the aux stream, followed by one copy
+        of every contrastive (task, domain) pair, by gmp_aug_node_masks / gmp_aug_two_views on the aux stream (with device_negatives
+        also the link-prediction negatives of every domain whose graphs fit gmp_aug_negative_edges), followed by one copy
         kernel that writes the results into a pinned host slot and a one-thread kernel that raises the slot's flag.  Safe to call
         from the prefetch thread while the launcher thread enqueues steps: the kernels depend on nothing a step computes, and
         wherever they land between the aux stream's packets they run at most one step later.  Returns the ticket
@@ -751,6 +756,21 @@ class StepEngine:
                     lay.append((t, d, {"rows": (take(8 * V), take(8 * V)), "mask": (take(8 * V), take(8 * V)),
                                        "edges": (take(16 * max(E, 1)), take(16 * max(E, 1))), "common": (take(8 * V), take(8 * V)),
                                        "counts": take(20 * G), "totals": take(32), "V": V, "E": E, "vptr": vptr_h}))
+        nlay = []                                   # link-prediction negatives on the device: one job per domain whose graphs fit the kernel
+        if self.device_negatives and "link_pred" in self.tasks:
+            from .ops import NEG_MAX_GRAPH_NODES, negative_capacity
+            for d in self.domains:
+                hb = inp.host[d]
+                if hb.num_graphs == 0:
+                    continue
+                meta = inp.__dict__.setdefault("_neg_meta", {}).get(d)
+                if meta is None:
+                    nmax = max(int(b - a) for a, b in zip(hb.ptr_host[:-1], hb.ptr_host[1:]))
+                    meta = inp._neg_meta[d] = (nmax, negative_capacity(hb.ptr_host, hb.num_edges) if nmax <= NEG_MAX_GRAPH_NODES else 0)
+                if meta[0] > NEG_MAX_GRAPH_NODES:
+                    continue                        # a graph over the kernel's limit: this domain's negatives stay on the host
+                cap = max(meta[1], 1)
+                nlay.append(("link_pred", d, {"neg": take(16 * cap), "cap": cap, "counts": take(4 * hb.num_graphs), "total": take(16), "nmax": meta[0]}))
         total = max(off, 16)
         slot_id = k % self.DRAW_SLOTS
         while len(self._draw_slots) <= slot_id:
@@ -776,6 +796,10 @@ class StepEngine:
                     emax_all = max([emax_all] + [int(b - a) for a, b in zip(hb.edge_ptr_host[:-1], hb.edge_ptr_host[1:])])
                     o["ws_off"], o["ws_bytes"] = ws_need, (lib.gmp_aug_workspace_bytes(hb.num_nodes, o["E"], hb.num_graphs) + 255) // 256 * 256
                     ws_need += o["ws_bytes"]
+            neg_nmax = max([1] + [o["nmax"] for (_, _, o) in nlay])
+            for (_, d, o) in nlay:
+                o["ws_off"], o["ws_bytes"] = ws_need, (lib.gmp_aug_negative_edges_workspace_bytes(inp.host[d].num_nodes, neg_nmax, o["cap"]) + 255) // 256 * 256
+                ws_need += o["ws_bytes"]
             if ws_need and (self._draw_ws is None or self._draw_ws.numel() < ws_need):
                 # (kernels of earlier tickets may still be using the old one on the aux stream: keep it alive.  One region per JOB -- the
                 # jobs of a ticket run concurrently; tickets follow each other on the aux stream and share the regions)
@@ -799,11 +823,21 @@ class StepEngine:
                 self._chk(lib.gmp_aug_node_masks_batch((L.AugMasksJob * len(mjobs))(*mjobs), len(mjobs), nmax_all, seed, aux), "aug_node_masks_batch")
             if vjobs:
                 self._chk(lib.gmp_aug_two_views_batch((L.AugViewsJob * len(vjobs))(*vjobs), len(vjobs), nmax_all, emax_all, seed, aux), "aug_two_views_batch")
+            if nlay:
+                njobs = []
+                for (t, d, o) in nlay:
+                    ptr, eptr, ei, _, _, _, _ = inp.dev_graph(d)
+                    hb = inp.host[d]
+                    sid = 16 * self.tasks.index(t) + 2 * self.domains.index(d) * len(self.tasks) * 16
+                    njobs.append(L.AugNegJob(ptr.data_ptr(), eptr.data_ptr(), ei.data_ptr() if hb.num_edges else None, hb.num_nodes, hb.num_edges,
+                                             hb.num_graphs, sid, hb.num_edges, base + o["neg"], o["cap"], base + o["counts"], base + o["total"],
+                                             ws_base + o["ws_off"], o["ws_bytes"]))
+                self._chk(lib.gmp_aug_negative_edges_batch((L.AugNegJob * len(njobs))(*njobs), len(njobs), neg_nmax, seed, aux), "aug_negative_edges_batch")
             src = (C.c_void_p * 1)(base)
             dst = (C.c_void_p * 1)(slot["pin"].data_ptr())
             self._chk(lib.gmp_upload(1, src, dst, (C.c_int64 * 1)((total + 15) // 16 * 16), aux), "draw results -> pinned host")
             self._chk(lib.gmp_gate_open(slot["flag"].data_ptr(), k + 1, aux), "draw flag")
-        return DrawTicket(slot, lay, k + 1)
+        return DrawTicket(slot, lay + nlay, k + 1)
 
     def _bury(self, obj=None) -> None:
         """Outgrown draw slots / workspaces may still be in use by tickets already on the aux stream: each is kept with an event recorded
@@ -816,7 +850,9 @@ class StepEngine:
 
     def collect_draws(self, inp: StepInputs, ticket: "DrawTicket") -> Dict[str, object]:
         """Wait for a ticket's flag (a word in pinned host memory the GPU sets behind its copy: no HIP call, no stream sync) and wrap
-        the slot's arrays as the step's artefacts.  Link-prediction negatives stay on the host (mostly "every non-edge", no draw)."""
+        the slot's arrays as the step's artefacts.  Link-prediction negatives come from the host sampler (mostly "every non-edge", no draw)
+        unless the engine was built with device_negatives: then the ticket carries them too, and only a domain batch with a graph over the
+        kernel's 1,024-node limit still asks the host."""
         import time as _t
         flag = ticket.slot["flag"].numpy()
         t_end = _t.time() + 120.0
@@ -828,12 +864,17 @@ class StepEngine:
         art: Dict[str, object] = {}
         for t in self.tasks:
             if t == "link_pred":
-                art[t] = {d: (_EMPTY_ART[t]() if not inp.host[d].num_graphs else self._negatives(inp.host[d])) for d in self.domains}
+                on_ticket = {d for (tt, d, _) in ticket.layout if tt == "link_pred"}
+                art[t] = {d: (None if d in on_ticket else _EMPTY_ART[t]() if not inp.host[d].num_graphs else self._negatives(inp.host[d]))
+                          for d in self.domains}
             elif t in ("node_feat_mask", "node_contrast", "graph_contrast"):
                 art[t] = {d: _EMPTY_ART[t]() for d in self.domains}        # domains without a drawn piece (no graphs / too few)
         for (t, d, o) in ticket.layout:
             if t == "node_feat_mask":
                 art[t][d] = buf[o["idx"]:o["idx"] + 8 * o["m"]].view(np.int64).copy()
+            elif t == "link_pred":
+                k = int(buf[o["total"]:o["total"] + 4].view(np.int32)[0])
+                art[t][d] = buf[o["neg"]:o["neg"] + 16 * o["cap"]].view(np.int64).reshape(2, -1)[:, :k].copy()
             else:
                 tot = buf[o["totals"]:o["totals"] + 20].view(np.int32)
                 views = []

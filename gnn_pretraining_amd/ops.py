@@ -894,6 +894,65 @@ def aug_two_views_batch(jobs, seed: int):
     return res
 
 
+NEG_MAX_GRAPH_NODES = 1024          # gmp_aug_negative_edges: nodes per graph
+
+
+def negative_capacity(ptr_host, num_neg: int) -> int:
+    """sum_g min(num_neg, n_g (n_g - 1)): the host-known bound on a batch's negatives that sizes gmp_aug_negative_edges' output."""
+    return sum(min(int(num_neg), int(b - a) * (int(b - a) - 1)) for a, b in zip(ptr_host[:-1], ptr_host[1:]) if b - a >= 2)
+
+
+def batched_negative_sampling(edge_index: Tensor, ptr: Tensor, eptr: Tensor, num_neg: int, seed: int,
+                              stream_id: int = 0) -> Tuple[Tensor, Tensor]:
+    """batched_negative_sampling(to_undirected(edge_index), batch, num_neg) of a domain batch on the device (gmp_aug_negative_edges;
+    the rule and its two departures from PyG: include/gnnmp.h).  edge_index [2, E], ptr / eptr [G + 1]: int64 on the device, batch
+    numbering.  Returns (neg [2, K] int64 on the device, counts [G] int32): graph g's counts[g] pairs in ascending code order, graphs
+    in batch order.  Synchronises (K is read back)."""
+    _need(ptr, torch.int64, "ptr", 1); _need(eptr, torch.int64, "eptr", 1); _need(edge_index, torch.int64, "edge_index", 2)
+    if ptr.numel() != eptr.numel() or edge_index.size(0) != 2 or num_neg < 0:
+        raise L.GnnmpError("batched_negative_sampling: ptr / eptr / edge_index [2, E] / num_neg >= 0 do not fit together")
+    dev, G = ptr.device, ptr.numel() - 1
+    if G <= 0:
+        return torch.empty(2, 0, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.int32, device=dev)
+    ptr_host = ptr.cpu().tolist()
+    N, E = int(ptr_host[-1]), int(edge_index.size(1))
+    nmax = max(int(b - a) for a, b in zip(ptr_host[:-1], ptr_host[1:]))
+    cap = max(negative_capacity(ptr_host, num_neg) if nmax <= NEG_MAX_GRAPH_NODES else 0, 1)
+    neg = torch.empty(2, cap, dtype=torch.int64, device=dev)
+    counts, total = torch.empty(G, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int32, device=dev)
+    l = L.lib()
+    ws = _ws(l.gmp_aug_negative_edges_workspace_bytes(N, nmax, cap), dev)
+    L.check(l.gmp_aug_negative_edges(_ptr(ptr), _ptr(eptr), _ptr(edge_index) if E else None, N, E, G, nmax, int(num_neg), seed & (2 ** 64 - 1),
+                                     stream_id & 0xffffffff, _ptr(neg), cap, _ptr(counts), _ptr(total), _ptr(ws), ws.numel(), _stream(ptr)),
+            "gmp_aug_negative_edges")
+    return neg[:, :int(total.item())], counts
+
+
+def batched_negative_sampling_batch(jobs, seed: int):
+    """gmp_aug_negative_edges for several domain batches in TWO launches.  jobs: [(edge_index, ptr, eptr, num_neg, stream_id)]; returns a
+    list of (neg, counts) identical to batched_negative_sampling(..., seed, stream_id) per job."""
+    l = L.lib()
+    hosts = [ptr.cpu().tolist() for _, ptr, _, _, _ in jobs]
+    nmax = max([1] + [int(b - a) for h in hosts for a, b in zip(h[:-1], h[1:])])
+    res, cjobs, keep = [], [], []
+    for (ei, ptr, eptr, num_neg, sid), h in zip(jobs, hosts):
+        _need(ptr, torch.int64, "ptr", 1); _need(eptr, torch.int64, "eptr", 1); _need(ei, torch.int64, "edge_index", 2)
+        dev, G = ptr.device, len(h) - 1
+        N, E = int(h[-1]), int(ei.size(1))
+        cap = max(negative_capacity(h, num_neg) if nmax <= NEG_MAX_GRAPH_NODES else 0, 1)
+        neg = torch.empty(2, cap, dtype=torch.int64, device=dev)
+        counts, total = torch.empty(max(G, 0), dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int32, device=dev)
+        ws = _ws(l.gmp_aug_negative_edges_workspace_bytes(N, nmax, cap), dev)          # (one region per job: the jobs of a launch run concurrently)
+        keep.append(ws)
+        cjobs.append(L.AugNegJob(_ptr(ptr), _ptr(eptr), _ptr(ei) if E else None, N, E, G, sid & 0xffffffff, int(num_neg), _ptr(neg), cap,
+                                 _ptr(counts), _ptr(total), _ptr(ws), ws.numel()))
+        res.append((neg, counts, total))
+    if cjobs:
+        L.check(l.gmp_aug_negative_edges_batch((L.AugNegJob * len(cjobs))(*cjobs), len(cjobs), nmax, seed & (2 ** 64 - 1), _stream(jobs[0][1])),
+                "gmp_aug_negative_edges_batch")
+    return [(neg[:, :int(total.item())], counts) for neg, counts, total in res]
+
+
 def dropout_rowdot_fwd(x: Tensor, w: Tensor, bias: Optional[Tensor], p: float, seed: int, stream_id: int):
     """(dropout(x), dropout(x) @ w + bias) for a Linear(F, 1) (gmp_dropout_rowdot_fwd); the dropped copy is x itself when p == 0."""
     _need(x, torch.float32, "x", 2)

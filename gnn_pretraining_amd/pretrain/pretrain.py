@@ -4,7 +4,7 @@ datasets in data/processed; synthetic stand-ins are generated when none were exp
 of the reference need the network).  wandb is replaced by a JSONL logger with the same metric keys.
 
 Build-only flags (the reference's flags are unchanged): --epochs, --steps-per-epoch, --log, --device, --data-root,
---data-scale, --rng, --module-path.
+--data-scale, --rng, --device-negatives, --module-path.
 """
 from __future__ import annotations
 
@@ -232,7 +232,7 @@ def run_evaluation_engine(state: StepState, engine, val_loaders, generator: torc
 
 def pretrain(cfg: PretrainConfig, epochs: int = EPOCHS, steps_per_epoch: Optional[int] = None, log_path: Optional[str] = None,
              device: Optional[str] = None, data_root: Optional[str] = None, data_scale: float = 1.0,
-             rng_mode: str = "reference", use_engine: bool = True) -> Path:
+             rng_mode: str = "reference", use_engine: bool = True, device_negatives: bool = False) -> Path:
     """pretrain.py:284-349.  `steps_per_epoch` truncates an epoch (the loader's own length -- 462 for the four-domain
     schemes on the real data -- is the default); data come from data/processed (synthetic stand-ins are generated on
     first use when no exported real data is there)."""
@@ -261,7 +261,8 @@ def pretrain(cfg: PretrainConfig, epochs: int = EPOCHS, steps_per_epoch: Optiona
     from ..engine import SUPPORTED_TASKS, StepEngine
     if use_engine and all(t in SUPPORTED_TASKS for t in cfg.active_tasks):
         engine = StepEngine(model, cfg.active_tasks, cfg.pretrain_domains, dev, seed=cfg.seed, rng_mode=rng_mode,
-                            max_rows=65536, max_edges=524288)      # 8 PROTEINS-sized graphs (<= 620 nodes) x 7 passes fit
+                            max_rows=65536, max_edges=524288,      # 8 PROTEINS-sized graphs (<= 620 nodes) x 7 passes fit
+                            device_negatives=device_negatives)
     best, stale, global_step = float("inf"), 0, [0]
     path = OUTPUT_DIR / f"model_{cfg.exp_name}_{cfg.seed}.pt"
     for epoch in range(1, epochs + 1):
@@ -295,7 +296,7 @@ def pretrain(cfg: PretrainConfig, epochs: int = EPOCHS, steps_per_epoch: Optiona
     return path
 
 
-def main() -> None:
+def parse_args(argv=None) -> argparse.Namespace:
     p = argparse.ArgumentParser()
     p.add_argument("--exp_name", type=str, required=True)
     p.add_argument("--seed", type=int, required=True)
@@ -305,11 +306,21 @@ def main() -> None:
     p.add_argument("--device", type=str, default=None)
     p.add_argument("--data-root", type=str, default=None, help="directory holding {D}/data.safetensors (default data/processed)")
     p.add_argument("--data-scale", type=float, default=1.0, help="size of the synthetic stand-ins generated on first use")
-    p.add_argument("--rng", choices=["reference", "vectorized"], default="reference")
+    p.add_argument("--rng", choices=["reference", "vectorized", "device"], default="reference",
+                   help="device: masks and augmented views are drawn on the GPU (Philox keys: the reference's distributions, not its stream)")
+    p.add_argument("--device-negatives", action="store_true",
+                   help="with --rng device: draw the link-prediction negatives on the GPU too (opt-in)")
     p.add_argument("--module-path", action="store_true", help="run the per-task nn.Module path instead of the stacked engine")
-    a = p.parse_args()
+    a = p.parse_args(argv)
+    if a.device_negatives and a.rng != "device":
+        p.error("--device-negatives needs --rng device")
+    return a
+
+
+def main() -> None:
+    a = parse_args()
     path = pretrain(PretrainConfig(exp_name=a.exp_name, seed=a.seed), a.epochs, a.steps_per_epoch, a.log, a.device,
-                    a.data_root, a.data_scale, a.rng, not a.module_path)
+                    a.data_root, a.data_scale, a.rng, not a.module_path, a.device_negatives)
     print(f"saved {path}")
 
 

@@ -769,6 +769,38 @@ int gmp_aug_node_masks_batch(const gmp_aug_masks_job* jobs, int count, int64_t m
 int gmp_aug_two_views_batch(const gmp_aug_views_job* jobs, int count, int64_t max_graph_nodes, int64_t max_graph_edges, uint64_t seed,
                             gmp_stream_t stream);
 
+/* Link-prediction negatives of a domain batch: batched_negative_sampling(to_undirected(edge_index), batch, num_neg) per graph, in
+ * batch-local numbering.  Per graph of n nodes: the undirected adjacency (both directions, duplicates coalesced, self loops ignored)
+ * has cnt entries; pop = n (n - 1); M = pop - cnt non-edges (ordered pairs i != j, not adjacent in either direction).  n < 2 or
+ * cnt >= pop give nothing.  When pop <= int(1.1 * num_neg / (1.0 - cnt / pop)) (the sampler's own fp64 expression) no draw happens: the
+ * graph gives its first min(M, num_neg) non-edges in ascending code i * n + j, bit for bit what the host sampler returns.  Otherwise
+ * every non-edge gets a Philox key (seed, stream_id, the ordered pair) and the num_neg smallest keys are the sample (ties to the
+ * lower code): a uniform num_neg-subset without replacement.  Two departures from PyG in that case: a graph always gives exactly
+ * min(M, num_neg) pairs (PyG can come back short after its three tries), and they are listed in ascending code order, not in random
+ * order.  neg_out [2, capacity] int64 holds the pairs compacted, graphs in batch order (row 1 at neg_out + capacity); counts [G] the
+ * pairs per graph; total [1] their sum.  capacity >= sum_g min(num_neg, n_g (n_g - 1)) (a host-known bound).  The workspace holds the
+ * bitmaps and per-graph slots: gmp_aug_negative_edges_workspace_bytes(num_nodes, max_graph_nodes, capacity), with the SAME
+ * max_graph_nodes as the call.  Limit: 1,024 nodes per graph (GMP_ERR_ARG above it, nothing is launched).  num_graphs == 0 is a no-op.
+ * gmp_aug_negative_edges_batch: all the jobs of a step in two launches (build, emit); results identical to the per-job calls. */
+size_t gmp_aug_negative_edges_workspace_bytes(int64_t num_nodes, int64_t max_graph_nodes, int64_t capacity);
+int gmp_aug_negative_edges(const int64_t* ptr, const int64_t* eptr, const int64_t* edge_index, int64_t num_nodes, int64_t num_edges,
+                           int num_graphs, int64_t max_graph_nodes, int64_t num_neg, uint64_t seed, uint32_t stream_id,
+                           int64_t* neg_out, int64_t capacity, int32_t* counts, int32_t* total, void* workspace, size_t workspace_bytes,
+                           gmp_stream_t stream);
+typedef struct {
+    const int64_t *ptr, *eptr, *edge_index;
+    int64_t num_nodes, num_edges;
+    int32_t num_graphs;
+    uint32_t stream_id;
+    int64_t num_neg;
+    int64_t* neg_out;
+    int64_t capacity;
+    int32_t *counts, *total;
+    void* workspace;
+    size_t workspace_bytes;
+} gmp_aug_neg_job;
+int gmp_aug_negative_edges_batch(const gmp_aug_neg_job* jobs, int count, int64_t max_graph_nodes, uint64_t seed, gmp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
