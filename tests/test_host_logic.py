@@ -51,7 +51,10 @@ def test_mask_indices_bit_exact_vs_oracle():
 
 # ---------------------------------------------------------------- engine host planning (no GPU involved)
 import numpy as np                                                        # noqa: E402
+import random                                                             # noqa: E402
+from gnn_pretraining_amd._lib import GnnmpError                            # noqa: E402
 from gnn_pretraining_amd.engine import StepEngine                          # noqa: E402
+from gnn_pretraining_amd.step_host import StepHost, hostdraw               # noqa: E402
 from gnn_pretraining_amd.pretrain import pretrain as PT                    # noqa: E402
 
 
@@ -63,12 +66,9 @@ class _Inp:
             r += host[d].num_nodes
 
 
-def _planner(mode, scheme="s4"):
-    e = StepEngine.__new__(StepEngine)                # host-side methods only: no device, no library
-    e.tasks, e.domains = PT.ACTIVE_TASKS[scheme], PT.PRETRAIN_DOMAINS[scheme]
-    e.max_rows, e.max_edges, e.S_MAX, e.KMAX, e.rng_mode, e._nprng = 16384, 131072, 64, 131072, mode, None
-    import random
-    e.neg_rng, e._neg_native, e.lp_merge, e.fwd_ranges, e.native_plan = random.Random(99), None, True, 2, True
+def _planner(mode, scheme="s4", **caps):
+    e = StepHost(PT.ACTIVE_TASKS[scheme], PT.PRETRAIN_DOMAINS[scheme], rng_mode=mode, neg_rng=random.Random(99), **caps)
+    e.lp_merge, e.fwd_ranges, e.native_plan = True, 2, True           # whatever the environment says
     return e
 
 
@@ -177,3 +177,42 @@ def test_plan_accepts_steps_with_absent_domains(mode, scheme):
             assert p.N == 0 and p.E == 0
         else:
             assert p.N > 0 and lens[np.isin(seg_dom, [e.domains.index(d) for d in present])].sum() == p.N
+
+
+def test_plan_refuses_a_step_beyond_the_capacities():
+    """The capacity checks of the GPU path hold on a host-only planner too, through the numpy layout and through plan_step: more
+    rows than max_rows; a tiny max_edges (the link-prediction rows are counted first, the edges of the stacked graph where no task
+    scores links); and the staging check of the packed upload arrays.  While rows, edges and link-prediction rows fit, the packed
+    arrays fit the staging capacities derived from them (cat64 <= 4 max_edges + 7 N), so that last check is reached by a planner
+    class with a lower capacity of its own."""
+    gen = torch.Generator().manual_seed(6)
+    inp = _Inp(S.pretrain_step_batches(gen, PT.PRETRAIN_DOMAINS["s4"]))
+    for native_plan in ([False, True] if hostdraw() is not None else [False]):
+        _check_capacities(inp, gen, native_plan)
+
+
+def _check_capacities(inp, gen, native_plan):
+    def planner(scheme="s4", **caps):
+        e = _planner("reference", scheme, **caps)
+        e.native_plan = native_plan
+        return e
+
+    e = planner()
+    art = e.draw(inp, gen)
+    assert (getattr(art, "raw", None) is not None) == (hostdraw() is not None)
+    p = e.plan(inp, art)
+    assert 64 < p.N <= e.max_rows and p.cat32.size <= e.i32_cap and p.cat64.size <= e.i64_cap
+    with pytest.raises(GnnmpError, match=r"step of \d+ rows / \d+ edges / \d+ segments exceeds the engine capacity"):
+        planner(max_rows=p.N - 1).plan(inp, art)
+    with pytest.raises(GnnmpError, match="too many link-prediction edges"):
+        planner(max_edges=16).plan(inp, art)
+    e2 = planner("s2", max_edges=16)
+    with pytest.raises(GnnmpError, match="exceeds the engine capacity"):
+        e2.plan(inp, e2.draw(inp, gen))
+    for cap, size in (("i32_cap", p.cat32.size), ("i64_cap", p.cat64.size)):
+        e = planner()
+        e.__class__ = type("ExactlyFull", (StepHost,), {cap: size})
+        e.plan(inp, art)                                   # accepted
+        e.__class__ = type("OneShort", (StepHost,), {cap: size - 1})
+        with pytest.raises(GnnmpError, match="staging buffer too small"):
+            e.plan(inp, art)

@@ -69,8 +69,8 @@ def test_engine_draw_uses_the_native_module_and_matches_python(monkeypatch):
     e.neg_rng = random.Random(4)
     art_native = e.draw(inp, g1)
     native_state = e.sync_neg_rng().getstate()
-    monkeypatch.setattr("gnn_pretraining_amd.engine._HOSTDRAW", None)
-    monkeypatch.setattr("gnn_pretraining_amd.engine._HOSTDRAW_TRIED", True)
+    monkeypatch.setattr("gnn_pretraining_amd.step_host._HOSTDRAW", None)
+    monkeypatch.setattr("gnn_pretraining_amd.step_host._HOSTDRAW_TRIED", True)
     e.neg_rng, e._neg_native = random.Random(4), None
     art_python = e.draw(inp, g2)
     assert torch.equal(g1.get_state(), g2.get_state())
@@ -127,8 +127,8 @@ def test_merged_pairs_hold_the_ordered_list_as_a_multiset(monkeypatch):
         pos = b.edge_index
         pairs, w, od = merge_mirrored_pairs(b, neg, 100, 7)
         with monkeypatch.context() as m:
-            m.setattr("gnn_pretraining_amd.engine._HOSTDRAW", None)
-            m.setattr("gnn_pretraining_amd.engine._HOSTDRAW_TRIED", True)
+            m.setattr("gnn_pretraining_amd.step_host._HOSTDRAW", None)
+            m.setattr("gnn_pretraining_amd.step_host._HOSTDRAW_TRIED", True)
             pairs_np, w_np, od_np = merge_mirrored_pairs(b, neg, 100, 7)
         assert np.array_equal(pairs, pairs_np) and np.array_equal(w, w_np) and np.array_equal(od, od_np)
         assert (pairs[0] <= pairs[1]).all() and pairs.dtype == np.int64 and w.dtype == np.float32 and od.dtype == np.int32 and od.shape == pairs.shape
