@@ -18,14 +18,14 @@ class TaskDesc(C.Structure):
     _fields_ = [("kind", i32), ("row0", i32), ("row1", i32), ("g_scale", p), ("loss_sum", p),
                 ("gemm_ws", p), ("gemm_ws_bytes", sz), ("loss_ws", p), ("loss_ws_bytes", sz),
                 ("mlp", Mlp2), ("idx", p), ("num_idx", i64), ("nfm_target", p),
-                ("ntx_n", i32 * MAXD), ("ntx_ws", p * MAXD), ("ntx_ws_bytes", sz * MAXD), ("ntx_sums", p), ("temperature", f32),
+                ("ntx_n", i32 * MAXD), ("ntx_ws", p), ("ntx_ws_bytes", sz), ("ntx_sums", p), ("temperature", f32),
                 ("pool_ptr", p), ("pool_gid", p), ("pool_B", i32), ("pool_r0", i32), ("pool_M", i32),
                 ("pool_mean", p), ("pool_max", p), ("g_mean", p), ("g_max", p), ("labels", p),
                 ("lp_K", i64), ("lp_edges", p), ("lp_labels", p), ("lp_pos", p),
-                ("lp_feat", p), ("lp_y1", p), ("lp_d1", p), ("lp_y2", p), ("lp_p", p), ("lp_gp", p), ("lp_gy2", p), ("lp_gy1", p),
+                ("lp_feat", p), ("lp_y1", p), ("lp_d1", p), ("lp_y2", p), ("lp_p", p), ("lp_gy2", p), ("lp_gy1", p),
                 ("lp_gfeat", p), ("lp_ghs", p), ("lp_ghd", p),
-                ("lp_off_w0", i64), ("lp_off_b0", i64), ("lp_off_w3", i64), ("lp_off_b3", i64),
-                ("lp_tg_w0", i64), ("lp_tg_b0", i64), ("lp_tg_w3", i64), ("lp_tg_b3", i64), ("lp_site", i32),
+                ("one_off_w0", i64), ("one_off_b0", i64), ("one_off_w3", i64), ("one_off_b3", i64),
+                ("one_tg_w0", i64), ("one_tg_b0", i64), ("one_tg_w3", i64), ("one_tg_b3", i64), ("one_site", i32),
                 ("da_labels", p), ("da_classes", i32), ("da_hidden", i32), ("da_lambda", f32), ("da_dropout", f32)]
 
 
@@ -53,6 +53,6 @@ class StepDesc(C.Structure):
                 ("enc_tg_w", i64 * MAXG), ("enc_tg_b", i64 * MAXG), ("enc_tg_gamma", i64 * MAXG), ("enc_tg_beta", i64 * MAXG),
                 ("off_mask_token", i64), ("tg_mask_token", i64), ("nfm_task", i32),
                 ("h", p * (LAYERS + 1)), ("layer", LayerDesc * LAYERS),
-                ("gA", p), ("gB", p), ("gW", p), ("gW2", p), ("rowdot", p), ("ga", p), ("gB2", p), ("gW3", p), ("gu_l", p * LAYERS), ("gz1_l", p * LAYERS),
-                ("bn_ws", p), ("bn_ws_bytes", sz), ("gemm_ws", p), ("gemm_ws_bytes", sz), ("loss_ws", p), ("loss_ws_bytes", sz),
+                ("gA", p), ("gB", p), ("gW", p), ("rowdot", p), ("ga", p), ("gu_l", p * LAYERS), ("gz1_l", p * LAYERS),
+                ("bn_ws", p), ("bn_ws_bytes", sz), ("gemm_ws", p), ("gemm_ws_bytes", sz),
                 ("task", TaskDesc * MAXT)]

@@ -251,8 +251,7 @@ class StepEngine(StepHost):
         self.gA, self.gB = f(R, H), f(R, H)                  # ping-pong [R,256] gradients
         self.ga = f(R, H)                                    # gradient w.r.t. a layer's aggregated input (own buffer: activations stay intact)
         self.gW = f(R, 2 * H)                                # [R,512] gradients
-        self.gW2 = f(R, 2 * H)
-        self.gB2, self.gW3 = f(R, H), f(R, 2 * H)
+        self.gW2 = f(R, 2 * H)                               # g_z1 of the Python sequence (the native executor has gz1_l)
         # per-layer g_u / g_z1 of the native executor's backward: aux never holds main back (gnnmp_step.h)
         self.gu_l, self.gz1_l = [f(R, H) for _ in range(Lr)], [f(R, 2 * H) for _ in range(Lr)]
         self.rowdot = f(Lr * R)                              # one slice per backward layer for the native executor (gnnmp_step.h)
@@ -314,10 +313,11 @@ class StepEngine(StepHost):
             "gp_in": (1024, H), "gp_y1": (1024, 2 * H), "gp_d1": (1024, 2 * H), "gp_y2": (1024, 16), "gp_g2": (1024, 16), "gp_g1": (1024, 2 * H), "gp_gin": (1024, H),
         }.items()}
         # (lp_lab: upload set below; merged rows keep two scores each -- one per ordered row of the reference's list)
-        self.lp_y2, self.lp_p, self.lp_gp, self.lp_gy2 = f(2 * self.KMAX), f(2 * self.KMAX), f(self.KMAX), f(2 * self.KMAX)
+        self.lp_y2, self.lp_p, self.lp_gy2 = f(2 * self.KMAX), f(2 * self.KMAX), f(2 * self.KMAX)
         self.gp_y2 = f(1024, GRAPH_PROPERTY_DIM)
         self.gp_g2 = f(1024, GRAPH_PROPERTY_DIM)
-        self.ntx_ws = [torch.empty(self.lib.gmp_nt_xent_grouped_workspace_bytes(self.D, 512, 128), dtype=torch.uint8, device=dev) for _ in range(2 * self.D)]
+        # one per contrastive head, keyed by the head's first scalar slot (0: node_contrast, D: graph_contrast)
+        self.ntx_ws = {s: torch.empty(self.lib.gmp_nt_xent_grouped_workspace_bytes(self.D, 512, 128), dtype=torch.uint8, device=dev) for s in (0, self.D)}
         # packed per-step index uploads (pinned staging; StepHost.plan checks a step against these capacities)
         # The host runs several steps ahead of the GPU (nothing in a step syncs), so the pinned staging buffers
         # form a ring: a slot is refilled only after the copy that last read it has completed (event per slot).
@@ -1269,20 +1269,23 @@ class StepEngine(StepHost):
             Ld.rm1, Ld.rv1, Ld.rm2, Ld.rv2 = ptr(bn1.running_mean), ptr(bn1.running_var), ptr(bn2.running_mean), ptr(bn2.running_var)
             Ld.a, Ld.z1, Ld.r1, Ld.z2 = ptr(self.a[l]), ptr(self.z1[l]), ptr(self.r1[l]), ptr(self.z2[l])
             Ld.m1, Ld.s1, Ld.m2, Ld.s2 = ptr(self.stat["m1"][l]), ptr(self.stat["s1"][l]), ptr(self.stat["m2"][l]), ptr(self.stat["s2"][l])
-        d.gA, d.gB, d.gW, d.gW2, d.rowdot = ptr(self.gA), ptr(self.gB), ptr(self.gW), ptr(self.gW2), ptr(self.rowdot)
-        d.ga = ptr(self.ga)
-        d.gB2, d.gW3 = ptr(self.gB2), ptr(self.gW3)
+        d.gA, d.gB, d.gW, d.rowdot, d.ga = ptr(self.gA), ptr(self.gB), ptr(self.gW), ptr(self.rowdot), ptr(self.ga)
         for l in range(GNN_NUM_LAYERS):
             d.gu_l[l], d.gz1_l[l] = ptr(self.gu_l[l]), ptr(self.gz1_l[l])
         d.bn_ws, d.bn_ws_bytes = ptr(self.bn_ws), self.bn_ws.numel()
         d.gemm_ws, d.gemm_ws_bytes = ptr(self.gemm_ws), self.gemm_ws.numel()
-        d.loss_ws, d.loss_ws_bytes = ptr(self.task_loss_ws[0]), self.task_loss_ws[0].numel()
         hd = self.hd
         mlp_cfg = {"node_feat_mask": (H, H, H, "nfm_in", "nfm_y1", "nfm_d1", "nfm_y2", "nfm_g", "nfm_g1", "nfm_gin"),   # (y2 is read again by the deferred loss sum)
                    "node_contrast": (H, H, 128, "nc_in", "nc_y1", "nc_d1", "nc_z", "nc_gz", "nc_g1", "nc_gin"),
                    "graph_contrast": (2 * H, H, 128, "gc_in", "gc_y1", "gc_d1", "gc_z", "gc_gz", "gc_g1", "gc_gin"),
                    "graph_prop": (H, 2 * H, GRAPH_PROPERTY_DIM, "gp_in", "gp_y1", "gp_d1", None, None, "gp_g1", "gp_gin")}
         sc = ptr(self.scal)
+
+        def head_offsets(ti, prefix):
+            """(field suffix, offset in flat, offset in task_grads) of the four tensors of the two-layer head `prefix`"""
+            return [(a, self.off[prefix + n], self._TG(ti, prefix + n))
+                    for a, n in (("w0", "mlp.0.weight"), ("b0", "mlp.0.bias"), ("w3", "mlp.3.weight"), ("b3", "mlp.3.bias"))]
+
         for ti, t in enumerate(self.tasks):
             td = d.task[ti]
             td.kind = TASK_KIND[t]
@@ -1294,10 +1297,8 @@ class StepEngine(StepHost):
                 m = td.mlp
                 m.k_in, m.k_hid, m.k_out, m.site = k_in, k_hid, k_out, 100 + ti
                 for i, dom in enumerate(D):
-                    for a, n in (("w0", "mlp.0.weight"), ("b0", "mlp.0.bias"), ("w3", "mlp.3.weight"), ("b3", "mlp.3.bias")):
-                        full = f"heads.{t}.{dom}.{n}"
-                        getattr(m, "off_" + a)[i] = self.off[full]
-                        getattr(m, "tg_" + a)[i] = self._TG(ti, full)
+                    for a, off, tg in head_offsets(ti, f"heads.{t}.{dom}."):
+                        getattr(m, "off_" + a)[i], getattr(m, "tg_" + a)[i] = off, tg
                 m.x, m.y1, m.d1, m.g_hid, m.g_in = ptr(hd[x]), ptr(hd[y1]), ptr(hd[d1]), ptr(hd[g_hid]), ptr(hd[g_in])
                 m.y2 = ptr(self.gp_y2) if t == "graph_prop" else ptr(hd[y2])
                 m.g_out = ptr(self.gp_g2) if t == "graph_prop" else ptr(hd[g_out])
@@ -1310,21 +1311,17 @@ class StepEngine(StepHost):
             if t == "domain_adv":
                 m = td.mlp
                 m.x, m.y1, m.d1, m.y2, m.g_out, m.g_hid, m.g_in = (ptr(hd[k]) for k in ("da_in", "da_y1", "da_d1", "da_logits", "da_glogits", "da_g1", "da_gin"))
-                for a, n in (("w0", "mlp.0.weight"), ("b0", "mlp.0.bias"), ("w3", "mlp.3.weight"), ("b3", "mlp.3.bias")):
-                    full = f"heads.domain_adv.classifier.{n}"
-                    setattr(td, "lp_off_" + a, self.off[full])
-                    setattr(td, "lp_tg_" + a, self._TG(ti, full))
-                td.lp_site, td.da_classes, td.da_hidden, td.da_dropout = 100 + ti, len(D), DA_HIDDEN, DA_DROPOUT
+                td.da_classes, td.da_hidden, td.da_dropout = len(D), DA_HIDDEN, DA_DROPOUT
             if t == "link_pred":
                 td.lp_labels = ptr(self.lp_lab)
                 for a in ("feat", "y1", "d1", "gy1", "gfeat", "ghs", "ghd"):
                     setattr(td, "lp_" + a, ptr(hd["lp_" + a]))
-                td.lp_y2, td.lp_p, td.lp_gp, td.lp_gy2 = ptr(self.lp_y2), ptr(self.lp_p), ptr(self.lp_gp), ptr(self.lp_gy2)
-                for a, n in (("w0", "mlp.0.weight"), ("b0", "mlp.0.bias"), ("w3", "mlp.3.weight"), ("b3", "mlp.3.bias")):
-                    full = f"heads.link_pred.predictor.{n}"
-                    setattr(td, "lp_off_" + a, self.off[full])
-                    setattr(td, "lp_tg_" + a, self._TG(ti, full))
-                td.lp_site = 100 + ti
+                td.lp_y2, td.lp_p, td.lp_gy2 = ptr(self.lp_y2), ptr(self.lp_p), ptr(self.lp_gy2)
+            if t in ("domain_adv", "link_pred"):      # one head shared by all domains
+                for a, off, tg in head_offsets(ti, "heads.domain_adv.classifier." if t == "domain_adv" else "heads.link_pred.predictor."):
+                    setattr(td, "one_off_" + a, off)
+                    setattr(td, "one_tg_" + a, tg)
+                td.one_site = 100 + ti
         self._desc = d
         main_h = torch.cuda.current_stream(self.device).cuda_stream
         self._stream_arr = (C.c_void_p * self.T)(*[(s.cuda_stream if s is not None else main_h) for s in self.task_streams])
@@ -1385,7 +1382,7 @@ class StepEngine(StepHost):
                 for di, n in enumerate(ns):
                     td.ntx_n[di] = n
                 ws = self._ntx_workspace(slot0, ns)
-                td.ntx_ws[0], td.ntx_ws_bytes[0] = ws.data_ptr(), ws.numel()
+                td.ntx_ws, td.ntx_ws_bytes = ws.data_ptr(), ws.numel()
             if t == "graph_contrast":
                 td.pool_ptr, td.pool_gid, td.pool_B, td.pool_r0, td.pool_M = p.d32["gc_ptr"], p.d64["gc_gid"], p.gc_B, p.gc_r0, p.gc_M
             if t == "graph_prop":

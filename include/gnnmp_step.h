@@ -46,9 +46,9 @@ typedef struct {
     /* gathers: NFM masked rows / NC common rows */
     const int64_t* idx; int64_t num_idx;
     float* nfm_target;
-    /* NT-Xent (NC, GC): per-domain pair counts and workspaces; sums land in ntx_sums[d] */
+    /* NT-Xent (NC, GC): per-domain pair counts and the one workspace of the grouped launch; sums land in ntx_sums[d] */
     int32_t ntx_n[GMP_STEP_MAX_DOMAINS];
-    void* ntx_ws[GMP_STEP_MAX_DOMAINS]; size_t ntx_ws_bytes[GMP_STEP_MAX_DOMAINS];
+    void* ntx_ws; size_t ntx_ws_bytes;
     float* ntx_sums;
     float temperature;
     /* read-out pooling (GC, GP) */
@@ -61,10 +61,10 @@ typedef struct {
        lp_pos [2, lp_K] names the one or two ordered rows each stands for (gnnmp.h gmp_lp_pair_*: a dropout mask, a score and a loss term per
        ordered row); lp_y2 / lp_p / lp_gy2 then hold 2 lp_K floats and lp_d1 is unused. */
     const int32_t* lp_pos;
-    float *lp_feat, *lp_y1, *lp_d1, *lp_y2, *lp_p, *lp_gp, *lp_gy2, *lp_gy1, *lp_gfeat, *lp_ghs, *lp_ghd;
-    /* offsets of a head shared by all domains: the LP scorer, and the domain classifier of GMP_TASK_DA */
-    int64_t lp_off_w0, lp_off_b0, lp_off_w3, lp_off_b3, lp_tg_w0, lp_tg_b0, lp_tg_w3, lp_tg_b3;
-    int32_t lp_site;
+    float *lp_feat, *lp_y1, *lp_d1, *lp_y2, *lp_p, *lp_gy2, *lp_gy1, *lp_gfeat, *lp_ghs, *lp_ghd;
+    /* the one two-layer head shared by all domains (the LP scorer, and the domain classifier of GMP_TASK_DA): offsets and dropout site */
+    int64_t one_off_w0, one_off_b0, one_off_w3, one_off_b3, one_tg_w0, one_tg_b0, one_tg_w3, one_tg_b3;
+    int32_t one_site;
     /* domain-adversarial task (scheme s5; tasks.py:315-343, heads.py:16-32,70-82): mean read-out -> gradient reversal
      * (backward scaled by -da_lambda) -> Linear 256->128, ReLU, Dropout(da_dropout), Linear 128->da_classes -> CE(sum)
      * against da_labels (the graph's domain index).  Buffers: mlp.x = pooled, mlp.y1/d1 hidden, mlp.y2 logits,
@@ -129,24 +129,25 @@ typedef struct {
     /* backbone */
     float* h[GMP_STEP_LAYERS + 1];
     gmp_layer_desc layer[GMP_STEP_LAYERS];
-    float *gA, *gB, *gW, *gW2, *rowdot;
+    float *gA, *gB, *gW;          /* [max_rows, 256] x 2 (gB: scratch of the encoder backward), [max_rows, 512] */
+    float* rowdot;                /* GMP_STEP_LAYERS * N floats: one slice per layer (the eps sum of a layer runs on aux, layers later) */
     float* ga;                    /* [max_rows, hidden] gradient w.r.t. a layer's aggregated input (scratch of the backward; a buffer of its
                                      own, so that every forward activation h[0..L], r1, z1, z2 is still intact after a step) */
-    float *gB2, *gW3;             /* second copies of gB / gW2: weight-gradient GEMMs of layer l read them on the aux stream
-                                     while layer l-1 already writes the other copy */
-    float* gu_l[GMP_STEP_LAYERS];   /* [N,256] per layer, or all NULL: g_u of every backward layer in a buffer of its own ... */
-    float* gz1_l[GMP_STEP_LAYERS];  /* [N,512] per layer: ... and g_z1, so the aux stream may lag main by any number of layers.
-                                       With them `rowdot` must hold GMP_STEP_LAYERS * N floats (one slice per layer). */
-    void* bn_ws; size_t bn_ws_bytes;
+    float* gu_l[GMP_STEP_LAYERS];   /* [N,256] per layer (required): g_u of every backward layer in a buffer of its own ... */
+    float* gz1_l[GMP_STEP_LAYERS];  /* [N,512] per layer (required): ... and g_z1, so the weight-gradient GEMMs that read them on the aux
+                                       stream may lag main by any number of layers */
+    void* bn_ws; size_t bn_ws_bytes;  /* at least 2 * GMP_STEP_LAYERS + 1 slices of gmp_bn_workspace_bytes(N, 512, S, max_seg): every BatchNorm
+                                         backward keeps its per-segment sums until aux has reduced them per task (GMP_ERR_WORKSPACE below that) */
     void* gemm_ws; size_t gemm_ws_bytes;
-    void* loss_ws; size_t loss_ws_bytes;
     gmp_task_desc task[GMP_STEP_MAX_TASKS];
 } gmp_step_desc;
 
 size_t gmp_step_desc_size(void);
 /* main: stream of the stacked pass; task_streams[t]: one stream per task head (may all equal main);
  * aux: stream for the CSR builds (may equal main).  NOT re-entrant: the call keeps its events, and what gmp_step_wait_grads
- * needs, in process-wide state (one engine steps at a time in a process; engines may alternate between calls). */
+ * needs, in process-wide state (one engine steps at a time in a process; engines may alternate between calls).
+ * GMP_ERR_ARG (bad sizes, a NULL gu_l[] / gz1_l[] / rowdot) and GMP_ERR_WORKSPACE (bn_ws below its 11 slices) are returned before
+ * anything is created or enqueued. */
 int gmp_pretrain_step_fwd_bwd(const gmp_step_desc* desc, gmp_stream_t main, const gmp_stream_t* task_streams,
                               gmp_stream_t aux);
 /* Data-parallel exchange beside the backward: make `stream` wait until the per-task gradients of one part of

@@ -273,8 +273,9 @@ def test_forward_in_row_ranges_gives_the_same_bits(monkeypatch, scheme, gates):
 @pytest.mark.parametrize("scheme", ["s4", "s5", "b2"])
 def test_gates_and_events_give_the_same_bits(monkeypatch, scheme):
     """The native executor carries its cross-stream dependencies by gates when every stream has a hardware queue of its own
-    (per-layer gradient buffers, eps sums and mask-token sum on aux, uploads on aux, one join gate) and by events otherwise
-    (GMP_STEP_GATES=0: the guarded double buffers, everything joined on main): same kernels on the same data, so the same bits."""
+    (eps sums and mask-token sum on aux, uploads on aux, one join gate) and by events otherwise (GMP_STEP_GATES=0: eps sums on main,
+    every weight-gradient GEMM on aux, aux and the heads' streams joined on main by event waits before the tail).  Both write g_u / g_z1
+    of every layer into buffers of their own: same kernels on the same data, so the same bits."""
     outs = []
     for gates in ("1", "0"):
         monkeypatch.setenv("GMP_STEP_GATES", gates)
