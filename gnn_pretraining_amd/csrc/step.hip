@@ -1,6 +1,6 @@
 // Whole-step executor: stacked forward, the five task heads (each on its own stream) and the stacked
 // backward of one pre-training step, enqueued from C++ so the host crosses the FFI once.  It is a
-// transcription of gnn_pretraining_amd/engine.py (_forward, _task_head, _backbone_backward): same entry
+// transcription of gnn_pretraining_amd/step_sequence.py (LaunchSequence: forward, heads, backward): same entry
 // points, same order, same buffers -> bitwise the same result (tests/test_gpu_engine.py).
 #include "../../include/gnnmp_step.h"
 #include <stdlib.h>

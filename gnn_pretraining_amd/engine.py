@@ -101,8 +101,9 @@ class DrawTicket:
 
 
 class StepEngine(StepHost):
-    """The device half of a step on top of StepHost's draws and layout: the parameter arena, streams and gates, the two executors (the
-    Python launch sequence below and csrc/step.hip through _fill_desc), the optimizer, the data-parallel exchange, the device draws."""
+    """The device half of a step on top of StepHost's draws and layout: the parameter arena, streams and gates, the native executor
+    (csrc/step.hip through _fill_desc), the optimizer, the data-parallel exchange, the device draws.  The same step launched kernel by
+    kernel from Python (native=False) is step_sequence.LaunchSequence, built on first use by sequence()."""
 
     def __init__(self, model: PretrainableGNN, tasks: Sequence[str], domains: Sequence[str], device,
                  max_rows: int = 16384, max_edges: int = 131072, seed: int = 0, shuffle_rng: Optional[random.Random] = None,
@@ -134,8 +135,7 @@ class StepEngine(StepHost):
         self.temperature = 0.5
         self.da_dropout = DA_DROPOUT
         self.grl_lambda = 0.0              # gradient-reversal strength of the domain-adversarial task (GRLScheduler)
-        self._p_cache, self._tg_cache = {}, {}
-        self._stream_handle = torch.cuda.current_stream(self.device).cuda_stream if torch.cuda.is_available() else 0
+        self._p_cache, self._sequence = {}, None
         self.host_ms = {"draw": 0.0, "plan": 0.0, "upload": 0.0, "launch": 0.0, "steps": 0}   # host time per phase (upload includes ring waits)
         self.dropout_p = DROPOUT_RATE
         self.max_grad_norm = 0.5
@@ -251,7 +251,6 @@ class StepEngine(StepHost):
         self.gA, self.gB = f(R, H), f(R, H)                  # ping-pong [R,256] gradients
         self.ga = f(R, H)                                    # gradient w.r.t. a layer's aggregated input (own buffer: activations stay intact)
         self.gW = f(R, 2 * H)                                # [R,512] gradients
-        self.gW2 = f(R, 2 * H)                               # g_z1 of the Python sequence (the native executor has gz1_l)
         # per-layer g_u / g_z1 of the native executor's backward: aux never holds main back (gnnmp_step.h)
         self.gu_l, self.gz1_l = [f(R, H) for _ in range(Lr)], [f(R, 2 * H) for _ in range(Lr)]
         self.rowdot = f(Lr * R)                              # one slice per backward layer for the native executor (gnnmp_step.h)
@@ -287,7 +286,6 @@ class StepEngine(StepHost):
             self.task_streams[ti] = b[1]
         self.task_gemm_ws = [torch.empty(24 << 20, dtype=torch.uint8, device=dev) for _ in range(self.T)]
         self.task_loss_ws = [torch.empty(self.lib.gmp_loss_workspace_bytes(R * H), dtype=torch.uint8, device=dev) for _ in range(self.T)]
-        self._cur_gemm_ws = self.gemm_ws
         # one slice per BatchNorm (11) + spare, each large enough for the long-segment regime (segments up to R rows): the
         # native executor keeps every BN backward's per-segment sums until the aux stream has reduced them per task
         self.bn_ws = torch.empty(12 * self.lib.gmp_bn_workspace_bytes(R, 2 * H, self.S_MAX, R), dtype=torch.uint8, device=dev)
@@ -299,7 +297,6 @@ class StepEngine(StepHost):
         self.lp_csr_ws = torch.empty(self.lib.gmp_csr_build_workspace_bytes(R, self.max_edges), dtype=torch.uint8, device=dev)
         self.lp_csr = [i32(R + 1), i32(self.max_edges), i32(self.max_edges), i32(R + 1), i32(self.max_edges), i32(self.max_edges)]
         self.loss_sums = torch.zeros(MAXT, device=dev)       # per-task loss SUMS of the last step
-        self.loss_ws = torch.empty(self.lib.gmp_loss_workspace_bytes(R * H), dtype=torch.uint8, device=dev)
         # head workspaces (rows bounded by max_rows / edges)
         self.hd = {k: f(n, c) for k, (n, c) in {
             "nfm_in": (R, H), "nfm_y1": (R, H), "nfm_d1": (R, H), "nfm_y2": (R, H), "nfm_tgt": (R, H), "nfm_g": (R, H), "nfm_g1": (R, H), "nfm_gin": (R, H),
@@ -519,33 +516,6 @@ class StepEngine(StepHost):
                 art[t][d] = (views[0], views[1])
         return art
 
-    # ------------------------------------------------------------------ device helpers
-    def _st(self):
-        """hipStream_t the launches go to.  Cached: torch.cuda.current_stream() costs ~5 us and a step makes ~300 launches."""
-        return self._stream_handle
-
-    def _use_stream(self, stream=None) -> None:
-        self._stream_handle = (stream or torch.cuda.current_stream(self.device)).cuda_stream
-
-    def _chk(self, rc: int, what: str) -> None:
-        if rc:
-            L.check(rc, what)
-
-    def _gemm(self, mode, A, B, bias, Cc, M, N, K, lda, ldb, ldc, relu=False, accumulate=False):
-        self._chk(self.lib.gmp_gemm_f32(mode, A, B, bias, Cc, M, N, K, lda, ldb, ldc, 1.0, int(accumulate), int(relu), None, 0, self._st()), "gemm")
-
-    def _gemm_g(self, mode, A, B, bias, Cc, rows, boff, biasoff, coff, asum, asumoff, M_tn, N, K, lda, ldb, ldc, relu=False):
-        G = len(rows) - 1
-        self._chk(self.lib.gmp_gemm_f32_grouped(mode, A, B, bias, Cc, G, _i32(rows), None if boff is None else _i64(boff),
-                                                None if biasoff is None else _i64(biasoff), None if coff is None else _i64(coff),
-                                                asum, None if asumoff is None else _i64(asumoff), M_tn, N, K, lda, ldb, ldc, 1.0, 0,
-                                                int(relu), self._cur_gemm_ws.data_ptr() if mode == TN else None, self._cur_gemm_ws.numel(),
-                                                self._st()), "gemm_grouped")
-
-    def _bn_cfg(self, relu: bool, dropout: bool, site: int) -> L.BnConfig:
-        p = self.dropout_p if (dropout and self.model.training) else 0.0
-        return L.BnConfig(int(self.model.training), int(relu), 1e-5, 0.1, p, (self.seed * 1000003 + self.step_count) & (2 ** 64 - 1), site)
-
     # ------------------------------------------------------------------ one step
     def prepare(self, inp: StepInputs, gen: torch.Generator, ticket: Optional[DrawTicket] = None):
         """Host half of a step (all RNG draws + the segment layout); may run on another thread ahead of time.  `ticket`: the
@@ -557,7 +527,7 @@ class StepEngine(StepHost):
              order: Optional[List[str]] = None, apply_update: bool = True, prepared=None) -> None:
         """Forward, backward, PCGrad, clip, AdamW for one step.  Nothing is read back: losses stay in
         self.loss_sums / self.plan_sizes until someone asks (losses())."""
-        self._use_stream()
+        main_h = torch.cuda.current_stream(self.device).cuda_stream
         if self.rng_mode == "device":
             # Device draws ride the aux stream, i.e. they run behind whatever the launcher has already enqueued there: the launcher
             # therefore keeps at most two steps in front of the GPU (enough to keep it fed: enqueueing a step takes half a step), so a
@@ -580,9 +550,8 @@ class StepEngine(StepHost):
         if self.native:
             self._forward_backward_native(p, inp)        # one C call enqueues the whole forward/heads/backward
         else:
-            self._forward(p, inp)
-            self._heads_and_backward(p, inp)
-        self._optimizer(p, order, apply_update)
+            self.sequence().run(p, inp)                  # the same launches one by one (step_sequence.py)
+        self._optimizer(p, order, apply_update, main_h)
         t4 = _t.perf_counter()
         h = self.host_ms
         h["draw"] += (t1 - t0) * 1e3; h["plan"] += (t2 - t1) * 1e3; h["upload"] += (t3 - t2) * 1e3; h["launch"] += (t4 - t3) * 1e3
@@ -599,6 +568,18 @@ class StepEngine(StepHost):
             self._bn_calls += int((lens > 0).sum())
             for di in range(self.D):
                 self._bn_calls_dom[di] += int(((lens > 0) & (dom == di)).sum())
+
+    def sequence(self):
+        """The Python launch sequence over this engine's arena (native=False; scripts time its forward)."""
+        if self._sequence is None:
+            from .step_sequence import LaunchSequence
+            self._sequence = LaunchSequence(self)
+        return self._sequence
+
+    @property
+    def dropout_seed(self) -> int:
+        """Seed of every dropout mask of the step about to run: both executors draw the same masks from it."""
+        return (self.seed * 1000003 + self.step_count) & (2 ** 64 - 1)
 
     def flush_counters(self) -> None:
         """Bring every BatchNorm's num_batches_tracked up to date (it only matters for the saved state_dict -- momentum is
@@ -658,7 +639,11 @@ class StepEngine(StepHost):
             self.has.copy_(torch.from_numpy(self.has_static).to(self.device))
             self._has_dirty = False
 
-    # ---- forward -----------------------------------------------------------------------------------
+    # ---- what both executors read: error check, addresses in the arena, plan helpers (more beside _fill_desc) ------------
+    def _chk(self, rc: int, what: str) -> None:
+        if rc:
+            L.check(rc, what)
+
     def _P(self, name: str) -> int:
         v = self._p_cache.get(name)
         if v is None:
@@ -669,293 +654,14 @@ class StepEngine(StepHost):
         """Float offset of (task t, tensor) inside the [T, P] per-task gradient buffer."""
         return t * self.P + self.off[name]
 
-    def _TGs(self, name: str) -> "C.Array":
-        """Per-task offsets of one tensor (static: cached as a ready ctypes array)."""
-        a = self._tg_cache.get(name)
-        if a is None:
-            a = self._tg_cache[name] = _i64([t * self.P + self.off[name] for t in range(self.T)])
-        return a
+    def head_offsets(self, ti: int, prefix: str):
+        """(field suffix, offset in flat, offset in task_grads) of the four tensors of the two-layer head `prefix`"""
+        return [(a, self.off[prefix + n], self._TG(ti, prefix + n))
+                for a, n in (("w0", "mlp.0.weight"), ("b0", "mlp.0.bias"), ("w3", "mlp.3.weight"), ("b3", "mlp.3.bias"))]
 
     @staticmethod
     def _lp_segmented(p: StepPlan) -> bool:
         return p.lp_S > 0 and p.lp_max_rows <= SEG_CSR_MAX_ROWS and p.lp_max_edges <= SEG_CSR_MAX_EDGES
-
-    def _forward(self, p: StepPlan, inp: StepInputs) -> None:
-        lib, st, N, D, P = self.lib, self._st(), p.N, self.domains, self._P
-        c = self.csr
-        main = torch.cuda.current_stream(self.device)
-        # both CSR builds depend only on the uploaded indices: they run beside the encoders on the aux stream
-        ev_up = torch.cuda.Event(); ev_up.record(main)
-        self.aux_stream.wait_event(ev_up)
-        with torch.cuda.stream(self.aux_stream):
-            ast = self.aux_stream.cuda_stream
-            if p.max_seg <= SEG_CSR_MAX_ROWS and p.max_seg_edges <= SEG_CSR_MAX_EDGES:      # block diagonal: one workgroup per segment
-                self._chk(lib.gmp_csr_build_segmented(p.d64["edge_index"], N, p.E, p.d32["seg_ptr"], p.d32["seg_eptr"], p.S, p.max_seg,
-                                                      p.max_seg_edges, c[0].data_ptr(), c[1].data_ptr(), c[2].data_ptr(), c[3].data_ptr(),
-                                                      c[4].data_ptr(), c[5].data_ptr(), self.csr_status.data_ptr(), ast), "csr_build_segmented")
-            else:
-                self._chk(lib.gmp_csr_build(p.d64["edge_index"], N, p.E, c[0].data_ptr(), c[1].data_ptr(), c[2].data_ptr(), c[3].data_ptr(),
-                                            c[4].data_ptr(), c[5].data_ptr(), self.csr_status.data_ptr(), self.csr_ws.data_ptr(),
-                                            self.csr_ws.numel(), ast), "csr_build")
-            ev_csr = torch.cuda.Event(); ev_csr.record(self.aux_stream)
-            if "link_pred" in self.tasks:
-                lc = self.lp_csr
-                if self._lp_segmented(p):
-                    self._chk(lib.gmp_csr_build_segmented(p.d64["lp_edges"], p.lp_rows_end, p.lp_K, p.d32["lp_seg_ptr"], p.d32["lp_seg_eptr"], p.lp_S,
-                                                          p.lp_max_rows, p.lp_max_edges, lc[0].data_ptr(), lc[1].data_ptr(), lc[2].data_ptr(),
-                                                          lc[3].data_ptr(), lc[4].data_ptr(), lc[5].data_ptr(), self.lp_csr_status.data_ptr(), ast), "lp csr (segmented)")
-                else:
-                    self._chk(lib.gmp_csr_build(p.d64["lp_edges"], N, p.lp_K, lc[0].data_ptr(), lc[1].data_ptr(), lc[2].data_ptr(), lc[3].data_ptr(),
-                                                lc[4].data_ptr(), lc[5].data_ptr(), self.lp_csr_status.data_ptr(), self.lp_csr_ws.data_ptr(),
-                                                self.lp_csr_ws.numel(), ast), "lp csr")
-            p.ev_lpcsr = torch.cuda.Event(); p.ev_lpcsr.record(self.aux_stream)
-        w_off = [self.off[f"input_encoders.{d}.linear.weight"] for d in D]
-        b_off = [self.off[f"input_encoders.{d}.linear.bias"] for d in D]
-        d_in = [DOMAIN_DIMENSIONS[d] for d in D]
-        self._chk(lib.gmp_encoder_fwd(inp.x_all.data_ptr(), inp.x_all.size(0), N, p.S, p.d32["src_row"], p.d32["seg_ptr"], p.d32["seg_dom"], p.d64.get("rowmask"),
-                                      p.d32["tiles"], p.num_tiles, self.flat.data_ptr(), len(D), _i64(w_off), _i64(b_off), _i32(d_in),
-                                      self.dpad, self.z0.data_ptr(), st), "encoder_fwd")
-        cfg = self._bn_cfg(True, True, 1)
-        e0 = f"input_encoders.{D[0]}."
-        self._chk(lib.gmp_bn_fwd(self.z0.data_ptr(), None, p.d32["seg_ptr"], p.d32["seg_dom"], p.S, p.max_seg, N, H,
-                                 P(e0 + "batch_norm.weight"), P(e0 + "batch_norm.bias"), self.enc_rm.data_ptr(), self.enc_rv.data_ptr(),
-                                 self.enc_mean.data_ptr(), self.enc_rstd.data_ptr(), self.h[0].data_ptr(), C.byref(cfg),
-                                 self.bn_ws.data_ptr(), self.bn_ws.numel(), st), "bn_fwd encoders")
-        if "node_feat_mask" in self.tasks and p.nfm_rows[-1]:
-            M = p.nfm_rows[-1]
-            self._chk(lib.gmp_row_gather(self.h[0].data_ptr(), p.d64["nfm_idx"], None, self.hd["nfm_tgt"].data_ptr(), M, N, H, st), "nfm target")
-            self._chk(lib.gmp_row_fill(self.h[0].data_ptr(), p.d64["nfm_idx"], P("mask_token"), M, N, H, 1, st), "nfm mask")
-        main.wait_event(ev_csr)
-        for l in range(GNN_NUM_LAYERS):
-            pre = f"gnn_backbone.layers.{l}."
-            layer = self.model.gnn_backbone.layers[l]
-            self._chk(lib.gmp_gin_aggregate_fwd(self.h[l].data_ptr(), c[0].data_ptr(), c[1].data_ptr(), P(pre + "gin_conv.eps"),
-                                                self.a[l].data_ptr(), N, H, st), "aggregate")
-            self._gemm(NT, self.a[l].data_ptr(), P(pre + "gin_conv.nn.0.weight"), P(pre + "gin_conv.nn.0.bias"), self.z1[l].data_ptr(),
-                       N, 2 * H, H, H, H, 2 * H)
-            bn1 = layer.gin_conv.nn[1]
-            cfg = self._bn_cfg(True, False, 0)
-            self._chk(lib.gmp_bn_fwd(self.z1[l].data_ptr(), None, p.d32["seg_ptr"], None, p.S, p.max_seg, N, 2 * H,
-                                     P(pre + "gin_conv.nn.1.weight"), P(pre + "gin_conv.nn.1.bias"), bn1.running_mean.data_ptr(),
-                                     bn1.running_var.data_ptr(), self.stat["m1"][l].data_ptr(), self.stat["s1"][l].data_ptr(),
-                                     self.r1[l].data_ptr(), C.byref(cfg), self.bn_ws.data_ptr(), self.bn_ws.numel(), st), "bn1")
-            self._gemm(NT, self.r1[l].data_ptr(), P(pre + "gin_conv.nn.3.weight"), P(pre + "gin_conv.nn.3.bias"), self.z2[l].data_ptr(),
-                       N, H, 2 * H, 2 * H, 2 * H, H)
-            bn2 = layer.batch_norm
-            cfg = self._bn_cfg(True, True, 10 + l)
-            self._chk(lib.gmp_bn_fwd(self.z2[l].data_ptr(), self.h[l].data_ptr(), p.d32["seg_ptr"], None, p.S, p.max_seg, N, H,
-                                     P(pre + "batch_norm.weight"), P(pre + "batch_norm.bias"), bn2.running_mean.data_ptr(),
-                                     bn2.running_var.data_ptr(), self.stat["m2"][l].data_ptr(), self.stat["s2"][l].data_ptr(),
-                                     self.h[l + 1].data_ptr(), C.byref(cfg), self.bn_ws.data_ptr(), self.bn_ws.numel(), st), "bn2")
-
-    # ---- head helpers ------------------------------------------------------------------------------
-    def _drop(self, src: Tensor, dst: Tensor, numel: int, site: int, p: Optional[float] = None) -> Tensor:
-        """dropout(src) -> dst (returns the tensor holding the result; p == 0 aliases src)."""
-        p = self.dropout_p if p is None else p
-        if not self.model.training or p <= 0:
-            return src
-        self._chk(self.lib.gmp_dropout_fwd(src.data_ptr(), dst.data_ptr(), numel, p,
-                                           (self.seed * 1000003 + self.step_count) & (2 ** 64 - 1), site, self._st()), "dropout")
-        return dst
-
-    def _relu_drop_bwd(self, g: Tensor, act: Tensor, out: Tensor, numel: int, site: int, p: Optional[float] = None) -> None:
-        p = (self.dropout_p if p is None else p) if self.model.training else 0.0
-        self._chk(self.lib.gmp_relu_dropout_bwd(g.data_ptr(), act.data_ptr(), out.data_ptr(), numel, p,
-                                                (self.seed * 1000003 + self.step_count) & (2 ** 64 - 1), site, self._st()), "relu_dropout_bwd")
-
-    def _mlp2_grouped(self, ti: int, task: str, x: Tensor, rows: List[int], k_in: int, k_hid: int, k_out: int, bufs, site: int):
-        """Per-domain two-layer MLPHead (Linear-ReLU-Dropout-Linear) over row groups; returns output tensor."""
-        y1, d1, y2 = bufs
-        D = self.domains
-        w0 = [self.off[f"heads.{task}.{d}.mlp.0.weight"] for d in D]
-        b0 = [self.off[f"heads.{task}.{d}.mlp.0.bias"] for d in D]
-        w3 = [self.off[f"heads.{task}.{d}.mlp.3.weight"] for d in D]
-        b3 = [self.off[f"heads.{task}.{d}.mlp.3.bias"] for d in D]
-        fp = self.flat.data_ptr()
-        self._gemm_g(NT, x.data_ptr(), fp, fp, y1.data_ptr(), rows, w0, b0, None, None, None, 0, k_hid, k_in, k_in, k_in, k_hid, relu=True)
-        d1 = self._drop(y1, d1, rows[-1] * k_hid, site)
-        self._gemm_g(NT, d1.data_ptr(), fp, fp, y2.data_ptr(), rows, w3, b3, None, None, None, 0, k_out, k_hid, k_hid, k_hid, k_out)
-        return d1
-
-    def _mlp2_grouped_bwd(self, ti: int, task: str, x: Tensor, rows: List[int], k_in: int, k_hid: int, k_out: int, y1: Tensor, d1: Tensor,
-                          g_out: Tensor, g_hid: Tensor, g_in: Tensor, site: int) -> None:
-        """Backward of _mlp2_grouped: per-domain weight/bias gradients go straight into task_grads[ti]."""
-        D, tg, fp = self.domains, self.task_grads.data_ptr(), self.flat.data_ptr()
-        TG = self._TG
-        w0 = [self.off[f"heads.{task}.{d}.mlp.0.weight"] for d in D]
-        w3 = [self.off[f"heads.{task}.{d}.mlp.3.weight"] for d in D]
-        # dW3 = g_out^T d1, db3 = colsum(g_out)
-        self._gemm_g(TN, g_out.data_ptr(), d1.data_ptr(), None, tg, rows, None, None, [TG(ti, f"heads.{task}.{d}.mlp.3.weight") for d in D],
-                     tg, [TG(ti, f"heads.{task}.{d}.mlp.3.bias") for d in D], k_out, k_hid, 0, k_out, k_hid, k_hid)
-        # g_d1 = g_out W3
-        self._gemm_g(NN, g_out.data_ptr(), fp, None, g_hid.data_ptr(), rows, w3, None, None, None, None, 0, k_hid, k_out, k_out, k_hid, k_hid)
-        self._relu_drop_bwd(g_hid, y1, g_hid, rows[-1] * k_hid, site)
-        self._gemm_g(TN, g_hid.data_ptr(), x.data_ptr(), None, tg, rows, None, None, [TG(ti, f"heads.{task}.{d}.mlp.0.weight") for d in D],
-                     tg, [TG(ti, f"heads.{task}.{d}.mlp.0.bias") for d in D], k_hid, k_in, 0, k_hid, k_in, k_in)
-        self._gemm_g(NN, g_hid.data_ptr(), fp, None, g_in.data_ptr(), rows, w0, None, None, None, None, 0, k_in, k_hid, k_hid, k_in, k_in)
-
-    # ---- heads + backward --------------------------------------------------------------------------
-    def _heads_and_backward(self, p: StepPlan, inp: StepInputs) -> None:
-        lib, st, N, D, P, TG = self.lib, self._st(), p.N, self.domains, self._P, self._TG
-        hd, tg = self.hd, self.task_grads.data_ptr()
-        hL = self.h[GNN_NUM_LAYERS]
-        gH = self.gA
-        gH[:N].zero_()
-        sc = self.scal.data_ptr()
-        T_ = float(self.temperature)
-        main = torch.cuda.current_stream(self.device)
-        ev_fwd = torch.cuda.Event(); ev_fwd.record(main)
-        done = []
-        order = [ti for ti in range(self.T) if self.task_streams[ti] is not None] + [ti for ti in range(self.T) if self.task_streams[ti] is None]
-        for ti in order:                                     # heads on other streams first, the ones packed onto main last
-            t = self.tasks[ti]
-            ts = main if self.task_streams[ti] is None else self.task_streams[ti]
-            if ts is not main:
-                ts.wait_event(ev_fwd)
-            if t == "link_pred":
-                ts.wait_event(p.ev_lpcsr)
-            with torch.cuda.stream(ts):
-                self._use_stream(ts)
-                self._cur_gemm_ws, self.loss_ws = self.task_gemm_ws[ti], self.task_loss_ws[ti]
-                self._task_head(p, inp, ti, t, hL, gH, sc, T_)
-                if ts is not main:
-                    ev = torch.cuda.Event(); ev.record(ts)
-                    done.append(ev)
-        self._use_stream(main)
-        self._cur_gemm_ws = self.gemm_ws
-        self.loss_ws = self.task_loss_ws[0]
-        for ev in done:
-            main.wait_event(ev)
-        main.wait_event(p.ev_lpcsr)
-        self._backbone_backward(p, inp)
-
-    def _task_head(self, p: StepPlan, inp: StepInputs, ti: int, t: str, hL: Tensor, gH: Tensor, sc: int, T_: float) -> None:
-        """Head forward, loss, and head backward of ONE task (writes its rows of gH and its slots of task_grads)."""
-        lib, st, N, D, P, TG = self.lib, self._st(), p.N, self.domains, self._P, self._TG
-        hd, tg = self.hd, self.task_grads.data_ptr()
-        gs = sc + 4 * ti                                        # device scalar 1/size_t: d total_t / d loss_sum
-        ls = self.loss_sums.data_ptr() + 4 * ti
-        if t == "node_feat_mask":
-            rows, M = p.nfm_rows, p.nfm_rows[-1]
-            if M == 0:
-                return
-            self._chk(lib.gmp_row_gather(hL.data_ptr(), p.d64["nfm_idx"], None, hd["nfm_in"].data_ptr(), M, N, H, st), "nfm gather")
-            d1 = self._mlp2_grouped(ti, t, hd["nfm_in"], rows, H, H, H, (hd["nfm_y1"], hd["nfm_d1"], hd["nfm_y2"]), 100 + ti)
-            self._chk(lib.gmp_mse_sum_fwd(hd["nfm_y2"].data_ptr(), hd["nfm_tgt"].data_ptr(), M * H, ls, self.loss_ws.data_ptr(), self.loss_ws.numel(), st), "mse")
-            self._chk(lib.gmp_mse_sum_bwd(hd["nfm_y2"].data_ptr(), hd["nfm_tgt"].data_ptr(), gs, hd["nfm_g"].data_ptr(), M * H, st), "mse bwd")
-            self._mlp2_grouped_bwd(ti, t, hd["nfm_in"], rows, H, H, H, hd["nfm_y1"], d1, hd["nfm_g"], hd["nfm_g1"], hd["nfm_y2"], 100 + ti)
-            self._chk(lib.gmp_row_fill(gH.data_ptr(), p.d64["nfm_idx"], hd["nfm_y2"].data_ptr(), M, N, H, 0, st), "nfm scatter")
-        elif t == "link_pred":
-            K = p.lp_K
-            w0, b0 = P("heads.link_pred.predictor.mlp.0.weight"), P("heads.link_pred.predictor.mlp.0.bias")
-            w3, b3 = P("heads.link_pred.predictor.mlp.3.weight"), P("heads.link_pred.predictor.mlp.3.bias")
-            self._chk(lib.gmp_lp_edge_features_fwd(hL.data_ptr(), p.d64["lp_edges"], hd["lp_feat"].data_ptr(), N, K, H, st), "lp feat")
-            self._gemm(NT, hd["lp_feat"].data_ptr(), w0, b0, hd["lp_y1"].data_ptr(), K, H, 3 * H, 3 * H, 3 * H, H, relu=True)
-            # the 256 -> 1 layer as a row dot product / outer product / weighted column sum (csrc/elementwise.hip), as in csrc/step.hip
-            pdrop = self.dropout_p if (self.model.training and self.dropout_p > 0) else 0.0
-            dseed = (self.seed * 1000003 + self.step_count) & (2 ** 64 - 1)
-            d1 = hd["lp_d1"] if pdrop > 0 else hd["lp_y1"]
-            pos = p.d32.get("lp_pos")            # merged rows: the ordered row(s) each stands for (a dropout mask per ordered row)
-            if pos is not None:
-                self._chk(lib.gmp_lp_pair_rowdot_fwd(hd["lp_y1"].data_ptr(), w3, b3, pos, self.lp_y2.data_ptr(), K, H, pdrop, dseed, 100 + ti, st), "lp pair rowdot")
-                self._chk(lib.gmp_lp_pair_sigmoid_bce_fwd_bwd(self.lp_y2.data_ptr(), self.lp_lab.data_ptr(), pos, K, gs, ls, self.lp_p.data_ptr(),
-                                                              self.lp_gy2.data_ptr(), self.loss_ws.data_ptr(), self.loss_ws.numel(), st), "pair sigmoid+bce")
-                self._chk(lib.gmp_lp_pair_outer_bwd(self.lp_gy2.data_ptr(), w3, hd["lp_y1"].data_ptr(), pos, hd["lp_gy1"].data_ptr(), K, H, pdrop, dseed,
-                                                    100 + ti, st), "lp pair outer")
-            else:
-                self._chk(lib.gmp_dropout_rowdot_fwd(hd["lp_y1"].data_ptr(), w3, b3, hd["lp_d1"].data_ptr(), self.lp_y2.data_ptr(), K, H, pdrop, dseed,
-                                                     100 + ti, st), "lp rowdot")
-                self._chk(lib.gmp_sigmoid_bce_signed_sum_fwd_bwd(self.lp_y2.data_ptr(), self.lp_lab.data_ptr(), K, gs, ls, self.lp_p.data_ptr(),
-                                                          self.lp_gy2.data_ptr(), self.loss_ws.data_ptr(), self.loss_ws.numel(), st), "sigmoid+bce")
-                self._chk(lib.gmp_outer_relu_dropout_bwd(self.lp_gy2.data_ptr(), w3, hd["lp_y1"].data_ptr(), hd["lp_gy1"].data_ptr(), K, H, pdrop, dseed,
-                                                         100 + ti, st), "lp outer")
-            one = [0, K]
-            # dW0 with db0 riding along (column sums of the A tile already in LDS)
-            self._gemm_g(TN, hd["lp_gy1"].data_ptr(), hd["lp_feat"].data_ptr(), None, tg, one, None, None,
-                         [TG(ti, "heads.link_pred.predictor.mlp.0.weight")], tg, [TG(ti, "heads.link_pred.predictor.mlp.0.bias")], H, 3 * H, 0, H, 3 * H, 3 * H)
-            if pos is not None:
-                self._chk(lib.gmp_lp_pair_weighted_colsum(self.lp_gy2.data_ptr(), hd["lp_y1"].data_ptr(), pos, tg + 4 * TG(ti, "heads.link_pred.predictor.mlp.3.weight"),
-                                                          tg + 4 * TG(ti, "heads.link_pred.predictor.mlp.3.bias"), K, H, pdrop, dseed, 100 + ti,
-                                                          self._cur_gemm_ws.data_ptr(), self._cur_gemm_ws.numel(), st), "lp pair dW3")
-            else:
-                self._chk(lib.gmp_weighted_colsum(self.lp_gy2.data_ptr(), d1.data_ptr(), tg + 4 * TG(ti, "heads.link_pred.predictor.mlp.3.weight"),
-                                                  tg + 4 * TG(ti, "heads.link_pred.predictor.mlp.3.bias"), K, H, self._cur_gemm_ws.data_ptr(),
-                                                  self._cur_gemm_ws.numel(), st), "lp dW3")
-            self._gemm(NN, hd["lp_gy1"].data_ptr(), w0, None, hd["lp_gfeat"].data_ptr(), K, 3 * H, H, H, 3 * H, 3 * H)
-            self._chk(lib.gmp_lp_edge_features_bwd(hd["lp_gfeat"].data_ptr(), hL.data_ptr(), p.d64["lp_edges"], hd["lp_ghs"].data_ptr(),
-                                                   hd["lp_ghd"].data_ptr(), N, K, H, st), "lp feat bwd")
-            # reduce the per-edge gradients onto nodes -- only over this task's own rows (other tasks' heads are
-            # writing their rows of gH concurrently on their own streams)
-            c = self.lp_csr
-            r0, r1 = p.task_row[ti], p.task_row[ti + 1]
-            g_rows = gH.data_ptr() + 4 * H * r0
-            self._chk(lib.gmp_segment_sum(hd["lp_ghs"].data_ptr(), c[3].data_ptr() + 4 * r0, c[5].data_ptr(), g_rows, r1 - r0, H, 0, 1, st), "lp g by src")
-            self._chk(lib.gmp_segment_sum(hd["lp_ghd"].data_ptr(), c[0].data_ptr() + 4 * r0, c[2].data_ptr(), g_rows, r1 - r0, H, 0, 1, st), "lp g by dst")
-        elif t == "node_contrast":
-            rows, M = p.nc_rows, p.nc_rows[-1]
-            if M == 0:
-                return
-            self._chk(lib.gmp_row_gather(hL.data_ptr(), p.d64["nc_idx"], None, hd["nc_in"].data_ptr(), M, N, H, st), "nc gather")
-            d1 = self._mlp2_grouped(ti, t, hd["nc_in"], rows, H, H, 128, (hd["nc_y1"], hd["nc_d1"], hd["nc_z"]), 100 + ti)
-            self._nt_xent_domains(p.nc_n, rows, hd["nc_z"], hd["nc_gz"], gs, ls, T_, 0)
-            self._mlp2_grouped_bwd(ti, t, hd["nc_in"], rows, H, H, 128, hd["nc_y1"], d1, hd["nc_gz"], hd["nc_g1"], hd["nc_gin"], 100 + ti)
-            self._chk(lib.gmp_row_fill(gH.data_ptr(), p.d64["nc_idx"], hd["nc_gin"].data_ptr(), M, N, H, 0, st), "nc scatter")
-        elif t == "graph_contrast":
-            rows, B = p.gc_rows, p.gc_B
-            if B == 0:
-                return
-            self._chk(lib.gmp_segment_sum(hL.data_ptr(), p.d32["gc_ptr"], None, hd["gc_mean"].data_ptr(), B, H, 1, 0, st), "gc mean")
-            self._chk(lib.gmp_segment_max_fwd(hL.data_ptr(), p.d32["gc_ptr"], hd["gc_max"].data_ptr(), B, H, st), "gc max")
-            torch.cat([hd["gc_mean"][:B], hd["gc_max"][:B]], dim=1, out=hd["gc_in"][:B])
-            d1 = self._mlp2_grouped(ti, t, hd["gc_in"], rows, 2 * H, H, 128, (hd["gc_y1"], hd["gc_d1"], hd["gc_z"]), 100 + ti)
-            self._nt_xent_domains(p.gc_n, rows, hd["gc_z"], hd["gc_gz"], gs, ls, T_, self.D)
-            self._mlp2_grouped_bwd(ti, t, hd["gc_in"], rows, 2 * H, H, 128, hd["gc_y1"], d1, hd["gc_gz"], hd["gc_g1"], hd["gc_gin"], 100 + ti)
-            hd["gc_gmean"][:B].copy_(hd["gc_gin"][:B, :H])
-            hd["gc_gmax"][:B].copy_(hd["gc_gin"][:B, H:])
-            g_rows = gH.data_ptr() + 4 * H * p.gc_r0
-            self._chk(lib.gmp_row_gather(hd["gc_gmean"].data_ptr(), p.d64["gc_gid"], p.d32["gc_ptr"], g_rows, p.gc_M, B, H, st), "gc mean bwd")
-            self._chk(lib.gmp_segment_max_bwd(hd["gc_gmax"].data_ptr(), hL.data_ptr(), hd["gc_max"].data_ptr(), p.d32["gc_ptr"], gH.data_ptr(),
-                                              B, H, 1, st), "gc max bwd")
-        elif t == "graph_prop":
-            rows, B = p.gp_rows, p.gp_B
-            G = GRAPH_PROPERTY_DIM
-            self._chk(lib.gmp_segment_sum(hL.data_ptr(), p.d32["gp_ptr"], None, hd["gp_in"].data_ptr(), B, H, 1, 0, st), "gp mean")
-            d1 = self._mlp2_grouped(ti, t, hd["gp_in"], rows, H, 2 * H, G, (hd["gp_y1"], hd["gp_d1"], self.gp_y2), 100 + ti)
-            self._chk(lib.gmp_mse_sum_fwd(self.gp_y2.data_ptr(), inp.graph_props.data_ptr(), B * G, ls, self.loss_ws.data_ptr(), self.loss_ws.numel(), st), "gp mse")
-            self._chk(lib.gmp_mse_sum_bwd(self.gp_y2.data_ptr(), inp.graph_props.data_ptr(), gs, self.gp_g2.data_ptr(), B * G, st), "gp mse bwd")
-            self._mlp2_grouped_bwd(ti, t, hd["gp_in"], rows, H, 2 * H, G, hd["gp_y1"], d1, self.gp_g2, hd["gp_g1"], hd["gp_gin"], 100 + ti)
-            g_rows = gH.data_ptr() + 4 * H * p.gp_r0
-            self._chk(lib.gmp_row_gather(hd["gp_gin"].data_ptr(), p.d64["gp_gid"], p.d32["gp_ptr"], g_rows, p.gp_M, B, H, st), "gp mean bwd")
-        elif t == "domain_adv":
-            # mean read-out -> gradient reversal -> Linear 256->128, ReLU, Dropout(.5), Linear 128->D -> CE(sum)  (heads.py:70-82)
-            B, Cc, lam = p.da_B, len(D), float(self.grl_lambda)
-            pre = "heads.domain_adv.classifier.mlp."
-            w0, b0, w3, b3 = P(pre + "0.weight"), P(pre + "0.bias"), P(pre + "3.weight"), P(pre + "3.bias")
-            self._chk(lib.gmp_segment_sum(hL.data_ptr(), p.d32["da_ptr"], None, hd["da_in"].data_ptr(), B, H, 1, 0, st), "da mean")
-            self._gemm(NT, hd["da_in"].data_ptr(), w0, b0, hd["da_y1"].data_ptr(), B, DA_HIDDEN, H, H, H, DA_HIDDEN, relu=True)
-            d1 = self._drop(hd["da_y1"], hd["da_d1"], B * DA_HIDDEN, 100 + ti, p=self.da_dropout)
-            self._gemm(NT, d1.data_ptr(), w3, b3, hd["da_logits"].data_ptr(), B, Cc, DA_HIDDEN, DA_HIDDEN, DA_HIDDEN, Cc)
-            self._chk(lib.gmp_cross_entropy_sum_fwd(hd["da_logits"].data_ptr(), p.d64["da_labels"], B, Cc, ls, self.loss_ws.data_ptr(), self.loss_ws.numel(), st), "da ce")
-            self._chk(lib.gmp_cross_entropy_sum_bwd(hd["da_logits"].data_ptr(), p.d64["da_labels"], B, Cc, gs, hd["da_glogits"].data_ptr(), st), "da ce bwd")
-            one = [0, B]
-            self._chk(lib.gmp_gemm_f32_grouped(TN, hd["da_glogits"].data_ptr(), d1.data_ptr(), None, tg, 1, _i32(one), None, None, _i64([TG(ti, pre + "3.weight")]),
-                                               tg, _i64([TG(ti, pre + "3.bias")]), Cc, DA_HIDDEN, 0, Cc, DA_HIDDEN, DA_HIDDEN, 1.0, 0, 0, None, 0, st), "da dW3")
-            self._gemm(NN, hd["da_glogits"].data_ptr(), w3, None, hd["da_g1"].data_ptr(), B, DA_HIDDEN, Cc, Cc, DA_HIDDEN, DA_HIDDEN)
-            self._relu_drop_bwd(hd["da_g1"], hd["da_y1"], hd["da_g1"], B * DA_HIDDEN, 100 + ti, p=self.da_dropout)
-            self._chk(lib.gmp_gemm_f32_grouped(TN, hd["da_g1"].data_ptr(), hd["da_in"].data_ptr(), None, tg, 1, _i32(one), None, None, _i64([TG(ti, pre + "0.weight")]),
-                                               tg, _i64([TG(ti, pre + "0.bias")]), DA_HIDDEN, H, 0, DA_HIDDEN, H, H, 1.0, 0, 0, None, 0, st), "da dW0")
-            self._chk(lib.gmp_gemm_f32(NN, hd["da_g1"].data_ptr(), w0, None, hd["da_gin"].data_ptr(), B, H, DA_HIDDEN, DA_HIDDEN, H, H, -lam, 0, 0, None, 0, st), "da grl")
-            g_rows = gH.data_ptr() + 4 * H * p.da_r0
-            self._chk(lib.gmp_row_gather(hd["da_gin"].data_ptr(), p.d64["da_gid"], p.d32["da_ptr"], g_rows, p.da_M, B, H, st), "da mean bwd")
-
-    def _nt_xent_domains(self, ns: List[int], rows: List[int], z: Tensor, gz: Tensor, gs: int, ls: int, temperature: float, slot0: int) -> None:
-        """One NT-Xent problem per domain on rows [rows[d], rows[d+1]) = [z1 ; z2]; loss sums land in scal[16+slot],
-        their total in the task's loss slot."""
-        lib, st = self.lib, self._st()
-        sc = self.scal.data_ptr()
-        ws = self._ntx_workspace(slot0, ns)
-        self._chk(lib.gmp_nt_xent_grouped(z.data_ptr(), gz.data_ptr(), len(ns), _i32(list(ns)), _i64([int(r) for r in rows[:len(ns)]]), 128,
-                                          temperature, gs, sc + 4 * (16 + slot0), ls, ws.data_ptr(), ws.numel(), st), "nt_xent grouped")
 
     def _ntx_workspace(self, slot0: int, ns) -> Tensor:
         """One grouped workspace per contrastive task (slot0 = 0 node level, D graph level), grown on demand."""
@@ -964,66 +670,9 @@ class StepEngine(StepHost):
             self.ntx_ws[slot0] = torch.empty(need, dtype=torch.uint8, device=self.device)
         return self.ntx_ws[slot0]
 
-    def _backbone_backward(self, p: StepPlan, inp: StepInputs) -> None:
-        lib, st, N, D, P, TG, T = self.lib, self._st(), p.N, self.domains, self._P, self._TG, self.T
-        tg = self.task_grads.data_ptr()
-        c = self.csr
-        gcur, gu, ga = self.gA, self.gB, self.ga
-        task_seg = self._task_segments(p)
-        trow = p.task_row
-        for l in reversed(range(GNN_NUM_LAYERS)):
-            pre = f"gnn_backbone.layers.{l}."
-            layer = self.model.gnn_backbone.layers[l]
-            bn2 = layer.batch_norm
-            cfg = self._bn_cfg(True, True, 10 + l)
-            self._chk(lib.gmp_bn_bwd(gcur.data_ptr(), self.z2[l].data_ptr(), self.h[l].data_ptr(), p.d32["seg_ptr"], None, p.S, p.max_seg, N, H,
-                                     P(pre + "batch_norm.weight"), P(pre + "batch_norm.bias"), bn2.running_mean.data_ptr(), bn2.running_var.data_ptr(),
-                                     self.stat["m2"][l].data_ptr(), self.stat["s2"][l].data_ptr(), gu.data_ptr(), tg, tg, _i32(task_seg),
-                                     self._TGs(pre + "batch_norm.weight"), self._TGs(pre + "batch_norm.bias"),
-                                     T, C.byref(cfg), self.bn_ws.data_ptr(), self.bn_ws.numel(), st), "bn2 bwd")
-            self._gemm_g(TN, gu.data_ptr(), self.r1[l].data_ptr(), None, tg, trow, None, None, [TG(t, pre + "gin_conv.nn.3.weight") for t in range(T)],
-                         tg, [TG(t, pre + "gin_conv.nn.3.bias") for t in range(T)], H, 2 * H, 0, H, 2 * H, 2 * H)
-            self._gemm(NN, gu.data_ptr(), P(pre + "gin_conv.nn.3.weight"), None, self.gW.data_ptr(), N, 2 * H, H, H, 2 * H, 2 * H)
-            bn1 = layer.gin_conv.nn[1]
-            cfg = self._bn_cfg(True, False, 0)
-            self._chk(lib.gmp_bn_bwd(self.gW.data_ptr(), self.z1[l].data_ptr(), None, p.d32["seg_ptr"], None, p.S, p.max_seg, N, 2 * H,
-                                     P(pre + "gin_conv.nn.1.weight"), P(pre + "gin_conv.nn.1.bias"), bn1.running_mean.data_ptr(), bn1.running_var.data_ptr(),
-                                     self.stat["m1"][l].data_ptr(), self.stat["s1"][l].data_ptr(), self.gW2.data_ptr(), tg, tg, _i32(task_seg),
-                                     self._TGs(pre + "gin_conv.nn.1.weight"), self._TGs(pre + "gin_conv.nn.1.bias"),
-                                     T, C.byref(cfg), self.bn_ws.data_ptr(), self.bn_ws.numel(), st), "bn1 bwd")
-            self._gemm_g(TN, self.gW2.data_ptr(), self.a[l].data_ptr(), None, tg, trow, None, None, [TG(t, pre + "gin_conv.nn.0.weight") for t in range(T)],
-                         tg, [TG(t, pre + "gin_conv.nn.0.bias") for t in range(T)], 2 * H, H, 0, 2 * H, H, H)
-            self._gemm(NN, self.gW2.data_ptr(), P(pre + "gin_conv.nn.0.weight"), None, ga.data_ptr(), N, H, 2 * H, 2 * H, H, H)
-            self._chk(lib.gmp_gin_aggregate_bwd_ex(ga.data_ptr(), c[3].data_ptr(), c[4].data_ptr(), P(pre + "gin_conv.eps"), self.h[l].data_ptr(),
-                                                   gu.data_ptr(), gcur.data_ptr(), self.rowdot.data_ptr(), N, H, st), "aggregate bwd")
-            self._chk(lib.gmp_group_sum_1d(self.rowdot.data_ptr(), T, _i32(trow), self._TGs(pre + "gin_conv.eps"), tg, st), "eps grad")
-        # ---- below the backbone: mask token (NFM) and the encoders (every task but NFM)
-        if "node_feat_mask" in self.tasks and p.nfm_rows[-1]:
-            ti, M = self.tasks.index("node_feat_mask"), p.nfm_rows[-1]
-            self._chk(lib.gmp_row_gather(gcur.data_ptr(), p.d64["nfm_idx"], None, self.hd["nfm_in"].data_ptr(), M, N, H, st), "token rows")
-            self._chk(lib.gmp_colsum(self.hd["nfm_in"].data_ptr(), tg + 4 * TG(ti, "mask_token"), M, H, H, 0, self.loss_ws.data_ptr(),
-                                     self.loss_ws.numel(), st), "token grad")
-        groups = self._encoder_groups(p)              # (zeroes the slots of the pairs that dropped out)
-        if not groups:
-            return
-        ptr = [groups[0][2]] + [hi for (_, _, _, hi) in groups]
-        e0 = f"input_encoders.{D[0]}."
-        cfg = self._bn_cfg(True, True, 1)
-        self._chk(lib.gmp_bn_bwd(gcur.data_ptr(), self.z0.data_ptr(), None, p.d32["seg_ptr"], p.d32["seg_dom"], p.S, p.max_seg, N, H,
-                                 P(e0 + "batch_norm.weight"), P(e0 + "batch_norm.bias"), self.enc_rm.data_ptr(), self.enc_rv.data_ptr(),
-                                 self.enc_mean.data_ptr(), self.enc_rstd.data_ptr(), gu.data_ptr(), tg, tg, _i32(ptr),
-                                 _i64([TG(ti, f"input_encoders.{d}.batch_norm.weight") for (ti, d, _, _) in groups]),
-                                 _i64([TG(ti, f"input_encoders.{d}.batch_norm.bias") for (ti, d, _, _) in groups]),
-                                 len(groups), C.byref(cfg), self.bn_ws.data_ptr(), self.bn_ws.numel(), st), "bn bwd encoders")
-        d_in = [DOMAIN_DIMENSIONS[d] for d in D]
-        self._chk(lib.gmp_encoder_bwd(inp.x_all.data_ptr(), inp.x_all.size(0), N, p.S, p.d32["src_row"], p.d32["seg_ptr"], p.d32["seg_dom"], p.d64.get("rowmask"),
-                                      gu.data_ptr(), len(D), _i32(d_in), self.dpad, len(groups), _i32(ptr),
-                                      _i64([TG(ti, f"input_encoders.{d}.linear.weight") for (ti, d, _, _) in groups]),
-                                      _i64([TG(ti, f"input_encoders.{d}.linear.bias") for (ti, d, _, _) in groups]), tg,
-                                      self.gemm_ws.data_ptr(), self.gemm_ws.numel(), st), "encoder bwd")
-
     # ---- optimizer ---------------------------------------------------------------------------------
-    def _optimizer(self, p: StepPlan, order: Optional[List[str]], apply_update: bool) -> None:
+    def _optimizer(self, p: StepPlan, order: Optional[List[str]], apply_update: bool, main_h: int) -> None:
+        """PCGrad, clip and AdamW behind the step's backward; main_h: the main stream's handle (hipStream_t)."""
         names = list(self.tasks)
         main_tasks = [t for t in names if t != "domain_adv"]     # pretrain.py:137-150: PCGrad over the main tasks, then
         extra = names.index("domain_adv") if "domain_adv" in names else -1   # domain_adv_loss.backward() accumulates on top
@@ -1052,7 +701,7 @@ class StepEngine(StepHost):
                 sync.average_(self.lib, torch.cuda.current_stream(self.device),
                               gate=(self.sync_flags.data_ptr(), self._epoch) if self.use_gates else None,
                               own_pass=lambda a, b, st: pcgrad(a, b, 1, st), foreign_pass=lambda a, b, st: pcgrad(a, b, 4, st))
-                pcgrad(0, self.K, 2, self._st())
+                pcgrad(0, self.K, 2, main_h)
                 return
         if self.parts_beside_backward:
             # PCGrad follows the backward part by part on the exchange stream (Gram / solve / combine of a part as soon as its
@@ -1062,11 +711,11 @@ class StepEngine(StepHost):
             sync.average_(self.lib, torch.cuda.current_stream(self.device), gate=(self.sync_flags.data_ptr(), self._epoch),
                           exchange=self.grad_sync is not None,
                           after_message=lambda parts, st: [pcgrad(a, b, 1, st) for a, b in _merge_runs([k_of[q] for q in parts])])
-            pcgrad(0, self.K, 2, self._st())
+            pcgrad(0, self.K, 2, main_h)
             return
         if self.grad_sync is not None:
             self._sync_task_grads()
-        pcgrad(0, self.K, 3, self._st())
+        pcgrad(0, self.K, 3, main_h)
 
     def _head_slices(self):
         out = []
@@ -1281,11 +930,6 @@ class StepEngine(StepHost):
                    "graph_prop": (H, 2 * H, GRAPH_PROPERTY_DIM, "gp_in", "gp_y1", "gp_d1", None, None, "gp_g1", "gp_gin")}
         sc = ptr(self.scal)
 
-        def head_offsets(ti, prefix):
-            """(field suffix, offset in flat, offset in task_grads) of the four tensors of the two-layer head `prefix`"""
-            return [(a, self.off[prefix + n], self._TG(ti, prefix + n))
-                    for a, n in (("w0", "mlp.0.weight"), ("b0", "mlp.0.bias"), ("w3", "mlp.3.weight"), ("b3", "mlp.3.bias"))]
-
         for ti, t in enumerate(self.tasks):
             td = d.task[ti]
             td.kind = TASK_KIND[t]
@@ -1297,7 +941,7 @@ class StepEngine(StepHost):
                 m = td.mlp
                 m.k_in, m.k_hid, m.k_out, m.site = k_in, k_hid, k_out, 100 + ti
                 for i, dom in enumerate(D):
-                    for a, off, tg in head_offsets(ti, f"heads.{t}.{dom}."):
+                    for a, off, tg in self.head_offsets(ti, f"heads.{t}.{dom}."):
                         getattr(m, "off_" + a)[i], getattr(m, "tg_" + a)[i] = off, tg
                 m.x, m.y1, m.d1, m.g_hid, m.g_in = ptr(hd[x]), ptr(hd[y1]), ptr(hd[d1]), ptr(hd[g_hid]), ptr(hd[g_in])
                 m.y2 = ptr(self.gp_y2) if t == "graph_prop" else ptr(hd[y2])
@@ -1318,7 +962,7 @@ class StepEngine(StepHost):
                     setattr(td, "lp_" + a, ptr(hd["lp_" + a]))
                 td.lp_y2, td.lp_p, td.lp_gy2 = ptr(self.lp_y2), ptr(self.lp_p), ptr(self.lp_gy2)
             if t in ("domain_adv", "link_pred"):      # one head shared by all domains
-                for a, off, tg in head_offsets(ti, "heads.domain_adv.classifier." if t == "domain_adv" else "heads.link_pred.predictor."):
+                for a, off, tg in self.head_offsets(ti, "heads.domain_adv.classifier." if t == "domain_adv" else "heads.link_pred.predictor."):
                     setattr(td, "one_off_" + a, off)
                     setattr(td, "one_tg_" + a, tg)
                 td.one_site = 100 + ti
@@ -1347,7 +991,7 @@ class StepEngine(StepHost):
                 td.lp_labels = self.lp_lab.data_ptr()
         self._epoch += 1
         d.epoch, d.sync_flags = self._epoch, (self.sync_flags.data_ptr() if self.use_gates else None)
-        d.seed = (self.seed * 1000003 + self.step_count) & (2 ** 64 - 1)
+        d.seed = self.dropout_seed
         d.seg_ptr, d.seg_dom, d.src_row, d.tiles = p.d32["seg_ptr"], p.d32["seg_dom"], p.d32["src_row"], p.d32["tiles"]
         d.edge_index, d.rowmask = p.d64["edge_index"], p.d64.get("rowmask")
         for i, v in enumerate(p.task_row):

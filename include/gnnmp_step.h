@@ -2,7 +2,7 @@
  * libgnnmp -- whole-step entry point: the stacked forward + task heads + stacked backward of one
  * pre-training step (reference src/pretrain/pretrain.py:113-150 over src/pretrain/tasks.py) enqueued by ONE C
  * call, so the host pays one FFI crossing instead of ~300.  It issues exactly the kernel sequence
- * gnn_pretraining_amd/engine.py issues through the per-operator entry points of gnnmp.h (the Python sequence stays
+ * gnn_pretraining_amd/step_sequence.py issues through the per-operator entry points of gnnmp.h (the Python sequence stays
  * as the tested reference: tests/test_gpu_engine.py checks the two give bitwise-identical parameters).
  *
  * All pointers are device pointers unless the field says "host".  Offsets "off_*" are in floats into `flat`

@@ -20,6 +20,7 @@ gen = torch.Generator().manual_seed(0)
 for k in range(20):
     eng.step(pool[k % len(pool)], gen)
 p, inp = eng.last_plan, pool[19 % len(pool)]
+main_h = torch.cuda.current_stream(dev).cuda_stream
 torch.cuda.synchronize()
 main = torch.cuda.current_stream(dev)
 reps = int(sys.argv[1]) if len(sys.argv) > 1 else 40
@@ -30,7 +31,7 @@ for trial in range(3):
     t0 = time.perf_counter()
     for _ in range(reps):
         eng._forward_backward_native(p, inp)
-        eng._optimizer(p, None, True)
+        eng._optimizer(p, None, True, main_h)
     t1 = time.perf_counter()
     b.record()
     torch.cuda.synchronize()

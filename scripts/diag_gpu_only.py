@@ -18,6 +18,7 @@ gen = torch.Generator().manual_seed(0)
 for k in range(20):
     eng.step(pool[k % len(pool)], gen)
 p, inp = eng.last_plan, pool[19 % len(pool)]
+main_h = torch.cuda.current_stream(dev).cuda_stream
 torch.cuda.synchronize()
 for reps in (100, 300):
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -25,7 +26,7 @@ for reps in (100, 300):
     a.record()
     for _ in range(reps):
         eng._forward_backward_native(p, inp)
-        eng._optimizer(p, None, True)
+        eng._optimizer(p, None, True, main_h)
     b.record()
     t1 = time.perf_counter()
     torch.cuda.synchronize()
@@ -48,7 +49,7 @@ for _ in range(reps):
     t1 = time.perf_counter()
     eng._chk(eng.lib.gmp_pretrain_step_fwd_bwd(C.byref(d), main.cuda_stream, eng._stream_arr, eng.aux_stream.cuda_stream), "x")
     t2 = time.perf_counter()
-    eng._optimizer(p, None, True)
+    eng._optimizer(p, None, True, main_h)
     t3 = time.perf_counter()
     T["fill"] += t1 - t0; T["native"] += t2 - t1; T["opt"] += t3 - t2
 torch.cuda.synchronize()

@@ -19,20 +19,22 @@ gen = torch.Generator().manual_seed(0)
 for k in range(5):
     eng.step(pool[k], gen)
 p = eng.last_plan
-lib, st, N, H = eng.lib, eng._st(), p.N, 256
+seq = eng.sequence()
+lib, (_, ln), N, H = eng.lib, seq._main(), p.N, 256
+st = ln.st
 P = eng._P
 l = 2
 pre = f"gnn_backbone.layers.{l}."
 c = eng.csr
 big = torch.zeros(256 * 1024 * 1024, device=dev)
-cfg1, cfg2 = eng._bn_cfg(True, False, 0), eng._bn_cfg(True, True, 10 + l)
+cfg1, cfg2 = seq._bn_cfg(True, False, 0), seq._bn_cfg(True, True, 10 + l)
 
 
 def k_agg(): eng._chk(lib.gmp_gin_aggregate_fwd(eng.h[l].data_ptr(), c[0].data_ptr(), c[1].data_ptr(), P(pre + "gin_conv.eps"), eng.a[l].data_ptr(), N, H, st), "a")
-def k_g1(): eng._gemm(NT, eng.a[l].data_ptr(), P(pre + "gin_conv.nn.0.weight"), P(pre + "gin_conv.nn.0.bias"), eng.z1[l].data_ptr(), N, 2 * H, H, H, H, 2 * H)
+def k_g1(): seq._gemm(ln, NT, eng.a[l].data_ptr(), P(pre + "gin_conv.nn.0.weight"), P(pre + "gin_conv.nn.0.bias"), eng.z1[l].data_ptr(), N, 2 * H, H, H, H, 2 * H)
 def k_b1(): eng._chk(lib.gmp_bn_fwd(eng.z1[l].data_ptr(), None, p.d32["seg_ptr"], None, p.S, p.max_seg, N, 2 * H, P(pre + "gin_conv.nn.1.weight"), P(pre + "gin_conv.nn.1.bias"), None, None,
                                     eng.stat["m1"][l].data_ptr(), eng.stat["s1"][l].data_ptr(), eng.r1[l].data_ptr(), C.byref(cfg1), eng.bn_ws.data_ptr(), eng.bn_ws.numel(), st), "b1")
-def k_g2(): eng._gemm(NT, eng.r1[l].data_ptr(), P(pre + "gin_conv.nn.3.weight"), P(pre + "gin_conv.nn.3.bias"), eng.z2[l].data_ptr(), N, H, 2 * H, 2 * H, 2 * H, H)
+def k_g2(): seq._gemm(ln, NT, eng.r1[l].data_ptr(), P(pre + "gin_conv.nn.3.weight"), P(pre + "gin_conv.nn.3.bias"), eng.z2[l].data_ptr(), N, H, 2 * H, 2 * H, 2 * H, H)
 def k_b2(): eng._chk(lib.gmp_bn_fwd(eng.z2[l].data_ptr(), eng.h[l].data_ptr(), p.d32["seg_ptr"], None, p.S, p.max_seg, N, H, P(pre + "batch_norm.weight"), P(pre + "batch_norm.bias"), None, None,
                                     eng.stat["m2"][l].data_ptr(), eng.stat["s2"][l].data_ptr(), eng.h[l + 1].data_ptr(), C.byref(cfg2), eng.bn_ws.data_ptr(), eng.bn_ws.numel(), st), "b2")
 
@@ -55,12 +57,12 @@ timed("the five chained (one layer)", lambda: (k_agg(), k_g1(), k_b1(), k_g2(), 
 
 def layer(l):
     pre = f"gnn_backbone.layers.{l}."
-    c1, c2 = eng._bn_cfg(True, False, 0), eng._bn_cfg(True, True, 10 + l)
+    c1, c2 = seq._bn_cfg(True, False, 0), seq._bn_cfg(True, True, 10 + l)
     eng._chk(lib.gmp_gin_aggregate_fwd(eng.h[l].data_ptr(), c[0].data_ptr(), c[1].data_ptr(), P(pre + "gin_conv.eps"), eng.a[l].data_ptr(), N, H, st), "a")
-    eng._gemm(NT, eng.a[l].data_ptr(), P(pre + "gin_conv.nn.0.weight"), P(pre + "gin_conv.nn.0.bias"), eng.z1[l].data_ptr(), N, 2 * H, H, H, H, 2 * H)
+    seq._gemm(ln, NT, eng.a[l].data_ptr(), P(pre + "gin_conv.nn.0.weight"), P(pre + "gin_conv.nn.0.bias"), eng.z1[l].data_ptr(), N, 2 * H, H, H, H, 2 * H)
     eng._chk(lib.gmp_bn_fwd(eng.z1[l].data_ptr(), None, p.d32["seg_ptr"], None, p.S, p.max_seg, N, 2 * H, P(pre + "gin_conv.nn.1.weight"), P(pre + "gin_conv.nn.1.bias"), None, None,
                             eng.stat["m1"][l].data_ptr(), eng.stat["s1"][l].data_ptr(), eng.r1[l].data_ptr(), C.byref(c1), eng.bn_ws.data_ptr(), eng.bn_ws.numel(), st), "b1")
-    eng._gemm(NT, eng.r1[l].data_ptr(), P(pre + "gin_conv.nn.3.weight"), P(pre + "gin_conv.nn.3.bias"), eng.z2[l].data_ptr(), N, H, 2 * H, 2 * H, 2 * H, H)
+    seq._gemm(ln, NT, eng.r1[l].data_ptr(), P(pre + "gin_conv.nn.3.weight"), P(pre + "gin_conv.nn.3.bias"), eng.z2[l].data_ptr(), N, H, 2 * H, 2 * H, 2 * H, H)
     eng._chk(lib.gmp_bn_fwd(eng.z2[l].data_ptr(), eng.h[l].data_ptr(), p.d32["seg_ptr"], None, p.S, p.max_seg, N, H, P(pre + "batch_norm.weight"), P(pre + "batch_norm.bias"), None, None,
                             eng.stat["m2"][l].data_ptr(), eng.stat["s2"][l].data_ptr(), eng.h[l + 1].data_ptr(), C.byref(c2), eng.bn_ws.data_ptr(), eng.bn_ws.numel(), st), "b2")
 
@@ -72,4 +74,4 @@ timed("flush kernel alone / 5", lambda: junk.add_(1.0), n=40)
 
 inp = pool[4 % len(pool)]
 
-timed("engine._forward (python path: encoders + CSR wait + 5 layers)", lambda: eng._forward(p, inp), n=40)
+timed("LaunchSequence.forward (python path: encoders + CSR wait + 5 layers)", lambda: seq.forward(p, inp), n=40)

@@ -18,12 +18,13 @@ gen = torch.Generator().manual_seed(0)
 for k in range(10):
     eng.step(pool[k % len(pool)], gen)
 p = eng.last_plan
+main_h = torch.cuda.current_stream(dev).cuda_stream
 torch.cuda.synchronize()
 reps = int(sys.argv[1]) if len(sys.argv) > 1 else 200
 a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 a.record()
 for _ in range(reps):
-    eng._optimizer(p, None, True)
+    eng._optimizer(p, None, True, main_h)
 b.record()
 torch.cuda.synchronize()
 print(f"optimizer tail: {a.elapsed_time(b) / reps * 1e3:.1f} us per call ({reps} calls back to back)")

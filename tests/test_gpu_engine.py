@@ -222,7 +222,7 @@ def test_engine_step_is_deterministic():
 
 @pytest.mark.parametrize("scheme", ["s4", "s5"])
 def test_native_executor_is_bitwise_identical_to_the_python_launch_sequence(scheme):
-    """csrc/step.hip transcribes engine._forward/_task_head/_backbone_backward: same kernels, same order, same buffers."""
+    """csrc/step.hip transcribes step_sequence.LaunchSequence (forward, the task heads, backward): same kernels, same order, same buffers."""
     outs = []
     for native in (False, True):
         _, hm, eng, host, inp, gen, tasks, _ = build(scheme, 71)

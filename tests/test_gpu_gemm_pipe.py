@@ -80,7 +80,7 @@ def test_pipelined_gemm_is_exact_on_integer_data(monkeypatch, tile):
 @pytest.mark.parametrize("R,Mo,No", [(7391, 512, 256), (6507, 256, 512), (1500, 128, 256)])
 @pytest.mark.parametrize("workspace", [True, False])
 def test_pipelined_grouped_weight_gradient(monkeypatch, tile, R, Mo, No, workspace):
-    """dW_t = g_t^T x_t and db_t = colsum(g_t) per task row range (the stacked backward, engine._backbone_backward): uneven ranges
+    """dW_t = g_t^T x_t and db_t = colsum(g_t) per task row range (the stacked backward, step_sequence.LaunchSequence.backward): uneven ranges
     whose lengths are not multiples of the 32-deep K-step; with a workspace the ranges are cut into row slices and reduced in
     slice order, without one the first kernel runs (callers without a workspace never reach the pipelined path)."""
     monkeypatch.setenv("GMP_GEMM_PIPE_TILE", tile)

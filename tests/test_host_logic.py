@@ -216,3 +216,12 @@ def _check_capacities(inp, gen, native_plan):
         e.__class__ = type("OneShort", (StepHost,), {cap: size - 1})
         with pytest.raises(GnnmpError, match="staging buffer too small"):
             e.plan(inp, art)
+
+
+def test_the_python_launch_sequence_lives_in_its_own_class_with_one_method_per_task():
+    """step_sequence.LaunchSequence dispatches every supported task kind (and nothing else); StepEngine keeps only the switch."""
+    from gnn_pretraining_amd.step_host import SUPPORTED_TASKS
+    from gnn_pretraining_amd.step_sequence import LaunchSequence
+    assert set(LaunchSequence.HEADS) == set(SUPPORTED_TASKS) and len(LaunchSequence.HEADS) == len(SUPPORTED_TASKS)
+    for name in ("_task_head", "_forward", "_backbone_backward"):
+        assert not hasattr(StepEngine, name), name
