@@ -164,6 +164,8 @@ _SIGS: Dict[str, tuple] = {
     "gmp_row_fill": (C.c_int, [p, p, p, i64, i64, i32, i32, p]),
     "gmp_hard_negative_workspace_bytes": (sz, [i64, i64]),
     "gmp_hard_negative_topk": (C.c_int, [p, i64, i64, p, i64, i64, p, p, p, p, sz, p]),
+    "gmp_hard_negative_stream_workspace_bytes": (sz, [i64, i64, i64]),
+    "gmp_hard_negative_topk_stream": (C.c_int, [p, i64, i64, p, i64, i64, p, p, p, p, sz, p]),
     "gmp_streams_share_queue": (C.c_int, [p, p, p]),
     "gmp_spin_us": (C.c_int, [i32, p]),
     "gmp_gate_wait": (C.c_int, [p, C.c_uint64, i32, p, p]),

@@ -3,7 +3,7 @@ miner, process_batch per task type, one AdamW step per batch over FinetuneGNN.pa
 test metrics from the best checkpoint.  Data come from the loaders of gnn_pretraining_amd/data (processed datasets in
 data/processed; synthetic stand-ins are generated when none were exported).  wandb is replaced by a JSONL logger with the
 same metric keys.  Build-only flags: --epochs, --device, --data-root, --data-scale, --log, --sparse-features, --lp-engine, --gc-engine,
---engine-eval, --lp-ranking, --device-metrics."""
+--engine-eval, --lp-ranking, --device-metrics, --miner."""
 from __future__ import annotations
 
 import argparse
@@ -36,9 +36,15 @@ class LinkPredictionHardNegativeMiner:
     (csrc/hardneg.hip) that never materialises the index lists of the ~n^2 candidate pairs; ties between equal scores go
     to the lower flat index i*n+j (torch.topk leaves them unspecified).  The random remainder -- reached only when 30 %
     of the candidate pairs is fewer than the batch, i.e. on graphs of a few dozen nodes -- follows the reference with
-    torch index ops on the device."""
+    torch index ops on the device.
+    impl ("matrix" / "stream" / "auto") picks the top-k kernel as ops.hard_negative_topk does: "stream" (csrc/hardneg_stream.hip)
+    holds nothing of size n^2.  The random remainder stays as it is under every impl: with its n x n boolean mask it is
+    reached only on those few-dozen-node graphs."""
 
-    def __init__(self) -> None:
+    def __init__(self, impl: str = "matrix") -> None:
+        if impl not in ops.MINER_IMPLS:
+            raise ValueError(f"LinkPredictionHardNegativeMiner: impl={impl!r} is not one of {ops.MINER_IMPLS}")
+        self.impl = impl
         self._count_key, self._count = None, 0
 
     def _num_potential(self, num_nodes: int, existing_edges: Tensor) -> int:
@@ -60,7 +66,7 @@ class LinkPredictionHardNegativeMiner:
             return torch.empty(2, 0, dtype=torch.long, device=device)
         num_hard = max(MIN_HARD_NEGATIVES, int(potential * HARD_NEGATIVE_RATIO))
         num_hard = min(num_hard, potential, num_negatives)
-        hard = ops.hard_negative_topk(node_embeddings.contiguous(), existing_edges.contiguous(), num_hard)
+        hard = ops.hard_negative_topk(node_embeddings.contiguous(), existing_edges.contiguous(), num_hard, impl=self.impl)
         remaining = num_negatives - num_hard
         if remaining <= 0:
             return hard
@@ -95,6 +101,7 @@ class FinetuneConfig:
     engine_eval: bool = False           # validation / test through the active engine's predict (BatchNorm folded into the GEMMs), not the module
     lp_ranking: bool = False            # link prediction on the engine: the test pass also ranks every true test edge against all nodes (MRR, Hits@K)
     device_metrics: bool = False        # batch scores from integer counts made on the GPU (metrics.compute_batch_metrics_device), not scikit-learn on host copies
+    miner_impl: str = "matrix"          # link-prediction domains: the hard-negative miner's top-k kernel (ops.hard_negative_topk impl), module path and lp_engine alike
 
     def __post_init__(self) -> None:
         if self.sparse_features and TASK_TYPES[self.domain_name] == "graph_classification":
@@ -103,6 +110,10 @@ class FinetuneConfig:
             raise ValueError(f"lp_engine applies to the link-prediction domains (Cora_LP / CiteSeer_LP), not to {self.domain_name}")
         if self.gc_engine and TASK_TYPES[self.domain_name] != "graph_classification":
             raise ValueError(f"gc_engine applies to the graph-classification domains (ENZYMES / PTC_MR), not to {self.domain_name}")
+        if self.miner_impl not in ops.MINER_IMPLS:
+            raise ValueError(f"miner_impl={self.miner_impl!r} is not one of {ops.MINER_IMPLS}")
+        if self.miner_impl != "matrix" and TASK_TYPES[self.domain_name] != "link_prediction":
+            raise ValueError(f"miner_impl applies to the link-prediction domains (Cora_LP / CiteSeer_LP), not to {self.domain_name}")
         if self.engine_eval and not engine_active(self):
             raise ValueError(f"engine_eval needs an active fine-tune engine for {self.domain_name}: "
                              + {"node_classification": "the node engine is switched off (GMP_FINETUNE_ENGINE=0)",
@@ -377,7 +388,7 @@ def finetune(cfg: FinetuneConfig, epochs: Optional[int] = None, device: Optional
                 data.x = SparseFeatures.from_dense(data.x)
     model = create_finetune_model(dev, cfg)
     optimizer = torch.optim.AdamW(model.param_groups)
-    miner = LinkPredictionHardNegativeMiner() if cfg.task_type == "link_prediction" else None
+    miner = LinkPredictionHardNegativeMiner(cfg.miner_impl) if cfg.task_type == "link_prediction" else None
     logger = JsonlLogger(log_path)
     torch.save({"epoch": 0, "model_state_dict": model.state_dict(), "val_metrics": {}}, path)
     key = "val/auc" if cfg.task_type == "link_prediction" else "val/accuracy"
@@ -457,6 +468,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--engine-eval", action="store_true", help="validation / test through the active engine's predict (needs the node engine, --lp-engine or --gc-engine)")
     p.add_argument("--lp-ranking", action="store_true", help="with --lp-engine: the test pass also logs test/mrr and test/hits@K (true test edges ranked against all nodes, known positives filtered)")
     p.add_argument("--device-metrics", action="store_true", help="batch scores (accuracy, F1, precision, recall, AUC) from integer counts made on the GPU instead of scikit-learn on host copies; same values")
+    p.add_argument("--miner", choices=list(ops.MINER_IMPLS), default="matrix",
+                   help="Cora_LP / CiteSeer_LP: the hard-negative miner's top-k kernel: matrix (n x n similarity in the workspace, n <= 65535), "
+                        "stream (tiles recomputed, workspace O(n d + E), n <= 2^20), auto (stream beyond 65535 nodes)")
     return p
 
 
@@ -464,7 +478,7 @@ def config_from_args(a: argparse.Namespace) -> FinetuneConfig:
     return FinetuneConfig(a.domain_name, a.finetune_strategy, a.pretrained_scheme, a.seed, sparse_features=a.sparse_features,
                           lp_engine=getattr(a, "lp_engine", False), gc_engine=getattr(a, "gc_engine", False),
                           engine_eval=getattr(a, "engine_eval", False), lp_ranking=getattr(a, "lp_ranking", False),
-                          device_metrics=getattr(a, "device_metrics", False))
+                          device_metrics=getattr(a, "device_metrics", False), miner_impl=getattr(a, "miner", "matrix"))
 
 
 def main() -> None:

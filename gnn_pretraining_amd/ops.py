@@ -609,21 +609,36 @@ def nt_xent_stream_bwd(z1: Tensor, z2: Tensor, temperature: float, g_scale: Tens
     return g1, g2
 
 
+MINER_IMPLS = ("matrix", "stream", "auto")
+MINER_MATRIX_MAX_N = 65535          # the dense form packs the flat pair index into 32 bits
+
+
 def hard_negative_topk(emb: Tensor, existing_edges: Tensor, k: int, return_scores: bool = False,
-                       return_matrix: bool = False):
+                       return_matrix: bool = False, impl: str = "matrix"):
     """Top-k cosine-similarity non-edges (finetune.py:45-75).  Returns edges [2,k] int64 (score-descending), and
-    optionally the selected scores [k] and the masked n x n similarity matrix."""
+    optionally the selected scores [k] and the masked n x n similarity matrix.
+    impl: "matrix" (csrc/hardneg.hip: the n x n matrix in the workspace, n <= 65535), "stream" (csrc/hardneg_stream.hip: tiles
+    recomputed in MFMA accumulators, workspace O(n d + E), n <= 2^20, a -1 / -inf tail when fewer than k pairs are unmasked),
+    or "auto" (stream when n > 65535, matrix otherwise)."""
+    if impl not in MINER_IMPLS:
+        raise ValueError(f"hard_negative_topk: impl={impl!r} is not one of {MINER_IMPLS}")
     _need(emb, torch.float32, "emb", 2); _need(existing_edges, torch.int64, "existing_edges", 2)
     n, d = emb.shape
     E = existing_edges.size(1)
     l = L.lib()
-    ws = _ws(l.gmp_hard_negative_workspace_bytes(n, d), emb.device)
+    stream = impl == "stream" or (impl == "auto" and n > MINER_MATRIX_MAX_N)
+    if stream:
+        fn, name, nbytes = l.gmp_hard_negative_topk_stream, "gmp_hard_negative_topk_stream", l.gmp_hard_negative_stream_workspace_bytes(n, d, E)
+    else:
+        # beyond its limit the dense entry point refuses n before it looks at the workspace: no 4 n^2 bytes just to hear that
+        fn, name, nbytes = l.gmp_hard_negative_topk, "gmp_hard_negative_topk", l.gmp_hard_negative_workspace_bytes(n, d) if n <= MINER_MATRIX_MAX_N else 0
+    ws = _ws(nbytes, emb.device)
     out = torch.empty(2, k, dtype=torch.int64, device=emb.device)
     sc = torch.empty(k, dtype=torch.float32, device=emb.device) if return_scores else None
     mat = torch.empty(n, n, dtype=torch.float32, device=emb.device) if return_matrix else None
-    L.check(l.gmp_hard_negative_topk(_ptr(emb), n, d, _ptr(existing_edges) if E else None, E, k, _ptr(out) if k else None,
-                                     _ptr(sc) if sc is not None else None, _ptr(mat) if mat is not None else None,
-                                     _ptr(ws), ws.numel(), _stream(emb)), "gmp_hard_negative_topk")
+    L.check(fn(_ptr(emb), n, d, _ptr(existing_edges) if E else None, E, k, _ptr(out) if k else None,
+               _ptr(sc) if sc is not None else None, _ptr(mat) if mat is not None else None,
+               _ptr(ws), ws.numel(), _stream(emb)), name)
     res = (out,)
     if return_scores:
         res += (sc,)

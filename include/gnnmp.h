@@ -570,6 +570,28 @@ int gmp_hard_negative_topk(const float* emb, int64_t n, int64_t dim, const int64
                            int64_t k, int64_t* out_edges, float* out_scores, float* scores_out,
                            void* workspace, size_t workspace_bytes, gmp_stream_t stream);
 
+/* The same contract without the n x n matrix (csrc/hardneg_stream.hip): similarity tiles are recomputed in MFMA
+ * accumulators (upper triangle only; a pair i < j stands for the ordered pairs (i,j) and (j,i)) for every pass of the
+ * same exact radix select, over the key (score descending, flat index i*n+j ascending, 40 bits).  Once the keys at or above
+ * the decided prefix fit a fixed candidate buffer (65,536 keys) the remaining histogram passes return at once, one more tile
+ * pass gathers the candidates and the k winners are ranked among them.
+ *   1 <= dim <= 256 (any value; GMP_ERR_UNSUPPORTED above), 1 <= n <= 2^20, 0 <= k <= 4096, E >= 0 (GMP_ERR_ARG otherwise).
+ *   workspace >= gmp_hard_negative_stream_workspace_bytes(n, dim, E) = O(n dim + E) + a constant below 1 MiB: the normalised
+ *   rows, both CSR orientations of existing_edges (gmp_csr_build; endpoints outside [0,n) are ignored) and the candidates.
+ *   scores_out: NULL or [n,n], the masked matrix exactly as the selection saw it, written by the same tile code -- the only
+ *   n^2 object, and only on request.
+ *   If fewer than k unmasked ordered pairs exist, the tail of out_edges is -1 and the tail of out_scores -inf.
+ *   Asynchronous on `stream`, no host read-back, no allocation; integer atomics only, and the output is a pure function of
+ *   the input.  Scores equal the dense form's bit for bit where the arithmetic is exact; elsewhere the two forms sum the
+ *   dim products in different orders.
+ *   Diagnostic: after the call has run, the first int32 of the workspace holds the number of histogram passes (tile passes
+ *   before the gather) that did work.
+ */
+size_t gmp_hard_negative_stream_workspace_bytes(int64_t n, int64_t dim, int64_t E);
+int gmp_hard_negative_topk_stream(const float* emb, int64_t n, int64_t dim, const int64_t* existing_edges, int64_t E,
+                                  int64_t k, int64_t* out_edges, float* out_scores, float* scores_out,
+                                  void* workspace, size_t workspace_bytes, gmp_stream_t stream);
+
 /* ------------------------------------------------------------------------- *
  * Pack / unpack a fixed list of slices of one buffer into one contiguous message (the data-parallel exchange of per-task
  * gradients: only the (task, tensor) pairs that carry a gradient travel).  table_dev: device int64 [2n+1] = n source offsets

@@ -1,6 +1,13 @@
-"""Timing of the hard-negative miner (csrc/hardneg.hip) at Cora / CiteSeer size, beside (a) the reference's own
-sequence of torch ops run on the same GPU (finetune.py:45-75 as written: dense mask, torch.where, torch.topk) and
-(b) the CPU oracle.  Usage: python scripts/bench_miner.py [--n 2708] [--k 256]"""
+"""Timing of the hard-negative miner.
+Without --impl: the dense form (csrc/hardneg.hip) at Cora / CiteSeer size, beside (a) the reference's own sequence of torch ops run
+on the same GPU (finetune.py:45-75 as written: dense mask, torch.where, torch.topk) and (b) the CPU oracle.
+    python scripts/bench_miner.py [--n 2708] [--k 256]
+With --impl {matrix,stream,both}: the dense form against the streaming form (csrc/hardneg_stream.hip) at 2,708 and 3,327 nodes (Cora,
+CiteSeer), 19,717 and 65,535, d = 256, k = 256, in alternated rounds (round r times one form, then the other); per size both times
+with their spread over the rounds, both workspace sizes, whether the two selections agree, and the number of histogram tile passes the
+streaming form ran (its device counter, read back after the timed loops).  At 65,535 nodes the dense form needs a 16 GiB workspace:
+only the streaming form runs there.
+    python scripts/bench_miner.py --impl both --out profiles/miner_stream.json"""
 import argparse
 import json
 import os
@@ -42,14 +49,80 @@ def timed(fn, iters):
     return a.elapsed_time(b) / iters * 1e3          # us
 
 
+SIZES = [(2708, 8446), (3327, 7283), (19717, 70918), (65535, 262140)]     # (nodes, directed training-edge entries: 80 % of the public counts; 4 n at 65,535)
+DENSE_MAX_N = 20000                                                          # above: the dense form's 4 n^2-byte workspace is not asked for
+
+
+def stream_passes(emb, edges, k):
+    """One direct call with a workspace of our own; the entry point leaves its histogram-pass count in the first int32."""
+    from gnn_pretraining_amd import _lib as L
+    l = L.lib()
+    n, d = emb.shape
+    E = edges.size(1)
+    ws = torch.empty(l.gmp_hard_negative_stream_workspace_bytes(n, d, E), dtype=torch.uint8, device=emb.device)
+    out = torch.empty(2, k, dtype=torch.int64, device=emb.device)
+    L.check(l.gmp_hard_negative_topk_stream(ops._ptr(emb), n, d, ops._ptr(edges), E, k, ops._ptr(out), None, None, ops._ptr(ws), ws.numel(),
+                                            ops._stream(emb)), "gmp_hard_negative_topk_stream")
+    torch.cuda.synchronize()
+    return int(ws[:4].view(torch.int32).item())
+
+
+def compare(a):
+    from gnn_pretraining_amd import _lib as L
+    l = L.lib()
+    sizes = [(a.n, a.edges)] if a.n_given else SIZES
+    rows = []
+    for n, E in sizes:
+        g = torch.Generator().manual_seed(0)
+        emb = torch.randn(n, a.d, generator=g).cuda()
+        edges = torch.randint(0, n, (2, E), generator=g).cuda()
+        impls = [i for i in ("matrix", "stream") if a.impl in (i, "both") and (i == "stream" or n <= DENSE_MAX_N)]
+        iters = a.iters if n < 10000 else max(a.iters // 5, 3)
+        times = {i: [] for i in impls}
+        for _ in range(a.rounds):                                            # alternated: matrix, stream, matrix, stream, ...
+            for i in impls:
+                times[i].append(timed(lambda: ops.hard_negative_topk(emb, edges, a.k, impl=i), iters))
+        row = {"n": n, "d": a.d, "E": E, "k": a.k, "iters": iters, "rounds": a.rounds}
+        for i in impls:
+            t = sorted(times[i])
+            row[f"{i}_us"] = round(t[len(t) // 2], 1)
+            row[f"{i}_us_rounds"] = [round(x, 1) for x in times[i]]
+        row["matrix_workspace_bytes"] = int(l.gmp_hard_negative_workspace_bytes(n, a.d))
+        row["stream_workspace_bytes"] = int(l.gmp_hard_negative_stream_workspace_bytes(n, a.d, E))
+        if "matrix" not in impls and a.impl != "stream":
+            row["matrix_skipped"] = "the dense form's workspace at this size is not allocated"
+        if "stream" in impls:
+            row["stream_hist_passes"] = stream_passes(emb, edges, a.k)
+            row["stream_tile_passes"] = row["stream_hist_passes"] + 1         # + the gather
+        if len(impls) == 2:
+            m, ms = ops.hard_negative_topk(emb, edges, a.k, return_scores=True, impl="matrix")
+            s, ss = ops.hard_negative_topk(emb, edges, a.k, return_scores=True, impl="stream")
+            row["same_pairs"] = bool(torch.equal(m, s))
+            row["max_score_diff"] = float((ms - ss).abs().max())
+            row["stream_over_matrix"] = round(row["stream_us"] / row["matrix_us"], 3)
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump({"device": torch.cuda.get_device_name(0), "rows": rows}, f, indent=1)
+            f.write("\n")
+
+
 def main():
     p = argparse.ArgumentParser()
+    p.add_argument("--impl", choices=["matrix", "stream", "both"], default=None, help="compare the miner's two forms over the size ladder")
+    p.add_argument("--out", type=str, default=None, help="with --impl: also write the rows to this JSON file")
+    p.add_argument("--rounds", type=int, default=3, help="with --impl: alternated rounds per size")
     p.add_argument("--n", type=int, default=2708)
     p.add_argument("--d", type=int, default=256)
     p.add_argument("--edges", type=int, default=8446)        # 80 % of Cora's 10,556 directed entries
     p.add_argument("--k", type=int, default=256)
     p.add_argument("--iters", type=int, default=50)
     a = p.parse_args()
+    a.n_given = any(x == "--n" or x.startswith("--n=") for x in sys.argv[1:])
+    if a.impl is not None:
+        return compare(a)
     g = torch.Generator().manual_seed(0)
     emb = torch.randn(a.n, a.d, generator=g).cuda()
     edges = torch.randint(0, a.n, (2, a.edges), generator=g).cuda()

@@ -1,0 +1,214 @@
+"""The streaming hard-negative miner (csrc/hardneg_stream.hip, ops.hard_negative_topk(impl="stream")) on the GPU against
+oracle/miner.py and against the dense form, at the bars of tests/test_gpu_miner.py: (a) where the arithmetic is exact, pairs, order and
+scores equal the oracle's and impl="matrix"'s bit for bit; (b) on random embeddings the selection equals the oracle's selection run on
+the kernel's own score matrix and the scores agree to 1e-5; plus the routes only this form has -- ties beyond its candidate buffer, a flat
+pair index beyond 32 bits, the -1 / -inf tail -- and the layers above it (miner class, FinetuneConfig.miner_impl)."""
+import math
+
+import numpy as np
+import pytest
+import torch
+
+from gnn_pretraining_amd import ops
+from gnn_pretraining_amd.finetune.finetune import LinkPredictionHardNegativeMiner
+from oracle import miner as OM
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+NINF = float("-inf")
+
+
+def _edges(n, m, seed):
+    g = torch.Generator().manual_seed(seed)
+    return torch.randint(0, n, (2, m), generator=g)
+
+
+def _four_ones(n, d, seed):
+    """rows with exactly four ones (tests/test_gpu_miner.py): norm 2, normalised entries 0.5, dot products m/4"""
+    rng = np.random.default_rng(seed)
+    x = np.zeros((n, d), dtype=np.float32)
+    for i in range(n):
+        x[i, rng.choice(d, size=4, replace=False)] = 1.0
+    return torch.from_numpy(x)
+
+
+def _sixteen_signs(n, d, seed):
+    """rows with sixteen +-1 entries: norm 4, normalised entries in {-0.25, 0, 0.25}, dot products m/16 -- exact in any order"""
+    rng = np.random.default_rng(seed)
+    x = np.zeros((n, d), dtype=np.float32)
+    for i in range(n):
+        x[i, rng.choice(d, size=16, replace=False)] = rng.choice([-1.0, 1.0], size=16)
+    return torch.from_numpy(x)
+
+
+def _stream(emb, ex, k, **kw):
+    out = ops.hard_negative_topk(emb.to(DEV), ex.to(DEV), k, impl="stream", **kw)
+    return tuple(t.cpu() for t in out) if isinstance(out, tuple) else out.cpu()
+
+
+def _check_exact(emb, ex, k):
+    got, sc = _stream(emb, ex, k, return_scores=True)
+    want = OM.mine_hard_negatives_for_edges(emb, torch.empty(2, k, dtype=torch.long), k, ex)
+    assert want.size(1) == k
+    assert torch.equal(got, want)                                    # same pairs, same order (ties: lower flat index)
+    sim, _ = OM.similarity_and_mask(emb, ex)
+    assert torch.equal(sc, sim[want[0], want[1]])
+    dense, dsc = ops.hard_negative_topk(emb.to(DEV), ex.to(DEV), k, return_scores=True, impl="matrix")
+    assert torch.equal(got, dense.cpu()) and torch.equal(sc, dsc.cpu())
+
+
+@pytest.mark.parametrize("n,d,m,k", [(64, 16, 100, 32), (301, 32, 900, 256), (1000, 24, 5000, 256), (130, 8, 0, 8)])
+def test_stream_bit_exact_on_four_ones_rows(n, d, m, k):
+    _check_exact(_four_ones(n, d, n + d), _edges(n, m, m + 1), k)
+
+
+def test_stream_bit_exact_on_sixteen_sign_rows_with_k_inside_a_tie_group():
+    _check_exact(_sixteen_signs(1000, 32, 11), _edges(1000, 5000, 5001), 256)
+
+
+RANDOM_CASES = [("randn", 257, 256, 700, 256), ("randn", 2708, 256, 8000, 256), ("randn", 333, 256, 50, 77), ("abs", 2708, 256, 8000, 256)]
+
+
+@pytest.mark.parametrize("kind,n,d,m,k", RANDOM_CASES)
+def test_stream_selection_is_exact_on_its_own_scores_and_scores_match_oracle(kind, n, d, m, k):
+    g = torch.Generator().manual_seed(n)
+    emb, ex = torch.randn(n, d, generator=g), _edges(n, m, 3)
+    if kind == "abs":
+        emb = emb.abs()
+    got, sc, mat = _stream(emb, ex, k, return_scores=True, return_matrix=True)
+    sim, potential = OM.similarity_and_mask(emb, ex)
+    # the score matrix: exactly symmetric, -inf exactly where the reference's mask excludes a pair, values within 1e-5
+    assert torch.equal(mat, mat.t())
+    assert torch.equal(torch.isinf(mat) & (mat < 0), ~potential)
+    err = float((mat[potential] - sim[potential]).abs().max())
+    print(f"{kind} n={n}: max |S - oracle| = {err:.3e}")
+    assert err < 1e-5
+    # index work on the same floats is exact
+    want = OM.mine_hard_negatives_for_edges(emb, torch.empty(2, k, dtype=torch.long), k, ex, similarity=mat)
+    assert torch.equal(got, want)
+    assert torch.equal(sc, mat[got[0], got[1]])
+    assert bool((sc[:-1] >= sc[1:]).all())
+    # against the oracle's own scores: the k-th score agrees, every pick is a valid candidate at or above it ...
+    ref = OM.mine_hard_negatives_for_edges(emb, torch.empty(2, k, dtype=torch.long), k, ex)
+    kth = sim[ref[0, -1], ref[1, -1]]
+    print(f"{kind} n={n}: k-th score {float(sc[-1]):.7f} oracle {float(kth):.7f}")
+    assert abs(float(sc[-1] - kth)) < 1e-5
+    assert bool(potential[got[0], got[1]].all()) and bool((sim[got[0], got[1]] >= kth - 2e-5).all())
+    # ... and no valid candidate clearly above the returned k-th score is missing
+    must = potential & (sim > float(sc[-1]) + 2e-5)
+    picked = torch.zeros_like(potential)
+    picked[got[0], got[1]] = True
+    assert not bool((must & ~picked).any())
+
+
+def test_ties_beyond_the_candidate_capacity():
+    n, k = 1500, 256
+    emb, ex = torch.ones(n, 4), _edges(n, 500, 17)
+    got, sc = _stream(emb, ex, k, return_scores=True)                # 2.25 M keys with the score 1.0: the flat-index digits decide
+    want = OM.mine_hard_negatives_for_edges(emb, torch.empty(2, k, dtype=torch.long), k, ex)
+    assert torch.equal(got, want)                                    # the first 256 unmasked pairs in row-major order
+    assert torch.equal(sc, torch.ones(k))
+
+
+def test_beyond_the_32_bit_flat_index():
+    n, d, k, lo, hi = 70000, 8, 256, 69950, 69990
+    emb = torch.zeros(n, d)
+    emb[lo:hi, 0] = 3.0
+    ex = torch.tensor([[69951, 69989, 5], [69960, 69950, 69970]])    # two inside the block (either direction), one outside
+    assert (n - 1) * n + n - 1 > 2 ** 32
+    masked = {(69951, 69960), (69960, 69951), (69989, 69950), (69950, 69989)}
+    pairs = [(i, j) for i in range(lo, hi) for j in range(lo, hi) if i != j and (i, j) not in masked]       # row-major: all score 1.0
+    want = torch.tensor(pairs[:k]).t()
+    got, sc = _stream(emb, ex, k, return_scores=True)
+    assert torch.equal(got, want) and torch.equal(sc, torch.ones(k))
+    auto, asc = ops.hard_negative_topk(emb.to(DEV), ex.to(DEV), k, return_scores=True, impl="auto")
+    assert torch.equal(auto.cpu(), got) and torch.equal(asc.cpu(), sc)
+    with pytest.raises(Exception):
+        ops.hard_negative_topk(emb.to(DEV), ex.to(DEV), k, impl="matrix")
+
+
+@pytest.mark.parametrize("n,d,m,k", [(5, 6, 3, 4), (5, 10, 0, 6), (70, 6, 40, 32), (200, 10, 0, 64)])
+def test_shape_edges_small_n_odd_dim_no_edges(n, d, m, k):
+    g = torch.Generator().manual_seed(n + d)
+    emb, ex = torch.randn(n, d, generator=g), _edges(n, m, 2)
+    got, sc, mat = _stream(emb, ex, k, return_scores=True, return_matrix=True)
+    sim, potential = OM.similarity_and_mask(emb, ex)
+    assert torch.equal(torch.isinf(mat) & (mat < 0), ~potential) and torch.equal(mat, mat.t())
+    assert float((mat[potential] - sim[potential]).abs().max()) < 1e-5
+    assert torch.equal(got, OM.mine_hard_negatives_for_edges(emb, torch.empty(2, k, dtype=torch.long), k, ex, similarity=mat))
+    assert torch.equal(sc, mat[got[0], got[1]])
+
+
+def test_zero_rows_k_bounds_short_tail_and_determinism():
+    emb = torch.zeros(40, 8)
+    emb[:10] = torch.randn(10, 8, generator=torch.Generator().manual_seed(1))
+    ex = _edges(40, 30, 2)
+    got, sc = _stream(emb, ex, 16, return_scores=True)               # zero rows: score 0, no NaN
+    assert bool(torch.isfinite(sc).all())
+    with pytest.raises(Exception):
+        _stream(emb, ex, 5000)
+    assert _stream(emb, ex, 0).shape == (2, 0)
+    # k above the number of unmasked ordered pairs: the pairs in order, then -1 / -inf
+    n, k = 6, 40
+    emb = torch.randn(n, 6, generator=torch.Generator().manual_seed(3))
+    ex = torch.tensor([[0, 1, 2, 2], [1, 0, 3, 2]])
+    got, sc, mat = _stream(emb, ex, k, return_scores=True, return_matrix=True)
+    _, potential = OM.similarity_and_mask(emb, ex)
+    P = int(potential.sum())
+    assert P == n * n - n - 4 and P < k
+    # every unmasked pair, stable by score over the row-major list (the oracle's rule; its own k stops at 30 % of them)
+    idx = torch.where(potential)
+    order = torch.from_numpy(np.argsort(-mat[potential].numpy(), kind="stable").copy())
+    want = torch.stack([idx[0][order], idx[1][order]])
+    assert torch.equal(got[:, :P], want) and torch.equal(sc[:P], mat[want[0], want[1]])
+    assert bool((got[:, P:] == -1).all()) and bool((sc[P:] == NINF).all())
+    # every pair masked: nothing but the tail
+    full = torch.tensor([[0, 0, 1], [1, 2, 2]])
+    got, sc = _stream(torch.ones(3, 4), full, 4, return_scores=True)
+    assert bool((got == -1).all()) and bool((sc == NINF).all())
+    # the output is a pure function of the input
+    emb, ex = torch.randn(700, 40, generator=torch.Generator().manual_seed(8)), _edges(700, 2000, 9)
+    a = _stream(emb, ex, 300, return_scores=True)
+    b = _stream(emb, ex, 300, return_scores=True)
+    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
+
+
+def test_miner_class_on_the_stream_form_matches_oracle_including_random_remainder():
+    miner = LinkPredictionHardNegativeMiner(impl="stream")
+    n = 500
+    emb, ex = _four_ones(n, 32, 9), _edges(n, 1500, 4)
+    pos = ex[:, :256]
+    got = miner.mine_hard_negatives_for_edges(emb.to(DEV), pos.to(DEV), 256, ex.to(DEV)).cpu()
+    assert torch.equal(got, OM.mine_hard_negatives_for_edges(emb, pos, 256, ex))
+    # tiny graph: 30 % of the candidates < batch -> hard part equals the oracle's, the rest are distinct valid non-edges
+    n = 12
+    emb, ex = _four_ones(n, 8, 1), _edges(n, 20, 6)
+    _, potential = OM.similarity_and_mask(emb, ex)
+    want_hard = OM.num_hard(int(potential.sum()), 64)
+    assert want_hard < 64
+    got = miner.mine_hard_negatives_for_edges(emb.to(DEV), ex[:, :1].to(DEV), 64, ex.to(DEV)).cpu()
+    ref = OM.mine_hard_negatives_for_edges(emb, ex[:, :1], 64, ex)
+    assert torch.equal(got[:, :want_hard], ref[:, :want_hard])
+    rest = got[:, want_hard:]
+    assert got.size(1) == ref.size(1) and bool(potential[rest[0], rest[1]].all())
+    hard = {(int(a), int(b)) for a, b in got[:, :want_hard].t()}
+    assert all((int(a), int(b)) not in hard and (int(b), int(a)) not in hard for a, b in rest.t())
+    assert len({(int(a), int(b)) for a, b in rest.t()}) == rest.size(1)
+
+
+def test_link_prediction_finetune_end_to_end_on_the_stream_miner(tmp_path, monkeypatch):
+    from gnn_pretraining_amd.finetune import finetune as FT
+    monkeypatch.setattr(FT, "OUTPUT_DIR", tmp_path / "finetune")
+    seen = []
+    real = ops.hard_negative_topk
+
+    def spy(*a, **kw):
+        seen.append(kw.get("impl"))
+        return real(*a, **kw)
+
+    monkeypatch.setattr(ops, "hard_negative_topk", spy)
+    cfg = FT.FinetuneConfig("Cora_LP", "full_finetune", "b1", 1, lp_engine=True, miner_impl="stream")
+    test = FT.finetune(cfg, epochs=1, data_root=str(tmp_path / "data"), data_scale=0.1)
+    assert seen and set(seen) == {"stream"}
+    assert all(math.isfinite(float(v)) for key, v in test.items() if key.startswith("test/") and isinstance(v, (int, float)))
+    assert 0.0 <= test["test/accuracy"] <= 1.0 and math.isfinite(test["test/auc"])
