@@ -707,7 +707,7 @@ __global__ __launch_bounds__(THREADS) void bn_param_grad_kernel(const float* __r
     g_gamma[grp.off_gamma[g] + c] = s2;
 }
 
-size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
+using gmp::al;
 int chunks_for(int64_t max_seg_rows) { return (int)((max_seg_rows + CHUNK - 1) / CHUNK); }
 int slabs_for(int64_t max_seg_rows) { return (int)((max_seg_rows + SLAB_ROWS - 1) / SLAB_ROWS); }
 int64_t slab_sync_words(int C, int S) { return SYNC_HDR + (int64_t)S * SRL * 2 * C * 2; }   // header + granules [S][32 slabs][2][C] of 8 bytes

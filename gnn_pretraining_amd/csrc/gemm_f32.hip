@@ -17,7 +17,7 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using gmp::f32x16;
 
 constexpr int BK_DEFAULT = 32;
 constexpr int THREADS = 256;
@@ -299,7 +299,7 @@ __global__ __launch_bounds__(THREADS) void gemm_kernel(const GemmArgs g) {
             const float sc = (EPI && !partial && g.scale) ? g.scale[col] : 1.f, sh = (EPI && !partial && g.scale) ? g.shift[col] : 0.f;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int64_t row = m0 + wm * (BM / 2) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+                const int64_t row = gmp::acc_row(r, half, m0 + wm * (BM / 2) + i * 32);
                 if (row >= Mrows) continue;
                 float v = acc[i][j][r];
                 if (!partial) {

@@ -25,7 +25,7 @@
 
 namespace g2 {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using gmp::f32x16;
 typedef __attribute__((address_space(3))) void lds_void;
 typedef const __attribute__((address_space(1))) void glb_void;
 
@@ -472,7 +472,7 @@ __global__ __launch_bounds__(THREADS) void gemm_pipe_kernel(const GemmArgs g, in
             for (int j = 0; j < TN; ++j)
 #pragma unroll
                 for (int r = 0; r < 16; ++r)
-                    tile[(i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * WC + j * 32 + l31] = acc[i][j][r];
+                    tile[gmp::acc_row(r, half, i * 32) * WC + j * 32 + l31] = acc[i][j][r];
         constexpr int LR = WC / 4, RPI = 64 / LR;              // lanes per row, rows per wave-instruction
         const int c4 = lane % LR, rsub = lane / LR;
         const int64_t col = col0 + 4 * c4;
@@ -544,7 +544,7 @@ __global__ __launch_bounds__(THREADS) void gemm_pipe_kernel(const GemmArgs g, in
             const float sc = (EPI && g.scale) ? g.scale[col] : 1.f, sh = (EPI && g.scale) ? g.shift[col] : 0.f;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int64_t row = row0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+                const int64_t row = gmp::acc_row(r, half, row0 + i * 32);
                 if (row >= Mrows) continue;
                 float v = g.alpha * acc[i][j][r] + bv;
                 if (g.accumulate) v += out[row * ldo + col];
@@ -667,7 +667,7 @@ __global__ __launch_bounds__(THREADS) void lp_bwd_fold_kernel(const LpFoldArgs g
 #pragma unroll
     for (int th = 0; th < 3; ++th)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) tile[th * 1024 + ((r & 3) + 8 * (r >> 2) + 4 * half) * 32 + l31] = acc[th][0][0][r];
+        for (int r = 0; r < 16; ++r) tile[th * 1024 + gmp::acc_row(r, half) * 32 + l31] = acc[th][0][0][r];
     const int c4 = lane & 7, rsub = lane >> 3;
     const int colq = (c0 + wn * 32) / 4 + c4;             // float4 column of the node-feature row
     const float4* __restrict__ h4 = reinterpret_cast<const float4*>(g.h);

@@ -105,6 +105,38 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// one wave's row: dst[0, d) = src / max(||src||, eps), zeros up to dpad (F.normalize, eps = 1e-12); the clamped norm to *norm if given
+__device__ __forceinline__ void normalize_row(const float* __restrict__ src, int d, float* __restrict__ dst, int dpad, float* __restrict__ norm) {
+    const int lane = threadIdx.x % 64;
+    float s = 0.f;
+    for (int c = lane; c < d; c += 64) s += src[c] * src[c];
+    s = wave_sum(s);
+    const float nr = fmaxf(sqrtf(s), 1e-12f);
+    for (int c = lane; c < dpad; c += 64) dst[c] = c < d ? src[c] / nr : 0.f;
+    if (norm && lane == 0) *norm = nr;
+}
+
+// out[0] = sum of v[0, n) in a fixed order, one workgroup (ntxent.hip)
+void sum_rows(const float* v, int64_t n, float* out, hipStream_t st);
+
+// C/D layout of the 32x32 MFMAs: the lane holds column lane & 31, register r of lane half `half` (lane >> 5) holds this row of a tile
+// whose first row is `row0` (summed from the left, in row0's type: the address arithmetic the kernels were tuned with)
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+template <typename T = int>
+__device__ __forceinline__ T acc_row(int r, int half, T row0 = 0) { return row0 + (r & 3) + 8 * (r >> 2) + 4 * half; }
+
+// float bits as an unsigned that orders like the float (radix select keys), and back
+__device__ __forceinline__ uint32_t orderable(float v) {
+    uint32_t u = __float_as_uint(v);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float from_orderable(uint32_t u) {
+    return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
+}
+
+// workspace slices start on 256 bytes
+inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
+
 }  // namespace gmp
 
 

@@ -28,27 +28,15 @@ struct SelectState {
     unsigned int out_count;
 };
 
-__device__ __forceinline__ uint32_t orderable(float v) {
-    uint32_t u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float from_orderable(uint32_t u) {
-    return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
-}
+using gmp::al;
+
 __device__ __forceinline__ unsigned long long make_key(float v, uint32_t flat) {
-    return ((unsigned long long)orderable(v) << 32) | (unsigned long long)(0xffffffffu - flat);
+    return ((unsigned long long)gmp::orderable(v) << 32) | (unsigned long long)(0xffffffffu - flat);
 }
 
 __global__ __launch_bounds__(THREADS) void hn_normalize_kernel(const float* __restrict__ z, int64_t n, int d, float* __restrict__ zn) {
-    const int lane = threadIdx.x % 64;
     const int64_t row = ((int64_t)blockIdx.x * THREADS + threadIdx.x) / 64;
-    if (row >= n) return;
-    const float* src = z + row * d;
-    float s = 0.f;
-    for (int c = lane; c < d; c += 64) s += src[c] * src[c];
-    s = gmp::wave_sum(s);
-    const float nr = fmaxf(sqrtf(s), 1e-12f);
-    for (int c = lane; c < d; c += 64) zn[row * d + c] = src[c] / nr;
+    if (row < n) gmp::normalize_row(z + row * d, d, zn + row * d, d, nullptr);
 }
 
 __global__ __launch_bounds__(THREADS) void hn_mask_kernel(float* __restrict__ S, int64_t n, const int64_t* __restrict__ edges, int64_t E) {
@@ -184,11 +172,9 @@ __global__ __launch_bounds__(THREADS) void hn_rank_kernel(const unsigned long lo
         const uint32_t flat = 0xffffffffu - (uint32_t)(mine & 0xffffffffull);
         out_edges[rank] = (int64_t)(flat / (uint32_t)n);
         out_edges[k + rank] = (int64_t)(flat % (uint32_t)n);
-        if (out_scores) out_scores[rank] = from_orderable((uint32_t)(mine >> 32));
+        if (out_scores) out_scores[rank] = gmp::from_orderable((uint32_t)(mine >> 32));
     }
 }
-
-inline size_t al(size_t b) { return (b + 255) & ~(size_t)255; }
 
 }  // namespace
 

@@ -1,5 +1,5 @@
 // Streaming hard-negative mining: the contract of hardneg.hip (gmp_hard_negative_topk) without the n x n similarity matrix.
-// A similarity tile lives only in MFMA accumulators, as in ntxent_stream.hip; the exact radix select of hardneg.hip runs over
+// A similarity tile (sim_tile.h) lives only in MFMA accumulators; the exact radix select of hardneg.hip runs over
 // RECOMPUTED tiles, so memory is O(n d + E + a fixed candidate capacity) and n is bounded by the 40 bits the flat pair index
 // i * n + j gets in the key (n <= 2^20) instead of by 65535.
 //
@@ -7,7 +7,8 @@
 //                            workgroup also resets the selection state
 //   gmp_csr_build            existing_edges grouped by target and by source (out-of-range endpoints dropped there)
 //   hns_tile_kernel<DP, M>   block (row tile of 128, column chunk of <= 1024): each of the four waves keeps its 32 rows in registers
-//                            and walks the chunk's 32-column tiles of zn (staged in LDS), S tile on v_mfma_f32_32x32x2_f32.  Only the
+//                            and walks the chunk's 32-column tiles of zn (staged in LDS), S tile on v_mfma_f32_32x32x2_f32 (Tile<DP>::product,
+//                            __builtin_amdgcn_mfma_f32_32x32x2f32).  Only the
 //                            UPPER triangle is computed: column tiles left of the row tile are skipped, elements j <= i dropped, and
 //                            an unmasked pair i < j with score s stands for the two keys (s, i n + j) and (s, j n + i).  The edge mask
 //                            is an LDS bitmap (one bit per element of the block's chunk) filled from the in- and out-neighbour lists
@@ -23,13 +24,13 @@
 // 11 / 11 / 11 / 7).  Integer atomics only; the result does not depend on the order they land in.
 #include <algorithm>
 
-#include "gnnmp_internal.h"
+#include "sim_tile.h"
 
 namespace {
 
-constexpr int THREADS = 256;
-constexpr int BM = 128;             // rows per workgroup (32 per wave)
-constexpr int BN = 32;              // columns per step
+using gmp::al;
+using namespace sim;
+
 constexpr int MAX_TPC = 32;         // column tiles per chunk: a mask bitmap of 128 rows x 1024 columns = 16 KiB
 constexpr int BINS = 2048;
 constexpr int MAX_K = 4096;
@@ -39,7 +40,6 @@ constexpr int FLAT_BITS = 40;
 constexpr unsigned long long FLAT_MAX = (1ull << FLAT_BITS) - 1ull;
 enum { HIST = 0, GATHER = 1, DUMP = 2 };
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned long long u64;
 
 // first in the workspace: `passes` is readable by the caller after the call (how many histogram passes ran)
@@ -55,8 +55,6 @@ struct State {
     u64 k_eff;                  // min(k, number of unmasked ordered pairs)
     u64 hist[BINS];
 };
-
-size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct Plan {
     int tiles, nct, tpc, C, dpad;
@@ -108,14 +106,6 @@ Ws carve(void* ws, int64_t n, int64_t d, int64_t E) {
     return w;
 }
 
-__device__ __forceinline__ uint32_t orderable(float v) {
-    uint32_t u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float from_orderable(uint32_t u) {
-    return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
-}
-
 __device__ void init_state(State* st, u64 k) {
     for (int i = threadIdx.x; i < BINS; i += blockDim.x) st->hist[i] = 0;
     if (threadIdx.x == 0) {
@@ -135,20 +125,9 @@ __device__ void init_state(State* st, u64 k) {
 __global__ __launch_bounds__(THREADS) void hns_normalize_kernel(const float* __restrict__ z, int64_t n, int d, int dpad, float* __restrict__ zn,
                                                                 State* st, u64 k) {
     if (blockIdx.x == 0) init_state(st, k);
-    const int lane = threadIdx.x % 64;
     const int64_t row = ((int64_t)blockIdx.x * THREADS + threadIdx.x) / 64;
-    if (row >= n) return;
-    const float* src = z + row * d;
-    float s = 0.f;
-    for (int c = lane; c < d; c += 64) s += src[c] * src[c];
-    s = gmp::wave_sum(s);
-    const float nr = fmaxf(sqrtf(s), 1e-12f);
-    for (int c = lane; c < dpad; c += 64) zn[row * dpad + c] = c < d ? src[c] / nr : 0.f;
+    if (row < n) gmp::normalize_row(z + row * d, d, zn + row * dpad, dpad, nullptr);
 }
-
-__device__ __forceinline__ int acc_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
-// a row difference as an int: only values within a tile are ever compared, anything further away just has to stay away
-__device__ __forceinline__ int rel(int64_t v) { return (int)max((int64_t)-(1 << 20), min((int64_t)(1 << 20), v)); }
 
 // one block: walk the digit histogram from the top, find the bucket holding the k_rem-th largest key
 __global__ __launch_bounds__(THREADS) void hns_pick_kernel(State* st, int is_flat, int shift, int bits) {
@@ -216,12 +195,7 @@ __global__ __launch_bounds__(THREADS, DP <= 128 ? 2 : 1) void hns_tile_kernel(co
                                                                               State* __restrict__ st, int is_flat, int shift, int bits,
                                                                               unsigned int* __restrict__ cand_s, u64* __restrict__ cand_f,
                                                                               float* __restrict__ scores_out) {
-    constexpr int LD = DP + 4;              // column-tile row stride: 16-byte slots of consecutive rows fall on consecutive bank slots
-    constexpr int KQ = DP / 8;              // float4 of the reduction range per lane (each half of the wave takes DP / 2)
-    constexpr int C4 = DP / 4;
-    constexpr int NLD = BN * C4 / THREADS;  // float4 per thread of one column tile
-    static_assert(DP % 32 == 0 && BN * C4 % THREADS == 0, "tile shape");
-    __shared__ float4 kt4[BN * LD / 4];
+    __shared__ float4 kt4[BN * Tile<DP>::LD / 4];
     __shared__ unsigned int bm[MAX_TPC * BM];               // [column tile of the chunk][wave][column]: bit r = row r of the wave is masked
     __shared__ unsigned int h[MODE == HIST ? BINS : 1];
     float* kt = reinterpret_cast<float*>(kt4);
@@ -268,33 +242,19 @@ __global__ __launch_bounds__(THREADS, DP <= 128 ? 2 : 1) void hns_tile_kernel(co
         }
     }
 
+    using Tl = Tile<DP>;
     // the wave's 32 rows: lane (row l31, k in [half DP/2, (half + 1) DP/2)), zero beyond dpad and beyond n
-    float4 q[KQ];
+    float4 q[Tl::KQ];
     {
         const int64_t qrow = i0 + l31;
 #pragma unroll
-        for (int u = 0; u < KQ; ++u) {
+        for (int u = 0; u < Tl::KQ; ++u) {
             const int k = half * (DP / 2) + 4 * u;
             q[u] = (qrow < n && k < dpad) ? *reinterpret_cast<const float4*>(zn + qrow * dpad + k) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
     }
     const int rlim = rel(n - i0 - 4 * half);    // accumulator row rr exists iff rr < rlim
-    float4 pf[NLD];
-    auto fetch = [&](int64_t j0) {
-#pragma unroll
-        for (int u = 0; u < NLD; ++u) {
-            const int it = t + u * THREADS, r = it / C4, c4 = it % C4;
-            const int64_t j = j0 + r;
-            pf[u] = (j < n && 4 * c4 < dpad) ? *reinterpret_cast<const float4*>(zn + j * dpad + 4 * c4) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    };
-    auto stash = [&]() {
-#pragma unroll
-        for (int u = 0; u < NLD; ++u) {
-            const int it = t + u * THREADS, r = it / C4, c4 = it % C4;
-            *reinterpret_cast<float4*>(kt + r * LD + 4 * c4) = pf[u];
-        }
-    };
+    float4 pf[Tl::NLD];
 
     const u64 dmask = (1ull << bits) - 1ull;
     const int hi = shift + bits;
@@ -310,43 +270,19 @@ __global__ __launch_bounds__(THREADS, DP <= 128 ? 2 : 1) void hns_tile_kernel(co
         pcnt += (c_);                                           \
     } while (0)
 
-    fetch((int64_t)ct0 * BN);
+    Tl::fetch(pf, zn, (int64_t)ct0 * BN, n, dpad, t);
     for (int ct = ct0; ct < ct1; ++ct) {
         __syncthreads();                    // the previous tile's readers are done (first trip: the bitmap and the bins are ready)
-        stash();
+        Tl::stash(pf, kt, t);
         __syncthreads();
-        if (ct + 1 < ct1) fetch((int64_t)(ct + 1) * BN);
+        if (ct + 1 < ct1) Tl::fetch(pf, zn, (int64_t)(ct + 1) * BN, n, dpad, t);
         const int64_t cbase = (int64_t)ct * BN;
         if (cbase + BN - 1 < i0 + (MODE == DUMP ? 0 : 1)) continue;     // this wave's rows all lie at or below the tile's columns
         const int64_t colj = cbase + l31;
 
-        f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-        const float4* b4 = reinterpret_cast<const float4*>(kt + l31 * LD + half * (DP / 2));
-        // two float4 of B ahead of the MFMAs that use them and no further (ntxent_stream.hip)
-        constexpr int SG = KQ >= 2 ? 2 : 1;
-        float4 bc[SG], bn[SG];
-#pragma unroll
-        for (int v = 0; v < SG; ++v) bc[v] = b4[v];
-#pragma unroll
-        for (int u0 = 0; u0 < KQ; u0 += SG) {
-#pragma unroll
-            for (int v = 0; v < SG; ++v)
-                if (u0 + SG + v < KQ) bn[v] = b4[u0 + SG + v];
-#pragma unroll
-            for (int v = 0; v < SG; ++v) {
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(q[u0 + v].x, bc[v].x, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(q[u0 + v].y, bc[v].y, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(q[u0 + v].z, bc[v].z, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(q[u0 + v].w, bc[v].w, acc, 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int v = 0; v < SG; ++v) bc[v] = bn[v];
-        }
+        const f32x16 acc = Tl::product(q, kt, l31, half);
 
-        // accumulator r is row i0 + 4 half + rr(r), rr = (r & 3) + 8 (r >> 2); column colj
+        // accumulator r is row i0 + 4 half + rr(r), rr = acc_row(r, 0); column colj
         const int dd = rel(colj - i0 - 4 * half);                       // column minus the lane's first row
         const bool col_ok = colj < n;
         const unsigned int mw = rowptr ? bm[(ct - cs) * BM + wave * 32 + l31] : 0u;
@@ -368,7 +304,7 @@ __global__ __launch_bounds__(THREADS, DP <= 128 ? 2 : 1) void hns_tile_kernel(co
                 continue;
             }
             if (!upper || masked) continue;
-            const u64 sb = orderable(v);
+            const u64 sb = gmp::orderable(v);
             if (MODE == HIST) {
                 if (!is_flat) {
                     if ((sb >> hi) == (sprefix >> hi)) HNS_HIST_ADD((unsigned int)((sb >> shift) & dmask), 2u);
@@ -437,7 +373,7 @@ __global__ __launch_bounds__(THREADS) void hns_rank_kernel(const State* __restri
         if (lane == 0 && rank < keff) {
             out_edges[rank] = (int64_t)(mf / (u64)n);
             out_edges[k + rank] = (int64_t)(mf % (u64)n);
-            if (out_scores) out_scores[rank] = from_orderable(ms);
+            if (out_scores) out_scores[rank] = gmp::from_orderable(ms);
         }
     }
 }

@@ -19,7 +19,7 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using gmp::f32x16;
 
 constexpr int F = 256;              // node embedding width
 constexpr int HID = 256;            // hidden units of the scorer
@@ -80,7 +80,7 @@ __device__ __forceinline__ float score_tile(float* __restrict__ tile, float* __r
             acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bv[q].w, acc, 0, 0, 0);
         }
 #pragma unroll
-        for (int r = 0; r < 16; ++r) red[(wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * 32 + l31] = acc[r];
+        for (int r = 0; r < 16; ++r) red[gmp::acc_row(r, half, wave * 32) * 32 + l31] = acc[r];
         __syncthreads();
         if (t < 256) {                                              // (waves 0-3: wave-uniform)
             const int col = n0 + 4 * c4;

@@ -23,7 +23,7 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using gmp::f32x16;
 
 constexpr int F = 256;              // node embedding width
 constexpr int HID = 256;            // hidden units of the scorer
@@ -98,7 +98,7 @@ __global__ __launch_bounds__(FWD_THREADS) void lp_score_fwd_kernel(const float* 
     }
     __syncthreads();                                            // every wave is done with the feature tile: it becomes red[8][32][32]
 #pragma unroll
-    for (int r = 0; r < 16; ++r) tile[(wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * 32 + l31] = acc[r];
+    for (int r = 0; r < 16; ++r) tile[gmp::acc_row(r, half, wave * 32) * 32 + l31] = acc[r];
     __syncthreads();
     if (t >= 256) return;                                       // (waves 4-7: wave-uniform)
     const int row = t >> 3, c4 = t & 7, col = n0 + 4 * c4;
@@ -200,7 +200,7 @@ __global__ __launch_bounds__(64) void lp_dw0_kernel(const float* __restrict__ h,
     }
     float* o = part + (int64_t)blockIdx.y * W0N;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) o[(int64_t)(n0 + (r & 3) + 8 * (r >> 2) + 4 * half) * KF + k0 + l31] = acc[r];
+    for (int r = 0; r < 16; ++r) o[(int64_t)gmp::acc_row(r, half, n0) * KF + k0 + l31] = acc[r];
 }
 
 // g_feat = g_z W0 for 32 pairs x (the same 32 columns of all three segments); wave w reduces hidden units [64 w, 64 w + 64)
@@ -232,7 +232,7 @@ __global__ __launch_bounds__(256) void lp_gfeat_kernel(const float* __restrict__
 #pragma unroll
     for (int s = 0; s < 3; ++s)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) red[wave][s][((r & 3) + 8 * (r >> 2) + 4 * half) * 32 + l31] = acc[s][r];
+        for (int r = 0; r < 16; ++r) red[wave][s][gmp::acc_row(r, half) * 32 + l31] = acc[s][r];
     __syncthreads();
     for (int e = t; e < 32 * 32; e += 256) {
         const int row = e >> 5, col = e & 31;

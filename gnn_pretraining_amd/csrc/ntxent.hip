@@ -6,6 +6,8 @@
 
 namespace {
 
+using gmp::al;
+
 constexpr int THREADS = 256;
 
 struct Ws {
@@ -15,8 +17,6 @@ struct Ws {
     float* gzn;    // [2n,d]
     float* rowloss;// [2n]
 };
-
-size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
 
 Ws carve(void* ws, int64_t n, int d) {
     char* p = (char*)ws;
@@ -30,19 +30,12 @@ Ws carve(void* ws, int64_t n, int d) {
     return w;
 }
 
-// one wave per row: zn = z / max(||z||, eps)   (F.normalize, eps = 1e-12)
+// one wave per row of [z1; z2]
 __global__ __launch_bounds__(THREADS) void normalize_kernel(const float* __restrict__ z1, const float* __restrict__ z2,
                                                             int64_t n, int d, float* __restrict__ zn, float* __restrict__ norm) {
-    const int lane = threadIdx.x % 64;
     const int64_t row = ((int64_t)blockIdx.x * THREADS + threadIdx.x) / 64;
     if (row >= 2 * n) return;
-    const float* src = row < n ? z1 + row * d : z2 + (row - n) * d;
-    float s = 0.f;
-    for (int c = lane; c < d; c += 64) s += src[c] * src[c];
-    s = gmp::wave_sum(s);
-    const float nr = fmaxf(sqrtf(s), 1e-12f);
-    for (int c = lane; c < d; c += 64) zn[row * d + c] = src[c] / nr;
-    if (lane == 0) norm[row] = nr;
+    gmp::normalize_row(row < n ? z1 + row * d : z2 + (row - n) * d, d, zn + row * d, d, norm + row);
 }
 
 __device__ __forceinline__ float block_reduce(float v, float* sh, bool is_max) {
@@ -124,6 +117,10 @@ int args_ok(const char* who, int64_t n, int d, float T) {
 
 }  // namespace
 
+void gmp::sum_rows(const float* v, int64_t n, float* out, hipStream_t st) {
+    hipLaunchKernelGGL(sum_rows_kernel, dim3(1), dim3(THREADS), 0, st, v, n, out);
+}
+
 extern "C" size_t gmp_nt_xent_workspace_bytes(int64_t n, int d) {
     if (n < 1 || d < 1) return 0;
     const size_t R = 2 * (size_t)n;
@@ -141,7 +138,7 @@ extern "C" int gmp_nt_xent_fwd(const float* z1, const float* z2, int64_t n, int 
     hipLaunchKernelGGL(normalize_kernel, dim3((unsigned)((R * 64 + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, z1, z2, n, d, w.zn, w.norm);
     if (int rc = gmp_gemm_f32(GMP_GEMM_NT, w.zn, w.zn, nullptr, w.G, R, R, d, d, d, R, 1.f / T, 0, 0, nullptr, 0, stream)) return rc;
     hipLaunchKernelGGL(row_loss_kernel, dim3((unsigned)R), dim3(THREADS), 0, st, w.G, n, w.rowloss);
-    hipLaunchKernelGGL(sum_rows_kernel, dim3(1), dim3(THREADS), 0, st, (const float*)w.rowloss, R, loss_sum);
+    gmp::sum_rows(w.rowloss, R, loss_sum, st);
     return gmp::check_launch("nt_xent_fwd kernels");
 }
 
@@ -207,13 +204,7 @@ __global__ __launch_bounds__(THREADS) void normalize_grouped_kernel(const float*
         if (lane == 0) norm[pr] = 1.f;
         return;
     }
-    const float* src = z + (g.off[grp] + i) * g.d;
-    float s = 0.f;
-    for (int c = lane; c < g.d; c += 64) s += src[c] * src[c];
-    s = gmp::wave_sum(s);
-    const float nr = fmaxf(sqrtf(s), 1e-12f);
-    for (int c = lane; c < g.d; c += 64) dst[c] = src[c] / nr;
-    if (lane == 0) norm[pr] = nr;
+    gmp::normalize_row(z + (g.off[grp] + i) * g.d, g.d, dst, g.d, norm + pr);
 }
 
 // block (i, grp): row i of group grp, exactly row_loss_kernel on the group's R x R corner; padding -> 0

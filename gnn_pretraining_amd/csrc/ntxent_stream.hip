@@ -1,5 +1,5 @@
 // Streaming NT-Xent / InfoNCE: the loss and gradient of ntxent.hip without the [2n, 2n] similarity matrix.  The similarity tile
-// lives only in MFMA accumulators (and, for the backward's second product, in a 32 x 32 per-wave LDS patch), so memory is O(n d)
+// (sim_tile.h) lives only in MFMA accumulators (and, for the backward's second product, in a 32 x 32 per-wave LDS patch), so memory is O(n d)
 // and n is bounded by int32 row indexing of the R = 2n rows, not by 8192.  fp32 end to end, every product on
 // v_mfma_f32_32x32x2_f32, every reduction in a fixed order (no float atomics): two calls on the same input are bitwise equal.
 //
@@ -10,31 +10,25 @@
 //                                         positive's similarity stored when its column passes; the lanes' partials are merged by a
 //                                         butterfly and written per (chunk, row)
 //             nts_finish_kernel           chunks merged in chunk order -> lse[R] (kept for the backward), rowloss = lse - s_pos
-//             nts_sum_rows_kernel         the fixed-order sum of ntxent.hip
+//             gmp::sum_rows               the fixed-order sum of ntxent.hip
 //   backward  nts_tile_kernel<DP, true>   S is symmetric and pos an involution, so (G + G^T) zn is one pass over recomputed tiles:
 //                                           g_zn_i = 1/T sum_{j != i} (exp(s_ij - lse_i) + exp(s_ij - lse_j) - 2 [j = pos(i)]) zn_j
 //                                         the weight tile goes through the wave's LDS patch to become the A operand of the second
 //                                         product with the zn column tile that is already in LDS; per-chunk partial g_zn
 //             nts_normalize_bwd_kernel    partials added in chunk order, then normalize_bwd_kernel's formula (norm <= 1e-12 rule)
-// The k order of an MFMA chain is free as long as A and B agree, so lanes 0-31 take the first half of the reduction range and
-// lanes 32-63 the second, each in float4 steps (ds_read_b128 / global dwordx4), as lp_score.hip does.
 // The exponentials: per S element the backward issues two v_exp_f32 next to 4 d MFMA flops (at d = 128, 32 x 8 issue cycles per
 // 128 MFMAs of 64 cycles).  A wave cannot hide them under its own dependent MFMAs, so for d <= 128 the kernel is bounded to
 // 256 registers and two workgroups share a CU: one wave's exponentials issue while the SIMD's other wave owns the MFMA pipe.
-#include "gnnmp_internal.h"
+#include "sim_tile.h"
 
 namespace {
 
-constexpr int THREADS = 256;
-constexpr int BM = 128;         // query rows per workgroup (32 per wave)
-constexpr int BN = 32;          // columns per step
+using gmp::al;
+using namespace sim;
+
 constexpr int WLD = 36;         // row stride of the weight patch (floats): 144 B, 16-byte slots of 32 rows spread over the banks
 constexpr int MAX_CHUNKS = 16;
 constexpr int64_t MAX_N = (INT32_MAX - BM) / 2;     // 2n rows plus one tile of padding stay int32
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // how the R x R problem is cut: row tiles x column chunks, enough workgroups for two per CU while a chunk keeps >= 2 column tiles
 struct Plan {
@@ -80,24 +74,13 @@ size_t ws_bytes_of(const Plan& p, int d) {
     return al(R * d * 4) + 4 * al(R * 4) + 2 * al(R * p.C * 4) + al(R * d * 4 * p.C) + 256;
 }
 
-// one wave per row: zn = z / max(||z||, eps)   (ntxent.hip's normalize_kernel)
+// one wave per row of [z1; z2]
 __global__ __launch_bounds__(THREADS) void nts_normalize_kernel(const float* __restrict__ z1, const float* __restrict__ z2, int64_t n, int d,
                                                                 float* __restrict__ zn, float* __restrict__ norm) {
-    const int lane = threadIdx.x % 64;
     const int64_t row = ((int64_t)blockIdx.x * THREADS + threadIdx.x) / 64;
     if (row >= 2 * n) return;
-    const float* src = row < n ? z1 + row * d : z2 + (row - n) * d;
-    float s = 0.f;
-    for (int c = lane; c < d; c += 64) s += src[c] * src[c];
-    s = gmp::wave_sum(s);
-    const float nr = fmaxf(sqrtf(s), 1e-12f);
-    for (int c = lane; c < d; c += 64) zn[row * d + c] = src[c] / nr;
-    if (lane == 0) norm[row] = nr;
+    gmp::normalize_row(row < n ? z1 + row * d : z2 + (row - n) * d, d, zn + row * d, d, norm + row);
 }
-
-__device__ __forceinline__ int acc_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
-// a row difference as an int: only values within a tile are ever compared, anything further away just has to stay away
-__device__ __forceinline__ int rel(int64_t v) { return (int)max((int64_t)-(1 << 20), min((int64_t)(1 << 20), v)); }
 
 // (m, s) <- (m, s) (+) (m2, s2) for sum_j exp(x_j) = s exp(m); an empty side is (-inf, 0)
 __device__ __forceinline__ void lse_merge(float& m, float& s, float m2, float s2) {
@@ -111,12 +94,8 @@ __global__ __launch_bounds__(THREADS, DP <= 128 ? 2 : 1) void nts_tile_kernel(co
                                                                               int nct, const float* __restrict__ lse, float* __restrict__ pm,
                                                                               float* __restrict__ ps, float* __restrict__ spos,
                                                                               float* __restrict__ gpart) {
-    constexpr int LD = DP + 4;              // column-tile row stride: 16-byte slots of consecutive rows fall on consecutive bank slots
-    constexpr int KQ = DP / 8;              // float4 of the reduction range per lane (each half of the wave takes DP / 2)
-    constexpr int C4 = DP / 4;
-    constexpr int NLD = BN * C4 / THREADS;  // float4 per thread of one column tile
+    constexpr int LD = Tile<DP>::LD;
     constexpr int NCB = DP / 32;            // 32-column blocks of g_zn
-    static_assert(DP % 32 == 0 && BN * C4 % THREADS == 0, "tile shape");
     __shared__ float4 kt4[BN * LD / 4];
     __shared__ float4 wst4[BWD ? 4 * 32 * WLD / 4 : 1];
     float* kt = reinterpret_cast<float*>(kt4);
@@ -126,33 +105,19 @@ __global__ __launch_bounds__(THREADS, DP <= 128 ? 2 : 1) void nts_tile_kernel(co
     const int chunk = blockIdx.y;
     const int ct0 = chunk * tpc, ct1 = min(ct0 + tpc, nct);
 
+    using Tl = Tile<DP>;
     // the wave's 32 query rows: lane (row l31, k in [half DP/2, (half + 1) DP/2)), zero beyond d and beyond R
-    float4 q[KQ];
+    float4 q[Tl::KQ];
     {
         const int64_t qrow = i0 + l31;
 #pragma unroll
-        for (int u = 0; u < KQ; ++u) {
+        for (int u = 0; u < Tl::KQ; ++u) {
             const int k = half * (DP / 2) + 4 * u;
             q[u] = (qrow < R && k < d) ? *reinterpret_cast<const float4*>(zn + qrow * d + k) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
     }
     const int rlim = rel(R - i0 - 4 * half);    // accumulator row rr exists iff rr < rlim
-    float4 pf[NLD];
-    auto fetch = [&](int64_t j0) {
-#pragma unroll
-        for (int u = 0; u < NLD; ++u) {
-            const int it = t + u * THREADS, r = it / C4, c4 = it % C4;
-            const int64_t j = j0 + r;
-            pf[u] = (j < R && 4 * c4 < d) ? *reinterpret_cast<const float4*>(zn + j * d + 4 * c4) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    };
-    auto stash = [&]() {
-#pragma unroll
-        for (int u = 0; u < NLD; ++u) {
-            const int it = t + u * THREADS, r = it / C4, c4 = it % C4;
-            *reinterpret_cast<float4*>(kt + r * LD + 4 * c4) = pf[u];
-        }
-    };
+    float4 pf[Tl::NLD];
 
     float rm[16], rs[16];                   // forward: running max / sum of exp of this lane's columns, per accumulator row
     float li[16];                           // backward: lse of the accumulator rows
@@ -172,46 +137,19 @@ __global__ __launch_bounds__(THREADS, DP <= 128 ? 2 : 1) void nts_tile_kernel(co
             for (int r = 0; r < 16; ++r) g[cb][r] = 0.f;
     }
 
-    fetch((int64_t)ct0 * BN);
+    Tl::fetch(pf, zn, (int64_t)ct0 * BN, R, d, t);
     for (int ct = ct0; ct < ct1; ++ct) {
         __syncthreads();                    // the previous tile's readers are done
-        stash();
+        Tl::stash(pf, kt, t);
         __syncthreads();
-        if (ct + 1 < ct1) fetch((int64_t)(ct + 1) * BN);
+        if (ct + 1 < ct1) Tl::fetch(pf, zn, (int64_t)(ct + 1) * BN, R, d, t);
         const int64_t col = (int64_t)ct * BN + l31;
         float lj = 0.f;
         if (BWD) lj = col < R ? lse[col] : 0.f;
 
-        // S tile: rows i0 + acc_row(r), column `col`
-        f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-        const float4* b4 = reinterpret_cast<const float4*>(kt + l31 * LD + half * (DP / 2));
-        // two float4 of B ahead of the MFMAs that use them and no further: left alone, the scheduler hoists every LDS read of the tile to
-        // the top and spills the query rows
-        constexpr int SG = KQ >= 2 ? 2 : 1;
-        float4 bc[SG], bn[SG];
-#pragma unroll
-        for (int v = 0; v < SG; ++v) bc[v] = b4[v];
-#pragma unroll
-        for (int u0 = 0; u0 < KQ; u0 += SG) {
-#pragma unroll
-            for (int v = 0; v < SG; ++v)
-                if (u0 + SG + v < KQ) bn[v] = b4[u0 + SG + v];
-#pragma unroll
-            for (int v = 0; v < SG; ++v) {
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(q[u0 + v].x, bc[v].x, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(q[u0 + v].y, bc[v].y, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(q[u0 + v].z, bc[v].z, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(q[u0 + v].w, bc[v].w, acc, 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int v = 0; v < SG; ++v) bc[v] = bn[v];
-        }
+        const f32x16 acc = Tl::product(q, kt, l31, half);     // rows i0 + acc_row(r, half), column `col`
 
-        // row / column tests as small ints relative to the wave's first row (64-bit row numbers per accumulator would cost 64 registers):
-        // accumulator r is row i0 + 4 half + rr(r), rr = (r & 3) + 8 (r >> 2) a compile-time constant
+        // row / column tests relative to the wave's first row (rel, sim_tile.h)
         const int dd = rel(col - i0 - 4 * half), dpos_a = rel(col - n - i0 - 4 * half), dpos_b = rel(col + n - i0 - 4 * half);
         const bool col_ok = col < R;
         if (!BWD) {
@@ -319,20 +257,6 @@ __global__ __launch_bounds__(THREADS) void nts_finish_kernel(const float* __rest
     rowloss[row] = l - spos[row];
 }
 
-// ntxent.hip's sum_rows_kernel
-__global__ __launch_bounds__(THREADS) void nts_sum_rows_kernel(const float* __restrict__ v, int64_t n, float* out) {
-    __shared__ float sh[THREADS];
-    float s = 0.f;
-    for (int64_t i = threadIdx.x; i < n; i += THREADS) s += v[i];
-    sh[threadIdx.x] = s;
-    __syncthreads();
-    for (int d = THREADS / 2; d > 0; d >>= 1) {
-        if (threadIdx.x < d) sh[threadIdx.x] += sh[threadIdx.x + d];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] = sh[0];
-}
-
 // one wave per row: g_zn = the chunks' partials in chunk order, then g_z = g_scale * (g_zn - zn <zn, g_zn>) / norm with
 // normalize_bwd_kernel's rule for norm <= 1e-12 (d <= 256: four columns per lane)
 __global__ __launch_bounds__(THREADS) void nts_normalize_bwd_kernel(const float* __restrict__ zn, const float* __restrict__ norm,
@@ -406,7 +330,7 @@ extern "C" int gmp_nt_xent_stream_fwd(const float* z1, const float* z2, int64_t 
     launch_tiles<false>(p, d, 1.f / T, w, st);
     hipLaunchKernelGGL(nts_finish_kernel, dim3((unsigned)((R + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, (const float*)w.pm,
                        (const float*)w.ps, (const float*)w.spos, R, p.C, w.lse, w.rowloss);
-    hipLaunchKernelGGL(nts_sum_rows_kernel, dim3(1), dim3(THREADS), 0, st, (const float*)w.rowloss, R, loss_sum);
+    gmp::sum_rows(w.rowloss, R, loss_sum, st);
     return gmp::check_launch("nt_xent_stream_fwd kernels");
 }
 

@@ -57,7 +57,8 @@ def _check_exact(emb, ex, k):
     assert torch.equal(got, dense.cpu()) and torch.equal(sc, dsc.cpu())
 
 
-@pytest.mark.parametrize("n,d,m,k", [(64, 16, 100, 32), (301, 32, 900, 256), (1000, 24, 5000, 256), (130, 8, 0, 8)])
+@pytest.mark.parametrize("n,d,m,k", [(64, 16, 100, 32), (301, 32, 900, 256), (1000, 24, 5000, 256), (130, 8, 0, 8),
+                                     (301, 40, 900, 256), (301, 100, 900, 256), (301, 160, 900, 256), (301, 256, 900, 256)])  # every tile width
 def test_stream_bit_exact_on_four_ones_rows(n, d, m, k):
     _check_exact(_four_ones(n, d, n + d), _edges(n, m, m + 1), k)
 
@@ -127,7 +128,7 @@ def test_beyond_the_32_bit_flat_index():
         ops.hard_negative_topk(emb.to(DEV), ex.to(DEV), k, impl="matrix")
 
 
-@pytest.mark.parametrize("n,d,m,k", [(5, 6, 3, 4), (5, 10, 0, 6), (70, 6, 40, 32), (200, 10, 0, 64)])
+@pytest.mark.parametrize("n,d,m,k", [(5, 6, 3, 4), (5, 10, 0, 6), (70, 6, 40, 32), (200, 10, 0, 64), (70, 38, 40, 32)])
 def test_shape_edges_small_n_odd_dim_no_edges(n, d, m, k):
     g = torch.Generator().manual_seed(n + d)
     emb, ex = torch.randn(n, d, generator=g), _edges(n, m, 2)

@@ -85,7 +85,8 @@ def errors(res, want):
 
 
 PARITY = [(2, 4, 1.0, None), (8, 128, 0.5, None), (170, 128, 0.5, None), (333, 128, 0.2, None), (1000, 64, 0.2, None),
-          (2049, 256, 0.5, None), (8192, 128, 0.2, None), (8193, 128, 0.5, None), (10000, 128, 0.2, None), (2048, 128, 0.1, 0.3)]
+          (2049, 256, 0.5, None), (8192, 128, 0.2, None), (8193, 128, 0.5, None), (10000, 128, 0.2, None), (2048, 128, 0.1, 0.3),
+          (333, 20, 0.5, None), (333, 32, 0.5, None), (333, 160, 0.5, None), (70, 36, 0.2, None)]     # tile widths 32, 32, 192, 64
 
 
 @pytest.mark.parametrize("n,d,T,clustered", PARITY)

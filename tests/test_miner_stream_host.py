@@ -75,7 +75,8 @@ def test_unknown_impl_raises():
 
 
 def test_stream_kernel_source_uses_the_fp32_mfma_and_no_float_atomics():
-    src = (ROOT / "gnn_pretraining_amd" / "csrc" / "hardneg_stream.hip").read_text()
+    csrc = ROOT / "gnn_pretraining_amd" / "csrc"                   # the file, the tile core and the helpers it is built on
+    src = "".join((csrc / f).read_text() for f in ("hardneg_stream.hip", "sim_tile.h", "gnnmp_internal.h"))
     assert "mfma_f32_32x32x2f32" in src
     for m in re.finditer(r"atomicAdd\(&([\w>-]+)", src):                               # integer counts only
         assert m.group(1) in ("h", "st->hist", "st->out_count"), m.group(0)

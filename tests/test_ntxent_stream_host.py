@@ -55,6 +55,7 @@ def test_workspace_of_a_problem_beyond_the_matrix_form():
 
 
 def test_stream_kernel_source_uses_the_f32_mfma_and_no_float_atomics():
-    src = (ROOT / "gnn_pretraining_amd" / "csrc" / "ntxent_stream.hip").read_text()
+    csrc = ROOT / "gnn_pretraining_amd" / "csrc"                   # the file, the tile core and the helpers it is built on
+    src = "".join((csrc / f).read_text() for f in ("ntxent_stream.hip", "sim_tile.h", "gnnmp_internal.h", "ntxent.hip"))
     assert "mfma_f32_32x32x2f32" in src
     assert not re.search(r"atomicAdd|__hip_atomic|unsafeAtomic", src)
