@@ -143,8 +143,9 @@ __device__ __forceinline__ float4 colsum_t(float4 v, float4 (*sh)[CQ_], int rl, 
     return s;
 }
 
-// RL row lanes per column quad: 32 (256 threads, segments up to 16 * 32 = 512 rows) or 64 (512 threads, up to 1,024 rows: the
-// 32-graph segments of the single-domain scheme and of validation batches stay in this one-read regime)
+// RL row lanes per column quad: 64 in the short regime (512 threads, 4 / 8 / 16 rows per thread, up to 1,024 rows: the 32-graph segments
+// of the single-domain scheme and of validation batches stay in this one-read regime), 256 in the medium one; nothing launches the
+// 32-lane default any more (the slab kernels, 256 threads, are the 32-lane layout)
 // CQT column quads per tile: 8 (32 columns) everywhere but the medium regime, which takes 4 (16 columns) x 256 row lanes
 template <int RPT, int RL = SRL, int CQT = SCQ>
 __global__ __launch_bounds__(RL * CQT) void bn_fwd_short_kernel(BnArgs a) {
@@ -742,18 +743,9 @@ extern "C" size_t gmp_bn_sync_bytes(int C, int S) { return (size_t)slab_sync_wor
 // (4 waves x 60 VGPRs per SIMD) only ONE such wave fits per SIMD, half the workgroups wait for a slot and the kernel takes
 // 31 us instead of the 15 us it takes alone; at 8 rows per thread two waves fit.  The forward takes the wide form too since the
 // column sums fold by shuffles (1.420 -> 1.405 ms per step; 1,024-thread blocks: no further gain).
-#define GMP_BN_SHORT_LAUNCH(KERNEL, MAXROWS, GRID, BLK, ST, ARGS, WIDE)                \
-    do {                                                                               \
-        if (WIDE) {                                                                    \
-            const dim3 blk2(2 * SRL * SCQ);                                            \
-            if ((MAXROWS) <= 8 * SRL) hipLaunchKernelGGL((KERNEL<4, 2 * SRL>), GRID, blk2, 0, ST, ARGS);        \
-            else if ((MAXROWS) <= 16 * SRL) hipLaunchKernelGGL((KERNEL<8, 2 * SRL>), GRID, blk2, 0, ST, ARGS);  \
-            else hipLaunchKernelGGL((KERNEL<16, 2 * SRL>), GRID, blk2, 0, ST, ARGS);   \
-        } else if ((MAXROWS) <= 4 * SRL) hipLaunchKernelGGL(KERNEL<4>, GRID, BLK, 0, ST, ARGS);      \
-        else if ((MAXROWS) <= 8 * SRL) hipLaunchKernelGGL(KERNEL<8>, GRID, BLK, 0, ST, ARGS); \
-        else if ((MAXROWS) <= 16 * SRL) hipLaunchKernelGGL(KERNEL<16>, GRID, BLK, 0, ST, ARGS); \
-        else hipLaunchKernelGGL((KERNEL<16, 2 * SRL>), GRID, dim3(2 * SRL * SCQ), 0, ST, ARGS);  \
-    } while (0)
+// Every short segment takes this form (the 32-lane launches went when both directions had turned wide): four, eight or sixteen rows per
+// thread.  The backward keeps the gated gradient in registers up to 384 rows (gmp_bn_bwd) and joins this ladder above.
+constexpr int WRL = 2 * SRL;      // 64 row lanes
 
 extern "C" int gmp_bn_fwd(const float* x, const float* residual, const int32_t* seg_ptr, const int32_t* seg_group, int S,
                           int64_t max_seg_rows, int64_t rows, int C, const float* gamma, const float* beta, float* running_mean,
@@ -779,7 +771,10 @@ extern "C" int gmp_bn_fwd(const float* x, const float* residual, const int32_t* 
         hipLaunchKernelGGL(bn_fwd_slab_kernel<SLAB_RPT>, dim3(S * a.slabs, C / SCOLS), blk, 0, st, a);
         if (a.fold_running) return gmp::check_launch("bn_fwd_slab_kernel");
     } else if (max_seg_rows <= SHORT_MAX) {
-        GMP_BN_SHORT_LAUNCH(bn_fwd_short_kernel, max_seg_rows, dim3(S, C / SCOLS), blk, st, a, true);
+        const dim3 grid(S, C / SCOLS), blk2(WRL * SCQ);
+        if (max_seg_rows <= 4 * WRL) hipLaunchKernelGGL((bn_fwd_short_kernel<4, WRL>), grid, blk2, 0, st, a);
+        else if (max_seg_rows <= 8 * WRL) hipLaunchKernelGGL((bn_fwd_short_kernel<8, WRL>), grid, blk2, 0, st, a);
+        else hipLaunchKernelGGL((bn_fwd_short_kernel<16, WRL>), grid, blk2, 0, st, a);
     } else if (max_seg_rows <= MID_MAX) {
         GMP_BN_MID_LAUNCH(bn_fwd_short_kernel, max_seg_rows, S, C, st, a);
     } else {
@@ -935,12 +930,14 @@ extern "C" int gmp_bn_bwd(const float* g_y, const float* x, const float* residua
             G = 0;
         }
         hipLaunchKernelGGL(bn_bwd_slab_kernel<SLAB_RPT>, dim3(S * a.slabs, C / SCOLS), blk, 0, st, a);
-    } else if (max_seg_rows <= 8 * SRL) {                                 // up to 256 rows: four rows per thread, the gated gradient kept in registers
-        hipLaunchKernelGGL((bn_bwd_short_kernel<4, 2 * SRL, SCQ, true>), dim3(S, C / SCOLS), dim3(2 * SRL * SCQ), 0, st, a);
-    } else if (max_seg_rows <= 12 * SRL) {                                // 257..384 rows (the stacked step): six rows per thread, likewise
-        hipLaunchKernelGGL((bn_bwd_short_kernel<6, 2 * SRL, SCQ, true>), dim3(S, C / SCOLS), dim3(2 * SRL * SCQ), 0, st, a);
+    } else if (max_seg_rows <= 4 * WRL) {                                 // up to 256 rows: four rows per thread, the gated gradient kept in registers
+        hipLaunchKernelGGL((bn_bwd_short_kernel<4, WRL, SCQ, true>), dim3(S, C / SCOLS), dim3(WRL * SCQ), 0, st, a);
+    } else if (max_seg_rows <= 6 * WRL) {                                 // 257..384 rows (the stacked step): six rows per thread, likewise
+        hipLaunchKernelGGL((bn_bwd_short_kernel<6, WRL, SCQ, true>), dim3(S, C / SCOLS), dim3(WRL * SCQ), 0, st, a);
+    } else if (max_seg_rows <= 8 * WRL) {                                 // 385..512 rows: eight rows per thread, the gradient read twice
+        hipLaunchKernelGGL((bn_bwd_short_kernel<8, WRL>), dim3(S, C / SCOLS), dim3(WRL * SCQ), 0, st, a);
     } else if (max_seg_rows <= SHORT_MAX) {
-        GMP_BN_SHORT_LAUNCH(bn_bwd_short_kernel, max_seg_rows, dim3(S, C / SCOLS), blk, st, a, true);
+        hipLaunchKernelGGL((bn_bwd_short_kernel<16, WRL>), dim3(S, C / SCOLS), dim3(WRL * SCQ), 0, st, a);
     } else if (max_seg_rows <= MID_MAX) {
         GMP_BN_MID_LAUNCH(bn_bwd_short_kernel, max_seg_rows, S, C, st, a);
     } else {

@@ -378,9 +378,29 @@ def bn_sync_words(channels: int, num_segments: int) -> int:
     return L.lib().gmp_bn_sync_bytes(channels, num_segments) // 4
 
 
+def _bn_params(Cc: int, S: int, seg_group: Optional[Tensor], named) -> None:
+    """gamma / beta (and the running pair, when given) are [C], or [groups, C] with a seg_group table of S entries (< groups: the caller's part)."""
+    if seg_group is None:
+        for n, t in named[:2]:
+            _need(t, torch.float32, n, 1)
+            if t.numel() != Cc:
+                raise L.GnnmpError(f"bn: {n} length")
+        return
+    _need(seg_group, torch.int32, "seg_group", 1)
+    if seg_group.numel() != S:
+        raise L.GnnmpError(f"bn: seg_group has {seg_group.numel()} entries for {S} segments")
+    for n, t in named:
+        if t is None:
+            continue
+        _need(t, torch.float32, n, 2)
+        if t.size(1) != Cc or t.size(0) != named[0][1].size(0):
+            raise L.GnnmpError(f"bn: {n} is {tuple(t.shape)} for [groups, {Cc}]")
+
+
 def bn_fwd(x: Tensor, residual: Optional[Tensor], seg_ptr: Tensor, max_seg_rows: int, gamma: Tensor, beta: Tensor,
-           running_mean: Optional[Tensor], running_var: Optional[Tensor], cfg: L.BnConfig):
-    """Returns (y, save_mean, save_rstd); the saved stats are None in eval mode."""
+           running_mean: Optional[Tensor], running_var: Optional[Tensor], cfg: L.BnConfig, seg_group: Optional[Tensor] = None):
+    """Returns (y, save_mean, save_rstd); the saved stats are None in eval mode.  seg_group (int32 [S], device): the parameter group of
+    each segment; gamma, beta and the running pair are then [groups, C]."""
     _need(x, torch.float32, "x", 2)
     rows, Cc = x.shape
     if residual is not None:
@@ -389,10 +409,7 @@ def bn_fwd(x: Tensor, residual: Optional[Tensor], seg_ptr: Tensor, max_seg_rows:
             raise L.GnnmpError("bn: residual shape")
     _need(seg_ptr, torch.int32, "seg_ptr", 1)
     S = seg_ptr.numel() - 1
-    for t, n in ((gamma, "gamma"), (beta, "beta")):
-        _need(t, torch.float32, n, 1)
-        if t.numel() != Cc:
-            raise L.GnnmpError(f"bn: {n} length")
+    _bn_params(Cc, S, seg_group, (("gamma", gamma), ("beta", beta), ("running_mean", running_mean), ("running_var", running_var)))
     y = torch.empty_like(x)
     sm = sr = None
     if cfg.training:
@@ -400,7 +417,7 @@ def bn_fwd(x: Tensor, residual: Optional[Tensor], seg_ptr: Tensor, max_seg_rows:
         sr = torch.empty(S, Cc, dtype=torch.float32, device=x.device)
     l = L.lib()
     ws = _ws(l.gmp_bn_workspace_bytes(rows, Cc, S, max_seg_rows), x.device)
-    L.check(l.gmp_bn_fwd(_ptr(x), _ptr(residual), _ptr(seg_ptr), None, S, max_seg_rows, rows, Cc, _ptr(gamma), _ptr(beta),
+    L.check(l.gmp_bn_fwd(_ptr(x), _ptr(residual), _ptr(seg_ptr), _ptr(seg_group), S, max_seg_rows, rows, Cc, _ptr(gamma), _ptr(beta),
                          _ptr(running_mean), _ptr(running_var), _ptr(sm), _ptr(sr), _ptr(y), C.byref(cfg),
                          _ptr(ws), ws.numel(), _stream(x)), "gmp_bn_fwd")
     return y, sm, sr
@@ -481,11 +498,14 @@ def linear_affine(A: Tensor, W: Tensor, bias: Optional[Tensor], scale: Tensor, s
 
 
 def bn_bwd(g_y: Tensor, x: Tensor, residual: Optional[Tensor], seg_ptr: Tensor, max_seg_rows: int, gamma: Tensor,
-           beta: Tensor, running_mean, running_var, save_mean, save_rstd, cfg: L.BnConfig, group_seg_ptr=None):
-    """Returns (g_u, g_gamma [G,C], g_beta [G,C]); group_seg_ptr: python list of segment offsets (default one group)."""
+           beta: Tensor, running_mean, running_var, save_mean, save_rstd, cfg: L.BnConfig, group_seg_ptr=None, seg_group: Optional[Tensor] = None):
+    """Returns (g_u, g_gamma [G,C], g_beta [G,C]); group_seg_ptr: python list of segment offsets (default one group).
+    seg_group (int32 [S], device): the parameter group of each segment; gamma, beta and the running pair are then [groups, C]."""
     _need(g_y, torch.float32, "g_y", 2); _need(x, torch.float32, "x", 2)
     rows, Cc = x.shape
     S = seg_ptr.numel() - 1
+    if seg_group is not None:
+        _bn_params(Cc, S, seg_group, (("gamma", gamma), ("beta", beta), ("running_mean", running_mean), ("running_var", running_var)))
     grp = [0, S] if group_seg_ptr is None else list(group_seg_ptr)
     G = len(grp) - 1
     arr = (C.c_int32 * (G + 1))(*grp)
@@ -494,7 +514,7 @@ def bn_bwd(g_y: Tensor, x: Tensor, residual: Optional[Tensor], seg_ptr: Tensor, 
     gb = torch.empty(G, Cc, dtype=torch.float32, device=x.device)
     l = L.lib()
     ws = _ws(l.gmp_bn_workspace_bytes(rows, Cc, S, max_seg_rows), x.device)
-    L.check(l.gmp_bn_bwd(_ptr(g_y), _ptr(x), _ptr(residual), _ptr(seg_ptr), None, S, max_seg_rows, rows, Cc, _ptr(gamma),
+    L.check(l.gmp_bn_bwd(_ptr(g_y), _ptr(x), _ptr(residual), _ptr(seg_ptr), _ptr(seg_group), S, max_seg_rows, rows, Cc, _ptr(gamma),
                          _ptr(beta), _ptr(running_mean), _ptr(running_var), _ptr(save_mean), _ptr(save_rstd),
                          _ptr(g_u), _ptr(gg), _ptr(gb), C.cast(arr, C.c_void_p), None, None, G, C.byref(cfg), _ptr(ws), ws.numel(),
                          _stream(x)), "gmp_bn_bwd")
