@@ -198,7 +198,12 @@ _SIGS: Dict[str, tuple] = {
                                            f32, p, p, p, p, p, sz, i32, p]),
     "gmp_mt_pcgrad_clip_adamw_ex": (C.c_int, [p, i64, i32, i32, p, p, p, p, i32, i32, i32, p, p, p, p, p, p, f32, f32, f32,
                                               f32, p, p, p, p, p, sz, i32, i32, i32, i32, p, p]),
+    "gmp_mt_surgery_clip_adamw": (C.c_int, [i32, i32, p, p, i64, i32, i32, p, p, p, p, i32, i32, i32, p, p, p, p, p, p, f32, f32, f32,
+                                            f32, p, p, p, p, p, sz, i32, i32, i32, i32, p, p]),
 }
+
+SURGERY_RULES = {"reference": 0, "pcgrad": 1, "mean": 2}      # GMP_SURGERY_* of include/gnnmp.h
+SURGERY_SCOPES = {"tensor": 0, "model": 1}
 
 
 def _declare(l: C.CDLL) -> None:

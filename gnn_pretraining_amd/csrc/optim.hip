@@ -11,6 +11,8 @@
 //   norm     one block: total squared norm (fixed order)
 //   adamw    clip coefficient + decoupled weight decay + Adam, per-tensor lr / step count
 // Everything is deterministic (no atomics).
+// Other surgery rules (gmp_mt_surgery_clip_adamw: PCGrad as published, per tensor or over the whole shared vector; the plain mean) swap
+// the solve for solve_rule (+ fold_solve for the whole-vector scope); gram, combine, norm and adamw are shared.
 #include "gnnmp_internal.h"
 
 namespace {
@@ -287,6 +289,214 @@ __global__ __launch_bounds__(64) void solve_kernel(const MtArgs a) {
         }
 }
 
+// ---- surgery rules beside the reference's (gmp_mt_surgery_clip_adamw) ---------------------------------------------------------
+// The Gram pass does not depend on the rule; a rule is another small solve in Gram space and another "which tensors get a gradient":
+//   pcgrad  PCGrad as published (Yu et al. 2020, Alg. 1): EVERY holder i of a tensor starts from its own gradient and walks the other
+//           tasks in the order perm[i] (a host-drawn permutation per task), projecting the running vector off each conflicting g_j; the
+//           tensor gets the mean over its holders, so a tensor with one holder (every head, mask_token) gets that gradient as it is.
+//           scope tensor: one walk per tensor on its own Gram matrix; scope model: ONE walk on the sum of the Gram matrices of the
+//           tensors two or more tasks hold (the tasks' whole shared vectors), its mixing weights used by each of those tensors.
+//   mean    the plain mean over the holders, no projections.
+// Kept apart from MtArgs, so the launches of the reference rule carry the arguments they always did.
+struct RuleArgs {
+    int rule, scope;
+    int perm[MAXT][MAXT - 1];  // perm[i][s]: the s-th ORDER POSITION task i (position i) walks; a row is a permutation of the other positions
+    double* colsum;            // [MAXT] model scope: sum over the walking tasks i of alpha[i][b], by order position b
+    int* model_metrics;        // [2] model scope: conflicts, projections of the one walk
+};
+constexpr int RULE_REFERENCE = 0, RULE_PCGRAD = 1, RULE_MEAN = 2, SCOPE_TENSOR = 0, SCOPE_MODEL = 1;
+
+// The walks of all holders on one Gram matrix (order space, NT >= n_order positions, Gp zero where a position holds nothing):
+// wsum[b] = sum over holders i of alpha[i][b] with v_i = sum_b alpha[i][b] g_b.  The walked position j is a kernel argument, the
+// same for the whole wave: what it selects is picked by unrolled compares, so every array keeps static indices and stays in registers.
+template <int NT>
+__device__ __forceinline__ void pcgrad_walk(const double (&Gp)[NT][NT], const bool (&hp)[NT], const RuleArgs& r, int n_order,
+                                            double (&wsum)[NT], int& conf, int& proj) {
+#pragma unroll
+    for (int b = 0; b < NT; ++b) wsum[b] = 0.0;
+#pragma unroll
+    for (int i = 0; i < NT; ++i) {
+        if (!hp[i]) continue;
+        double al[NT];
+#pragma unroll
+        for (int b = 0; b < NT; ++b) al[b] = b == i ? 1.0 : 0.0;
+#pragma unroll
+        for (int s = 0; s < NT - 1; ++s) {
+            if (s < n_order - 1) {
+                const int j = r.perm[i][s];
+                double u[NT];                              // u[p] = <v, g_p>
+                double ni = 0.0;
+#pragma unroll
+                for (int p = 0; p < NT; ++p) {
+                    double t = 0.0;
+#pragma unroll
+                    for (int q = 0; q < NT; ++q) t += al[q] * Gp[q][p];
+                    u[p] = t;
+                    ni += al[p] * t;
+                }
+                double dot = 0.0, nj = 0.0;
+                bool hj = false;
+#pragma unroll
+                for (int c = 0; c < NT; ++c)
+                    if (c == j) { dot = u[c]; nj = Gp[c][c]; hj = hp[c]; }
+                if (hj && ni > 0.0 && nj > 0.0) {          // a zero norm on either side: the pair is skipped
+                    ++proj;
+                    if (dot < 0.0) {
+                        ++conf;
+                        const double f = dot / nj;         // project off task j's ORIGINAL gradient
+#pragma unroll
+                        for (int c = 0; c < NT; ++c)
+                            if (c == j) al[c] -= f;
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int b = 0; b < NT; ++b) wsum[b] += al[b];
+    }
+}
+
+// model scope: G^ = sum of the Gram matrices of the tensors two or more tasks of the order hold, ascending k, in double (one thread per
+// entry, no atomics), then the one walk on it over the tasks that hold any such tensor.  One block.
+template <int NT>
+__global__ __launch_bounds__(64) void fold_solve_kernel(const MtArgs a, const RuleArgs r) {
+    __shared__ unsigned s_mask[64];
+    __shared__ double s_G[MAXT][MAXT];
+    __shared__ int s_ps[MAXT];
+    const int tid = threadIdx.x, x = tid / MAXT, y = tid % MAXT;        // order positions
+    int ox = 0, oy = 0;
+#pragma unroll
+    for (int i = 0; i < MAXT; ++i) {
+        if (i == x) ox = a.order[i];
+        if (i == y) oy = a.order[i];
+    }
+    const bool live = x < a.n_order && y < a.n_order;
+    double s = 0.0;
+    int any = 0;
+    constexpr int U = 32;      // (a tile in two rounds of requests: the block is alone on its queue, so the rounds' latencies add up)
+    for (int k0 = 0; k0 < a.K; k0 += 64) {
+        const int k = k0 + tid;
+        unsigned m = 0;
+        if (k < a.K) {
+#pragma unroll
+            for (int i = 0; i < MAXT; ++i)
+                if (i < a.n_order && a.has[k * MAXT + a.order[i]]) m |= 1u << i;
+        }
+        s_mask[tid] = m;
+        __syncthreads();
+        if (live) {
+            for (int c0 = 0; c0 < 64; c0 += U) {           // U entries requested together, added in tensor order
+                double v[U];
+#pragma unroll
+                for (int c = 0; c < U; ++c) {
+                    const unsigned mk = s_mask[c0 + c];      // 0 beyond K
+                    const bool in = __popc(mk) >= 2 && ((mk >> x) & 1u) && ((mk >> y) & 1u);
+                    // read without a branch, so the round's requests go out together: an entry outside S holds whatever the buffer held
+                    // (the Gram pass never wrote it) and is dropped by the select; the tensor index is clamped into the buffer
+                    const double g = a.gram[((int64_t)min(k0 + c0 + c, a.K - 1) * MAXT + ox) * MAXT + oy];
+                    v[c] = in ? g : 0.0;
+                    any |= in;
+                }
+#pragma unroll
+                for (int c = 0; c < U; ++c) s += v[c];
+            }
+        }
+        __syncthreads();
+    }
+    s_G[x][y] = live ? s : 0.0;
+    if (x == y) s_ps[x] = live && any;
+    __syncthreads();
+    double Gp[NT][NT];
+    bool hp[NT];
+#pragma unroll
+    for (int i = 0; i < NT; ++i) {
+        hp[i] = s_ps[i] != 0;
+#pragma unroll
+        for (int j = 0; j < NT; ++j) Gp[i][j] = s_G[i][j];
+    }
+    double wsum[NT];
+    int conf = 0, proj = 0;
+    pcgrad_walk<NT>(Gp, hp, r, a.n_order, wsum, conf, proj);      // every lane the same walk; lane 0 writes it
+    if (tid == 0) {
+#pragma unroll
+        for (int b = 0; b < MAXT; ++b) r.colsum[b] = 0.0;
+#pragma unroll
+        for (int b = 0; b < NT; ++b) r.colsum[b] = wsum[b];
+        r.model_metrics[0] = conf;
+        r.model_metrics[1] = proj;
+    }
+}
+
+// solve_kernel's counterpart for the other rules: one thread per tensor -> mixing weights, flag, step count, conflict / projection counts
+template <int NT>
+__global__ __launch_bounds__(64) void solve_rule_kernel(const MtArgs a, const RuleArgs r) {
+    __shared__ int s_conf[64], s_proj[64];
+    int conf = 0, proj = 0;
+    const int k = a.k0 + blockIdx.x * 64 + threadIdx.x;
+    if (k < a.k1) {
+        const unsigned char* has = a.has + k * MAXT;
+        bool hp[NT];
+        int nh = 0;
+#pragma unroll
+        for (int i = 0; i < NT; ++i) {
+            hp[i] = i < a.n_order && has[a.order[i]];
+            nh += hp[i];
+        }
+        double wsum[NT];
+#pragma unroll
+        for (int i = 0; i < NT; ++i) wsum[i] = hp[i] ? 1.0 : 0.0;         // mean, and every tensor with one holder
+        if (r.rule == RULE_PCGRAD && nh > 1) {
+            if (r.scope == SCOPE_MODEL) {
+#pragma unroll
+                for (int i = 0; i < NT; ++i) wsum[i] = hp[i] ? r.colsum[i] : 0.0;
+            } else {
+                const double* G = a.gram + (int64_t)k * MAXT * MAXT;
+                double Gp[NT][NT];
+#pragma unroll
+                for (int i = 0; i < NT; ++i)
+#pragma unroll
+                    for (int j = 0; j < NT; ++j) Gp[i][j] = (hp[i] && hp[j]) ? G[a.order[i] * MAXT + a.order[j]] : 0.0;     // (read without the branch: 2 us slower)
+                pcgrad_walk<NT>(Gp, hp, r, a.n_order, wsum, conf, proj);
+            }
+        }
+        if (r.rule == RULE_PCGRAD && r.scope == SCOPE_MODEL && k == 0 && a.n_order > 1) {      // the one walk's counts, once
+            conf = r.model_metrics[0];
+            proj = r.model_metrics[1];
+        }
+        float* w = a.weights + k * MAXT;
+        for (int t = 0; t < MAXT; ++t) w[t] = 0.f;
+        int flag = nh > 0 ? 1 : 0;
+#pragma unroll
+        for (int i = 0; i < NT; ++i)
+            if (hp[i]) w[a.order[i]] = (float)(wsum[i] / nh);
+        if (a.extra_task >= 0 && has[a.extra_task]) {
+            w[a.extra_task] += 1.f;
+            flag = 1;
+        }
+        a.flags[k] = flag;
+        if (a.steps && !(a.abort && *a.abort)) a.steps[k] += (float)flag;
+    }
+    s_conf[threadIdx.x] = conf;
+    s_proj[threadIdx.x] = proj;
+    __syncthreads();
+    for (int d = 32; d > 0; d >>= 1) {
+        if (threadIdx.x < d) {
+            s_conf[threadIdx.x] += s_conf[threadIdx.x + d];
+            s_proj[threadIdx.x] += s_proj[threadIdx.x + d];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {                    // the slots of [k0, k1), as solve_kernel fills them
+        a.block_metrics[2 * (a.k0 + blockIdx.x)] = s_conf[0];
+        a.block_metrics[2 * (a.k0 + blockIdx.x) + 1] = s_proj[0];
+    }
+    if (blockIdx.x == 0)
+        for (int i = (int)gridDim.x + threadIdx.x; i < a.k1 - a.k0; i += 64) {
+            a.block_metrics[2 * (a.k0 + i)] = 0;
+            a.block_metrics[2 * (a.k0 + i) + 1] = 0;
+        }
+}
+
 // Every tensor starts on a 16-byte boundary of the flat buffers and is padded to a multiple of 4 floats (zeros in params, in the
 // gradients and in the optimizer state, and they stay zeros), so both sweeps below move float4.
 __global__ __launch_bounds__(TB) void combine_kernel(MtArgs a) {
@@ -452,18 +662,36 @@ __global__ __launch_bounds__(TB) void adamw_kernel(MtArgs a) {
 extern "C" size_t gmp_mt_workspace_bytes(int num_tensors) {
     const size_t K = num_tensors > 0 ? num_tensors : 0;
     return K * MAXT * MAXT * sizeof(double) * (1 + GCH) + K * MAXT * sizeof(float) + K * sizeof(int) + K * CH * sizeof(float) +
-           (K + 2) * 2 * sizeof(int) + 1024;
+           (K + 2) * 2 * sizeof(int) + MAXT * sizeof(double) + 1024;
 }
 
-extern "C" int gmp_mt_pcgrad_clip_adamw_ex(const float* task_grads, int64_t task_stride, int num_tasks, int num_tensors,
-                                           const int64_t* tensor_off, const int32_t* tensor_len, const uint8_t* has,
-                                           const int32_t* order_host, int n_order, int last_task, int extra_task,
-                                           float* params, float* exp_avg, float* exp_avg_sq, float* steps,
-                                           const float* lr, const float* wd, float beta1, float beta2, float eps,
-                                           float max_norm, float* final_grad, float* normsq_out, int32_t* metrics_out,
-                                           int32_t* flags_out, void* ws, size_t ws_bytes, int apply_update,
-                                           int k_begin, int k_end, int phases, const int32_t* abort_flag, gmp_stream_t stream) {
-    if (k_begin < 0 || k_end > num_tensors || k_begin > k_end || !(phases & 7))
+namespace {
+
+template <int NT>
+void launch_rule_solve(const MtArgs& a, const RuleArgs& r, bool fold, hipStream_t st) {
+    if (fold) hipLaunchKernelGGL(fold_solve_kernel<NT>, dim3(1), dim3(64), 0, st, a, r);
+    else hipLaunchKernelGGL(solve_rule_kernel<NT>, dim3((a.k1 - a.k0 + 63) / 64), dim3(64), 0, st, a, r);
+}
+void rule_solve(const MtArgs& a, const RuleArgs& r, bool fold, hipStream_t st) {
+    switch (a.n_order) {                  // the walks are unrolled over the tasks of the order
+        case 1: case 2: launch_rule_solve<2>(a, r, fold, st); break;
+        case 3: launch_rule_solve<3>(a, r, fold, st); break;
+        case 4: launch_rule_solve<4>(a, r, fold, st); break;
+        case 5: launch_rule_solve<5>(a, r, fold, st); break;
+        case 6: launch_rule_solve<6>(a, r, fold, st); break;
+        default: launch_rule_solve<MAXT>(a, r, fold, st); break;
+    }
+}
+
+int mt_run(int rule, int scope, const int32_t* perm_host, const float* task_grads, int64_t task_stride, int num_tasks, int num_tensors,
+           const int64_t* tensor_off, const int32_t* tensor_len, const uint8_t* has,
+           const int32_t* order_host, int n_order, int last_task, int extra_task,
+           float* params, float* exp_avg, float* exp_avg_sq, float* steps,
+           const float* lr, const float* wd, float beta1, float beta2, float eps,
+           float max_norm, float* final_grad, float* normsq_out, int32_t* metrics_out,
+           int32_t* flags_out, void* ws, size_t ws_bytes, int apply_update,
+           int k_begin, int k_end, int phases, const int32_t* abort_flag, gmp_stream_t stream) {
+    if (k_begin < 0 || k_end > num_tensors || k_begin > k_end || (rule == RULE_REFERENCE && !(phases & 7)))      // (the other rules' phases: checked by the caller)
         return gmp::fail(GMP_ERR_ARG, "mt_pcgrad: tensors [%d, %d) of %d, phases %d", k_begin, k_end, num_tensors, phases);
     if (num_tasks < 1 || num_tasks > MAXT || num_tensors < 1 || n_order < 1 || n_order > num_tasks)
         return gmp::fail(GMP_ERR_ARG, "mt_pcgrad: tasks=%d tensors=%d n_order=%d", num_tasks, num_tensors, n_order);
@@ -481,11 +709,27 @@ extern "C" int gmp_mt_pcgrad_clip_adamw_ex(const float* task_grads, int64_t task
     a.gram_part = (double*)w; w += (size_t)num_tensors * GCH * MAXT * MAXT * sizeof(double);
     a.weights = (float*)w; w += (size_t)num_tensors * MAXT * sizeof(float);
     a.partial = (float*)w; w += (size_t)num_tensors * CH * sizeof(float);
-    a.block_metrics = (int*)w;
+    a.block_metrics = (int*)w; w += (size_t)num_tensors * 2 * sizeof(int);          // (a multiple of 8 bytes from the start, as all the above)
+    RuleArgs r{};
+    r.rule = rule; r.scope = rule == RULE_PCGRAD ? scope : SCOPE_TENSOR;             // the scope belongs to pcgrad alone
+    r.colsum = (double*)w; w += MAXT * sizeof(double);
+    r.model_metrics = (int*)w;
     a.flags = flags_out; a.steps = steps; a.metrics = metrics_out;
     for (int i = 0; i < n_order; ++i) {
         if (order_host[i] < 0 || order_host[i] >= num_tasks) return gmp::fail(GMP_ERR_ARG, "mt_pcgrad: order[%d]=%d", i, order_host[i]);
         a.order[i] = order_host[i];
+    }
+    if (rule == RULE_PCGRAD && n_order > 1) {
+        if (!perm_host) return gmp::fail(GMP_ERR_ARG, "mt_surgery: pcgrad needs the permutation table");
+        for (int i = 0; i < n_order; ++i) {          // row i: every other order position exactly once
+            unsigned seen = 1u << i;
+            for (int s = 0; s < n_order - 1; ++s) {
+                const int j = perm_host[i * (n_order - 1) + s];
+                if (j < 0 || j >= n_order || (seen >> j & 1u)) return gmp::fail(GMP_ERR_ARG, "mt_surgery: perm[%d][%d]=%d", i, s, j);
+                seen |= 1u << j;
+                r.perm[i][s] = j;
+            }
+        }
     }
     a.n_order = n_order; a.last_task = last_task; a.extra_task = extra_task;
     a.final_grad = final_grad; a.normsq = normsq_out; a.params = params; a.exp_avg = exp_avg; a.exp_avg_sq = exp_avg_sq;
@@ -496,19 +740,34 @@ extern "C" int gmp_mt_pcgrad_clip_adamw_ex(const float* task_grads, int64_t task
     // upper bound of the chunk count of n tensors inside a buffer of task_stride floats: every tensor has at least one chunk, and at most one
     // more than its float4 / MINP4 (the kernels find their chunk themselves and the surplus workgroups leave at once)
     auto nblk = [&](int n) { return (unsigned)(task_stride / (4 * MINP4) + 2 * (int64_t)n + 1); };
-    if ((phases & 1) && nk > 0) {
-        if (n_order > 1) {
-            switch (num_tasks) {          // (tasks beyond a.T never own a tensor: the generic form covers any count)
-                case 2: hipLaunchKernelGGL(gram_kernel<2>, dim3(nblk(nk)), dim3(TB), 0, st, a); break;
-                case 3: hipLaunchKernelGGL(gram_kernel<3>, dim3(nblk(nk)), dim3(TB), 0, st, a); break;
-                case 4: hipLaunchKernelGGL(gram_kernel<4>, dim3(nblk(nk)), dim3(TB), 0, st, a); break;
-                case 5: hipLaunchKernelGGL(gram_kernel<5>, dim3(nblk(nk)), dim3(TB), 0, st, a); break;
-                case 6: hipLaunchKernelGGL(gram_kernel<6>, dim3(nblk(nk)), dim3(TB), 0, st, a); break;
-                default: hipLaunchKernelGGL(gram_kernel<MAXT>, dim3(nblk(nk)), dim3(TB), 0, st, a); break;
-            }
-            hipLaunchKernelGGL(gram_finish_kernel, dim3(nk), dim3(64), 0, st, a);
+    auto gram = [&]() {
+        switch (num_tasks) {          // (tasks beyond a.T never own a tensor: the generic form covers any count)
+            case 2: hipLaunchKernelGGL(gram_kernel<2>, dim3(nblk(nk)), dim3(TB), 0, st, a); break;
+            case 3: hipLaunchKernelGGL(gram_kernel<3>, dim3(nblk(nk)), dim3(TB), 0, st, a); break;
+            case 4: hipLaunchKernelGGL(gram_kernel<4>, dim3(nblk(nk)), dim3(TB), 0, st, a); break;
+            case 5: hipLaunchKernelGGL(gram_kernel<5>, dim3(nblk(nk)), dim3(TB), 0, st, a); break;
+            case 6: hipLaunchKernelGGL(gram_kernel<6>, dim3(nblk(nk)), dim3(TB), 0, st, a); break;
+            default: hipLaunchKernelGGL(gram_kernel<MAXT>, dim3(nblk(nk)), dim3(TB), 0, st, a); break;
         }
-        hipLaunchKernelGGL(solve_kernel, dim3((nk + 63) / 64), dim3(64), 0, st, a);
+        hipLaunchKernelGGL(gram_finish_kernel, dim3(nk), dim3(64), 0, st, a);
+    };
+    const bool walks = rule == RULE_PCGRAD && n_order > 1;          // the only rule beside the reference's that reads a Gram matrix
+    if (r.scope == SCOPE_MODEL) {
+        if ((phases & 8) && nk > 0 && walks) gram();
+        if (phases & 16) {
+            a.k0 = 0; a.k1 = num_tensors;
+            if (walks) rule_solve(a, r, true, st);
+            rule_solve(a, r, false, st);
+            hipLaunchKernelGGL(combine_kernel, dim3(nblk(num_tensors)), dim3(TB), 0, st, a);
+        }
+    } else if ((phases & 1) && nk > 0) {
+        if (rule == RULE_REFERENCE) {
+            if (n_order > 1) gram();
+            hipLaunchKernelGGL(solve_kernel, dim3((nk + 63) / 64), dim3(64), 0, st, a);
+        } else {
+            if (walks) gram();
+            rule_solve(a, r, false, st);
+        }
         hipLaunchKernelGGL(combine_kernel, dim3(nblk(nk)), dim3(TB), 0, st, a);
     }
     if ((phases & 4) && nk > 0) hipLaunchKernelGGL(foreign_kernel, dim3(nblk(nk)), dim3(TB), 0, st, a);
@@ -517,6 +776,43 @@ extern "C" int gmp_mt_pcgrad_clip_adamw_ex(const float* task_grads, int64_t task
         if (apply_update) hipLaunchKernelGGL(adamw_kernel, dim3(nblk(num_tensors)), dim3(TB), 0, st, a);
     }
     return gmp::check_launch("mt_pcgrad_clip_adamw kernels");
+}
+
+}  // namespace
+
+extern "C" int gmp_mt_pcgrad_clip_adamw_ex(const float* task_grads, int64_t task_stride, int num_tasks, int num_tensors,
+                                           const int64_t* tensor_off, const int32_t* tensor_len, const uint8_t* has,
+                                           const int32_t* order_host, int n_order, int last_task, int extra_task,
+                                           float* params, float* exp_avg, float* exp_avg_sq, float* steps,
+                                           const float* lr, const float* wd, float beta1, float beta2, float eps,
+                                           float max_norm, float* final_grad, float* normsq_out, int32_t* metrics_out,
+                                           int32_t* flags_out, void* ws, size_t ws_bytes, int apply_update,
+                                           int k_begin, int k_end, int phases, const int32_t* abort_flag, gmp_stream_t stream) {
+    return mt_run(RULE_REFERENCE, SCOPE_TENSOR, nullptr, task_grads, task_stride, num_tasks, num_tensors, tensor_off, tensor_len, has, order_host,
+                  n_order, last_task, extra_task, params, exp_avg, exp_avg_sq, steps, lr, wd, beta1, beta2, eps, max_norm, final_grad,
+                  normsq_out, metrics_out, flags_out, ws, ws_bytes, apply_update, k_begin, k_end, phases, abort_flag, stream);
+}
+
+extern "C" int gmp_mt_surgery_clip_adamw(int rule, int scope, const int32_t* perm_host,
+                                         const float* task_grads, int64_t task_stride, int num_tasks, int num_tensors,
+                                         const int64_t* tensor_off, const int32_t* tensor_len, const uint8_t* has,
+                                         const int32_t* order_host, int n_order, int last_task, int extra_task,
+                                         float* params, float* exp_avg, float* exp_avg_sq, float* steps,
+                                         const float* lr, const float* wd, float beta1, float beta2, float eps,
+                                         float max_norm, float* final_grad, float* normsq_out, int32_t* metrics_out,
+                                         int32_t* flags_out, void* ws, size_t ws_bytes, int apply_update,
+                                         int k_begin, int k_end, int phases, const int32_t* abort_flag, gmp_stream_t stream) {
+    if (rule != RULE_REFERENCE && rule != RULE_PCGRAD && rule != RULE_MEAN) return gmp::fail(GMP_ERR_ARG, "mt_surgery: rule %d", rule);
+    if (scope != SCOPE_TENSOR && scope != SCOPE_MODEL) return gmp::fail(GMP_ERR_ARG, "mt_surgery: scope %d", scope);
+    if (rule != RULE_REFERENCE) {
+        const bool model = rule == RULE_PCGRAD && scope == SCOPE_MODEL;
+        const int allowed = model ? (8 | 16 | 2) : 3;         // the foreign pass (4) encodes the reference's emission rule
+        if (!phases || (phases & ~allowed))
+            return gmp::fail(GMP_ERR_ARG, "mt_surgery: phases %d with rule %d, scope %d (allowed bits %d)", phases, rule, scope, allowed);
+    }
+    return mt_run(rule, scope, perm_host, task_grads, task_stride, num_tasks, num_tensors, tensor_off, tensor_len, has, order_host,
+                  n_order, last_task, extra_task, params, exp_avg, exp_avg_sq, steps, lr, wd, beta1, beta2, eps, max_norm, final_grad,
+                  normsq_out, metrics_out, flags_out, ws, ws_bytes, apply_update, k_begin, k_end, phases, abort_flag, stream);
 }
 
 extern "C" int gmp_mt_pcgrad_clip_adamw(const float* task_grads, int64_t task_stride, int num_tasks, int num_tensors,

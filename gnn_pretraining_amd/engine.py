@@ -108,7 +108,8 @@ class StepEngine(StepHost):
     def __init__(self, model: PretrainableGNN, tasks: Sequence[str], domains: Sequence[str], device,
                  max_rows: int = 16384, max_edges: int = 131072, seed: int = 0, shuffle_rng: Optional[random.Random] = None,
                  grad_sync=None, rng_mode: str = "reference", native: bool = True, neg_rng: Optional[random.Random] = None,
-                 dp_mode: Optional[str] = None, device_negatives: bool = False) -> None:
+                 dp_mode: Optional[str] = None, device_negatives: bool = False, surgery: str = "reference",
+                 surgery_scope: str = "tensor") -> None:
         super().__init__(tasks, domains, seed=seed, rng_mode=rng_mode, neg_rng=neg_rng, max_rows=max_rows, max_edges=max_edges)
         self.native = native       # True: csrc/step.hip enqueues the step; False: the same launches one by one from Python
         # data-parallel exchange: "allreduce" (every rank all-reduces all per-task gradients and runs the whole PCGrad: dist.OverlappedGradSync)
@@ -117,6 +118,17 @@ class StepEngine(StepHost):
         self.dp_mode = dp_mode or os.environ.get("GMP_DP_MODE", "allreduce")
         if self.dp_mode not in ("allreduce", "sharded"):
             raise ValueError("dp_mode must be 'allreduce' or 'sharded'")
+        # gradient-surgery rule (include/gnnmp.h gmp_mt_surgery_clip_adamw): "reference" = the reference's PCGrad, quirk included (only
+        # tensors of the first-shuffled task get the PCGrad mean, the last task keeps its raw gradient, the other heads get none);
+        # "pcgrad" = PCGrad as published, per tensor or over the whole shared vector ("model"); "mean" = the plain mean (scope unused)
+        if surgery not in L.SURGERY_RULES or surgery_scope not in L.SURGERY_SCOPES:
+            raise ValueError(f"surgery must be one of {sorted(L.SURGERY_RULES)}, surgery_scope one of {sorted(L.SURGERY_SCOPES)}")
+        if surgery == "reference" and surgery_scope != "tensor":
+            raise ValueError("the reference rule is per tensor: surgery_scope='model' needs surgery='pcgrad'")
+        if surgery != "reference" and self.dp_mode == "sharded":
+            raise ValueError("dp_mode='sharded' needs surgery='reference': its foreign pass encodes the reference's emission rule")
+        self.surgery, self.surgery_scope = surgery, surgery_scope
+        self.last_order, self.last_perm = None, None
         self._shard_sync_obj = None
         # link-prediction negatives drawn on the device too (csrc/augment.hip gmp_aug_negative_edges), riding the draw ticket: opt-in
         if device_negatives and rng_mode != "device":
@@ -676,23 +688,41 @@ class StepEngine(StepHost):
         names = list(self.tasks)
         main_tasks = [t for t in names if t != "domain_adv"]     # pretrain.py:137-150: PCGrad over the main tasks, then
         extra = names.index("domain_adv") if "domain_adv" in names else -1   # domain_adv_loss.backward() accumulates on top
-        if order is None:
+        rule, model_scope = L.SURGERY_RULES[self.surgery], self.surgery == "pcgrad" and self.surgery_scope == "model"
+        perm = None
+        if self.surgery == "reference":
+            if order is None:
+                order = list(main_tasks)
+                if len(order) > 1:
+                    (self.shuffle_rng or random).shuffle(order)       # reference: unseeded random.shuffle (gradient_surgery.py:43)
+        else:
+            # the other rules have no first-shuffled task: the order is the dict order (whatever `order` says), and PCGrad as published
+            # draws, for each task in turn, the order in which it meets the others -- positions of `order`
             order = list(main_tasks)
-            if len(order) > 1:
-                (self.shuffle_rng or random).shuffle(order)       # reference: unseeded random.shuffle (gradient_surgery.py:43)
+            if self.surgery == "pcgrad":
+                perm = []
+                for i in range(len(order)):
+                    row = [j for j in range(len(order)) if j != i]
+                    (self.shuffle_rng or random).shuffle(row)
+                    perm.append(row)
         idx = [names.index(t) for t in order]
-        self.last_order = order
+        self.last_order, self.last_perm = order, perm
         oidx = _i32(idx)
+        pidx = _i32([j for row in perm for j in row]) if perm and len(order) > 1 else None
+        gram_only, all_tensors = (8, 16) if model_scope else (1, 0)     # model scope: Gram per part, one fold + solve + combine at the end
 
         def pcgrad(k0: int, k1: int, phases: int, stream: int) -> None:
-            self._chk(self.lib.gmp_mt_pcgrad_clip_adamw_ex(
-                self.task_grads.data_ptr(), self.P, self.T, self.K, self.t_off.data_ptr(), self.t_len.data_ptr(), self.has.data_ptr(),
-                oidx, len(idx), names.index(main_tasks[-1]), extra, self.flat.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
-                self.steps.data_ptr() if apply_update else None, self.lr.data_ptr(), self.wd.data_ptr(), 0.9, 0.999, 1e-8, self.max_grad_norm,
-                self.final_grad.data_ptr(), self.normsq.data_ptr(), self.metrics.data_ptr(), self.flags.data_ptr(), self.mt_ws.data_ptr(),
-                self.mt_ws.numel(), int(apply_update), k0, k1, phases,
-                (self.sync_flags.data_ptr() + 4 * 63) if self.use_gates else None,      # a timed-out gate: no update from this step on
-                stream), "mt_pcgrad_clip_adamw")
+            args = (self.task_grads.data_ptr(), self.P, self.T, self.K, self.t_off.data_ptr(), self.t_len.data_ptr(), self.has.data_ptr(),
+                    oidx, len(idx), names.index(main_tasks[-1]), extra, self.flat.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
+                    self.steps.data_ptr() if apply_update else None, self.lr.data_ptr(), self.wd.data_ptr(), 0.9, 0.999, 1e-8, self.max_grad_norm,
+                    self.final_grad.data_ptr(), self.normsq.data_ptr(), self.metrics.data_ptr(), self.flags.data_ptr(), self.mt_ws.data_ptr(),
+                    self.mt_ws.numel(), int(apply_update), k0, k1, phases,
+                    (self.sync_flags.data_ptr() + 4 * 63) if self.use_gates else None,      # a timed-out gate: no update from this step on
+                    stream)
+            if rule == 0:
+                self._chk(self.lib.gmp_mt_pcgrad_clip_adamw_ex(*args), "mt_pcgrad_clip_adamw")
+            else:
+                self._chk(self.lib.gmp_mt_surgery_clip_adamw(rule, L.SURGERY_SCOPES[self.surgery_scope], pidx, *args), "mt_surgery_clip_adamw")
 
         if self.grad_sync is not None and self.dp_mode == "sharded" and self.native:
             from . import dist as D
@@ -710,12 +740,12 @@ class StepEngine(StepHost):
             k_of = self._part_tensors
             sync.average_(self.lib, torch.cuda.current_stream(self.device), gate=(self.sync_flags.data_ptr(), self._epoch),
                           exchange=self.grad_sync is not None,
-                          after_message=lambda parts, st: [pcgrad(a, b, 1, st) for a, b in _merge_runs([k_of[q] for q in parts])])
-            pcgrad(0, self.K, 2, main_h)
+                          after_message=lambda parts, st: [pcgrad(a, b, gram_only, st) for a, b in _merge_runs([k_of[q] for q in parts])])
+            pcgrad(0, self.K, all_tensors | 2, main_h)
             return
         if self.grad_sync is not None:
             self._sync_task_grads()
-        pcgrad(0, self.K, 3, main_h)
+        pcgrad(0, self.K, gram_only | all_tensors | 2, main_h)
 
     def _head_slices(self):
         out = []

@@ -95,15 +95,31 @@ class GradientSurgery:
     (gradient_surgery.py:61): only tensors present in the FIRST shuffled task's gradient set
     receive the PCGrad mean; the others keep whatever the LAST task's backward left in .grad."""
 
-    def __init__(self, device: torch.device, grad_sync=None, shuffle_rng: Optional[random.Random] = None) -> None:
+    RULES, SCOPES = ("reference", "pcgrad", "mean"), ("tensor", "model")
+
+    def __init__(self, device: torch.device, grad_sync=None, shuffle_rng: Optional[random.Random] = None,
+                 rule: str = "reference", scope: str = "tensor") -> None:
+        """rule "reference": the class docstring's.  "pcgrad": PCGrad as published (Yu et al. 2020, Alg. 1) -- every holder of a tensor
+        walks the other tasks in an order of its own (`perm`), the tensor gets the mean over its holders, so every parameter some task
+        reaches is trained in every step; scope "tensor" projects tensor by tensor, "model" once over the whole shared vector (the
+        tensors two or more tasks hold).  "mean": the plain mean over the holders (scope unused).  The same rules as the engine's
+        (include/gnnmp.h gmp_mt_surgery_clip_adamw)."""
+        if rule not in self.RULES or scope not in self.SCOPES:
+            raise ValueError(f"rule must be one of {self.RULES}, scope one of {self.SCOPES}")
+        if rule == "reference" and scope != "tensor":
+            raise ValueError("the reference rule is per tensor: scope='model' needs rule='pcgrad'")
         self.device = device
         self.grad_sync = grad_sync          # dist.FlatGradSync: per-task gradients are averaged over ranks BEFORE PCGrad
         self.shuffle_rng = shuffle_rng      # data-parallel runs need the same task order on every rank
+        self.rule, self.scope = rule, scope
+        self.last_perm: Optional[List[List[int]]] = None
 
     def apply_gradient_surgery(self, model: nn.Module, task_losses: Dict[str, Tensor], task_names: List[str],
-                               order: Optional[List[str]] = None) -> Dict[str, float]:
+                               order: Optional[List[str]] = None, perm: Optional[List[List[int]]] = None) -> Dict[str, float]:
         if len(task_losses) <= 1:
             return {}
+        if self.rule != "reference":
+            return self._apply_rule(model, task_losses, perm)
         named = list(model.named_parameters())
         grads: Dict[str, Dict[str, Tensor]] = {}
         for t, loss in task_losses.items():
@@ -179,6 +195,91 @@ class GradientSurgery:
                     term = grads[tasks[b]][n] * w[b]
                     acc = term if acc is None else acc.add_(term)
             final[n] = acc if acc is not None else torch.zeros_like(grads[first][n])
+        metrics = {"gradient_surgery/total_conflicts": conflicts, "gradient_surgery/total_projections": projections,
+                   "gradient_surgery/conflict_ratio": conflicts / max(projections, 1)}
+        return final, metrics
+
+    # ---- the rules beside the reference's ------------------------------------------------------------
+    def draw_perm(self, n: int) -> List[List[int]]:
+        """For each task in turn, one shuffle of the other tasks' positions (the engine's _optimizer draws the same way)."""
+        perm = []
+        for i in range(n):
+            row = [j for j in range(n) if j != i]
+            (self.shuffle_rng or random).shuffle(row)
+            perm.append(row)
+        return perm
+
+    def _apply_rule(self, model: nn.Module, task_losses: Dict[str, Tensor], perm: Optional[List[List[int]]]) -> Dict[str, float]:
+        named = list(model.named_parameters())
+        tasks = list(task_losses)                       # no first-shuffled task here: positions are the dict order
+        grads: Dict[str, Dict[str, Tensor]] = {}
+        for t, loss in task_losses.items():
+            model.zero_grad(set_to_none=True)
+            loss.backward(retain_graph=True)
+            grads[t] = {n: p.grad for n, p in named if p.grad is not None}
+        if self.grad_sync is not None:
+            self.grad_sync.average_task_grads_(grads)
+        if self.rule == "pcgrad":
+            if perm is None:
+                perm = self.draw_perm(len(tasks))
+            for i, row in enumerate(perm):
+                if sorted(row) != [j for j in range(len(tasks)) if j != i]:
+                    raise ValueError(f"perm[{i}] = {row} is no permutation of the other tasks' positions")
+        else:
+            perm = None
+        self.last_perm = perm
+        final, metrics = self._combine_rule(grads, tasks, perm)
+        for n, p in named:
+            if n in final:
+                p.grad = final[n]
+        return metrics
+
+    def _combine_rule(self, grads, tasks: List[str], perm):
+        T = len(tasks)
+        names = sorted({n for t in tasks for n in grads[t]})
+        holders = {n: [i for i, t in enumerate(tasks) if n in grads[t]] for n in names}
+        count = {"conflicts": 0, "projections": 0}
+
+        def walk(G: List[List[float]], held: List[int]) -> List[float]:
+            """every holder's walk on one Gram matrix -> sum over the holders i of alpha[i][b] (v_i = sum_b alpha[i][b] g_b)"""
+            col = [0.0] * T
+            for i in held:
+                a = [1.0 if b == i else 0.0 for b in range(T)]
+                for j in perm[i]:
+                    if j not in held:
+                        continue
+                    u = [sum(a[q] * G[q][p] for q in range(T)) for p in range(T)]        # <v, g_p>
+                    norm_i_sq, norm_j_sq = sum(a[p] * u[p] for p in range(T)), G[j][j]
+                    if norm_i_sq <= 0.0 or norm_j_sq <= 0.0:
+                        continue
+                    count["projections"] += 1
+                    if u[j] < 0:
+                        count["conflicts"] += 1
+                        a[j] -= u[j] / norm_j_sq
+                col = [c + x for c, x in zip(col, a)]
+            return col
+
+        weight: Dict[str, List[float]] = {n: [1.0 if b in holders[n] else 0.0 for b in range(T)] for n in names}    # the plain sum
+        shared = [n for n in names if len(holders[n]) >= 2]
+        if self.rule == "pcgrad" and shared:
+            gram = self._gram(grads, tasks, shared)
+            if self.scope == "model":
+                col = walk(gram.sum(0).tolist(), sorted({i for n in shared for i in holders[n]}))
+                for n in shared:
+                    weight[n] = [col[b] if b in holders[n] else 0.0 for b in range(T)]
+            else:
+                for k, n in enumerate(shared):
+                    weight[n] = walk(gram[k].tolist(), holders[n])
+        final = {}
+        for n in names:
+            acc = None
+            for b in holders[n]:
+                w = weight[n][b] / len(holders[n])
+                if w != 0.0:
+                    term = grads[tasks[b]][n] * w
+                    acc = term if acc is None else acc.add_(term)
+            final[n] = acc if acc is not None else torch.zeros_like(grads[tasks[holders[n][0]]][n])
+        conflicts, projections = count["conflicts"], count["projections"]
         metrics = {"gradient_surgery/total_conflicts": conflicts, "gradient_surgery/total_projections": projections,
                    "gradient_surgery/conflict_ratio": conflicts / max(projections, 1)}
         return final, metrics

@@ -4,7 +4,7 @@ datasets in data/processed; synthetic stand-ins are generated when none were exp
 of the reference need the network).  wandb is replaced by a JSONL logger with the same metric keys.
 
 Build-only flags (the reference's flags are unchanged): --epochs, --steps-per-epoch, --log, --device, --data-root,
---data-scale, --rng, --device-negatives, --module-path.
+--data-scale, --rng, --device-negatives, --module-path, --surgery, --surgery-scope.
 """
 from __future__ import annotations
 
@@ -58,13 +58,13 @@ class StepState:
     """Everything one optimisation step touches besides the model."""
 
     def __init__(self, model: PretrainableGNN, cfg: PretrainConfig, steps_per_epoch: int, epochs: int = EPOCHS,
-                 grad_sync=None, shuffle_rng=None) -> None:
+                 grad_sync=None, shuffle_rng=None, surgery: str = "reference", surgery_scope: str = "tensor") -> None:
         self.model, self.cfg, self.grad_sync = model, cfg, grad_sync
         self.grl = GRLScheduler(total_epochs=epochs, steps_per_epoch=steps_per_epoch)
         self.temperature = TemperatureScheduler(total_steps=steps_per_epoch * epochs)
         self.tasks: Dict[str, BasePretrainTask] = instantiate_tasks(model, cfg.active_tasks, self.grl, self.temperature)
         self.optimizer = TaskSpecificOptimizer(model=model, active_tasks=cfg.active_tasks)
-        self.surgery = GradientSurgery(device=model.device, grad_sync=grad_sync, shuffle_rng=shuffle_rng)
+        self.surgery = GradientSurgery(device=model.device, grad_sync=grad_sync, shuffle_rng=shuffle_rng, rule=surgery, scope=surgery_scope)
         self.balancer = AdaptiveLossBalancer()
 
 
@@ -232,10 +232,12 @@ def run_evaluation_engine(state: StepState, engine, val_loaders, generator: torc
 
 def pretrain(cfg: PretrainConfig, epochs: int = EPOCHS, steps_per_epoch: Optional[int] = None, log_path: Optional[str] = None,
              device: Optional[str] = None, data_root: Optional[str] = None, data_scale: float = 1.0,
-             rng_mode: str = "reference", use_engine: bool = True, device_negatives: bool = False) -> Path:
+             rng_mode: str = "reference", use_engine: bool = True, device_negatives: bool = False,
+             surgery: str = "reference", surgery_scope: str = "tensor") -> Path:
     """pretrain.py:284-349.  `steps_per_epoch` truncates an epoch (the loader's own length -- 462 for the four-domain
     schemes on the real data -- is the default); data come from data/processed (synthetic stand-ins are generated on
-    first use when no exported real data is there)."""
+    first use when no exported real data is there).  `surgery` / `surgery_scope`: the gradient-surgery rule of both paths (control.GradientSurgery,
+    StepEngine); the default is the reference's.  Its metric keys (gradient_surgery/*) are the same under every rule."""
     from ..data.data_setup import ensure_processed
     from ..data.pretrain_data_loaders import create_train_data_loader, create_val_data_loader
     from .._host import limit_host_threads
@@ -255,14 +257,15 @@ def pretrain(cfg: PretrainConfig, epochs: int = EPOCHS, steps_per_epoch: Optiona
     train_loader = create_train_data_loader(cfg.pretrain_domains, generator, root)
     steps = min(len(train_loader), steps_per_epoch) if steps_per_epoch else len(train_loader)
     model = PretrainableGNN(device=dev, domain_names=cfg.pretrain_domains, task_names=cfg.active_tasks)
-    state = StepState(model, cfg, steps, epochs)
+    state = StepState(model, cfg, steps, epochs, surgery=surgery, surgery_scope=surgery_scope)
+    print(f"gradient surgery: rule {surgery}, scope {surgery_scope if surgery == 'pcgrad' else 'tensor'}")
     logger = JsonlLogger(log_path)
     engine = None
     from ..engine import SUPPORTED_TASKS, StepEngine
     if use_engine and all(t in SUPPORTED_TASKS for t in cfg.active_tasks):
         engine = StepEngine(model, cfg.active_tasks, cfg.pretrain_domains, dev, seed=cfg.seed, rng_mode=rng_mode,
                             max_rows=65536, max_edges=524288,      # 8 PROTEINS-sized graphs (<= 620 nodes) x 7 passes fit
-                            device_negatives=device_negatives)
+                            device_negatives=device_negatives, surgery=surgery, surgery_scope=surgery_scope)
     best, stale, global_step = float("inf"), 0, [0]
     path = OUTPUT_DIR / f"model_{cfg.exp_name}_{cfg.seed}.pt"
     for epoch in range(1, epochs + 1):
@@ -311,7 +314,14 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--device-negatives", action="store_true",
                    help="with --rng device: draw the link-prediction negatives on the GPU too (opt-in)")
     p.add_argument("--module-path", action="store_true", help="run the per-task nn.Module path instead of the stacked engine")
+    p.add_argument("--surgery", choices=["reference", "pcgrad", "mean"], default="reference",
+                   help="gradient-surgery rule: reference = the reference's PCGrad, quirk included (most heads get no gradient in most steps); "
+                        "pcgrad = PCGrad as published (every head trained in every step); mean = the plain mean over the tasks")
+    p.add_argument("--surgery-scope", choices=["tensor", "model"], default="tensor",
+                   help="with --surgery pcgrad: project tensor by tensor, or once over the whole shared parameter vector")
     a = p.parse_args(argv)
+    if a.surgery_scope == "model" and a.surgery == "reference":
+        p.error("--surgery-scope model needs --surgery pcgrad")
     if a.device_negatives and a.rng != "device":
         p.error("--device-negatives needs --rng device")
     return a
@@ -320,7 +330,7 @@ def parse_args(argv=None) -> argparse.Namespace:
 def main() -> None:
     a = parse_args()
     path = pretrain(PretrainConfig(exp_name=a.exp_name, seed=a.seed), a.epochs, a.steps_per_epoch, a.log, a.device,
-                    a.data_root, a.data_scale, a.rng, not a.module_path, a.device_negatives)
+                    a.data_root, a.data_scale, a.rng, not a.module_path, a.device_negatives, a.surgery, a.surgery_scope)
     print(f"saved {path}")
 
 

@@ -740,6 +740,45 @@ int gmp_mt_pcgrad_clip_adamw_ex(const float* task_grads, int64_t task_stride, in
  * engine passes the error word of its cross-stream gates (sync_flags[63]), so a gate that timed out cannot turn into an update
  * computed from incomplete gradients; the host sees the flag at its next check_gates(). */
 
+/* The same tail under another gradient-surgery RULE.  The Gram pass, combine, norm, clip and AdamW are the ones above; a rule is another
+ * small solve in Gram space and another answer to "which tensors get a gradient".  P = the tasks of order_host, H_k = those of P that
+ * hold tensor k.
+ *   GMP_SURGERY_REFERENCE  the reference's rule, bit for bit gmp_mt_pcgrad_clip_adamw_ex (scope and perm_host are not read; the only
+ *                          rule that reads last_task).
+ *   GMP_SURGERY_PCGRAD     PCGrad as published (Yu et al. 2020, Alg. 1).  Every i in H_k starts from v = g_i[k] and walks the other
+ *                          tasks in the order perm_host[i] (tasks outside H_k are skipped): a pair with ||v||^2 <= 0 or ||g_j||^2 <= 0
+ *                          is skipped, every other pair counts one projection, and where <v, g_j> < 0 one conflict and
+ *                          v -= <v, g_j> / ||g_j||^2 g_j (g_j as the task produced it).  final[k] = mean over H_k of the v_i; a tensor with
+ *                          one holder gets that gradient as it is, so every head is trained in every step.  flag[k] = |H_k| > 0.
+ *       GMP_SURGERY_SCOPE_TENSOR  one such walk per tensor, on the tensor's own Gram matrix.
+ *       GMP_SURGERY_SCOPE_MODEL   ONE walk on G^ = the sum of the Gram matrices of the tensors with |H_k| >= 2 (ascending k, double),
+ *                          i.e. on the tasks' whole shared vectors, over the tasks that hold any such tensor; with v_i = sum_b
+ *                          alpha[i][b] g_b, tensor k of that set takes g_b[k] with weight (sum_i alpha[i][b]) / |H_k|.  The other
+ *                          tensors behave as in tensor scope.  Conflicts and projections are those of the one walk.
+ *   GMP_SURGERY_MEAN       final[k] = mean over H_k of g_i[k]; no projections (metrics 0, 0); scope is not read.
+ *   extra_task is added on top under every rule and sets the flag.
+ * perm_host [n_order][n_order - 1] (host, read during the call; pcgrad only, may be null when n_order == 1): row i lists the ORDER
+ * POSITIONS task order_host[i] walks, a permutation of the positions other than i.
+ * phases: tensor scope (and mean) -- bits 0 and 1 as above.  Model scope -- bit value 8 = the Gram matrices of [k_begin, k_end) only,
+ * bit value 16 = fold, solve and combine over ALL tensors (once every tensor's Gram matrix stands), bit 1 as above; the one-shot call is
+ * 8 | 16 | 2 over all tensors.  Bit 0 with model scope, bits 8 / 16 without it and the foreign pass (bit 2, which encodes the
+ * reference's emission rule) with any other rule than the reference's are GMP_ERR_ARG, as are an unknown rule or scope and a perm_host
+ * row that is no permutation; nothing is launched then. */
+#define GMP_SURGERY_REFERENCE 0
+#define GMP_SURGERY_PCGRAD 1
+#define GMP_SURGERY_MEAN 2
+#define GMP_SURGERY_SCOPE_TENSOR 0
+#define GMP_SURGERY_SCOPE_MODEL 1
+int gmp_mt_surgery_clip_adamw(int rule, int scope, const int32_t* perm_host,
+                              const float* task_grads, int64_t task_stride, int num_tasks, int num_tensors,
+                              const int64_t* tensor_off, const int32_t* tensor_len, const uint8_t* has,
+                              const int32_t* order_host, int n_order, int last_task, int extra_task,
+                              float* params, float* exp_avg, float* exp_avg_sq, float* steps,
+                              const float* lr, const float* wd, float beta1, float beta2, float eps,
+                              float max_norm, float* final_grad, float* normsq_out, int32_t* metrics_out,
+                              int32_t* flags_out, void* ws, size_t ws_bytes, int apply_update,
+                              int k_begin, int k_end, int phases, const int32_t* abort_flag, gmp_stream_t stream);
+
 
 /* ---- device-side augmentation and masking ------------------------------------------------------------
  * The per-graph loops of src/pretrain/augmentations.py:17-111 (GraphAugmentor.create_two_views: node drop, subgraph relabel,

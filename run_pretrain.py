@@ -2,7 +2,8 @@
 """Pre-training CLI with the reference's flags (run_pretrain.py:82-98): --sweep | --exp_name S --seed N.
 Each experiment runs as a child process (`python -m gnn_pretraining_amd.pretrain.pretrain`) with PYTHONPATH=cwd;
 a failing child makes this script exit 1 with the child's stderr in the message.  Extra flags after `--` are
-passed through to the child (e.g. `-- --epochs 1 --steps-per-epoch 20`)."""
+passed through to the child (e.g. `-- --epochs 1 --steps-per-epoch 20`, or `-- --surgery pcgrad --surgery-scope model` for PCGrad as
+published instead of the reference's rule; `-- --surgery mean` for the plain mean)."""
 import argparse
 import os
 import subprocess
