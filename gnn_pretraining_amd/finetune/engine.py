@@ -9,6 +9,12 @@ autograd nodes.  Here the same step is ~60 launches with no autograd and no host
 the encoder's K = 1,433 is padded to 1,440 (a multiple of the GEMM's 32-deep K-step; the weight's padded columns stay zero), and
 the optimizer is the pre-training engine's multi-tensor AdamW over one flat buffer.
 
+Structure: BackboneEngine holds what every fine-tune step shares (flat buffer, streams and gates, the backbone forward, backward and AdamW)
+and is built from the model alone; a leaf supplies N, csr, seg_ptr[1] = N and the encoder input (dense `x` with leading dimension dpad, or
+`xs` / `x_csc` with `sparse` set), sizes the row buffers with _alloc_rows, stores its step's inputs on itself, calls _enqueue, and implements
+its one hook, _head_backward.  FullGraphEngine adds a graph fixed at construction; on it sit NodeClassificationEngine (logits, CE head,
+the hipGraph capture) and LinkPredictionEngine; GraphClassificationEngine sits on the base directly (capacities, a batch per step).
+
 `FinetuneGNN` stays the owner of the parameters (its tensors become views into the flat buffer, `state_dict()` keys unchanged),
 so checkpoints, evaluation and the reference-shaped loop around it are untouched.
 
@@ -37,7 +43,7 @@ bitwise the step without it."""
 from __future__ import annotations
 
 import ctypes as C
-import os as _os_mod
+import os
 from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import torch
@@ -61,39 +67,22 @@ def _i64(xs):
     return (C.c_int64 * len(xs))(*[int(v) for v in xs])
 
 
-class NodeClassificationEngine:
-    def __init__(self, model: FinetuneGNN, x: Tensor, edge_index: Tensor, device, seed: int = 0) -> None:
+def _ptr(t: Optional[Tensor]) -> Optional[int]:
+    return None if t is None else t.data_ptr()
+
+
+class BackboneEngine:
+    """Everything the three engines share, and nothing else; built from the model alone (the structure paragraph of the module docstring)."""
+    def __init__(self, model: FinetuneGNN, d_in: int, device, seed: int = 0) -> None:
         self.model, self.device, self.lib = model, torch.device(device), L.lib()
         self.seed, self.step_count, self.dropout_p = seed, 0, DROPOUT_RATE
         dev = self.device
-        self.N, self.d_in = int(x.size(0)), int(x.size(1))
-        self.dpad = (self.d_in + 31) // 32 * 32
-        # sparse (CSR) features: the encoder is gmp_sparse_linear_fwd / _wgrad on the same [256, dpad] weight slot; the CSC form the
-        # weight gradient reads is built here, once (the features never change)
-        self.sparse = isinstance(x, SparseFeatures)
-        if self.sparse:
-            self.x, self.xs = None, x.to(dev)
-            self.x_csc = self.xs.csc()
-            self.sp_wt = torch.empty(self.lib.gmp_sparse_linear_workspace_bytes(self.d_in, H), dtype=torch.uint8, device=dev)
-            self.sp_status = torch.zeros(1, dtype=torch.int32, device=dev)          # skipped indices (none once csc() has passed): loss()
-            self.colsum_ws = torch.empty(max(self.lib.gmp_colsum_workspace_bytes(self.N, H), 16), dtype=torch.uint8, device=dev)
-        else:
-            self.x = torch.zeros(self.N, self.dpad, device=dev)
-            self.x[:, :self.d_in] = x.to(dev)
-        self.csr = ops.csr_build(edge_index.to(dev).contiguous(), self.N)
-        head = model.classification_head                  # (the link-prediction head has no class logits: LinkPredictionEngine)
-        self.classes = int(head.mlp[0].weight.size(0)) if hasattr(head, "mlp") else 0
+        self.d_in, self.dpad = int(d_in), (int(d_in) + 31) // 32 * 32
+        self.N, self.csr, self.sparse, self.x, self.num_targets = 0, None, False, None, 0
         self._flatten()
         f = lambda *s: torch.empty(*s, device=dev)
-        N, Lr = self.N, GNN_NUM_LAYERS
-        self.z0, self.h = f(N, H), [f(N, H) for _ in range(Lr + 1)]
-        self.a, self.z1, self.r1, self.z2 = [f(N, H) for _ in range(Lr)], [f(N, 2 * H) for _ in range(Lr)], [f(N, 2 * H) for _ in range(Lr)], [f(N, H) for _ in range(Lr)]
-        self.stat = {k: f(Lr, c) for k, c in (("m1", 2 * H), ("s1", 2 * H), ("m2", H), ("s2", H))}
+        self.stat = {k: f(GNN_NUM_LAYERS, c) for k, c in (("m1", 2 * H), ("s1", 2 * H), ("m2", H), ("s2", H))}
         self.enc_mean, self.enc_rstd = f(H), f(H)
-        self.logits, self.gA, self.gB, self.ga, self.gW, self.gW2 = f(N, self.classes), f(N, H), f(N, H), f(N, H), f(N, 2 * H), f(N, 2 * H)
-        # per-layer g_u / g_z1 (+ one g_u for the encoder): the weight-gradient GEMMs read them on the side stream while the chain moves on
-        self.gu_l, self.gz1_l = [f(N, H) for _ in range(Lr + 1)], [f(N, 2 * H) for _ in range(Lr)]
-        self.rowdot = f(Lr, N)
         # the side stream must sit on a hardware queue of its own: in a process whose queues are taken (bench.py after the pre-training engine) a fresh
         # pool stream shared the main stream's queue and the forked step took 3.98 ms instead of 0.88 -- measured, not assumed (streams.py)
         if dev.type == "cuda":
@@ -102,35 +91,24 @@ class NodeClassificationEngine:
             # main <-> side dependencies by gates (a sleeping wave on a flag word, csrc/streams.hip) instead of events where the two streams
             # were measured on different hardware queues: a queue parked on an event wait costs the running one ~2 us per kernel boundary
             own_queue = not ST.share_queue(torch.cuda.current_stream(dev).cuda_stream, self.side.cuda_stream)
-            self._gates_ok = own_queue and _os_mod.environ.get("GMP_FINETUNE_GATES", "1") != "0"
+            self._gates_ok = own_queue and os.environ.get("GMP_FINETUNE_GATES", "1") != "0"
         else:
             self.side, self._gates_ok, own_queue = None, False, False
-        self.sync_flags = torch.zeros(64, dtype=torch.int32, device=dev)
-        self._epoch = 0
+        self.sync_flags, self._epoch = torch.zeros(64, dtype=torch.int32, device=dev), 0
         self.side_ws = torch.empty(32 << 20, dtype=torch.uint8, device=dev)
-        self.seed_word = torch.zeros(1, dtype=torch.int64, device=dev)        # device copy of step_count for captured steps (gmp_bn_config.seed_dev)
-        import os as _os
-        # Default since the slab BatchNorm: launch by launch, the weight-gradient GEMMs on the side stream (0.88 ms per step; the host needs
-        # 0.55-0.68 ms for the 120 ctypes launches and keeps up).  GMP_FINETUNE_GRAPH=1: the step captured once and replayed (bitwise the
-        # same numbers, host 0.43 ms per replay, 0.95 ms per step on ONE chain: replaying a graph with a second branch costs the host 1.45 ms on
-        # this runtime -- ROCm 7.2, profiles/README.md round 3 -- so a captured step keeps its weight gradients in the chain).
-        self.use_graph = dev.type == "cuda" and _os.environ.get("GMP_FINETUNE_GRAPH", "0") == "1"
-        # (no queue of its own for the side stream -- every hardware queue of the process taken --: the fork would run behind main's kernels in
-        # the same in-order queue, slower than the plain chain)
-        self.fork_wgrads = _os.environ.get("GMP_FINETUNE_FORK", "0" if (self.use_graph or not own_queue) else "1") == "1"
-        self._graph, self._graph_key, self._graph_step, self._graph_seen = None, None, -1, None
-        self.seg_ptr = torch.tensor([0, N], dtype=torch.int32, device=dev)
-        self.bn_ws = torch.empty(self.lib.gmp_bn_workspace_bytes(N, 2 * H, 1, N), dtype=torch.uint8, device=dev)
+        # Default since the slab BatchNorm: launch by launch, the weight-gradient GEMMs on the side stream (0.88 ms per Cora_NC step; the host needs
+        # 0.55-0.68 ms for the 120 ctypes launches and keeps up).  Not without a queue of its own for the side stream (every hardware queue of the
+        # process taken): the fork would run behind main's kernels in the same in-order queue, slower than the plain chain
+        self.fork_wgrads = os.environ.get("GMP_FINETUNE_FORK", "1" if own_queue else "0") == "1"
+        self.seg_ptr = torch.zeros(2, dtype=torch.int32, device=dev)                # the one BatchNorm segment [0, N)
         # rendezvous words of the BatchNorm slab form (gmp_bn_config.sync: the graph's 2,708 rows as 128-row slabs over the whole chip, one
         # launch); every BatchNorm of the step runs on the main stream, so one buffer serves them all.  GMP_BN_SLABS=0: one workgroup per strip
         self.bn_sync = (torch.zeros(self.lib.gmp_bn_sync_bytes(2 * H, 1) // 4, dtype=torch.int32, device=dev)
-                        if _os.environ.get("GMP_BN_SLABS", "1") != "0" else None)
+                        if os.environ.get("GMP_BN_SLABS", "1") != "0" else None)
         self.gemm_ws = torch.empty(32 << 20, dtype=torch.uint8, device=dev)
-        self.loss_ws = torch.empty(self.lib.gmp_loss_workspace_bytes(N * H), dtype=torch.uint8, device=dev)
         self.loss_sum, self.g_scale = torch.zeros(1, device=dev), torch.ones(1, device=dev)
         self.mt_ws = torch.empty(self.lib.gmp_mt_workspace_bytes(self.K), dtype=torch.uint8, device=dev)
         self.normsq, self.metrics, self.flags = torch.zeros(1, device=dev), torch.zeros(2, dtype=torch.int32, device=dev), torch.zeros(self.K, dtype=torch.int32, device=dev)
-        self._train_idx: Optional[Tensor] = None
         self._bn_calls = 0
         # inference path: the (scale, shift) table of the 11 BatchNorms (encoder, then inner / outer of each layer), refilled per pass
         self._fold_ch = [H] + [2 * H, H] * GNN_NUM_LAYERS
@@ -138,6 +116,18 @@ class NodeClassificationEngine:
         self._fold_table = torch.empty(2 * sum(self._fold_ch), device=dev)
         self._infer_loss: Optional[Tuple[Tensor, int]] = None     # (loss sum, count) of the last predict with targets; a step clears it
         self._fwd_gen, self._embed_gen = 0, -1                    # forwards that wrote h[] so far / the one whose output embed() last returned
+
+    def _alloc_rows(self, cap_n: int) -> None:
+        """Every [rows, 256 / 512] activation and gradient buffer and the BatchNorm workspace, for up to cap_n rows."""
+        f, Lr = (lambda *s: torch.empty(*s, device=self.device)), GNN_NUM_LAYERS
+        self.z0, self.h = f(cap_n, H), [f(cap_n, H) for _ in range(Lr + 1)]
+        self.a, self.z1 = [f(cap_n, H) for _ in range(Lr)], [f(cap_n, 2 * H) for _ in range(Lr)]
+        self.r1, self.z2 = [f(cap_n, 2 * H) for _ in range(Lr)], [f(cap_n, H) for _ in range(Lr)]
+        self.gA, self.ga, self.gW = f(cap_n, H), f(cap_n, H), f(cap_n, 2 * H)
+        # per-layer g_u / g_z1 (+ one g_u for the encoder): the weight-gradient GEMMs read them on the side stream while the chain moves on
+        self.gu_l, self.gz1_l = [f(cap_n, H) for _ in range(Lr + 1)], [f(cap_n, 2 * H) for _ in range(Lr)]
+        self.rowdot = f(Lr, cap_n)
+        self.bn_ws = torch.empty(max(self.lib.gmp_bn_workspace_bytes(cap_n, 2 * H, 1, cap_n), 16), dtype=torch.uint8, device=self.device)
 
     # ------------------------------------------------------------------ parameters: one flat buffer, the module's tensors view into it
     def _flatten(self) -> None:
@@ -194,13 +184,13 @@ class NodeClassificationEngine:
         p = self.dropout_p if (dropout and self.model.training) else 0.0
         base = self.seed * 1000003
         sync = (self.bn_sync.data_ptr(), self.bn_sync.numel()) if self.bn_sync is not None else (None, 0)
-        if self._seed_dev:
-            return L.BnConfig(int(self.model.training), int(relu), 1e-5, 0.1, p, base & (2 ** 64 - 1), site + self._site_base, self._seed_dev, *sync)
-        return L.BnConfig(int(self.model.training), int(relu), 1e-5, 0.1, p, (base + self.step_count) & (2 ** 64 - 1), site + self._site_base, None, *sync)
+        step = 0 if self._seed_dev else self.step_count
+        return L.BnConfig(int(self.model.training), int(relu), 1e-5, 0.1, p, (base + step) & (2 ** 64 - 1), site + self._site_base, self._seed_dev, *sync)
 
-    _seed_dev = None
+    _seed_dev = None                    # the device word a captured step reads its step number from (NodeClassificationEngine.step)
     _site_base = 0                      # added to every dropout site of a forward (LinkPredictionEngine.mining_forward: a second pass per step)
 
+    # ------------------------------------------------------------------ the launches that recur; pointers are resolved at every launch
     def _gemm(self, st, mode, A, B, bias, Cc, M, N, K, lda, ldb, ldc, ws: Optional[Tensor] = None):
         self._chk(self.lib.gmp_gemm_f32(mode, A, B, bias, Cc, M, N, K, lda, ldb, ldc, 1.0, 0, 0, None if ws is None else ws.data_ptr(),
                                         0 if ws is None else ws.numel(), st), "gemm")
@@ -211,53 +201,61 @@ class NodeClassificationEngine:
         self._chk(self.lib.gmp_gemm_f32_grouped(TN, G, X, None, g, 1, _i32([0, self.N]), None, None, _i64([self._G(w_name)]), g, _i64([self._G(b_name)]),
                                                 M_tn, N_out, 0, M_tn, ldx, N_out, 1.0, 0, 0, ws.data_ptr(), ws.numel(), st), "wgrad")
 
+    def _bn_fwd(self, st, z: Tensor, resid: Optional[Tensor], pre: str, bn, mean: Optional[Tensor], rstd: Optional[Tensor], out: Tensor, cfg: L.BnConfig):
+        """out = act(BatchNorm(z) [+ resid]) over the one segment [0, N): `pre` names the affine pair in the flat buffer, `bn` the module
+        whose running statistics it reads (and in training updates), mean / rstd the rows the backward reads (None in eval mode)."""
+        N, P = self.N, self._P
+        self._chk(self.lib.gmp_bn_fwd(z.data_ptr(), _ptr(resid), self.seg_ptr.data_ptr(), None, 1, N, N, z.size(1), P(pre + "weight"), P(pre + "bias"),
+                                      bn.running_mean.data_ptr(), bn.running_var.data_ptr(), _ptr(mean), _ptr(rstd), out.data_ptr(), C.byref(cfg),
+                                      self.bn_ws.data_ptr(), self.bn_ws.numel(), st), "bn " + pre)
+
+    def _bn_bwd(self, st, gy: Tensor, z: Tensor, resid: Optional[Tensor], pre: str, bn, mean: Tensor, rstd: Tensor, gz: Tensor, cfg: L.BnConfig):
+        """gz = d loss / d z of _bn_fwd's launch from gy = d loss / d out; the affine pair's gradients go straight into the gradient buffer."""
+        N, P, g = self.N, self._P, self.grad.data_ptr()
+        self._chk(self.lib.gmp_bn_bwd(gy.data_ptr(), z.data_ptr(), _ptr(resid), self.seg_ptr.data_ptr(), None, 1, N, N, z.size(1), P(pre + "weight"),
+                                      P(pre + "bias"), bn.running_mean.data_ptr(), bn.running_var.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+                                      gz.data_ptr(), g, g, _i32([0, 1]), _i64([self._G(pre + "weight")]), _i64([self._G(pre + "bias")]), 1,
+                                      C.byref(cfg), self.bn_ws.data_ptr(), self.bn_ws.numel(), st), "bn bwd " + pre)
+
+    def _sparse_encoder(self, st) -> None:
+        """z0 = xs W^T + b (gmp_sparse_linear_fwd on the [256, dpad] weight slot)."""
+        xs, P = self.xs, self._P
+        self._chk(self.lib.gmp_sparse_linear_fwd(xs.rowptr.data_ptr(), xs.col.data_ptr(), xs.val.data_ptr(), self.N, self.d_in, P("input_encoder.linear.weight"),
+                                                 self.dpad, P("input_encoder.linear.bias"), self.z0.data_ptr(), H, H, self.sp_status.data_ptr(),
+                                                 self.sp_wt.data_ptr(), self.sp_wt.numel(), st), "sparse encoder")
+
     # ------------------------------------------------------------------ forward (finetune_model.py:68-80, message passing on the full graph)
     def forward(self) -> Tensor:
+        """Encoder + backbone in the model's mode (the leaf's head runs behind it).  The engine's own buffer: the next forward overwrites it."""
         self._backbone_forward()
-        self._gemm(torch.cuda.current_stream(self.device).cuda_stream, NT, self.h[GNN_NUM_LAYERS].data_ptr(), self._P("classification_head.mlp.0.weight"),
-                   self._P("classification_head.mlp.0.bias"), self.logits.data_ptr(), self.N, self.classes, H, H, H, self.classes)
         if self.model.training:
             self._bn_calls += 1             # num_batches_tracked only matters for a saved state_dict (momentum is fixed): flush_counters()
-        return self.logits
+        return self.h[GNN_NUM_LAYERS]
 
     def _backbone_forward(self) -> None:
         """Encoder + the GIN layers into h[GNN_NUM_LAYERS]; every activation the backward reads stays in the engine's buffers."""
         lib, N, P, c = self.lib, self.N, self._P, self.csr
         self._fwd_gen += 1
         st = torch.cuda.current_stream(self.device).cuda_stream
-        enc, sp = self.model.input_encoder, self.seg_ptr.data_ptr()
         # 2,708 x 1,440 -> 256 is 172 output tiles for 256 CUs; unsliced since round 3 (three K-slices + their reduction: 38 us, one launch: 33 --
         # gmp_gemm_f32_workspace_bytes now slices NT / NN only below ~100 tiles)
         if self.sparse:
-            xs = self.xs
-            self._chk(lib.gmp_sparse_linear_fwd(xs.rowptr.data_ptr(), xs.col.data_ptr(), xs.val.data_ptr(), N, self.d_in, P("input_encoder.linear.weight"),
-                                                self.dpad, P("input_encoder.linear.bias"), self.z0.data_ptr(), H, H, self.sp_status.data_ptr(),
-                                                self.sp_wt.data_ptr(), self.sp_wt.numel(), st), "sparse encoder")
+            self._sparse_encoder(st)
         else:
             self._gemm(st, NT, self.x.data_ptr(), P("input_encoder.linear.weight"), P("input_encoder.linear.bias"), self.z0.data_ptr(), N, H, self.dpad,
                        self.dpad, self.dpad, H, ws=self.gemm_ws)
-        cfg = self._cfg(True, True, 1)
-        self._chk(lib.gmp_bn_fwd(self.z0.data_ptr(), None, sp, None, 1, N, N, H, P("input_encoder.batch_norm.weight"), P("input_encoder.batch_norm.bias"),
-                                 enc.batch_norm.running_mean.data_ptr(), enc.batch_norm.running_var.data_ptr(), self.enc_mean.data_ptr(),
-                                 self.enc_rstd.data_ptr(), self.h[0].data_ptr(), C.byref(cfg), self.bn_ws.data_ptr(), self.bn_ws.numel(), st), "bn encoder")
+        self._bn_fwd(st, self.z0, None, "input_encoder.batch_norm.", self.model.input_encoder.batch_norm, self.enc_mean, self.enc_rstd, self.h[0], self._cfg(True, True, 1))
         for l in range(GNN_NUM_LAYERS):
             pre, layer = f"gnn_backbone.layers.{l}.", self.model.gnn_backbone.layers[l]
             self._chk(lib.gmp_gin_aggregate_fwd(self.h[l].data_ptr(), c.rowptr.data_ptr(), c.col.data_ptr(), P(pre + "gin_conv.eps"), self.a[l].data_ptr(), N, H, st), "aggregate")
             self._gemm(st, NT, self.a[l].data_ptr(), P(pre + "gin_conv.nn.0.weight"), P(pre + "gin_conv.nn.0.bias"), self.z1[l].data_ptr(), N, 2 * H, H, H, H, 2 * H)
-            bn1, cfg = layer.gin_conv.nn[1], self._cfg(True, False, 0)
-            self._chk(lib.gmp_bn_fwd(self.z1[l].data_ptr(), None, sp, None, 1, N, N, 2 * H, P(pre + "gin_conv.nn.1.weight"), P(pre + "gin_conv.nn.1.bias"),
-                                     bn1.running_mean.data_ptr(), bn1.running_var.data_ptr(), self.stat["m1"][l].data_ptr(), self.stat["s1"][l].data_ptr(),
-                                     self.r1[l].data_ptr(), C.byref(cfg), self.bn_ws.data_ptr(), self.bn_ws.numel(), st), "bn1")
+            self._bn_fwd(st, self.z1[l], None, pre + "gin_conv.nn.1.", layer.gin_conv.nn[1], self.stat["m1"][l], self.stat["s1"][l], self.r1[l], self._cfg(True, False, 0))
             self._gemm(st, NT, self.r1[l].data_ptr(), P(pre + "gin_conv.nn.3.weight"), P(pre + "gin_conv.nn.3.bias"), self.z2[l].data_ptr(), N, H, 2 * H, 2 * H, 2 * H, H)
-            bn2, cfg = layer.batch_norm, self._cfg(True, True, 10 + l)
-            self._chk(lib.gmp_bn_fwd(self.z2[l].data_ptr(), self.h[l].data_ptr(), sp, None, 1, N, N, H, P(pre + "batch_norm.weight"), P(pre + "batch_norm.bias"),
-                                     bn2.running_mean.data_ptr(), bn2.running_var.data_ptr(), self.stat["m2"][l].data_ptr(), self.stat["s2"][l].data_ptr(),
-                                     self.h[l + 1].data_ptr(), C.byref(cfg), self.bn_ws.data_ptr(), self.bn_ws.numel(), st), "bn2")
+            self._bn_fwd(st, self.z2[l], self.h[l], pre + "batch_norm.", layer.batch_norm, self.stat["m2"][l], self.stat["s2"][l], self.h[l + 1], self._cfg(True, True, 10 + l))
 
     # ------------------------------------------------------------------ inference: eval mode, BatchNorm folded into the GEMM epilogues
     def _bn_modules(self):
-        enc = self.model.input_encoder
-        return [enc.batch_norm] + [b for l in self.model.gnn_backbone.layers for b in (l.gin_conv.nn[1], l.batch_norm)]
+        return [self.model.input_encoder.batch_norm] + [b for l in self.model.gnn_backbone.layers for b in (l.gin_conv.nn[1], l.batch_norm)]
 
     def _bn_names(self) -> List[str]:
         return ["input_encoder.batch_norm."] + [f"gnn_backbone.layers.{l}.{n}" for l in range(GNN_NUM_LAYERS) for n in ("gin_conv.nn.1.", "batch_norm.")]
@@ -282,14 +280,8 @@ class NodeClassificationEngine:
                                                 ws.data_ptr(), ws.numel(), st), "linear affine")
 
         if self.sparse:
-            xs, enc = self.xs, self.model.input_encoder
-            self._chk(lib.gmp_sparse_linear_fwd(xs.rowptr.data_ptr(), xs.col.data_ptr(), xs.val.data_ptr(), N, self.d_in, P("input_encoder.linear.weight"),
-                                                self.dpad, P("input_encoder.linear.bias"), self.z0.data_ptr(), H, H, self.sp_status.data_ptr(),
-                                                self.sp_wt.data_ptr(), self.sp_wt.numel(), st), "sparse encoder")
-            cfg = L.BnConfig(0, 1, 1e-5, 0.1, 0.0, 0, 0, None, None, 0)
-            self._chk(lib.gmp_bn_fwd(self.z0.data_ptr(), None, self.seg_ptr.data_ptr(), None, 1, N, N, H, P("input_encoder.batch_norm.weight"),
-                                     P("input_encoder.batch_norm.bias"), enc.batch_norm.running_mean.data_ptr(), enc.batch_norm.running_var.data_ptr(),
-                                     None, None, self.h[0].data_ptr(), C.byref(cfg), self.bn_ws.data_ptr(), self.bn_ws.numel(), st), "bn encoder (eval)")
+            self._sparse_encoder(st)
+            self._bn_fwd(st, self.z0, None, "input_encoder.batch_norm.", bns[0], None, None, self.h[0], L.BnConfig(0, 1, 1e-5, 0.1, 0.0, 0, 0, None, None, 0))
         else:
             lin(self.x.data_ptr(), "input_encoder.linear.weight", "input_encoder.linear.bias", None, 0, self.h[0].data_ptr(), N, H, self.dpad, self.dpad, self.dpad)
         for l in range(GNN_NUM_LAYERS):
@@ -306,71 +298,17 @@ class NodeClassificationEngine:
         self._embed_gen = self._fwd_gen
         return out
 
-    def predict(self, node_indices: Tensor, targets: Optional[Tensor] = None) -> Tensor:
-        """Eval-mode logits [len(node_indices), C] of the given nodes; with targets, loss() then returns their mean cross-entropy.
-        Changes nothing a training step reads: parameters, optimizer state, running statistics, counters and the captured step stay as they are."""
-        from .. import operators as O
-        hL = self._infer_forward()
-        self._gemm(torch.cuda.current_stream(self.device).cuda_stream, NT, hL.data_ptr(), self._P("classification_head.mlp.0.weight"),
-                   self._P("classification_head.mlp.0.bias"), self.logits.data_ptr(), self.N, self.classes, H, H, H, self.classes)
-        with torch.no_grad():
-            rows = O.take_rows(self.logits, node_indices)
-            self._infer_loss = None
-            if targets is not None:
-                self._infer_loss = (ops.cross_entropy_sum_fwd(rows, targets.contiguous()), int(node_indices.numel()))
-        return rows
-
     def flush_counters(self) -> None:
         if self._bn_calls:
-            enc = self.model.input_encoder
-            for bn in [enc.batch_norm] + [b for l in self.model.gnn_backbone.layers for b in (l.gin_conv.nn[1], l.batch_norm)]:
+            for bn in self._bn_modules():
                 bn.num_batches_tracked += self._bn_calls
             self._bn_calls = 0
 
     # ------------------------------------------------------------------ one optimisation step (finetune.py:162-179 + 318-320)
-    def step(self, node_indices: Tensor, targets: Tensor, apply_update: bool = True) -> None:
-        """loss = cross_entropy(model(data)[node_indices], targets) (mean); backward; AdamW.  Nothing is read back: loss().
-        Training steps with an update are replayed from a hipGraph captured at the first such call for these index tensors."""
-        self._infer_loss = None
-        if not (self.use_graph and apply_update and self.model.training):
-            self._enqueue(node_indices, targets, apply_update, forked=self.fork_wgrads)
-            self.step_count += 1
-            return
-        key = (node_indices.data_ptr(), targets.data_ptr(), int(node_indices.numel()))
-        if self._graph_key != key:
-            # an eager step first (it IS this call's step): code objects loaded, LDS attributes set, row buffers allocated -- nothing of
-            # that may happen inside a capture.  The capture itself (tens of ms) waits for the SECOND call with the same index tensors:
-            # a caller that builds fresh tensors per call never pays for it.
-            self._enqueue(node_indices, targets, True)
-            self.step_count += 1
-            if self._graph_seen != key:
-                self._graph_seen, self._graph_keep = key, (node_indices, targets)
-                return
-            main = torch.cuda.current_stream(self.device)
-            main.synchronize()
-            graph = torch.cuda.CUDAGraph()
-            self._seed_dev = self.seed_word.data_ptr()
-            try:
-                with torch.cuda.graph(graph):
-                    self._enqueue(node_indices, targets, True, forked=self.fork_wgrads)
-                    self._chk(self.lib.gmp_counter_add(self.seed_word.data_ptr(), 1, torch.cuda.current_stream(self.device).cuda_stream), "seed word")
-            finally:
-                self._seed_dev = None
-            self._bn_calls -= 1                                     # (forward() counted the capture pass, which ran nothing)
-            self._graph, self._graph_key, self._graph_step = graph, key, -1
-            self._graph_keep = (node_indices, targets)             # the captured launches hold these pointers
-            return
-        if self._graph_step != self.step_count:                    # eager steps ran in between (evaluation does not count): resynchronise
-            self.seed_word.fill_(self.step_count)
-        self._graph.replay()
-        self._fwd_gen += 1
-        self.step_count += 1
-        self._graph_step = self.step_count
-        self._bn_calls += 1
-
-    def _enqueue(self, node_indices: Tensor, targets: Tensor, apply_update: bool, forked: bool = False) -> None:
-        """The step's launches on the current stream.  forked: the weight-gradient GEMMs (they only feed the gradient buffer) go to the
-        side stream behind an event of the main one -- inside a capture a parallel branch of the graph -- and are joined before AdamW."""
+    def _enqueue(self, apply_update: bool, forked: bool = False) -> None:
+        """The step's launches on the current stream, for the inputs the leaf's step() has stored on the engine.  forked: the weight-gradient
+        GEMMs (they only feed the gradient buffer) go to the side stream behind an event of the main one -- inside a capture a parallel
+        branch of the graph -- and are joined before AdamW."""
         lib, N, P, c = self.lib, self.N, self._P, self.csr
         main = torch.cuda.current_stream(self.device)
         st = main.cuda_stream
@@ -383,18 +321,15 @@ class NodeClassificationEngine:
             self._epoch += 1
         flags, epoch, nfork = self.sync_flags.data_ptr(), self._epoch, [0]
 
-        def fork(by_gemm: bool = False) -> None:
-            """The side stream may read what main has produced so far.  by_gemm (gates only): the caller launches a GEMM on MAIN next, which
-            carries the signal as it starts (gmp_gate_open_by_next_gemm) -- no one-thread launch on the chain."""
+        def fork() -> None:
+            """The side stream may read what main has produced so far.  The caller launches a GEMM on MAIN next; with gates that GEMM carries
+            the signal as it starts (gmp_gate_open_by_next_gemm) -- no one-thread launch on the chain."""
             if side is None:
                 return
             if gates:
                 k = nfork[0]
                 nfork[0] = k + 1
-                if by_gemm:
-                    self._chk(lib.gmp_gate_open_by_next_gemm(flags + 4 * k, epoch), "gate open by gemm")
-                else:
-                    self._chk(lib.gmp_gate_open(flags + 4 * k, epoch, st), "gate open")
+                self._chk(lib.gmp_gate_open_by_next_gemm(flags + 4 * k, epoch), "gate open by gemm")
                 self._chk(lib.gmp_gate_wait(flags, 1 << k, epoch, flags + 4 * 63, sst), "gate wait")
             else:
                 side.wait_stream(main)
@@ -405,46 +340,30 @@ class NodeClassificationEngine:
                 self._chk(lib.gmp_gate_open(flags + 4 * (nfork[0] - 1), epoch, st), "gate open")
 
         self.forward()
-        self._head_backward(node_indices, targets, st)
-        g = self.grad.data_ptr()
-        gcur, ga = self.gA, self.ga
-        sp, one = self.seg_ptr.data_ptr(), _i32([0, 1])
-        pending_eps = None
+        self._head_backward(st)
+        g, gcur, ga, pending_eps = self.grad.data_ptr(), self.gA, self.ga, None
         for l in reversed(range(GNN_NUM_LAYERS)):
             pre, layer = f"gnn_backbone.layers.{l}.", self.model.gnn_backbone.layers[l]
             gu, gz1 = self.gu_l[l], self.gz1_l[l]
-            bn2, cfg = layer.batch_norm, self._cfg(True, True, 10 + l)
-            self._chk(lib.gmp_bn_bwd(gcur.data_ptr(), self.z2[l].data_ptr(), self.h[l].data_ptr(), sp, None, 1, N, N, H, P(pre + "batch_norm.weight"),
-                                     P(pre + "batch_norm.bias"), bn2.running_mean.data_ptr(), bn2.running_var.data_ptr(), self.stat["m2"][l].data_ptr(),
-                                     self.stat["s2"][l].data_ptr(), gu.data_ptr(), g, g, one, _i64([self._G(pre + "batch_norm.weight")]),
-                                     _i64([self._G(pre + "batch_norm.bias")]), 1, C.byref(cfg), self.bn_ws.data_ptr(), self.bn_ws.numel(), st), "bn2 bwd")
-            fork(by_gemm=True)
+            self._bn_bwd(st, gcur, self.z2[l], self.h[l], pre + "batch_norm.", layer.batch_norm, self.stat["m2"][l], self.stat["s2"][l], gu, self._cfg(True, True, 10 + l))
+            fork()
             self._gemm(st, NN, gu.data_ptr(), P(pre + "gin_conv.nn.3.weight"), None, self.gW.data_ptr(), N, 2 * H, H, H, 2 * H, 2 * H)
             flush()
             if pending_eps is not None:                             # (the previous layer's aggregation backward is behind this fork too)
                 self._eps_grad(sst, pending_eps)
                 pending_eps = None
             self._wgrad(sst, gu.data_ptr(), self.r1[l].data_ptr(), pre + "gin_conv.nn.3.weight", pre + "gin_conv.nn.3.bias", H, 2 * H, 2 * H, wws)
-            bn1, cfg = layer.gin_conv.nn[1], self._cfg(True, False, 0)
-            self._chk(lib.gmp_bn_bwd(self.gW.data_ptr(), self.z1[l].data_ptr(), None, sp, None, 1, N, N, 2 * H, P(pre + "gin_conv.nn.1.weight"),
-                                     P(pre + "gin_conv.nn.1.bias"), bn1.running_mean.data_ptr(), bn1.running_var.data_ptr(), self.stat["m1"][l].data_ptr(),
-                                     self.stat["s1"][l].data_ptr(), gz1.data_ptr(), g, g, one, _i64([self._G(pre + "gin_conv.nn.1.weight")]),
-                                     _i64([self._G(pre + "gin_conv.nn.1.bias")]), 1, C.byref(cfg), self.bn_ws.data_ptr(), self.bn_ws.numel(), st), "bn1 bwd")
-            fork(by_gemm=True)
+            self._bn_bwd(st, self.gW, self.z1[l], None, pre + "gin_conv.nn.1.", layer.gin_conv.nn[1], self.stat["m1"][l], self.stat["s1"][l], gz1, self._cfg(True, False, 0))
+            fork()
             self._gemm(st, NN, gz1.data_ptr(), P(pre + "gin_conv.nn.0.weight"), None, ga.data_ptr(), N, H, 2 * H, 2 * H, H, H)
             flush()
             self._wgrad(sst, gz1.data_ptr(), self.a[l].data_ptr(), pre + "gin_conv.nn.0.weight", pre + "gin_conv.nn.0.bias", 2 * H, H, H, wws)
-            rowdot = self.rowdot[l]
             self._chk(lib.gmp_gin_aggregate_bwd_ex(ga.data_ptr(), c.rowptr_t.data_ptr(), c.col_t.data_ptr(), P(pre + "gin_conv.eps"), self.h[l].data_ptr(),
-                                                   gu.data_ptr(), gcur.data_ptr(), rowdot.data_ptr(), N, H, st), "aggregate bwd")
+                                                   gu.data_ptr(), gcur.data_ptr(), self.rowdot[l].data_ptr(), N, H, st), "aggregate bwd")
             pending_eps = l                                          # eps gradient: a 5 us sum that only feeds the gradient buffer -- with the next fork
         self._eps_grad(st, pending_eps)                             # layer 0's: on main, in front of the encoder backward
-        enc, cfg = self.model.input_encoder, self._cfg(True, True, 1)
         gu = self.gu_l[GNN_NUM_LAYERS]
-        self._chk(lib.gmp_bn_bwd(gcur.data_ptr(), self.z0.data_ptr(), None, sp, None, 1, N, N, H, P("input_encoder.batch_norm.weight"),
-                                 P("input_encoder.batch_norm.bias"), enc.batch_norm.running_mean.data_ptr(), enc.batch_norm.running_var.data_ptr(),
-                                 self.enc_mean.data_ptr(), self.enc_rstd.data_ptr(), gu.data_ptr(), g, g, one, _i64([self._G("input_encoder.batch_norm.weight")]),
-                                 _i64([self._G("input_encoder.batch_norm.bias")]), 1, C.byref(cfg), self.bn_ws.data_ptr(), self.bn_ws.numel(), st), "bn encoder bwd")
+        self._bn_bwd(st, gcur, self.z0, None, "input_encoder.batch_norm.", self.model.input_encoder.batch_norm, self.enc_mean, self.enc_rstd, gu, self._cfg(True, True, 1))
         if self.sparse:                                             # dW over the whole [256, dpad] slot (padding columns 0.0), db = colsum
             colptr, row, val_t = self.x_csc
             self._chk(lib.gmp_sparse_linear_wgrad(colptr.data_ptr(), row.data_ptr(), val_t.data_ptr(), N, self.d_in, gu.data_ptr(), H,
@@ -466,38 +385,17 @@ class NodeClassificationEngine:
                                                self.final_grad.data_ptr(), self.normsq.data_ptr(), self.metrics.data_ptr(), self.flags.data_ptr(),
                                                self.mt_ws.data_ptr(), self.mt_ws.numel(), int(apply_update), st), "adamw")
 
-    def _head_backward(self, node_indices: Tensor, targets: Tensor, st: int) -> None:
-        """Loss and head of the step after forward(): d loss / d h[GNN_NUM_LAYERS] into gA (the backbone backward starts from it)."""
-        lib, N, P, Cn = self.lib, self.N, self._P, self.classes
-        M = int(node_indices.numel())
-        if self._train_idx is None or self._train_idx.numel() != M:
-            f = lambda *s: torch.empty(*s, device=self.device)
-            self._rows_logits, self._rows_g, self._rows_h = f(M, Cn), f(M, Cn), f(M, H)
-            self._rows_gh = f(M, H)
-        self._train_idx, self.num_targets = node_indices, M
-        self.g_scale.fill_(1.0 / M)
-        idx, tgt, g = node_indices.data_ptr(), targets.data_ptr(), self.grad.data_ptr()
-        hL = self.h[GNN_NUM_LAYERS]
-        self._chk(lib.gmp_row_gather(self.logits.data_ptr(), idx, None, self._rows_logits.data_ptr(), M, N, Cn, st), "logit rows")
-        self._chk(lib.gmp_cross_entropy_sum_fwd(self._rows_logits.data_ptr(), tgt, M, Cn, self.loss_sum.data_ptr(), self.loss_ws.data_ptr(), self.loss_ws.numel(), st), "ce")
-        self._chk(lib.gmp_cross_entropy_sum_bwd(self._rows_logits.data_ptr(), tgt, M, Cn, self.g_scale.data_ptr(), self._rows_g.data_ptr(), st), "ce bwd")
-        # head: dW = g^T h[idx], db = colsum(g), g_h[idx] = g W  (only the M training rows carry a gradient)
-        self._chk(lib.gmp_row_gather(hL.data_ptr(), idx, None, self._rows_h.data_ptr(), M, N, H, st), "h rows")
-        self._chk(lib.gmp_gemm_f32_grouped(TN, self._rows_g.data_ptr(), self._rows_h.data_ptr(), None, g, 1, _i32([0, M]), None, None,
-                                           _i64([self._G("classification_head.mlp.0.weight")]), g, _i64([self._G("classification_head.mlp.0.bias")]),
-                                           Cn, H, 0, Cn, H, H, 1.0, 0, 0, None, 0, st), "head wgrad")
-        self._gemm(st, NN, self._rows_g.data_ptr(), P("classification_head.mlp.0.weight"), None, self._rows_gh.data_ptr(), M, H, Cn, Cn, H, H)
-        gcur = self.gA
-        gcur.zero_()
-        self._chk(lib.gmp_row_fill(gcur.data_ptr(), idx, self._rows_gh.data_ptr(), M, N, H, 0, st), "scatter g_h")
+    def _head_backward(self, st: int) -> None:
+        """The leaf's: loss and head after forward(), from the inputs its step() stored; d loss / d h[GNN_NUM_LAYERS] into gA."""
+        raise NotImplementedError
 
     def _eps_grad(self, stream: int, l: int) -> None:
         self._chk(self.lib.gmp_group_sum_1d(self.rowdot[l].data_ptr(), 1, _i32([0, self.N]), _i64([self._G(f"gnn_backbone.layers.{l}.gin_conv.eps")]),
                                             self.grad.data_ptr(), stream), "eps grad")
 
     def loss(self) -> float:
-        """Mean cross-entropy of the last step (a read-back: the one place the loop synchronises, so the gates' time-out word and the slab
-        BatchNorm's are looked at here too)."""
+        """Mean loss of the last step, or of the last predict with targets (a read-back: the one place the loop synchronises, so the gates'
+        time-out word and the slab BatchNorm's are looked at here too)."""
         infer = self._infer_loss
         v = float((self.loss_sum if infer is None else infer[0]).item())
         if self.sparse and int(self.sp_status.item()) != 0:
@@ -515,6 +413,135 @@ class NodeClassificationEngine:
         return self.final_grad[o:o + p.numel()].view_as(p)
 
 
+class FullGraphEngine(BackboneEngine):
+    """A fixed graph given at construction: its features (dense, or a graph.SparseFeatures) and its CSR are set up once, here."""
+
+    def __init__(self, model: FinetuneGNN, x: Tensor, edge_index: Tensor, device, seed: int = 0) -> None:
+        super().__init__(model, int(x.size(1)), device, seed)
+        dev, self.N = self.device, int(x.size(0))
+        # sparse (CSR) features: the encoder is gmp_sparse_linear_fwd / _wgrad on the same [256, dpad] weight slot; the CSC form the
+        # weight gradient reads is built here, once (the features never change)
+        self.sparse = isinstance(x, SparseFeatures)
+        if self.sparse:
+            self.xs = x.to(dev)
+            self.x_csc = self.xs.csc()
+            self.sp_wt = torch.empty(self.lib.gmp_sparse_linear_workspace_bytes(self.d_in, H), dtype=torch.uint8, device=dev)
+            self.sp_status = torch.zeros(1, dtype=torch.int32, device=dev)          # skipped indices (none once csc() has passed): loss()
+            self.colsum_ws = torch.empty(max(self.lib.gmp_colsum_workspace_bytes(self.N, H), 16), dtype=torch.uint8, device=dev)
+        else:
+            self.x = torch.zeros(self.N, self.dpad, device=dev)
+            self.x[:, :self.d_in] = x.to(dev)
+        self.csr = ops.csr_build(edge_index.to(dev).contiguous(), self.N)
+        self.seg_ptr[1:].fill_(self.N)
+        self._alloc_rows(self.N)
+
+
+class NodeClassificationEngine(FullGraphEngine):
+    def __init__(self, model: FinetuneGNN, x: Tensor, edge_index: Tensor, device, seed: int = 0) -> None:
+        super().__init__(model, x, edge_index, device, seed)
+        dev = self.device
+        self.classes = int(model.classification_head.mlp[0].weight.size(0))
+        self.logits = torch.empty(self.N, self.classes, device=dev)
+        self.loss_ws = torch.empty(self.lib.gmp_loss_workspace_bytes(self.N * H), dtype=torch.uint8, device=dev)
+        self.seed_word = torch.zeros(1, dtype=torch.int64, device=dev)        # device copy of step_count for captured steps (gmp_bn_config.seed_dev)
+        # GMP_FINETUNE_GRAPH=1: the step captured once and replayed (bitwise the numbers of the eager default, host 0.43 ms per replay,
+        # 0.95 ms per step on ONE chain: replaying a graph with a second branch costs the host 1.45 ms on this runtime -- ROCm 7.2,
+        # profiles/README.md round 3 -- so a captured step keeps its weight gradients in the chain unless GMP_FINETUNE_FORK says otherwise).
+        self.use_graph = dev.type == "cuda" and os.environ.get("GMP_FINETUNE_GRAPH", "0") == "1"
+        if self.use_graph and "GMP_FINETUNE_FORK" not in os.environ:
+            self.fork_wgrads = False
+        self._graph, self._graph_key, self._graph_step, self._graph_seen = None, None, -1, None
+        self._train_idx: Optional[Tensor] = None
+        self._step_args: Optional[Tuple[Tensor, Tensor]] = None  # (node_indices, targets) of the step being enqueued: _head_backward
+
+    def forward(self) -> Tensor:
+        self._head_logits(super().forward())
+        return self.logits
+
+    def _head_logits(self, hL: Tensor) -> None:
+        self._gemm(torch.cuda.current_stream(self.device).cuda_stream, NT, hL.data_ptr(), self._P("classification_head.mlp.0.weight"),
+                   self._P("classification_head.mlp.0.bias"), self.logits.data_ptr(), self.N, self.classes, H, H, H, self.classes)
+
+    def predict(self, node_indices: Tensor, targets: Optional[Tensor] = None) -> Tensor:
+        """Eval-mode logits [len(node_indices), C] of the given nodes; with targets, loss() then returns their mean cross-entropy.
+        Changes nothing a training step reads: parameters, optimizer state, running statistics, counters and the captured step stay as they are."""
+        self._head_logits(self._infer_forward())
+        with torch.no_grad():
+            rows = OP.take_rows(self.logits, node_indices)
+            self._infer_loss = None
+            if targets is not None:
+                self._infer_loss = (ops.cross_entropy_sum_fwd(rows, targets.contiguous()), int(node_indices.numel()))
+        return rows
+
+    # ------------------------------------------------------------------ one optimisation step (finetune.py:162-179 + 318-320)
+    def step(self, node_indices: Tensor, targets: Tensor, apply_update: bool = True) -> None:
+        """loss = cross_entropy(model(data)[node_indices], targets) (mean); backward; AdamW.  Nothing is read back: loss().
+        Training steps with an update are replayed from a hipGraph captured at the first such call for these index tensors."""
+        self._infer_loss, self._step_args = None, (node_indices, targets)
+        if not (self.use_graph and apply_update and self.model.training):
+            self._enqueue(apply_update, forked=self.fork_wgrads)
+            self.step_count += 1
+            return
+        key = (node_indices.data_ptr(), targets.data_ptr(), int(node_indices.numel()))
+        if self._graph_key != key:
+            # an eager step first (it IS this call's step): code objects loaded, LDS attributes set, row buffers allocated -- nothing of
+            # that may happen inside a capture.  The capture itself (tens of ms) waits for the SECOND call with the same index tensors:
+            # a caller that builds fresh tensors per call never pays for it.
+            self._enqueue(True)
+            self.step_count += 1
+            if self._graph_seen != key:
+                self._graph_seen, self._graph_keep = key, (node_indices, targets)
+                return
+            torch.cuda.current_stream(self.device).synchronize()
+            graph = torch.cuda.CUDAGraph()
+            self._seed_dev = self.seed_word.data_ptr()
+            try:
+                with torch.cuda.graph(graph):
+                    self._enqueue(True, forked=self.fork_wgrads)
+                    self._chk(self.lib.gmp_counter_add(self.seed_word.data_ptr(), 1, torch.cuda.current_stream(self.device).cuda_stream), "seed word")
+            finally:
+                self._seed_dev = None
+            self._bn_calls -= 1                                     # (forward() counted the capture pass, which ran nothing)
+            self._graph, self._graph_key, self._graph_step = graph, key, -1
+            self._graph_keep = (node_indices, targets)             # the captured launches hold these pointers
+            return
+        if self._graph_step != self.step_count:                    # eager steps ran in between (evaluation does not count): resynchronise
+            self.seed_word.fill_(self.step_count)
+        self._graph.replay()
+        self._fwd_gen += 1
+        self.step_count += 1
+        self._graph_step = self.step_count
+        self._bn_calls += 1
+
+    def _head_backward(self, st: int) -> None:
+        """Loss and head of the step after forward(): d loss / d h[GNN_NUM_LAYERS] into gA (the backbone backward starts from it)."""
+        lib, N, P, Cn = self.lib, self.N, self._P, self.classes
+        node_indices, targets = self._step_args
+        M = int(node_indices.numel())
+        if self._train_idx is None or self._train_idx.numel() != M:
+            f = lambda *s: torch.empty(*s, device=self.device)
+            self._rows_logits, self._rows_g, self._rows_h, self._rows_gh = f(M, Cn), f(M, Cn), f(M, H), f(M, H)
+        self._train_idx, self.num_targets = node_indices, M
+        self.g_scale.fill_(1.0 / M)
+        idx, tgt, g = node_indices.data_ptr(), targets.data_ptr(), self.grad.data_ptr()
+        hL = self.h[GNN_NUM_LAYERS]
+        self._chk(lib.gmp_row_gather(self.logits.data_ptr(), idx, None, self._rows_logits.data_ptr(), M, N, Cn, st), "logit rows")
+        self._chk(lib.gmp_cross_entropy_sum_fwd(self._rows_logits.data_ptr(), tgt, M, Cn, self.loss_sum.data_ptr(), self.loss_ws.data_ptr(), self.loss_ws.numel(), st), "ce")
+        self._chk(lib.gmp_cross_entropy_sum_bwd(self._rows_logits.data_ptr(), tgt, M, Cn, self.g_scale.data_ptr(), self._rows_g.data_ptr(), st), "ce bwd")
+        # head: dW = g^T h[idx], db = colsum(g), g_h[idx] = g W  (only the M training rows carry a gradient)
+        self._chk(lib.gmp_row_gather(hL.data_ptr(), idx, None, self._rows_h.data_ptr(), M, N, H, st), "h rows")
+        self._chk(lib.gmp_gemm_f32_grouped(TN, self._rows_g.data_ptr(), self._rows_h.data_ptr(), None, g, 1, _i32([0, M]), None, None,
+                                           _i64([self._G("classification_head.mlp.0.weight")]), g, _i64([self._G("classification_head.mlp.0.bias")]),
+                                           Cn, H, 0, Cn, H, H, 1.0, 0, 0, None, 0, st), "head wgrad")
+        self._gemm(st, NN, self._rows_g.data_ptr(), P("classification_head.mlp.0.weight"), None, self._rows_gh.data_ptr(), M, H, Cn, Cn, H, H)
+        self.gA.zero_()
+        self._chk(lib.gmp_row_fill(self.gA.data_ptr(), idx, self._rows_gh.data_ptr(), M, N, H, 0, st), "scatter g_h")
+
+    def logits_of_step(self) -> Tensor:
+        """The last step's logits [len(node_indices), C] of its training rows (the engine's buffer: the next step overwrites it)."""
+        return self._rows_logits
+
+
 LP_SCORER_SITE = 40                 # dropout site of the scorer's hidden layer (the backbone's: 1 and 10-14)
 MINING_SITE_BASE = 100              # added to the backbone's sites in the mining pass: masks independent of the training forward's
 _LP_HEAD = "classification_head.predictor.mlp."
@@ -528,24 +555,22 @@ class LinkRanks(NamedTuple):
     logit: Tensor       # [Q] the true pair's logit (sigmoid of it is predict()'s probability)
 
 
-class LinkPredictionEngine(NodeClassificationEngine):
+class LinkPredictionEngine(FullGraphEngine):
     """One link-prediction fine-tune step (Cora_LP / CiteSeer_LP, src/finetune/finetune.py:181-211) as an explicit kernel sequence.
 
     The reference's training batch is: a no-grad train-mode embedding pass over the message-passing graph (train_pos) to mine hard
     negatives, a second full forward, the MLPLinkPredictor over [pos | neg], BCE (mean), backward, AdamW.  Here:
-      mining_forward()   the first pass -- the node engine's encoder + backbone launches with dropout sites MINING_SITE_BASE higher,
+      mining_forward()   the first pass -- the shared encoder + backbone launches with dropout sites MINING_SITE_BASE higher,
                          BatchNorm in batch statistics updating the running ones, counted in num_batches_tracked (twice per step, as on
                          the module path); LinkPredictionHardNegativeMiner runs on its output unchanged
       step(pos, neg)     the pairs into a preallocated buffer, the training forward, the fused scorer (gmp_lp_score_fwd: the [K, 768]
                          features never leave LDS), gmp_sigmoid_bce_sum_fwd_bwd, gmp_lp_score_bwd (head gradients straight into the flat
-                         buffer, per-pair g_hs / g_hd), csr_build + two segment_sums onto the nodes, then the node engine's backbone
+                         buffer, per-pair g_hs / g_hd), csr_build + two segment_sums onto the nodes, then the shared backbone
                          backward (side-stream fork, gates) and AdamW with the reference's groups.  Nothing is read back.
     The module stays the owner of the parameters (views into the flat buffer), so evaluation and checkpoints go through it."""
 
     def __init__(self, model: FinetuneGNN, x: Tensor, message_passing_edges: Tensor, device, seed: int = 0, max_pairs: int = 512) -> None:
         super().__init__(model, x, message_passing_edges, device, seed)
-        self.use_graph = False              # the pair list changes every step: no captured replay
-        self.kmax, self.num_targets = 0, 0
         self._pairs: Optional[Tensor] = None
         self._grow(max_pairs)
 
@@ -565,13 +590,7 @@ class LinkPredictionEngine(NodeClassificationEngine):
         self.pair_csr = [i32(N + 1), i32(kmax), i32(kmax), i32(N + 1), i32(kmax), i32(kmax), i32(1)]
         self.pair_csr_ws = ws(lib.gmp_csr_build_workspace_bytes(N, kmax))
 
-    # ------------------------------------------------------------------ forward: encoder + backbone only (the scorer runs in the step)
-    def forward(self) -> Tensor:
-        self._backbone_forward()
-        if self.model.training:
-            self._bn_calls += 1
-        return self.h[GNN_NUM_LAYERS]
-
+    # ------------------------------------------------------------------ forward: the base's, encoder + backbone only (the scorer runs in the step)
     def mining_forward(self) -> Tensor:
         """The reference's no-grad embedding pass (finetune.py:181-190) in the model's mode.  Returns the engine's own [N, 256] buffer: the
         next forward overwrites it."""
@@ -599,12 +618,13 @@ class LinkPredictionEngine(NodeClassificationEngine):
         if Q:
             self.labels[P_:K].fill_(0.0)
         self._pairs, self.num_targets = pairs, K
-        self._enqueue(pairs, self.labels, apply_update, forked=self.fork_wgrads)
+        self._enqueue(apply_update, forked=self.fork_wgrads)
         self.step_count += 1
 
-    def _head_backward(self, pairs: Tensor, labels: Tensor, st: int) -> None:
+    def _head_backward(self, st: int) -> None:
         """Scorer, loss and their backward after forward(): d loss / d h[GNN_NUM_LAYERS] into gA."""
         lib, N, P, g = self.lib, self.N, self._P, self.grad.data_ptr()
+        pairs, labels = self._pairs, self.labels
         K = int(pairs.size(1))
         src, dst = pairs.data_ptr(), pairs.data_ptr() + 8 * K
         p = self.dropout_p if self.model.training else 0.0
@@ -638,11 +658,7 @@ class LinkPredictionEngine(NodeClassificationEngine):
         K = int(edges.size(1))
         if K == 0:
             raise ValueError("LinkPredictionEngine.predict: no pairs")
-        hL = self.embed() if embeddings is None else embeddings
-        if hL.data_ptr() != self.h[GNN_NUM_LAYERS].data_ptr() or hL.size(0) != self.N:
-            raise ValueError("LinkPredictionEngine.predict: embeddings must be the result of this engine's embed()")
-        if self._embed_gen != self._fwd_gen:
-            raise ValueError("LinkPredictionEngine.predict: a forward or a step has overwritten these embeddings since embed() returned them")
+        hL = self._embeddings("predict", embeddings)
         if K > self.kmax:
             self._grow(max(K, 2 * self.kmax))
         lib, P, st = self.lib, self._P, torch.cuda.current_stream(self.device).cuda_stream
@@ -660,14 +676,18 @@ class LinkPredictionEngine(NodeClassificationEngine):
         self._infer_loss = (loss_sum, K)
         return probs
 
-    def _ranking_inputs(self, who: str, embeddings: Optional[Tensor], filter_edges: Optional[Tensor]):
-        """The embeddings under predict()'s rules, the scorer's weights and the filter's source-major CSR (cached per tensor)."""
+    def _embeddings(self, who: str, embeddings: Optional[Tensor]) -> Tensor:
+        """embed() if none are given; given ones must be this engine's, and no forward may have overwritten them since."""
         hL = self.embed() if embeddings is None else embeddings
         if hL.data_ptr() != self.h[GNN_NUM_LAYERS].data_ptr() or hL.size(0) != self.N:
             raise ValueError(f"LinkPredictionEngine.{who}: embeddings must be the result of this engine's embed()")
         if self._embed_gen != self._fwd_gen:
             raise ValueError(f"LinkPredictionEngine.{who}: a forward or a step has overwritten these embeddings since embed() returned them")
-        mlp = self.model.classification_head.predictor.mlp
+        return hL
+
+    def _ranking_inputs(self, who: str, embeddings: Optional[Tensor], filter_edges: Optional[Tensor]):
+        """The embeddings under predict()'s rules, the scorer's weights and the filter's source-major CSR (cached per tensor)."""
+        hL, mlp = self._embeddings(who, embeddings), self.model.classification_head.predictor.mlp
         return hL, (mlp[0].weight, mlp[0].bias, mlp[3].weight, mlp[3].bias), None if filter_edges is None else filter_edges.to(self.device)
 
     def rank(self, edges: Tensor, filter_edges: Optional[Tensor] = None, embeddings: Optional[Tensor] = None) -> "LinkRanks":
@@ -692,10 +712,6 @@ class LinkPredictionEngine(NodeClassificationEngine):
         return idx, ops.sigmoid_fwd(logit.view(-1)).view_as(logit)
 
     # ------------------------------------------------------------------ read-backs
-    def loss(self) -> float:
-        """Mean BCE of the last step (synchronises; checks the gate and slab time-out words like the node engine)."""
-        return super().loss()
-
     def probabilities(self) -> Tensor:
         """sigmoid(logit) of the last step's pairs, [pos | neg] order."""
         return self.probs[:self.num_targets]
@@ -708,19 +724,19 @@ GC_HEAD_SITE = 41                   # dropout site of the graph-classification h
 _GC_HEAD = "classification_head.mlp."
 
 
-class GraphClassificationEngine(NodeClassificationEngine):
+class GraphClassificationEngine(BackboneEngine):
     """One graph-classification fine-tune step (ENZYMES / PTC_MR, src/finetune/finetune.py:136-158 + 283-331) as an explicit kernel sequence.
 
     The reference's training batch is 32 graphs (about 1,000 rows for ENZYMES, 450 for PTC_MR): forward, global_mean_pool, the
     256 -> 128 -> C head, cross-entropy (C > 2) or BCE-with-logits on logits[:, 1] (C == 2), backward, AdamW.  The batch -- and with it the
-    number of rows, edges and graphs -- changes every step, so unlike the node engine this one works on CAPACITIES:
+    number of rows, edges and graphs -- changes every step, so unlike the full-graph engines this one works on CAPACITIES:
       buffers            activations, gradients, the CSR and the workspaces are sized for max_nodes / max_edges / max_graphs and regrown by
                          doubling when a batch exceeds them (_alloc); every row-major buffer has leading dimension 256 / 512, so a step
                          uses its first N rows and rows a larger previous batch left behind are never read
       step(batch)        the batch's x into the padded [N, dpad] input (the padding columns stay zero), gmp_csr_build on the device into the
-                         preallocated CSR, seg_ptr = [0, N], the node engine's backbone forward, the fused head (gmp_gc_head_fwd: pooling,
+                         preallocated CSR, seg_ptr = [0, N], the shared backbone forward, the fused head (gmp_gc_head_fwd: pooling,
                          both layers, the loss and d loss / d logits in one kernel + the loss sum), gmp_gc_head_bwd (head gradients straight
-                         into the flat buffer, every row of d loss / d h written), then the node engine's backbone backward (side-stream
+                         into the flat buffer, every row of d loss / d h written), then the shared backbone backward (side-stream
                          fork, gates) and AdamW.  Nothing is read back; no captured replay (shapes change every step).
     Which tensors train comes from the model (requires_grad as FinetuneGNN set it: the encoder is frozen for ENZYMES, the backbone for
     linear_probe), the learning rates are those of FinetuneGNN.param_groups.  A frozen tensor is never touched by the optimizer -- no update,
@@ -731,31 +747,21 @@ class GraphClassificationEngine(NodeClassificationEngine):
     module path, 0.88 against 2.98 at the PTC_MR shape; about 120 launches per step, host-bound."""
 
     def __init__(self, model: FinetuneGNN, device, seed: int = 0, max_nodes: int = 2048, max_edges: int = 8192, max_graphs: int = 64) -> None:
-        d_in = int(model.input_encoder.linear.weight.size(1))
-        # the node engine's set-up (flat buffer, streams, gates, optimizer state) on a one-row placeholder graph; _alloc sizes the rest
-        super().__init__(model, torch.zeros(1, d_in), torch.zeros(2, 1, dtype=torch.long), device, seed)
-        self.use_graph = False              # N, E and B change every step: no captured replay
-        del self.logits                     # (the node engine's [N, classes] buffer: here logits() is the last step's [B, C])
+        super().__init__(model, int(model.input_encoder.linear.weight.size(1)), device, seed)
         self.classes = int(model.classification_head.mlp[3].weight.size(0))
-        self.B, self.num_targets = 0, 0
-        self._ptr32: Optional[Tensor] = None
+        self.B, self._unlabelled = 0, False
+        self._ptr32: Optional[Tensor] = None                     # the loaded batch's graph offsets; None: no batch loaded yet
         self._y: Optional[Tensor] = None
         self._alloc(max(int(max_nodes), 1), max(int(max_edges), 1), max(int(max_graphs), 1))
 
     def _alloc(self, cap_n: int, cap_e: int, cap_b: int) -> None:
-        dev, lib, Lr = self.device, self.lib, GNN_NUM_LAYERS
+        dev, lib = self.device, self.lib
         f = lambda *s: torch.empty(*s, device=dev)
         i32 = lambda n: torch.empty(n, dtype=torch.int32, device=dev)
         ws = lambda n: torch.empty(max(int(n), 16), dtype=torch.uint8, device=dev)
         self.cap_n, self.cap_e, self.cap_b = cap_n, cap_e, cap_b
         self.x = torch.zeros(cap_n, self.dpad, device=dev)
-        self.z0, self.h = f(cap_n, H), [f(cap_n, H) for _ in range(Lr + 1)]
-        self.a, self.z1 = [f(cap_n, H) for _ in range(Lr)], [f(cap_n, 2 * H) for _ in range(Lr)]
-        self.r1, self.z2 = [f(cap_n, 2 * H) for _ in range(Lr)], [f(cap_n, H) for _ in range(Lr)]
-        self.gA, self.gB, self.ga, self.gW, self.gW2 = f(cap_n, H), f(cap_n, H), f(cap_n, H), f(cap_n, 2 * H), f(cap_n, 2 * H)
-        self.gu_l, self.gz1_l = [f(cap_n, H) for _ in range(Lr + 1)], [f(cap_n, 2 * H) for _ in range(Lr)]
-        self.rowdot = f(Lr, cap_n)
-        self.bn_ws = ws(lib.gmp_bn_workspace_bytes(cap_n, 2 * H, 1, cap_n))
+        self._alloc_rows(cap_n)
         self.csr = ops.CSR(i32(cap_n + 1), i32(cap_e), i32(cap_e), i32(cap_n + 1), i32(cap_e), i32(cap_e), cap_n, torch.zeros(1, dtype=torch.int32, device=dev))
         self.csr_ws = ws(lib.gmp_csr_build_workspace_bytes(cap_n, cap_e))
         self.pooled, self.act = f(cap_b, H), f(cap_b, self.model.classification_head.mlp[0].weight.size(0))
@@ -793,15 +799,17 @@ class GraphClassificationEngine(NodeClassificationEngine):
     def forward(self, batch=None) -> Tensor:
         """The backbone's output for `batch` (or for the batch already loaded) in the model's mode: the first N rows of the engine's own
         buffer, which the next forward overwrites."""
-        if batch is not None:
-            self._load(batch)
-        self._backbone_forward()
-        if self.model.training:
-            self._bn_calls += 1
-        return self.h[GNN_NUM_LAYERS][:self.N]
+        self._load_or_keep(batch)
+        return super().forward()[:self.N]
 
-    def evaluate(self, batch) -> Tensor:
-        """logits [B, C] of `batch` in the model's mode (forward + the fused head; loss() then holds the batch's mean loss)."""
+    def _load_or_keep(self, batch, need_y: bool = True) -> None:
+        if batch is not None:
+            self._load(batch, need_y)
+        elif self._ptr32 is None:
+            raise ValueError("GraphClassificationEngine: no batch has been loaded yet")
+
+    def evaluate(self, batch=None) -> Tensor:
+        """logits [B, C] of `batch` (or of the batch already loaded) in the model's mode (forward + the fused head; loss() then holds the batch's mean loss)."""
         self.forward(batch)
         self._head_forward(torch.cuda.current_stream(self.device).cuda_stream)
         return self.logits()
@@ -810,11 +818,8 @@ class GraphClassificationEngine(NodeClassificationEngine):
     def embed(self, batch=None) -> Tensor:
         """The backbone's eval-mode output rows [N, 256] for `batch` (or for the batch already loaded), whatever model.training is.  Loads the
         batch and regrows the capacities as step does; labels are not needed.  The engine's own buffer: the next forward overwrites it."""
-        if batch is not None:
-            self._load(batch, need_y=False)
-        out = self._infer_forward()[:self.N]
-        self._embed_gen = self._fwd_gen
-        return out
+        self._load_or_keep(batch, need_y=False)
+        return super().embed()
 
     def predict(self, batch) -> Tensor:
         """Eval-mode logits [B, C] of `batch` (the folded backbone + the fused head with p = 0).  With labels (batch.y) loss() then holds the
@@ -833,7 +838,7 @@ class GraphClassificationEngine(NodeClassificationEngine):
         """loss = classification_loss(model(batch), batch.y) (mean over the batch's graphs); backward; AdamW.  `batch` is the loader's Batch
         (x, edge_index, ptr32, y), moved to the device if it is not there yet."""
         self._load(batch)
-        self._enqueue(None, None, apply_update, forked=self.fork_wgrads)
+        self._enqueue(apply_update, forked=self.fork_wgrads)
         self.step_count += 1
 
     def _head_args(self):
@@ -851,7 +856,7 @@ class GraphClassificationEngine(NodeClassificationEngine):
                                       self.logits_b.data_ptr(), self.loss_sum.data_ptr(), self.g_logits.data_ptr(), p, seed, GC_HEAD_SITE,
                                       self.head_ws.data_ptr(), self.head_ws.numel(), st), "gc head")
 
-    def _head_backward(self, _unused_a, _unused_b, st: int) -> None:
+    def _head_backward(self, st: int) -> None:
         """Head, loss and their backward after forward(): d loss / d h[GNN_NUM_LAYERS] into every row of gA."""
         lib, P, g = self.lib, self._P, self.grad.data_ptr()
         p, seed = self._head_args()
@@ -864,9 +869,9 @@ class GraphClassificationEngine(NodeClassificationEngine):
 
     # ------------------------------------------------------------------ read-backs
     def loss(self) -> float:
-        """Mean loss of the last step (synchronises; checks the gate and slab time-out words like the node engine, and the CSR build's
+        """Mean loss of the last step (synchronises; checks the gate and slab time-out words as every engine does, and the CSR build's
         count of edge endpoints outside the batch)."""
-        if getattr(self, "_unlabelled", False):
+        if self._unlabelled:
             raise L.GnnmpError("fine-tune engine: the last predict had no labels (batch.y): there is no loss to report")
         v = super().loss()
         if int(self.csr.status.item()) != 0:

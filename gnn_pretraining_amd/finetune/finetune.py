@@ -244,27 +244,31 @@ def run_training(model: FinetuneGNN, optimizer, train_loader, device, epoch: int
                                                 probabilities, t0, model, device_metrics=cfg.device_metrics), global_step[0])
 
 
+def _log_engine_step(engine, m: Dict, epoch: int, step: int, t0: float, logger: JsonlLogger) -> None:
+    """What the three engine loops log beside their batch metrics m: the groups' learning rates, the gradient norm, progress and time."""
+    for pg in engine.model.param_groups:
+        m[f'train/lr/{pg["name"]}'] = pg["lr"]
+    m["train/gradients/model_grad_norm"] = float(engine.normsq.sqrt())
+    m["train/progress/epoch"], m["train/progress/step"] = epoch, step
+    m["train/system/time_per_step"] = time.time() - t0
+    logger.log(m, step)
+
+
 def run_training_node_engine(engine, train_loader, device, epoch: int, global_step: List[int], cfg: FinetuneConfig, logger: JsonlLogger) -> None:
     """run_training for the full-graph node-classification domains on the explicit-kernel step (finetune/engine.py): one
     engine.step per batch -- forward on all nodes, CE on the batch's nodes, backward, AdamW with the reference's parameter groups --
     with no autograd graph and nothing read back unless a log is being written."""
-    model = engine.model
-    model.train()
+    engine.model.train()
     for (_, node_indices, targets) in train_loader:
         t0 = time.time()
         global_step[0] += 1
         idx, tgt = node_indices.to(device), targets.to(device)
         engine.step(idx, tgt)
         if logger.f:
-            lg = engine._rows_logits.detach()
+            lg = engine.logits_of_step().detach()
             loss = torch.tensor(engine.loss())
             m = _batch_metrics_fn(cfg.device_metrics)(cfg.domain_name, tgt, lg.argmax(dim=1), torch.softmax(lg, dim=1), loss, "train")
-            for pg in model.param_groups:
-                m[f'train/lr/{pg["name"]}'] = pg["lr"]
-            m["train/gradients/model_grad_norm"] = float(engine.normsq.sqrt())
-            m["train/progress/epoch"], m["train/progress/step"] = epoch, global_step[0]
-            m["train/system/time_per_step"] = time.time() - t0
-            logger.log(m, global_step[0])
+            _log_engine_step(engine, m, epoch, global_step[0], t0, logger)
 
 
 def run_training_lp_engine(engine, train_loader, device, epoch: int, global_step: List[int], cfg: FinetuneConfig, miner,
@@ -272,8 +276,7 @@ def run_training_lp_engine(engine, train_loader, device, epoch: int, global_step
     """run_training for the link-prediction domains on the explicit-kernel step (finetune/engine.py LinkPredictionEngine): per batch the
     mining pass, the hard-negative miner on its output, then engine.step -- training forward, fused scorer, BCE, backward, AdamW with the
     reference's parameter groups -- with no autograd graph and nothing read back unless a log is being written."""
-    model = engine.model
-    model.train()
+    engine.model.train()
     edges = _train_edges(train_loader, device)
     for (_, pos_edges, _) in train_loader:
         t0 = time.time()
@@ -286,20 +289,14 @@ def run_training_lp_engine(engine, train_loader, device, epoch: int, global_step
             p, labels = engine.probabilities().detach(), engine.labels_of_step()
             loss = torch.tensor(engine.loss())
             m = _batch_metrics_fn(cfg.device_metrics)(cfg.domain_name, labels.long(), (p > 0.5).long(), torch.stack([1 - p, p], dim=1), loss, "train")
-            for pg in model.param_groups:
-                m[f'train/lr/{pg["name"]}'] = pg["lr"]
-            m["train/gradients/model_grad_norm"] = float(engine.normsq.sqrt())
-            m["train/progress/epoch"], m["train/progress/step"] = epoch, global_step[0]
-            m["train/system/time_per_step"] = time.time() - t0
-            logger.log(m, global_step[0])
+            _log_engine_step(engine, m, epoch, global_step[0], t0, logger)
 
 
 def run_training_gc_engine(engine, train_loader, device, epoch: int, global_step: List[int], cfg: FinetuneConfig, logger: JsonlLogger) -> None:
     """run_training for the graph-classification domains on the explicit-kernel step (finetune/engine.py GraphClassificationEngine): one
     engine.step per batch -- the batch's CSR, forward, fused pooling + head + loss, backward, AdamW with the reference's parameter groups --
     with no autograd graph and nothing read back unless a log is being written."""
-    model = engine.model
-    model.train()
+    engine.model.train()
     for batch in train_loader:
         t0 = time.time()
         global_step[0] += 1
@@ -309,12 +306,7 @@ def run_training_gc_engine(engine, train_loader, device, epoch: int, global_step
             lg = engine.logits().detach()
             loss = torch.tensor(engine.loss())
             m = _batch_metrics_fn(cfg.device_metrics)(cfg.domain_name, b.y, lg.argmax(dim=1), torch.softmax(lg, dim=1), loss, "train")
-            for pg in model.param_groups:
-                m[f'train/lr/{pg["name"]}'] = pg["lr"]
-            m["train/gradients/model_grad_norm"] = float(engine.normsq.sqrt())
-            m["train/progress/epoch"], m["train/progress/step"] = epoch, global_step[0]
-            m["train/system/time_per_step"] = time.time() - t0
-            logger.log(m, global_step[0])
+            _log_engine_step(engine, m, epoch, global_step[0], t0, logger)
 
 
 def evaluate(model: FinetuneGNN, loader, device, cfg: FinetuneConfig, prefix: str, miner, train_edges) -> List[Dict[str, float]]:

@@ -19,8 +19,9 @@ for fork in (False, True, False, True):
     eng.use_graph, eng.fork_wgrads = False, fork
     idx = torch.randperm(g.num_nodes, generator=gen)[:140].to(dev)
     y = g.y[idx.cpu()].to(dev)
+    eng._step_args = (idx, y)
     for _ in range(10):
-        eng._enqueue(idx, y, True, forked=fork)
+        eng._enqueue(True, forked=fork)
         eng.step_count += 1
     torch.cuda.synchronize()
     main = torch.cuda.current_stream(dev)
@@ -29,7 +30,7 @@ for fork in (False, True, False, True):
     a.record()
     t0 = time.perf_counter()
     for _ in range(reps):
-        eng._enqueue(idx, y, True, forked=fork)          # (step() forks only inside a capture)
+        eng._enqueue(True, forked=fork)          # (step() forks only inside a capture)
         eng.step_count += 1
     t1 = time.perf_counter()
     b.record()

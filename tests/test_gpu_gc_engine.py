@@ -277,3 +277,15 @@ def test_pretrain_then_graph_classification_finetune_on_the_engine(tmp_path, mon
                        data_scale=0.03, log_path=str(log))
     assert np.isfinite(test["test/accuracy"]) and 0.0 <= test["test/accuracy"] <= 1.0
     assert any('"train/' in line for line in log.read_text().splitlines()), "no training metrics logged"
+
+
+def test_an_engine_without_a_loaded_batch_refuses_forward_embed_and_evaluate(monkeypatch):
+    """Construction sets up no graph of its own (no placeholder, no csr_build), so there is nothing to run on until a batch is loaded."""
+    from gnn_pretraining_amd.finetune.engine import GraphClassificationEngine, NodeClassificationEngine
+    assert NodeClassificationEngine not in GraphClassificationEngine.__mro__
+    monkeypatch.setattr(ops, "csr_build", lambda *a, **k: pytest.fail("csr_build at construction"))
+    eng = GraphClassificationEngine(FinetuneGNN(DEV, "PTC_MR", "full_finetune"), DEV, max_nodes=8, max_edges=8, max_graphs=2)
+    for call in (eng.forward, eng.embed, eng.evaluate):
+        with pytest.raises(ValueError, match="no batch has been loaded"):
+            call()
+    assert eng._fwd_gen == 0                                  # (refused before anything was launched)

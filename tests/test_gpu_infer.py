@@ -408,9 +408,9 @@ def _snapshot(eng):
     eng.flush_counters()
     torch.cuda.synchronize()
     sd = {k: v.clone() for k, v in eng.model.state_dict().items() if "running_" in k or k.endswith("num_batches_tracked")}
+    capture = dict(seed_word=eng.seed_word.clone(), graph=eng._graph) if hasattr(eng, "seed_word") else {}   # the node engine's alone
     return dict(flat=eng.flat.clone(), grad=eng.grad.clone(), final_grad=eng.final_grad.clone(), exp_avg=eng.exp_avg.clone(),
-                exp_avg_sq=eng.exp_avg_sq.clone(), steps=eng.steps.clone(), seed_word=eng.seed_word.clone(), buffers=sd,
-                step_count=eng.step_count, bn_calls=eng._bn_calls, graph=eng._graph)
+                exp_avg_sq=eng.exp_avg_sq.clone(), steps=eng.steps.clone(), buffers=sd, step_count=eng.step_count, bn_calls=eng._bn_calls, **capture)
 
 
 def _assert_same(a, b, what):
