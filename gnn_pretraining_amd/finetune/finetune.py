@@ -3,7 +3,7 @@ miner, process_batch per task type, one AdamW step per batch over FinetuneGNN.pa
 test metrics from the best checkpoint.  Data come from the loaders of gnn_pretraining_amd/data (processed datasets in
 data/processed; synthetic stand-ins are generated when none were exported).  wandb is replaced by a JSONL logger with the
 same metric keys.  Build-only flags: --epochs, --device, --data-root, --data-scale, --log, --sparse-features, --lp-engine, --gc-engine,
---engine-eval, --lp-ranking, --device-metrics, --miner."""
+--engine-eval, --lp-ranking, --device-metrics, --miner, --knn-probe."""
 from __future__ import annotations
 
 import argparse
@@ -21,7 +21,8 @@ from .. import operators as O, ops
 from ..constants import NUM_CLASSES, TASK_TYPES
 from ..graph import SparseFeatures
 from ..models.finetune_model import FinetuneGNN, create_finetune_model
-from .metrics import compute_batch_metrics, compute_batch_metrics_device, compute_test_metrics, compute_training_metrics, compute_validation_metrics, ranking_metrics
+from .metrics import (compute_batch_metrics, compute_batch_metrics_device, compute_test_metrics, compute_training_metrics, compute_validation_metrics,
+                      knn_probe_accuracy, ranking_metrics)
 
 OUTPUT_DIR = Path(__file__).resolve().parents[2] / "outputs" / "finetune"
 BATCH_SIZES = {"ENZYMES": 32, "PTC_MR": 32, "Cora_NC": -1, "CiteSeer_NC": -1, "Cora_LP": 256, "CiteSeer_LP": 256}
@@ -102,6 +103,7 @@ class FinetuneConfig:
     lp_ranking: bool = False            # link prediction on the engine: the test pass also ranks every true test edge against all nodes (MRR, Hits@K)
     device_metrics: bool = False        # batch scores from integer counts made on the GPU (metrics.compute_batch_metrics_device), not scikit-learn on host copies
     miner_impl: str = "matrix"          # link-prediction domains: the hard-negative miner's top-k kernel (ops.hard_negative_topk impl), module path and lp_engine alike
+    knn_probe: int = 0                  # classification domains on an engine: k of the weighted k-NN probe on the backbone's embeddings (val/ and test/knn_accuracy); 0 = off
 
     def __post_init__(self) -> None:
         if self.sparse_features and TASK_TYPES[self.domain_name] == "graph_classification":
@@ -118,6 +120,14 @@ class FinetuneConfig:
             raise ValueError(f"engine_eval needs an active fine-tune engine for {self.domain_name}: "
                              + {"node_classification": "the node engine is switched off (GMP_FINETUNE_ENGINE=0)",
                                 "link_prediction": "pass lp_engine (--lp-engine)",
+                                "graph_classification": "pass gc_engine (--gc-engine)"}[TASK_TYPES[self.domain_name]])
+        if not 0 <= self.knn_probe <= ops.KNN_MAX_K:
+            raise ValueError(f"knn_probe={self.knn_probe} (the number of neighbours, 1 <= k <= {ops.KNN_MAX_K}; 0 switches the probe off)")
+        if self.knn_probe and TASK_TYPES[self.domain_name] == "link_prediction":
+            raise ValueError(f"knn_probe classifies nodes or graphs from labelled neighbours: {self.domain_name} has no class labels")
+        if self.knn_probe and not engine_active(self):
+            raise ValueError(f"knn_probe needs an active fine-tune engine for {self.domain_name} (it reads the engine's eval-mode embed()): "
+                             + {"node_classification": "the node engine is switched off (GMP_FINETUNE_ENGINE=0)",
                                 "graph_classification": "pass gc_engine (--gc-engine)"}[TASK_TYPES[self.domain_name]])
         if self.lp_ranking and not self.lp_engine:
             raise ValueError("lp_ranking ranks with the link-prediction engine (gmp_lp_rank): pass lp_engine (--lp-engine)")
@@ -350,6 +360,29 @@ def rank_test_edges(engine, train_loader, val_loader, test_loader, device) -> Di
     return {f"test/{k}": v for k, v in ranking_metrics(ranks).items()}
 
 
+def knn_probe(engine, train_loader, loader, device, cfg: FinetuneConfig) -> float:
+    """cfg.knn_probe: the accuracy of the weighted k-NN classifier (metrics.knn_probe_accuracy) that labels the rows of `loader`'s split
+    from the train split's, on the engine's eval-mode backbone output as the parameters stand now -- node embeddings for node
+    classification (one embed(), the two splits' rows gathered from it), mean-pooled graph embeddings for graph classification (one
+    embed(batch) per batch of the split taken in dataset order).  Reads the parameters and running statistics and draws nothing: no
+    generator, no dropout counter and no BatchNorm update is touched, so training goes on as without it."""
+    with torch.no_grad():
+        if cfg.task_type == "node_classification":
+            emb, y = engine.embed(), train_loader.dataset.data.y
+            sets = [(ops.row_gather(emb, ds.indices.to(device)), y[ds.indices].to(torch.long).to(device)) for ds in (train_loader.dataset, loader.dataset)]
+        else:
+            sets = []
+            for ds in (train_loader.dataset, loader.dataset):
+                pooled, labels = [], []
+                for s in range(0, len(ds), max(cfg.batch_size, 1)):
+                    b = ds.collate(torch.arange(s, min(s + max(cfg.batch_size, 1), len(ds)))).to(device)
+                    pooled.append(O.global_mean_pool(engine.embed(b), b.batch, ptr32=b.ptr32))
+                    labels.append(b.y.to(torch.long))
+                sets.append((torch.cat(pooled), torch.cat(labels)))
+        (db, db_y), (q, q_y) = sets
+        return knn_probe_accuracy(db, db_y, q, q_y, NUM_CLASSES[cfg.domain_name], cfg.knn_probe)["accuracy"]
+
+
 def finetune(cfg: FinetuneConfig, epochs: Optional[int] = None, device: Optional[str] = None,
              data_root: Optional[str] = None, data_scale: float = 1.0, log_path: Optional[str] = None) -> Dict[str, float]:
     """finetune.py:334-445.  Returns the test metrics of the best-validation checkpoint."""
@@ -404,6 +437,9 @@ def finetune(cfg: FinetuneConfig, epochs: Optional[int] = None, device: Optional
         eval_engine = node_engine or lp_engine or gc_engine
         if eval_engine is None:
             raise ValueError(f"engine_eval needs an active fine-tune engine for {cfg.domain_name}")
+    probe_engine = (node_engine or gc_engine) if cfg.knn_probe else None
+    if probe_engine is not None:                             # the embeddings before any training
+        logger.log({"val/knn_accuracy": knn_probe(probe_engine, train_loader, val_loader, dev, cfg)}, 0)
     for epoch in range(1, (epochs or cfg.epochs) + 1):
         if node_engine is not None:
             run_training_node_engine(node_engine, train_loader, dev, epoch, global_step, cfg, logger)
@@ -421,6 +457,8 @@ def finetune(cfg: FinetuneConfig, epochs: Optional[int] = None, device: Optional
             val = compute_validation_metrics(evaluate_engine(eval_engine, val_loader, dev, cfg, "val"), epoch)
         else:
             val = compute_validation_metrics(evaluate(model, val_loader, dev, cfg, "val", miner, edges), epoch)
+        if probe_engine is not None:
+            val["val/knn_accuracy"] = knn_probe(probe_engine, train_loader, val_loader, dev, cfg)
         if val[key] > best:
             best, stale = val[key], 0
             torch.save({"epoch": epoch, "model_state_dict": model.state_dict(), "val_metrics": val}, path)
@@ -435,6 +473,8 @@ def finetune(cfg: FinetuneConfig, epochs: Optional[int] = None, device: Optional
     else:
         test_batches = evaluate(model, test_loader, dev, cfg, "test", miner, _train_edges(train_loader, dev))
     test = compute_test_metrics(test_batches, epoch, stale, start, model)
+    if probe_engine is not None:
+        test["test/knn_accuracy"] = knn_probe(probe_engine, train_loader, test_loader, dev, cfg)
     if cfg.lp_ranking:
         test.update(rank_test_edges(lp_engine, train_loader, val_loader, test_loader, dev))
     logger.log(test, global_step[0])
@@ -463,6 +503,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--miner", choices=list(ops.MINER_IMPLS), default="matrix",
                    help="Cora_LP / CiteSeer_LP: the hard-negative miner's top-k kernel: matrix (n x n similarity in the workspace, n <= 65535), "
                         "stream (tiles recomputed, workspace O(n d + E), n <= 2^20), auto (stream beyond 65535 nodes)")
+    p.add_argument("--knn-probe", type=int, default=0, metavar="K",
+                   help="classification domains on an engine: also log val/knn_accuracy (every epoch and once before training) and test/knn_accuracy, "
+                        "the weighted k-NN classifier (K neighbours, 1..64, cosine, T = 0.07) on the backbone's embeddings; 0 = off")
     return p
 
 
@@ -470,7 +513,8 @@ def config_from_args(a: argparse.Namespace) -> FinetuneConfig:
     return FinetuneConfig(a.domain_name, a.finetune_strategy, a.pretrained_scheme, a.seed, sparse_features=a.sparse_features,
                           lp_engine=getattr(a, "lp_engine", False), gc_engine=getattr(a, "gc_engine", False),
                           engine_eval=getattr(a, "engine_eval", False), lp_ranking=getattr(a, "lp_ranking", False),
-                          device_metrics=getattr(a, "device_metrics", False), miner_impl=getattr(a, "miner", "matrix"))
+                          device_metrics=getattr(a, "device_metrics", False), miner_impl=getattr(a, "miner", "matrix"),
+                          knn_probe=getattr(a, "knn_probe", 0))
 
 
 def main() -> None:

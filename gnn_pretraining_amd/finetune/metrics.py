@@ -112,6 +112,23 @@ def compute_batch_metrics_device(domain_name: str, targets: Tensor, predictions:
     return m
 
 
+def knn_probe_accuracy(db_emb: Tensor, db_labels: Tensor, query_emb: Tensor, query_labels: Tensor, num_classes: int, k: int = 20,
+                       temperature: float = 0.07) -> Dict:
+    """The weighted k-NN probe of Wu et al. 2018 (InstDisc; also DINO's): every query embedding is classified from its k nearest
+    labelled database embeddings in cosine similarity, each voting exp(similarity / temperature) for its class (ops.knn_topk +
+    ops.knn_vote: csrc/knn.hip, no nq x ndb matrix).  Embeddings fp32 [n, d <= 256] and labels int64 [n] on the GPU.  Returns
+    {"accuracy": correct / num_samples, "correct", "num_samples"}: the accuracy is a ratio of two integers counted on the device
+    (one read-back).  Needs no trained head; nothing here feeds back into training."""
+    from .. import ops
+    idx, sim = ops.knn_topk(query_emb.detach().contiguous(), db_emb.detach().contiguous(), k)
+    _, pred = ops.knn_vote(idx, sim, db_labels.to(torch.int64).contiguous(), num_classes, temperature)
+    n = int(query_labels.numel())
+    if n == 0:
+        raise ValueError("knn_probe_accuracy: no queries")
+    correct = int((pred == query_labels.to(torch.int64)).sum().item())
+    return {"accuracy": correct / n, "correct": correct, "num_samples": n}
+
+
 def compute_training_metrics(epoch: int, step: int, loss: Tensor, optimizer: torch.optim.Optimizer, domain_name: str,
                              targets: Tensor, predictions: Tensor, probabilities: Tensor, step_start_time: float,
                              model: torch.nn.Module, device_metrics: bool = False) -> Dict[str, float]:

@@ -1134,7 +1134,58 @@ def lp_topk(h: Tensor, src: Tensor, k: int, w0: Tensor, b0: Tensor, w3: Tensor, 
     return idx, logit
 
 
-CLS_MAX_ROWS, CLS_MAX_CLASSES = 262144, 32        # gmp_cls_counts: the pair count is n^2 compares (gnnmp.h)
+KNN_MAX_K, KNN_MAX_DIM, KNN_MAX_CLASSES = 64, 256, 32       # gmp_knn_topk / gmp_knn_vote (gnnmp.h)
+
+
+def knn_topk(queries: Tensor, database: Tensor, k: int, exclude_self: bool = False, return_matrix: bool = False):
+    """The k (1 <= k <= 64) nearest database rows of every query row in cosine similarity (gnnmp.h gmp_knn_topk; csrc/knn.hip): returns
+    (idx [nq, k] int64, sim [nq, k]), similarity descending, ties to the lower database index, -1 / -inf behind a query's last candidate.
+    queries [nq, d] and database [ndb, d] fp32 contiguous, 1 <= d <= 256.  Nothing of size nq x ndb is allocated unless return_matrix asks
+    for the similarity matrix as the selection saw it (a third result, tests only).  exclude_self: leave-one-out over one set -- queries
+    and database must be the same tensor; row i never returns i."""
+    _need(queries, torch.float32, "queries", 2); _need(database, torch.float32, "database", 2)
+    nq, d = queries.shape
+    ndb = database.size(0)
+    if database.size(1) != d or database.device != queries.device:
+        raise L.GnnmpError(f"knn_topk: queries {tuple(queries.shape)} on {queries.device}, database {tuple(database.shape)} on {database.device}")
+    if not 1 <= int(k) <= KNN_MAX_K or not 1 <= d <= KNN_MAX_DIM:
+        raise L.GnnmpError(f"knn_topk: k={k} dim={d} (1 <= k <= {KNN_MAX_K}, 1 <= dim <= {KNN_MAX_DIM})")
+    if exclude_self and (queries.data_ptr() != database.data_ptr() or nq != ndb):
+        raise L.GnnmpError("knn_topk: exclude_self is leave-one-out over one set: pass the same tensor as queries and as database")
+    dev, l = queries.device, L.lib()
+    idx, sim = torch.empty(nq, k, dtype=torch.int64, device=dev), torch.empty(nq, k, device=dev)
+    mat = torch.empty(nq, ndb, device=dev) if return_matrix else None
+    ws = _ws(l.gmp_knn_workspace_bytes(nq, ndb, d, int(k)), dev)
+    L.check(l.gmp_knn_topk(_ptr(queries), nq, _ptr(database), ndb, d, int(k), int(bool(exclude_self)), _ptr(idx), _ptr(sim), _ptr(mat),
+                           _ptr(ws), ws.numel(), _stream(queries)), "gmp_knn_topk")
+    return (idx, sim, mat) if return_matrix else (idx, sim)
+
+
+def knn_vote(idx: Tensor, sim: Tensor, labels: Tensor, num_classes: int, temperature: float = 0.07) -> Tuple[Tensor, Tensor]:
+    """The weighted k-NN vote of Wu et al. 2018 on knn_topk's (idx, sim) (gnnmp.h gmp_knn_vote): class_scores [nq, C] with [q, c] = the
+    sum over q's neighbours r, in order, of exp(sim[q, r] / temperature) where labels[idx[q, r]] == c, and pred [nq] int64 = the argmax
+    (ties to the lower class, -1 for a query without neighbours).  labels int64 [ndb].  Raises when a neighbour's label lies outside
+    [0, num_classes) (one read-back of the status word)."""
+    _need(idx, torch.int64, "idx", 2); _need(sim, torch.float32, "sim", 2); _need(labels, torch.int64, "labels", 1)
+    nq, k = idx.shape
+    if tuple(sim.shape) != (nq, k) or sim.device != idx.device or labels.device != idx.device:
+        raise L.GnnmpError(f"knn_vote: idx {tuple(idx.shape)} on {idx.device}, sim {tuple(sim.shape)} on {sim.device}, labels on {labels.device}")
+    if not 1 <= k <= KNN_MAX_K or not 2 <= int(num_classes) <= KNN_MAX_CLASSES or not float(temperature) > 0.0:
+        raise L.GnnmpError(f"knn_vote: k={k} num_classes={num_classes} temperature={temperature} "
+                           f"(1 <= k <= {KNN_MAX_K}, 2 <= num_classes <= {KNN_MAX_CLASSES}, temperature > 0)")
+    dev = idx.device
+    scores = torch.empty(nq, int(num_classes), device=dev)
+    pred = torch.empty(nq, dtype=torch.int64, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    L.check(L.lib().gmp_knn_vote(_ptr(idx), _ptr(sim), nq, k, _ptr(labels), labels.numel(), int(num_classes), float(temperature), _ptr(scores),
+                                 _ptr(pred), _ptr(status), _stream(idx)), "gmp_knn_vote")
+    bad = int(status.item())
+    if bad:
+        raise L.GnnmpError(f"knn_vote: {bad} neighbours have a label outside [0, {num_classes})")
+    return scores, pred
+
+
+CLS_MAX_ROWS, CLS_MAX_CLASSES = 262144, 32       # gmp_cls_counts: the pair count is n^2 compares (gnnmp.h)
 
 
 def cls_counts_packed(targets: Tensor, predictions: Tensor, probabilities: Tensor) -> Tensor:

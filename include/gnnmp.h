@@ -347,6 +347,34 @@ int gmp_lp_topk(const float* h, const int64_t* src, int64_t num_nodes, int64_t n
                 gmp_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
+ * Streaming k-nearest neighbours in cosine similarity and the weighted k-NN vote on top of them (the k-NN probe of Wu et al. 2018 for
+ * self-supervised embeddings): q [nq, dim] queries against db [ndb, dim] database rows, both contiguous fp32.  Rows are normalised as the
+ * hard-negative miner does, z / max(||z||, 1e-12) with the stride padded with zeros, so a zero row scores 0 against everything and never
+ * gives NaN.  The similarity of a (query, database row) pair is one k-ordered fp32 MFMA chain (csrc/sim_tile.h): its bits depend on
+ * neither the grid nor the other rows.  No [nq, ndb] array exists unless matrix_out is given.
+ * gmp_knn_topk, for 1 <= k <= 64: idx [nq, k] int64 and sim [nq, k], per query the k best database rows, similarity descending, ties to
+ *   the lower database index (a total order); a query with fewer than k candidates is padded with -1 / -inf.
+ *   exclude_self != 0 leaves out j == i (leave-one-out over one set) and requires q == db and nq == ndb, GMP_ERR_ARG otherwise.
+ *   matrix_out: NULL or [nq, ndb], every similarity exactly as the selection saw it (the diagonal included) -- test / diagnostic hook.
+ *   1 <= dim <= 256, 1 <= nq, ndb < 2^31; nq == 0 is a no-op and ndb == 0 writes the -1 / -inf tail alone, both GMP_OK.  GMP_ERR_ARG
+ *   outside those ranges, GMP_ERR_WORKSPACE when workspace_bytes < gmp_knn_workspace_bytes(nq, ndb, dim, k); nothing is launched then.
+ *   gmp_knn_workspace_bytes = 4 (nq + ndb) dpad + 8 nq parts k + a constant below 1 KiB, dpad = dim rounded up to 4: the two normalised
+ *   copies and per query `parts` lists of k 64-bit keys; the database is cut into parts (at most 16) only while nq <= 32,640, so beyond
+ *   that it is 4 (nq + ndb) dpad + 8 nq k (2.5 GiB at nq = ndb = 2^20, dim = 256, k = 64).  0 for sizes outside the ranges.
+ *   Asynchronous on `stream`, no host read-back, no allocation, integer compares only: the output is a pure function of the input.
+ * gmp_knn_vote, on idx / sim [nq, k] as gmp_knn_topk returns them and db_labels [ndb] int64: class_scores [nq, classes] with
+ *   class_scores[q, c] = the sum over r = 0 .. k-1, in that order and in fp32, of exp(sim[q, r] / temperature) where idx[q, r] >= 0 and
+ *   db_labels[idx[q, r]] == c; pred [nq] int64 = the argmax, ties to the lower class, -1 for a query without a valid neighbour.
+ *   status int32 [1] (zeroed inside the call) counts the neighbours whose label lies outside [0, classes) or whose index lies outside
+ *   [0, ndb); those are skipped.  1 <= k <= 64, 2 <= classes <= 32, temperature > 0 (GMP_ERR_ARG otherwise).
+ * ------------------------------------------------------------------------- */
+size_t gmp_knn_workspace_bytes(int64_t nq, int64_t ndb, int dim, int k);
+int gmp_knn_topk(const float* q, int64_t nq, const float* db, int64_t ndb, int dim, int k, int exclude_self, int64_t* idx, float* sim,
+                 float* matrix_out, void* workspace, size_t workspace_bytes, gmp_stream_t stream);
+int gmp_knn_vote(const int64_t* idx, const float* sim, int64_t nq, int k, const int64_t* db_labels, int64_t ndb, int classes,
+                 float temperature, float* class_scores, int64_t* pred, int32_t* status, gmp_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
  * Integer counts for the classification metrics of fine-tuning (src/finetune/metrics.py:39-82: accuracy, F1, precision, recall and the
  * one-vs-rest ROC AUC of scikit-learn), from targets [n] int64, predictions [n] int64 and probabilities [n, classes] fp32 contiguous:
  *   confusion  int64 [classes * classes]  entry [t * classes + p] = rows with target t and prediction p
