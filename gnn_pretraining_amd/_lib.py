@@ -127,6 +127,10 @@ _SIGS: Dict[str, tuple] = {
     "gmp_knn_workspace_bytes": (sz, [i64, i64, i32, i32]),
     "gmp_knn_topk": (C.c_int, [p, i64, p, i64, i32, i32, i32, p, p, p, p, sz, p]),
     "gmp_knn_vote": (C.c_int, [p, p, i64, i32, p, i64, i32, f32, p, p, p, p]),
+    "gmp_kmeans_workspace_bytes": (sz, [i64, i32, i32]),
+    "gmp_kmeans_assign": (C.c_int, [p, i64, p, i32, i32, p, p, p, p, sz, p]),
+    "gmp_kmeans_fit": (C.c_int, [p, i64, p, i32, i32, i32, p, p, p, p, p, sz, p]),
+    "gmp_contingency": (C.c_int, [p, p, i64, i32, i32, p, p, p]),
     "gmp_cls_counts_workspace_bytes": (sz, [i64, i32]),
     "gmp_cls_counts": (C.c_int, [p, p, p, i64, i32, p, p, p, p, sz, p]),
     "gmp_graph_props_workspace_bytes": (sz, [i32, i64]),

@@ -43,14 +43,17 @@ __device__ __forceinline__ float4 lds_f4(lds_row_ptr p, int i) {
 
 // NV = float4 per lane (F <= 256*NV).  SELF: out = scale*self + sum.  DOT: also write
 // rowdot[r] = <self[r], dotx[r]> (eps gradient, reduced per task afterwards).  ADDEND: out += addend[r]
-// (the residual branch's gradient joins the aggregation's in the same pass).
-template <int NV, bool SELF, bool IDX, bool MEAN, bool ACCUM, bool DOT, bool ADDEND = false>
+// (the residual branch's gradient joins the aggregation's in the same pass).  GATED: the kernel begins with a plain load of *gate and
+// returns when it reads 0 (gmp::seg_sum_gated, the k-means loop's early exit); the other instantiations never touch the pointer.
+template <int NV, bool SELF, bool IDX, bool MEAN, bool ACCUM, bool DOT, bool ADDEND = false, bool GATED = false>
 __global__ __launch_bounds__(BLOCK) void seg_sum_kernel(const float4* __restrict__ src, const int* __restrict__ ptr,
                                                         const int* __restrict__ idx, const float4* __restrict__ self,
                                                         const float* __restrict__ eps, const float4* __restrict__ dotx,
                                                         float4* __restrict__ out, float* __restrict__ rowdot,
                                                         int64_t nrows, int F4, int rows_per_wave,
-                                                        const float4* __restrict__ addend = nullptr) {
+                                                        const float4* __restrict__ addend = nullptr,
+                                                        const int* __restrict__ gate = nullptr) {
+    if (GATED && *gate == 0) return;
     // XCD-aware: hardware deals blocks round-robin over 8 XCDs; give XCD k the k-th
     // contiguous eighth of the chunk space (gridDim.x is a multiple of 8).
     __builtin_amdgcn_s_setprio(3);
@@ -363,14 +366,14 @@ Plan make_plan(int64_t nrows) {
     return Plan{(int)blocks, (int)rpw};
 }
 
-template <bool SELF, bool IDX, bool MEAN, bool ACCUM, bool DOT, bool ADDEND = false>
+template <bool SELF, bool IDX, bool MEAN, bool ACCUM, bool DOT, bool ADDEND = false, bool GATED = false>
 int launch_nv(int nv, const Plan& p, hipStream_t st, const float* src, const int* ptr, const int* idx,
               const float* self, const float* eps, const float* dotx, float* out, float* partials, int64_t nrows,
-              int F4, const float* addend = nullptr) {
+              int F4, const float* addend = nullptr, const int* gate = nullptr) {
 #define GMP_LAUNCH_NV(NV)                                                                                       \
-    hipLaunchKernelGGL((seg_sum_kernel<NV, SELF, IDX, MEAN, ACCUM, DOT, ADDEND>), dim3(p.grid), dim3(BLOCK), 0, st, \
+    hipLaunchKernelGGL((seg_sum_kernel<NV, SELF, IDX, MEAN, ACCUM, DOT, ADDEND, GATED>), dim3(p.grid), dim3(BLOCK), 0, st, \
                        (const float4*)src, ptr, idx, (const float4*)self, eps, (const float4*)dotx, (float4*)out, \
-                       partials, nrows, F4, p.rows_per_wave, (const float4*)addend)
+                       partials, nrows, F4, p.rows_per_wave, (const float4*)addend, gate)
     switch (nv) {
         case 1: GMP_LAUNCH_NV(1); break;
         case 2: GMP_LAUNCH_NV(2); break;
@@ -426,6 +429,13 @@ int check_feat(const char* who, int feat) {
 }
 
 }  // namespace
+
+int gmp::seg_sum_gated(const float* src, const int* ptr, const int* idx, float* out, int64_t nrows, int feat, const int* gate, hipStream_t st) {
+    if (int rc = check_feat("seg_sum_gated", feat)) return rc;
+    const int F4 = feat / 4;
+    return launch_nv<false, true, false, false, false, false, true>((F4 + 63) / 64, make_plan(nrows), st, src, ptr, idx, nullptr, nullptr, nullptr, out,
+                                                                    nullptr, nrows, F4, nullptr, gate);
+}
 
 extern "C" int gmp_gin_aggregate_fwd(const float* x, const int32_t* rowptr, const int32_t* col, const float* eps,
                                      float* out, int64_t N, int feat, gmp_stream_t stream) {

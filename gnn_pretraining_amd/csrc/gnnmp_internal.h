@@ -119,6 +119,11 @@ __device__ __forceinline__ void normalize_row(const float* __restrict__ src, int
 // out[0] = sum of v[0, n) in a fixed order, one workgroup (ntxent.hip)
 void sum_rows(const float* v, int64_t n, float* out, hipStream_t st);
 
+// out[r] = sum over e in [ptr[r], ptr[r + 1]) of src[idx[e]] in ascending e, rows of `feat` floats (a multiple of 4): aggregate.hip's
+// seg_sum_kernel (one wave per output row, a fixed fp32 order).  Every workgroup first loads *gate and returns when it is 0: the
+// k-means loop's early exit (kmeans.hip).
+int seg_sum_gated(const float* src, const int* ptr, const int* idx, float* out, int64_t nrows, int feat, const int* gate, hipStream_t st);
+
 // C/D layout of the 32x32 MFMAs: the lane holds column lane & 31, register r of lane half `half` (lane >> 5) holds this row of a tile
 // whose first row is `row0` (summed from the left, in row0's type: the address arithmetic the kernels were tuned with)
 typedef float f32x16 __attribute__((ext_vector_type(16)));

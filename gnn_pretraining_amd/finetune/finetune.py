@@ -3,7 +3,7 @@ miner, process_batch per task type, one AdamW step per batch over FinetuneGNN.pa
 test metrics from the best checkpoint.  Data come from the loaders of gnn_pretraining_amd/data (processed datasets in
 data/processed; synthetic stand-ins are generated when none were exported).  wandb is replaced by a JSONL logger with the
 same metric keys.  Build-only flags: --epochs, --device, --data-root, --data-scale, --log, --sparse-features, --lp-engine, --gc-engine,
---engine-eval, --lp-ranking, --device-metrics, --miner, --knn-probe."""
+--engine-eval, --lp-ranking, --device-metrics, --miner, --knn-probe, --cluster-probe."""
 from __future__ import annotations
 
 import argparse
@@ -22,7 +22,7 @@ from ..constants import NUM_CLASSES, TASK_TYPES
 from ..graph import SparseFeatures
 from ..models.finetune_model import FinetuneGNN, create_finetune_model
 from .metrics import (compute_batch_metrics, compute_batch_metrics_device, compute_test_metrics, compute_training_metrics, compute_validation_metrics,
-                      knn_probe_accuracy, ranking_metrics)
+                      cluster_probe, knn_probe_accuracy, ranking_metrics)
 
 OUTPUT_DIR = Path(__file__).resolve().parents[2] / "outputs" / "finetune"
 BATCH_SIZES = {"ENZYMES": 32, "PTC_MR": 32, "Cora_NC": -1, "CiteSeer_NC": -1, "Cora_LP": 256, "CiteSeer_LP": 256}
@@ -30,6 +30,7 @@ EPOCHS = {"ENZYMES": 100, "PTC_MR": 100, "Cora_NC": 200, "CiteSeer_NC": 200, "Co
 HARD_NEGATIVE_RATIO = 0.3
 MIN_HARD_NEGATIVES = 8
 PATIENCE_FRACTION = 0.5
+CLUSTER_PROBE_MAX_INIT = 64             # --cluster-probe N_INIT: k-means restarts per scored split
 
 
 class LinkPredictionHardNegativeMiner:
@@ -104,6 +105,7 @@ class FinetuneConfig:
     device_metrics: bool = False        # batch scores from integer counts made on the GPU (metrics.compute_batch_metrics_device), not scikit-learn on host copies
     miner_impl: str = "matrix"          # link-prediction domains: the hard-negative miner's top-k kernel (ops.hard_negative_topk impl), module path and lp_engine alike
     knn_probe: int = 0                  # classification domains on an engine: k of the weighted k-NN probe on the backbone's embeddings (val/ and test/knn_accuracy); 0 = off
+    cluster_probe: int = 0              # classification domains on an engine: restarts of the k-means clustering probe on the backbone's embeddings (val/cluster_nmi, test/cluster_nmi / _ari / _accuracy); 0 = off
 
     def __post_init__(self) -> None:
         if self.sparse_features and TASK_TYPES[self.domain_name] == "graph_classification":
@@ -127,6 +129,15 @@ class FinetuneConfig:
             raise ValueError(f"knn_probe classifies nodes or graphs from labelled neighbours: {self.domain_name} has no class labels")
         if self.knn_probe and not engine_active(self):
             raise ValueError(f"knn_probe needs an active fine-tune engine for {self.domain_name} (it reads the engine's eval-mode embed()): "
+                             + {"node_classification": "the node engine is switched off (GMP_FINETUNE_ENGINE=0)",
+                                "graph_classification": "pass gc_engine (--gc-engine)"}[TASK_TYPES[self.domain_name]])
+        if not 0 <= self.cluster_probe <= CLUSTER_PROBE_MAX_INIT:
+            raise ValueError(f"cluster_probe={self.cluster_probe} (the number of k-means restarts, 1 <= n_init <= {CLUSTER_PROBE_MAX_INIT}; "
+                             "0 switches the probe off)")
+        if self.cluster_probe and TASK_TYPES[self.domain_name] == "link_prediction":
+            raise ValueError(f"cluster_probe scores clusters of nodes or graphs against class labels: {self.domain_name} has no class labels")
+        if self.cluster_probe and not engine_active(self):
+            raise ValueError(f"cluster_probe needs an active fine-tune engine for {self.domain_name} (it reads the engine's eval-mode embed()): "
                              + {"node_classification": "the node engine is switched off (GMP_FINETUNE_ENGINE=0)",
                                 "graph_classification": "pass gc_engine (--gc-engine)"}[TASK_TYPES[self.domain_name]])
         if self.lp_ranking and not self.lp_engine:
@@ -360,27 +371,40 @@ def rank_test_edges(engine, train_loader, val_loader, test_loader, device) -> Di
     return {f"test/{k}": v for k, v in ranking_metrics(ranks).items()}
 
 
-def knn_probe(engine, train_loader, loader, device, cfg: FinetuneConfig) -> float:
-    """cfg.knn_probe: the accuracy of the weighted k-NN classifier (metrics.knn_probe_accuracy) that labels the rows of `loader`'s split
-    from the train split's, on the engine's eval-mode backbone output as the parameters stand now -- node embeddings for node
-    classification (one embed(), the two splits' rows gathered from it), mean-pooled graph embeddings for graph classification (one
-    embed(batch) per batch of the split taken in dataset order).  Reads the parameters and running statistics and draws nothing: no
-    generator, no dropout counter and no BatchNorm update is touched, so training goes on as without it."""
+def probe_embeddings(engine, datasets, device, cfg: FinetuneConfig):
+    """What the probes score: per dataset (a split) its rows of the engine's eval-mode backbone output as the parameters stand now and
+    their labels, both on the device -- node embeddings for node classification (one embed(), every split's rows gathered from it),
+    mean-pooled graph embeddings for graph classification (one embed(batch) per batch of the split taken in dataset order).  Reads the
+    parameters and running statistics and draws nothing: no generator, no dropout counter and no BatchNorm update is touched, so
+    training goes on as without it."""
     with torch.no_grad():
         if cfg.task_type == "node_classification":
-            emb, y = engine.embed(), train_loader.dataset.data.y
-            sets = [(ops.row_gather(emb, ds.indices.to(device)), y[ds.indices].to(torch.long).to(device)) for ds in (train_loader.dataset, loader.dataset)]
-        else:
-            sets = []
-            for ds in (train_loader.dataset, loader.dataset):
-                pooled, labels = [], []
-                for s in range(0, len(ds), max(cfg.batch_size, 1)):
-                    b = ds.collate(torch.arange(s, min(s + max(cfg.batch_size, 1), len(ds)))).to(device)
-                    pooled.append(O.global_mean_pool(engine.embed(b), b.batch, ptr32=b.ptr32))
-                    labels.append(b.y.to(torch.long))
-                sets.append((torch.cat(pooled), torch.cat(labels)))
-        (db, db_y), (q, q_y) = sets
-        return knn_probe_accuracy(db, db_y, q, q_y, NUM_CLASSES[cfg.domain_name], cfg.knn_probe)["accuracy"]
+            emb, y = engine.embed(), datasets[0].data.y
+            return [(ops.row_gather(emb, ds.indices.to(device)), y[ds.indices].to(torch.long).to(device)) for ds in datasets]
+        sets = []
+        for ds in datasets:
+            pooled, labels = [], []
+            for s in range(0, len(ds), max(cfg.batch_size, 1)):
+                b = ds.collate(torch.arange(s, min(s + max(cfg.batch_size, 1), len(ds)))).to(device)
+                pooled.append(O.global_mean_pool(engine.embed(b), b.batch, ptr32=b.ptr32))
+                labels.append(b.y.to(torch.long))
+            sets.append((torch.cat(pooled), torch.cat(labels)))
+        return sets
+
+
+def knn_probe(engine, train_loader, loader, device, cfg: FinetuneConfig) -> float:
+    """cfg.knn_probe: the accuracy of the weighted k-NN classifier (metrics.knn_probe_accuracy) that labels the rows of `loader`'s split
+    from the train split's, on probe_embeddings' rows."""
+    (db, db_y), (q, q_y) = probe_embeddings(engine, (train_loader.dataset, loader.dataset), device, cfg)
+    return knn_probe_accuracy(db, db_y, q, q_y, NUM_CLASSES[cfg.domain_name], cfg.knn_probe)["accuracy"]
+
+
+def cluster_probe_scores(engine, loader, device, cfg: FinetuneConfig) -> Dict[str, float]:
+    """cfg.cluster_probe: NMI, ARI and matched accuracy (metrics.cluster_probe: spherical k-means with as many clusters as the domain
+    has classes, cfg.cluster_probe restarts) of `loader`'s split on probe_embeddings' rows.  The seeds come from a generator of the
+    probe's own (cfg.seed), never from the training generator."""
+    (emb, y), = probe_embeddings(engine, (loader.dataset,), device, cfg)
+    return cluster_probe(emb, y, NUM_CLASSES[cfg.domain_name], n_init=cfg.cluster_probe, seed=cfg.seed)
 
 
 def finetune(cfg: FinetuneConfig, epochs: Optional[int] = None, device: Optional[str] = None,
@@ -440,6 +464,9 @@ def finetune(cfg: FinetuneConfig, epochs: Optional[int] = None, device: Optional
     probe_engine = (node_engine or gc_engine) if cfg.knn_probe else None
     if probe_engine is not None:                             # the embeddings before any training
         logger.log({"val/knn_accuracy": knn_probe(probe_engine, train_loader, val_loader, dev, cfg)}, 0)
+    cluster_engine = (node_engine or gc_engine) if cfg.cluster_probe else None
+    if cluster_engine is not None:
+        logger.log({"val/cluster_nmi": cluster_probe_scores(cluster_engine, val_loader, dev, cfg)["nmi"]}, 0)
     for epoch in range(1, (epochs or cfg.epochs) + 1):
         if node_engine is not None:
             run_training_node_engine(node_engine, train_loader, dev, epoch, global_step, cfg, logger)
@@ -459,6 +486,8 @@ def finetune(cfg: FinetuneConfig, epochs: Optional[int] = None, device: Optional
             val = compute_validation_metrics(evaluate(model, val_loader, dev, cfg, "val", miner, edges), epoch)
         if probe_engine is not None:
             val["val/knn_accuracy"] = knn_probe(probe_engine, train_loader, val_loader, dev, cfg)
+        if cluster_engine is not None:
+            val["val/cluster_nmi"] = cluster_probe_scores(cluster_engine, val_loader, dev, cfg)["nmi"]
         if val[key] > best:
             best, stale = val[key], 0
             torch.save({"epoch": epoch, "model_state_dict": model.state_dict(), "val_metrics": val}, path)
@@ -475,6 +504,9 @@ def finetune(cfg: FinetuneConfig, epochs: Optional[int] = None, device: Optional
     test = compute_test_metrics(test_batches, epoch, stale, start, model)
     if probe_engine is not None:
         test["test/knn_accuracy"] = knn_probe(probe_engine, train_loader, test_loader, dev, cfg)
+    if cluster_engine is not None:
+        scores = cluster_probe_scores(cluster_engine, test_loader, dev, cfg)
+        test.update({f"test/cluster_{k}": scores[k] for k in ("nmi", "ari", "accuracy")})
     if cfg.lp_ranking:
         test.update(rank_test_edges(lp_engine, train_loader, val_loader, test_loader, dev))
     logger.log(test, global_step[0])
@@ -506,6 +538,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--knn-probe", type=int, default=0, metavar="K",
                    help="classification domains on an engine: also log val/knn_accuracy (every epoch and once before training) and test/knn_accuracy, "
                         "the weighted k-NN classifier (K neighbours, 1..64, cosine, T = 0.07) on the backbone's embeddings; 0 = off")
+    p.add_argument("--cluster-probe", type=int, default=0, metavar="N_INIT",
+                   help="classification domains on an engine: also log val/cluster_nmi (every epoch and once before training) and test/cluster_nmi, "
+                        "test/cluster_ari, test/cluster_accuracy, spherical k-means (k = the number of classes, N_INIT restarts, 1..64, k-means++) on "
+                        "the backbone's embeddings; 0 = off")
     return p
 
 
@@ -514,7 +550,7 @@ def config_from_args(a: argparse.Namespace) -> FinetuneConfig:
                           lp_engine=getattr(a, "lp_engine", False), gc_engine=getattr(a, "gc_engine", False),
                           engine_eval=getattr(a, "engine_eval", False), lp_ranking=getattr(a, "lp_ranking", False),
                           device_metrics=getattr(a, "device_metrics", False), miner_impl=getattr(a, "miner", "matrix"),
-                          knn_probe=getattr(a, "knn_probe", 0))
+                          knn_probe=getattr(a, "knn_probe", 0), cluster_probe=getattr(a, "cluster_probe", 0))
 
 
 def main() -> None:

@@ -129,6 +129,103 @@ def knn_probe_accuracy(db_emb: Tensor, db_labels: Tensor, query_emb: Tensor, que
     return {"accuracy": correct / n, "correct": correct, "num_samples": n}
 
 
+def clustering_scores(table) -> Dict[str, float]:
+    """NMI (arithmetic normalisation), ARI, purity and accuracy of a clustering against class labels, in float64 on the host from the
+    integer contingency table alone: table [clusters, classes] with [k, c] = rows of cluster k and class c (ops.contingency).  Clusters
+    and classes without rows do not count, as in scikit-learn, whose values these are:
+      nmi       I / ((H_clusters + H_classes) / 2), I = sum n_kc / n log(n n_kc / (n_k n_c)); 1.0 when both sides have one group, 0.0 when I = 0
+      ari       from the pair counts: 2 (tp tn - fn fp) / ((tp + fn)(fn + tn) + (tp + fp)(fp + tn)) in integers; 1.0 when fn = fp = 0
+      purity    sum over clusters of the largest class count / n
+      accuracy  the best one-to-one matching of clusters to classes (scipy.optimize.linear_sum_assignment on the table) / n"""
+    from scipy.optimize import linear_sum_assignment
+    t = np.asarray(table, dtype=np.int64)
+    if t.ndim != 2 or bool((t < 0).any()):
+        raise ValueError(f"clustering_scores: table of shape {t.shape} (a 2-D array of counts)")
+    n = int(t.sum())
+    if n == 0:
+        raise ValueError("clustering_scores: no samples")
+    full = t
+    t = t[t.sum(axis=1) > 0][:, t.sum(axis=0) > 0]
+    nk, nc = t.sum(axis=1), t.sum(axis=0)
+
+    def entropy(counts) -> float:
+        p = counts.astype(np.float64)
+        return 0.0 if p.size == 1 else float(-np.sum(p / n * (np.log(p) - np.log(n))))
+
+    if nk.size == 1 and nc.size == 1:
+        nmi = 1.0
+    elif nk.size == 1 or nc.size == 1:
+        nmi = 0.0
+    else:
+        kk, cc = np.nonzero(t)
+        v = t[kk, cc].astype(np.float64)
+        terms = v / n * (np.log(v) - np.log(n)) + v / n * (-np.log((nk[kk] * nc[cc]).astype(np.float64)) + 2.0 * np.log(n))
+        terms = np.where(np.abs(terms) < np.finfo(np.float64).eps, 0.0, terms)
+        mi = max(float(terms.sum()), 0.0)
+        nmi = 0.0 if mi == 0.0 else mi / ((entropy(nk) + entropy(nc)) / 2.0)
+    sq = int(sum(int(v) * int(v) for v in t.ravel()))
+    tp = sq - n
+    fp = int(sum(int(v) * int(v) for v in nk)) - sq             # same cluster, different class
+    fn = int(sum(int(v) * int(v) for v in nc)) - sq
+    tn = n * n - fp - fn - sq
+    ari = 1.0 if fn == 0 and fp == 0 else 2.0 * (tp * tn - fn * fp) / ((tp + fn) * (fn + tn) + (tp + fp) * (fp + tn))
+    rows, cols = linear_sum_assignment(full, maximize=True)
+    return {"nmi": float(nmi), "ari": float(ari), "purity": int(t.max(axis=1).sum()) / n, "accuracy": int(full[rows, cols].sum()) / n}
+
+
+def _kmeans_seeds(x: Tensor, num_clusters: int, init: str, gen: torch.Generator) -> Tensor:
+    """Rows of x to start from (indices, on the host).  "random": the first rows of a permutation.  "k-means++": a uniform row, then each
+    further one drawn with probability proportional to max(0, 2 - 2 sim_best), the squared distance on the sphere to the nearest centre
+    chosen so far (ops.kmeans_assign); all weights zero: the lowest row not yet chosen.  More clusters than rows: every row once in that
+    order, then again from the start (the duplicates stay empty)."""
+    from .. import ops
+    n = x.size(0)
+    if init == "random":
+        return torch.randperm(n, generator=gen)[torch.arange(num_clusters) % n]
+    chosen = [int(torch.randint(n, (1,), generator=gen))]
+    while len(chosen) < min(num_clusters, n):
+        _, sim_best = ops.kmeans_assign(x, x[torch.tensor(chosen, device=x.device)].contiguous())
+        w = (2.0 - 2.0 * sim_best.double().cpu()).clamp_(min=0.0)
+        w[torch.tensor(chosen)] = 0.0
+        if float(w.sum()) > 0.0:
+            chosen.append(int(torch.multinomial(w, 1, generator=gen)))
+        else:
+            taken = set(chosen)
+            chosen.append(next(i for i in range(n) if i not in taken))
+    return torch.tensor(chosen)[torch.arange(num_clusters) % n]
+
+
+def cluster_probe(emb: Tensor, labels: Tensor, num_clusters: int, n_init: int = 10, max_iter: int = 100, seed: int = 0,
+                  init: str = "k-means++") -> Dict:
+    """The clustering probe for self-supervised embeddings: spherical k-means with num_clusters clusters on emb [n, d <= 256] (fp32, on
+    the GPU; ops.kmeans_fit: csrc/kmeans.hip), n_init restarts, the one with the largest sum of similarities kept (ties to the earlier),
+    scored against labels int64 [n] in [0, num_clusters) through the integer table of ops.contingency and clustering_scores.  The seeds
+    are drawn on the host from a generator of this function's own (seed, restart): nothing else's random state moves, and the result is a
+    function of (emb, labels, the arguments).  Returns the four scores and objective, n_iter, converged, empty_clusters, restart of
+    the kept fit.  Needs no labelled neighbours and no trained head; nothing here feeds back into training."""
+    from .. import ops
+    if init not in ("k-means++", "random"):
+        raise ValueError(f"cluster_probe: init={init!r} (\"k-means++\" or \"random\")")
+    x = emb.detach().contiguous()
+    n = int(x.size(0))
+    if n < 1 or not 1 <= int(num_clusters) <= ops.KMEANS_MAX_CLUSTERS or int(n_init) < 1:
+        raise ValueError(f"cluster_probe: {num_clusters} clusters, {n} rows, n_init={n_init} (rows >= 1, 1 <= clusters <= {ops.KMEANS_MAX_CLUSTERS}, "
+                         "n_init >= 1)")
+    best = None
+    for restart in range(int(n_init)):
+        gen = torch.Generator().manual_seed(int(seed) * 1000003 + restart)
+        rows = _kmeans_seeds(x, int(num_clusters), init, gen)
+        fit = ops.kmeans_fit(x, x[rows.to(x.device)].contiguous(), max_iter)
+        objective = float(fit.sim.double().sum().item())
+        if best is None or objective > best[0]:
+            best = (objective, fit, restart)
+    objective, fit, restart = best
+    table = ops.contingency(fit.labels, labels.to(torch.int64).contiguous(), int(num_clusters), int(num_clusters)).cpu().numpy()
+    out = clustering_scores(table)
+    out.update(objective=objective, n_iter=fit.n_iter, converged=fit.converged, empty_clusters=fit.empty, restart=restart)
+    return out
+
+
 def compute_training_metrics(epoch: int, step: int, loss: Tensor, optimizer: torch.optim.Optimizer, domain_name: str,
                              targets: Tensor, predictions: Tensor, probabilities: Tensor, step_start_time: float,
                              model: torch.nn.Module, device_metrics: bool = False) -> Dict[str, float]:

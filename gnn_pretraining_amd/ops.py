@@ -1185,7 +1185,82 @@ def knn_vote(idx: Tensor, sim: Tensor, labels: Tensor, num_classes: int, tempera
     return scores, pred
 
 
-CLS_MAX_ROWS, CLS_MAX_CLASSES = 262144, 32       # gmp_cls_counts: the pair count is n^2 compares (gnnmp.h)
+KMEANS_MAX_CLUSTERS, KMEANS_MAX_DIM, KMEANS_MAX_ITER = 1024, 256, 10000       # gmp_kmeans_assign / gmp_kmeans_fit / gmp_contingency (gnnmp.h)
+
+class KMeansFit(NamedTuple):
+    centroids: Tensor  # [kc, d]
+    labels: Tensor     # [n] int64, the last assignment pass
+    sim: Tensor        # [n] the winning similarities of that pass
+    n_iter: int
+    converged: bool    # the last pass moved no row
+    empty: int         # clusters the last update found without rows
+
+
+def _kmeans_args(who: str, x: Tensor, centroids: Tensor) -> Tuple[int, int, int]:
+    _need(x, torch.float32, "x", 2); _need(centroids, torch.float32, "centroids", 2)
+    n, d = x.shape
+    kc = centroids.size(0)
+    if centroids.size(1) != d or centroids.device != x.device:
+        raise L.GnnmpError(f"{who}: x {tuple(x.shape)} on {x.device}, centroids {tuple(centroids.shape)} on {centroids.device}")
+    if not 1 <= kc <= KMEANS_MAX_CLUSTERS or not 1 <= d <= KMEANS_MAX_DIM:
+        raise L.GnnmpError(f"{who}: clusters={kc} dim={d} (1 <= clusters <= {KMEANS_MAX_CLUSTERS}, 1 <= dim <= {KMEANS_MAX_DIM})")
+    return n, kc, d
+
+
+def kmeans_assign(x: Tensor, centroids: Tensor, return_matrix: bool = False):
+    """Every row of x [n, d] to its centroid of greatest cosine similarity (gnnmp.h gmp_kmeans_assign; csrc/kmeans.hip): returns
+    (labels [n] int64, sim [n]), ties to the lower centroid index.  x and centroids [kc, d] fp32 contiguous, 1 <= kc <= 1024,
+    1 <= d <= 256; both are normalised inside (a zero row scores 0 and lands on centroid 0).  Nothing of size n x kc is allocated unless
+    return_matrix asks for the similarity matrix as the selection saw it (a third result, tests only)."""
+    n, kc, d = _kmeans_args("kmeans_assign", x, centroids)
+    dev, l = x.device, L.lib()
+    labels, sim = torch.empty(n, dtype=torch.int64, device=dev), torch.empty(n, device=dev)
+    mat = torch.empty(n, kc, device=dev) if return_matrix else None
+    ws = _ws(l.gmp_kmeans_workspace_bytes(n, kc, d), dev)
+    L.check(l.gmp_kmeans_assign(_ptr(x), n, _ptr(centroids), kc, d, _ptr(labels), _ptr(sim), _ptr(mat), _ptr(ws), ws.numel(), _stream(x)),
+            "gmp_kmeans_assign")
+    return (labels, sim, mat) if return_matrix else (labels, sim)
+
+
+def kmeans_fit(x: Tensor, init_centroids: Tensor, max_iter: int = 100) -> KMeansFit:
+    """Spherical k-means from the given centroids (gnnmp.h gmp_kmeans_fit): up to max_iter Lloyd iterations -- assign every row to its
+    centroid of greatest cosine similarity, stop when no label changed, otherwise each centroid becomes the normalised sum of its rows
+    (in a fixed order: bitwise repeatable; a cluster without rows keeps its centroid) -- enqueued at once, without a host round trip in
+    between.  Returns (centroids [kc, d], labels [n] int64 and sim [n] of the last assignment, n_iter, converged, empty): the three
+    scalars come from one host copy at the end; empty = clusters the last update found without rows."""
+    n, kc, d = _kmeans_args("kmeans_fit", x, init_centroids)
+    if not 1 <= int(max_iter) <= KMEANS_MAX_ITER:
+        raise L.GnnmpError(f"kmeans_fit: max_iter={max_iter} (1 <= max_iter <= {KMEANS_MAX_ITER})")
+    dev, l = x.device, L.lib()
+    centroids = init_centroids.clone()
+    labels, sim = torch.empty(n, dtype=torch.int64, device=dev), torch.empty(n, device=dev)
+    info = torch.zeros(4, dtype=torch.int64, device=dev)
+    ws = _ws(l.gmp_kmeans_workspace_bytes(n, kc, d), dev)
+    L.check(l.gmp_kmeans_fit(_ptr(x), n, _ptr(init_centroids), kc, d, int(max_iter), _ptr(centroids), _ptr(labels), _ptr(sim), _ptr(info),
+                             _ptr(ws), ws.numel(), _stream(x)), "gmp_kmeans_fit")
+    n_iter, changed, empty, _ = (int(v) for v in info.tolist())                 # the one read-back
+    return KMeansFit(centroids, labels, sim, n_iter, n > 0 and changed == 0, empty)
+
+
+def contingency(a: Tensor, b: Tensor, na: int, nb: int) -> Tensor:
+    """table [na, nb] int64 with table[a[i], b[i]] = the number of such rows (gnnmp.h gmp_contingency: integer atomics, exact), a and b
+    int64 [n] on the GPU, 1 <= na, nb <= 1024.  Raises when an entry lies outside its range (one read-back of the status word)."""
+    _need(a, torch.int64, "a", 1); _need(b, torch.int64, "b", 1)
+    n = a.numel()
+    if b.numel() != n or b.device != a.device:
+        raise L.GnnmpError(f"contingency: a [{n}] on {a.device}, b [{b.numel()}] on {b.device}")
+    if not 1 <= int(na) <= KMEANS_MAX_CLUSTERS or not 1 <= int(nb) <= KMEANS_MAX_CLUSTERS:
+        raise L.GnnmpError(f"contingency: na={na} nb={nb} (1 <= na, nb <= {KMEANS_MAX_CLUSTERS})")
+    table = torch.zeros(int(na), int(nb), dtype=torch.int64, device=a.device)
+    status = torch.zeros(1, dtype=torch.int32, device=a.device)
+    L.check(L.lib().gmp_contingency(_ptr(a), _ptr(b), n, int(na), int(nb), _ptr(table), _ptr(status), _stream(a)), "gmp_contingency")
+    bad = int(status.item())
+    if bad:
+        raise L.GnnmpError(f"contingency: {bad} rows have an entry outside [0, {na}) x [0, {nb})")
+    return table
+
+
+CLS_MAX_ROWS, CLS_MAX_CLASSES = 262144, 32      # gmp_cls_counts: the pair count is n^2 compares (gnnmp.h)
 
 
 def cls_counts_packed(targets: Tensor, predictions: Tensor, probabilities: Tensor) -> Tensor:

@@ -375,6 +375,43 @@ int gmp_knn_vote(const int64_t* idx, const float* sim, int64_t nq, int k, const 
                  float temperature, float* class_scores, int64_t* pred, int32_t* status, gmp_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
+ * Spherical k-means (k-means in cosine similarity on L2-normalised rows, the clustering probe for self-supervised embeddings) and the
+ * integer contingency table its scores are computed from: x [n, dim] rows against kc centroids [kc, dim], contiguous fp32.  Rows and
+ * centroids are normalised as gmp_knn_topk does, z / max(||z||, 1e-12) with the stride padded with zeros (a zero row scores 0 against every
+ * centroid and lands on centroid 0), and the similarity of a (row, centroid) pair is the same k-ordered fp32 MFMA chain (csrc/sim_tile.h)
+ * gmp_knn_topk computes for those two rows.  No [n, kc] array exists unless matrix_out is given.
+ * gmp_kmeans_assign: labels [n] int64 = the centroid of greatest similarity, ties to the lower centroid index (integer compares on
+ *   (score bits, ~index), a total order), sim [n] = that similarity.  matrix_out: NULL or [n, kc], every similarity exactly as the
+ *   selection saw it -- test / diagnostic hook.
+ * gmp_kmeans_fit enqueues max_iter Lloyd iterations on `stream` with no host synchronisation:
+ *       c = normalize(init);  for it = 1 .. max_iter:  labels_new, sim = assign(xn, c);  changed = (it == 1) ? n : count(labels_new != labels);
+ *       labels = labels_new;  if changed == 0: stop (converged);  c = update(xn, labels, c)
+ *   update: centroid j = normalize(sum of xn[i] over labels[i] == j), the sum in ascending i (a stable counting sort by label and a
+ *   segmented sum, no floating-point atomics: bitwise repeatable, whatever order the workgroups run in); a cluster without rows keeps its
+ *   centroid.
+ *   After convergence every remaining kernel reads the device-side `changed` word, finds 0 and returns at once.  Outputs: labels and sim of
+ *   the last assignment pass; centroids [kc, dim], unit rows from the last update -- a cluster that never had a row keeps its row of
+ *   `init` as given (init may be `centroids` itself); info int64 [4] = {iterations run, changed of the last pass, clusters the last update
+ *   found empty, 0}.  Every iteration normalises the stored centroids again, so T iterations in one call equal T calls of one iteration,
+ *   each started from the centroids of the one before, bit for bit.  One wave sums a cluster's rows, so the update's time grows with the
+ *   largest cluster.
+ * gmp_contingency: table int64 [na, nb] with table[a[i], b[i]] += 1 over i < n, a and b int64 [n], integer atomics; status int32 [1] counts
+ *   the rows with a[i] outside [0, na) or b[i] outside [0, nb), which are left out.  Both are zeroed inside the call.
+ * 0 <= n < 2^31, 1 <= kc <= 1024, 1 <= dim <= 256, 1 <= max_iter <= 10000, 1 <= na, nb <= 1024: GMP_ERR_ARG outside those ranges or on a
+ * NULL pointer, GMP_ERR_WORKSPACE when workspace_bytes < gmp_kmeans_workspace_bytes(n, kc, dim); nothing is launched then.  n == 0 is a
+ * no-op (no output is touched), GMP_OK.  gmp_kmeans_workspace_bytes = 4 (n + 2 kc) dpad + 4 n + 4 kc ceil(n / 256) + 8 kc + a constant below
+ * 4 KiB, dpad = dim rounded up to 4 (the normalised rows and centroids, the sums, the sorted row list and the sort's counts per chunk of
+ * 256 rows: at most 20 bytes per row beside the normalised copy), 0 for sizes outside the ranges.
+ * Asynchronous on `stream`, no allocation, no global state.
+ * ------------------------------------------------------------------------- */
+size_t gmp_kmeans_workspace_bytes(int64_t n, int kc, int dim);
+int gmp_kmeans_assign(const float* x, int64_t n, const float* centroids, int kc, int dim, int64_t* labels, float* sim, float* matrix_out,
+                      void* workspace, size_t workspace_bytes, gmp_stream_t stream);
+int gmp_kmeans_fit(const float* x, int64_t n, const float* init, int kc, int dim, int max_iter, float* centroids, int64_t* labels, float* sim,
+                   int64_t* info, void* workspace, size_t workspace_bytes, gmp_stream_t stream);
+int gmp_contingency(const int64_t* a, const int64_t* b, int64_t n, int na, int nb, int64_t* table, int32_t* status, gmp_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
  * Integer counts for the classification metrics of fine-tuning (src/finetune/metrics.py:39-82: accuracy, F1, precision, recall and the
  * one-vs-rest ROC AUC of scikit-learn), from targets [n] int64, predictions [n] int64 and probabilities [n, classes] fp32 contiguous:
  *   confusion  int64 [classes * classes]  entry [t * classes + p] = rows with target t and prediction p

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Fine-tuning CLI with the reference's flags (run_finetune.py:129-154):
 --sweep | --domain_sweep D | --domain_name D --finetune_strategy {full_finetune,linear_probe} --pretrained_scheme {b1..s5} --seed N.
-Flags after `--` go to every run unchanged (gnn_pretraining_amd/finetune/finetune.py build_parser: --epochs, --gc-engine, --knn-probe K, ...)."""
+Flags after `--` go to every run unchanged (gnn_pretraining_amd/finetune/finetune.py build_parser: --epochs, --gc-engine, --knn-probe K, --cluster-probe N_INIT, ...)."""
 import argparse
 import os
 import subprocess

@@ -1,0 +1,335 @@
+"""The k-means clustering probe (csrc/kmeans.hip: ops.kmeans_assign / ops.kmeans_fit / ops.contingency, metrics.cluster_probe,
+--cluster-probe) on the GPU against the fp64 definition of tests/kmeans_ref.py: (a) where the arithmetic is exact, labels and similarities
+equal the reference's bit for bit across every tile width and both sides of the 128-row and 32-centroid tile edges; (b) the assignment
+is k-NN with k = 1 on the same similarity core, bit for bit; (c) on random rows the similarities agree with fp64 to 1e-5 and the
+selection is exact on the kernel's own scores; (d) a fit step by step: one call of T iterations is T calls of one, repeatable, every
+label fp64's argmax outside a 2e-5 margin, every update within 1e-5 of fp64's; (e) the edges of the contract; (f) the contingency table;
+(g), (h) the layers above."""
+import functools
+import json
+import math
+
+import numpy as np
+import pytest
+import torch
+
+import kmeans_ref as R
+import knn_ref
+from gnn_pretraining_amd import ops
+from gnn_pretraining_amd._lib import GnnmpError
+from gnn_pretraining_amd.finetune.metrics import cluster_probe, clustering_scores
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+CLASSES = 7
+
+
+def _dev(a):
+    return torch.as_tensor(a).to(DEV).contiguous()
+
+
+def _assign(x, c, **kw):
+    return tuple(t.cpu().numpy() for t in ops.kmeans_assign(_dev(x), _dev(c), **kw))
+
+
+# ---------------------------------------------------------------------------- (a) exact arithmetic
+EXACT_SHAPES = [(1, 1, 8), (5, 3, 6), (127, 31, 16), (128, 32, 32), (129, 33, 40), (301, 70, 100), (301, 1024, 160), (300, 64, 256)]
+
+
+@pytest.mark.parametrize("n,kc,d", EXACT_SHAPES)
+def test_bit_exact_on_four_ones_and_sixteen_sign_rows(n, kc, d):
+    for gen in (knn_ref.four_ones, knn_ref.sixteen_signs):
+        if gen is knn_ref.sixteen_signs and d < 16:
+            continue
+        x, c = gen(n, d, n + d), gen(kc, d, kc + d + 1)
+        labels, sim = _assign(x, c)
+        want_labels, want_sim = R.assign(x, c)
+        assert labels.dtype == np.int64 and np.array_equal(labels, want_labels)     # ties (there are many): the lower centroid
+        assert sim.dtype == np.float32 and np.array_equal(sim.astype(np.float64), want_sim)
+
+
+# ---------------------------------------------------------------------------- (b) the shared core
+@pytest.mark.parametrize("d", [24, 40, 100, 256])
+def test_assignment_is_knn_with_one_neighbour_bit_for_bit(d):
+    g = torch.Generator().manual_seed(d)
+    x, c = torch.randn(700, d, generator=g), torch.randn(90, d, generator=g)
+    c[40:50] = c[:10]                                                # duplicated centroids: exact ties
+    c[77] = x[5]
+    x[100:110] = 0.0                                                 # zero rows
+    x[200:230] = x[300:330]                                          # repeated rows
+    x[400:410] = c[3:13]
+    xd, cd = x.to(DEV), c.to(DEV)
+    labels, sim = ops.kmeans_assign(xd, cd)
+    idx, ksim = ops.knn_topk(xd, cd, 1)
+    assert torch.equal(labels, idx[:, 0])
+    assert torch.equal(sim.view(torch.int32), ksim[:, 0].contiguous().view(torch.int32))
+    assert (labels[100:110] == 0).all() and (sim[100:110] == 0).all()               # a zero row: score 0, centroid 0
+    assert (labels[400:407] == torch.arange(3, 10, device=DEV)).all()              # rows 3 .. 9 of c: the lower of each duplicate pair
+    assert torch.equal(labels[200:230], labels[300:330])
+
+
+# ---------------------------------------------------------------------------- (c) random rows against fp64
+@pytest.mark.parametrize("kind,n,kc,d", [("randn", 300, 100, 256), ("randn", 257, 250, 40), ("abs", 500, 7, 256), ("randn", 130, 33, 100)])
+def test_selection_is_exact_on_its_own_scores_and_scores_match_fp64(kind, n, kc, d):
+    g = torch.Generator().manual_seed(n + kc)
+    x, c = torch.randn(n, d, generator=g), torch.randn(kc, d, generator=g)
+    if kind == "abs":
+        x, c = x.abs(), c.abs()
+    labels, sim, mat = _assign(x, c, return_matrix=True)
+    err = float(np.abs(mat - R.cosine(x.numpy(), c.numpy())).max())
+    print(f"{(kind, n, kc, d)}: max |S - fp64| = {err:.3e}")
+    assert err < 1e-5
+    want_labels, want_sim = R.assign(None, None, similarity=mat)
+    assert np.array_equal(labels, want_labels) and np.array_equal(sim, want_sim)
+    plain = _assign(x, c)
+    assert np.array_equal(plain[0], labels) and np.array_equal(plain[1], sim)      # the hook changes nothing
+
+
+# ---------------------------------------------------------------------------- (d) a fit, step by step
+FIT_CASES = [("randn", 1000, 256, 33), ("randn", 2500, 40, 64), ("abs", 500, 256, 7)]
+FIT_STEPS = 6
+
+
+def _fit_inputs(kind, n, d, kc):
+    g = torch.Generator().manual_seed(n + kc)
+    x = torch.randn(n, d, generator=g)
+    if kind == "abs":
+        x = x.abs()
+    return x, x[torch.randperm(n, generator=g)[:kc]].contiguous()
+
+
+def _host(fit):
+    return fit.centroids.cpu().numpy(), fit.labels.cpu().numpy(), fit.sim.cpu().numpy()
+
+
+def _same_bits(a, b):
+    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+
+
+@functools.lru_cache(maxsize=None)
+def _fit_case(i):
+    """FIT_CASES[i]: the chain of FIT_STEPS one-iteration fits, each started from the centroids of the one before (computed once)"""
+    kind, n, d, kc = FIT_CASES[i]
+    x, init = _fit_inputs(kind, n, d, kc)
+    xd, c = x.to(DEV), init.to(DEV)
+    chain = []
+    for _ in range(FIT_STEPS):
+        fit = ops.kmeans_fit(xd, c, max_iter=1)
+        chain.append((c.cpu().numpy(), fit))
+        c = fit.centroids
+    return x, init, xd, chain
+
+
+@pytest.mark.parametrize("i", range(len(FIT_CASES)))
+def test_one_call_equals_chained_single_iterations_and_is_repeatable(i):
+    x, init, xd, chain = _fit_case(i)
+    for steps in (1, 2, FIT_STEPS):
+        whole, again = ops.kmeans_fit(xd, init.to(DEV), max_iter=steps), ops.kmeans_fit(xd, init.to(DEV), max_iter=steps)
+        last = chain[steps - 1][1]
+        for a, b, c in zip(_host(whole), _host(again), _host(last)):     # centroids, labels, sim
+            assert _same_bits(a, b) and _same_bits(a, c)
+        assert whole.n_iter <= steps and whole.n_iter == again.n_iter and whole.empty == again.empty
+        assert all(f.n_iter == 1 and not f.converged for _, f in chain)            # a first pass always counts n changes
+        # the whole fit's bookkeeping against the chain's labels: it stops at the first pass that moved no row
+        moved = [int((chain[t][1].labels != chain[t - 1][1].labels).sum()) for t in range(1, steps)]
+        stop = next((t + 2 for t, m in enumerate(moved) if m == 0), steps)
+        assert whole.n_iter == stop and whole.converged == (0 in moved)
+
+
+@pytest.mark.parametrize("i", range(len(FIT_CASES)))
+def test_every_step_follows_fp64_from_the_gpus_own_centroids(i):
+    x, init, xd, chain = _fit_case(i)
+    xn = R.normalize(x.numpy())
+    worst_sim = worst_c = 0.0
+    for step, (c_prev, fit) in enumerate(chain, 1):
+        centroids, labels, sim = _host(fit)
+        cn = R.normalize(c_prev)
+        cos = xn @ cn.T
+        top = np.sort(cos, axis=1)
+        best, gap = top[:, -1], (top[:, -1] - top[:, -2]) if cos.shape[1] > 1 else np.full(cos.shape[0], np.inf)
+        picked = cos[np.arange(cos.shape[0]), labels]
+        assert (picked >= best - 2e-5).all()                         # every label is within 2e-5 of fp64's best ...
+        clear = gap > 2e-5
+        assert np.array_equal(labels[clear], cos.argmax(axis=1)[clear])            # ... and is fp64's argmax where that is clear
+        inside = float((~clear).mean())
+        print(f"{FIT_CASES[i]} step {step}: rows inside the 2e-5 margin: {int((~clear).sum())} of {clear.size}")
+        assert inside <= 0.01
+        worst_sim = max(worst_sim, float(np.abs(sim - picked).max()))
+        want = R.update(xn, labels, cn)
+        worst_c = max(worst_c, float(np.abs(centroids - want).max()))
+        assert fit.empty == cn.shape[0] - np.unique(labels).size
+    print(f"{FIT_CASES[i]}: max |sim - fp64| = {worst_sim:.3e}, max |centroid - fp64 update| = {worst_c:.3e}")
+    assert worst_sim < 1e-5
+    assert worst_c < 1e-5
+
+
+# ---------------------------------------------------------------------------- (e) edges
+def _planted(n=600, seed=7):
+    g = torch.Generator().manual_seed(seed)
+    centres = torch.randn(CLASSES, 64, generator=g)
+    y = torch.randint(0, CLASSES, (n,), generator=g)
+    y[:CLASSES] = torch.arange(CLASSES)                              # every class occurs
+    x = centres[y] + 0.05 * torch.randn(n, 64, generator=g)
+    return x, y
+
+
+def test_planted_clusters_converge_at_the_second_pass_with_perfect_scores():
+    x, y = _planted()
+    init = torch.stack([x[int((y == c).nonzero()[0])] for c in range(CLASSES)])    # one row per class
+    fit = ops.kmeans_fit(x.to(DEV), init.to(DEV), max_iter=50)
+    assert fit.n_iter == 2 and fit.converged and fit.empty == 0
+    c_ref, labels_ref, sim_ref, info = R.fit(x.numpy(), init.numpy(), 50)
+    assert info == [2, 0, 0, 0] and np.array_equal(fit.labels.cpu().numpy(), labels_ref)
+    assert np.array_equal(labels_ref, y.numpy())                     # (cluster c started on a row of class c)
+    assert float(np.abs(fit.centroids.cpu().numpy() - c_ref).max()) < 1e-5 and float(np.abs(fit.sim.cpu().numpy() - sim_ref).max()) < 1e-5
+    table = ops.contingency(fit.labels, y.to(DEV), CLASSES, CLASSES)
+    s = clustering_scores(table.cpu().numpy())
+    assert s["nmi"] == 1.0 and s["ari"] == 1.0 and s["accuracy"] == 1.0 and s["purity"] == 1.0
+
+
+def test_duplicate_initial_centroids_leave_the_higher_one_empty_and_untouched():
+    x, y = _planted()
+    init = torch.stack([x[int((y == c).nonzero()[0])] for c in range(CLASSES)]) * 3.0   # not unit rows: "untouched" means as given
+    init[5] = init[2]
+    fit = ops.kmeans_fit(x.to(DEV), init.to(DEV), max_iter=1)        # the pass that sees the duplicates: the tie goes to centroid 2
+    assert fit.empty == 1 and not bool((fit.labels == 5).any()) and bool((fit.labels == 2).any())
+    assert torch.equal(fit.centroids[5].cpu().view(torch.int32), init[5].view(torch.int32))
+    others = [j for j in range(CLASSES) if j != 5]
+    norms = fit.centroids[others].double().norm(dim=1).cpu()
+    assert float((norms - 1.0).abs().max()) < 1e-6                   # every cluster with rows: a unit centroid
+    # (from the second pass on centroid 2 has moved to its cluster's mean and centroid 5, still a data row, wins that row back)
+    fit = ops.kmeans_fit(x.to(DEV), init.to(DEV), max_iter=6)
+    _, labels_ref, _, info = R.fit(x.numpy(), init.numpy(), 6)
+    assert np.array_equal(fit.labels.cpu().numpy(), labels_ref) and [fit.n_iter, fit.empty] == [info[0], info[2]]
+    # duplicates that point away from every row stay empty through every pass, both of them
+    far = -3.0 * x.mean(dim=0, keepdim=True)
+    init = torch.cat([init[:5], far, far, init[5:]])
+    init[7] = x[int((y == 5).nonzero()[0])]
+    fit = ops.kmeans_fit(x.to(DEV), init.to(DEV), max_iter=6)
+    assert fit.n_iter == 2 and fit.converged and fit.empty == 2 and not bool(((fit.labels == 5) | (fit.labels == 6)).any())
+    assert torch.equal(fit.centroids[5:7].cpu().view(torch.int32), init[5:7].view(torch.int32))
+
+
+def test_more_clusters_than_rows_one_iteration_and_refusals():
+    g = torch.Generator().manual_seed(3)
+    x, init = torch.randn(5, 8, generator=g), torch.randn(9, 8, generator=g)
+    fit = ops.kmeans_fit(x.to(DEV), init.to(DEV), max_iter=3)
+    c_ref, labels_ref, sim_ref, info = R.fit(x.numpy(), init.numpy(), 3)
+    assert np.array_equal(fit.labels.cpu().numpy(), labels_ref) and [fit.n_iter, fit.empty] == [info[0], info[2]] and fit.empty >= 4
+    assert fit.converged == (info[1] == 0)
+    used = np.unique(labels_ref)
+    assert float(np.abs(fit.centroids.cpu().numpy()[used] - c_ref[used]).max()) < 1e-5
+    one = ops.kmeans_fit(x.to(DEV), init.to(DEV), max_iter=1)
+    assert one.n_iter == 1 and not one.converged                     # one pass: n changes by definition
+    labels0, sim0 = _assign(x, init)
+    assert np.array_equal(one.labels.cpu().numpy(), labels0) and np.array_equal(one.sim.cpu().numpy(), sim0)
+    xd = x.to(DEV)
+    with pytest.raises(GnnmpError):
+        ops.kmeans_fit(x, init)                                      # CPU tensors: there is no fallback
+    with pytest.raises(GnnmpError):
+        ops.kmeans_assign(x, init)
+    with pytest.raises(GnnmpError):
+        ops.contingency(torch.zeros(3, dtype=torch.int64), torch.zeros(3, dtype=torch.int64), 2, 2)
+    for kc in (0, 1025):
+        with pytest.raises(GnnmpError):
+            ops.kmeans_assign(xd, torch.zeros(kc, 8, device=DEV))
+        with pytest.raises(GnnmpError):
+            ops.kmeans_fit(xd, torch.zeros(kc, 8, device=DEV))
+    with pytest.raises(GnnmpError):
+        ops.kmeans_fit(torch.zeros(4, 257, device=DEV), torch.zeros(2, 257, device=DEV))
+    with pytest.raises(GnnmpError):
+        ops.kmeans_assign(torch.zeros(4, 257, device=DEV), torch.zeros(2, 257, device=DEV))
+    for bad in (0, 10001):
+        with pytest.raises(GnnmpError):
+            ops.kmeans_fit(xd, init.to(DEV), max_iter=bad)
+    with pytest.raises(GnnmpError):
+        ops.kmeans_assign(xd.double(), init.to(DEV).double())        # wrong dtype
+
+
+# ---------------------------------------------------------------------------- (f) the contingency table
+@pytest.mark.parametrize("classes", [1, 2, 33, 1024])
+@pytest.mark.parametrize("n", [1, 129, 5000])
+def test_contingency_equals_numpy(classes, n):
+    g = torch.Generator().manual_seed(classes + n)
+    a, b = torch.randint(0, classes, (n,), generator=g), torch.randint(0, classes, (n,), generator=g)
+    table = ops.contingency(a.to(DEV), b.to(DEV), classes, classes)
+    assert table.dtype == torch.int64 and tuple(table.shape) == (classes, classes)
+    assert np.array_equal(table.cpu().numpy(), R.contingency(a.numpy(), b.numpy(), classes, classes))
+    if classes == 33:                                                # a rectangular table
+        b2 = b % 2
+        assert np.array_equal(ops.contingency(a.to(DEV), b2.to(DEV), 33, 2).cpu().numpy(), R.contingency(a.numpy(), b2.numpy(), 33, 2))
+
+
+def test_contingency_refuses_entries_out_of_range():
+    a, b = torch.tensor([0, 1, 2], device=DEV), torch.tensor([1, 0, 1], device=DEV)
+    assert ops.contingency(a, b, 3, 2).tolist() == [[0, 1], [1, 0], [0, 1]]
+    for bad_a, bad_b in [(torch.tensor([0, 3, 2], device=DEV), b), (a, torch.tensor([1, 2, 1], device=DEV)), (torch.tensor([0, -1, 2], device=DEV), b)]:
+        with pytest.raises(GnnmpError, match="outside"):
+            ops.contingency(bad_a, bad_b, 3, 2)
+    for kw in (dict(na=0, nb=2), dict(na=3, nb=1025)):
+        with pytest.raises(GnnmpError):
+            ops.contingency(a, b, **kw)
+    with pytest.raises(GnnmpError):
+        ops.contingency(a, b[:2], 3, 2)
+
+
+# ---------------------------------------------------------------------------- (g) the probe
+def test_cluster_probe_on_planted_clusters_and_its_seed():
+    x, y = _planted()
+    xd, yd = x.to(DEV), y.to(DEV)
+    m = cluster_probe(xd, yd, CLASSES, n_init=3)
+    assert m["accuracy"] == 1.0 and m["nmi"] == 1.0 and m["ari"] == 1.0 and m["converged"] and m["empty_clusters"] == 0
+    shuffled = y[torch.randperm(y.numel(), generator=torch.Generator().manual_seed(1))]
+    s = cluster_probe(xd, shuffled.to(DEV), CLASSES, n_init=3)
+    print(f"NMI with permuted labels: {s['nmi']:.4f}")
+    assert s["nmi"] < 0.1 and s["objective"] == m["objective"]       # the clustering does not look at the labels
+    assert cluster_probe(xd, yd, CLASSES, n_init=2, init="random")["nmi"] > 0.5
+    with pytest.raises(ValueError):
+        cluster_probe(xd, yd, CLASSES, init="furthest")
+    # rows without structure: every restart ends somewhere else, so the seed shows
+    g = torch.Generator().manual_seed(9)
+    z, zy = torch.randn(400, 16, generator=g).to(DEV), torch.randint(0, 5, (400,), generator=g).to(DEV)
+    state = torch.random.get_rng_state()
+    a, b, c = cluster_probe(z, zy, 5, n_init=3, seed=0), cluster_probe(z, zy, 5, n_init=3, seed=0), cluster_probe(z, zy, 5, n_init=3, seed=1)
+    assert torch.equal(state, torch.random.get_rng_state())          # a generator of its own
+    assert a == b and a["objective"] != c["objective"]
+    assert 0 <= a["restart"] < 3 and 0.0 <= a["nmi"] <= 1.0 and -1.0 <= a["ari"] <= 1.0
+
+
+# ---------------------------------------------------------------------------- (h) end to end
+@pytest.mark.parametrize("domain,kw", [("Cora_NC", {}), ("ENZYMES", {"gc_engine": True})])
+def test_finetune_logs_the_probe_and_trains_bit_for_bit_as_without_it(domain, kw, tmp_path, monkeypatch):
+    from gnn_pretraining_amd.finetune import finetune as FT
+    monkeypatch.setattr(FT, "OUTPUT_DIR", tmp_path / "finetune")
+    calls = []
+    real = ops.kmeans_fit
+
+    def spy(*a, **k):
+        calls.append(a[1].size(0))
+        return real(*a, **k)
+
+    monkeypatch.setattr(ops, "kmeans_fit", spy)
+
+    def run(probe, log):
+        cfg = FT.FinetuneConfig(domain, "full_finetune", "b1", 1, cluster_probe=probe, **kw)
+        test = FT.finetune(cfg, epochs=1, data_root=str(tmp_path / "data"), data_scale=0.1, log_path=str(log))
+        state = torch.load(FT.OUTPUT_DIR / f"model_{cfg.exp_name}_{cfg.seed}.pt", map_location="cpu", weights_only=True)["model_state_dict"]
+        return test, state, [json.loads(line) for line in open(log)]
+
+    from gnn_pretraining_amd.constants import NUM_CLASSES
+    test, state, records = run(2, tmp_path / "on.jsonl")
+    assert len(calls) == 3 * 2 and set(calls) == {NUM_CLASSES[domain]}             # step 0, the epoch, the test split: two restarts each
+    assert 0.0 <= test["test/cluster_nmi"] <= 1.0 and 0.0 <= test["test/cluster_accuracy"] <= 1.0 and -1.0 <= test["test/cluster_ari"] <= 1.0
+    first = [r for r in records if r["step"] == 0]
+    assert len(first) == 1 and 0.0 <= first[0]["val/cluster_nmi"] <= 1.0 and records[0] is first[0]
+    per_epoch = [r for r in records if "val/accuracy" in r]
+    assert len(per_epoch) == 1 and 0.0 <= per_epoch[0]["val/cluster_nmi"] <= 1.0
+    assert all(k in records[-1] for k in ("test/cluster_nmi", "test/cluster_ari", "test/cluster_accuracy"))
+
+    n_calls = len(calls)
+    test0, state0, records0 = run(0, tmp_path / "off.jsonl")
+    assert len(calls) == n_calls                                     # off: the kernel is never reached
+    assert not any(k.startswith(("val/cluster_", "test/cluster_")) for r in records0 for k in r)
+    assert test0["test/loss"] == test["test/loss"] and test0["test/accuracy"] == test["test/accuracy"]
+    assert math.isfinite(test["test/loss"])
+    assert state.keys() == state0.keys() and all(torch.equal(state[n], state0[n]) for n in state)
