@@ -3,7 +3,7 @@ miner, process_batch per task type, one AdamW step per batch over FinetuneGNN.pa
 test metrics from the best checkpoint.  Data come from the loaders of gnn_pretraining_amd/data (processed datasets in
 data/processed; synthetic stand-ins are generated when none were exported).  wandb is replaced by a JSONL logger with the
 same metric keys.  Build-only flags: --epochs, --device, --data-root, --data-scale, --log, --sparse-features, --lp-engine, --gc-engine,
---engine-eval, --lp-ranking, --device-metrics, --miner, --knn-probe, --cluster-probe."""
+--engine-eval, --lp-ranking, --device-metrics, --miner, --knn-probe, --cluster-probe, --logreg-probe."""
 from __future__ import annotations
 
 import argparse
@@ -22,7 +22,7 @@ from ..constants import NUM_CLASSES, TASK_TYPES
 from ..graph import SparseFeatures
 from ..models.finetune_model import FinetuneGNN, create_finetune_model
 from .metrics import (compute_batch_metrics, compute_batch_metrics_device, compute_test_metrics, compute_training_metrics, compute_validation_metrics,
-                      cluster_probe, knn_probe_accuracy, ranking_metrics)
+                      cluster_probe, knn_probe_accuracy, linear_eval_probe, ranking_metrics)
 
 OUTPUT_DIR = Path(__file__).resolve().parents[2] / "outputs" / "finetune"
 BATCH_SIZES = {"ENZYMES": 32, "PTC_MR": 32, "Cora_NC": -1, "CiteSeer_NC": -1, "Cora_LP": 256, "CiteSeer_LP": 256}
@@ -106,6 +106,7 @@ class FinetuneConfig:
     miner_impl: str = "matrix"          # link-prediction domains: the hard-negative miner's top-k kernel (ops.hard_negative_topk impl), module path and lp_engine alike
     knn_probe: int = 0                  # classification domains on an engine: k of the weighted k-NN probe on the backbone's embeddings (val/ and test/knn_accuracy); 0 = off
     cluster_probe: int = 0              # classification domains on an engine: restarts of the k-means clustering probe on the backbone's embeddings (val/cluster_nmi, test/cluster_nmi / _ari / _accuracy); 0 = off
+    logreg_probe: int = 0               # classification domains on an engine: Adam iterations of the linear-evaluation probe (softmax regression fitted on the train split's embeddings: val/ and test/logreg_accuracy); 0 = off
 
     def __post_init__(self) -> None:
         if self.sparse_features and TASK_TYPES[self.domain_name] == "graph_classification":
@@ -138,6 +139,15 @@ class FinetuneConfig:
             raise ValueError(f"cluster_probe scores clusters of nodes or graphs against class labels: {self.domain_name} has no class labels")
         if self.cluster_probe and not engine_active(self):
             raise ValueError(f"cluster_probe needs an active fine-tune engine for {self.domain_name} (it reads the engine's eval-mode embed()): "
+                             + {"node_classification": "the node engine is switched off (GMP_FINETUNE_ENGINE=0)",
+                                "graph_classification": "pass gc_engine (--gc-engine)"}[TASK_TYPES[self.domain_name]])
+        if not 0 <= self.logreg_probe <= ops.LOGREG_MAX_ITER:
+            raise ValueError(f"logreg_probe={self.logreg_probe} (the number of Adam iterations, 1 <= iters <= {ops.LOGREG_MAX_ITER}; "
+                             "0 switches the probe off)")
+        if self.logreg_probe and TASK_TYPES[self.domain_name] == "link_prediction":
+            raise ValueError(f"logreg_probe fits a classifier of nodes or graphs on class labels: {self.domain_name} has no class labels")
+        if self.logreg_probe and not engine_active(self):
+            raise ValueError(f"logreg_probe needs an active fine-tune engine for {self.domain_name} (it reads the engine's eval-mode embed()): "
                              + {"node_classification": "the node engine is switched off (GMP_FINETUNE_ENGINE=0)",
                                 "graph_classification": "pass gc_engine (--gc-engine)"}[TASK_TYPES[self.domain_name]])
         if self.lp_ranking and not self.lp_engine:
@@ -407,6 +417,13 @@ def cluster_probe_scores(engine, loader, device, cfg: FinetuneConfig) -> Dict[st
     return cluster_probe(emb, y, NUM_CLASSES[cfg.domain_name], n_init=cfg.cluster_probe, seed=cfg.seed)
 
 
+def logreg_probe(engine, train_loader, loader, device, cfg: FinetuneConfig) -> float:
+    """cfg.logreg_probe: the accuracy on `loader`'s split of the softmax regression (metrics.linear_eval_probe: cfg.logreg_probe Adam
+    iterations from zero, no random state) fitted on the train split, on probe_embeddings' rows."""
+    (tr, tr_y), (q, q_y) = probe_embeddings(engine, (train_loader.dataset, loader.dataset), device, cfg)
+    return linear_eval_probe(tr, tr_y, q, q_y, NUM_CLASSES[cfg.domain_name], iters=cfg.logreg_probe)["accuracy"]
+
+
 def finetune(cfg: FinetuneConfig, epochs: Optional[int] = None, device: Optional[str] = None,
              data_root: Optional[str] = None, data_scale: float = 1.0, log_path: Optional[str] = None) -> Dict[str, float]:
     """finetune.py:334-445.  Returns the test metrics of the best-validation checkpoint."""
@@ -467,6 +484,9 @@ def finetune(cfg: FinetuneConfig, epochs: Optional[int] = None, device: Optional
     cluster_engine = (node_engine or gc_engine) if cfg.cluster_probe else None
     if cluster_engine is not None:
         logger.log({"val/cluster_nmi": cluster_probe_scores(cluster_engine, val_loader, dev, cfg)["nmi"]}, 0)
+    logreg_engine = (node_engine or gc_engine) if cfg.logreg_probe else None
+    if logreg_engine is not None:
+        logger.log({"val/logreg_accuracy": logreg_probe(logreg_engine, train_loader, val_loader, dev, cfg)}, 0)
     for epoch in range(1, (epochs or cfg.epochs) + 1):
         if node_engine is not None:
             run_training_node_engine(node_engine, train_loader, dev, epoch, global_step, cfg, logger)
@@ -488,6 +508,8 @@ def finetune(cfg: FinetuneConfig, epochs: Optional[int] = None, device: Optional
             val["val/knn_accuracy"] = knn_probe(probe_engine, train_loader, val_loader, dev, cfg)
         if cluster_engine is not None:
             val["val/cluster_nmi"] = cluster_probe_scores(cluster_engine, val_loader, dev, cfg)["nmi"]
+        if logreg_engine is not None:
+            val["val/logreg_accuracy"] = logreg_probe(logreg_engine, train_loader, val_loader, dev, cfg)
         if val[key] > best:
             best, stale = val[key], 0
             torch.save({"epoch": epoch, "model_state_dict": model.state_dict(), "val_metrics": val}, path)
@@ -507,6 +529,8 @@ def finetune(cfg: FinetuneConfig, epochs: Optional[int] = None, device: Optional
     if cluster_engine is not None:
         scores = cluster_probe_scores(cluster_engine, test_loader, dev, cfg)
         test.update({f"test/cluster_{k}": scores[k] for k in ("nmi", "ari", "accuracy")})
+    if logreg_engine is not None:
+        test["test/logreg_accuracy"] = logreg_probe(logreg_engine, train_loader, test_loader, dev, cfg)
     if cfg.lp_ranking:
         test.update(rank_test_edges(lp_engine, train_loader, val_loader, test_loader, dev))
     logger.log(test, global_step[0])
@@ -542,6 +566,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help="classification domains on an engine: also log val/cluster_nmi (every epoch and once before training) and test/cluster_nmi, "
                         "test/cluster_ari, test/cluster_accuracy, spherical k-means (k = the number of classes, N_INIT restarts, 1..64, k-means++) on "
                         "the backbone's embeddings; 0 = off")
+    p.add_argument("--logreg-probe", type=int, default=0, metavar="ITERS",
+                   help="classification domains on an engine: also log val/logreg_accuracy (every epoch and once before training) and "
+                        "test/logreg_accuracy, linear evaluation: a softmax regression fitted on the train split's embeddings (ITERS full-batch Adam "
+                        "iterations from zero, 1..10000, lr 0.01, rows L2-normalised) and scored on the split; 0 = off")
     return p
 
 
@@ -550,7 +578,8 @@ def config_from_args(a: argparse.Namespace) -> FinetuneConfig:
                           lp_engine=getattr(a, "lp_engine", False), gc_engine=getattr(a, "gc_engine", False),
                           engine_eval=getattr(a, "engine_eval", False), lp_ranking=getattr(a, "lp_ranking", False),
                           device_metrics=getattr(a, "device_metrics", False), miner_impl=getattr(a, "miner", "matrix"),
-                          knn_probe=getattr(a, "knn_probe", 0), cluster_probe=getattr(a, "cluster_probe", 0))
+                          knn_probe=getattr(a, "knn_probe", 0), cluster_probe=getattr(a, "cluster_probe", 0),
+                          logreg_probe=getattr(a, "logreg_probe", 0))
 
 
 def main() -> None:

@@ -129,6 +129,30 @@ def knn_probe_accuracy(db_emb: Tensor, db_labels: Tensor, query_emb: Tensor, que
     return {"accuracy": correct / n, "correct": correct, "num_samples": n}
 
 
+def linear_eval_probe(train_emb: Tensor, train_labels: Tensor, emb: Tensor, labels: Tensor, num_classes: int, iters: int = 100,
+                      lr: float = 0.01, l2: float = 0.0) -> Dict:
+    """Linear evaluation of frozen embeddings (the protocol of DGI, GRACE, GraphCL, InfoGraph): a multinomial logistic regression is
+    fitted on the L2-normalised train embeddings (ops.logreg_fit: csrc/logreg.hip, `iters` full-batch Adam updates from zero, all
+    enqueued at once) and scored on the rows of `emb` (ops.logreg_predict).  Embeddings fp32 [n, d <= 256] and labels int64 [n] in
+    [0, num_classes <= 32) on the GPU.  Returns {"accuracy": correct / num_samples, "correct", "num_samples", "train_loss" (the loss
+    before the last update), "train_accuracy"}: the accuracies are ratios of integers counted on the device, and everything comes back
+    in one read-back.  Nothing here feeds back into training."""
+    from .. import ops
+    n, n_train = int(labels.numel()), int(train_labels.numel())
+    if n == 0 or n_train == 0:
+        raise ValueError(f"linear_eval_probe: {n_train} train rows, {n} rows to score")
+    x_train, y_train = train_emb.detach().contiguous(), train_labels.to(torch.int64).contiguous()
+    fit, status = ops._logreg_enqueue(x_train, y_train, num_classes, iters, lr, l2, None, False, False)
+    pred = ops.logreg_predict(emb.detach().contiguous(), fit.state.weight, fit.state.bias)
+    pred_train = ops.logreg_predict(x_train, fit.state.weight, fit.state.bias)
+    words = torch.stack([status[0].double(), (pred == labels.to(torch.int64)).sum().double(), (pred_train == y_train).sum().double(),
+                         fit.loss_history[-1].double()]).tolist()                # the one read-back (the counts are exact in a double)
+    bad, correct, correct_train, loss = int(words[0]), int(words[1]), int(words[2]), float(words[3])
+    if bad:
+        raise ValueError(f"linear_eval_probe: {bad} train rows have a label outside [0, {num_classes})")
+    return {"accuracy": correct / n, "correct": correct, "num_samples": n, "train_loss": loss, "train_accuracy": correct_train / n_train}
+
+
 def clustering_scores(table) -> Dict[str, float]:
     """NMI (arithmetic normalisation), ARI, purity and accuracy of a clustering against class labels, in float64 on the host from the
     integer contingency table alone: table [clusters, classes] with [k, c] = rows of cluster k and class c (ops.contingency).  Clusters

@@ -1260,6 +1260,105 @@ def contingency(a: Tensor, b: Tensor, na: int, nb: int) -> Tensor:
     return table
 
 
+LOGREG_MAX_CLASSES, LOGREG_MAX_DIM, LOGREG_MAX_ITER = 32, 256, 10000           # gmp_logreg_fit / gmp_logreg_predict (gnnmp.h)
+
+
+class LogRegState(NamedTuple):
+    """What a softmax-regression fit resumes from: the parameters, Adam's two moments on the block (W | b), and the number of updates."""
+    weight: Tensor      # [C, d]
+    bias: Tensor        # [C]
+    exp_avg: Tensor     # [C, d + 1]
+    exp_avg_sq: Tensor  # [C, d + 1]
+    step: Tensor        # int64 [1], on the device
+
+
+class LogRegFit(NamedTuple):
+    state: LogRegState
+    loss_history: Tensor            # [iters]: entry k = the loss at the parameters before update k of this call
+    grad: Optional[Tensor] = None   # [C, d + 1]: (gW | gb) of the last iteration as the update saw it (return_grad)
+    logits: Optional[Tensor] = None  # [n, C]: the logits of the last iteration (return_logits)
+
+
+def logreg_init(num_classes: int, dim: int, device) -> LogRegState:
+    """The defined starting point of logreg_fit: everything zero (the problem is convex; no random state is involved)."""
+    c, d = int(num_classes), int(dim)
+    if not 2 <= c <= LOGREG_MAX_CLASSES or not 1 <= d <= LOGREG_MAX_DIM:
+        raise L.GnnmpError(f"logreg_init: num_classes={num_classes} dim={dim} (2 <= num_classes <= {LOGREG_MAX_CLASSES}, 1 <= dim <= {LOGREG_MAX_DIM})")
+    return LogRegState(torch.zeros(c, d, device=device), torch.zeros(c, device=device), torch.zeros(c, d + 1, device=device),
+                       torch.zeros(c, d + 1, device=device), torch.zeros(1, dtype=torch.int64, device=device))
+
+
+def _logreg_enqueue(x: Tensor, labels: Tensor, num_classes: int, iters: int, lr: float, l2: float, state: Optional[LogRegState],
+                    return_grad: bool, return_logits: bool) -> Tuple[LogRegFit, Tensor]:
+    """logreg_fit without the read-back: (the fit, status int32 [1] still on the device) -- for callers that read it with other words."""
+    _need(x, torch.float32, "x", 2); _need(labels, torch.int64, "labels", 1)
+    n, d = x.shape
+    c = int(num_classes)
+    if labels.numel() != n or labels.device != x.device:
+        raise L.GnnmpError(f"logreg_fit: x {tuple(x.shape)} on {x.device}, labels [{labels.numel()}] on {labels.device}")
+    if not 2 <= c <= LOGREG_MAX_CLASSES or not 1 <= d <= LOGREG_MAX_DIM or not 1 <= int(iters) <= LOGREG_MAX_ITER:
+        raise L.GnnmpError(f"logreg_fit: num_classes={num_classes} dim={d} iters={iters} (2 <= num_classes <= {LOGREG_MAX_CLASSES}, "
+                           f"1 <= dim <= {LOGREG_MAX_DIM}, 1 <= iters <= {LOGREG_MAX_ITER})")
+    if not float(lr) > 0.0 or not float(l2) >= 0.0:
+        raise L.GnnmpError(f"logreg_fit: lr={lr} l2={l2} (lr > 0, l2 >= 0)")
+    dev, l = x.device, L.lib()
+    if state is None:
+        state = logreg_init(c, d, dev)
+    else:
+        want = ((c, d), (c,), (c, d + 1), (c, d + 1), (1,))
+        dtypes = (torch.float32,) * 4 + (torch.int64,)
+        for t, shape, dtype, name in zip(state, want, dtypes, LogRegState._fields):
+            _need(t, dtype, f"state.{name}")
+            if tuple(t.shape) != shape or t.device != dev:
+                raise L.GnnmpError(f"logreg_fit: state.{name} {tuple(t.shape)} on {t.device} (expected {shape} on {dev})")
+        state = LogRegState(*(t.clone() for t in state))            # the caller's state is left alone
+    loss = torch.zeros(int(iters), device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    grad = torch.zeros(c, d + 1, device=dev) if return_grad else None
+    logits = torch.zeros(n, c, device=dev) if return_logits else None
+    ws = _ws(l.gmp_logreg_workspace_bytes(n, c, d), dev)
+    L.check(l.gmp_logreg_fit(_ptr(x), _ptr(labels), n, c, d, int(iters), float(lr), float(l2), _ptr(state.weight), _ptr(state.bias),
+                             _ptr(state.exp_avg), _ptr(state.exp_avg_sq), _ptr(state.step), _ptr(loss), _ptr(status), _ptr(grad), _ptr(logits),
+                             _ptr(ws), ws.numel(), _stream(x)), "gmp_logreg_fit")
+    return LogRegFit(state, loss, grad, logits), status
+
+
+def logreg_fit(x: Tensor, labels: Tensor, num_classes: int, iters: int = 100, lr: float = 0.01, l2: float = 0.0,
+               state: Optional[LogRegState] = None, return_grad: bool = False, return_logits: bool = False) -> LogRegFit:
+    """Softmax regression on the L2-normalised rows of x [n, d <= 256] (fp32, on the GPU) against labels int64 [n] in [0, num_classes),
+    2 <= num_classes <= 32 (gnnmp.h gmp_logreg_fit; csrc/logreg.hip): `iters` full-batch Adam updates (torch.optim.Adam's rule, lr, ridge
+    l2 on the weights alone) of the mean cross-entropy, enqueued at once, two launches each, without a host round trip, an [n, C] array or
+    a floating-point atomic: bitwise repeatable, and T iterations in one call equal T calls of one chained through `state`.  Starts from
+    `state` (cloned, never mutated) or from logreg_init's zeros.  Returns LogRegFit(state, loss_history [iters], grad, logits): the last
+    two are test hooks (None unless asked for) and change nothing else.  Raises when a label lies outside its range (the one read-back)."""
+    fit, status = _logreg_enqueue(x, labels, num_classes, iters, lr, l2, state, return_grad, return_logits)
+    bad = int(status.item())
+    if bad:
+        raise L.GnnmpError(f"logreg_fit: {bad} rows have a label outside [0, {num_classes})")
+    return fit
+
+
+def logreg_predict(x: Tensor, weight: Tensor, bias: Tensor, return_logits: bool = False):
+    """pred [n] int64 = the class of the greatest logit <xn_i, W_c> + b_c of every row of x [n, d], rows normalised and logits computed
+    exactly as logreg_fit does (gnnmp.h gmp_logreg_predict); ties to the lower class.  weight [C, d] and bias [C] fp32 on the GPU.
+    return_logits adds the [n, C] logits as a second result."""
+    _need(x, torch.float32, "x", 2); _need(weight, torch.float32, "weight", 2); _need(bias, torch.float32, "bias", 1)
+    n, d = x.shape
+    c = weight.size(0)
+    if weight.size(1) != d or bias.numel() != c or weight.device != x.device or bias.device != x.device:
+        raise L.GnnmpError(f"logreg_predict: x {tuple(x.shape)} on {x.device}, weight {tuple(weight.shape)} on {weight.device}, "
+                           f"bias {tuple(bias.shape)} on {bias.device}")
+    if not 2 <= c <= LOGREG_MAX_CLASSES or not 1 <= d <= LOGREG_MAX_DIM:
+        raise L.GnnmpError(f"logreg_predict: num_classes={c} dim={d} (2 <= num_classes <= {LOGREG_MAX_CLASSES}, 1 <= dim <= {LOGREG_MAX_DIM})")
+    dev, l = x.device, L.lib()
+    pred = torch.zeros(n, dtype=torch.int64, device=dev)
+    logits = torch.zeros(n, c, device=dev) if return_logits else None
+    ws = _ws(l.gmp_logreg_workspace_bytes(n, c, d), dev)
+    L.check(l.gmp_logreg_predict(_ptr(x), n, _ptr(weight), _ptr(bias), c, d, _ptr(pred), _ptr(logits), _ptr(ws), ws.numel(), _stream(x)),
+            "gmp_logreg_predict")
+    return (pred, logits) if return_logits else pred
+
+
 CLS_MAX_ROWS, CLS_MAX_CLASSES = 262144, 32      # gmp_cls_counts: the pair count is n^2 compares (gnnmp.h)
 
 

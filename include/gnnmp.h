@@ -412,6 +412,45 @@ int gmp_kmeans_fit(const float* x, int64_t n, const float* init, int kc, int dim
 int gmp_contingency(const int64_t* a, const int64_t* b, int64_t n, int na, int nb, int64_t* table, int32_t* status, gmp_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
+ * Softmax regression (the linear-evaluation probe for self-supervised embeddings: a multinomial logistic regression fitted with Adam on
+ * frozen rows): x [n, dim] contiguous fp32, labels [n] int64, W [classes, dim], b [classes].  Rows are normalised as gmp_knn_topk and
+ * gmp_kmeans_* do, xn_i = x_i / max(||x_i||, 1e-12) with the stride padded with zeros (a zero row scores b alone); the copy is made once
+ * per call and lives in the workspace.  All in fp32 unless said otherwise:
+ *   logits   z[i, c] = <xn_i, W_c> + b_c, the k-ordered fp32 MFMA chain of csrc/sim_tile.h;  p_i = softmax(z_i) with the row maximum
+ *            subtracted;  row loss = logsumexp(z_i) - z[i, y_i]
+ *   loss     L = S_L / n + (l2 / 2) sum(W^2), S_L the sum of the row losses
+ *   gradient gW = S_W / n + l2 W, gb = S_b / n; S_W[c, :] = the unscaled sum over rows of (p[i, c] - [y_i == c]) xn_i, S_b[c] the sum of
+ *            (p[i, c] - [y_i == c]); each entry is divided by n once, a correctly rounded fp32 division.  The ridge term acts on W only.
+ *   update   Adam as torch.optim.Adam (no amsgrad) on the [classes, dim + 1] block (W | b): t += 1; m = b1 m + (1 - b1) g;
+ *            v = b2 v + (1 - b2) g g; theta -= lr / (1 - b1^t) m / (sqrt(v) / sqrt(1 - b2^t) + eps); b1 = 0.9, b2 = 0.999, eps = 1e-8 (the
+ *            two bias corrections in double, as torch computes them)
+ * gmp_logreg_fit enqueues `iters` iterations on `stream`, two launches each (the row pass: logits, softmax, loss and the S_W / S_b
+ *   partial sums of a workgroup from ONE read of each normalised row; then reduce + ridge + Adam + loss + step count), with no host
+ *   synchronisation.  W, b, exp_avg and exp_avg_sq [classes, dim + 1] and step int64 [1] (a device word) are read and written in place;
+ *   loss_history [iters]: entry k = L at the parameters before update k of this call.  The row pass runs min(ceil(n / 128), 256) workgroups
+ *   that walk the 128-row tiles with a grid stride; each writes its sums to its own workspace slot and the slots are added in ascending
+ *   order: no floating-point atomics, so one call of T iterations leaves the same bits as T calls of one, and two runs on the same input
+ *   leave the same bits.  A row whose label lies outside [0, classes) contributes nothing and is counted in status int32 [1] (zeroed
+ *   inside the call); n in the divisions stays n.  No [n, classes] array exists unless logits_out is given.
+ *   Hooks for tests and diagnostics, NULL otherwise: grad_out [classes, dim + 1] = (gW | gb) of the call's LAST iteration exactly as the
+ *   update saw it, logits_out [n, classes] = the logits of that iteration.  They change no other output bit.
+ * gmp_logreg_predict: the same normalisation and logits; pred [n] int64 = the argmax, ties to the lower class (integer compares on
+ *   (score bits, ~class), as gmp_kmeans_assign); logits_out NULL or [n, classes].
+ * 0 <= n < 2^31, 2 <= classes <= 32, 1 <= dim <= 256, 1 <= iters <= 10000: GMP_ERR_ARG outside those ranges or on a NULL pointer,
+ * GMP_ERR_WORKSPACE when workspace_bytes < gmp_logreg_workspace_bytes(n, classes, dim); nothing is launched then.  n == 0 is a no-op (no
+ * output is touched), GMP_OK.  gmp_logreg_workspace_bytes = 4 n dpad + 4 min(ceil(n / 128), 256) slot + a constant below 1 KiB, dpad = dim
+ * rounded up to 4, slot = classes dpad + classes + 2 rounded up to 64 (the normalised rows and one slot of partial sums per workgroup of
+ * the row pass: at most 8.1 MiB beside the normalised copy), 0 for sizes outside the ranges.  Asynchronous on `stream`, no allocation, no
+ * global state.
+ * ------------------------------------------------------------------------- */
+size_t gmp_logreg_workspace_bytes(int64_t n, int classes, int dim);
+int gmp_logreg_fit(const float* x, const int64_t* labels, int64_t n, int classes, int dim, int iters, float lr, float l2, float* W, float* b,
+                   float* exp_avg, float* exp_avg_sq, int64_t* step, float* loss_history, int32_t* status, float* grad_out, float* logits_out,
+                   void* workspace, size_t workspace_bytes, gmp_stream_t stream);
+int gmp_logreg_predict(const float* x, int64_t n, const float* W, const float* b, int classes, int dim, int64_t* pred, float* logits_out,
+                       void* workspace, size_t workspace_bytes, gmp_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
  * Integer counts for the classification metrics of fine-tuning (src/finetune/metrics.py:39-82: accuracy, F1, precision, recall and the
  * one-vs-rest ROC AUC of scikit-learn), from targets [n] int64, predictions [n] int64 and probabilities [n, classes] fp32 contiguous:
  *   confusion  int64 [classes * classes]  entry [t * classes + p] = rows with target t and prediction p

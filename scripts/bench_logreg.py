@@ -1,0 +1,129 @@
+"""Time per iteration and peak memory of the softmax-regression fit of the linear-evaluation probe (ops.logreg_fit: csrc/logreg.hip)
+beside the route a user has without it: the same loop in torch (F.normalize once, then x @ W.T + b, cross_entropy, autograd and
+torch.optim.Adam: a dozen launches per iteration, two passes over the embeddings and the n x classes logits with their gradient).
+Cases (n, classes) at d = 256: (2,708, 7), (19,717, 3), (65,535, 32), seeded randn rows around one centre per class, labels i % classes,
+100 iterations per call (neither route reads anything back inside the loop; the fit's one read-back of its status word at the end is
+inside its time).  Per case and route: the median over alternated rounds of the mean call time after warm-up divided by the
+iterations, the spread over the rounds, and torch.cuda.max_memory_allocated over one call (absolute, and above what was allocated
+before the call: the inputs); plus how far the two routes' weights and last losses are apart.  A second block records the whole fit of
+the four blob cases of tests/test_gpu_logreg.py against the float64 reference of tests/logreg_ref.py (final loss, max |W - W_fp64|,
+train accuracy).  No bar on time or memory.
+    python scripts/bench_logreg.py --out profiles/logreg.json"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+from gnn_pretraining_amd import ops                                               # noqa: E402
+
+CASES = [(2708, 7), (19717, 3), (65535, 32)]
+
+
+def torch_route(x, y, classes, iters, lr):
+    xn = F.normalize(x, dim=1)
+    W = torch.zeros(classes, x.size(1), device=x.device, requires_grad=True)
+    b = torch.zeros(classes, device=x.device, requires_grad=True)
+    opt = torch.optim.Adam([W, b], lr=lr)
+    for _ in range(iters):
+        opt.zero_grad(set_to_none=True)
+        loss = F.cross_entropy(xn @ W.t() + b, y)
+        loss.backward()
+        opt.step()
+    return W.detach(), b.detach(), loss.detach()
+
+
+def timed(fn, reps):
+    for _ in range(2):
+        fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / reps * 1e3          # us
+
+
+def peak_bytes(fn):
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    before = torch.cuda.memory_allocated()
+    torch.cuda.reset_peak_memory_stats()
+    out = fn()
+    torch.cuda.synchronize()
+    peak = torch.cuda.max_memory_allocated()
+    del out
+    return peak, peak - before
+
+
+def blob_rows():
+    import logreg_ref as R
+    rows = []
+    for n, d, classes, noise in R.BLOB_CASES:
+        x, y = R.blobs(n, d, classes, noise)
+        W64, _, _, _, _, hist = R.fit(x, y, classes, 100, 0.01)
+        xd, yd = torch.from_numpy(x).cuda(), torch.from_numpy(y).cuda()
+        fit = ops.logreg_fit(xd, yd, classes, iters=100, lr=0.01)
+        pred = ops.logreg_predict(xd, fit.state.weight, fit.state.bias)
+        rows.append({"n": n, "d": d, "classes": classes, "noise": noise, "iterations": 100, "final_loss": float(fit.loss_history[-1]),
+                     "final_loss_fp64": float(hist[-1]), "max_abs_weight_minus_fp64": float(np.abs(fit.state.weight.cpu().numpy() - W64).max()),
+                     "train_accuracy": float((pred == yd).float().mean())})
+        print(json.dumps(rows[-1]), flush=True)
+    return rows
+
+
+def main():
+    p = argparse.ArgumentParser()
+    p.add_argument("--out", type=str, default=None, help="also write the rows to this JSON file")
+    p.add_argument("--d", type=int, default=256)
+    p.add_argument("--iterations", type=int, default=100, help="Adam iterations per call")
+    p.add_argument("--rounds", type=int, default=3, help="alternated rounds per case")
+    p.add_argument("--reps", type=int, default=5, help="calls per round at fewer than 10,000 rows (2 above)")
+    a = p.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_logreg.py measures on the GPU: no device found")
+    rows = []
+    for n, classes in CASES:
+        g = torch.Generator().manual_seed(0)
+        y = torch.arange(n) % classes
+        x = (torch.randn(classes, a.d, generator=g)[y] + torch.randn(n, a.d, generator=g)).cuda()
+        y = y.cuda()
+        routes = {"logreg_fit": lambda: ops.logreg_fit(x, y, classes, iters=a.iterations, lr=0.01),
+                  "torch": lambda: torch_route(x, y, classes, a.iterations, 0.01)}
+        reps = a.reps if n < 10000 else 2
+        times = {r: [] for r in routes}
+        for _ in range(a.rounds):
+            for r, fn in routes.items():
+                times[r].append(timed(fn, reps) / a.iterations)
+        row = {"n": n, "classes": classes, "d": a.d, "iterations": a.iterations, "reps": reps, "rounds": a.rounds, "logits_bytes": 4 * n * classes}
+        for r, fn in routes.items():
+            t = sorted(times[r])
+            row[f"{r}_us_per_iteration"] = round(t[len(t) // 2], 1)
+            row[f"{r}_us_per_iteration_rounds"] = [round(v, 1) for v in times[r]]
+            row[f"{r}_peak_bytes"], row[f"{r}_peak_bytes_above_inputs"] = peak_bytes(fn)
+        fit, (tw, tb, tl) = routes["logreg_fit"](), routes["torch"]()
+        row["max_abs_weight_difference"] = float((fit.state.weight - tw).abs().max())
+        row["last_loss_logreg_fit"], row["last_loss_torch"] = float(fit.loss_history[-1]), float(tl)
+        row["logreg_over_torch_time"] = round(row["logreg_fit_us_per_iteration"] / row["torch_us_per_iteration"], 3)
+        row["logreg_over_torch_peak_above_inputs"] = round(row["logreg_fit_peak_bytes_above_inputs"] / row["torch_peak_bytes_above_inputs"], 4)
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+        del x, y, routes, fit
+    blobs = blob_rows()
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump({"device": torch.cuda.get_device_name(0), "rows": rows, "blob_fits": blobs}, f, indent=1)
+            f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
