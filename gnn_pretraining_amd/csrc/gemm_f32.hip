@@ -466,11 +466,7 @@ int launch_pipe_cfg(const GemmArgs& g, int tiles_m, int tiles_n, int z, hipStrea
     // a workgroup may ask for up to 160 KiB of LDS once the function says so -- per DEVICE (the attribute belongs to the device's copy of
     // the function): one bit per device ordinal, set after the call succeeded there; racing threads at worst both make the (idempotent) call
     static std::atomic<uint64_t> attr_set{0};
-    if (!gmp::lds_attr_done(attr_set)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES) != hipSuccess)
-            return gmp::fail(GMP_ERR_LAUNCH, "gemm_pipe: cannot reserve %d bytes of LDS", C::LDS_BYTES);
-        gmp::lds_attr_mark(attr_set);
-    }
+    if (int rc = gmp::reserve_lds(attr_set, reinterpret_cast<const void*>(kern), C::LDS_BYTES, "gemm_pipe")) return rc;
     hipLaunchKernelGGL(kern, dim3((unsigned)(tiles_m * tiles_n), 1, (unsigned)z), dim3(g2::THREADS), C::LDS_BYTES, st, g, tiles_m, tiles_n);
     return gmp::check_launch("gemm_pipe_kernel");
 }
@@ -481,11 +477,7 @@ int launch_pipe_gen(const GemmArgs& g, int64_t rows, int z, hipStream_t st) {
     using C = g2::Cfg<1, 1, KC, KC, 4, 4>;
     auto kern = g2::gemm_pipe_kernel<1, 1, KC, KC, 4, 4, false, GEN>;
     static std::atomic<uint64_t> attr_set{0};
-    if (!gmp::lds_attr_done(attr_set)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES) != hipSuccess)
-            return gmp::fail(GMP_ERR_LAUNCH, "gemm_pipe (generated operand): cannot reserve %d bytes of LDS", C::LDS_BYTES);
-        gmp::lds_attr_mark(attr_set);
-    }
+    if (int rc = gmp::reserve_lds(attr_set, reinterpret_cast<const void*>(kern), C::LDS_BYTES, "gemm_pipe (generated operand)")) return rc;
     const int tiles_m = (int)((rows + 63) / 64), tiles_n = (int)((g.N + 63) / 64);
     hipLaunchKernelGGL(kern, dim3((unsigned)(tiles_m * tiles_n), 1, (unsigned)z), dim3(g2::THREADS), C::LDS_BYTES, st, g, tiles_m, tiles_n);
     return gmp::check_launch("gemm_pipe_kernel (generated operand)");
@@ -884,11 +876,7 @@ extern "C" int gmp_lp_feat_gemm_bwd_fold(const float* gy1, const float* w0, cons
     using C = g2::Cfg<1, 1, true, false, 4>;
     auto kern = g2::lp_bwd_fold_kernel;
     static std::atomic<uint64_t> attr_set{0};
-    if (!gmp::lds_attr_done(attr_set)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES) != hipSuccess)
-            return gmp::fail(GMP_ERR_LAUNCH, "lp_feat_gemm_bwd_fold: cannot reserve %d bytes of LDS", C::LDS_BYTES);
-        gmp::lds_attr_mark(attr_set);
-    }
+    if (int rc = gmp::reserve_lds(attr_set, reinterpret_cast<const void*>(kern), C::LDS_BYTES, "lp_feat_gemm_bwd_fold")) return rc;
     const int tiles_m = (int)((K + C::BM - 1) / C::BM);
     if (gmp::lane_takes((hipStream_t)stream)) g_lp_fold_launches.fetch_add(1, std::memory_order_relaxed);      // (one count per launch, whichever lane makes it)
     hipLaunchKernelGGL(kern, dim3((unsigned)(tiles_m * (256 / C::BN))), dim3(g2::THREADS), C::LDS_BYTES, (hipStream_t)stream, a, tiles_m);

@@ -66,6 +66,14 @@ inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 inline int cur_device() { int d = 0; (void)hipGetDevice(&d); return d; }
 inline bool lds_attr_done(const std::atomic<uint64_t>& m) { const int d = cur_device(); return d < 64 && ((m.load(std::memory_order_acquire) >> d) & 1ull); }
 inline void lds_attr_mark(std::atomic<uint64_t>& m) { const int d = cur_device(); if (d < 64) m.fetch_or(1ull << d, std::memory_order_release); }
+// more than 64 KiB of dynamic LDS for `kernel`: the opt-in, made once per device
+inline int reserve_lds(std::atomic<uint64_t>& done, const void* kernel, int bytes, const char* who) {
+    if (lds_attr_done(done)) return GMP_OK;
+    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess)
+        return fail(GMP_ERR_LAUNCH, "%s: cannot reserve %d bytes of LDS", who, bytes);
+    lds_attr_mark(done);
+    return GMP_OK;
+}
 
 // ---- Philox4x32-10 (counter-based RNG for dropout; mask is regenerated in the
 // backward pass from (seed, stream, element) instead of being stored) ----------
@@ -139,8 +147,38 @@ __device__ __forceinline__ float from_orderable(uint32_t u) {
     return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
 }
 
+// 64-bit selection key: the orderable score bits (high word), then `low`, which every caller passes as 0xffffffff - index: a greater key is
+// a higher score, then a lower index.  And back: the index behind the low word, the score.
+typedef unsigned long long u64;
+__device__ __forceinline__ u64 pack_key(float v, uint32_t low) { return ((u64)orderable(v) << 32) | (u64)low; }
+__device__ __forceinline__ uint32_t key_low(u64 key) { return 0xffffffffu - (uint32_t)key; }
+__device__ __forceinline__ float key_score(u64 key) { return from_orderable((uint32_t)(key >> 32)); }
+
+// the wave's earlier LDS writes are visible to its later reads: all that data private to one wave needs
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 // workspace slices start on 256 bytes
 inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// A workspace handed out slice by slice.  `align` moves the base up to the next 256 bytes and counts those 256 in total(); carving a
+// null base gives the size to ask for.
+class Carver {
+    char *base, *q;
+    bool align;
+public:
+    Carver(void* ws, bool align) : base(align ? (char*)(((uintptr_t)ws + 255) / 256 * 256) : (char*)ws), q(base), align(align) {}
+    template <typename T>
+    T* take(size_t count) {
+        T* p = (T*)q;
+        q += al(count * sizeof(T));
+        return p;
+    }
+    size_t total() const { return (size_t)(q - base) + (align ? 256 : 0); }
+};
 
 }  // namespace gmp
 

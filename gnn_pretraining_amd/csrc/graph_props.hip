@@ -316,12 +316,7 @@ extern "C" int gmp_graph_props(const int64_t* ptr, const int64_t* eptr, const in
     if (!two) return GMP_OK;
     const int cap_l = (int)std::min<int64_t>(max_graph_nodes, LARGE_N);
     static std::atomic<uint64_t> attr_set{0};                        // once per device, for the largest graph the instance takes
-    if (!gmp::lds_attr_done(attr_set)) {
-        if (hipFuncSetAttribute((const void*)graph_props_kernel<LARGE_N / 64, 1024>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds_bytes(LARGE_N)) != hipSuccess)
-            return gmp::fail(GMP_ERR_LAUNCH, "graph_props: LDS attribute");
-        gmp::lds_attr_mark(attr_set);
-    }
+    if (int rc = gmp::reserve_lds(attr_set, (const void*)graph_props_kernel<LARGE_N / 64, 1024>, (int)lds_bytes(LARGE_N), "graph_props")) return rc;
     hipLaunchKernelGGL((graph_props_kernel<LARGE_N / 64, 1024>), grid, dim3(1024), lds_bytes(cap_l), st, ptr, eptr, edge_index, num_edges,
                        SMALL_N + 1, cap_l, 1, counts, clustering_sum);
     return gmp::check_launch("graph_props_kernel<16>");

@@ -30,6 +30,8 @@ struct SelectState {
 
 using gmp::al;
 
+// gmp::pack_key with the inversion of the flat index inside: written through pack_key, hipcc allocates the histogram and gather kernels'
+// registers differently, so this file keeps its own spelling
 __device__ __forceinline__ unsigned long long make_key(float v, uint32_t flat) {
     return ((unsigned long long)gmp::orderable(v) << 32) | (unsigned long long)(0xffffffffu - flat);
 }
@@ -169,10 +171,10 @@ __global__ __launch_bounds__(THREADS) void hn_rank_kernel(const unsigned long lo
         for (int j = 0; j < lim; ++j) rank += tile[j] > mine;
     }
     if (i < k) {
-        const uint32_t flat = 0xffffffffu - (uint32_t)(mine & 0xffffffffull);
+        const uint32_t flat = gmp::key_low(mine);
         out_edges[rank] = (int64_t)(flat / (uint32_t)n);
         out_edges[k + rank] = (int64_t)(flat % (uint32_t)n);
-        if (out_scores) out_scores[rank] = gmp::from_orderable((uint32_t)(mine >> 32));
+        if (out_scores) out_scores[rank] = gmp::key_score(mine);
     }
 }
 

@@ -28,7 +28,6 @@
 
 namespace {
 
-using gmp::al;
 using namespace sim;
 
 constexpr int MAX_TPC = 32;         // column tiles per chunk: a mask bitmap of 128 rows x 1024 columns = 16 KiB
@@ -39,8 +38,6 @@ constexpr int64_t MAX_N = 1 << 20;
 constexpr int FLAT_BITS = 40;
 constexpr unsigned long long FLAT_MAX = (1ull << FLAT_BITS) - 1ull;
 enum { HIST = 0, GATHER = 1, DUMP = 2 };
-
-typedef unsigned long long u64;
 
 // first in the workspace: `passes` is readable by the caller after the call (how many histogram passes ran)
 struct State {
@@ -62,7 +59,7 @@ struct Plan {
 
 Plan make_plan(int64_t n, int64_t d) {
     Plan p;
-    p.dpad = (int)((d + 3) / 4 * 4);
+    p.dpad = pad4(d);
     p.tiles = (int)((n + BM - 1) / BM);
     p.nct = (int)((n + BN - 1) / BN);
     int c = (512 + p.tiles - 1) / p.tiles;              // half of the blocks lie under the diagonal and leave at once: one round of 256 CUs             // about half of the blocks lie under the diagonal and leave at once
@@ -85,24 +82,22 @@ struct Ws {
 };
 
 Ws carve(void* ws, int64_t n, int64_t d, int64_t E) {
-    char* q = (char*)ws;
+    gmp::Carver c(ws, false);
     Ws w;
-    const size_t dpad = (size_t)((d + 3) / 4 * 4);
-    w.st = (State*)q; q += al(sizeof(State));
-    w.zn = (float*)q; q += al((size_t)n * dpad * 4);
-    w.cand_s = (unsigned int*)q; q += al((size_t)CAP * 4);
-    w.cand_f = (u64*)q; q += al((size_t)CAP * 8);
-    w.rowptr = (int*)q; q += al((size_t)(n + 1) * 4);
-    w.rowptr_t = (int*)q; q += al((size_t)(n + 1) * 4);
-    w.col = (int*)q; q += al((size_t)E * 4);
-    w.perm = (int*)q; q += al((size_t)E * 4);
-    w.col_t = (int*)q; q += al((size_t)E * 4);
-    w.perm_t = (int*)q; q += al((size_t)E * 4);
-    w.status = (int*)q; q += 256;
-    w.csr_ws = q;
+    w.st = c.take<State>(1);
+    w.zn = c.take<float>((size_t)n * pad4(d));
+    w.cand_s = c.take<unsigned int>(CAP);
+    w.cand_f = c.take<u64>(CAP);
+    w.rowptr = c.take<int>((size_t)n + 1);
+    w.rowptr_t = c.take<int>((size_t)n + 1);
+    w.col = c.take<int>((size_t)E);
+    w.perm = c.take<int>((size_t)E);
+    w.col_t = c.take<int>((size_t)E);
+    w.perm_t = c.take<int>((size_t)E);
+    w.status = c.take<int>(1);
     w.csr_ws_bytes = gmp_csr_build_workspace_bytes(n, E);
-    q += al(w.csr_ws_bytes);
-    w.total = (size_t)(q - (char*)ws);
+    w.csr_ws = c.take<char>(w.csr_ws_bytes);
+    w.total = c.total();
     return w;
 }
 
@@ -382,15 +377,10 @@ template <int MODE>
 void launch_tiles(const Plan& p, int64_t n, const Ws& w, bool mask, int is_flat, int shift, int bits, float* scores_out, hipStream_t st) {
     const dim3 grid((unsigned)p.tiles, (unsigned)p.C), block(THREADS);
     const int* rp = mask ? w.rowptr : nullptr;
-#define HNS_LAUNCH(DP)                                                                                                                       \
-    hipLaunchKernelGGL((hns_tile_kernel<DP, MODE>), grid, block, 0, st, (const float*)w.zn, n, p.dpad, p.tpc, p.nct, rp, (const int*)w.col,    \
-                       (const int*)w.rowptr_t, (const int*)w.col_t, w.st, is_flat, shift, bits, w.cand_s, w.cand_f, scores_out)
-    if (p.dpad <= 32) HNS_LAUNCH(32);
-    else if (p.dpad <= 64) HNS_LAUNCH(64);
-    else if (p.dpad <= 128) HNS_LAUNCH(128);
-    else if (p.dpad <= 192) HNS_LAUNCH(192);
-    else HNS_LAUNCH(256);
-#undef HNS_LAUNCH
+    dispatch_dp(p.dpad, [&](auto dp) {
+        hipLaunchKernelGGL((hns_tile_kernel<dp(), MODE>), grid, block, 0, st, (const float*)w.zn, n, p.dpad, p.tpc, p.nct, rp, (const int*)w.col,
+                           (const int*)w.rowptr_t, (const int*)w.col_t, w.st, is_flat, shift, bits, w.cand_s, w.cand_f, scores_out);
+    });
 }
 
 }  // namespace

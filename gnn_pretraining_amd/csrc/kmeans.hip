@@ -36,10 +36,7 @@
 
 namespace {
 
-using gmp::al;
 using namespace sim;
-
-typedef unsigned long long u64;
 
 constexpr int MAX_CLUSTERS = 1024;
 constexpr int MAX_DIM = 256;
@@ -65,30 +62,21 @@ struct Ws {
 };
 
 Ws carve(void* ws, int64_t n, int kc, int dim) {
-    char* base = (char*)(((uintptr_t)ws + 255) / 256 * 256);
-    char* q = base;
-    const int dpad = (dim + 3) / 4 * 4;
+    gmp::Carver c(ws, true);
+    const int dpad = pad4(dim);
     const int64_t chunks = (n + CHUNK - 1) / CHUNK;
     Ws w;
-    w.xn = (float*)q; q += al((size_t)n * dpad * 4);
-    w.cn = (float*)q; q += al((size_t)kc * dpad * 4);
-    w.sums = (float*)q; q += al((size_t)kc * dpad * 4);
-    w.rowptr = (int*)q; q += al((size_t)(kc + 1) * 4);
-    w.totals = (int*)q; q += al((size_t)kc * 4);
-    w.perm = (int*)q; q += al((size_t)n * 4);
-    w.counts = (int*)q; q += al((size_t)chunks * kc * 4);
-    w.ctrl = (Ctrl*)q; q += 256;
-    w.total = (size_t)(q - base) + 256;
+    w.xn = c.take<float>((size_t)n * dpad);
+    w.cn = c.take<float>((size_t)kc * dpad);
+    w.sums = c.take<float>((size_t)kc * dpad);
+    w.rowptr = c.take<int>((size_t)kc + 1);
+    w.totals = c.take<int>((size_t)kc);
+    w.perm = c.take<int>((size_t)n);
+    w.counts = c.take<int>((size_t)chunks * kc);
+    w.ctrl = c.take<Ctrl>(1);
+    w.total = c.total();
     return w;
 }
-
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ u64 make_key(float v, uint32_t inv_col) { return ((u64)gmp::orderable(v) << 32) | (u64)inv_col; }
 
 // rows [0, n) of x into xn, rows [0, kc) of c into cn; a fit (ctrl != NULL) also copies c to c_copy and opens the gate
 __global__ __launch_bounds__(THREADS) void kmeans_normalize_kernel(const float* __restrict__ x, int64_t n, const float* c, int kc, int d, int dpad,
@@ -165,7 +153,7 @@ __global__ __launch_bounds__(THREADS, DP <= 128 ? 2 : 1) void kmeans_assign_kern
             const int rr = acc_row(r, 0);
             const bool in = col_ok && rr < rlim;
             if (matrix_out && in) matrix_out[(i0 + 4 * half + rr) * kc + colj] = acc[r];
-            const u64 key = in ? make_key(acc[r], inv_col) : 0ull;
+            const u64 key = in ? gmp::pack_key(acc[r], inv_col) : 0ull;
             best[r] = key > best[r] ? key : best[r];
         }
     }
@@ -187,12 +175,12 @@ __global__ __launch_bounds__(THREADS, DP <= 128 ? 2 : 1) void kmeans_assign_kern
     const int rr = acc_row(l31 & 15, 0);
     const bool valid = l31 < 16 && rr < rlim;
     const int64_t row = i0 + 4 * half + rr;
-    const int64_t lab = (int64_t)(0xffffffffu - (uint32_t)mine);
+    const int64_t lab = (int64_t)gmp::key_low(mine);
     const bool moved = valid && compare && labels[row] != lab;
     const u64 bal = __ballot(moved);
     if (valid) {
         labels[row] = lab;
-        sim_out[row] = gmp::from_orderable((uint32_t)(mine >> 32));
+        sim_out[row] = gmp::key_score(mine);
     }
     if (bal != 0ull && lane == 0) atomicAdd(&ctrl->moved, (unsigned int)__popcll(bal));
 }
@@ -296,7 +284,7 @@ __global__ __launch_bounds__(THREADS) void kmeans_scatter_kernel(const int64_t* 
     for (int w = 0; w < THREADS / 64; ++w) {                        // the waves in row order
         if (wave == w && valid) {
             perm[cur[lab] + rank] = (int)row;
-            wave_sync();                                            // every lane of the label has read the cursor
+            gmp::wave_sync();                                            // every lane of the label has read the cursor
             if (rank == group - 1) cur[lab] += group;
         }
         __syncthreads();
@@ -363,11 +351,7 @@ int launch_assign(const Ws& w, int64_t n, int kc, int dpad, int64_t* labels, flo
 }
 
 int assign(const Ws& w, int64_t n, int kc, int dpad, int64_t* labels, float* sim_out, float* matrix_out, Ctrl* ctrl, int compare, hipStream_t st) {
-    if (dpad <= 32) return launch_assign<32>(w, n, kc, dpad, labels, sim_out, matrix_out, ctrl, compare, st);
-    if (dpad <= 64) return launch_assign<64>(w, n, kc, dpad, labels, sim_out, matrix_out, ctrl, compare, st);
-    if (dpad <= 128) return launch_assign<128>(w, n, kc, dpad, labels, sim_out, matrix_out, ctrl, compare, st);
-    if (dpad <= 192) return launch_assign<192>(w, n, kc, dpad, labels, sim_out, matrix_out, ctrl, compare, st);
-    return launch_assign<256>(w, n, kc, dpad, labels, sim_out, matrix_out, ctrl, compare, st);
+    return dispatch_dp(dpad, [&](auto dp) { return launch_assign<dp()>(w, n, kc, dpad, labels, sim_out, matrix_out, ctrl, compare, st); });
 }
 
 bool sizes_ok(int64_t n, int kc, int dim) { return n >= 0 && n < ROW_LIMIT && kc >= 1 && kc <= MAX_CLUSTERS && dim >= 1 && dim <= MAX_DIM; }
@@ -390,7 +374,7 @@ extern "C" int gmp_kmeans_assign(const float* x, int64_t n, const float* centroi
     if (!ws || ws_bytes < need) return gmp::fail(GMP_ERR_WORKSPACE, "kmeans_assign: workspace %zu < %zu", ws ? ws_bytes : (size_t)0, need);
     hipStream_t st = (hipStream_t)stream;
     const Ws w = carve(ws, n, kc, dim);
-    const int dpad = (dim + 3) / 4 * 4;
+    const int dpad = pad4(dim);
     hipLaunchKernelGGL(kmeans_normalize_kernel, dim3((unsigned)gmp::cdiv((n + kc) * 64, THREADS)), dim3(THREADS), 0, st, x, n, centroids, kc, dim, dpad,
                        w.xn, w.cn, (float*)nullptr, (Ctrl*)nullptr);
     if (int rc = gmp::check_launch("kmeans_normalize_kernel")) return rc;
@@ -408,7 +392,7 @@ extern "C" int gmp_kmeans_fit(const float* x, int64_t n, const float* init, int 
     if (!ws || ws_bytes < need) return gmp::fail(GMP_ERR_WORKSPACE, "kmeans_fit: workspace %zu < %zu", ws ? ws_bytes : (size_t)0, need);
     hipStream_t st = (hipStream_t)stream;
     const Ws w = carve(ws, n, kc, dim);
-    const int dpad = (dim + 3) / 4 * 4;
+    const int dpad = pad4(dim);
     const int64_t chunks = (n + CHUNK - 1) / CHUNK;
     const int* gate = &w.ctrl->changed;
     hipLaunchKernelGGL(kmeans_normalize_kernel, dim3((unsigned)gmp::cdiv((n + kc) * 64, THREADS)), dim3(THREADS), 0, st, x, n, init, kc, dim, dpad, w.xn,

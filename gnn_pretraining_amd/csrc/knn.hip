@@ -25,10 +25,7 @@
 
 namespace {
 
-using gmp::al;
 using namespace sim;
-
-typedef unsigned long long u64;
 
 constexpr int MAXK = 64;                    // list length
 constexpr int MAX_DIM = 256;
@@ -43,7 +40,7 @@ struct Plan {
 
 Plan make_plan(int64_t nq, int64_t ndb, int dim) {
     Plan p;
-    p.dpad = (dim + 3) / 4 * 4;
+    p.dpad = pad4(dim);
     p.tiles = (int)((nq + BM - 1) / BM);
     p.nct = (int)((ndb + BN - 1) / BN);
     // the database is cut only where the row tiles alone leave most of the 256 CUs idle: about two rounds of blocks, at most 16 parts
@@ -61,24 +58,15 @@ struct Ws {
 };
 
 Ws carve(void* ws, int64_t nq, int64_t ndb, int dim, int k) {
-    char* base = (char*)(((uintptr_t)ws + 255) / 256 * 256);
-    char* q = base;
+    gmp::Carver c(ws, true);
     const Plan p = make_plan(nq, ndb, dim);
     Ws w;
-    w.qn = (float*)q; q += al((size_t)nq * p.dpad * 4);
-    w.dbn = (float*)q; q += al((size_t)ndb * p.dpad * 4);
-    w.lists = (u64*)q; q += al((size_t)nq * p.parts * k * 8);
-    w.total = (size_t)(q - base) + 256;
+    w.qn = c.take<float>((size_t)nq * p.dpad);
+    w.dbn = c.take<float>((size_t)ndb * p.dpad);
+    w.lists = c.take<u64>((size_t)nq * p.parts * k);
+    w.total = c.total();
     return w;
 }
-
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ u64 make_key(float v, uint32_t inv_col) { return ((u64)gmp::orderable(v) << 32) | (u64)inv_col; }
 
 // v of lane `src` (wave-uniform)
 __device__ __forceinline__ u64 read_lane(u64 v, int src) {
@@ -158,7 +146,7 @@ __global__ __launch_bounds__(THREADS, DP <= 128 ? 2 : 1) void knn_scan_kernel(co
             const int rr = acc_row(r, 0);
             const bool in = col_ok && rr < rlim;
             if (matrix_out && in) matrix_out[(i0 + 4 * half + rr) * ndb + colj] = acc[r];
-            const bool ok = in && !(excl && dd == rr) && make_key(acc[r], inv_col) > thr[wave * 32 + 4 * half + rr];
+            const bool ok = in && !(excl && dd == rr) && gmp::pack_key(acc[r], inv_col) > thr[wave * 32 + 4 * half + rr];
             fl |= (ok ? 1u : 0u) << r;
         }
         if (__ballot(fl != 0u) == 0ull) continue;
@@ -168,7 +156,7 @@ __global__ __launch_bounds__(THREADS, DP <= 128 ? 2 : 1) void knn_scan_kernel(co
             const bool mine = (fl >> r) & 1u;
             const u64 bal = __ballot(mine);
             if (bal == 0ull) continue;
-            const u64 ck = make_key(pick(acc, r), inv_col);
+            const u64 ck = gmp::pack_key(pick(acc, r), inv_col);
             const int rr = acc_row(r, 0);
 #pragma unroll 1
             for (int h = 0; h < 2; ++h) {                           // the row of the lower half of the wave, then the upper half's
@@ -187,7 +175,7 @@ __global__ __launch_bounds__(THREADS, DP <= 128 ? 2 : 1) void knn_scan_kernel(co
                     ccnt += x > ck ? 1 : 0;                         // survivors before my survivor
                     if (l31 == b) base = __popcll(gt);
                 }
-                wave_sync();                                        // every list entry is in a register: the list can be rewritten
+                gmp::wave_sync();                                        // every list entry is in a register: the list can be rewritten
                 if (lane < k) {
                     const int nr = lane + cnt;
                     if (nr < k) {
@@ -222,7 +210,7 @@ __global__ __launch_bounds__(THREADS) void knn_merge_kernel(const u64* __restric
     if (q >= nq) return;                                            // (only wave-level synchronisation below)
     u64* const mk = ks[wave];
     for (int i = lane; i < n; i += 64) mk[i] = lists[q * n + i];
-    wave_sync();
+    gmp::wave_sync();
     int real = 0;
     for (int i = lane; i < n; i += 64) {
         const u64 key = mk[i];
@@ -231,8 +219,8 @@ __global__ __launch_bounds__(THREADS) void knn_merge_kernel(const u64* __restric
         int rank = 0;
         for (int j = 0; j < n; ++j) rank += mk[j] > key ? 1 : 0;
         if (rank < k) {
-            idx[q * k + rank] = (int64_t)(0xffffffffu - (uint32_t)key);
-            sim_out[q * k + rank] = gmp::from_orderable((uint32_t)(key >> 32));
+            idx[q * k + rank] = (int64_t)gmp::key_low(key);
+            sim_out[q * k + rank] = gmp::key_score(key);
         }
     }
 #pragma unroll
@@ -284,11 +272,7 @@ __global__ __launch_bounds__(THREADS) void knn_vote_kernel(const int64_t* __rest
 template <int DP>
 int launch_scan(const Plan& p, const Ws& w, int64_t nq, int64_t ndb, int k, int excl, float* matrix_out, hipStream_t st) {
     static std::atomic<uint64_t> attr{0};                           // up to 99,840 bytes of LDS (DP = 256, k = 64): opt in once per device
-    if (!gmp::lds_attr_done(attr)) {
-        if (hipFuncSetAttribute((const void*)knn_scan_kernel<DP>, hipFuncAttributeMaxDynamicSharedMemorySize, scan_lds_bytes<DP>(MAXK)) != hipSuccess)
-            return gmp::fail(GMP_ERR_LAUNCH, "knn_topk: cannot reserve %d bytes of LDS", scan_lds_bytes<DP>(MAXK));
-        gmp::lds_attr_mark(attr);
-    }
+    if (int rc = gmp::reserve_lds(attr, (const void*)knn_scan_kernel<DP>, scan_lds_bytes<DP>(MAXK), "knn_topk")) return rc;
     hipLaunchKernelGGL((knn_scan_kernel<DP>), dim3((unsigned)p.tiles, (unsigned)p.parts), dim3(THREADS), (size_t)scan_lds_bytes<DP>(k), st,
                        (const float*)w.qn, nq, (const float*)w.dbn, ndb, p.dpad, p.tpc, p.nct, k, excl, p.parts, w.lists, matrix_out);
     return gmp::check_launch("knn_scan_kernel");
@@ -328,14 +312,8 @@ extern "C" int gmp_knn_topk(const float* q, int64_t nq, const float* db, int64_t
     hipLaunchKernelGGL(knn_normalize_kernel, dim3((unsigned)gmp::cdiv(rows * 64, THREADS)), dim3(THREADS), 0, st, q, shared ? (int64_t)0 : nq, db, ndb,
                        dim, p.dpad, w.qn, w.dbn);
     if (int rc = gmp::check_launch("knn_normalize_kernel")) return rc;
-    int rc;
     const int excl = exclude_self ? 1 : 0;
-    if (p.dpad <= 32) rc = launch_scan<32>(p, w, nq, ndb, k, excl, matrix_out, st);
-    else if (p.dpad <= 64) rc = launch_scan<64>(p, w, nq, ndb, k, excl, matrix_out, st);
-    else if (p.dpad <= 128) rc = launch_scan<128>(p, w, nq, ndb, k, excl, matrix_out, st);
-    else if (p.dpad <= 192) rc = launch_scan<192>(p, w, nq, ndb, k, excl, matrix_out, st);
-    else rc = launch_scan<256>(p, w, nq, ndb, k, excl, matrix_out, st);
-    if (rc != GMP_OK) return rc;
+    if (int rc = dispatch_dp(p.dpad, [&](auto dp) { return launch_scan<dp()>(p, w, nq, ndb, k, excl, matrix_out, st); })) return rc;
     hipLaunchKernelGGL(knn_merge_kernel, dim3((unsigned)gmp::cdiv(nq, WAVES)), dim3(THREADS), 0, st, (const u64*)w.lists, nq, p.parts * k, k, idx, sim_out);
     return gmp::check_launch("knn_merge_kernel");
 }

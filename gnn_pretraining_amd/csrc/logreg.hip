@@ -25,10 +25,7 @@
 
 namespace {
 
-using gmp::al;
 using namespace sim;
-
-typedef unsigned long long u64;
 
 constexpr int MAX_CLASSES = 32;
 constexpr int MIN_CLASSES = 2;
@@ -53,20 +50,17 @@ struct Ws {
 int groups_for(int64_t n) { return (int)std::min<int64_t>((n + BM - 1) / BM, MAX_GROUPS); }
 
 Ws carve(void* ws, int64_t n, int classes, int dim) {
-    char* base = (char*)(((uintptr_t)ws + 255) / 256 * 256);
-    char* q = base;
-    const int dpad = (dim + 3) / 4 * 4;
+    gmp::Carver c(ws, true);
+    const int dpad = pad4(dim);
     Ws w;
     w.groups = groups_for(n);
     w.slot = (classes * dpad + classes + 2 + 63) / 64 * 64;
-    w.xn = (float*)q; q += al((size_t)n * dpad * 4);
-    w.parts = (float*)q; q += al((size_t)w.groups * w.slot * 4);
-    w.ctrl = (Ctrl*)q; q += 256;
-    w.total = (size_t)(q - base) + 256;
+    w.xn = c.take<float>((size_t)n * dpad);
+    w.parts = c.take<float>((size_t)w.groups * w.slot);
+    w.ctrl = c.take<Ctrl>(1);
+    w.total = c.total();
     return w;
 }
-
-__device__ __forceinline__ u64 make_key(float v, uint32_t inv_col) { return ((u64)gmp::orderable(v) << 32) | (u64)inv_col; }
 
 __global__ __launch_bounds__(THREADS) void logreg_normalize_kernel(const float* __restrict__ x, int64_t n, int d, int dpad, float* __restrict__ xn,
                                                                    const int64_t* __restrict__ labels, int classes, int32_t* __restrict__ status,
@@ -218,12 +212,12 @@ __global__ __launch_bounds__(THREADS) void logreg_rows_kernel(const float* __res
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int c = acc_row(r, half);
-                const u64 key = c < classes ? make_key(z[r], 0xffffffffu - (uint32_t)c) : 0ull;
+                const u64 key = c < classes ? gmp::pack_key(z[r], 0xffffffffu - (uint32_t)c) : 0ull;
                 best = key > best ? key : best;
             }
             const u64 other = __shfl_xor(best, 32, 64);
             best = other > best ? other : best;
-            if (half == 0 && row_ok) pred[row] = (int64_t)(0xffffffffu - (uint32_t)best);
+            if (half == 0 && row_ok) pred[row] = (int64_t)gmp::key_low(best);
         }
         __syncthreads();                                            // the tile's readers are done
     }
@@ -304,11 +298,7 @@ int launch_rows(const Ws& w, int64_t n, const float* W, const float* b, int clas
                 int64_t* pred, hipStream_t st) {
     static std::atomic<uint64_t> attr{0};                           // up to 150,048 bytes of LDS (DP = 256, a fit): opt in once per device
     constexpr int lds = rows_lds_bytes<DP>(FIT);
-    if (!gmp::lds_attr_done(attr)) {
-        if (hipFuncSetAttribute((const void*)logreg_rows_kernel<DP, FIT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
-            return gmp::fail(GMP_ERR_LAUNCH, "logreg: cannot reserve %d bytes of LDS", lds);
-        gmp::lds_attr_mark(attr);
-    }
+    if (int rc = gmp::reserve_lds(attr, (const void*)logreg_rows_kernel<DP, FIT>, lds, "logreg")) return rc;
     hipLaunchKernelGGL((logreg_rows_kernel<DP, FIT>), dim3((unsigned)w.groups), dim3(THREADS), (size_t)lds, st, (const float*)w.xn, n, W, b, classes, d,
                        dpad, labels, w.parts, w.slot, logits_out, pred);
     return gmp::check_launch("logreg_rows_kernel");
@@ -317,11 +307,7 @@ int launch_rows(const Ws& w, int64_t n, const float* W, const float* b, int clas
 template <bool FIT>
 int rows(const Ws& w, int64_t n, const float* W, const float* b, int classes, int d, int dpad, const int64_t* labels, float* logits_out, int64_t* pred,
          hipStream_t st) {
-    if (dpad <= 32) return launch_rows<32, FIT>(w, n, W, b, classes, d, dpad, labels, logits_out, pred, st);
-    if (dpad <= 64) return launch_rows<64, FIT>(w, n, W, b, classes, d, dpad, labels, logits_out, pred, st);
-    if (dpad <= 128) return launch_rows<128, FIT>(w, n, W, b, classes, d, dpad, labels, logits_out, pred, st);
-    if (dpad <= 192) return launch_rows<192, FIT>(w, n, W, b, classes, d, dpad, labels, logits_out, pred, st);
-    return launch_rows<256, FIT>(w, n, W, b, classes, d, dpad, labels, logits_out, pred, st);
+    return dispatch_dp(dpad, [&](auto dp) { return launch_rows<dp(), FIT>(w, n, W, b, classes, d, dpad, labels, logits_out, pred, st); });
 }
 
 bool sizes_ok(int64_t n, int classes, int dim) {
@@ -348,7 +334,7 @@ extern "C" int gmp_logreg_fit(const float* x, const int64_t* labels, int64_t n, 
     if (!ws || ws_bytes < need) return gmp::fail(GMP_ERR_WORKSPACE, "logreg_fit: workspace %zu < %zu", ws ? ws_bytes : (size_t)0, need);
     hipStream_t st = (hipStream_t)stream;
     const Ws w = carve(ws, n, classes, dim);
-    const int dpad = (dim + 3) / 4 * 4;
+    const int dpad = pad4(dim);
     if (hipMemsetAsync(status, 0, sizeof(int32_t), st) != hipSuccess) return gmp::fail(GMP_ERR_LAUNCH, "logreg_fit: memset");
     hipLaunchKernelGGL(logreg_normalize_kernel, dim3((unsigned)gmp::cdiv(n * 64, THREADS)), dim3(THREADS), 0, st, x, n, dim, dpad, w.xn, labels, classes,
                        status, (const int64_t*)step, w.ctrl);
@@ -375,7 +361,7 @@ extern "C" int gmp_logreg_predict(const float* x, int64_t n, const float* W, con
     if (!ws || ws_bytes < need) return gmp::fail(GMP_ERR_WORKSPACE, "logreg_predict: workspace %zu < %zu", ws ? ws_bytes : (size_t)0, need);
     hipStream_t st = (hipStream_t)stream;
     const Ws w = carve(ws, n, classes, dim);
-    const int dpad = (dim + 3) / 4 * 4;
+    const int dpad = pad4(dim);
     hipLaunchKernelGGL(logreg_normalize_kernel, dim3((unsigned)gmp::cdiv(n * 64, THREADS)), dim3(THREADS), 0, st, x, n, dim, dpad, w.xn,
                        (const int64_t*)nullptr, classes, (int32_t*)nullptr, (const int64_t*)nullptr, (Ctrl*)nullptr);
     if (int rc = gmp::check_launch("logreg_normalize_kernel")) return rc;

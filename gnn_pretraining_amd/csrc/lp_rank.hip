@@ -300,15 +300,6 @@ int common_ok(const char* who, int64_t N, int64_t Q, int feat, int hidden, const
     return GMP_OK;
 }
 
-template <typename Kern>
-int reserve_lds(Kern kern, std::atomic<uint64_t>& done, const char* who) {      // > 64 KiB of dynamic LDS: opt in once per device
-    if (gmp::lds_attr_done(done)) return GMP_OK;
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) != hipSuccess)
-        return gmp::fail(GMP_ERR_LAUNCH, "%s: cannot reserve %d bytes of LDS", who, LDS_BYTES);
-    gmp::lds_attr_mark(done);
-    return GMP_OK;
-}
-
 }  // namespace
 
 extern "C" size_t gmp_lp_rank_workspace_bytes(int64_t Q, int64_t N) {
@@ -331,8 +322,8 @@ extern "C" int gmp_lp_rank(const float* h, const int64_t* src, const int64_t* ds
     const int64_t tiles = (N + BM - 1) / BM;
     if (Q * std::max<int64_t>(tiles, 1) >= ((int64_t)1 << 31)) return gmp::fail(GMP_ERR_ARG, "lp_rank: Q=%lld x %lld candidate tiles exceed one grid", (long long)Q, (long long)tiles);
     static std::atomic<uint64_t> attr_true{0}, attr_count{0};
-    if (int rc = reserve_lds(lp_rank_true_kernel, attr_true, "lp_rank")) return rc;
-    if (int rc = reserve_lds(lp_rank_count_kernel, attr_count, "lp_rank")) return rc;
+    if (int rc = gmp::reserve_lds(attr_true, (const void*)lp_rank_true_kernel, LDS_BYTES, "lp_rank")) return rc;
+    if (int rc = gmp::reserve_lds(attr_count, (const void*)lp_rank_count_kernel, LDS_BYTES, "lp_rank")) return rc;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(lp_rank_true_kernel, dim3((unsigned)gmp::cdiv(Q, BM)), dim3(THREADS), LDS_BYTES, st, h, src, dst, N, Q, w0, b0, w3, b3,
                        logit_true, n_greater, n_equal);
@@ -356,7 +347,7 @@ extern "C" int gmp_lp_topk(const float* h, const int64_t* src, int64_t N, int64_
     const int parts = topk_parts(Q, N);
     if (Q * parts >= ((int64_t)1 << 31)) return gmp::fail(GMP_ERR_ARG, "lp_topk: Q=%lld", (long long)Q);
     static std::atomic<uint64_t> attr_scan{0};
-    if (int rc = reserve_lds(lp_topk_scan_kernel, attr_scan, "lp_topk")) return rc;
+    if (int rc = gmp::reserve_lds(attr_scan, (const void*)lp_topk_scan_kernel, LDS_BYTES, "lp_topk")) return rc;
     char* base = (char*)(((uintptr_t)workspace + 255) / 256 * 256);
     float* part_v = (float*)base;
     int32_t* part_i = (int32_t*)(base + (size_t)Q * parts * MAXK * 4);

@@ -323,11 +323,7 @@ extern "C" int gmp_lp_score_fwd(const float* h, const int64_t* src, const int64_
         return gmp::fail(GMP_ERR_ARG, "lp_score_fwd: h, w0, b0, w3 and act must be 16-byte aligned");
     if (workspace_bytes < gmp_lp_score_fwd_workspace_bytes(K)) return gmp::fail(GMP_ERR_ARG, "lp_score_fwd: workspace too small");
     static std::atomic<uint64_t> attr_set{0};               // > 64 KiB of dynamic LDS: opt in once per device (gnnmp_internal.h)
-    if (!gmp::lds_attr_done(attr_set)) {
-        if (hipFuncSetAttribute((const void*)lp_score_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, FWD_LDS) != hipSuccess)
-            return gmp::fail(GMP_ERR_LAUNCH, "lp_score_fwd: cannot reserve %d bytes of LDS", FWD_LDS);
-        gmp::lds_attr_mark(attr_set);
-    }
+    if (int rc = gmp::reserve_lds(attr_set, (const void*)lp_score_fwd_kernel, FWD_LDS, "lp_score_fwd")) return rc;
     hipStream_t st = (hipStream_t)stream;
     float* part = (float*)workspace;
     hipLaunchKernelGGL(lp_score_fwd_kernel, dim3((unsigned)gmp::cdiv(K, BM), HID / 32), dim3(FWD_THREADS), FWD_LDS, st, h, src, dst, N, K,

@@ -23,7 +23,6 @@
 
 namespace {
 
-using gmp::al;
 using namespace sim;
 
 constexpr int WLD = 36;         // row stride of the weight patch (floats): 144 B, 16-byte slots of 32 rows spread over the banks
@@ -52,26 +51,23 @@ Plan make_plan(int64_t n) {
 
 struct Ws {
     float *zn, *norm, *lse, *spos, *rowloss, *pm, *ps, *gpart;
+    size_t total;
 };
 
 Ws carve(void* ws, const Plan& p, int d) {
-    char* q = (char*)ws;
+    gmp::Carver c(ws, false);
     Ws w;
     const size_t R = (size_t)p.R;
-    w.zn = (float*)q; q += al(R * d * 4);
-    w.norm = (float*)q; q += al(R * 4);
-    w.lse = (float*)q; q += al(R * 4);
-    w.spos = (float*)q; q += al(R * 4);
-    w.rowloss = (float*)q; q += al(R * 4);
-    w.pm = (float*)q; q += al(R * p.C * 4);
-    w.ps = (float*)q; q += al(R * p.C * 4);
-    w.gpart = (float*)q;                                // [C][R][d]
+    w.zn = c.take<float>(R * d);
+    w.norm = c.take<float>(R);
+    w.lse = c.take<float>(R);
+    w.spos = c.take<float>(R);
+    w.rowloss = c.take<float>(R);
+    w.pm = c.take<float>(R * p.C);
+    w.ps = c.take<float>(R * p.C);
+    w.gpart = c.take<float>(R * d * p.C);               // [C][R][d]
+    w.total = c.total() + 256;
     return w;
-}
-
-size_t ws_bytes_of(const Plan& p, int d) {
-    const size_t R = (size_t)p.R;
-    return al(R * d * 4) + 4 * al(R * 4) + 2 * al(R * p.C * 4) + al(R * d * 4 * p.C) + 256;
 }
 
 // one wave per row of [z1; z2]
@@ -299,22 +295,17 @@ int args_ok(const char* who, int64_t n, int d, float T) {
 template <bool BWD>
 void launch_tiles(const Plan& p, int d, float invT, const Ws& w, hipStream_t st) {
     const dim3 grid((unsigned)p.tiles, (unsigned)p.C), block(THREADS);
-#define NTS_LAUNCH(DP)                                                                                                                    \
-    hipLaunchKernelGGL((nts_tile_kernel<DP, BWD>), grid, block, 0, st, (const float*)w.zn, p.R, d, invT, p.tpc, p.nct, (const float*)w.lse, w.pm, \
-                       w.ps, w.spos, w.gpart)
-    if (d <= 32) NTS_LAUNCH(32);
-    else if (d <= 64) NTS_LAUNCH(64);
-    else if (d <= 128) NTS_LAUNCH(128);
-    else if (d <= 192) NTS_LAUNCH(192);
-    else NTS_LAUNCH(256);
-#undef NTS_LAUNCH
+    dispatch_dp(d, [&](auto dp) {
+        hipLaunchKernelGGL((nts_tile_kernel<dp(), BWD>), grid, block, 0, st, (const float*)w.zn, p.R, d, invT, p.tpc, p.nct, (const float*)w.lse,
+                           w.pm, w.ps, w.spos, w.gpart);
+    });
 }
 
 }  // namespace
 
 extern "C" size_t gmp_nt_xent_stream_workspace_bytes(int64_t n, int d) {
     if (n < 1 || n > MAX_N || d < 1) return 0;
-    return ws_bytes_of(make_plan(n), d);
+    return carve(nullptr, make_plan(n), d).total;
 }
 
 extern "C" int gmp_nt_xent_stream_fwd(const float* z1, const float* z2, int64_t n, int d, float T, float* loss_sum, void* ws, size_t ws_bytes,
@@ -322,9 +313,9 @@ extern "C" int gmp_nt_xent_stream_fwd(const float* z1, const float* z2, int64_t 
     if (int rc = args_ok("nt_xent_stream_fwd", n, d, T)) return rc;
     if (!z1 || !z2 || !loss_sum || !ws) return gmp::fail(GMP_ERR_ARG, "nt_xent_stream_fwd: null pointer");
     const Plan p = make_plan(n);
-    if (ws_bytes < ws_bytes_of(p, d)) return gmp::fail(GMP_ERR_WORKSPACE, "nt_xent_stream_fwd: workspace");
-    hipStream_t st = (hipStream_t)stream;
     const Ws w = carve(ws, p, d);
+    if (ws_bytes < w.total) return gmp::fail(GMP_ERR_WORKSPACE, "nt_xent_stream_fwd: workspace");
+    hipStream_t st = (hipStream_t)stream;
     const int64_t R = p.R;
     hipLaunchKernelGGL(nts_normalize_kernel, dim3((unsigned)((R * 64 + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, z1, z2, n, d, w.zn, w.norm);
     launch_tiles<false>(p, d, 1.f / T, w, st);
@@ -340,9 +331,9 @@ extern "C" int gmp_nt_xent_stream_bwd(const float* z1, const float* z2, int64_t 
     if (int rc = args_ok("nt_xent_stream_bwd", n, d, T)) return rc;
     if (!g_scale || !g_z1 || !g_z2 || !ws) return gmp::fail(GMP_ERR_ARG, "nt_xent_stream_bwd: null pointer");
     const Plan p = make_plan(n);
-    if (ws_bytes < ws_bytes_of(p, d)) return gmp::fail(GMP_ERR_WORKSPACE, "nt_xent_stream_bwd: workspace");
-    hipStream_t st = (hipStream_t)stream;
     const Ws w = carve(ws, p, d);
+    if (ws_bytes < w.total) return gmp::fail(GMP_ERR_WORKSPACE, "nt_xent_stream_bwd: workspace");
+    hipStream_t st = (hipStream_t)stream;
     const int64_t R = p.R;
     launch_tiles<true>(p, d, 1.f / T, w, st);
     hipLaunchKernelGGL(nts_normalize_bwd_kernel, dim3((unsigned)((R * 64 + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, (const float*)w.zn,

@@ -4,6 +4,8 @@
 // v_mfma_f32_32x32x2_f32 chain and lives only in accumulators.  The chain is a k-ordered fp32 fma chain, so whoever builds on this
 // header sees the same bits for the same rows; the tile loop (barriers, which tiles to skip, the epilogue) belongs to each kernel.
 #pragma once
+#include <type_traits>
+
 #include "gnnmp_internal.h"
 
 namespace sim {
@@ -14,6 +16,20 @@ constexpr int BN = 32;          // columns per step
 
 using gmp::acc_row;
 using gmp::f32x16;
+using gmp::u64;
+
+// the row stride of a normalised copy: the dimension padded to a multiple of 4
+constexpr int pad4(int64_t dim) { return (int)((dim + 3) / 4 * 4); }
+
+// f(std::integral_constant<int, DP>{}) for the smallest Tile<DP> that holds rows of dpad <= 256 floats
+template <typename F>
+auto dispatch_dp(int dpad, F&& f) {
+    if (dpad <= 32) return f(std::integral_constant<int, 32>{});
+    if (dpad <= 64) return f(std::integral_constant<int, 64>{});
+    if (dpad <= 128) return f(std::integral_constant<int, 128>{});
+    if (dpad <= 192) return f(std::integral_constant<int, 192>{});
+    return f(std::integral_constant<int, 256>{});
+}
 
 // a row difference as an int: only values within a tile are ever compared, anything further away just has to stay away.  Row / column
 // tests are made on such small ints relative to the wave's first row (64-bit row numbers per accumulator would cost 64 registers):

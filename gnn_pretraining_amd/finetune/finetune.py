@@ -12,7 +12,7 @@ import os
 import time
 from dataclasses import dataclass
 from pathlib import Path
-from typing import Dict, List, Optional, Tuple
+from typing import Callable, Dict, List, Optional, Tuple
 
 import torch
 from torch import Tensor
@@ -31,6 +31,50 @@ HARD_NEGATIVE_RATIO = 0.3
 MIN_HARD_NEGATIVES = 8
 PATIENCE_FRACTION = 0.5
 CLUSTER_PROBE_MAX_INIT = 64             # --cluster-probe N_INIT: k-means restarts per scored split
+
+
+@dataclass(frozen=True)
+class Probe:
+    """One embedding probe of the classification domains: an integer FinetuneConfig field (0 = off) with its flag, and what it scores.
+    score((train_emb, train_y) or None, (emb, y), cfg) -> the probe's scores of the split (rows of probe_embeddings); those named in
+    `val` / `test` are logged as {prefix}/{name}_{score}."""
+    field: str
+    name: str
+    flag: str
+    metavar: str
+    help: str
+    max_value: int
+    meaning: str                        # what the integer is, for the bound's message
+    purpose: str                        # what the probe does with class labels, for the message on domains without any
+    needs_train: bool
+    score: Callable
+    val: Tuple[str, ...]
+    test: Tuple[str, ...]
+
+
+PROBES = (
+    Probe(field="knn_probe", name="knn", flag="--knn-probe", metavar="K", max_value=ops.KNN_MAX_K,
+          help="classification domains on an engine: also log val/knn_accuracy (every epoch and once before training) and test/knn_accuracy, "
+               "the weighted k-NN classifier (K neighbours, 1..64, cosine, T = 0.07) on the backbone's embeddings; 0 = off",
+          meaning="the number of neighbours, 1 <= k", purpose="classifies nodes or graphs from labelled neighbours", needs_train=True,
+          score=lambda train, split, cfg: knn_probe_accuracy(*train, *split, NUM_CLASSES[cfg.domain_name], cfg.knn_probe),
+          val=("accuracy",), test=("accuracy",)),
+    # (the seeds come from a generator of the probe's own, seeded with cfg.seed, never from the training generator)
+    Probe(field="cluster_probe", name="cluster", flag="--cluster-probe", metavar="N_INIT", max_value=CLUSTER_PROBE_MAX_INIT,
+          help="classification domains on an engine: also log val/cluster_nmi (every epoch and once before training) and test/cluster_nmi, "
+               "test/cluster_ari, test/cluster_accuracy, spherical k-means (k = the number of classes, N_INIT restarts, 1..64, k-means++) on "
+               "the backbone's embeddings; 0 = off",
+          meaning="the number of k-means restarts, 1 <= n_init", purpose="scores clusters of nodes or graphs against class labels", needs_train=False,
+          score=lambda train, split, cfg: cluster_probe(*split, NUM_CLASSES[cfg.domain_name], n_init=cfg.cluster_probe, seed=cfg.seed),
+          val=("nmi",), test=("nmi", "ari", "accuracy")),
+    Probe(field="logreg_probe", name="logreg", flag="--logreg-probe", metavar="ITERS", max_value=ops.LOGREG_MAX_ITER,
+          help="classification domains on an engine: also log val/logreg_accuracy (every epoch and once before training) and "
+               "test/logreg_accuracy, linear evaluation: a softmax regression fitted on the train split's embeddings (ITERS full-batch Adam "
+               "iterations from zero, 1..10000, lr 0.01, rows L2-normalised) and scored on the split; 0 = off",
+          meaning="the number of Adam iterations, 1 <= iters", purpose="fits a classifier of nodes or graphs on class labels", needs_train=True,
+          score=lambda train, split, cfg: linear_eval_probe(*train, *split, NUM_CLASSES[cfg.domain_name], iters=cfg.logreg_probe),
+          val=("accuracy",), test=("accuracy",)),
+)
 
 
 class LinkPredictionHardNegativeMiner:
@@ -124,32 +168,16 @@ class FinetuneConfig:
                              + {"node_classification": "the node engine is switched off (GMP_FINETUNE_ENGINE=0)",
                                 "link_prediction": "pass lp_engine (--lp-engine)",
                                 "graph_classification": "pass gc_engine (--gc-engine)"}[TASK_TYPES[self.domain_name]])
-        if not 0 <= self.knn_probe <= ops.KNN_MAX_K:
-            raise ValueError(f"knn_probe={self.knn_probe} (the number of neighbours, 1 <= k <= {ops.KNN_MAX_K}; 0 switches the probe off)")
-        if self.knn_probe and TASK_TYPES[self.domain_name] == "link_prediction":
-            raise ValueError(f"knn_probe classifies nodes or graphs from labelled neighbours: {self.domain_name} has no class labels")
-        if self.knn_probe and not engine_active(self):
-            raise ValueError(f"knn_probe needs an active fine-tune engine for {self.domain_name} (it reads the engine's eval-mode embed()): "
-                             + {"node_classification": "the node engine is switched off (GMP_FINETUNE_ENGINE=0)",
-                                "graph_classification": "pass gc_engine (--gc-engine)"}[TASK_TYPES[self.domain_name]])
-        if not 0 <= self.cluster_probe <= CLUSTER_PROBE_MAX_INIT:
-            raise ValueError(f"cluster_probe={self.cluster_probe} (the number of k-means restarts, 1 <= n_init <= {CLUSTER_PROBE_MAX_INIT}; "
-                             "0 switches the probe off)")
-        if self.cluster_probe and TASK_TYPES[self.domain_name] == "link_prediction":
-            raise ValueError(f"cluster_probe scores clusters of nodes or graphs against class labels: {self.domain_name} has no class labels")
-        if self.cluster_probe and not engine_active(self):
-            raise ValueError(f"cluster_probe needs an active fine-tune engine for {self.domain_name} (it reads the engine's eval-mode embed()): "
-                             + {"node_classification": "the node engine is switched off (GMP_FINETUNE_ENGINE=0)",
-                                "graph_classification": "pass gc_engine (--gc-engine)"}[TASK_TYPES[self.domain_name]])
-        if not 0 <= self.logreg_probe <= ops.LOGREG_MAX_ITER:
-            raise ValueError(f"logreg_probe={self.logreg_probe} (the number of Adam iterations, 1 <= iters <= {ops.LOGREG_MAX_ITER}; "
-                             "0 switches the probe off)")
-        if self.logreg_probe and TASK_TYPES[self.domain_name] == "link_prediction":
-            raise ValueError(f"logreg_probe fits a classifier of nodes or graphs on class labels: {self.domain_name} has no class labels")
-        if self.logreg_probe and not engine_active(self):
-            raise ValueError(f"logreg_probe needs an active fine-tune engine for {self.domain_name} (it reads the engine's eval-mode embed()): "
-                             + {"node_classification": "the node engine is switched off (GMP_FINETUNE_ENGINE=0)",
-                                "graph_classification": "pass gc_engine (--gc-engine)"}[TASK_TYPES[self.domain_name]])
+        for p in PROBES:
+            value = getattr(self, p.field)
+            if not 0 <= value <= p.max_value:
+                raise ValueError(f"{p.field}={value} ({p.meaning} <= {p.max_value}; 0 switches the probe off)")
+            if value and TASK_TYPES[self.domain_name] == "link_prediction":
+                raise ValueError(f"{p.field} {p.purpose}: {self.domain_name} has no class labels")
+            if value and not engine_active(self):
+                raise ValueError(f"{p.field} needs an active fine-tune engine for {self.domain_name} (it reads the engine's eval-mode embed()): "
+                                 + {"node_classification": "the node engine is switched off (GMP_FINETUNE_ENGINE=0)",
+                                    "graph_classification": "pass gc_engine (--gc-engine)"}[TASK_TYPES[self.domain_name]])
         if self.lp_ranking and not self.lp_engine:
             raise ValueError("lp_ranking ranks with the link-prediction engine (gmp_lp_rank): pass lp_engine (--lp-engine)")
         self.exp_name = f"{self.domain_name}_{self.finetune_strategy}_{self.pretrained_scheme}"
@@ -402,26 +430,19 @@ def probe_embeddings(engine, datasets, device, cfg: FinetuneConfig):
         return sets
 
 
-def knn_probe(engine, train_loader, loader, device, cfg: FinetuneConfig) -> float:
-    """cfg.knn_probe: the accuracy of the weighted k-NN classifier (metrics.knn_probe_accuracy) that labels the rows of `loader`'s split
-    from the train split's, on probe_embeddings' rows."""
-    (db, db_y), (q, q_y) = probe_embeddings(engine, (train_loader.dataset, loader.dataset), device, cfg)
-    return knn_probe_accuracy(db, db_y, q, q_y, NUM_CLASSES[cfg.domain_name], cfg.knn_probe)["accuracy"]
-
-
-def cluster_probe_scores(engine, loader, device, cfg: FinetuneConfig) -> Dict[str, float]:
-    """cfg.cluster_probe: NMI, ARI and matched accuracy (metrics.cluster_probe: spherical k-means with as many clusters as the domain
-    has classes, cfg.cluster_probe restarts) of `loader`'s split on probe_embeddings' rows.  The seeds come from a generator of the
-    probe's own (cfg.seed), never from the training generator."""
-    (emb, y), = probe_embeddings(engine, (loader.dataset,), device, cfg)
-    return cluster_probe(emb, y, NUM_CLASSES[cfg.domain_name], n_init=cfg.cluster_probe, seed=cfg.seed)
-
-
-def logreg_probe(engine, train_loader, loader, device, cfg: FinetuneConfig) -> float:
-    """cfg.logreg_probe: the accuracy on `loader`'s split of the softmax regression (metrics.linear_eval_probe: cfg.logreg_probe Adam
-    iterations from zero, no random state) fitted on the train split, on probe_embeddings' rows."""
-    (tr, tr_y), (q, q_y) = probe_embeddings(engine, (train_loader.dataset, loader.dataset), device, cfg)
-    return linear_eval_probe(tr, tr_y, q, q_y, NUM_CLASSES[cfg.domain_name], iters=cfg.logreg_probe)["accuracy"]
+def run_probes(engine, train_loader, loader, device, cfg: FinetuneConfig, prefix: str) -> Dict[str, float]:
+    """The scores of every active probe (PROBES, in that order) on `loader`'s split, keyed as they are logged under `prefix` ("val" /
+    "test").  One probe_embeddings pass serves them all; the train split is embedded only when an active probe fits on it."""
+    active = [p for p in PROBES if getattr(cfg, p.field)]
+    if not active:
+        return {}
+    with_train = any(p.needs_train for p in active)
+    sets = probe_embeddings(engine, ((train_loader.dataset,) if with_train else ()) + (loader.dataset,), device, cfg)
+    out = {}
+    for p in active:
+        scores = p.score(sets[0] if p.needs_train else None, sets[-1], cfg)
+        out.update({f"{prefix}/{p.name}_{k}": scores[k] for k in getattr(p, prefix)})
+    return out
 
 
 def finetune(cfg: FinetuneConfig, epochs: Optional[int] = None, device: Optional[str] = None,
@@ -478,15 +499,11 @@ def finetune(cfg: FinetuneConfig, epochs: Optional[int] = None, device: Optional
         eval_engine = node_engine or lp_engine or gc_engine
         if eval_engine is None:
             raise ValueError(f"engine_eval needs an active fine-tune engine for {cfg.domain_name}")
-    probe_engine = (node_engine or gc_engine) if cfg.knn_probe else None
-    if probe_engine is not None:                             # the embeddings before any training
-        logger.log({"val/knn_accuracy": knn_probe(probe_engine, train_loader, val_loader, dev, cfg)}, 0)
-    cluster_engine = (node_engine or gc_engine) if cfg.cluster_probe else None
-    if cluster_engine is not None:
-        logger.log({"val/cluster_nmi": cluster_probe_scores(cluster_engine, val_loader, dev, cfg)["nmi"]}, 0)
-    logreg_engine = (node_engine or gc_engine) if cfg.logreg_probe else None
-    if logreg_engine is not None:
-        logger.log({"val/logreg_accuracy": logreg_probe(logreg_engine, train_loader, val_loader, dev, cfg)}, 0)
+    probe_engine = node_engine or gc_engine                  # (a configuration with a probe on has one: __post_init__)
+    before = run_probes(probe_engine, train_loader, val_loader, dev, cfg, "val")     # the embeddings before any training
+    for p in PROBES:                                         # one line per active probe
+        if getattr(cfg, p.field):
+            logger.log({k: v for k, v in before.items() if k.startswith(f"val/{p.name}_")}, 0)
     for epoch in range(1, (epochs or cfg.epochs) + 1):
         if node_engine is not None:
             run_training_node_engine(node_engine, train_loader, dev, epoch, global_step, cfg, logger)
@@ -504,12 +521,7 @@ def finetune(cfg: FinetuneConfig, epochs: Optional[int] = None, device: Optional
             val = compute_validation_metrics(evaluate_engine(eval_engine, val_loader, dev, cfg, "val"), epoch)
         else:
             val = compute_validation_metrics(evaluate(model, val_loader, dev, cfg, "val", miner, edges), epoch)
-        if probe_engine is not None:
-            val["val/knn_accuracy"] = knn_probe(probe_engine, train_loader, val_loader, dev, cfg)
-        if cluster_engine is not None:
-            val["val/cluster_nmi"] = cluster_probe_scores(cluster_engine, val_loader, dev, cfg)["nmi"]
-        if logreg_engine is not None:
-            val["val/logreg_accuracy"] = logreg_probe(logreg_engine, train_loader, val_loader, dev, cfg)
+        val.update(run_probes(probe_engine, train_loader, val_loader, dev, cfg, "val"))
         if val[key] > best:
             best, stale = val[key], 0
             torch.save({"epoch": epoch, "model_state_dict": model.state_dict(), "val_metrics": val}, path)
@@ -524,13 +536,7 @@ def finetune(cfg: FinetuneConfig, epochs: Optional[int] = None, device: Optional
     else:
         test_batches = evaluate(model, test_loader, dev, cfg, "test", miner, _train_edges(train_loader, dev))
     test = compute_test_metrics(test_batches, epoch, stale, start, model)
-    if probe_engine is not None:
-        test["test/knn_accuracy"] = knn_probe(probe_engine, train_loader, test_loader, dev, cfg)
-    if cluster_engine is not None:
-        scores = cluster_probe_scores(cluster_engine, test_loader, dev, cfg)
-        test.update({f"test/cluster_{k}": scores[k] for k in ("nmi", "ari", "accuracy")})
-    if logreg_engine is not None:
-        test["test/logreg_accuracy"] = logreg_probe(logreg_engine, train_loader, test_loader, dev, cfg)
+    test.update(run_probes(probe_engine, train_loader, test_loader, dev, cfg, "test"))
     if cfg.lp_ranking:
         test.update(rank_test_edges(lp_engine, train_loader, val_loader, test_loader, dev))
     logger.log(test, global_step[0])
@@ -559,17 +565,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--miner", choices=list(ops.MINER_IMPLS), default="matrix",
                    help="Cora_LP / CiteSeer_LP: the hard-negative miner's top-k kernel: matrix (n x n similarity in the workspace, n <= 65535), "
                         "stream (tiles recomputed, workspace O(n d + E), n <= 2^20), auto (stream beyond 65535 nodes)")
-    p.add_argument("--knn-probe", type=int, default=0, metavar="K",
-                   help="classification domains on an engine: also log val/knn_accuracy (every epoch and once before training) and test/knn_accuracy, "
-                        "the weighted k-NN classifier (K neighbours, 1..64, cosine, T = 0.07) on the backbone's embeddings; 0 = off")
-    p.add_argument("--cluster-probe", type=int, default=0, metavar="N_INIT",
-                   help="classification domains on an engine: also log val/cluster_nmi (every epoch and once before training) and test/cluster_nmi, "
-                        "test/cluster_ari, test/cluster_accuracy, spherical k-means (k = the number of classes, N_INIT restarts, 1..64, k-means++) on "
-                        "the backbone's embeddings; 0 = off")
-    p.add_argument("--logreg-probe", type=int, default=0, metavar="ITERS",
-                   help="classification domains on an engine: also log val/logreg_accuracy (every epoch and once before training) and "
-                        "test/logreg_accuracy, linear evaluation: a softmax regression fitted on the train split's embeddings (ITERS full-batch Adam "
-                        "iterations from zero, 1..10000, lr 0.01, rows L2-normalised) and scored on the split; 0 = off")
+    for probe in PROBES:
+        p.add_argument(probe.flag, type=int, default=0, metavar=probe.metavar, help=probe.help)
     return p
 
 
@@ -578,8 +575,7 @@ def config_from_args(a: argparse.Namespace) -> FinetuneConfig:
                           lp_engine=getattr(a, "lp_engine", False), gc_engine=getattr(a, "gc_engine", False),
                           engine_eval=getattr(a, "engine_eval", False), lp_ranking=getattr(a, "lp_ranking", False),
                           device_metrics=getattr(a, "device_metrics", False), miner_impl=getattr(a, "miner", "matrix"),
-                          knn_probe=getattr(a, "knn_probe", 0), cluster_probe=getattr(a, "cluster_probe", 0),
-                          logreg_probe=getattr(a, "logreg_probe", 0))
+                          **{p.field: getattr(a, p.field, 0) for p in PROBES})
 
 
 def main() -> None:

@@ -4,10 +4,8 @@ equal the reference's bit for bit across every tile width and both sides of the 
 is k-NN with k = 1 on the same similarity core, bit for bit; (c) on random rows the similarities agree with fp64 to 1e-5 and the
 selection is exact on the kernel's own scores; (d) a fit step by step: one call of T iterations is T calls of one, repeatable, every
 label fp64's argmax outside a 2e-5 margin, every update within 1e-5 of fp64's; (e) the edges of the contract; (f) the contingency table;
-(g), (h) the layers above."""
+(g) the probe of metrics.py above them (finetune() with the probe on: tests/test_gpu_probes.py)."""
 import functools
-import json
-import math
 
 import numpy as np
 import pytest
@@ -294,42 +292,3 @@ def test_cluster_probe_on_planted_clusters_and_its_seed():
     assert torch.equal(state, torch.random.get_rng_state())          # a generator of its own
     assert a == b and a["objective"] != c["objective"]
     assert 0 <= a["restart"] < 3 and 0.0 <= a["nmi"] <= 1.0 and -1.0 <= a["ari"] <= 1.0
-
-
-# ---------------------------------------------------------------------------- (h) end to end
-@pytest.mark.parametrize("domain,kw", [("Cora_NC", {}), ("ENZYMES", {"gc_engine": True})])
-def test_finetune_logs_the_probe_and_trains_bit_for_bit_as_without_it(domain, kw, tmp_path, monkeypatch):
-    from gnn_pretraining_amd.finetune import finetune as FT
-    monkeypatch.setattr(FT, "OUTPUT_DIR", tmp_path / "finetune")
-    calls = []
-    real = ops.kmeans_fit
-
-    def spy(*a, **k):
-        calls.append(a[1].size(0))
-        return real(*a, **k)
-
-    monkeypatch.setattr(ops, "kmeans_fit", spy)
-
-    def run(probe, log):
-        cfg = FT.FinetuneConfig(domain, "full_finetune", "b1", 1, cluster_probe=probe, **kw)
-        test = FT.finetune(cfg, epochs=1, data_root=str(tmp_path / "data"), data_scale=0.1, log_path=str(log))
-        state = torch.load(FT.OUTPUT_DIR / f"model_{cfg.exp_name}_{cfg.seed}.pt", map_location="cpu", weights_only=True)["model_state_dict"]
-        return test, state, [json.loads(line) for line in open(log)]
-
-    from gnn_pretraining_amd.constants import NUM_CLASSES
-    test, state, records = run(2, tmp_path / "on.jsonl")
-    assert len(calls) == 3 * 2 and set(calls) == {NUM_CLASSES[domain]}             # step 0, the epoch, the test split: two restarts each
-    assert 0.0 <= test["test/cluster_nmi"] <= 1.0 and 0.0 <= test["test/cluster_accuracy"] <= 1.0 and -1.0 <= test["test/cluster_ari"] <= 1.0
-    first = [r for r in records if r["step"] == 0]
-    assert len(first) == 1 and 0.0 <= first[0]["val/cluster_nmi"] <= 1.0 and records[0] is first[0]
-    per_epoch = [r for r in records if "val/accuracy" in r]
-    assert len(per_epoch) == 1 and 0.0 <= per_epoch[0]["val/cluster_nmi"] <= 1.0
-    assert all(k in records[-1] for k in ("test/cluster_nmi", "test/cluster_ari", "test/cluster_accuracy"))
-
-    n_calls = len(calls)
-    test0, state0, records0 = run(0, tmp_path / "off.jsonl")
-    assert len(calls) == n_calls                                     # off: the kernel is never reached
-    assert not any(k.startswith(("val/cluster_", "test/cluster_")) for r in records0 for k in r)
-    assert test0["test/loss"] == test["test/loss"] and test0["test/accuracy"] == test["test/accuracy"]
-    assert math.isfinite(test["test/loss"])
-    assert state.keys() == state0.keys() and all(torch.equal(state[n], state0[n]) for n in state)

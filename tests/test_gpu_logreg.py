@@ -3,10 +3,9 @@ GPU against the fp64 definition of tests/logreg_ref.py: (a) where the arithmetic
 reference's bit for bit across every tile width and both sides of the 128-row tile edge; (b) on random rows logits, gradient and loss agree
 with fp64; (c) the update is Adam on the kernel's own gradient; (d) one call of T iterations is T calls of one, repeatable, and the hooks
 change nothing; (e) a whole fit separates the blob cases the reference separates with a margin; (f) the edges of the contract; (g) the
-layers above."""
+probe of metrics.py above them (finetune() with the probe on: tests/test_gpu_probes.py)."""
 import ctypes
 import functools
-import json
 import math
 
 import numpy as np
@@ -273,7 +272,7 @@ def test_a_dimension_that_is_no_multiple_of_four(d):
     assert float(np.abs(_np(fit.grad) - g64).max()) < 2e-5 and abs(float(fit.loss_history[2]) - L64) < 2e-5
 
 
-# ---------------------------------------------------------------------------- (g) the layers above
+# ---------------------------------------------------------------------------- (g) the probe
 def test_linear_eval_probe_counts_equal_the_fp64_references():
     n, d, C, noise = R.BLOB_CASES[1]
     x, y = R.blobs(n, d, C, noise)
@@ -300,40 +299,3 @@ def test_linear_eval_probe_counts_equal_the_fp64_references():
         linear_eval_probe(_dev(x[tr]), _dev(bad), _dev(x[te]), _dev(y[te]), C, iters=2)
     with pytest.raises(ValueError):
         linear_eval_probe(_dev(x[tr]), _dev(y[tr]), _dev(x[:0]), _dev(y[:0]), C)
-
-
-@pytest.mark.parametrize("domain,kw", [("Cora_NC", {}), ("ENZYMES", {"gc_engine": True})])
-def test_finetune_logs_the_probe_and_trains_bit_for_bit_as_without_it(domain, kw, tmp_path, monkeypatch):
-    from gnn_pretraining_amd.finetune import finetune as FT
-    monkeypatch.setattr(FT, "OUTPUT_DIR", tmp_path / "finetune")
-    calls = []
-    real = ops._logreg_enqueue
-
-    def spy(*a, **k):
-        calls.append((a[2], a[3]))                                   # (num_classes, iters)
-        return real(*a, **k)
-
-    monkeypatch.setattr(ops, "_logreg_enqueue", spy)
-
-    def run(probe, log):
-        cfg = FT.FinetuneConfig(domain, "full_finetune", "b1", 1, logreg_probe=probe, **kw)
-        test = FT.finetune(cfg, epochs=1, data_root=str(tmp_path / "data"), data_scale=0.1, log_path=str(log))
-        state = torch.load(FT.OUTPUT_DIR / f"model_{cfg.exp_name}_{cfg.seed}.pt", map_location="cpu", weights_only=True)["model_state_dict"]
-        return test, state, [json.loads(line) for line in open(log)]
-
-    from gnn_pretraining_amd.constants import NUM_CLASSES
-    test, state, records = run(20, tmp_path / "on.jsonl")
-    assert calls == [(NUM_CLASSES[domain], 20)] * 3                  # step 0, the epoch, the test split
-    assert 0.0 <= test["test/logreg_accuracy"] <= 1.0
-    first = [r for r in records if r["step"] == 0]
-    assert len(first) == 1 and 0.0 <= first[0]["val/logreg_accuracy"] <= 1.0 and records[0] is first[0]
-    per_epoch = [r for r in records if "val/accuracy" in r]
-    assert len(per_epoch) == 1 and 0.0 <= per_epoch[0]["val/logreg_accuracy"] <= 1.0
-    assert "test/logreg_accuracy" in records[-1]
-
-    test0, state0, records0 = run(0, tmp_path / "off.jsonl")
-    assert len(calls) == 3                                           # off: the kernel is never reached
-    assert not any(k.startswith(("val/logreg_", "test/logreg_")) for r in records0 for k in r)
-    assert test0["test/loss"] == test["test/loss"] and test0["test/accuracy"] == test["test/accuracy"]
-    assert math.isfinite(test["test/loss"])
-    assert state.keys() == state0.keys() and all(torch.equal(state[n], state0[n]) for n in state)

@@ -1,6 +1,6 @@
 """Host-side contract of the k-means clustering probe (csrc/kmeans.hip): the fp64 reference of tests/kmeans_ref.py pinned on cases worked
 out by hand, its scores and metrics.clustering_scores against scikit-learn and a brute-force matching, declaration / binding / export of
-the four C-ABI entry points, a workspace without the n x kc matrix, the --cluster-probe flag and its FinetuneConfig field, and every bad
+the four C-ABI entry points, a workspace without the n x kc matrix, and every bad
 call refused with its error code before anything is launched (so this runs without a GPU)."""
 import ctypes
 import itertools
@@ -10,11 +10,9 @@ import pytest
 
 import kmeans_ref as R
 from gnn_pretraining_amd import _lib as L, ops
-from gnn_pretraining_amd.finetune import finetune as FT
 from gnn_pretraining_amd.finetune.metrics import clustering_scores
 
 ERR_ARG, ERR_WORKSPACE = -1, -3
-BASE = ["--finetune_strategy", "full_finetune", "--pretrained_scheme", "b1", "--seed", "1"]
 SYMBOLS = ("gmp_kmeans_workspace_bytes", "gmp_kmeans_assign", "gmp_kmeans_fit", "gmp_contingency")
 
 
@@ -174,33 +172,3 @@ def test_a_short_workspace_is_refused_and_no_rows_is_a_no_op():
     assert fit_call(ws_bytes=need - 1) == ERR_WORKSPACE and fit_call(ws=0) == ERR_WORKSPACE
     assert b"kmeans_fit" in L.lib().gmp_last_error_string()
     assert assign_call(n=0, ws=0, ws_bytes=0) == 0 and fit_call(n=0, ws=0, ws_bytes=0) == 0 and contingency_call(n=0) == 0
-
-
-# ---------------------------------------------------------------------------- the flag
-def test_cluster_probe_flag_and_config_field():
-    a = FT.build_parser().parse_args(["--domain_name", "Cora_NC"] + BASE)
-    assert a.cluster_probe == 0 and FT.config_from_args(a).cluster_probe == 0
-    assert FT.FinetuneConfig("Cora_NC", "full_finetune", "b1", 1).cluster_probe == 0
-    a = FT.build_parser().parse_args(["--domain_name", "Cora_NC", "--cluster-probe", "10"] + BASE)
-    assert a.cluster_probe == 10 and FT.config_from_args(a).cluster_probe == 10
-    a = FT.build_parser().parse_args(["--domain_name", "ENZYMES", "--gc-engine", "--cluster-probe", "64", "--knn-probe", "5"] + BASE)
-    cfg = FT.config_from_args(a)
-    assert cfg.cluster_probe == 64 and cfg.knn_probe == 5 and cfg.gc_engine
-    for k in ("-1", "65", "1000"):
-        with pytest.raises(ValueError, match="cluster_probe"):
-            FT.config_from_args(FT.build_parser().parse_args(["--domain_name", "Cora_NC", "--cluster-probe", k] + BASE))
-    with pytest.raises(SystemExit):
-        FT.build_parser().parse_args(["--domain_name", "Cora_NC", "--cluster-probe", "many"] + BASE)
-
-
-def test_cluster_probe_is_refused_without_class_labels_or_without_an_engine(monkeypatch):
-    for domain in ("Cora_LP", "CiteSeer_LP"):
-        with pytest.raises(ValueError, match="no class labels"):
-            FT.FinetuneConfig(domain, "full_finetune", "b1", 1, lp_engine=True, cluster_probe=10)
-    with pytest.raises(ValueError, match="--gc-engine"):
-        FT.FinetuneConfig("ENZYMES", "full_finetune", "b1", 1, cluster_probe=10)
-    assert FT.FinetuneConfig("PTC_MR", "linear_probe", "b1", 1, gc_engine=True, cluster_probe=10).cluster_probe == 10
-    monkeypatch.setenv("GMP_FINETUNE_ENGINE", "0")
-    with pytest.raises(ValueError, match="GMP_FINETUNE_ENGINE=0"):
-        FT.FinetuneConfig("Cora_NC", "full_finetune", "b1", 1, cluster_probe=10)
-    assert FT.FinetuneConfig("Cora_NC", "full_finetune", "b1", 1).cluster_probe == 0  # off: nothing to refuse

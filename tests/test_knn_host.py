@@ -1,6 +1,5 @@
 """Host-side contract of the streaming k-nearest-neighbour probe (csrc/knn.hip): the fp64 reference of tests/knn_ref.py pinned on cases
-worked out by hand, declaration / binding / export of the three C-ABI entry points, a workspace without the nq x ndb matrix, the
---knn-probe flag and its FinetuneConfig field, and every bad call refused with its error code before anything is launched (so this runs
+worked out by hand, declaration / binding / export of the three C-ABI entry points, a workspace without the nq x ndb matrix, and every bad call refused with its error code before anything is launched (so this runs
 without a GPU)."""
 import ctypes
 
@@ -9,10 +8,8 @@ import pytest
 
 import knn_ref as R
 from gnn_pretraining_amd import _lib as L
-from gnn_pretraining_amd.finetune import finetune as FT
 
 ERR_ARG, ERR_WORKSPACE = -1, -3
-BASE = ["--finetune_strategy", "full_finetune", "--pretrained_scheme", "b1", "--seed", "1"]
 SYMBOLS = ("gmp_knn_workspace_bytes", "gmp_knn_topk", "gmp_knn_vote")
 NINF = float("-inf")
 
@@ -117,33 +114,3 @@ def test_topk_exclude_self_needs_one_set_and_a_short_workspace_is_refused():
 def test_vote_refuses_bad_sizes_and_null_pointers(kw):
     assert vote_call(**kw) == ERR_ARG
     assert b"knn_vote" in L.lib().gmp_last_error_string()
-
-
-# ---------------------------------------------------------------------------- the flag
-def test_knn_probe_flag_and_config_field():
-    a = FT.build_parser().parse_args(["--domain_name", "Cora_NC"] + BASE)
-    assert a.knn_probe == 0 and FT.config_from_args(a).knn_probe == 0
-    assert FT.FinetuneConfig("Cora_NC", "full_finetune", "b1", 1).knn_probe == 0
-    a = FT.build_parser().parse_args(["--domain_name", "Cora_NC", "--knn-probe", "20"] + BASE)
-    assert a.knn_probe == 20 and FT.config_from_args(a).knn_probe == 20
-    a = FT.build_parser().parse_args(["--domain_name", "ENZYMES", "--gc-engine", "--knn-probe", "64"] + BASE)
-    cfg = FT.config_from_args(a)
-    assert cfg.knn_probe == 64 and cfg.gc_engine
-    for k in ("-1", "65", "1000"):
-        with pytest.raises(ValueError, match="knn_probe"):
-            FT.config_from_args(FT.build_parser().parse_args(["--domain_name", "Cora_NC", "--knn-probe", k] + BASE))
-    with pytest.raises(SystemExit):
-        FT.build_parser().parse_args(["--domain_name", "Cora_NC", "--knn-probe", "many"] + BASE)
-
-
-def test_knn_probe_is_refused_without_class_labels_or_without_an_engine(monkeypatch):
-    for domain in ("Cora_LP", "CiteSeer_LP"):
-        with pytest.raises(ValueError, match="no class labels"):
-            FT.FinetuneConfig(domain, "full_finetune", "b1", 1, lp_engine=True, knn_probe=20)
-    with pytest.raises(ValueError, match="--gc-engine"):
-        FT.FinetuneConfig("ENZYMES", "full_finetune", "b1", 1, knn_probe=20)
-    assert FT.FinetuneConfig("PTC_MR", "linear_probe", "b1", 1, gc_engine=True, knn_probe=20).knn_probe == 20
-    monkeypatch.setenv("GMP_FINETUNE_ENGINE", "0")
-    with pytest.raises(ValueError, match="GMP_FINETUNE_ENGINE=0"):
-        FT.FinetuneConfig("Cora_NC", "full_finetune", "b1", 1, knn_probe=20)
-    assert FT.FinetuneConfig("Cora_NC", "full_finetune", "b1", 1).knn_probe == 0      # off: nothing to refuse

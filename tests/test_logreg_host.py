@@ -1,7 +1,7 @@
 """Host-side contract of the linear-evaluation probe (csrc/logreg.hip): the fp64 reference of tests/logreg_ref.py against
 torch.nn.functional.cross_entropy + torch.optim.Adam in float64, the blob cases of the GPU whole-fit test solved by the reference alone
 (train accuracy 1.0 with a margin, so the GPU test may ask for every prediction), declaration / binding of the three C-ABI entry points,
-a workspace without the n x classes matrix, the --logreg-probe flag and its FinetuneConfig field, and every bad call refused with its
+a workspace without the n x classes matrix, and every bad call refused with its
 error code before anything is launched (so this runs without a GPU)."""
 import ctypes
 import functools
@@ -12,10 +12,8 @@ import torch
 
 import logreg_ref as R
 from gnn_pretraining_amd import _lib as L, ops
-from gnn_pretraining_amd.finetune import finetune as FT
 
 ERR_ARG, ERR_WORKSPACE = -1, -3
-BASE = ["--finetune_strategy", "full_finetune", "--pretrained_scheme", "b1", "--seed", "1"]
 SYMBOLS = ("gmp_logreg_workspace_bytes", "gmp_logreg_fit", "gmp_logreg_predict")
 
 
@@ -134,33 +132,3 @@ def test_bad_calls_are_refused_before_anything_is_launched():
         ops.logreg_fit(x, torch.zeros(4, dtype=torch.int64), 3)      # CPU tensors: there is no fallback
     with pytest.raises(L.GnnmpError):
         ops.logreg_predict(x, torch.zeros(3, 8), torch.zeros(3))
-
-
-# ---------------------------------------------------------------------------- the flag
-def test_logreg_probe_flag_and_config_field():
-    a = FT.build_parser().parse_args(["--domain_name", "Cora_NC"] + BASE)
-    assert a.logreg_probe == 0 and FT.config_from_args(a).logreg_probe == 0
-    assert FT.FinetuneConfig("Cora_NC", "full_finetune", "b1", 1).logreg_probe == 0
-    a = FT.build_parser().parse_args(["--domain_name", "Cora_NC", "--logreg-probe", "100"] + BASE)
-    assert a.logreg_probe == 100 and FT.config_from_args(a).logreg_probe == 100
-    a = FT.build_parser().parse_args(["--domain_name", "ENZYMES", "--gc-engine", "--logreg-probe", "10000", "--knn-probe", "5", "--cluster-probe", "2"] + BASE)
-    cfg = FT.config_from_args(a)
-    assert cfg.logreg_probe == 10000 and cfg.knn_probe == 5 and cfg.cluster_probe == 2 and cfg.gc_engine
-    for k in ("-1", "10001", "100000"):
-        with pytest.raises(ValueError, match="logreg_probe"):
-            FT.config_from_args(FT.build_parser().parse_args(["--domain_name", "Cora_NC", "--logreg-probe", k] + BASE))
-    with pytest.raises(SystemExit):
-        FT.build_parser().parse_args(["--domain_name", "Cora_NC", "--logreg-probe", "many"] + BASE)
-
-
-def test_logreg_probe_is_refused_without_class_labels_or_without_an_engine(monkeypatch):
-    for domain in ("Cora_LP", "CiteSeer_LP"):
-        with pytest.raises(ValueError, match="no class labels"):
-            FT.FinetuneConfig(domain, "full_finetune", "b1", 1, lp_engine=True, logreg_probe=100)
-    with pytest.raises(ValueError, match="--gc-engine"):
-        FT.FinetuneConfig("ENZYMES", "full_finetune", "b1", 1, logreg_probe=100)
-    assert FT.FinetuneConfig("PTC_MR", "linear_probe", "b1", 1, gc_engine=True, logreg_probe=100).logreg_probe == 100
-    monkeypatch.setenv("GMP_FINETUNE_ENGINE", "0")
-    with pytest.raises(ValueError, match="GMP_FINETUNE_ENGINE=0"):
-        FT.FinetuneConfig("Cora_NC", "full_finetune", "b1", 1, logreg_probe=100)
-    assert FT.FinetuneConfig("Cora_NC", "full_finetune", "b1", 1).logreg_probe == 0    # off: nothing to refuse
