@@ -332,7 +332,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(GemmArgs g) {
     }
 }
 
-// grouped TN split: C_g = alpha * sum_slices partial, column sums likewise (slice order: deterministic)
+// grouped TN split: C_g = act(alpha * sum_slices partial (+ C_g)), the epilogue of the unsliced kernels (accumulate, relu; the grouped TN form
+// takes no bias); column sums likewise, always stored (slice order: deterministic)
 // VEC: N, ldc and every output offset are multiples of 4 floats -- a thread owns four consecutive outputs and keeps up to eight slices'
 // float4 loads in flight before it adds them IN SLICE ORDER (the scalar form issued one 4-byte load per add: 7.6 us for the 4 MB of an
 // eight-slice 512 x 256 gradient, twice what the bytes take; same sums, bit for bit)
@@ -356,7 +357,11 @@ __global__ __launch_bounds__(256) void grouped_reduce_kernel(const GemmArgs g) {
                         if (z0 + u < g.gsplit) { s.x += v[u].x; s.y += v[u].y; s.z += v[u].z; s.w += v[u].w; }
                 }
                 const int64_t i = 4 * q;
-                *reinterpret_cast<float4*>(g.C + g.coff[grp] + (i / g.N) * g.ldc + i % g.N) = make_float4(g.alpha * s.x, g.alpha * s.y, g.alpha * s.z, g.alpha * s.w);
+                float4* o = reinterpret_cast<float4*>(g.C + g.coff[grp] + (i / g.N) * g.ldc + i % g.N);
+                float4 v = make_float4(g.alpha * s.x, g.alpha * s.y, g.alpha * s.z, g.alpha * s.w);
+                if (g.accumulate) { const float4 c = *o; v.x += c.x; v.y += c.y; v.z += c.z; v.w += c.w; }
+                if (g.relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+                *o = v;
             } else if (g.asum) {
                 for (int64_t m = 4 * (q - quads); m < g.M && m < 4 * (q - quads) + 4; ++m) {
                     float s = 0.f;
@@ -371,7 +376,11 @@ __global__ __launch_bounds__(256) void grouped_reduce_kernel(const GemmArgs g) {
         float s = 0.f;
         if (i < total) {
             for (int z = 0; z < g.gsplit; ++z) s += g.gpart[((int64_t)grp * g.gsplit + z) * total + i];
-            g.C[g.coff[grp] + (i / g.N) * g.ldc + i % g.N] = g.alpha * s;
+            float* o = g.C + g.coff[grp] + (i / g.N) * g.ldc + i % g.N;
+            float v = g.alpha * s;
+            if (g.accumulate) v += *o;
+            if (g.relu) v = fmaxf(v, 0.f);
+            *o = v;
         } else if (g.asum) {
             const int64_t m = i - total;
             for (int z = 0; z < g.gsplit; ++z) s += g.gasum_part[((int64_t)grp * g.gsplit + z) * g.M + m];
@@ -618,6 +627,7 @@ int gmp::gemm_f32_epilogue(int mode, const float* A, const float* B, const float
                (lda % 4 == 0) && aligned16(A), (ldb % 4 == 0) && aligned16(B)};
     if (!epi) take_signal(g);
     g.vecC = (ldc % 4 == 0) && aligned16(C);
+    if (bias && !aligned16(bias)) g.vecC = 0;          // the float4 epilogue of the pipelined kernel reads the bias in quads too
     if (epi) {
         g.scale = scale; g.shift = shift; g.resid = resid; g.ldr = ldr;
         // float4 epilogue of the pipelined kernel: every per-column / per-element operand 16-byte addressable, whole quads of columns
@@ -690,6 +700,12 @@ int grouped_impl(int mode, const float* A, const float* B, const float* bias, fl
     if (mode < 0 || mode > 2) return gmp::fail(GMP_ERR_ARG, "gemm_grouped: mode %d", mode);
     if (groups < 1 || groups > MAXG || !group_rows_host) return gmp::fail(GMP_ERR_ARG, "gemm_grouped: %d groups (max %d)", groups, MAXG);
     if (N <= 0 || K < 0 || !A || !B || !C) return gmp::fail(GMP_ERR_ARG, "gemm_grouped: bad argument");
+    if (mode == GMP_GEMM_TN && (M_tn < 0 || bias)) return gmp::fail(GMP_ERR_ARG, "gemm_grouped: the TN form takes M_tn >= 0 and no bias");
+    // the rules of gmp_gemm_f32 (a too small ldc would let one row's store run into the next)
+    const int64_t need_lda = mode == GMP_GEMM_TN ? M_tn : K, need_ldb = mode == GMP_GEMM_NT ? K : N;
+    if (lda < need_lda || ldb < need_ldb || ldc < N)
+        return gmp::fail(GMP_ERR_ARG, "gemm_grouped: leading dims (%lld,%lld,%lld) too small for M_tn=%lld N=%lld K=%lld mode %d",
+                         (long long)lda, (long long)ldb, (long long)ldc, (long long)M_tn, (long long)N, (long long)K, mode);
     GemmArgs g{};
     g.A = A; g.B = B; g.bias = bias; g.C = C; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
     g.alpha = alpha; g.accumulate = accumulate; g.relu = relu; g.splitk = 1; g.partial = nullptr;
@@ -697,7 +713,7 @@ int grouped_impl(int mode, const float* A, const float* B, const float* bias, fl
     g.vecB = (ldb % 4 == 0) && aligned16(B);
     g.groups = groups;
     g.gsplit = 1;
-    g.vecC = (ldc % 4 == 0) && aligned16(C);
+    g.vecC = (ldc % 4 == 0) && aligned16(C) && (!bias || aligned16(bias));      // (the pipelined kernel's float4 epilogue reads the bias in quads)
     g.asum = mode == GMP_GEMM_TN ? a_colsum : nullptr;
     int64_t max_rows = 0;
     for (int i = 0; i <= groups; ++i) {
@@ -712,6 +728,7 @@ int grouped_impl(int mode, const float* A, const float* B, const float* bias, fl
         g.asumoff[i] = a_colsum_off_host ? a_colsum_off_host[i] : (int64_t)i * M_tn;
         if ((g.boff[i] % 4) || (g.coff[i] % 4)) g.vecB = 0;
         if (g.coff[i] % 4) g.vecC = 0;
+        if (bias && (g.biasoff[i] % 4)) g.vecC = 0;
     }
     hipStream_t st = (hipStream_t)stream;
     if (mode == GMP_GEMM_TN) {

@@ -157,7 +157,17 @@ int gmp_gemm_f32(int mode, const float* A, const float* B, const float* bias, fl
  *            A[:, m] -- the bias gradient rides along with the weight gradient for free.
  *            workspace (nullable): lets TN slice each group's rows over several workgroups (partials summed
  *            in slice order by a second kernel) when the output alone cannot fill the chip.
- * Offsets are in floats; NULL offset arrays mean 0. */
+ * Offsets are in floats; NULL offset arrays mean 0 (a_colsum_off_host: g * M_tn).
+ * Epilogue, every mode and every path (with or without a workspace): C = alpha * product (+ bias, NT / NN only: a bias with TN is refused);
+ *   accumulate != 0 -> that value is ADDED to what C held; relu != 0 -> max(., 0) last.  An empty group of the TN form therefore leaves
+ *   zeros, or C as it was under accumulate; an empty group of NT / NN owns no rows and writes nothing.  a_colsum is always stored, never
+ *   accumulated.  Rows of C beyond group_rows_host[groups] and columns beyond N (ldc > N) are never written.
+ * Leading dimensions follow gmp_gemm_f32: NT lda, ldb >= K; NN lda >= K, ldb >= N; TN lda >= M_tn, ldb >= N; always ldc >= N -- anything
+ *   smaller is GMP_ERR_ARG and nothing is launched.  groups outside 1 .. 24, a NULL or descending row list, N <= 0 likewise.
+ * Alignment is never required: bases, leading dimensions and offsets (b_off, bias_off, c_off) that are not multiples of 4 floats / 16 bytes
+ *   only select the guarded loads and scalar stores (and with them possibly the other kernel family: the same products, summed in that
+ *   kernel's order).  A call whose groups are all empty (TN: M_tn == 0)
+ *   launches nothing, returns GMP_OK and leaves a pending gmp_gate_open_by_next_gemm signal pending. */
 int gmp_gemm_f32_grouped(int mode, const float* A, const float* B, const float* bias, float* C, int groups,
                          const int32_t* group_rows_host, const int64_t* b_off_host, const int64_t* bias_off_host,
                          const int64_t* c_off_host, float* a_colsum, const int64_t* a_colsum_off_host,
