@@ -134,6 +134,10 @@ _SIGS: Dict[str, tuple] = {
     "gmp_logreg_workspace_bytes": (sz, [i64, i32, i32]),
     "gmp_logreg_fit": (C.c_int, [p, p, i64, i32, i32, i32, f32, f32, p, p, p, p, p, p, p, p, p, p, sz, p]),
     "gmp_logreg_predict": (C.c_int, [p, i64, p, p, i32, i32, p, p, p, sz, p]),
+    "gmp_repr_workspace_bytes": (sz, [i64, i32]),
+    "gmp_repr_pair_stats": (C.c_int, [p, i64, i32, f32, p, p, sz, p]),
+    "gmp_repr_alignment": (C.c_int, [p, p, i64, i32, f32, p, p, sz, p]),
+    "gmp_repr_gram": (C.c_int, [p, i64, i32, p, p, p, sz, p]),
     "gmp_cls_counts_workspace_bytes": (sz, [i64, i32]),
     "gmp_cls_counts": (C.c_int, [p, p, p, i64, i32, p, p, p, p, sz, p]),
     "gmp_graph_props_workspace_bytes": (sz, [i32, i64]),

@@ -3,7 +3,7 @@ miner, process_batch per task type, one AdamW step per batch over FinetuneGNN.pa
 test metrics from the best checkpoint.  Data come from the loaders of gnn_pretraining_amd/data (processed datasets in
 data/processed; synthetic stand-ins are generated when none were exported).  wandb is replaced by a JSONL logger with the
 same metric keys.  Build-only flags: --epochs, --device, --data-root, --data-scale, --log, --sparse-features, --lp-engine, --gc-engine,
---engine-eval, --lp-ranking, --device-metrics, --miner, --knn-probe, --cluster-probe, --logreg-probe."""
+--engine-eval, --lp-ranking, --device-metrics, --miner, --knn-probe, --cluster-probe, --logreg-probe, --repr-stats."""
 from __future__ import annotations
 
 import argparse
@@ -17,7 +17,7 @@ from typing import Callable, Dict, List, Optional, Tuple
 import torch
 from torch import Tensor
 
-from .. import operators as O, ops
+from .. import operators as O, ops, repr_stats as RS
 from ..constants import NUM_CLASSES, TASK_TYPES
 from ..graph import SparseFeatures
 from ..models.finetune_model import FinetuneGNN, create_finetune_model
@@ -151,6 +151,7 @@ class FinetuneConfig:
     knn_probe: int = 0                  # classification domains on an engine: k of the weighted k-NN probe on the backbone's embeddings (val/ and test/knn_accuracy); 0 = off
     cluster_probe: int = 0              # classification domains on an engine: restarts of the k-means clustering probe on the backbone's embeddings (val/cluster_nmi, test/cluster_nmi / _ari / _accuracy); 0 = off
     logreg_probe: int = 0               # classification domains on an engine: Adam iterations of the linear-evaluation probe (softmax regression fitted on the train split's embeddings: val/ and test/logreg_accuracy); 0 = off
+    repr_stats: bool = False            # on an engine: the label-free statistics of the validation embeddings (repr_stats.embedding_stats: val/repr_uniformity, val/repr_mean_cosine, val/repr_rankme); every domain, link prediction included
 
     def __post_init__(self) -> None:
         if self.sparse_features and TASK_TYPES[self.domain_name] == "graph_classification":
@@ -178,6 +179,11 @@ class FinetuneConfig:
                 raise ValueError(f"{p.field} needs an active fine-tune engine for {self.domain_name} (it reads the engine's eval-mode embed()): "
                                  + {"node_classification": "the node engine is switched off (GMP_FINETUNE_ENGINE=0)",
                                     "graph_classification": "pass gc_engine (--gc-engine)"}[TASK_TYPES[self.domain_name]])
+        if self.repr_stats and not engine_active(self):
+            raise ValueError(f"repr_stats needs an active fine-tune engine for {self.domain_name} (it reads the engine's eval-mode embed()): "
+                             + {"node_classification": "the node engine is switched off (GMP_FINETUNE_ENGINE=0)",
+                                "link_prediction": "pass lp_engine (--lp-engine)",
+                                "graph_classification": "pass gc_engine (--gc-engine)"}[TASK_TYPES[self.domain_name]])
         if self.lp_ranking and not self.lp_engine:
             raise ValueError("lp_ranking ranks with the link-prediction engine (gmp_lp_rank): pass lp_engine (--lp-engine)")
         self.exp_name = f"{self.domain_name}_{self.finetune_strategy}_{self.pretrained_scheme}"
@@ -430,18 +436,31 @@ def probe_embeddings(engine, datasets, device, cfg: FinetuneConfig):
         return sets
 
 
+def repr_stats_keys(emb: Tensor) -> Dict[str, float]:
+    """cfg.repr_stats: the label-free statistics of the rows of emb (repr_stats.embedding_stats) as they are logged."""
+    return {f"val/repr_{k}": v for k, v in RS.embedding_stats(emb.contiguous()).items()}
+
+
 def run_probes(engine, train_loader, loader, device, cfg: FinetuneConfig, prefix: str) -> Dict[str, float]:
     """The scores of every active probe (PROBES, in that order) on `loader`'s split, keyed as they are logged under `prefix` ("val" /
-    "test").  One probe_embeddings pass serves them all; the train split is embedded only when an active probe fits on it."""
+    "test").  One probe_embeddings pass serves them all; the train split is embedded only when an active probe fits on it.  With
+    cfg.repr_stats the validation split's rows of that same pass (on a link-prediction domain, which has no probes: every row of the
+    engine's embed()) also give val/repr_*."""
     active = [p for p in PROBES if getattr(cfg, p.field)]
-    if not active:
+    want_repr = cfg.repr_stats and prefix == "val"
+    if not active and not want_repr:
         return {}
+    if cfg.task_type == "link_prediction":
+        with torch.no_grad():
+            return repr_stats_keys(engine.embed())
     with_train = any(p.needs_train for p in active)
     sets = probe_embeddings(engine, ((train_loader.dataset,) if with_train else ()) + (loader.dataset,), device, cfg)
     out = {}
     for p in active:
         scores = p.score(sets[0] if p.needs_train else None, sets[-1], cfg)
         out.update({f"{prefix}/{p.name}_{k}": scores[k] for k in getattr(p, prefix)})
+    if want_repr:
+        out.update(repr_stats_keys(sets[-1][0]))
     return out
 
 
@@ -499,11 +518,13 @@ def finetune(cfg: FinetuneConfig, epochs: Optional[int] = None, device: Optional
         eval_engine = node_engine or lp_engine or gc_engine
         if eval_engine is None:
             raise ValueError(f"engine_eval needs an active fine-tune engine for {cfg.domain_name}")
-    probe_engine = node_engine or gc_engine                  # (a configuration with a probe on has one: __post_init__)
+    probe_engine = node_engine or gc_engine or lp_engine     # (a configuration with a probe or repr_stats on has one: __post_init__)
     before = run_probes(probe_engine, train_loader, val_loader, dev, cfg, "val")     # the embeddings before any training
     for p in PROBES:                                         # one line per active probe
         if getattr(cfg, p.field):
             logger.log({k: v for k, v in before.items() if k.startswith(f"val/{p.name}_")}, 0)
+    if cfg.repr_stats:
+        logger.log({k: v for k, v in before.items() if k.startswith("val/repr_")}, 0)
     for epoch in range(1, (epochs or cfg.epochs) + 1):
         if node_engine is not None:
             run_training_node_engine(node_engine, train_loader, dev, epoch, global_step, cfg, logger)
@@ -567,6 +588,9 @@ def build_parser() -> argparse.ArgumentParser:
                         "stream (tiles recomputed, workspace O(n d + E), n <= 2^20), auto (stream beyond 65535 nodes)")
     for probe in PROBES:
         p.add_argument(probe.flag, type=int, default=0, metavar=probe.metavar, help=probe.help)
+    p.add_argument("--repr-stats", action="store_true",
+                   help="on an engine, every domain: also log val/repr_uniformity, val/repr_mean_cosine and val/repr_rankme (every epoch and once "
+                        "before training), the label-free statistics of the validation embeddings (on Cora_LP / CiteSeer_LP: of all node embeddings)")
     return p
 
 
@@ -575,7 +599,7 @@ def config_from_args(a: argparse.Namespace) -> FinetuneConfig:
                           lp_engine=getattr(a, "lp_engine", False), gc_engine=getattr(a, "gc_engine", False),
                           engine_eval=getattr(a, "engine_eval", False), lp_ranking=getattr(a, "lp_ranking", False),
                           device_metrics=getattr(a, "device_metrics", False), miner_impl=getattr(a, "miner", "matrix"),
-                          **{p.field: getattr(a, p.field, 0) for p in PROBES})
+                          repr_stats=getattr(a, "repr_stats", False), **{p.field: getattr(a, p.field, 0) for p in PROBES})
 
 
 def main() -> None:

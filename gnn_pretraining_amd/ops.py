@@ -1359,6 +1359,63 @@ def logreg_predict(x: Tensor, weight: Tensor, bias: Tensor, return_logits: bool 
     return (pred, logits) if return_logits else pred
 
 
+REPR_MAX_DIM = 256              # gmp_repr_* (gnnmp.h)
+REPR_MAX_ROWS = 2**20           # the rows gmp_repr_workspace_bytes sizes a workspace for
+
+
+def _repr_args(who: str, z: Tensor, name: str, min_rows: int) -> Tuple[int, int]:
+    _need(z, torch.float32, name, 2)
+    n, d = z.shape
+    if not min_rows <= n <= REPR_MAX_ROWS or not 1 <= d <= REPR_MAX_DIM:
+        raise L.GnnmpError(f"{who}: {name} {tuple(z.shape)} ({min_rows} <= rows <= {REPR_MAX_ROWS}, 1 <= dim <= {REPR_MAX_DIM})")
+    return n, d
+
+
+def repr_pair_stats(z: Tensor, t: float = 2.0) -> Tensor:
+    """The all-pairs sums of the rows of z [n, d] (fp32 contiguous, 2 <= n <= 2^20, 1 <= d <= 256) on the unit sphere, without the n x n
+    similarity matrix (gnnmp.h gmp_repr_pair_stats; csrc/repr_stats.hip): an fp64 [2] tensor on the device, [0] = the sum over i < j of
+    exp(-2 t (1 - s_ij)), [1] = the sum over i < j of s_ij, with s_ij the cosine similarity of rows i and j (a zero row scores 0).  t >= 0.
+    No read-back; two calls on the same input give equal bits."""
+    n, d = _repr_args("repr_pair_stats", z, "z", 2)
+    if not float(t) >= 0.0:
+        raise L.GnnmpError(f"repr_pair_stats: t={t} (must be >= 0)")
+    dev, l = z.device, L.lib()
+    out = torch.empty(2, dtype=torch.float64, device=dev)
+    ws = _ws(l.gmp_repr_workspace_bytes(n, d), dev)
+    L.check(l.gmp_repr_pair_stats(_ptr(z), n, d, float(t), _ptr(out), _ptr(ws), ws.numel(), _stream(z)), "gmp_repr_pair_stats")
+    return out
+
+
+def repr_alignment_sum(z1: Tensor, z2: Tensor, alpha: float = 2.0) -> Tensor:
+    """An fp64 [1] tensor on the device: the sum over the rows i of max(0, 2 - 2 s_ii)^(alpha / 2), s_ii the cosine similarity of row i of
+    z1 and row i of z2 (both [n, d] fp32 contiguous, 1 <= n <= 2^20, 1 <= d <= 256), i.e. of ||zn1_i - zn2_i||^alpha on the unit sphere
+    (gnnmp.h gmp_repr_alignment).  alpha > 0.  No read-back."""
+    n, d = _repr_args("repr_alignment_sum", z1, "z1", 1)
+    _need(z2, torch.float32, "z2", 2)
+    if tuple(z2.shape) != (n, d) or z2.device != z1.device:
+        raise L.GnnmpError(f"repr_alignment_sum: z1 {tuple(z1.shape)} on {z1.device}, z2 {tuple(z2.shape)} on {z2.device}")
+    if not float(alpha) > 0.0:
+        raise L.GnnmpError(f"repr_alignment_sum: alpha={alpha} (must be positive)")
+    dev, l = z1.device, L.lib()
+    out = torch.empty(1, dtype=torch.float64, device=dev)
+    ws = _ws(l.gmp_repr_workspace_bytes(n, d), dev)
+    L.check(l.gmp_repr_alignment(_ptr(z1), _ptr(z2), n, d, float(alpha), _ptr(out), _ptr(ws), ws.numel(), _stream(z1)), "gmp_repr_alignment")
+    return out
+
+
+def repr_gram(z: Tensor) -> Tuple[Tensor, Tensor]:
+    """(gram [d, d], colsum [d]), both fp64 on the device: Z^T Z and the sum of the rows of z [n, d] (fp32 contiguous, 1 <= n <= 2^20,
+    1 <= d <= 256, rows as they are, not normalised), products and sums in fp64 (gnnmp.h gmp_repr_gram): every product of two fp32 values
+    is exact in fp64, so the error is that of the fp64 sums alone.  gram is bitwise symmetric.  No read-back."""
+    n, d = _repr_args("repr_gram", z, "z", 1)
+    dev, l = z.device, L.lib()
+    gram = torch.empty(d, d, dtype=torch.float64, device=dev)
+    colsum = torch.empty(d, dtype=torch.float64, device=dev)
+    ws = _ws(l.gmp_repr_workspace_bytes(n, d), dev)
+    L.check(l.gmp_repr_gram(_ptr(z), n, d, _ptr(gram), _ptr(colsum), _ptr(ws), ws.numel(), _stream(z)), "gmp_repr_gram")
+    return gram, colsum
+
+
 CLS_MAX_ROWS, CLS_MAX_CLASSES = 262144, 32      # gmp_cls_counts: the pair count is n^2 compares (gnnmp.h)
 
 

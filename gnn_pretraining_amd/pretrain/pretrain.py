@@ -4,7 +4,7 @@ datasets in data/processed; synthetic stand-ins are generated when none were exp
 of the reference need the network).  wandb is replaced by a JSONL logger with the same metric keys.
 
 Build-only flags (the reference's flags are unchanged): --epochs, --steps-per-epoch, --log, --device, --data-root,
---data-scale, --rng, --device-negatives, --module-path, --surgery, --surgery-scope.
+--data-scale, --rng, --device-negatives, --module-path, --surgery, --surgery-scope, --repr-stats.
 """
 from __future__ import annotations
 
@@ -230,14 +230,63 @@ def run_evaluation_engine(state: StepState, engine, val_loaders, generator: torc
     return _val_metrics(state, per_dt)
 
 
+REPR_STATS_LEVELS = ("off", "graph", "node")
+
+
+@torch.no_grad()
+def run_repr_stats(state: StepState, val_loaders, device, level: str) -> Dict[str, float]:
+    """The label-free statistics of the backbone's embeddings (repr_stats.py) over every domain's whole validation set, as the
+    parameters stand now: val/repr/{domain}/uniformity, /mean_cosine and /rankme of the mean-pooled graph embeddings (level "graph") or
+    of the node rows (level "node", the first ops.REPR_MAX_ROWS of them), their means over the domains as val/repr/uniformity and so
+    on, and val/repr/{domain}/alignment between the mean-pooled embeddings of the two views GraphAugmentor draws of every graph.
+    A pure reader: the model runs in eval mode under no_grad (no dropout counter, no running statistic moves) and is put back into
+    the mode it was in; the views come from a generator of this function's own, seeded with cfg.seed at every call, so every call
+    scores the same views and the shared generator, the engine's streams and the checkpoint are what they are without it."""
+    from .. import operators as O, ops, repr_stats as RS
+    from .augmentations import GraphAugmentor
+    model = state.model
+    was_training = model.training
+    model.eval()
+    views_gen = torch.Generator()
+    views_gen.manual_seed(state.cfg.seed)
+    out: Dict[str, float] = {}
+    names = ("uniformity", "mean_cosine", "rankme")
+    try:
+        for d, loader in val_loaders.items():
+            rows, v1, v2 = [], [], []
+            for host in loader.batches():
+                b = host.to(device)
+                h = model(b, d)
+                rows.append(h if level == "node" else O.global_mean_pool(h, b.batch, ptr32=b.ptr32))
+                a1, a2, _, _ = GraphAugmentor.create_two_views(b, views_gen)
+                v1.append(O.global_mean_pool(model(a1, d), a1.batch, ptr32=a1.ptr32))
+                v2.append(O.global_mean_pool(model(a2, d), a2.batch, ptr32=a2.ptr32))
+            z = torch.cat(rows).contiguous()
+            if z.size(0) > ops.REPR_MAX_ROWS:
+                print(f"repr stats: {d}: the first {ops.REPR_MAX_ROWS} of {z.size(0)} rows are scored")
+                z = z[:ops.REPR_MAX_ROWS].contiguous()
+            for k, v in RS.embedding_stats(z).items():
+                out[f"val/repr/{d}/{k}"] = v
+            out[f"val/repr/{d}/alignment"] = RS.alignment(torch.cat(v1).contiguous(), torch.cat(v2).contiguous())
+        for k in names:
+            out[f"val/repr/{k}"] = sum(out[f"val/repr/{d}/{k}"] for d in val_loaders) / len(val_loaders)
+    finally:
+        model.train(was_training)
+    return out
+
+
 def pretrain(cfg: PretrainConfig, epochs: int = EPOCHS, steps_per_epoch: Optional[int] = None, log_path: Optional[str] = None,
              device: Optional[str] = None, data_root: Optional[str] = None, data_scale: float = 1.0,
              rng_mode: str = "reference", use_engine: bool = True, device_negatives: bool = False,
-             surgery: str = "reference", surgery_scope: str = "tensor") -> Path:
+             surgery: str = "reference", surgery_scope: str = "tensor", repr_stats: str = "off") -> Path:
     """pretrain.py:284-349.  `steps_per_epoch` truncates an epoch (the loader's own length -- 462 for the four-domain
     schemes on the real data -- is the default); data come from data/processed (synthetic stand-ins are generated on
     first use when no exported real data is there).  `surgery` / `surgery_scope`: the gradient-surgery rule of both paths (control.GradientSurgery,
-    StepEngine); the default is the reference's.  Its metric keys (gradient_surgery/*) are the same under every rule."""
+    StepEngine); the default is the reference's.  Its metric keys (gradient_surgery/*) are the same under every rule.
+    `repr_stats` ("graph" / "node"): also log run_repr_stats' val/repr/* keys, once before the first epoch (step 0) and with every
+    epoch's val/* record; training and the checkpoint are bit for bit what they are without it."""
+    if repr_stats not in REPR_STATS_LEVELS:
+        raise ValueError(f"repr_stats={repr_stats!r} is not one of {REPR_STATS_LEVELS}")
     from ..data.data_setup import ensure_processed
     from ..data.pretrain_data_loaders import create_train_data_loader, create_val_data_loader
     from .._host import limit_host_threads
@@ -268,6 +317,8 @@ def pretrain(cfg: PretrainConfig, epochs: int = EPOCHS, steps_per_epoch: Optiona
                             device_negatives=device_negatives, surgery=surgery, surgery_scope=surgery_scope)
     best, stale, global_step = float("inf"), 0, [0]
     path = OUTPUT_DIR / f"model_{cfg.exp_name}_{cfg.seed}.pt"
+    if repr_stats != "off":
+        logger.log(run_repr_stats(state, val_loaders, dev, repr_stats), 0)      # the embeddings before any training
     for epoch in range(1, epochs + 1):
         t0 = time.time()
         if engine is not None:
@@ -283,7 +334,8 @@ def pretrain(cfg: PretrainConfig, epochs: int = EPOCHS, steps_per_epoch: Optiona
         else:
             val = run_evaluation(state, val_loaders, generator, dev)
         val.update({"epoch_seconds": time.time() - t0, "train_seconds": t1 - t0, "train_graphs_per_s": steps * BATCH_SIZE / (t1 - t0)})
-        logger.log(val, global_step[0])
+        # (val/repr/* ride in the log record only: the checkpoint's val_metrics below keep the reference's keys)
+        logger.log({**val, **run_repr_stats(state, val_loaders, dev, repr_stats)} if repr_stats != "off" else val, global_step[0])
         if val["val/loss/total"] < best:
             best, stale = val["val/loss/total"], 0
             ckpt = {"epoch": epoch, "model_state_dict": model.state_dict(),
@@ -319,6 +371,9 @@ def parse_args(argv=None) -> argparse.Namespace:
                         "pcgrad = PCGrad as published (every head trained in every step); mean = the plain mean over the tasks")
     p.add_argument("--surgery-scope", choices=["tensor", "model"], default="tensor",
                    help="with --surgery pcgrad: project tensor by tensor, or once over the whole shared parameter vector")
+    p.add_argument("--repr-stats", choices=list(REPR_STATS_LEVELS), default="off",
+                   help="also log val/repr/*: uniformity, mean cosine and RankMe of the validation embeddings (graph: mean-pooled graph "
+                        "embeddings; node: node rows) and the alignment of two augmented views, before training and after every epoch")
     a = p.parse_args(argv)
     if a.surgery_scope == "model" and a.surgery == "reference":
         p.error("--surgery-scope model needs --surgery pcgrad")
@@ -330,7 +385,7 @@ def parse_args(argv=None) -> argparse.Namespace:
 def main() -> None:
     a = parse_args()
     path = pretrain(PretrainConfig(exp_name=a.exp_name, seed=a.seed), a.epochs, a.steps_per_epoch, a.log, a.device,
-                    a.data_root, a.data_scale, a.rng, not a.module_path, a.device_negatives, a.surgery, a.surgery_scope)
+                    a.data_root, a.data_scale, a.rng, not a.module_path, a.device_negatives, a.surgery, a.surgery_scope, repr_stats=a.repr_stats)
     print(f"saved {path}")
 
 

@@ -461,6 +461,33 @@ int gmp_logreg_predict(const float* x, int64_t n, const float* W, const float* b
                        void* workspace, size_t workspace_bytes, gmp_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
+ * Label-free statistics of an embedding matrix (csrc/repr_stats.hip): the sums behind uniformity and alignment (Wang & Isola 2020) and the
+ * fp64 Gram matrix whose spectrum gives RankMe (Garrido et al. 2023).  z [n, dim] contiguous fp32, 1 <= dim <= 256.  Where rows are
+ * normalised it is as gmp_knn_topk does, zn = z / max(||z||, 1e-12): a zero row stays zero and its similarities are 0.  s_ij = <zn_i, zn_j>.
+ * Outputs are fp64 sums on the device (the caller divides); every reduction runs in a fixed order without floating-point atomics, so two
+ * calls on the same input give equal bits.  Asynchronous on `stream`, no host read-back, no allocation.
+ * gmp_repr_pair_stats, 2 <= n <= 2^20, t >= 0: out[0] = the sum over i < j of exp(-2 t (1 - s_ij)) (= exp(-t ||zn_i - zn_j||^2) on unit
+ *   rows), out[1] = the sum over i < j of s_ij.  s_ij is the k-ordered fp32 MFMA chain of csrc/sim_tile.h and lives only in accumulators:
+ *   no n x n array exists, every unordered pair is computed once.  The 16 values a lane holds of a tile are summed in fp32, everything
+ *   above that in fp64.
+ * gmp_repr_alignment, 1 <= n <= 2^24, alpha > 0: out[0] = the sum over i of max(0, 2 - 2 s_ii)^(alpha / 2), s_ii = <zn1_i, zn2_i> of the
+ *   rows of z1 and z2 [n, dim]; the dot products and norms are accumulated in fp64.
+ * gmp_repr_gram, 1 <= n <= 2^24: gram [dim, dim] = Z^T Z and colsum [dim] = the sum of the rows, both fp64, on the raw (not normalised)
+ *   rows.  Products and accumulation are fp64 (v_mfma_f64_16x16x4_f64) from fp32 inputs widened on load, so every product is exact; gram
+ *   is bitwise symmetric.
+ * GMP_ERR_ARG outside those ranges, GMP_ERR_WORKSPACE when the workspace is short; nothing is launched then.
+ * gmp_repr_workspace_bytes(n, dim), 1 <= n <= 2^20, serves all three: 4 n dpad (the normalised copy, dpad = dim rounded up to 4) + at most
+ *   64 partial Grams of 8 DP^2 bytes (DP = dim rounded up to 32, 64, 128, 192 or 256) + under 1 MiB of partial sums.  0 outside that
+ *   range; gmp_repr_alignment and gmp_repr_gram beyond 2^20 rows need no more than gmp_repr_workspace_bytes(2^20, dim).
+ * ------------------------------------------------------------------------- */
+size_t gmp_repr_workspace_bytes(int64_t n, int dim);
+int gmp_repr_pair_stats(const float* z, int64_t n, int dim, float t, double* out, void* workspace, size_t workspace_bytes, gmp_stream_t stream);
+int gmp_repr_alignment(const float* z1, const float* z2, int64_t n, int dim, float alpha, double* out, void* workspace, size_t workspace_bytes,
+                       gmp_stream_t stream);
+int gmp_repr_gram(const float* z, int64_t n, int dim, double* gram, double* colsum, void* workspace, size_t workspace_bytes,
+                  gmp_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
  * Integer counts for the classification metrics of fine-tuning (src/finetune/metrics.py:39-82: accuracy, F1, precision, recall and the
  * one-vs-rest ROC AUC of scikit-learn), from targets [n] int64, predictions [n] int64 and probabilities [n, classes] fp32 contiguous:
  *   confusion  int64 [classes * classes]  entry [t * classes + p] = rows with target t and prediction p
