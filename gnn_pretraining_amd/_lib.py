@@ -124,6 +124,11 @@ _SIGS: Dict[str, tuple] = {
     "gmp_lp_topk_workspace_bytes": (sz, [i64, i64]),
     "gmp_lp_rank": (C.c_int, [p, p, p, i64, i64, i32, i32, p, p, p, p, p, p, i64, p, p, p, p, sz, p]),
     "gmp_lp_topk": (C.c_int, [p, p, i64, i64, i32, i32, i32, p, p, p, p, p, p, i64, p, p, p, sz, p]),
+    "gmp_lp_cn_tile_nodes": (C.c_int, []),
+    "gmp_lp_cn_rank_workspace_bytes": (sz, [i64, i64]),
+    "gmp_lp_cn_score": (C.c_int, [p, p, i64, i64, p, p, i64, p, i32, p, p]),
+    "gmp_lp_cn_rank": (C.c_int, [p, p, i64, i64, p, p, i64, p, i32, p, p, i64, p, p, p, p, sz, p]),
+    "gmp_graph_simple_check": (C.c_int, [p, p, i64, i64, p, p]),
     "gmp_knn_workspace_bytes": (sz, [i64, i64, i32, i32]),
     "gmp_knn_topk": (C.c_int, [p, i64, p, i64, i32, i32, i32, p, p, p, p, sz, p]),
     "gmp_knn_vote": (C.c_int, [p, p, i64, i32, p, i64, i32, f32, p, p, p, p]),

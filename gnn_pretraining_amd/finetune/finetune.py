@@ -151,6 +151,7 @@ class FinetuneConfig:
     knn_probe: int = 0                  # classification domains on an engine: k of the weighted k-NN probe on the backbone's embeddings (val/ and test/knn_accuracy); 0 = off
     cluster_probe: int = 0              # classification domains on an engine: restarts of the k-means clustering probe on the backbone's embeddings (val/cluster_nmi, test/cluster_nmi / _ari / _accuracy); 0 = off
     logreg_probe: int = 0               # classification domains on an engine: Adam iterations of the linear-evaluation probe (softmax regression fitted on the train split's embeddings: val/ and test/logreg_accuracy); 0 = off
+    lp_heuristics: bool = False         # link-prediction domains: the test record also carries test/{cn,jaccard,aa,ra}_mrr / _hits@K, the neighbourhood baselines ranked like lp_ranking on the message-passing graph (link_heuristics.py); needs no engine
     repr_stats: bool = False            # on an engine: the label-free statistics of the validation embeddings (repr_stats.embedding_stats: val/repr_uniformity, val/repr_mean_cosine, val/repr_rankme); every domain, link prediction included
 
     def __post_init__(self) -> None:
@@ -186,6 +187,8 @@ class FinetuneConfig:
                                 "graph_classification": "pass gc_engine (--gc-engine)"}[TASK_TYPES[self.domain_name]])
         if self.lp_ranking and not self.lp_engine:
             raise ValueError("lp_ranking ranks with the link-prediction engine (gmp_lp_rank): pass lp_engine (--lp-engine)")
+        if self.lp_heuristics and TASK_TYPES[self.domain_name] != "link_prediction":
+            raise ValueError(f"lp_heuristics applies to the link-prediction domains (Cora_LP / CiteSeer_LP), not to {self.domain_name}")
         self.exp_name = f"{self.domain_name}_{self.finetune_strategy}_{self.pretrained_scheme}"
         self.task_type = TASK_TYPES[self.domain_name]
         self.batch_size = BATCH_SIZES[self.domain_name]
@@ -415,6 +418,23 @@ def rank_test_edges(engine, train_loader, val_loader, test_loader, device) -> Di
     return {f"test/{k}": v for k, v in ranking_metrics(ranks).items()}
 
 
+def rank_test_edges_heuristics(train_loader, val_loader, test_loader, device) -> Dict[str, float]:
+    """cfg.lp_heuristics: rank_test_edges with the four neighbourhood baselines (link_heuristics.KINDS) in place of the trained scorer.
+    They see the message-passing graph alone -- the train split's positive edges; validation and test edges enter the filter only.
+    Reads the datasets and nothing else: no model, no generator, no dropout counter, no BatchNorm state."""
+    from . import link_heuristics as LH
+    data = train_loader.dataset
+    graph = data.train_edges.to(device).contiguous()
+    pos = test_loader.dataset.pos_edges.to(device).contiguous()
+    known = torch.cat([data.train_edges, val_loader.dataset.pos_edges, test_loader.dataset.pos_edges], dim=1).to(device)
+    known = torch.cat([known, known.flip(0)], dim=1).contiguous()
+    out = {}
+    for kind in LH.KINDS:
+        ranks = LH.heuristic_ranks(graph, data.data.num_nodes, pos, kind, filter_edges=known).rank
+        out.update({f"test/{kind}_{k}": v for k, v in ranking_metrics(ranks).items()})
+    return out
+
+
 def probe_embeddings(engine, datasets, device, cfg: FinetuneConfig):
     """What the probes score: per dataset (a split) its rows of the engine's eval-mode backbone output as the parameters stand now and
     their labels, both on the device -- node embeddings for node classification (one embed(), every split's rows gathered from it),
@@ -560,6 +580,8 @@ def finetune(cfg: FinetuneConfig, epochs: Optional[int] = None, device: Optional
     test.update(run_probes(probe_engine, train_loader, test_loader, dev, cfg, "test"))
     if cfg.lp_ranking:
         test.update(rank_test_edges(lp_engine, train_loader, val_loader, test_loader, dev))
+    if cfg.lp_heuristics:
+        test.update(rank_test_edges_heuristics(train_loader, val_loader, test_loader, dev))
     logger.log(test, global_step[0])
     print(f"{cfg.exp_name}: best {key} {best:.4f}, test/accuracy {test['test/accuracy']:.4f}, test/auc {test['test/auc']:.4f}, "
           f"training_time {test['test/training_time']:.2f}s, saved {path}")
@@ -582,6 +604,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--gc-engine", action="store_true", help="ENZYMES / PTC_MR: the explicit-kernel fine-tune step (GraphClassificationEngine)")
     p.add_argument("--engine-eval", action="store_true", help="validation / test through the active engine's predict (needs the node engine, --lp-engine or --gc-engine)")
     p.add_argument("--lp-ranking", action="store_true", help="with --lp-engine: the test pass also logs test/mrr and test/hits@K (true test edges ranked against all nodes, known positives filtered)")
+    p.add_argument("--lp-heuristics", action="store_true", help="Cora_LP / CiteSeer_LP: the test record also carries test/{cn,jaccard,aa,ra}_mrr and _hits@K, the common-neighbour, Jaccard, Adamic-Adar and resource-allocation baselines ranked like --lp-ranking on the training graph (needs neither --lp-engine nor --lp-ranking)")
     p.add_argument("--device-metrics", action="store_true", help="batch scores (accuracy, F1, precision, recall, AUC) from integer counts made on the GPU instead of scikit-learn on host copies; same values")
     p.add_argument("--miner", choices=list(ops.MINER_IMPLS), default="matrix",
                    help="Cora_LP / CiteSeer_LP: the hard-negative miner's top-k kernel: matrix (n x n similarity in the workspace, n <= 65535), "
@@ -599,7 +622,8 @@ def config_from_args(a: argparse.Namespace) -> FinetuneConfig:
                           lp_engine=getattr(a, "lp_engine", False), gc_engine=getattr(a, "gc_engine", False),
                           engine_eval=getattr(a, "engine_eval", False), lp_ranking=getattr(a, "lp_ranking", False),
                           device_metrics=getattr(a, "device_metrics", False), miner_impl=getattr(a, "miner", "matrix"),
-                          repr_stats=getattr(a, "repr_stats", False), **{p.field: getattr(a, p.field, 0) for p in PROBES})
+                          repr_stats=getattr(a, "repr_stats", False), lp_heuristics=getattr(a, "lp_heuristics", False),
+                          **{p.field: getattr(a, p.field, 0) for p in PROBES})
 
 
 def main() -> None:

@@ -1134,7 +1134,83 @@ def lp_topk(h: Tensor, src: Tensor, k: int, w0: Tensor, b0: Tensor, w3: Tensor, 
     return idx, logit
 
 
-KNN_MAX_K, KNN_MAX_DIM, KNN_MAX_CLASSES = 64, 256, 32       # gmp_knn_topk / gmp_knn_vote (gnnmp.h)
+LP_CN_MODES = {"sum": 0, "jaccard": 1}                      # gmp_lp_cn_score / gmp_lp_cn_rank (gnnmp.h)
+
+
+def _lp_cn_args(who: str, rowptr: Tensor, col: Tensor, weight: Optional[Tensor], mode: str) -> Tuple[int, int, int]:
+    """(num_nodes, nnz, mode code) of a simple-graph CSR and its scorer (gnnmp.h gmp_lp_cn_score)."""
+    _need(rowptr, torch.int32, "rowptr", 1); _need(col, torch.int32, "col", 1)
+    if rowptr.numel() < 1:
+        raise L.GnnmpError(f"{who}: rowptr is empty (it has num_nodes + 1 entries)")
+    if mode not in LP_CN_MODES:
+        raise L.GnnmpError(f"{who}: mode={mode!r} is not one of {tuple(LP_CN_MODES)}")
+    N = rowptr.numel() - 1
+    if weight is not None:
+        _need(weight, torch.float32, "weight", 1)
+        if mode == "jaccard":
+            raise L.GnnmpError(f"{who}: Jaccard takes no weight array")
+        if weight.numel() != N:
+            raise L.GnnmpError(f"{who}: weight has {weight.numel()} entries for {N} nodes")
+    return N, col.numel(), LP_CN_MODES[mode]
+
+
+def lp_cn_score(rowptr: Tensor, col: Tensor, src: Tensor, dst: Tensor, weight: Optional[Tensor] = None, mode: str = "sum") -> Tensor:
+    """The neighbourhood score of every pair (src[p], dst[p]) on the simple undirected graph (rowptr, col) (int32 CSR: symmetric, no
+    loops, rows strictly ascending; gnnmp.h gmp_lp_cn_score): mode "sum" the fp32 sum of weight[z] over the common neighbours z in
+    ascending z (weight None: 1, the common-neighbour count), mode "jaccard" CN / (deg s + deg d - CN).  A pair with an endpoint outside
+    the graph scores 0."""
+    N, nnz, code = _lp_cn_args("lp_cn_score", rowptr, col, weight, mode)
+    _need(src, torch.int64, "src", 1); _need(dst, torch.int64, "dst", 1)
+    P = src.numel()
+    if dst.numel() != P:
+        raise L.GnnmpError("lp_cn_score: src and dst differ in length")
+    score = torch.empty(P, device=rowptr.device)
+    L.check(L.lib().gmp_lp_cn_score(_ptr(rowptr), _ptr(col), N, nnz, _ptr(src), _ptr(dst), P, _ptr(weight), code, _ptr(score),
+                                    _stream(rowptr)), "gmp_lp_cn_score")
+    return score
+
+
+def lp_cn_rank(rowptr: Tensor, col: Tensor, src: Tensor, dst: Tensor, weight: Optional[Tensor] = None, mode: str = "sum",
+               filter_rowptr: Optional[Tensor] = None, filter_col: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
+    """Every true pair (src[q], dst[q]) ranked against all nodes with lp_cn_score's scorer (gnnmp.h gmp_lp_cn_rank): returns
+    (score_true [Q], n_greater [Q] int32, n_equal [Q] int32) over the candidates c other than src[q], dst[q] and the entries of
+    src[q]'s row of the optional filter CSR (lp_rank's).  A candidate's score has the bits lp_cn_score gives the pair; Jaccard is
+    compared exactly in integers.  Nothing of size Q x N is allocated."""
+    N, nnz, code = _lp_cn_args("lp_cn_rank", rowptr, col, weight, mode)
+    if (filter_rowptr is None) != (filter_col is None):
+        raise L.GnnmpError("lp_cn_rank: filter_rowptr and filter_col go together")
+    fnnz = 0
+    if filter_rowptr is not None:
+        _need(filter_rowptr, torch.int32, "filter_rowptr", 1); _need(filter_col, torch.int32, "filter_col", 1)
+        if filter_rowptr.numel() != N + 1:
+            raise L.GnnmpError(f"lp_cn_rank: filter_rowptr has {filter_rowptr.numel()} entries for {N} nodes")
+        fnnz = filter_col.numel()
+    _need(src, torch.int64, "src", 1); _need(dst, torch.int64, "dst", 1)
+    Q, dev, l = src.numel(), rowptr.device, L.lib()
+    if dst.numel() != Q:
+        raise L.GnnmpError("lp_cn_rank: src and dst differ in length")
+    score = torch.empty(Q, device=dev)
+    n_greater, n_equal = torch.empty(Q, dtype=torch.int32, device=dev), torch.empty(Q, dtype=torch.int32, device=dev)
+    ws = _ws(l.gmp_lp_cn_rank_workspace_bytes(Q, N), dev)
+    L.check(l.gmp_lp_cn_rank(_ptr(rowptr), _ptr(col), N, nnz, _ptr(src), _ptr(dst), Q, _ptr(weight), code, _ptr(filter_rowptr),
+                             _ptr(filter_col), fnnz, _ptr(score), _ptr(n_greater), _ptr(n_equal), _ptr(ws), ws.numel(), _stream(rowptr)),
+            "gmp_lp_cn_rank")
+    return score, n_greater, n_equal
+
+
+def graph_simple_check(rowptr: Tensor, col: Tensor) -> Tensor:
+    """int32 [1] on the device: how many entries of the int32 CSR (rowptr, col) keep it from being a simple undirected graph -- out of
+    range, a self-loop, not greater than the entry before it in the row, or without the mirror entry (gnnmp.h gmp_graph_simple_check)."""
+    _need(rowptr, torch.int32, "rowptr", 1); _need(col, torch.int32, "col", 1)
+    if rowptr.numel() < 1:
+        raise L.GnnmpError("graph_simple_check: rowptr is empty (it has num_nodes + 1 entries)")
+    violations = torch.empty(1, dtype=torch.int32, device=rowptr.device)
+    L.check(L.lib().gmp_graph_simple_check(_ptr(rowptr), _ptr(col), rowptr.numel() - 1, col.numel(), _ptr(violations), _stream(rowptr)),
+            "gmp_graph_simple_check")
+    return violations
+
+
+KNN_MAX_K, KNN_MAX_DIM, KNN_MAX_CLASSES = 64, 256, 32      # gmp_knn_topk / gmp_knn_vote (gnnmp.h)
 
 
 def knn_topk(queries: Tensor, database: Tensor, k: int, exclude_self: bool = False, return_matrix: bool = False):

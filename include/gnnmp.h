@@ -357,6 +357,42 @@ int gmp_lp_topk(const float* h, const int64_t* src, int64_t num_nodes, int64_t n
                 gmp_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
+ * Structural link-prediction baselines: common neighbours, Adamic-Adar, resource allocation and Jaccard on a simple undirected graph,
+ * scored for explicit pairs or ranked under gmp_lp_rank's protocol (csrc/lp_heuristics.hip).
+ * The graph is a CSR, rowptr int32 [num_nodes + 1] and col int32 [nnz]: symmetric, no self-loops, every row strictly ascending.
+ * gmp_graph_simple_check counts the entries that break this; on such a graph the two scorers give wrong numbers but read nothing outside
+ * the arrays (rowptr is clamped to [0, nnz], entries outside [0, num_nodes) are skipped).
+ * mode 0, the weighted sum: S_w(s, c) = the sum over z in N(s) & N(c) of weight[z], weight fp32 [num_nodes], NULL = 1.0f everywhere
+ *   (common neighbours: exact integers below 2^24).  fp32, started at 0.0f, one plain add per z in ASCENDING z -- part of the contract: a
+ *   score is bitwise reproducible, and the same pair has the same bits from gmp_lp_cn_score and as a candidate of gmp_lp_cn_rank.
+ *   Adamic-Adar is weight[z] = 1 / ln(deg z) for deg z >= 2 else 0, resource allocation 1 / deg z for deg z >= 1 else 0; the caller
+ *   computes them (the Python layer: float64 on the host, rounded once) -- the kernels see an array only.
+ * mode 1, Jaccard: CN / (deg s + deg c - CN), 0 for an empty union, deg from rowptr; weight must be NULL.  The float quotient is what
+ *   is written; ranking compares a / b with c / d exactly, as a d against c b in int64.
+ * gmp_lp_cn_score: score [num_pairs]; a pair with an endpoint outside [0, num_nodes) scores 0.
+ * gmp_lp_cn_rank, for Q true pairs (src[q], dst[q]): score_true [Q] (gmp_lp_cn_score's), and over the candidates c in [0, num_nodes)
+ *   except c == src[q], c == dst[q] and the entries of src[q]'s filter row (gmp_lp_rank's filter CSR: unsorted rows, duplicates and
+ *   out-of-range entries allowed; both NULL = none): n_greater [Q] and n_equal [Q], int32, the filtered rank being 1 + n_greater +
+ *   n_equal / 2.  Integer sums: independent of the block order.  No per-candidate score is written to memory and no workspace is needed
+ *   (gmp_lp_cn_rank_workspace_bytes is 0; workspace may be NULL).  Candidates are taken in tiles of gmp_lp_cn_tile_nodes().
+ * gmp_graph_simple_check: *violations (int32, zeroed inside the call) = the number of entries that lie outside [0, num_nodes), equal
+ *   their row, are not greater than their predecessor in the row, or lack the mirror entry, plus the rows whose rowptr bounds are not
+ *   0 <= rowptr[v] <= rowptr[v + 1] <= nnz, rowptr[0] == 0, rowptr[num_nodes] == nnz.
+ * GMP_ERR_ARG: num_nodes or nnz outside [0, 2^31), Q x tiles >= 2^31, a null pointer, mode outside {0, 1}, a weight array with mode 1.
+ * num_pairs == 0 / num_queries == 0 return GMP_OK without a launch.  Asynchronous on `stream`, no host read-back, no allocation.
+ * ------------------------------------------------------------------------- */
+int gmp_lp_cn_tile_nodes(void);
+size_t gmp_lp_cn_rank_workspace_bytes(int64_t num_queries, int64_t num_nodes);
+int gmp_lp_cn_score(const int32_t* rowptr, const int32_t* col, int64_t num_nodes, int64_t nnz, const int64_t* src, const int64_t* dst,
+                    int64_t num_pairs, const float* weight, int mode, float* score, gmp_stream_t stream);
+int gmp_lp_cn_rank(const int32_t* rowptr, const int32_t* col, int64_t num_nodes, int64_t nnz, const int64_t* src, const int64_t* dst,
+                   int64_t num_queries, const float* weight, int mode, const int32_t* filter_rowptr, const int32_t* filter_col,
+                   int64_t filter_nnz, float* score_true, int32_t* n_greater, int32_t* n_equal, void* workspace, size_t workspace_bytes,
+                   gmp_stream_t stream);
+int gmp_graph_simple_check(const int32_t* rowptr, const int32_t* col, int64_t num_nodes, int64_t nnz, int32_t* violations,
+                           gmp_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
  * Streaming k-nearest neighbours in cosine similarity and the weighted k-NN vote on top of them (the k-NN probe of Wu et al. 2018 for
  * self-supervised embeddings): q [nq, dim] queries against db [ndb, dim] database rows, both contiguous fp32.  Rows are normalised as the
  * hard-negative miner does, z / max(||z||, 1e-12) with the stride padded with zeros, so a zero row scores 0 against everything and never
