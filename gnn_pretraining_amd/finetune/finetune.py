@@ -3,7 +3,8 @@ miner, process_batch per task type, one AdamW step per batch over FinetuneGNN.pa
 test metrics from the best checkpoint.  Data come from the loaders of gnn_pretraining_amd/data (processed datasets in
 data/processed; synthetic stand-ins are generated when none were exported).  wandb is replaced by a JSONL logger with the
 same metric keys.  Build-only flags: --epochs, --device, --data-root, --data-scale, --log, --sparse-features, --lp-engine, --gc-engine,
---engine-eval, --lp-ranking, --device-metrics, --miner, --knn-probe, --cluster-probe, --logreg-probe, --repr-stats."""
+--engine-eval, --lp-ranking, --device-metrics, --miner, --knn-probe, --cluster-probe, --logreg-probe, --repr-stats, --lp-heuristics,
+--wl-baseline."""
 from __future__ import annotations
 
 import argparse
@@ -153,6 +154,7 @@ class FinetuneConfig:
     logreg_probe: int = 0               # classification domains on an engine: Adam iterations of the linear-evaluation probe (softmax regression fitted on the train split's embeddings: val/ and test/logreg_accuracy); 0 = off
     lp_heuristics: bool = False         # link-prediction domains: the test record also carries test/{cn,jaccard,aa,ra}_mrr / _hits@K, the neighbourhood baselines ranked like lp_ranking on the message-passing graph (link_heuristics.py); needs no engine
     repr_stats: bool = False            # on an engine: the label-free statistics of the validation embeddings (repr_stats.embedding_stats: val/repr_uniformity, val/repr_mean_cosine, val/repr_rankme); every domain, link prediction included
+    wl_baseline: int = 0                # graph-classification domains: rounds of the Weisfeiler-Lehman subtree baseline on the raw graphs (graph_baselines.py: test/wl_knn_accuracy, test/wl_logreg_accuracy); needs no engine and no probe; 0 = off
 
     def __post_init__(self) -> None:
         if self.sparse_features and TASK_TYPES[self.domain_name] == "graph_classification":
@@ -189,6 +191,10 @@ class FinetuneConfig:
             raise ValueError("lp_ranking ranks with the link-prediction engine (gmp_lp_rank): pass lp_engine (--lp-engine)")
         if self.lp_heuristics and TASK_TYPES[self.domain_name] != "link_prediction":
             raise ValueError(f"lp_heuristics applies to the link-prediction domains (Cora_LP / CiteSeer_LP), not to {self.domain_name}")
+        if not 0 <= self.wl_baseline <= ops.WL_MAX_ITERS:
+            raise ValueError(f"wl_baseline={self.wl_baseline} (the number of refinement rounds, 1 <= rounds <= {ops.WL_MAX_ITERS}; 0 switches the baseline off)")
+        if self.wl_baseline and TASK_TYPES[self.domain_name] != "graph_classification":
+            raise ValueError(f"wl_baseline applies to the graph-classification domains (ENZYMES / PTC_MR), not to {self.domain_name}")
         self.exp_name = f"{self.domain_name}_{self.finetune_strategy}_{self.pretrained_scheme}"
         self.task_type = TASK_TYPES[self.domain_name]
         self.batch_size = BATCH_SIZES[self.domain_name]
@@ -435,6 +441,16 @@ def rank_test_edges_heuristics(train_loader, val_loader, test_loader, device) ->
     return out
 
 
+def wl_baseline_keys(train_loader, test_loader, device, cfg: FinetuneConfig) -> Dict[str, float]:
+    """cfg.wl_baseline: what test/accuracy and the probes have to beat on a graph-classification domain -- the Weisfeiler-Lehman subtree
+    features of the raw graphs with cfg.wl_baseline rounds, fitted on the train split and scored on the test split by a k-NN vote on the
+    exact kernel and a softmax regression on the hashed histogram (graph_baselines.wl_baseline).  Reads the datasets and nothing else: no
+    model, no generator, no dropout counter, no BatchNorm state."""
+    from . import graph_baselines as GB
+    scores = GB.wl_baseline(train_loader.dataset, test_loader.dataset, NUM_CLASSES[cfg.domain_name], cfg.wl_baseline, device=device)
+    return {f"test/wl_{k}": v for k, v in scores.items()}
+
+
 def probe_embeddings(engine, datasets, device, cfg: FinetuneConfig):
     """What the probes score: per dataset (a split) its rows of the engine's eval-mode backbone output as the parameters stand now and
     their labels, both on the device -- node embeddings for node classification (one embed(), every split's rows gathered from it),
@@ -582,6 +598,8 @@ def finetune(cfg: FinetuneConfig, epochs: Optional[int] = None, device: Optional
         test.update(rank_test_edges(lp_engine, train_loader, val_loader, test_loader, dev))
     if cfg.lp_heuristics:
         test.update(rank_test_edges_heuristics(train_loader, val_loader, test_loader, dev))
+    if cfg.wl_baseline:
+        test.update(wl_baseline_keys(train_loader, test_loader, dev, cfg))
     logger.log(test, global_step[0])
     print(f"{cfg.exp_name}: best {key} {best:.4f}, test/accuracy {test['test/accuracy']:.4f}, test/auc {test['test/auc']:.4f}, "
           f"training_time {test['test/training_time']:.2f}s, saved {path}")
@@ -609,6 +627,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--miner", choices=list(ops.MINER_IMPLS), default="matrix",
                    help="Cora_LP / CiteSeer_LP: the hard-negative miner's top-k kernel: matrix (n x n similarity in the workspace, n <= 65535), "
                         "stream (tiles recomputed, workspace O(n d + E), n <= 2^20), auto (stream beyond 65535 nodes)")
+    p.add_argument("--wl-baseline", type=int, default=0, metavar="H",
+                   help="ENZYMES / PTC_MR: the test record also carries test/wl_knn_accuracy and test/wl_logreg_accuracy, the Weisfeiler-Lehman "
+                        "subtree baseline with H refinement rounds (1..7) on the raw graphs, fitted on the train split and scored on the test "
+                        "split (needs neither --gc-engine nor a probe flag); 0 = off")
     for probe in PROBES:
         p.add_argument(probe.flag, type=int, default=0, metavar=probe.metavar, help=probe.help)
     p.add_argument("--repr-stats", action="store_true",
@@ -622,7 +644,7 @@ def config_from_args(a: argparse.Namespace) -> FinetuneConfig:
                           lp_engine=getattr(a, "lp_engine", False), gc_engine=getattr(a, "gc_engine", False),
                           engine_eval=getattr(a, "engine_eval", False), lp_ranking=getattr(a, "lp_ranking", False),
                           device_metrics=getattr(a, "device_metrics", False), miner_impl=getattr(a, "miner", "matrix"),
-                          repr_stats=getattr(a, "repr_stats", False), lp_heuristics=getattr(a, "lp_heuristics", False),
+                          repr_stats=getattr(a, "repr_stats", False), lp_heuristics=getattr(a, "lp_heuristics", False), wl_baseline=getattr(a, "wl_baseline", 0),
                           **{p.field: getattr(a, p.field, 0) for p in PROBES})
 
 

@@ -1,0 +1,119 @@
+"""The model-free baseline of graph classification: the Weisfeiler-Lehman subtree kernel (Shervashidze et al., JMLR 2011) on the raw graphs,
+refined, sorted and counted on the GPU (csrc/wl.hip; the definition is above gmp_wl_refine in include/gnnmp.h), with the pinned k-NN vote
+and softmax regression of the embedding probes on top.  A GIN is bounded by the 1-WL test, so this is what the backbone's probes have to
+beat.  It reads the datasets only: no model, no generator, no dropout counter, no BatchNorm state.
+
+    initial_labels(x)                                 the discrete node labels behind one-hot features, None for continuous ones
+    wl_features(batch, iters, dim=256, labels="auto") WLFeatures of one collated Batch: the exact (sorted) and the hashed (hist) feature map
+    wl_kernel(feat_a, feat_b)                         the int64 Gram of the subtree kernel between two WLFeatures
+    normalised_similarity(K_et, K_ee, K_tt)           K / sqrt(K_ee K_tt) in fp64
+    wl_neighbours(sim, k)                             the k most similar columns per row, ties to the lower index
+    wl_baseline(train_ds, eval_ds, num_classes, iters, k=20, device="cuda")    {"knn_accuracy", "logreg_accuracy"}
+"""
+from __future__ import annotations
+
+from typing import Dict, NamedTuple, Optional, Tuple, Union
+
+import torch
+from torch import Tensor
+
+from .. import ops
+from .._lib import GnnmpError
+from .link_heuristics import simple_graph
+
+
+class WLFeatures(NamedTuple):
+    sorted: Tensor                 # int64 [(iters + 1) * N]: per graph, all its colours in ascending unsigned order
+    hist: Tensor                   # int32 [G, dim]
+    ptr: Tensor                    # int64 [G + 1]
+    iters: int
+
+
+def initial_labels(x: Tensor) -> Optional[Tensor]:
+    """The int64 argmax per row when every row of x [N, F] is one-hot -- exactly one non-zero entry and it equals 1 (MUTAG, NCI1, PTC_MR)
+    -- and None otherwise: on the standardised continuous features of ENZYMES and PROTEINS the refinement then starts from the node
+    degrees, the usual start for graphs without discrete labels."""
+    if x.dim() != 2 or x.size(1) == 0:
+        return None
+    nz = x != 0
+    if not bool(((nz.sum(dim=1) == 1) & ((x == 1).sum(dim=1) == 1)).all()):
+        return None
+    return nz.to(torch.int64).argmax(dim=1)
+
+
+def wl_features(batch, iters: int, dim: int = ops.WL_MAX_DIM, labels: Union[str, None, Tensor] = "auto") -> WLFeatures:
+    """`iters` rounds of WL refinement of one collated Batch on the GPU (ops.wl_refine on simple_graph(batch.edge_index)).  labels: "auto" =
+    initial_labels(batch.x), None = degrees, or an int64 [N] tensor.  Raises GnnmpError naming the first graph the kernel refuses (more
+    than ops.WL_MAX_GRAPH_NODES nodes), and when a CSR entry was skipped for leaving its graph (one read-back of the status words)."""
+    if not batch.x.is_cuda:
+        raise GnnmpError(f"wl_features: expected a batch on the GPU (the HIP path has no CPU fallback), got {batch.x.device}")
+    if isinstance(labels, str):
+        if labels != "auto":
+            raise ValueError(f"wl_features: labels={labels!r} (\"auto\", None or an int64 tensor)")
+        labels = initial_labels(batch.x)
+    rowptr, col = simple_graph(batch.edge_index.contiguous(), batch.num_nodes)
+    ptr = batch.ptr.to(torch.int64).contiguous()
+    out = ops.wl_refine(ptr, rowptr, col, None if labels is None else labels.to(torch.int64).contiguous(), iters, dim,
+                        max_graph_nodes=batch.max_graph_nodes)
+    status = out.status.cpu()
+    if bool((status & 1).any()):
+        g = int((status & 1).nonzero()[0])
+        raise GnnmpError(f"wl_features: graph {g} has {batch.ptr_host[g + 1] - batch.ptr_host[g]} nodes, more than the "
+                         f"{ops.WL_MAX_GRAPH_NODES} the kernel takes (there is no host fallback)")
+    if bool((status >> 8).any()):
+        g = int((status >> 8).nonzero()[0])
+        raise GnnmpError(f"wl_features: {int(status[g] >> 8)} adjacency entries of graph {g} point outside the graph and were skipped")
+    return WLFeatures(out.sorted, out.hist, ptr, int(iters))
+
+
+def wl_kernel(feat_a: WLFeatures, feat_b: WLFeatures) -> Tensor:
+    """K int64 [Ga, Gb]: the WL subtree kernel between the graphs of two refinements made with the same number of rounds."""
+    if feat_a.iters != feat_b.iters:
+        raise GnnmpError(f"wl_kernel: the two refinements ran {feat_a.iters} and {feat_b.iters} rounds")
+    return ops.wl_gram(feat_a.sorted, feat_a.ptr, feat_b.sorted, feat_b.ptr, feat_a.iters)
+
+
+def normalised_similarity(K_et: Tensor, K_ee: Tensor, K_tt: Tensor) -> Tensor:
+    """s [n_eval, n_train] = K_et / sqrt(K_ee[:, None] * K_tt[None, :]) in fp64 from the integer Gram and the two self-similarity vectors;
+    0 where a self-similarity is 0 (an empty graph)."""
+    den = torch.sqrt(K_ee.to(torch.float64)[:, None] * K_tt.to(torch.float64)[None, :])
+    ok = den > 0
+    return torch.where(ok, K_et.to(torch.float64) / torch.where(ok, den, torch.ones_like(den)), torch.zeros_like(den))
+
+
+def wl_neighbours(sim: Tensor, k: int) -> Tuple[Tensor, Tensor]:
+    """(idx int64 [n, k'], sim fp64 [n, k']), k' = min(k, columns): the most similar columns of every row by a stable descending sort,
+    so ties go to the lower index."""
+    val, idx = torch.sort(sim, dim=1, descending=True, stable=True)
+    kk = min(int(k), sim.size(1))
+    return idx[:, :kk].contiguous(), val[:, :kk].contiguous()
+
+
+def _collate(ds, device):
+    return ds.collate(torch.arange(len(ds))).to(device)
+
+
+def wl_baseline(train_ds, eval_ds, num_classes: int, iters: int, k: int = 20, device="cuda") -> Dict[str, float]:
+    """{"knn_accuracy", "logreg_accuracy"} of the WL subtree features with `iters` rounds, fitted on train_ds and scored on eval_ds (two
+    graph datasets with collate(); each split is collated into ONE batch, in dataset order).
+    knn: s = K[eval, train] / sqrt(K_ee K_tt) in fp64 (the self-similarities are the diagonals of the same Gram kernel, 0 where one is 0),
+    the min(k, n_train) nearest by a stable descending sort (ties to the lower train index), then s in fp32 through ops.knn_vote at its
+    default temperature.  The [n_eval, n_train] matrix IS the product here -- the kernel's Gram -- and is a few hundred squared on the TU
+    datasets: there is nothing to stream.
+    logreg: ops.logreg_fit on the train split's hashed histogram (as fp32, at its defaults: 100 iterations, lr 0.01), ops.logreg_predict
+    on the evaluation split's."""
+    if not 1 <= int(iters) <= ops.WL_MAX_ITERS:
+        raise ValueError(f"wl_baseline: iters={iters} (1 <= iters <= {ops.WL_MAX_ITERS})")
+    if not 1 <= int(k) <= ops.KNN_MAX_K:
+        raise ValueError(f"wl_baseline: k={k} (1 <= k <= {ops.KNN_MAX_K})")
+    if len(train_ds) == 0 or len(eval_ds) == 0:
+        raise ValueError(f"wl_baseline: {len(train_ds)} train and {len(eval_ds)} evaluation graphs (both splits need one)")
+    tb, eb = _collate(train_ds, device), _collate(eval_ds, device)
+    ft, fe = wl_features(tb, iters), wl_features(eb, iters)
+    y_train, y_eval = tb.y.to(torch.int64).contiguous(), eb.y.to(torch.int64).contiguous()
+    sim = normalised_similarity(wl_kernel(fe, ft), wl_kernel(fe, fe).diagonal(), wl_kernel(ft, ft).diagonal())
+    idx, val = wl_neighbours(sim, k)
+    _, knn_pred = ops.knn_vote(idx, val.to(torch.float32).contiguous(), y_train, num_classes)
+    fit = ops.logreg_fit(ft.hist.to(torch.float32).contiguous(), y_train, num_classes)
+    lr_pred = ops.logreg_predict(fe.hist.to(torch.float32).contiguous(), fit.state.weight, fit.state.bias)
+    return {"knn_accuracy": float((knn_pred == y_eval).float().mean()), "logreg_accuracy": float((lr_pred == y_eval).float().mean())}

@@ -1552,6 +1552,68 @@ def graph_properties(ptr: Tensor, eptr: Tensor, edge_index: Tensor, max_graph_no
     return counts, csum
 
 
+WL_MAX_ITERS, WL_MAX_DIM, WL_MAX_GRAPH_NODES = 7, 256, 1024       # gmp_wl_refine / gmp_wl_gram (gnnmp.h)
+
+
+class WLRefinement(NamedTuple):
+    """wl_refine's outputs (gnnmp.h gmp_wl_refine)."""
+    sorted: Tensor                 # int64 [(iters + 1) * N]: graph g's colours, ascending as unsigned words, at [(iters + 1) ptr[g], (iters + 1) ptr[g+1])
+    hist: Tensor                   # int32 [G, dim]: the hashed feature map
+    status: Tensor                 # int32 [G]: bit 0 = refused (too large), bits 8.. = skipped CSR entries
+    colors: Optional[Tensor] = None   # int64 [iters + 1, N], only with return_colors
+
+
+def wl_refine(ptr: Tensor, rowptr: Tensor, col: Tensor, labels: Optional[Tensor] = None, iters: int = 3, dim: int = 256,
+              max_graph_nodes: Optional[int] = None, return_colors: bool = False, fill: int = 0) -> WLRefinement:
+    """`iters` rounds of hashed Weisfeiler-Lehman colour refinement of a batch of graphs in one launch (gnnmp.h gmp_wl_refine holds the
+    definition; csrc/wl.hip): ptr int64 [G + 1] node offsets, (rowptr, col) the int32 CSR of the batch's simple undirected graph
+    (finetune.link_heuristics.simple_graph), labels int64 [N] or None (None: a node's degree inside its graph).  0 <= iters <= 7,
+    1 <= dim <= 256.  Returns WLRefinement(sorted, hist, status[, colors]); the outputs start as `fill`, which is what a refused graph
+    (status bit 0: more than min(max_graph_nodes, WL_MAX_GRAPH_NODES) nodes) keeps.  max_graph_nodes: the largest ptr[g + 1] - ptr[g]
+    when the caller knows it (None reads it back from ptr, one synchronisation).  No other read-back: status stays on the device."""
+    _need(ptr, torch.int64, "ptr", 1); _need(rowptr, torch.int32, "rowptr", 1); _need(col, torch.int32, "col", 1)
+    G, N, dev = ptr.numel() - 1, rowptr.numel() - 1, ptr.device
+    if G < 0 or N < 0:
+        raise L.GnnmpError(f"wl_refine: ptr {tuple(ptr.shape)}, rowptr {tuple(rowptr.shape)} (G + 1 and N + 1 entries)")
+    if rowptr.device != dev or col.device != dev:
+        raise L.GnnmpError("wl_refine: ptr, rowptr and col must be on one device")
+    if labels is not None:
+        _need(labels, torch.int64, "labels", 1)
+        if labels.numel() != N or labels.device != dev:
+            raise L.GnnmpError(f"wl_refine: labels has {labels.numel()} entries on {labels.device} for {N} nodes on {dev}")
+    if not 0 <= int(iters) <= WL_MAX_ITERS or not 1 <= int(dim) <= WL_MAX_DIM:
+        raise L.GnnmpError(f"wl_refine: iters={iters} dim={dim} (0 <= iters <= {WL_MAX_ITERS}, 1 <= dim <= {WL_MAX_DIM})")
+    iters, dim = int(iters), int(dim)
+    srt = torch.full(((iters + 1) * N,), fill, dtype=torch.int64, device=dev)
+    hist = torch.full((G, dim), fill, dtype=torch.int32, device=dev)
+    status = torch.zeros(G, dtype=torch.int32, device=dev)
+    colors = torch.full((iters + 1, N), fill, dtype=torch.int64, device=dev) if return_colors else None
+    if G:
+        if max_graph_nodes is None:
+            max_graph_nodes = max(int((ptr[1:] - ptr[:-1]).max()), 0)
+        L.check(L.lib().gmp_wl_refine(_ptr(ptr), G, _ptr(rowptr), _ptr(col), N, col.numel(), _ptr(labels), iters, dim, int(max_graph_nodes),
+                                      _ptr(colors), _ptr(srt), _ptr(hist), _ptr(status), None, 0, _stream(ptr)), "gmp_wl_refine")
+    return WLRefinement(srt, hist, status, colors)
+
+
+def wl_gram(sorted_a: Tensor, ptr_a: Tensor, sorted_b: Tensor, ptr_b: Tensor, iters: int) -> Tensor:
+    """K int64 [Ga, Gb], the Weisfeiler-Lehman subtree kernel between two batches refined by wl_refine with the same `iters` (gnnmp.h
+    gmp_wl_gram): K[i, j] = the number of pairs of equal colours between graph i's segment of sorted_a and graph j's segment of
+    sorted_b (the two may be the same tensors).  Exact integers."""
+    _need(sorted_a, torch.int64, "sorted_a", 1); _need(ptr_a, torch.int64, "ptr_a", 1)
+    _need(sorted_b, torch.int64, "sorted_b", 1); _need(ptr_b, torch.int64, "ptr_b", 1)
+    dev = sorted_a.device
+    if ptr_a.device != dev or sorted_b.device != dev or ptr_b.device != dev:
+        raise L.GnnmpError("wl_gram: the four inputs must be on one device")
+    if not 0 <= int(iters) <= WL_MAX_ITERS or ptr_a.numel() < 1 or ptr_b.numel() < 1:
+        raise L.GnnmpError(f"wl_gram: iters={iters} (0 <= iters <= {WL_MAX_ITERS}), ptr_a {tuple(ptr_a.shape)}, ptr_b {tuple(ptr_b.shape)}")
+    Ga, Gb = ptr_a.numel() - 1, ptr_b.numel() - 1
+    K = torch.zeros(Ga, Gb, dtype=torch.int64, device=dev)
+    L.check(L.lib().gmp_wl_gram(_ptr(sorted_a), _ptr(ptr_a), Ga, sorted_a.numel(), _ptr(sorted_b), _ptr(ptr_b), Gb, sorted_b.numel(),
+                                int(iters), _ptr(K), _stream(sorted_a)), "gmp_wl_gram")
+    return K
+
+
 def gc_head_fwd(h: Tensor, ptr: Tensor, w0: Tensor, b0: Tensor, w3: Tensor, b3: Tensor, target: Tensor, g_scale: Tensor, p: float = 0.0,
                 seed: int = 0, site: int = 0) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
     """The fused graph-classification head up to the loss (gnnmp.h gmp_gc_head_fwd): h [N, 256] (rows contiguous, any leading dimension),

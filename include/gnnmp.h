@@ -579,6 +579,47 @@ int gmp_graph_props(const int64_t* ptr, const int64_t* eptr, const int64_t* edge
                     void* workspace, size_t workspace_bytes, gmp_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
+ * The Weisfeiler-Lehman subtree baseline of graph classification (Shervashidze et al., JMLR 2011; csrc/wl.hip): hashed colour refinement
+ * of a batch of graphs, one workgroup per graph, and the exact subtree kernel between two refined batches.  Integer arithmetic only.
+ * All arithmetic is on unsigned 64-bit words modulo 2^64.  mix is the splitmix64 finaliser,
+ *   z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31,
+ * and K1 = 0x9E3779B97F4A7C15, K2 = 0xD1B54A32D192ED03.
+ * The batch: ptr int64 [num_graphs + 1] node offsets (as for gmp_graph_props), a simple undirected CSR over the batch's nodes, rowptr int32
+ * [num_nodes + 1] and col int32 [nnz] under the contract of gmp_lp_cn_score / gmp_graph_simple_check (rowptr is clamped to [0, nnz]),
+ * and labels int64 [num_nodes] or NULL: with NULL a node's label is its degree in the CSR counted inside its own graph.  An entry of col
+ * outside its row's own graph [ptr[g], ptr[g+1]) is skipped, never dereferenced, and counted in the graph's status word.
+ *   c_0[v]     = mix(label[v] + K1)
+ *   c_{t+1}[v] = mix(c_t[v] * K1 + (the sum over u in N(v) of mix(c_t[u])) + (t + 1) * K2),   t = 0 .. iters - 1.
+ * The neighbour sum is commutative and exact, so the result does not depend on neighbour order, node numbering or scheduling.
+ * gmp_wl_refine writes, for 0 <= iters <= 7 and 1 <= dim <= 256:
+ *   colors int64 [iters + 1, num_nodes]  the colour bits c_t[v] (optional, NULL to skip: a diagnostic and test hook);
+ *   sorted int64 [(iters + 1) * num_nodes]  graph g owns [(iters + 1) ptr[g], (iters + 1) ptr[g+1]): all its (iters + 1) n_g colours in
+ *     ascending UNSIGNED order -- the exact feature map in sparse form;
+ *   hist int32 [num_graphs, dim]  hist[g, b] = the number of (node, iteration) colours c of g with b = (uint32(c >> 32) * dim) >> 32 --
+ *     the hashed feature map;
+ *   status int32 [num_graphs]  bit 0 = the graph is refused: n_g > min(max_graph_nodes, 1024), ptr decreasing, or its node range leaves
+ *     [0, num_nodes]; bits 8.. = the number of skipped entries (saturating at 2^23 - 1).  A graph with bit 0 set gets ONLY its status
+ *     written: its parts of colors, sorted and hist keep what the caller left there.
+ * n_g = 0 and 1 are valid.  max_graph_nodes is the caller's bound on ptr[g+1] - ptr[g]; it selects the launch (n <= 256: 256 threads, at
+ * most 21 KiB of LDS; n <= 1024: 1024 threads, at most 81 KiB) and sizes the LDS.  No workspace (gmp_wl_workspace_bytes is 0; workspace may
+ * be NULL).
+ * gmp_wl_gram: K int64 [num_graphs_a, num_graphs_b], K[i, j] = the number of pairs (x in segment i of sorted_a, y in segment j of
+ * sorted_b) with x == y -- the WL subtree kernel, the sum over iterations and colours of count_i * count_j -- between two `sorted` arrays
+ * of gmp_wl_refine made with the same iters (they may be the same array); len_a / len_b = the int64 words in each array, to which the
+ * segments are clamped.  One wave per entry, equal runs counted by binary searches, int64 products, no atomics.  On unsorted input the
+ * result is wrong, but nothing outside the arrays is read.
+ * Both: asynchronous on `stream`, no allocation, no global state, no host read-back.  GMP_ERR_ARG before any launch on a null pointer
+ * (labels and colors may be NULL), iters outside [0, 7], dim outside [1, 256], a negative size, num_nodes or nnz >= 2^31, or a Gram of
+ * more than 2^33 entries.  num_graphs == 0, num_graphs_a == 0 and num_graphs_b == 0 are no-ops.
+ * ------------------------------------------------------------------------- */
+size_t gmp_wl_workspace_bytes(int num_graphs, int64_t max_graph_nodes, int iters);
+int gmp_wl_refine(const int64_t* ptr, int num_graphs, const int32_t* rowptr, const int32_t* col, int64_t num_nodes, int64_t nnz,
+                  const int64_t* labels, int iters, int dim, int64_t max_graph_nodes, int64_t* colors, int64_t* sorted, int32_t* hist,
+                  int32_t* status, void* workspace, size_t workspace_bytes, gmp_stream_t stream);
+int gmp_wl_gram(const int64_t* sorted_a, const int64_t* ptr_a, int64_t num_graphs_a, int64_t len_a, const int64_t* sorted_b,
+                const int64_t* ptr_b, int64_t num_graphs_b, int64_t len_b, int iters, int64_t* K, gmp_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
  * The fused graph-classification head of fine-tuning (finetune_model.py:68-80, finetune.py:110-114) over one batch of
  * num_graphs graphs; graph b owns the rows ptr[b] .. ptr[b+1] of h (ptr: device int32 [num_graphs + 1]):
  *   pooled[b] = mean of the graph's rows, divisor max(count, 1) (gmp_segment_sum(mean = 1); an empty graph pools to zero),
