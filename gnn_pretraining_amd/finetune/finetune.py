@@ -4,7 +4,7 @@ test metrics from the best checkpoint.  Data come from the loaders of gnn_pretra
 data/processed; synthetic stand-ins are generated when none were exported).  wandb is replaced by a JSONL logger with the
 same metric keys.  Build-only flags: --epochs, --device, --data-root, --data-scale, --log, --sparse-features, --lp-engine, --gc-engine,
 --engine-eval, --lp-ranking, --device-metrics, --miner, --knn-probe, --cluster-probe, --logreg-probe, --repr-stats, --lp-heuristics,
---wl-baseline."""
+--wl-baseline, --label-propagation."""
 from __future__ import annotations
 
 import argparse
@@ -154,6 +154,7 @@ class FinetuneConfig:
     logreg_probe: int = 0               # classification domains on an engine: Adam iterations of the linear-evaluation probe (softmax regression fitted on the train split's embeddings: val/ and test/logreg_accuracy); 0 = off
     lp_heuristics: bool = False         # link-prediction domains: the test record also carries test/{cn,jaccard,aa,ra}_mrr / _hits@K, the neighbourhood baselines ranked like lp_ranking on the message-passing graph (link_heuristics.py); needs no engine
     repr_stats: bool = False            # on an engine: the label-free statistics of the validation embeddings (repr_stats.embedding_stats: val/repr_uniformity, val/repr_mean_cosine, val/repr_rankme); every domain, link prediction included
+    label_propagation: int = 0          # node-classification domains: rounds of the label-spreading and label-propagation baselines on the raw graph (node_baselines.py: test/labelspread_accuracy, test/labelprop_accuracy and their _unreached counts); needs no engine and no probe; 0 = off
     wl_baseline: int = 0                # graph-classification domains: rounds of the Weisfeiler-Lehman subtree baseline on the raw graphs (graph_baselines.py: test/wl_knn_accuracy, test/wl_logreg_accuracy); needs no engine and no probe; 0 = off
 
     def __post_init__(self) -> None:
@@ -195,6 +196,10 @@ class FinetuneConfig:
             raise ValueError(f"wl_baseline={self.wl_baseline} (the number of refinement rounds, 1 <= rounds <= {ops.WL_MAX_ITERS}; 0 switches the baseline off)")
         if self.wl_baseline and TASK_TYPES[self.domain_name] != "graph_classification":
             raise ValueError(f"wl_baseline applies to the graph-classification domains (ENZYMES / PTC_MR), not to {self.domain_name}")
+        if not 0 <= self.label_propagation <= ops.LABELPROP_MAX_ROUNDS:
+            raise ValueError(f"label_propagation={self.label_propagation} (the number of propagation rounds, 1 <= rounds <= {ops.LABELPROP_MAX_ROUNDS}; 0 switches the baselines off)")
+        if self.label_propagation and TASK_TYPES[self.domain_name] != "node_classification":
+            raise ValueError(f"label_propagation applies to the node-classification domains (Cora_NC / CiteSeer_NC), not to {self.domain_name}")
         self.exp_name = f"{self.domain_name}_{self.finetune_strategy}_{self.pretrained_scheme}"
         self.task_type = TASK_TYPES[self.domain_name]
         self.batch_size = BATCH_SIZES[self.domain_name]
@@ -451,6 +456,16 @@ def wl_baseline_keys(train_loader, test_loader, device, cfg: FinetuneConfig) -> 
     return {f"test/wl_{k}": v for k, v in scores.items()}
 
 
+def label_baseline_keys(train_loader, test_loader, device, cfg: FinetuneConfig) -> Dict[str, float]:
+    """cfg.label_propagation: what test/accuracy has to beat on a node-classification domain -- label spreading and label propagation with
+    cfg.label_propagation rounds over the whole raw graph, seeded with the train split's labels and scored on the test split
+    (node_baselines.label_baselines).  Reads the datasets and nothing else: no model, no generator, no dropout counter, no BatchNorm state."""
+    from . import node_baselines as NB
+    train, test = train_loader.dataset, test_loader.dataset
+    scores = NB.label_baselines(train.data, train.indices, test.indices, NUM_CLASSES[cfg.domain_name], cfg.label_propagation, device=device)
+    return {f"test/{k}": v for k, v in scores.items()}
+
+
 def probe_embeddings(engine, datasets, device, cfg: FinetuneConfig):
     """What the probes score: per dataset (a split) its rows of the engine's eval-mode backbone output as the parameters stand now and
     their labels, both on the device -- node embeddings for node classification (one embed(), every split's rows gathered from it),
@@ -600,6 +615,8 @@ def finetune(cfg: FinetuneConfig, epochs: Optional[int] = None, device: Optional
         test.update(rank_test_edges_heuristics(train_loader, val_loader, test_loader, dev))
     if cfg.wl_baseline:
         test.update(wl_baseline_keys(train_loader, test_loader, dev, cfg))
+    if cfg.label_propagation:
+        test.update(label_baseline_keys(train_loader, test_loader, dev, cfg))
     logger.log(test, global_step[0])
     print(f"{cfg.exp_name}: best {key} {best:.4f}, test/accuracy {test['test/accuracy']:.4f}, test/auc {test['test/auc']:.4f}, "
           f"training_time {test['test/training_time']:.2f}s, saved {path}")
@@ -631,6 +648,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help="ENZYMES / PTC_MR: the test record also carries test/wl_knn_accuracy and test/wl_logreg_accuracy, the Weisfeiler-Lehman "
                         "subtree baseline with H refinement rounds (1..7) on the raw graphs, fitted on the train split and scored on the test "
                         "split (needs neither --gc-engine nor a probe flag); 0 = off")
+    p.add_argument("--label-propagation", type=int, default=0, metavar="T",
+                   help="Cora_NC / CiteSeer_NC: the test record also carries test/labelspread_accuracy, test/labelprop_accuracy and their "
+                        "_unreached counts, label spreading (alpha 0.9) and label propagation with T rounds (1..10000) over the raw graph, "
+                        "seeded with the train split's labels and scored on the test split (needs neither an engine nor a probe flag); 0 = off")
     for probe in PROBES:
         p.add_argument(probe.flag, type=int, default=0, metavar=probe.metavar, help=probe.help)
     p.add_argument("--repr-stats", action="store_true",
@@ -645,6 +666,7 @@ def config_from_args(a: argparse.Namespace) -> FinetuneConfig:
                           engine_eval=getattr(a, "engine_eval", False), lp_ranking=getattr(a, "lp_ranking", False),
                           device_metrics=getattr(a, "device_metrics", False), miner_impl=getattr(a, "miner", "matrix"),
                           repr_stats=getattr(a, "repr_stats", False), lp_heuristics=getattr(a, "lp_heuristics", False), wl_baseline=getattr(a, "wl_baseline", 0),
+                          label_propagation=getattr(a, "label_propagation", 0),
                           **{p.field: getattr(a, p.field, 0) for p in PROBES})
 
 

@@ -1614,6 +1614,56 @@ def wl_gram(sorted_a: Tensor, ptr_a: Tensor, sorted_b: Tensor, ptr_b: Tensor, it
     return K
 
 
+LABELPROP_MAX_CLASSES, LABELPROP_MAX_ROUNDS = 32, 10000            # gmp_label_propagate (gnnmp.h)
+
+
+class LabelPropagation(NamedTuple):
+    """label_propagate's outputs (gnnmp.h gmp_label_propagate)."""
+    out: Tensor                    # fp32 [n, classes]: F after the last round
+    pred: Tensor                   # int64 [n]: the argmax of each row of out, ties to the lower class
+    status: Tensor                 # int32 [2]: CSR entries outside [0, n) (skipped), rows of out whose maximum is not > 0
+    residual: Optional[Tensor] = None   # fp32 [rounds]: max |F(t+1) - F(t)| per round, only with return_residual
+
+
+def label_propagate(rowptr: Tensor, col: Tensor, f0: Tensor, rounds: int, alpha: float, beta: float, left: Optional[Tensor] = None,
+                    right: Optional[Tensor] = None, clamp: Optional[Tensor] = None, f_init: Optional[Tensor] = None,
+                    return_residual: bool = False) -> LabelPropagation:
+    """`rounds` rounds of F <- alpha * left[i] * (sum over the row's entries j, in order, of right[j] * F[j]) + beta * f0, rows with
+    clamp[i] != 0 put back to f0, started from f_init (None: f0), one launch per round and no host synchronisation (gnnmp.h
+    gmp_label_propagate holds the definition; csrc/label_prop.hip).  (rowptr, col) an int32 CSR over n nodes, f0 / f_init fp32
+    [n, classes] with 1 <= classes <= 32, left / right fp32 [n] or None (ones), clamp uint8 [n] or None.  Every multiply and add is
+    rounded on its own in a fixed order: the bits are reproducible, and `rounds` rounds equal `rounds` chained calls of one.  Returns
+    LabelPropagation(out, pred, status[, residual]); status stays on the device."""
+    _need(rowptr, torch.int32, "rowptr", 1); _need(col, torch.int32, "col", 1); _need(f0, torch.float32, "f0", 2)
+    n, classes, dev = rowptr.numel() - 1, f0.size(1), rowptr.device
+    if n < 0 or f0.size(0) != n:
+        raise L.GnnmpError(f"label_propagate: rowptr has {rowptr.numel()} entries for the {f0.size(0)} rows of f0 (n + 1 entries)")
+    if not 1 <= classes <= LABELPROP_MAX_CLASSES or not 1 <= int(rounds) <= LABELPROP_MAX_ROUNDS:
+        raise L.GnnmpError(f"label_propagate: classes={classes} rounds={rounds} (1 <= classes <= {LABELPROP_MAX_CLASSES}, "
+                           f"1 <= rounds <= {LABELPROP_MAX_ROUNDS})")
+    for t, name, dtype in ((left, "left", torch.float32), (right, "right", torch.float32), (clamp, "clamp", torch.uint8)):
+        if t is not None:
+            _need(t, dtype, name, 1)
+            if t.numel() != n:
+                raise L.GnnmpError(f"label_propagate: {name} has {t.numel()} entries for {n} nodes")
+    if f_init is not None:
+        _need(f_init, torch.float32, "f_init", 2)
+        if f_init.shape != f0.shape:
+            raise L.GnnmpError(f"label_propagate: f_init {tuple(f_init.shape)} against f0 {tuple(f0.shape)}")
+    if any(t is not None and t.device != dev for t in (col, f0, left, right, clamp, f_init)):
+        raise L.GnnmpError("label_propagate: every input must be on one device")
+    rounds, l = int(rounds), L.lib()
+    out = torch.empty(n, classes, device=dev)
+    pred = torch.empty(n, dtype=torch.int64, device=dev)
+    status = torch.zeros(2, dtype=torch.int32, device=dev)
+    residual = torch.empty(rounds, device=dev) if return_residual else None
+    ws = _ws(l.gmp_label_propagate_workspace_bytes(n, classes), dev)
+    L.check(l.gmp_label_propagate(_ptr(rowptr), _ptr(col), n, col.numel(), _ptr(left), _ptr(right), _ptr(f0), _ptr(f_init), _ptr(clamp), classes,
+                                  rounds, float(alpha), float(beta), _ptr(out), _ptr(pred), _ptr(residual), _ptr(status), _ptr(ws), ws.numel(),
+                                  _stream(rowptr)), "gmp_label_propagate")
+    return LabelPropagation(out, pred, status, residual)
+
+
 def gc_head_fwd(h: Tensor, ptr: Tensor, w0: Tensor, b0: Tensor, w3: Tensor, b3: Tensor, target: Tensor, g_scale: Tensor, p: float = 0.0,
                 seed: int = 0, site: int = 0) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
     """The fused graph-classification head up to the loss (gnnmp.h gmp_gc_head_fwd): h [N, 256] (rows contiguous, any leading dimension),

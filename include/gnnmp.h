@@ -620,6 +620,38 @@ int gmp_wl_gram(const int64_t* sorted_a, const int64_t* ptr_a, int64_t num_graph
                 const int64_t* ptr_b, int64_t num_graphs_b, int64_t len_b, int iters, int64_t* K, gmp_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
+ * Degree-normalised propagation of a narrow matrix over a graph, iterated with a teleport term (csrc/label_prop.hip): label spreading
+ * (Zhou et al. 2004), label propagation (Zhu & Ghahramani 2002), and the smoothing step of APPNP and Correct-and-Smooth.
+ * The graph is a CSR, rowptr int32 [n + 1] and col int32 [nnz]; left and right are fp32 [n] scales, NULL = all ones; f0 and f_init are
+ * contiguous fp32 [n, classes], f_init NULL = f0; clamp is uint8 [n] or NULL.  All arithmetic is IEEE fp32, every multiply and every add
+ * rounded on its own (no fused multiply-add), subnormals kept.  F(0) = f_init.  For round t = 0 .. rounds - 1, row i, class c:
+ *   acc = 0;  for k = rowptr[i] .. rowptr[i+1] - 1, ASCENDING:  j = col[k];  acc = acc + (right[j] * F(t)[j, c])
+ *   v   = left[i] * acc
+ *   o   = (alpha * v) + (beta * f0[i, c])
+ *   F(t+1)[i, c] = clamp && clamp[i] ? f0[i, c] : o
+ *   residual[t]  = max over i, c of |F(t+1)[i, c] - F(t)[i, c]|
+ * out [n, classes] = F(rounds).  pred int64 [n] (or NULL) = the argmax of each row of out, ties to the lower class, by integer compares on
+ * (score bits made orderable, ~class) as gmp_kmeans_assign compares.  residual fp32 [rounds] or NULL.  status int32 [2], zeroed inside the
+ * call: status[0] = the number of CSR entries whose col lies outside [0, n) -- counted once, skipped (not added as zero) in every round;
+ * status[1] = the number of rows of out whose maximum is not > 0: the nodes no label reached.  rowptr is clamped to [0, nnz], so a
+ * malformed CSR gives wrong numbers but reads nothing outside col.
+ * Determinism: a row's sum is sequential in ascending k, there is no floating-point atomic, and the residual is an integer atomic max on
+ * the bit pattern of a non-negative float.  So two calls leave the same bits, and one call of T rounds leaves the bits of T calls of one
+ * round, each fed the previous out as f_init.
+ * One launch per round (round t + 1 reads all of round t; there is no in-kernel grid barrier), all enqueued on `stream` without a host
+ * synchronisation; F ping-pongs between two [n, classes] buffers in the workspace and the last round writes out, pred and status[1].
+ * 0 <= n < 2^31, 0 <= nnz < 2^31, 1 <= classes <= 32, 1 <= rounds <= 10000: GMP_ERR_ARG outside those ranges, on a null required pointer
+ * (rowptr, f0, out, status; col when nnz > 0) and when out overlaps f0 or f_init; GMP_ERR_WORKSPACE when the workspace is smaller than
+ * gmp_label_propagate_workspace_bytes(n, classes) (0 for sizes out of range).  Nothing is launched in an error case.  n == 0 returns
+ * GMP_OK and writes nothing.  Asynchronous, no allocation, no global state.
+ * ------------------------------------------------------------------------- */
+size_t gmp_label_propagate_workspace_bytes(int64_t n, int classes);
+int gmp_label_propagate(const int32_t* rowptr, const int32_t* col, int64_t n, int64_t nnz, const float* left, const float* right,
+                        const float* f0, const float* f_init, const uint8_t* clamp, int classes, int rounds, float alpha, float beta,
+                        float* out, int64_t* pred, float* residual, int32_t* status, void* workspace, size_t workspace_bytes,
+                        gmp_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
  * The fused graph-classification head of fine-tuning (finetune_model.py:68-80, finetune.py:110-114) over one batch of
  * num_graphs graphs; graph b owns the rows ptr[b] .. ptr[b+1] of h (ptr: device int32 [num_graphs + 1]):
  *   pooled[b] = mean of the graph's rows, divisor max(count, 1) (gmp_segment_sum(mean = 1); an empty graph pools to zero),

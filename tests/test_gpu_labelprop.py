@@ -1,0 +1,296 @@
+"""gmp_label_propagate on the GPU (csrc/label_prop.hip: ops.label_propagate, finetune/node_baselines.py, --label-propagation) against the
+fp32 definition of tests/labelprop_ref.py.  A row's sum is sequential and every operation is rounded on its own, so every float output is
+compared for BIT EQUALITY; pred, status and residual are compared exactly.  test_labelprop_host.py ties that definition to float64 and to
+the closed form."""
+import ctypes as C
+import functools
+import json
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import labelprop_ref as R
+from gnn_pretraining_amd import _lib as L, ops
+from gnn_pretraining_amd._lib import GnnmpError
+from gnn_pretraining_amd.finetune import node_baselines as NB
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+GMP_OK, GMP_ERR_ARG, GMP_ERR_WORKSPACE = 0, -1, -3
+SENTINEL = -7.0
+ALPHA, BETA = R.ALPHA, R.BETA
+
+
+def _t(a, dtype=None):
+    if a is None or isinstance(a, torch.Tensor):
+        return a
+    t = torch.as_tensor(np.ascontiguousarray(a))
+    return (t if dtype is None else t.to(dtype)).to(DEV).contiguous()
+
+
+def _bits(x):
+    return np.ascontiguousarray(x.cpu().numpy() if isinstance(x, torch.Tensor) else x, dtype=np.float32).view(np.uint32)
+
+
+def _gpu(g, f0, rounds, alpha, beta, left=None, right=None, clamp=None, f_init=None):
+    return ops.label_propagate(_t(g.rowptr, torch.int32), _t(g.col, torch.int32), _t(f0), rounds, float(alpha), float(beta), left=_t(left),
+                               right=_t(right), clamp=_t(clamp, torch.uint8), f_init=_t(f_init), return_residual=True)
+
+
+def _assert_same(got, want):
+    assert got.out.dtype == torch.float32 and got.pred.dtype == torch.int64 and got.status.dtype == torch.int32
+    assert np.array_equal(_bits(got.out), _bits(want.out))
+    assert np.array_equal(got.pred.cpu().numpy(), want.pred)
+    assert np.array_equal(got.status.cpu().numpy(), want.status)
+    assert np.array_equal(_bits(got.residual), _bits(want.residual))
+
+
+def _check(g, f0, rounds, alpha, beta, left=None, right=None, clamp=None, f_init=None):
+    got = _gpu(g, f0, rounds, alpha, beta, left, right, clamp, f_init)
+    want = R.propagate(g.rowptr, g.col, f0, rounds, alpha, beta, left, right, clamp, f_init)
+    _assert_same(got, want)
+    return got, want
+
+
+@functools.lru_cache(maxsize=None)
+def _planted():
+    g, y, seeds = R.planted()
+    return g, y, seeds, R.one_hot(g.n, R.PLANTED_CLASSES, seeds, y[seeds])
+
+
+# ---------------------------------------------------------------------------- 1. the planted graph
+@pytest.mark.parametrize("clamped", [False, True], ids=["free", "clamp"])
+@pytest.mark.parametrize("kind", ["sym", "rw"])
+@pytest.mark.parametrize("rounds", [1, 2, 50])
+def test_planted_graph(rounds, kind, clamped):
+    g, _, seeds, f0 = _planted()
+    left, right = R.degree_scales(g.rowptr, kind)
+    got, want = _check(g, f0, rounds, ALPHA, BETA, left, right, R.seed_mask(g.n, seeds) if clamped else None)
+    assert want.status[1] >= 1 and not got.out[0].any()                                   # the isolated node stays unreached
+
+
+def test_planted_graph_from_another_start():
+    g, _, seeds, f0 = _planted()
+    left, right = R.degree_scales(g.rowptr, "sym")
+    f_init = np.random.default_rng(5).random(f0.shape).astype(np.float32)
+    _check(g, f0, 3, ALPHA, BETA, left, right, None, f_init)
+    _check(g, f0, 3, ALPHA, BETA, left, right, R.seed_mask(g.n, seeds), f_init)
+
+
+# ---------------------------------------------------------------------------- 2. lane-group and block boundaries
+@pytest.mark.parametrize("classes", [1, 3, 4, 5, 8, 31, 32])
+def test_widths(classes):
+    g = R.random_graph(150, 6.0, 10 + classes)
+    f0, f_init, left, right, clamp = R.random_inputs(g.n, classes, 20 + classes)
+    _check(g, f0, 3, 0.75, 0.5, left, right, clamp, f_init)
+    _check(g, f0, 2, 0.75, 0.5)                                                           # no scales, no clamp, F(0) = f0
+
+
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 257])
+def test_row_counts(n):
+    for classes in (1, 7, 32):                                                            # 64, 8 and 2 rows per wave
+        g = R.random_graph(n, 5.0, n)
+        f0, f_init, left, right, clamp = R.random_inputs(n, classes, n + classes)
+        _check(g, f0, 2, 0.75, 0.5, left, right, clamp, f_init)
+
+
+def test_star_with_a_long_row():
+    g = R.star(300, 5)
+    assert g.rowptr[1] - g.rowptr[0] == 300                                               # 37 unrolled chunks and a tail of 4
+    for classes in (1, 7):
+        f0, f_init, left, right, clamp = R.random_inputs(g.n, classes, 3)
+        _check(g, f0, 3, 0.75, 0.5, left, right, None, f_init)
+    left, right = R.degree_scales(g.rowptr, "sym")
+    _check(g, R.one_hot(g.n, 2, [0, 5], [0, 1]), 4, ALPHA, BETA, left, right)
+
+
+def test_graph_without_edges():
+    g = R.empty(70)
+    f0, f_init, left, right, clamp = R.random_inputs(70, 5, 1)
+    got, _ = _check(g, f0, 2, 0.5, 0.25, left, right, clamp, f_init)
+    assert g.col.size == 0 and int(got.status[0]) == 0
+
+
+# ---------------------------------------------------------------------------- 3. subnormals
+def test_path_reaches_subnormals():
+    g, f0, left, right, alpha, beta, rounds = R.subnormal_case()
+    got, want = _check(g, f0, rounds, alpha, beta, left, right)
+    out = got.out.cpu().numpy()
+    tiny = np.finfo(np.float32).tiny
+    assert ((out > 0) & (out < tiny)).sum() >= 2                                          # kept, not flushed: the denormal mode is part of the contract
+
+
+# ---------------------------------------------------------------------------- 4. status, argmax
+def test_stray_columns_are_counted_once_and_skipped():
+    g = R.random_graph(150, 6.0, 4)
+    s = R.with_stray_columns(g)
+    f0, f_init, left, right, clamp = R.random_inputs(g.n, 7, 4)
+    got = _gpu(s, f0, 3, 0.75, 0.5, left, right, clamp, f_init)
+    want = R.propagate(g.rowptr, g.col, f0, 3, 0.75, 0.5, left, right, clamp, f_init)     # the graph without them
+    assert int(got.status[0]) == 2 and int(got.status[1]) == want.status[1]
+    assert np.array_equal(_bits(got.out), _bits(want.out)) and np.array_equal(got.pred.cpu().numpy(), want.pred)
+    assert np.array_equal(_bits(got.residual), _bits(want.residual))
+
+
+def test_argmax_ties_go_to_the_lower_class():
+    g = R.path(6)                                                                         # node 2 hears nodes 1 and 3 equally
+    f0 = R.one_hot(6, 4, [1, 3], [2, 1])
+    got, want = _check(g, f0, 1, 1.0, 0.0)
+    out = got.out.cpu().numpy()
+    assert out[2, 1] == out[2, 2] > 0 and int(got.pred[2]) == 1 and want.pred[2] == 1
+    assert got.pred.cpu().tolist() == [2, 0, 1, 0, 1, 0]                                  # all-zero rows answer class 0
+    assert int(got.status[1]) == 3
+    tie = np.array([[0.5, 0.5, 0.1], [0.0, 0.0, 0.0], [0.1, 0.7, 0.7], [-1.0, -0.5, -0.5]], np.float32)
+    got, _ = _check(R.empty(4), tie, 1, 0.0, 1.0)
+    assert got.pred.cpu().tolist() == [0, 0, 1, 1] and got.status.cpu().tolist() == [0, 2]
+
+
+# ---------------------------------------------------------------------------- 5. determinism
+def test_one_call_equals_chained_single_rounds():
+    g, _, seeds, f0 = _planted()
+    left, right = R.degree_scales(g.rowptr, "sym")
+    whole = _gpu(g, f0, 6, ALPHA, BETA, left, right)
+    f, residual = None, []
+    for _ in range(6):
+        step = _gpu(g, f0, 1, ALPHA, BETA, left, right, None, f)
+        f = step.out
+        residual.append(step.residual)
+    assert torch.equal(f.view(torch.int32), whole.out.view(torch.int32)) and torch.equal(step.pred, whole.pred)
+    assert torch.equal(torch.cat(residual).view(torch.int32), whole.residual.view(torch.int32))
+    assert torch.equal(step.status, whole.status)
+
+
+def test_two_calls_leave_the_same_bits():
+    g = R.random_graph(257, 8.0, 9)
+    f0, f_init, left, right, clamp = R.random_inputs(g.n, 31, 9)
+    a = _gpu(g, f0, 7, 0.75, 0.5, left, right, clamp, f_init)
+    b = _gpu(g, f0, 7, 0.75, 0.5, left, right, clamp, f_init)
+    assert torch.equal(a.out.view(torch.int32), b.out.view(torch.int32)) and torch.equal(a.pred, b.pred)
+    assert torch.equal(a.residual.view(torch.int32), b.residual.view(torch.int32)) and torch.equal(a.status, b.status)
+
+
+# ---------------------------------------------------------------------------- 6. the error path
+def test_errors_launch_nothing():
+    g, _, _, f0h = _planted()
+    n, classes = g.n, f0h.shape[1]
+    rp, cl, f0 = _t(g.rowptr, torch.int32), _t(g.col, torch.int32), _t(f0h)
+    wide = torch.zeros(n, 33, device=DEV)
+    out = torch.full((n, 33), SENTINEL, device=DEV)
+    pred = torch.full((n,), int(SENTINEL), dtype=torch.int64, device=DEV)
+    status = torch.full((2,), int(SENTINEL), dtype=torch.int32, device=DEV)
+    ws = torch.empty(L.lib().gmp_label_propagate_workspace_bytes(n, 32), dtype=torch.uint8, device=DEV)
+    p = lambda t: C.c_void_p(0 if t is None else t.data_ptr())                   # noqa: E731
+
+    def call(n_=n, nnz_=cl.numel(), f0_=f0, f_init_=None, classes_=classes, rounds=3, out_=out, status_=status, rp_=rp, ws_bytes=ws.numel()):
+        return L.lib().gmp_label_propagate(p(rp_), p(cl), n_, nnz_, None, None, p(f0_), p(f_init_), None, classes_, rounds, 0.9, 0.1, p(out_), p(pred),
+                                           None, p(status_), p(ws), ws_bytes, None)
+
+    for rc in (call(classes_=0), call(classes_=33, f0_=wide), call(rounds=0), call(rounds=10001), call(out_=f0), call(f_init_=out),
+               call(n_=-1), call(n_=2 ** 31), call(nnz_=-1), call(nnz_=2 ** 31), call(rp_=None), call(f0_=None), call(out_=None),
+               call(status_=None)):
+        assert rc == GMP_ERR_ARG
+    assert "label_propagate" in L.lib().gmp_last_error_string().decode()
+    assert call(ws_bytes=L.lib().gmp_label_propagate_workspace_bytes(n, classes) - 1) == GMP_ERR_WORKSPACE
+    assert call(n_=0) == GMP_OK                                                           # nothing to do, nothing written
+    torch.cuda.synchronize()
+    assert bool((out == SENTINEL).all()) and bool((pred == int(SENTINEL)).all()) and bool((status == int(SENTINEL)).all())
+    assert torch.equal(f0.cpu(), torch.from_numpy(f0h))
+    assert call() == GMP_OK                                                               # and the same arguments, unbroken, run
+    torch.cuda.synchronize()
+    assert status.cpu().tolist()[0] == 0 and not bool((out.reshape(-1)[: n * classes] == SENTINEL).any())
+    with pytest.raises(GnnmpError, match="classes"):
+        ops.label_propagate(rp, cl, wide, 3, 0.9, 0.1)
+    with pytest.raises(GnnmpError, match="rounds"):
+        ops.label_propagate(rp, cl, f0, 0, 0.9, 0.1)
+    with pytest.raises(GnnmpError, match="left has"):
+        ops.label_propagate(rp, cl, f0, 1, 0.9, 0.1, left=torch.ones(n - 1, device=DEV))
+    with pytest.raises(GnnmpError):
+        ops.label_propagate(rp.cpu(), cl, f0, 1, 0.9, 0.1)
+    empty = ops.label_propagate(torch.zeros(1, dtype=torch.int32, device=DEV), torch.zeros(0, dtype=torch.int32, device=DEV),
+                                torch.zeros(0, 4, device=DEV), 2, 0.9, 0.1)
+    assert empty.out.shape == (0, 4) and empty.pred.shape == (0,) and empty.status.cpu().tolist() == [0, 0]
+
+
+# ---------------------------------------------------------------------------- 7. the baselines
+class _Data:
+    def __init__(self, g, y):
+        self.edge_index, self.num_nodes, self.y = torch.from_numpy(g.edges), g.n, torch.from_numpy(y)
+
+
+def _reference_baselines(g, y, train, evaluate, classes, rounds):
+    f0 = R.one_hot(g.n, classes, train, y[train])
+    left, right = R.degree_scales(g.rowptr, "sym")
+    spread = R.propagate(g.rowptr, g.col, f0, rounds, ALPHA, BETA, left, right)
+    left, _ = R.degree_scales(g.rowptr, "rw")
+    prop = R.propagate(g.rowptr, g.col, f0, rounds, 1.0, 0.0, left, None, clamp=R.seed_mask(g.n, train))
+    return {f"{name}_{k}": v for name, res in (("labelspread", spread), ("labelprop", prop))
+            for k, v in (("accuracy", float((res.pred[evaluate] == y[evaluate]).astype(np.float32).mean())),
+                         ("unreached", int((res.out[evaluate] == 0).all(axis=1).sum())))}, spread, prop
+
+
+def test_label_baselines_on_the_planted_graph():
+    g, y, seeds, _ = _planted()
+    evaluate = np.setdiff1d(np.arange(g.n), seeds)
+    got = NB.label_baselines(_Data(g, y), torch.from_numpy(seeds), torch.from_numpy(evaluate), R.PLANTED_CLASSES, 50, device=DEV)
+    want, spread, prop = _reference_baselines(g, y, seeds, evaluate, R.PLANTED_CLASSES, 50)
+    print("label_baselines", got)
+    assert got == want and isinstance(got["labelprop_unreached"], int)
+    assert got["labelspread_unreached"] >= 1 and got["labelspread_accuracy"] > 0.5 and got["labelprop_accuracy"] > 0.5
+    edges = torch.from_numpy(g.edges).to(DEV)
+    a = NB.label_spreading(edges, g.n, torch.from_numpy(seeds), torch.from_numpy(y[seeds]), R.PLANTED_CLASSES)     # the defaults: 50 rounds, alpha 0.9
+    b = NB.label_propagation(edges, g.n, torch.from_numpy(seeds), torch.from_numpy(y[seeds]), R.PLANTED_CLASSES)
+    assert np.array_equal(_bits(a.out), _bits(spread.out)) and np.array_equal(_bits(b.out), _bits(prop.out))
+    rowptr, col = NB.simple_graph(edges, g.n)
+    assert np.array_equal(rowptr.cpu().numpy(), g.rowptr) and np.array_equal(col.cpu().numpy(), g.col)
+    for kind in ("sym", "rw"):
+        got_s, want_s = NB.degree_scales(rowptr, kind), R.degree_scales(g.rowptr, kind)
+        assert got_s[0].is_cuda and np.array_equal(_bits(got_s[0]), _bits(want_s[0])) and (got_s[1] is None) == (want_s[1] is None)
+    assert NB.degree_scales(rowptr, "sym")[1] is not None
+
+
+def test_label_baselines_refuse_indices_outside_the_graph():
+    g, y, seeds, _ = _planted()
+    ok = torch.from_numpy(seeds)
+    for train, evaluate in ((torch.tensor([0, g.n]), ok), (ok, torch.tensor([-1, 4]))):
+        with pytest.raises(GnnmpError, match="outside"):
+            NB.label_baselines(_Data(g, y), train, evaluate, R.PLANTED_CLASSES, 5, device=DEV)
+    with pytest.raises(GnnmpError, match="outside"):
+        NB.label_spreading(torch.from_numpy(g.edges).to(DEV), g.n, ok, torch.full_like(ok, 7), R.PLANTED_CLASSES)
+
+
+# ---------------------------------------------------------------------------- 8. the command-line path
+def _run_cli(root, monkeypatch, name, extra):
+    from gnn_pretraining_amd import operators as O
+    from gnn_pretraining_amd.finetune import finetune as FT
+    monkeypatch.setattr(FT, "OUTPUT_DIR", root / name)
+    monkeypatch.setattr(O.DROPOUT, "count", 0)                                    # the module path's dropout counter is process-wide
+    log = root / f"{name}.jsonl"
+    monkeypatch.setattr(sys, "argv", ["finetune", "--domain_name", "Cora_NC", "--finetune_strategy", "full_finetune", "--pretrained_scheme", "b1",
+                                      "--seed", "5", "--epochs", "1", "--data-root", str(root / "data"), "--data-scale", "0.1",
+                                      "--log", str(log)] + extra)
+    FT.main()
+    rec = [json.loads(line) for line in log.read_text().splitlines()]
+    state = torch.load(next((root / name).glob("model_*.pt")), map_location="cpu", weights_only=True)["model_state_dict"]
+    return rec, state
+
+
+def test_cli_logs_the_four_keys_and_leaves_training_alone(tmp_path, monkeypatch):
+    """python -m gnn_pretraining_amd.finetune.finetune ... --label-propagation 10, in process: one epoch on the synthetic Cora_NC stand-in.
+    The test record carries the four keys, equal to label_baselines called directly on the same splits; every other key but the timing
+    ones, and the checkpoint, are bit for bit those of the same run without the flag."""
+    from gnn_pretraining_amd.constants import NUM_CLASSES
+    from gnn_pretraining_amd.data.finetune_data_loaders import create_finetune_data_loader
+    keys = [f"test/{name}_{k}" for name in ("labelspread", "labelprop") for k in ("accuracy", "unreached")]
+    rec1, state1 = _run_cli(tmp_path, monkeypatch, "with", ["--label-propagation", "10"])
+    rec0, state0 = _run_cli(tmp_path, monkeypatch, "without", [])
+    test1 = [r for r in rec1 if keys[0] in r]
+    assert len(test1) == 1 and "test/accuracy" in test1[0] and all(k in test1[0] for k in keys)
+    assert not any("label" in k for r in rec1 if r is not test1[0] for k in r) and not any("label" in k for r in rec0 for k in r)
+    sets = {sp: create_finetune_data_loader("Cora_NC", sp, -1, torch.Generator(), tmp_path / "data").dataset for sp in ("train", "test")}
+    direct = NB.label_baselines(sets["train"].data, sets["train"].indices, sets["test"].indices, NUM_CLASSES["Cora_NC"], 10, device=DEV)
+    assert {k: test1[0][k] for k in keys} == {f"test/{k}": v for k, v in direct.items()}
+    assert state1.keys() == state0.keys() and all(torch.equal(state1[k], state0[k]) for k in state1)
+    for k, v in [r for r in rec0 if "test/accuracy" in r][0].items():
+        assert "time" in k or test1[0][k] == v or (v != v and test1[0][k] != test1[0][k]), k
