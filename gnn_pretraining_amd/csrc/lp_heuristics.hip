@@ -18,9 +18,7 @@
 //   simple_check_kernel  one wave per row
 // Every read of col is bounded by rowptr clamped to [0, nnz], every entry outside [0, N) is skipped and every LDS slot index is checked: a
 // CSR that breaks the assumptions gives wrong numbers, never an access outside the arrays.
-#include <algorithm>
-
-#include "gnnmp_internal.h"
+#include "lp_filter.h"
 
 namespace {
 
@@ -149,14 +147,7 @@ __global__ __launch_bounds__(THREADS) void cn_count_kernel(const int32_t* __rest
             __syncthreads();
         }
     }
-    // the filter row, gmp_lp_rank's contract: any order, duplicates, entries outside [0, N) ignored
-    if (frowptr && s >= 0 && s < N) {
-        const int64_t fb = max((int64_t)frowptr[s], (int64_t)0), fe = min((int64_t)frowptr[s + 1], fnnz);
-        for (int64_t i = fb + t; i < fe; i += THREADS) {
-            const uint64_t off = (uint64_t)((int64_t)fcol[i] - c0);
-            if (off < (uint64_t)TC) atomicOr(&fbits[off >> 5], 1u << (unsigned)(off & 31));
-        }
-    }
+    lpf::mark<TC / 32, THREADS>(frowptr, fcol, fnnz, s, N, c0, fbits);     // gmp_lp_rank's filter row
     const Row rd = row_of(rowptr, nnz, N, d);
     if (mode == MODE_JACCARD) {                                     // the true pair's count again, as an integer: the float quotient does not carry it
         for (int64_t i = rs.b + t; i < rs.e; i += THREADS) {
@@ -172,7 +163,7 @@ __global__ __launch_bounds__(THREADS) void cn_count_kernel(const int32_t* __rest
     int greater = 0, equal = 0;
     for (int r = t; r < TC; r += THREADS) {
         const int64_t c = c0 + r;
-        if (c >= N || c == s || c == d || ((fbits[r >> 5] >> (r & 31)) & 1u)) continue;
+        if (c >= N || c == s || c == d || lpf::marked(fbits, r)) continue;
         int cmp;
         if (mode == MODE_JACCARD) {
             const Row rc = row_of(rowptr, nnz, N, c);
@@ -267,17 +258,14 @@ extern "C" int gmp_lp_cn_rank(const int32_t* rowptr, const int32_t* col, int64_t
     if (int rc = graph_ok("lp_cn_rank", rowptr, col, N, nnz)) return rc;
     if (int rc = scorer_ok("lp_cn_rank", weight, mode)) return rc;
     if (Q < 0 || filter_nnz < 0) return gmp::fail(GMP_ERR_ARG, "lp_cn_rank: Q=%lld filter_nnz=%lld", (long long)Q, (long long)filter_nnz);
-    if ((filter_rowptr == nullptr) != (filter_col == nullptr) && filter_nnz != 0)
-        return gmp::fail(GMP_ERR_ARG, "lp_cn_rank: filter_rowptr and filter_col must both be given or both be null");
+    if (int rc = lpf::filter_ok("lp_cn_rank", filter_rowptr, filter_col, filter_nnz)) return rc;
     if (Q == 0) return GMP_OK;
     if (!src || !dst || !score_true || !n_greater || !n_equal) return gmp::fail(GMP_ERR_ARG, "lp_cn_rank: null pointer");
     const int64_t tiles = (N + TC - 1) / TC;
-    if (Q * std::max<int64_t>(tiles, 1) >= ((int64_t)1 << 31))
-        return gmp::fail(GMP_ERR_ARG, "lp_cn_rank: Q=%lld x %lld candidate tiles exceed one grid", (long long)Q, (long long)tiles);
+    if (int rc = lpf::grid_ok("lp_cn_rank", Q, tiles)) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (int rc = launch_pairs("lp_cn_rank", rowptr, col, N, nnz, src, dst, Q, weight, mode, score_true, n_greater, n_equal, st)) return rc;
     if (tiles == 0) return GMP_OK;
-    if (!filter_col) filter_rowptr = nullptr;
     hipLaunchKernelGGL(cn_count_kernel, dim3((unsigned)(Q * tiles)), dim3(THREADS), 0, st, rowptr, col, N, nnz, src, dst, (int)tiles, weight, mode,
                        filter_rowptr, filter_col, filter_nnz, (const float*)score_true, n_greater, n_equal);
     return gmp::check_launch("cn_count_kernel");

@@ -5,7 +5,7 @@
 // features live only in LDS / registers.  Every product runs on v_mfma_f32_32x32x2_f32 (exact fp32, like the rest of the library),
 // and every reduction over pairs is a fixed-order sum (slices in LDS, partials in a workspace reduced in order): no float atomics.
 //
-// Forward (two launches):
+// Forward (two launches; the tile code is lp_tile.h's, which lp_rank.hip's ranking shares):
 //   lp_score_fwd_kernel   one block per (32 pairs, 32 hidden units): the block builds the 32 x 768 feature tile in LDS, its eight
 //                         waves each take a 96-deep k-slice (48 MFMAs), the slices are added in order through LDS, then the epilogue
 //                         (bias, ReLU, the Philox mask of gmp_dropout_fwd over the [K, 256] activation) writes act = relu(z) (the kept
@@ -19,27 +19,15 @@
 //                         reduction, added in order), turned straight into the per-pair g_hs / g_hd of gmp_lp_edge_features_bwd
 //   lp_wgrad_final_kernel the slice partials of dW0, db0, dw3, db3 added in order into the gradient buffer
 // An index outside [0, N) reads as a zero row (gmp_row_gather); rows of a tile beyond K are computed as zeros and never stored.
-#include "gnnmp_internal.h"
+#include "lp_tile.h"
 
 namespace {
 
-using gmp::f32x16;
+using namespace lpt;                // F, HID, KF, BM, LDA, THREADS, zero4, row4, aligned16 and the forward's tile code
 
-constexpr int F = 256;              // node embedding width
-constexpr int HID = 256;            // hidden units of the scorer
-constexpr int KF = 3 * F;           // feature width
-constexpr int BM = 32;              // pairs per tile
-constexpr int LDA = KF + 4;         // LDS row stride of the feature tile (16-byte skew: conflict-free ds_read_b128 down a column)
-constexpr int FWD_THREADS = 512;    // 8 waves, one 96-deep k-slice each
 constexpr int FWD_LDS = BM * LDA * 4;
 constexpr int MS = 128;             // pairs per slice of the dW0 reduction
 constexpr int64_t W0N = (int64_t)HID * KF;
-
-__device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-
-__device__ __forceinline__ float4 row4(const float4* __restrict__ h, int64_t i, int64_t N, int c4) {
-    return (i >= 0 && i < N) ? h[i * (F / 4) + c4] : zero4();
-}
 
 __device__ __forceinline__ float row1(const float* __restrict__ h, int64_t i, int64_t N, int c) {
     return (i >= 0 && i < N) ? h[i * F + c] : 0.f;
@@ -53,72 +41,30 @@ __device__ __forceinline__ float4 mask4(int64_t m, int col, float p, uint64_t se
     return gmp::dropout_scale4(seed, site, (uint64_t)(m * (HID / 4) + (col >> 2)), p, 1.f / (1.f - p));
 }
 
-__global__ __launch_bounds__(FWD_THREADS) void lp_score_fwd_kernel(const float* __restrict__ h, const int64_t* __restrict__ src,
-                                                                   const int64_t* __restrict__ dst, int64_t N, int64_t K,
-                                                                   const float* __restrict__ w0, const float* __restrict__ b0,
-                                                                   const float* __restrict__ w3, float* __restrict__ act,
-                                                                   float* __restrict__ part, float p, uint64_t seed, uint32_t site) {
+__global__ __launch_bounds__(THREADS) void lp_score_fwd_kernel(const float* __restrict__ h, const int64_t* __restrict__ src,
+                                                               const int64_t* __restrict__ dst, int64_t N, int64_t K,
+                                                               const float* __restrict__ w0, const float* __restrict__ b0,
+                                                               const float* __restrict__ w3, float* __restrict__ act,
+                                                               float* __restrict__ part, float p, uint64_t seed, uint32_t site) {
     extern __shared__ float4 smem4[];
     float* tile = reinterpret_cast<float*>(smem4);
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, l31 = lane & 31, half = lane >> 5;
     const int64_t m0 = (int64_t)blockIdx.x * BM;
     const int n0 = blockIdx.y * 32;
-    const float4* h4 = reinterpret_cast<const float4*>(h);
 
-    // the 32 x 768 feature tile
-    for (int it = t; it < BM * (F / 4); it += FWD_THREADS) {
-        const int r = it / (F / 4), c4 = it % (F / 4);
-        const int64_t m = m0 + r;
-        float4 s = zero4(), d = zero4();
-        if (m < K) { s = row4(h4, src[m], N, c4); d = row4(h4, dst[m], N, c4); }
-        float* o = tile + r * LDA + 4 * c4;
-        *reinterpret_cast<float4*>(o) = make_float4(s.x + d.x, s.y + d.y, s.z + d.z, s.w + d.w);
-        *reinterpret_cast<float4*>(o + F) = make_float4(s.x * d.x, s.y * d.y, s.z * d.z, s.w * d.w);
-        *reinterpret_cast<float4*>(o + 2 * F) = make_float4(fabsf(s.x - d.x), fabsf(s.y - d.y), fabsf(s.z - d.z), fabsf(s.w - d.w));
-    }
+    const auto node = [&](const int64_t* idx, int r) { return m0 + r < K ? idx[m0 + r] : (int64_t)-1; };   // beyond K: a zero row
+    build(tile, reinterpret_cast<const float4*>(h), N, [&](int r) { return node(src, r); }, [&](int r) { return node(dst, r); });
     __syncthreads();
-
-    // wave `wave`: k in [96 wave, 96 wave + 96); lanes 0-31 take its first 48 k, lanes 32-63 the second (A and B agree on the pairing)
-    const int kb = 96 * wave + 48 * half;
-    const float4* a4 = reinterpret_cast<const float4*>(tile + l31 * LDA + kb);
-    const float4* b4 = reinterpret_cast<const float4*>(w0 + (int64_t)(n0 + l31) * KF + kb);
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    float4 bv[12];
-#pragma unroll
-    for (int q = 0; q < 12; ++q) bv[q] = b4[q];
-#pragma unroll
-    for (int q = 0; q < 12; ++q) {
-        const float4 av = a4[q];
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bv[q].x, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bv[q].y, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bv[q].z, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bv[q].w, acc, 0, 0, 0);
-    }
+    const f32x16 acc = slice(tile, w0, n0, wave, l31, half);
     __syncthreads();                                            // every wave is done with the feature tile: it becomes red[8][32][32]
-#pragma unroll
-    for (int r = 0; r < 16; ++r) tile[gmp::acc_row(r, half, wave * 32) * 32 + l31] = acc[r];
+    spill(tile, acc, wave, l31, half);
     __syncthreads();
     if (t >= 256) return;                                       // (waves 4-7: wave-uniform)
     const int row = t >> 3, c4 = t & 7, col = n0 + 4 * c4;
-    float4 z = zero4();
-#pragma unroll
-    for (int w = 0; w < 8; ++w) {                               // k-slices in order
-        const float4 v = *reinterpret_cast<const float4*>(tile + (w * 32 + row) * 32 + 4 * c4);
-        z.x += v.x; z.y += v.y; z.z += v.z; z.w += v.w;
-    }
-    const float4 bb = *reinterpret_cast<const float4*>(b0 + col), ww = *reinterpret_cast<const float4*>(w3 + col);
-    const float4 a = make_float4(fmaxf(z.x + bb.x, 0.f), fmaxf(z.y + bb.y, 0.f), fmaxf(z.z + bb.z, 0.f), fmaxf(z.w + bb.w, 0.f));
+    const float4 a = hidden4(tile, b0, n0);
     const int64_t m = m0 + row;
     const float4 mk = mask4(m, col, p, seed, site);
-    float dot = a.x * mk.x * ww.x;
-    dot += a.y * mk.y * ww.y;
-    dot += a.z * mk.z * ww.z;
-    dot += a.w * mk.w * ww.w;
-    dot += __shfl_xor(dot, 1, 64);                              // the row's 8 lanes, a fixed butterfly
-    dot += __shfl_xor(dot, 2, 64);
-    dot += __shfl_xor(dot, 4, 64);
+    const float dot = partial_dot(make_float4(a.x * mk.x, a.y * mk.y, a.z * mk.z, a.w * mk.w), w3, n0);
     if (m < K) {
         *reinterpret_cast<float4*>(act + m * HID + col) = a;
         if (c4 == 0) part[(int64_t)blockIdx.y * K + m] = dot;
@@ -282,18 +228,17 @@ struct BwdWs {
     size_t bytes;
 };
 
-BwdWs bwd_layout(int64_t K, char* base) {
-    auto al = [](size_t b) { return (b + 255) / 256 * 256; };
+BwdWs bwd_layout(int64_t K, void* workspace) {
     BwdWs w;
     w.T = gmp::cdiv(K, BM);
     w.S = gmp::cdiv(K, MS);
-    size_t o = 0;
-    w.gz = (float*)(base + o);   o += al((size_t)w.T * BM * HID * 4);
-    w.dw0p = (float*)(base + o); o += al((size_t)w.S * W0N * 4);
-    w.db0p = (float*)(base + o); o += al((size_t)w.T * HID * 4);
-    w.dw3p = (float*)(base + o); o += al((size_t)w.T * HID * 4);
-    w.db3p = (float*)(base + o); o += al((size_t)w.T * 4);
-    w.bytes = o;
+    gmp::Carver c(workspace, true);
+    w.gz = c.take<float>((size_t)w.T * BM * HID);
+    w.dw0p = c.take<float>((size_t)w.S * W0N);
+    w.db0p = c.take<float>((size_t)w.T * HID);
+    w.dw3p = c.take<float>((size_t)w.T * HID);
+    w.db3p = c.take<float>((size_t)w.T);
+    w.bytes = c.total();
     return w;
 }
 
@@ -303,13 +248,11 @@ int shape_ok(const char* who, int64_t N, int64_t K, int feat, int hidden) {
     return GMP_OK;
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
 
 extern "C" size_t gmp_lp_score_fwd_workspace_bytes(int64_t K) { return (size_t)(K > 0 ? K : 1) * (HID / 32) * 4; }
 
-extern "C" size_t gmp_lp_score_bwd_workspace_bytes(int64_t K) { return bwd_layout(K > 0 ? K : 0, nullptr).bytes + 256; }
+extern "C" size_t gmp_lp_score_bwd_workspace_bytes(int64_t K) { return bwd_layout(K > 0 ? K : 0, nullptr).bytes; }
 
 extern "C" int gmp_lp_score_fwd(const float* h, const int64_t* src, const int64_t* dst, int64_t N, int64_t K, int feat, int hidden,
                                 const float* w0, const float* b0, const float* w3, const float* b3, float* act, float* logit,
@@ -326,7 +269,7 @@ extern "C" int gmp_lp_score_fwd(const float* h, const int64_t* src, const int64_
     if (int rc = gmp::reserve_lds(attr_set, (const void*)lp_score_fwd_kernel, FWD_LDS, "lp_score_fwd")) return rc;
     hipStream_t st = (hipStream_t)stream;
     float* part = (float*)workspace;
-    hipLaunchKernelGGL(lp_score_fwd_kernel, dim3((unsigned)gmp::cdiv(K, BM), HID / 32), dim3(FWD_THREADS), FWD_LDS, st, h, src, dst, N, K,
+    hipLaunchKernelGGL(lp_score_fwd_kernel, dim3((unsigned)gmp::cdiv(K, BM), HID / 32), dim3(THREADS), FWD_LDS, st, h, src, dst, N, K,
                        w0, b0, w3, act, part, p, seed, site);
     if (int rc = gmp::check_launch("lp_score_fwd_kernel")) return rc;
     hipLaunchKernelGGL(lp_logit_kernel, dim3((unsigned)gmp::cdiv(K, 256)), dim3(256), 0, st, (const float*)part, b3, logit, K);
@@ -344,8 +287,7 @@ extern "C" int gmp_lp_score_bwd(const float* h, const int64_t* src, const int64_
         return gmp::fail(GMP_ERR_ARG, "lp_score_bwd: null pointer");
     if (!aligned16(w3) || !aligned16(act)) return gmp::fail(GMP_ERR_ARG, "lp_score_bwd: w3 and act must be 16-byte aligned");
     if (workspace_bytes < gmp_lp_score_bwd_workspace_bytes(K)) return gmp::fail(GMP_ERR_ARG, "lp_score_bwd: workspace too small");
-    char* base = (char*)(((uintptr_t)workspace + 255) / 256 * 256);
-    const BwdWs w = bwd_layout(K, base);
+    const BwdWs w = bwd_layout(K, workspace);
     hipStream_t st = (hipStream_t)stream;
     if (K > 0) {
         hipLaunchKernelGGL(lp_gz_kernel, dim3((unsigned)w.T), dim3(256), 0, st, act, g_logit, w3, w.gz, w.db0p, w.dw3p, w.db3p, K, p, seed, site);

@@ -554,6 +554,11 @@ class LinkRanks(NamedTuple):
     rank: Tensor        # [Q] float32: 1 + n_greater + n_equal / 2
     logit: Tensor       # [Q] the true pair's logit (sigmoid of it is predict()'s probability)
 
+    @classmethod
+    def from_counts(cls, n_greater: Tensor, n_equal: Tensor, logit: Tensor) -> "LinkRanks":
+        """A tie sits at the mean over its orders."""
+        return cls(n_greater, n_equal, 1.0 + n_greater.to(torch.float32) + 0.5 * n_equal.to(torch.float32), logit)
+
 
 class LinkPredictionEngine(FullGraphEngine):
     """One link-prediction fine-tune step (Cora_LP / CiteSeer_LP, src/finetune/finetune.py:181-211) as an explicit kernel sequence.
@@ -699,7 +704,7 @@ class LinkPredictionEngine(FullGraphEngine):
             raise ValueError("LinkPredictionEngine.rank: no pairs")
         hL, weights, filt = self._ranking_inputs("rank", embeddings, filter_edges)
         logit, n_greater, n_equal = OP.lp_rank(hL, edges, *weights, filter_edges=filt)
-        return LinkRanks(n_greater, n_equal, 1.0 + n_greater.to(torch.float32) + 0.5 * n_equal.to(torch.float32), logit)
+        return LinkRanks.from_counts(n_greater, n_equal, logit)
 
     def top_k(self, sources: Tensor, k: int, filter_edges: Optional[Tensor] = None, embeddings: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
         """The k (1 <= k <= 64) most probable destinations of every node of sources [Q] (int64, on the device) among all N nodes

@@ -119,4 +119,4 @@ def heuristic_ranks(edge_index: Tensor, num_nodes: int, edges: Tensor, kind: str
     e = _pairs("heuristic_ranks", edges)
     frowptr, fcol = _lp_filter("heuristic_ranks", filter_edges, num_nodes)
     score, n_greater, n_equal = ops.lp_cn_rank(rowptr, col, e[0], e[1], weight, mode, frowptr, fcol)
-    return LinkRanks(n_greater, n_equal, 1.0 + n_greater.to(torch.float32) + 0.5 * n_equal.to(torch.float32), score)
+    return LinkRanks.from_counts(n_greater, n_equal, score)

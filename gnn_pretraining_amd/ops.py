@@ -1083,19 +1083,24 @@ def lp_score_node_grad(g_hs: Tensor, g_hd: Tensor, pairs: Tensor, num_nodes: int
     return segment_sum(g_hd, csr.rowptr, csr.perm, out=gh, accumulate=True)
 
 
-def _lp_rank_args(who: str, h: Tensor, w0: Tensor, b0: Tensor, w3: Tensor, b3: Tensor, filter_rowptr: Optional[Tensor],
-                  filter_col: Optional[Tensor]) -> int:
-    _need(h, torch.float32, "h", 2)
-    for t, n in ((w0, "w0"), (b0, "b0"), (w3, "w3"), (b3, "b3")):
-        _need(t, torch.float32, n)
+def _lp_filter_args(who: str, num_nodes: int, filter_rowptr: Optional[Tensor], filter_col: Optional[Tensor]) -> int:
+    """The entry count of a ranker's optional filter CSR (int32 rowptr [num_nodes + 1] / col), 0 without one."""
     if (filter_rowptr is None) != (filter_col is None):
         raise L.GnnmpError(f"{who}: filter_rowptr and filter_col go together")
     if filter_rowptr is None:
         return 0
     _need(filter_rowptr, torch.int32, "filter_rowptr", 1); _need(filter_col, torch.int32, "filter_col", 1)
-    if filter_rowptr.numel() != h.size(0) + 1:
-        raise L.GnnmpError(f"{who}: filter_rowptr has {filter_rowptr.numel()} entries for {h.size(0)} nodes")
+    if filter_rowptr.numel() != num_nodes + 1:
+        raise L.GnnmpError(f"{who}: filter_rowptr has {filter_rowptr.numel()} entries for {num_nodes} nodes")
     return filter_col.numel()
+
+
+def _lp_rank_args(who: str, h: Tensor, w0: Tensor, b0: Tensor, w3: Tensor, b3: Tensor, filter_rowptr: Optional[Tensor],
+                  filter_col: Optional[Tensor]) -> int:
+    _need(h, torch.float32, "h", 2)
+    for t, n in ((w0, "w0"), (b0, "b0"), (w3, "w3"), (b3, "b3")):
+        _need(t, torch.float32, n)
+    return _lp_filter_args(who, h.size(0), filter_rowptr, filter_col)
 
 
 def lp_rank(h: Tensor, src: Tensor, dst: Tensor, w0: Tensor, b0: Tensor, w3: Tensor, b3: Tensor, filter_rowptr: Optional[Tensor] = None,
@@ -1177,14 +1182,7 @@ def lp_cn_rank(rowptr: Tensor, col: Tensor, src: Tensor, dst: Tensor, weight: Op
     src[q]'s row of the optional filter CSR (lp_rank's).  A candidate's score has the bits lp_cn_score gives the pair; Jaccard is
     compared exactly in integers.  Nothing of size Q x N is allocated."""
     N, nnz, code = _lp_cn_args("lp_cn_rank", rowptr, col, weight, mode)
-    if (filter_rowptr is None) != (filter_col is None):
-        raise L.GnnmpError("lp_cn_rank: filter_rowptr and filter_col go together")
-    fnnz = 0
-    if filter_rowptr is not None:
-        _need(filter_rowptr, torch.int32, "filter_rowptr", 1); _need(filter_col, torch.int32, "filter_col", 1)
-        if filter_rowptr.numel() != N + 1:
-            raise L.GnnmpError(f"lp_cn_rank: filter_rowptr has {filter_rowptr.numel()} entries for {N} nodes")
-        fnnz = filter_col.numel()
+    fnnz = _lp_filter_args("lp_cn_rank", N, filter_rowptr, filter_col)
     _need(src, torch.int64, "src", 1); _need(dst, torch.int64, "dst", 1)
     Q, dev, l = src.numel(), rowptr.device, L.lib()
     if dst.numel() != Q:

@@ -59,7 +59,11 @@ def test_ranking_symbols_are_declared_bound_and_exported():
 
 
 def test_ranking_kernel_source_keeps_the_scorers_products_and_has_no_float_atomics():
-    src = (ROOT / "gnn_pretraining_amd" / "csrc" / "lp_rank.hip").read_text()
+    csrc = ROOT / "gnn_pretraining_amd" / "csrc"
+    src = (csrc / "lp_rank.hip").read_text()
+    assert '#include "lp_tile.h"' in src and '#include "lp_filter.h"' in src            # the scorer's tile code and the filter bitmap
+    assert '#include "lp_tile.h"' in (csrc / "lp_score.hip").read_text()                # ... which the training forward runs too
+    src += (csrc / "lp_tile.h").read_text() + (csrc / "lp_filter.h").read_text()
     assert "mfma_f32_32x32x2f32" in src
     for m in re.finditer(r"atomicAdd\(&(\w+)", src):                                   # integer counts only
         assert m.group(1) in ("cnt", "n_greater", "n_equal"), m.group(0)
