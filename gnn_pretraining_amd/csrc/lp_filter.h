@@ -1,4 +1,4 @@
-// The candidate filter shared by the all-candidate rankers (lp_rank.hip, lp_heuristics.hip): a query with source s skips the entries of
+// The candidate filter shared by the all-candidate rankers (lp_rank.hip, lp_heuristics.hip, lp_walk.hip): a query with source s skips the entries of
 // row s of an optional filter CSR (int32 rowptr / col, any order, duplicates allowed).  A block that walks the candidates
 // [c0, c0 + 32 W) keeps the row as a bitmap of W words in LDS; what it counts or compares belongs to each kernel.
 #pragma once
@@ -17,6 +17,18 @@ __device__ __forceinline__ void mark(const int32_t* __restrict__ rowptr, const i
         for (int64_t i = b + threadIdx.x; i < e; i += THREADS) {
             const uint64_t off = (uint64_t)((int64_t)col[i] - c0);
             if (off < (uint64_t)(32 * W)) atomicOr(&bits[off >> 5], 1u << (unsigned)(off & 31));
+        }
+    }
+}
+
+// The same for a block of `threads` that keeps a bitmap of a run-time number of `words` (lp_walk.hip: one bitmap over all candidates).
+__device__ __forceinline__ void mark(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, int64_t nnz, int64_t s, int64_t N,
+                                     int64_t c0, unsigned int* bits, int64_t words, int threads) {
+    if (rowptr && s >= 0 && s < N) {
+        const int64_t b = max((int64_t)rowptr[s], (int64_t)0), e = min((int64_t)rowptr[s + 1], nnz);
+        for (int64_t i = b + threadIdx.x; i < e; i += threads) {
+            const uint64_t off = (uint64_t)((int64_t)col[i] - c0);
+            if (off < (uint64_t)(32 * words)) atomicOr(&bits[off >> 5], 1u << (unsigned)(off & 31));
         }
     }
 }

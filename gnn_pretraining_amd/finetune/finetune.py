@@ -155,6 +155,7 @@ class FinetuneConfig:
     lp_heuristics: bool = False         # link-prediction domains: the test record also carries test/{cn,jaccard,aa,ra}_mrr / _hits@K, the neighbourhood baselines ranked like lp_ranking on the message-passing graph (link_heuristics.py); needs no engine
     repr_stats: bool = False            # on an engine: the label-free statistics of the validation embeddings (repr_stats.embedding_stats: val/repr_uniformity, val/repr_mean_cosine, val/repr_rankme); every domain, link prediction included
     label_propagation: int = 0          # node-classification domains: rounds of the label-spreading and label-propagation baselines on the raw graph (node_baselines.py: test/labelspread_accuracy, test/labelprop_accuracy and their _unreached counts); needs no engine and no probe; 0 = off
+    lp_walks: int = 0                   # link-prediction domains: rounds of the walk-based baselines; the test record also carries test/{katz,ppr,hops}_mrr / _hits@K, ranked like lp_heuristics on the message-passing graph (link_walks.py); needs no engine; 0 = off
     wl_baseline: int = 0                # graph-classification domains: rounds of the Weisfeiler-Lehman subtree baseline on the raw graphs (graph_baselines.py: test/wl_knn_accuracy, test/wl_logreg_accuracy); needs no engine and no probe; 0 = off
 
     def __post_init__(self) -> None:
@@ -192,6 +193,10 @@ class FinetuneConfig:
             raise ValueError("lp_ranking ranks with the link-prediction engine (gmp_lp_rank): pass lp_engine (--lp-engine)")
         if self.lp_heuristics and TASK_TYPES[self.domain_name] != "link_prediction":
             raise ValueError(f"lp_heuristics applies to the link-prediction domains (Cora_LP / CiteSeer_LP), not to {self.domain_name}")
+        if not 0 <= self.lp_walks <= ops.LP_WALK_MAX_ROUNDS:
+            raise ValueError(f"lp_walks={self.lp_walks} (the number of propagation rounds, 1 <= rounds <= {ops.LP_WALK_MAX_ROUNDS}; 0 switches the baselines off)")
+        if self.lp_walks and TASK_TYPES[self.domain_name] != "link_prediction":
+            raise ValueError(f"lp_walks applies to the link-prediction domains (Cora_LP / CiteSeer_LP), not to {self.domain_name}")
         if not 0 <= self.wl_baseline <= ops.WL_MAX_ITERS:
             raise ValueError(f"wl_baseline={self.wl_baseline} (the number of refinement rounds, 1 <= rounds <= {ops.WL_MAX_ITERS}; 0 switches the baseline off)")
         if self.wl_baseline and TASK_TYPES[self.domain_name] != "graph_classification":
@@ -429,19 +434,38 @@ def rank_test_edges(engine, train_loader, val_loader, test_loader, device) -> Di
     return {f"test/{k}": v for k, v in ranking_metrics(ranks).items()}
 
 
-def rank_test_edges_heuristics(train_loader, val_loader, test_loader, device) -> Dict[str, float]:
-    """cfg.lp_heuristics: rank_test_edges with the four neighbourhood baselines (link_heuristics.KINDS) in place of the trained scorer.
-    They see the message-passing graph alone -- the train split's positive edges; validation and test edges enter the filter only.
-    Reads the datasets and nothing else: no model, no generator, no dropout counter, no BatchNorm state."""
-    from . import link_heuristics as LH
+def _structural_ranking_inputs(train_loader, val_loader, test_loader, device):
+    """(graph, num_nodes, true test edges, filter edges) of the model-free link baselines: the message-passing graph is the train
+    split's positive edges alone; the known positives of the three splits, in both directions, are the filter."""
     data = train_loader.dataset
     graph = data.train_edges.to(device).contiguous()
     pos = test_loader.dataset.pos_edges.to(device).contiguous()
     known = torch.cat([data.train_edges, val_loader.dataset.pos_edges, test_loader.dataset.pos_edges], dim=1).to(device)
     known = torch.cat([known, known.flip(0)], dim=1).contiguous()
+    return graph, data.data.num_nodes, pos, known
+
+
+def rank_test_edges_heuristics(train_loader, val_loader, test_loader, device) -> Dict[str, float]:
+    """cfg.lp_heuristics: rank_test_edges with the four neighbourhood baselines (link_heuristics.KINDS) in place of the trained scorer.
+    They see the message-passing graph alone -- the train split's positive edges; validation and test edges enter the filter only.
+    Reads the datasets and nothing else: no model, no generator, no dropout counter, no BatchNorm state."""
+    from . import link_heuristics as LH
+    graph, num_nodes, pos, known = _structural_ranking_inputs(train_loader, val_loader, test_loader, device)
     out = {}
     for kind in LH.KINDS:
-        ranks = LH.heuristic_ranks(graph, data.data.num_nodes, pos, kind, filter_edges=known).rank
+        ranks = LH.heuristic_ranks(graph, num_nodes, pos, kind, filter_edges=known).rank
+        out.update({f"test/{kind}_{k}": v for k, v in ranking_metrics(ranks).items()})
+    return out
+
+
+def rank_test_edges_walks(train_loader, val_loader, test_loader, device, rounds: int) -> Dict[str, float]:
+    """cfg.lp_walks: rank_test_edges_heuristics with the three walk-based baselines (link_walks.KINDS: Katz, rooted PageRank, hop
+    distance) at `rounds` rounds -- the same graph, the same filter, the same half-tie rank.  Reads the datasets and nothing else."""
+    from . import link_walks as LW
+    graph, num_nodes, pos, known = _structural_ranking_inputs(train_loader, val_loader, test_loader, device)
+    out = {}
+    for kind in LW.KINDS:
+        ranks = LW.walk_ranks(graph, num_nodes, pos, kind, rounds, filter_edges=known).rank
         out.update({f"test/{kind}_{k}": v for k, v in ranking_metrics(ranks).items()})
     return out
 
@@ -613,6 +637,8 @@ def finetune(cfg: FinetuneConfig, epochs: Optional[int] = None, device: Optional
         test.update(rank_test_edges(lp_engine, train_loader, val_loader, test_loader, dev))
     if cfg.lp_heuristics:
         test.update(rank_test_edges_heuristics(train_loader, val_loader, test_loader, dev))
+    if cfg.lp_walks:
+        test.update(rank_test_edges_walks(train_loader, val_loader, test_loader, dev, cfg.lp_walks))
     if cfg.wl_baseline:
         test.update(wl_baseline_keys(train_loader, test_loader, dev, cfg))
     if cfg.label_propagation:
@@ -640,6 +666,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--engine-eval", action="store_true", help="validation / test through the active engine's predict (needs the node engine, --lp-engine or --gc-engine)")
     p.add_argument("--lp-ranking", action="store_true", help="with --lp-engine: the test pass also logs test/mrr and test/hits@K (true test edges ranked against all nodes, known positives filtered)")
     p.add_argument("--lp-heuristics", action="store_true", help="Cora_LP / CiteSeer_LP: the test record also carries test/{cn,jaccard,aa,ra}_mrr and _hits@K, the common-neighbour, Jaccard, Adamic-Adar and resource-allocation baselines ranked like --lp-ranking on the training graph (needs neither --lp-engine nor --lp-ranking)")
+    p.add_argument("--lp-walks", type=int, default=0, metavar="R",
+                   help="Cora_LP / CiteSeer_LP: the test record also carries test/{katz,ppr,hops}_mrr and _hits@K, the Katz index (beta 0.05), "
+                        "rooted PageRank (alpha 0.15) and hop-distance baselines with R rounds (1..64), ranked like --lp-heuristics on the "
+                        "training graph (needs neither --lp-engine nor --lp-ranking); 0 = off")
     p.add_argument("--device-metrics", action="store_true", help="batch scores (accuracy, F1, precision, recall, AUC) from integer counts made on the GPU instead of scikit-learn on host copies; same values")
     p.add_argument("--miner", choices=list(ops.MINER_IMPLS), default="matrix",
                    help="Cora_LP / CiteSeer_LP: the hard-negative miner's top-k kernel: matrix (n x n similarity in the workspace, n <= 65535), "
@@ -665,7 +695,7 @@ def config_from_args(a: argparse.Namespace) -> FinetuneConfig:
                           lp_engine=getattr(a, "lp_engine", False), gc_engine=getattr(a, "gc_engine", False),
                           engine_eval=getattr(a, "engine_eval", False), lp_ranking=getattr(a, "lp_ranking", False),
                           device_metrics=getattr(a, "device_metrics", False), miner_impl=getattr(a, "miner", "matrix"),
-                          repr_stats=getattr(a, "repr_stats", False), lp_heuristics=getattr(a, "lp_heuristics", False), wl_baseline=getattr(a, "wl_baseline", 0),
+                          repr_stats=getattr(a, "repr_stats", False), lp_heuristics=getattr(a, "lp_heuristics", False), lp_walks=getattr(a, "lp_walks", 0), wl_baseline=getattr(a, "wl_baseline", 0),
                           label_propagation=getattr(a, "label_propagation", 0),
                           **{p.field: getattr(a, p.field, 0) for p in PROBES})
 

@@ -1196,6 +1196,71 @@ def lp_cn_rank(rowptr: Tensor, col: Tensor, src: Tensor, dst: Tensor, weight: Op
     return score, n_greater, n_equal
 
 
+LP_WALK_MODES = {"sum": 0, "hops": 1}                       # gmp_lp_walk_score / gmp_lp_walk_rank (gnnmp.h)
+LP_WALK_MAX_ROUNDS = 64
+
+
+def _lp_walk_args(who: str, rowptr: Tensor, col: Tensor, rounds: int, damping: float, weight: Optional[Tensor], mode: str) -> Tuple[int, int, int]:
+    """(num_nodes, nnz, mode code) of a simple-graph CSR and its walk scorer (gnnmp.h gmp_lp_walk_score)."""
+    _need(rowptr, torch.int32, "rowptr", 1); _need(col, torch.int32, "col", 1)
+    if rowptr.numel() < 1:
+        raise L.GnnmpError(f"{who}: rowptr is empty (it has num_nodes + 1 entries)")
+    if mode not in LP_WALK_MODES:
+        raise L.GnnmpError(f"{who}: mode={mode!r} is not one of {tuple(LP_WALK_MODES)}")
+    if not 1 <= int(rounds) <= LP_WALK_MAX_ROUNDS:
+        raise L.GnnmpError(f"{who}: rounds={rounds} (1 <= rounds <= {LP_WALK_MAX_ROUNDS})")
+    if mode == "sum" and not 0.0 < float(damping) <= 1.0:
+        raise L.GnnmpError(f"{who}: damping={damping} (0 < damping <= 1)")
+    N = rowptr.numel() - 1
+    if weight is not None:
+        _need(weight, torch.float32, "weight", 1)
+        if mode == "hops":
+            raise L.GnnmpError(f"{who}: hops take no weight array")
+        if weight.numel() != N:
+            raise L.GnnmpError(f"{who}: weight has {weight.numel()} entries for {N} nodes")
+    return N, col.numel(), LP_WALK_MODES[mode]
+
+
+def lp_walk_score(rowptr: Tensor, col: Tensor, src: Tensor, dst: Tensor, rounds: int, damping: float = 1.0, weight: Optional[Tensor] = None,
+                  mode: str = "sum") -> Tensor:
+    """The walk score of every pair (src[p], dst[p]) on the simple undirected graph (rowptr, col) (int32 CSR, lp_cn_score's contract;
+    gnnmp.h gmp_lp_walk_score): mode "sum" the fp32 sum over l <= rounds of y_l[dst], y_l = damping * A diag(weight) y_{l-1} from y_0 =
+    e_src, every row folded in ascending neighbour order (weight None: 1); mode "hops" minus the BFS distance, -(rounds + 1) beyond
+    `rounds` hops.  An endpoint outside the graph scores 0 / -(rounds + 1).  Pairs with equal sources next to each other share one
+    propagation."""
+    N, nnz, code = _lp_walk_args("lp_walk_score", rowptr, col, rounds, damping, weight, mode)
+    _need(src, torch.int64, "src", 1); _need(dst, torch.int64, "dst", 1)
+    P, dev, l = src.numel(), rowptr.device, L.lib()
+    if dst.numel() != P:
+        raise L.GnnmpError("lp_walk_score: src and dst differ in length")
+    score = torch.empty(P, device=dev)
+    ws = _ws(l.gmp_lp_walk_workspace_bytes(P, N), dev)
+    L.check(l.gmp_lp_walk_score(_ptr(rowptr), _ptr(col), N, nnz, _ptr(src), _ptr(dst), P, _ptr(weight), float(damping), int(rounds), code,
+                                _ptr(score), _ptr(ws), ws.numel(), _stream(rowptr)), "gmp_lp_walk_score")
+    return score
+
+
+def lp_walk_rank(rowptr: Tensor, col: Tensor, src: Tensor, dst: Tensor, rounds: int, damping: float = 1.0, weight: Optional[Tensor] = None,
+                 mode: str = "sum", filter_rowptr: Optional[Tensor] = None, filter_col: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
+    """Every true pair (src[q], dst[q]) ranked against all nodes with lp_walk_score's scorer (gnnmp.h gmp_lp_walk_rank): returns
+    (score_true [Q], n_greater [Q] int32, n_equal [Q] int32) over the candidates c other than src[q], dst[q] and the entries of
+    src[q]'s row of the optional filter CSR (lp_rank's).  A candidate's score has the bits lp_walk_score gives the pair.  One workgroup
+    per query keeps its vectors in LDS (num_nodes <= gmp_lp_walk_lds_nodes()) or in a bounded workspace: nothing of size Q x N."""
+    N, nnz, code = _lp_walk_args("lp_walk_rank", rowptr, col, rounds, damping, weight, mode)
+    fnnz = _lp_filter_args("lp_walk_rank", N, filter_rowptr, filter_col)
+    _need(src, torch.int64, "src", 1); _need(dst, torch.int64, "dst", 1)
+    Q, dev, l = src.numel(), rowptr.device, L.lib()
+    if dst.numel() != Q:
+        raise L.GnnmpError("lp_walk_rank: src and dst differ in length")
+    score = torch.empty(Q, device=dev)
+    n_greater, n_equal = torch.empty(Q, dtype=torch.int32, device=dev), torch.empty(Q, dtype=torch.int32, device=dev)
+    ws = _ws(l.gmp_lp_walk_workspace_bytes(Q, N), dev)
+    L.check(l.gmp_lp_walk_rank(_ptr(rowptr), _ptr(col), N, nnz, _ptr(src), _ptr(dst), Q, _ptr(weight), float(damping), int(rounds), code,
+                               _ptr(filter_rowptr), _ptr(filter_col), fnnz, _ptr(score), _ptr(n_greater), _ptr(n_equal), _ptr(ws), ws.numel(),
+                               _stream(rowptr)), "gmp_lp_walk_rank")
+    return score, n_greater, n_equal
+
+
 def graph_simple_check(rowptr: Tensor, col: Tensor) -> Tensor:
     """int32 [1] on the device: how many entries of the int32 CSR (rowptr, col) keep it from being a simple undirected graph -- out of
     range, a self-loop, not greater than the entry before it in the row, or without the mirror entry (gnnmp.h gmp_graph_simple_check)."""

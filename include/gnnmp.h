@@ -393,6 +393,52 @@ int gmp_graph_simple_check(const int32_t* rowptr, const int32_t* col, int64_t nu
                            gmp_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
+ * Walk-based link-prediction baselines: the damped walk sum (Katz, rooted PageRank) and the hop distance, scored for explicit pairs or
+ * ranked under gmp_lp_rank's protocol (csrc/lp_walk.hip).  The graph is the CSR of a simple undirected graph, the contract of
+ * gmp_lp_cn_score above: a CSR that breaks it gives wrong numbers but nothing outside the arrays is read (rowptr is clamped to [0, nnz],
+ * entries outside [0, num_nodes) are skipped).
+ * Inputs: a source s, `rounds` R with 1 <= R <= 64, `damping` a (fp32, finite, 0 < a <= 1), an optional fp32 weight per node w (NULL = 1).
+ * mode 0, the walk sum:
+ *   y_0 = e_s and acc = 0.0f everywhere.
+ *   for l = 1 .. R and every node v:  t = 0.0f;  for z in N(v) in ASCENDING z: t = t + w[z] * y_{l-1}[z]  (a plain add of y_{l-1}[z] when
+ *   w is NULL);  y_l[v] = a * t;  acc[v] = acc[v] + y_l[v].
+ *   score(s, c) = acc[c].
+ *   Every multiply and add is rounded on its own (no fused multiply-add), subnormals are kept, there are no float atomics: a score is
+ *   bitwise reproducible, and the same pair has the same bits from gmp_lp_walk_score and as a candidate of gmp_lp_walk_rank.  All terms
+ *   are non-negative, so skipping zero terms or unreached rows changes no bit.  A source outside [0, num_nodes) has an all-zero acc.
+ *   With w = NULL and a = beta this is the truncated Katz index, the sum over l <= R of beta^l (A^l)[s, c]; with w[z] = 1 / deg z and
+ *   a = 1 - alpha it is the R-term rooted PageRank of s at c divided by alpha (the same order).  The caller computes w (the Python
+ *   layer: float64 on the host, rounded once) -- the kernel sees an array only.
+ * mode 1, hops: dist(s, c) the BFS distance in integers; score = -(float)dist if dist <= R, else -(float)(R + 1) (unreachable nodes and a
+ *   source or destination outside the graph included).  weight must be NULL and damping is ignored.  Not derived from acc > 0: an
+ *   underflow must not move a node.
+ * gmp_lp_walk_score: score [num_pairs]; a destination outside [0, num_nodes) scores 0 (mode 0) / -(R + 1) (mode 1).  Runs of equal
+ *   sources share one propagation.
+ * gmp_lp_walk_rank, for Q true pairs (src[q], dst[q]): score_true [Q] (gmp_lp_walk_score's), and over the candidates c in [0, num_nodes)
+ *   except c == src[q], c == dst[q] and the entries of src[q]'s filter row (gmp_lp_rank's filter CSR: unsorted rows, duplicates and
+ *   out-of-range entries allowed; both NULL = none): n_greater [Q] and n_equal [Q], int32, the filtered rank being 1 + n_greater +
+ *   n_equal / 2.  One workgroup per query stores its three outputs itself: no [Q, num_nodes] array, no output atomics, no memset.
+ * Storage: for num_nodes <= gmp_lp_walk_lds_nodes() the per-query vectors live in LDS and no workspace is needed (NULL is fine).  Beyond
+ *   it they live in `workspace`, gmp_lp_walk_workspace_bytes(Q, num_nodes) bytes, shared by at most gmp_lp_walk_resident_blocks()
+ *   workgroups that loop over the queries: the size does not grow with Q beyond that many and is at most resident_blocks *
+ *   (16 num_nodes + 4096).  Both paths run the same code and give the same bits.
+ * GMP_ERR_ARG: rounds outside [1, 64]; in mode 0 a damping that is NaN, <= 0 or > 1; a weight array with mode 1; mode outside {0, 1};
+ *   num_nodes or nnz outside [0, 2^31); a negative count; a null pointer; filter_rowptr without filter_col (or the reverse) with
+ *   filter_nnz != 0; a workspace that is too small.  num_pairs == 0 / num_queries == 0 return GMP_OK without a launch.  Asynchronous on
+ *   `stream`, no host read-back, no allocation.
+ * ------------------------------------------------------------------------- */
+int gmp_lp_walk_lds_nodes(void);
+int gmp_lp_walk_resident_blocks(void);
+size_t gmp_lp_walk_workspace_bytes(int64_t num_queries, int64_t num_nodes);
+int gmp_lp_walk_score(const int32_t* rowptr, const int32_t* col, int64_t num_nodes, int64_t nnz, const int64_t* src, const int64_t* dst,
+                      int64_t num_pairs, const float* weight, float damping, int rounds, int mode, float* score, void* workspace,
+                      size_t workspace_bytes, gmp_stream_t stream);
+int gmp_lp_walk_rank(const int32_t* rowptr, const int32_t* col, int64_t num_nodes, int64_t nnz, const int64_t* src, const int64_t* dst,
+                     int64_t num_queries, const float* weight, float damping, int rounds, int mode, const int32_t* filter_rowptr,
+                     const int32_t* filter_col, int64_t filter_nnz, float* score_true, int32_t* n_greater, int32_t* n_equal, void* workspace,
+                     size_t workspace_bytes, gmp_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
  * Streaming k-nearest neighbours in cosine similarity and the weighted k-NN vote on top of them (the k-NN probe of Wu et al. 2018 for
  * self-supervised embeddings): q [nq, dim] queries against db [ndb, dim] database rows, both contiguous fp32.  Rows are normalised as the
  * hard-negative miner does, z / max(||z||, 1e-12) with the stride padded with zeros, so a zero row scores 0 against everything and never
