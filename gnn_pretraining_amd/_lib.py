@@ -133,6 +133,9 @@ _SIGS: Dict[str, tuple] = {
     "gmp_lp_walk_workspace_bytes": (sz, [i64, i64]),
     "gmp_lp_walk_score": (C.c_int, [p, p, i64, i64, p, p, i64, p, f32, i32, i32, p, p, sz, p]),
     "gmp_lp_walk_rank": (C.c_int, [p, p, i64, i64, p, p, i64, p, f32, i32, i32, p, p, i64, p, p, p, p, sz, p]),
+    "gmp_emb_link_workspace_bytes": (sz, [i64, i64, i32]),
+    "gmp_emb_link_score": (C.c_int, [p, i64, i32, i32, p, p, i64, p, p, sz, p]),
+    "gmp_emb_link_rank": (C.c_int, [p, i64, i32, i32, p, p, i64, p, p, i64, p, p, p, p, p, sz, p]),
     "gmp_graph_simple_check": (C.c_int, [p, p, i64, i64, p, p]),
     "gmp_knn_workspace_bytes": (sz, [i64, i64, i32, i32]),
     "gmp_knn_topk": (C.c_int, [p, i64, p, i64, i32, i32, i32, p, p, p, p, sz, p]),

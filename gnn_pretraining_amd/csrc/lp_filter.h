@@ -1,4 +1,4 @@
-// The candidate filter shared by the all-candidate rankers (lp_rank.hip, lp_heuristics.hip, lp_walk.hip): a query with source s skips the entries of
+// The candidate filter shared by the all-candidate rankers (lp_rank.hip, lp_heuristics.hip, lp_walk.hip, emb_link.hip): a query with source s skips the entries of
 // row s of an optional filter CSR (int32 rowptr / col, any order, duplicates allowed).  A block that walks the candidates
 // [c0, c0 + 32 W) keeps the row as a bitmap of W words in LDS; what it counts or compares belongs to each kernel.
 #pragma once
@@ -29,6 +29,21 @@ __device__ __forceinline__ void mark(const int32_t* __restrict__ rowptr, const i
         for (int64_t i = b + threadIdx.x; i < e; i += threads) {
             const uint64_t off = (uint64_t)((int64_t)col[i] - c0);
             if (off < (uint64_t)(32 * words)) atomicOr(&bits[off >> 5], 1u << (unsigned)(off & 31));
+        }
+    }
+}
+
+// The marking for a block that walks the candidates [c0, c0 + width) for MANY queries at once and lays its bitmap out itself (emb_link.hip:
+// one bit per (query row, candidate)): set(off) for every entry c0 + off of row s that falls into the window, same clamps as above.  The
+// threads that share the row call it with first = 0 .. step - 1.
+template <typename F>
+__device__ __forceinline__ void mark_each(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, int64_t nnz, int64_t s, int64_t N,
+                                          int64_t c0, int64_t width, int first, int step, F&& set) {
+    if (rowptr && s >= 0 && s < N) {
+        const int64_t b = max((int64_t)rowptr[s], (int64_t)0), e = min((int64_t)rowptr[s + 1], nnz);
+        for (int64_t i = b + first; i < e; i += step) {
+            const uint64_t off = (uint64_t)((int64_t)col[i] - c0);
+            if (off < (uint64_t)width) set((int)off);
         }
     }
 }

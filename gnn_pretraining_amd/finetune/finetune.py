@@ -4,7 +4,7 @@ test metrics from the best checkpoint.  Data come from the loaders of gnn_pretra
 data/processed; synthetic stand-ins are generated when none were exported).  wandb is replaced by a JSONL logger with the
 same metric keys.  Build-only flags: --epochs, --device, --data-root, --data-scale, --log, --sparse-features, --lp-engine, --gc-engine,
 --engine-eval, --lp-ranking, --device-metrics, --miner, --knn-probe, --cluster-probe, --logreg-probe, --repr-stats, --lp-heuristics,
---wl-baseline, --label-propagation."""
+--wl-baseline, --label-propagation, --link-probe."""
 from __future__ import annotations
 
 import argparse
@@ -156,6 +156,7 @@ class FinetuneConfig:
     repr_stats: bool = False            # on an engine: the label-free statistics of the validation embeddings (repr_stats.embedding_stats: val/repr_uniformity, val/repr_mean_cosine, val/repr_rankme); every domain, link prediction included
     label_propagation: int = 0          # node-classification domains: rounds of the label-spreading and label-propagation baselines on the raw graph (node_baselines.py: test/labelspread_accuracy, test/labelprop_accuracy and their _unreached counts); needs no engine and no probe; 0 = off
     lp_walks: int = 0                   # link-prediction domains: rounds of the walk-based baselines; the test record also carries test/{katz,ppr,hops}_mrr / _hits@K, ranked like lp_heuristics on the message-passing graph (link_walks.py); needs no engine; 0 = off
+    link_probe: bool = False            # link-prediction domains on the engine: the parameter-free embedding link probe (link_probe.py): val/embed_{cos,dot}_mrr / _auc every epoch and once before training, test/embed_{cos,dot}_mrr / _hits@K / _auc
     wl_baseline: int = 0                # graph-classification domains: rounds of the Weisfeiler-Lehman subtree baseline on the raw graphs (graph_baselines.py: test/wl_knn_accuracy, test/wl_logreg_accuracy); needs no engine and no probe; 0 = off
 
     def __post_init__(self) -> None:
@@ -189,6 +190,11 @@ class FinetuneConfig:
                              + {"node_classification": "the node engine is switched off (GMP_FINETUNE_ENGINE=0)",
                                 "link_prediction": "pass lp_engine (--lp-engine)",
                                 "graph_classification": "pass gc_engine (--gc-engine)"}[TASK_TYPES[self.domain_name]])
+        if self.link_probe and TASK_TYPES[self.domain_name] != "link_prediction":
+            raise ValueError(f"link_probe applies to the link-prediction domains (Cora_LP / CiteSeer_LP), not to {self.domain_name}")
+        if self.link_probe and not engine_active(self):
+            raise ValueError(f"link_probe needs an active fine-tune engine for {self.domain_name} (it reads the engine's eval-mode embed()): "
+                             "pass lp_engine (--lp-engine)")
         if self.lp_ranking and not self.lp_engine:
             raise ValueError("lp_ranking ranks with the link-prediction engine (gmp_lp_rank): pass lp_engine (--lp-engine)")
         if self.lp_heuristics and TASK_TYPES[self.domain_name] != "link_prediction":
@@ -423,14 +429,18 @@ def evaluate_engine(engine, loader, device, cfg: FinetuneConfig, prefix: str) ->
     return out
 
 
+def _known_positives(train_loader, val_loader, test_loader, device) -> Tensor:
+    """The filter of the ranking evaluations: the known positives of the three splits, in both directions (the graphs are undirected)."""
+    known = torch.cat([train_loader.dataset.train_edges, val_loader.dataset.pos_edges, test_loader.dataset.pos_edges], dim=1).to(device)
+    return torch.cat([known, known.flip(0)], dim=1).contiguous()
+
+
 def rank_test_edges(engine, train_loader, val_loader, test_loader, device) -> Dict[str, float]:
     """The filtered ranking evaluation of link prediction (cfg.lp_ranking): every true test edge (s, d) is ranked among all nodes as
     destinations of s, the known positives of the three splits (either direction: the graphs are undirected) filtered out; MRR and
     Hits@K over those ranks.  One embed(), one LinkPredictionEngine.rank()."""
     pos = test_loader.dataset.pos_edges.to(device).contiguous()
-    known = torch.cat([train_loader.dataset.train_edges, val_loader.dataset.pos_edges, test_loader.dataset.pos_edges], dim=1).to(device)
-    known = torch.cat([known, known.flip(0)], dim=1).contiguous()
-    ranks = engine.rank(pos, filter_edges=known).rank
+    ranks = engine.rank(pos, filter_edges=_known_positives(train_loader, val_loader, test_loader, device)).rank
     return {f"test/{k}": v for k, v in ranking_metrics(ranks).items()}
 
 
@@ -440,9 +450,7 @@ def _structural_ranking_inputs(train_loader, val_loader, test_loader, device):
     data = train_loader.dataset
     graph = data.train_edges.to(device).contiguous()
     pos = test_loader.dataset.pos_edges.to(device).contiguous()
-    known = torch.cat([data.train_edges, val_loader.dataset.pos_edges, test_loader.dataset.pos_edges], dim=1).to(device)
-    known = torch.cat([known, known.flip(0)], dim=1).contiguous()
-    return graph, data.data.num_nodes, pos, known
+    return graph, data.data.num_nodes, pos, _known_positives(train_loader, val_loader, test_loader, device)
 
 
 def rank_test_edges_heuristics(train_loader, val_loader, test_loader, device) -> Dict[str, float]:
@@ -516,18 +524,39 @@ def repr_stats_keys(emb: Tensor) -> Dict[str, float]:
     return {f"val/repr_{k}": v for k, v in RS.embedding_stats(emb.contiguous()).items()}
 
 
-def run_probes(engine, train_loader, loader, device, cfg: FinetuneConfig, prefix: str) -> Dict[str, float]:
+LINK_PROBE_VAL = ("mrr", "auc")          # of link_probe's five scores per kind, those the validation record carries
+
+
+def link_probe_keys(emb: Tensor, loader, known: Tensor, device, prefix: str) -> Dict[str, float]:
+    """cfg.link_probe: the embedding link probe (link_probe.link_probe) on `loader`'s split as it is logged under `prefix`.  The ranking
+    is rank_test_edges's protocol with the cosine / the inner product in place of the trained scorer -- every true edge (s, d) of the
+    split ranked as a destination of s among all nodes, `known` (_known_positives) filtered out -- and the AUC is over the positive and
+    negative pairs and labels that evaluate() scores for the split.  The test record carries all five scores per kind, the validation
+    record LINK_PROBE_VAL."""
+    from . import link_probe as LPR
+    ds = loader.dataset
+    scores = LPR.link_probe(emb, ds.pos_edges.to(device).contiguous(), known, ds.edges.to(device).contiguous(), ds.labels.to(device))
+    keep = None if prefix == "test" else tuple(f"_{k}" for k in LINK_PROBE_VAL)
+    return {f"{prefix}/{k}": v for k, v in scores.items() if keep is None or k.endswith(keep)}
+
+
+def run_probes(engine, train_loader, loader, device, cfg: FinetuneConfig, prefix: str, known: Optional[Tensor] = None) -> Dict[str, float]:
     """The scores of every active probe (PROBES, in that order) on `loader`'s split, keyed as they are logged under `prefix` ("val" /
     "test").  One probe_embeddings pass serves them all; the train split is embedded only when an active probe fits on it.  With
     cfg.repr_stats the validation split's rows of that same pass (on a link-prediction domain, which has no probes: every row of the
-    engine's embed()) also give val/repr_*."""
+    engine's embed()) also give val/repr_*.  With cfg.link_probe (link-prediction domains; `known` is the ranking filter) that one
+    embed() also serves link_probe_keys."""
     active = [p for p in PROBES if getattr(cfg, p.field)]
     want_repr = cfg.repr_stats and prefix == "val"
-    if not active and not want_repr:
+    if not active and not want_repr and not cfg.link_probe:
         return {}
     if cfg.task_type == "link_prediction":
         with torch.no_grad():
-            return repr_stats_keys(engine.embed())
+            emb = engine.embed()
+            out = repr_stats_keys(emb) if want_repr else {}
+            if cfg.link_probe:
+                out.update(link_probe_keys(emb, loader, known, device, prefix))
+            return out
     with_train = any(p.needs_train for p in active)
     sets = probe_embeddings(engine, ((train_loader.dataset,) if with_train else ()) + (loader.dataset,), device, cfg)
     out = {}
@@ -594,12 +623,15 @@ def finetune(cfg: FinetuneConfig, epochs: Optional[int] = None, device: Optional
         if eval_engine is None:
             raise ValueError(f"engine_eval needs an active fine-tune engine for {cfg.domain_name}")
     probe_engine = node_engine or gc_engine or lp_engine     # (a configuration with a probe or repr_stats on has one: __post_init__)
-    before = run_probes(probe_engine, train_loader, val_loader, dev, cfg, "val")     # the embeddings before any training
+    known = _known_positives(train_loader, val_loader, test_loader, dev) if cfg.link_probe else None
+    before = run_probes(probe_engine, train_loader, val_loader, dev, cfg, "val", known)      # the embeddings before any training
     for p in PROBES:                                         # one line per active probe
         if getattr(cfg, p.field):
             logger.log({k: v for k, v in before.items() if k.startswith(f"val/{p.name}_")}, 0)
     if cfg.repr_stats:
         logger.log({k: v for k, v in before.items() if k.startswith("val/repr_")}, 0)
+    if cfg.link_probe:
+        logger.log({k: v for k, v in before.items() if k.startswith("val/embed_")}, 0)
     for epoch in range(1, (epochs or cfg.epochs) + 1):
         if node_engine is not None:
             run_training_node_engine(node_engine, train_loader, dev, epoch, global_step, cfg, logger)
@@ -617,7 +649,7 @@ def finetune(cfg: FinetuneConfig, epochs: Optional[int] = None, device: Optional
             val = compute_validation_metrics(evaluate_engine(eval_engine, val_loader, dev, cfg, "val"), epoch)
         else:
             val = compute_validation_metrics(evaluate(model, val_loader, dev, cfg, "val", miner, edges), epoch)
-        val.update(run_probes(probe_engine, train_loader, val_loader, dev, cfg, "val"))
+        val.update(run_probes(probe_engine, train_loader, val_loader, dev, cfg, "val", known))
         if val[key] > best:
             best, stale = val[key], 0
             torch.save({"epoch": epoch, "model_state_dict": model.state_dict(), "val_metrics": val}, path)
@@ -632,7 +664,7 @@ def finetune(cfg: FinetuneConfig, epochs: Optional[int] = None, device: Optional
     else:
         test_batches = evaluate(model, test_loader, dev, cfg, "test", miner, _train_edges(train_loader, dev))
     test = compute_test_metrics(test_batches, epoch, stale, start, model)
-    test.update(run_probes(probe_engine, train_loader, test_loader, dev, cfg, "test"))
+    test.update(run_probes(probe_engine, train_loader, test_loader, dev, cfg, "test", known))
     if cfg.lp_ranking:
         test.update(rank_test_edges(lp_engine, train_loader, val_loader, test_loader, dev))
     if cfg.lp_heuristics:
@@ -670,6 +702,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help="Cora_LP / CiteSeer_LP: the test record also carries test/{katz,ppr,hops}_mrr and _hits@K, the Katz index (beta 0.05), "
                         "rooted PageRank (alpha 0.15) and hop-distance baselines with R rounds (1..64), ranked like --lp-heuristics on the "
                         "training graph (needs neither --lp-engine nor --lp-ranking); 0 = off")
+    p.add_argument("--link-probe", action="store_true",
+                   help="with --lp-engine: also log val/embed_{cos,dot}_mrr and _auc (every epoch and once before training) and "
+                        "test/embed_{cos,dot}_mrr, _hits@K and _auc, the parameter-free embedding link probe: pairs scored by the cosine / the "
+                        "inner product of the backbone's embeddings, ranked like --lp-ranking, AUC over the split's labelled pairs")
     p.add_argument("--device-metrics", action="store_true", help="batch scores (accuracy, F1, precision, recall, AUC) from integer counts made on the GPU instead of scikit-learn on host copies; same values")
     p.add_argument("--miner", choices=list(ops.MINER_IMPLS), default="matrix",
                    help="Cora_LP / CiteSeer_LP: the hard-negative miner's top-k kernel: matrix (n x n similarity in the workspace, n <= 65535), "
@@ -696,7 +732,7 @@ def config_from_args(a: argparse.Namespace) -> FinetuneConfig:
                           engine_eval=getattr(a, "engine_eval", False), lp_ranking=getattr(a, "lp_ranking", False),
                           device_metrics=getattr(a, "device_metrics", False), miner_impl=getattr(a, "miner", "matrix"),
                           repr_stats=getattr(a, "repr_stats", False), lp_heuristics=getattr(a, "lp_heuristics", False), lp_walks=getattr(a, "lp_walks", 0), wl_baseline=getattr(a, "wl_baseline", 0),
-                          label_propagation=getattr(a, "label_propagation", 0),
+                          label_propagation=getattr(a, "label_propagation", 0), link_probe=getattr(a, "link_probe", False),
                           **{p.field: getattr(a, p.field, 0) for p in PROBES})
 
 

@@ -1261,6 +1261,60 @@ def lp_walk_rank(rowptr: Tensor, col: Tensor, src: Tensor, dst: Tensor, rounds: 
     return score, n_greater, n_equal
 
 
+EMB_LINK_MODES = {"cos": 0, "dot": 1}                       # gmp_emb_link_score / gmp_emb_link_rank (gnnmp.h)
+EMB_LINK_MAX_DIM = 256
+
+
+def _emb_link_args(who: str, h: Tensor, src: Tensor, dst: Tensor, mode: str) -> Tuple[int, int, int]:
+    """(num_nodes, number of pairs, mode code) of an embedding matrix and its pairs (gnnmp.h gmp_emb_link_score)."""
+    if mode not in EMB_LINK_MODES:
+        raise L.GnnmpError(f"{who}: mode={mode!r} is not one of {tuple(EMB_LINK_MODES)}")
+    _need(h, torch.float32, "h", 2)
+    _need(src, torch.int64, "src", 1); _need(dst, torch.int64, "dst", 1)
+    if not 1 <= h.size(1) <= EMB_LINK_MAX_DIM:
+        raise L.GnnmpError(f"{who}: dim={h.size(1)} (1 <= dim <= {EMB_LINK_MAX_DIM})")
+    if dst.numel() != src.numel():
+        raise L.GnnmpError(f"{who}: src and dst differ in length")
+    return h.size(0), src.numel(), EMB_LINK_MODES[mode]
+
+
+def emb_link_score(h: Tensor, src: Tensor, dst: Tensor, mode: str = "cos") -> Tensor:
+    """The score of every pair (src[p], dst[p]) from the rows of h [N, d <= 256] alone (gnnmp.h gmp_emb_link_score; csrc/emb_link.hip):
+    mode "cos" the cosine of the two rows, normalised as knn_topk normalises (a zero row scores 0), mode "dot" their inner product.  An
+    endpoint outside [0, N) reads as a zero row.  Returns score [P]."""
+    N, P, code = _emb_link_args("emb_link_score", h, src, dst, mode)
+    dev, l = h.device, L.lib()
+    score = torch.empty(P, device=dev)
+    ws = _ws(l.gmp_emb_link_workspace_bytes(N, P, h.size(1)), dev)
+    L.check(l.gmp_emb_link_score(_ptr(h), N, h.size(1), code, _ptr(src), _ptr(dst), P, _ptr(score), _ptr(ws), ws.numel(), _stream(h)),
+            "gmp_emb_link_score")
+    return score
+
+
+def emb_link_rank(h: Tensor, src: Tensor, dst: Tensor, mode: str = "cos", filter_rowptr: Optional[Tensor] = None,
+                  filter_col: Optional[Tensor] = None, filter_edges: Optional[Tensor] = None, return_matrix: bool = False):
+    """Every true pair (src[q], dst[q]) ranked against all nodes with emb_link_score's scorer (gnnmp.h gmp_emb_link_rank): returns
+    (score_true [Q], n_greater [Q] int32, n_equal [Q] int32) over the candidates c other than src[q], dst[q] and the entries of
+    src[q]'s row of the optional filter -- a CSR (lp_rank's: int32 rowptr [N + 1] / col, row = source) or filter_edges int64 [2, E]
+    (source, destination), turned into that CSR by csr_build.  A candidate's score has the bits emb_link_score gives the pair.  Nothing
+    of size Q x N is allocated unless return_matrix asks for every score as the compare saw it (a fourth result, tests only)."""
+    N, Q, code = _emb_link_args("emb_link_rank", h, src, dst, mode)
+    if filter_edges is not None:
+        if filter_rowptr is not None or filter_col is not None:
+            raise L.GnnmpError("emb_link_rank: pass the filter as a CSR or as filter_edges, not both")
+        csr = csr_build(filter_edges, N)
+        filter_rowptr, filter_col = csr.rowptr_t, csr.col_t
+    fnnz = _lp_filter_args("emb_link_rank", N, filter_rowptr, filter_col)
+    dev, l = h.device, L.lib()
+    score = torch.empty(Q, device=dev)
+    n_greater, n_equal = torch.empty(Q, dtype=torch.int32, device=dev), torch.empty(Q, dtype=torch.int32, device=dev)
+    mat = torch.empty(Q, N, device=dev) if return_matrix else None
+    ws = _ws(l.gmp_emb_link_workspace_bytes(N, Q, h.size(1)), dev)
+    L.check(l.gmp_emb_link_rank(_ptr(h), N, h.size(1), code, _ptr(src), _ptr(dst), Q, _ptr(filter_rowptr), _ptr(filter_col), fnnz, _ptr(score),
+                                _ptr(n_greater), _ptr(n_equal), _ptr(mat), _ptr(ws), ws.numel(), _stream(h)), "gmp_emb_link_rank")
+    return (score, n_greater, n_equal, mat) if return_matrix else (score, n_greater, n_equal)
+
+
 def graph_simple_check(rowptr: Tensor, col: Tensor) -> Tensor:
     """int32 [1] on the device: how many entries of the int32 CSR (rowptr, col) keep it from being a simple undirected graph -- out of
     range, a self-loop, not greater than the entry before it in the row, or without the mirror entry (gnnmp.h gmp_graph_simple_check)."""

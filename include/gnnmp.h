@@ -467,6 +467,38 @@ int gmp_knn_vote(const int64_t* idx, const float* sim, int64_t nq, int k, const 
                  float temperature, float* class_scores, int64_t* pred, int32_t* status, gmp_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
+ * The embedding link probe: a pair of nodes scored from the rows of an embedding matrix alone, for explicit pairs or ranked against all
+ * nodes under gmp_lp_rank's protocol (csrc/emb_link.hip).  No parameters, no fitting, no random state.
+ * Inputs: h [num_nodes, dim] contiguous fp32, 1 <= dim <= 256.
+ * mode 0, cosine: rows normalised exactly as gmp_knn_topk normalises, z / max(||z||, 1e-12) with the stride padded with zeros to a
+ *   multiple of 4; a zero row scores 0 against everything.
+ * mode 1, inner product: the raw rows in the same padded copy, without the division.
+ * The score of a pair (s, c) is one k-ordered fp32 MFMA chain of row s against row c (csrc/sim_tile.h): its bits depend on neither the
+ *   grid nor the other pairs, so the same pair has the same bits from gmp_emb_link_score, as score_true, as a candidate inside
+ *   gmp_emb_link_rank and in matrix_out; in mode 0 they are the bits gmp_knn_topk's matrix_out has for the query row h[s] against the
+ *   database row c.  A src or dst outside [0, num_nodes) reads as a zero row (score +0.0f); such a source has an empty filter row.
+ * gmp_emb_link_score: score [num_pairs].
+ * gmp_emb_link_rank, for Q true pairs (src[q], dst[q]): score_true [Q], and over the candidates c in [0, num_nodes) except c == src[q],
+ *   c == dst[q] and the entries of src[q]'s filter row (gmp_lp_rank's filter CSR: unsorted rows, duplicates and out-of-range entries
+ *   allowed; both NULL = none): n_greater [Q] and n_equal [Q], int32, zeroed inside the call, scores compared as IEEE floats (>, ==); the
+ *   filtered rank is 1 + n_greater + n_equal / 2.  Counts are integer sums: they do not depend on the block order.
+ *   matrix_out: NULL or [Q, num_nodes], every score exactly as the compare saw it (the filtered and the self columns included) -- test /
+ *   diagnostic hook that changes no other output bit.  No [Q, num_nodes] array exists unless it is given.
+ * GMP_ERR_ARG: dim outside [1, 256]; mode outside {0, 1}; num_nodes or a count outside [0, 2^31); a negative filter_nnz; a null required
+ *   pointer; filter_rowptr without filter_col (or the reverse) with filter_nnz != 0; (query tiles of 128) x (candidate chunks) beyond one
+ *   grid of 2^31 - 1 blocks.  GMP_ERR_WORKSPACE when workspace_bytes < gmp_emb_link_workspace_bytes(num_nodes, count, dim) =
+ *   256 + 4 num_nodes dpad rounded up to 256 bytes, dpad = dim rounded up to 4: the padded copy of h (it does not grow with the count);
+ *   0 for sizes outside the ranges.  Nothing is launched in an error case.  num_pairs == 0 / num_queries == 0 return GMP_OK without a
+ *   launch.  Asynchronous on `stream`, no host read-back, no allocation, no global state, no float atomics.
+ * ------------------------------------------------------------------------- */
+size_t gmp_emb_link_workspace_bytes(int64_t num_nodes, int64_t num_queries, int dim);
+int gmp_emb_link_score(const float* h, int64_t num_nodes, int dim, int mode, const int64_t* src, const int64_t* dst, int64_t num_pairs,
+                       float* score, void* workspace, size_t workspace_bytes, gmp_stream_t stream);
+int gmp_emb_link_rank(const float* h, int64_t num_nodes, int dim, int mode, const int64_t* src, const int64_t* dst, int64_t num_queries,
+                      const int32_t* filter_rowptr, const int32_t* filter_col, int64_t filter_nnz, float* score_true, int32_t* n_greater,
+                      int32_t* n_equal, float* matrix_out, void* workspace, size_t workspace_bytes, gmp_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
  * Spherical k-means (k-means in cosine similarity on L2-normalised rows, the clustering probe for self-supervised embeddings) and the
  * integer contingency table its scores are computed from: x [n, dim] rows against kc centroids [kc, dim], contiguous fp32.  Rows and
  * centroids are normalised as gmp_knn_topk does, z / max(||z||, 1e-12) with the stride padded with zeros (a zero row scores 0 against every
