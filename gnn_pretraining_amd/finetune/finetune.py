@@ -4,7 +4,7 @@ test metrics from the best checkpoint.  Data come from the loaders of gnn_pretra
 data/processed; synthetic stand-ins are generated when none were exported).  wandb is replaced by a JSONL logger with the
 same metric keys.  Build-only flags: --epochs, --device, --data-root, --data-scale, --log, --sparse-features, --lp-engine, --gc-engine,
 --engine-eval, --lp-ranking, --device-metrics, --miner, --knn-probe, --cluster-probe, --logreg-probe, --repr-stats, --lp-heuristics,
---wl-baseline, --label-propagation, --link-probe."""
+--wl-baseline, --label-propagation, --link-probe, --sgc-baseline."""
 from __future__ import annotations
 
 import argparse
@@ -157,6 +157,7 @@ class FinetuneConfig:
     label_propagation: int = 0          # node-classification domains: rounds of the label-spreading and label-propagation baselines on the raw graph (node_baselines.py: test/labelspread_accuracy, test/labelprop_accuracy and their _unreached counts); needs no engine and no probe; 0 = off
     lp_walks: int = 0                   # link-prediction domains: rounds of the walk-based baselines; the test record also carries test/{katz,ppr,hops}_mrr / _hits@K, ranked like lp_heuristics on the message-passing graph (link_walks.py); needs no engine; 0 = off
     link_probe: bool = False            # link-prediction domains on the engine: the parameter-free embedding link probe (link_probe.py): val/embed_{cos,dot}_mrr / _auc every epoch and once before training, test/embed_{cos,dot}_mrr / _hits@K / _auc
+    sgc_baseline: int = 0               # node-classification domains: K of the SGC baseline S^K X and, beside it, the raw-feature baseline, both a softmax regression fitted on the train split (node_baselines.py: test/rawfeat_accuracy, test/sgc_accuracy); needs no engine and no probe; 0 = off
     wl_baseline: int = 0                # graph-classification domains: rounds of the Weisfeiler-Lehman subtree baseline on the raw graphs (graph_baselines.py: test/wl_knn_accuracy, test/wl_logreg_accuracy); needs no engine and no probe; 0 = off
 
     def __post_init__(self) -> None:
@@ -211,6 +212,10 @@ class FinetuneConfig:
             raise ValueError(f"label_propagation={self.label_propagation} (the number of propagation rounds, 1 <= rounds <= {ops.LABELPROP_MAX_ROUNDS}; 0 switches the baselines off)")
         if self.label_propagation and TASK_TYPES[self.domain_name] != "node_classification":
             raise ValueError(f"label_propagation applies to the node-classification domains (Cora_NC / CiteSeer_NC), not to {self.domain_name}")
+        if not 0 <= self.sgc_baseline <= ops.FEATPROP_MAX_ROUNDS:
+            raise ValueError(f"sgc_baseline={self.sgc_baseline} (the number of propagation rounds, 1 <= rounds <= {ops.FEATPROP_MAX_ROUNDS}; 0 switches the baselines off)")
+        if self.sgc_baseline and TASK_TYPES[self.domain_name] != "node_classification":
+            raise ValueError(f"sgc_baseline applies to the node-classification domains (Cora_NC / CiteSeer_NC), not to {self.domain_name}")
         self.exp_name = f"{self.domain_name}_{self.finetune_strategy}_{self.pretrained_scheme}"
         self.task_type = TASK_TYPES[self.domain_name]
         self.batch_size = BATCH_SIZES[self.domain_name]
@@ -498,6 +503,17 @@ def label_baseline_keys(train_loader, test_loader, device, cfg: FinetuneConfig) 
     return {f"test/{k}": v for k, v in scores.items()}
 
 
+def feature_baseline_keys(train_loader, test_loader, device, cfg: FinetuneConfig) -> Dict[str, float]:
+    """cfg.sgc_baseline: what test/accuracy has to beat on a node-classification domain once the features are read -- a softmax regression
+    on the raw features and SGC, the same regression on S^K X with K = cfg.sgc_baseline, fitted on the train split's rows and scored on the
+    test split (node_baselines.feature_baselines).  Reads the datasets and nothing else: no model, no generator, no dropout counter, no
+    BatchNorm state."""
+    from . import node_baselines as NB
+    train, test = train_loader.dataset, test_loader.dataset
+    scores = NB.feature_baselines(train.data, train.indices, test.indices, NUM_CLASSES[cfg.domain_name], cfg.sgc_baseline, device=device)
+    return {f"test/{k}": v for k, v in scores.items()}
+
+
 def probe_embeddings(engine, datasets, device, cfg: FinetuneConfig):
     """What the probes score: per dataset (a split) its rows of the engine's eval-mode backbone output as the parameters stand now and
     their labels, both on the device -- node embeddings for node classification (one embed(), every split's rows gathered from it),
@@ -675,6 +691,8 @@ def finetune(cfg: FinetuneConfig, epochs: Optional[int] = None, device: Optional
         test.update(wl_baseline_keys(train_loader, test_loader, dev, cfg))
     if cfg.label_propagation:
         test.update(label_baseline_keys(train_loader, test_loader, dev, cfg))
+    if cfg.sgc_baseline:
+        test.update(feature_baseline_keys(train_loader, test_loader, dev, cfg))
     logger.log(test, global_step[0])
     print(f"{cfg.exp_name}: best {key} {best:.4f}, test/accuracy {test['test/accuracy']:.4f}, test/auc {test['test/auc']:.4f}, "
           f"training_time {test['test/training_time']:.2f}s, saved {path}")
@@ -718,6 +736,11 @@ def build_parser() -> argparse.ArgumentParser:
                    help="Cora_NC / CiteSeer_NC: the test record also carries test/labelspread_accuracy, test/labelprop_accuracy and their "
                         "_unreached counts, label spreading (alpha 0.9) and label propagation with T rounds (1..10000) over the raw graph, "
                         "seeded with the train split's labels and scored on the test split (needs neither an engine nor a probe flag); 0 = off")
+    p.add_argument("--sgc-baseline", type=int, default=0, metavar="K",
+                   help="Cora_NC / CiteSeer_NC: the test record also carries test/rawfeat_accuracy and test/sgc_accuracy, a softmax regression "
+                        "on the raw features and SGC (the same regression on S^K X, K rounds 1..64 of the degree-scaled propagation with "
+                        "self-loops), fitted on the train split and scored on the test split (needs neither an engine nor a probe flag; "
+                        "combines with --label-propagation and --sparse-features); 0 = off")
     for probe in PROBES:
         p.add_argument(probe.flag, type=int, default=0, metavar=probe.metavar, help=probe.help)
     p.add_argument("--repr-stats", action="store_true",
@@ -732,7 +755,7 @@ def config_from_args(a: argparse.Namespace) -> FinetuneConfig:
                           engine_eval=getattr(a, "engine_eval", False), lp_ranking=getattr(a, "lp_ranking", False),
                           device_metrics=getattr(a, "device_metrics", False), miner_impl=getattr(a, "miner", "matrix"),
                           repr_stats=getattr(a, "repr_stats", False), lp_heuristics=getattr(a, "lp_heuristics", False), lp_walks=getattr(a, "lp_walks", 0), wl_baseline=getattr(a, "wl_baseline", 0),
-                          label_propagation=getattr(a, "label_propagation", 0), link_probe=getattr(a, "link_probe", False),
+                          label_propagation=getattr(a, "label_propagation", 0), sgc_baseline=getattr(a, "sgc_baseline", 0), link_probe=getattr(a, "link_probe", False),
                           **{p.field: getattr(a, p.field, 0) for p in PROBES})
 
 

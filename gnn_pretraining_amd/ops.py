@@ -1781,6 +1781,63 @@ def label_propagate(rowptr: Tensor, col: Tensor, f0: Tensor, rounds: int, alpha:
     return LabelPropagation(out, pred, status, residual)
 
 
+FEATPROP_MAX_DIM = 16384                                           # gmp_feature_propagate (gnnmp.h)
+FEATPROP_MAX_ROUNDS = 64
+
+
+class FeaturePropagation(NamedTuple):
+    """feature_propagate's outputs (gnnmp.h gmp_feature_propagate)."""
+    out: Tensor                    # fp32 [n, d]: H after the last round
+    status: Tensor                 # int32 [2]: CSR entries outside [0, n) (skipped), feature entries that break the CSR form (skipped)
+
+
+def feature_propagate(rowptr: Tensor, col: Tensor, x, rounds: int, left: Optional[Tensor] = None, right: Optional[Tensor] = None,
+                      out: Optional[Tensor] = None) -> FeaturePropagation:
+    """`rounds` rounds of H <- left[i] * (sum over the row's entries j, in order, of right[j] * H[j]) from H = x, one launch per round and
+    no host synchronisation (gnnmp.h gmp_feature_propagate holds the definition; csrc/feature_prop.hip).  (rowptr, col) an int32 CSR over
+    n nodes; x a dense fp32 [n, d] tensor with contiguous rows (any leading dimension) or a graph.SparseFeatures, 1 <= d <= 16384,
+    1 <= rounds <= 64; left / right fp32 [n] or None (ones); out (allocated when None) fp32 [n, d] with contiguous rows, not overlapping
+    x -- its padding columns are left alone.  Every multiply and add is rounded on its own in a fixed order: the bits are reproducible,
+    the CSR form gives the bits of the dense form on to_dense(), and `rounds` rounds equal `rounds` chained calls of one.  Returns
+    FeaturePropagation(out, status); status stays on the device."""
+    from .graph import SparseFeatures
+    _need(rowptr, torch.int32, "rowptr", 1); _need(col, torch.int32, "col", 1)
+    sparse = isinstance(x, SparseFeatures)
+    if sparse:
+        _sparse_ok(x)
+    elif isinstance(x, Tensor):
+        _need_rows(x, "x")
+    else:
+        raise L.GnnmpError(f"feature_propagate: x must be a dense fp32 tensor or SparseFeatures, got {type(x).__name__}")
+    n, d, dev = rowptr.numel() - 1, int(x.shape[1]), rowptr.device
+    if n < 0 or x.shape[0] != n:
+        raise L.GnnmpError(f"feature_propagate: rowptr has {rowptr.numel()} entries for the {x.shape[0]} rows of x (n + 1 entries)")
+    if not 1 <= d <= FEATPROP_MAX_DIM or not 1 <= int(rounds) <= FEATPROP_MAX_ROUNDS:
+        raise L.GnnmpError(f"feature_propagate: d={d} rounds={rounds} (1 <= d <= {FEATPROP_MAX_DIM}, 1 <= rounds <= {FEATPROP_MAX_ROUNDS})")
+    for t, name in ((left, "left"), (right, "right")):
+        if t is not None:
+            _need(t, torch.float32, name, 1)
+            if t.numel() != n:
+                raise L.GnnmpError(f"feature_propagate: {name} has {t.numel()} entries for {n} nodes")
+    if out is None:
+        out = torch.empty(n, d, device=dev)
+    else:
+        _need_rows(out, "out")
+        if tuple(out.shape) != (n, d):
+            raise L.GnnmpError(f"feature_propagate: out {tuple(out.shape)} against x {(n, d)}")
+    inputs = (col, left, right, out) + ((x.rowptr, x.col, x.val) if sparse else (x,))
+    if any(t is not None and t.device != dev for t in inputs):
+        raise L.GnnmpError("feature_propagate: every input must be on one device")
+    rounds, l = int(rounds), L.lib()
+    status = torch.zeros(2, dtype=torch.int32, device=dev)
+    ld = lambda t: t.stride(0) if t.size(0) > 1 else t.size(1)                     # noqa: E731
+    ws = _ws(l.gmp_feature_propagate_workspace_bytes(n, d, rounds), dev)
+    feat_args = (None, 0, _ptr(x.rowptr), _ptr(x.col), _ptr(x.val), x.val.numel()) if sparse else (_ptr(x), ld(x), None, None, None, 0)
+    L.check(l.gmp_feature_propagate(_ptr(rowptr), _ptr(col), n, col.numel(), _ptr(left), _ptr(right), *feat_args, d, rounds, _ptr(out), ld(out),
+                                    _ptr(status), _ptr(ws), ws.numel(), _stream(rowptr)), "gmp_feature_propagate")
+    return FeaturePropagation(out, status)
+
+
 def gc_head_fwd(h: Tensor, ptr: Tensor, w0: Tensor, b0: Tensor, w3: Tensor, b3: Tensor, target: Tensor, g_scale: Tensor, p: float = 0.0,
                 seed: int = 0, site: int = 0) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
     """The fused graph-classification head up to the loss (gnnmp.h gmp_gc_head_fwd): h [N, 256] (rows contiguous, any leading dimension),

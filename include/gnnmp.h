@@ -730,6 +730,47 @@ int gmp_label_propagate(const int32_t* rowptr, const int32_t* col, int64_t n, in
                         gmp_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
+ * Degree-scaled propagation of a WIDE feature matrix over a graph (csrc/feature_prop.hip): H <- diag(left) A diag(right) H, `rounds`
+ * times -- with A = adjacency + I and left = right = 1 / sqrt(deg + 1) the S^K X of SGC (Wu et al. 2019).
+ * The graph is a CSR, rowptr int32 [n + 1] and col int32 [nnz]; left and right are fp32 [n] scales, NULL = all ones.  The features come
+ * in exactly one of two forms: dense, x fp32 [n, d] with leading dimension ldx (x_rowptr, x_col, x_val NULL), or CSR, x_rowptr int32
+ * [n + 1], x_col int32 [x_nnz], x_val fp32 [x_nnz] (x NULL; ldx is ignored).  All arithmetic is IEEE fp32, every multiply and every add
+ * rounded on its own (no fused multiply-add), subnormals kept.  H(0) = X.  For round t = 0 .. rounds - 1, row i, column c:
+ *   acc = +0;  for k = rowptr[i] .. rowptr[i+1] - 1, ASCENDING:  j = col[k];  acc = acc + (right[j] * H(t)[j, c])
+ *   H(t+1)[i, c] = left[i] * acc
+ * out [n, d] (leading dimension ldo) = H(rounds).  Per column this is gmp_label_propagate with alpha = 1, beta = 0 and no clamp, with
+ * the same bits.  Self-loops are the caller's business: ordinary CSR entries at their sorted position.
+ * status int32 [2], zeroed inside the call.  status[0] = the number of adjacency entries whose col lies outside [0, n): counted once
+ * (in round 1), skipped -- not added as zero -- in every round.  status[1] = the number of stored feature entries that break the CSR
+ * form's contract (0 with dense features): a feature row's columns must be strictly ascending, and an entry x_col[e] outside [0, d) or
+ * not greater than the stored x_col[e - 1] of the same row is skipped and counted, once per entry.  (A row that holds one column twice
+ * AROUND a skipped entry -- 5, 3, 5 -- keeps both and is outside the contract: status[1] is non-zero, and which term that column sees is
+ * unspecified.)  rowptr and x_rowptr are clamped to [0, nnz] and [0, x_nnz], so a malformed CSR gives wrong numbers but reads nothing
+ * outside col, x_col and x_val.
+ * CSR features and dense features agree bit for bit: for finite inputs the CSR form leaves the bits the dense form leaves on the
+ * densified matrix.  The first round with CSR features visits a neighbour's stored entries only; the terms it leaves out are
+ * right[j] * 0 = +-0, the accumulator starts at +0 and can never become -0 (x + (-x) rounds to +0), and acc + (+-0) = acc, so a skipped
+ * r * 0 term changes nothing.  A stored explicit zero is added as the dense form adds it.
+ * Determinism: a row's sum is sequential in ascending k and there is no floating-point atomic.  Two calls leave the same bits, and one
+ * call of T rounds leaves the bits of T chained calls of one round.
+ * One launch per round (there is no in-kernel grid barrier), all enqueued on `stream` without a host synchronisation.  H ping-pongs
+ * between min(rounds - 1, 2) buffers of n x dpad floats (dpad = d rounded up to 4) in the workspace and the last round writes out, so
+ * rounds == 1 needs no workspace (ws may be NULL); x is never written.  Loads and stores are single dwords: ldx and ldo may be any value
+ * >= d, multiples of 4 or not (CiteSeer's rows are 3,703 floats), bases need 4-byte alignment only, row offsets j * ld are 64-bit, and
+ * the columns [d, ldo) of out are not touched.
+ * 0 <= n < 2^31, 0 <= nnz, x_nnz < 2^31, 1 <= d <= 16384, 1 <= rounds <= 64.  GMP_ERR_ARG, with nothing launched: a size outside those
+ * ranges, both feature forms or neither, ldx < d (dense) or ldo < d, a null required pointer (rowptr, out, status; col when nnz > 0;
+ * x_col and x_val when x_nnz > 0), out overlapping x (x_val) or the workspace, or a workspace smaller than
+ * gmp_feature_propagate_workspace_bytes(n, d, rounds) (0 for sizes out of range and for rounds == 1).  n == 0 returns GMP_OK and writes
+ * nothing.  Asynchronous, no allocation, no global state.
+ * ------------------------------------------------------------------------- */
+size_t gmp_feature_propagate_workspace_bytes(int64_t n, int32_t d, int32_t rounds);
+int gmp_feature_propagate(const int32_t* rowptr, const int32_t* col, int64_t n, int64_t nnz, const float* left, const float* right,
+                          const float* x, int64_t ldx, const int32_t* x_rowptr, const int32_t* x_col, const float* x_val, int64_t x_nnz,
+                          int32_t d, int32_t rounds, float* out, int64_t ldo, int32_t* status, void* ws, size_t ws_bytes,
+                          gmp_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
  * The fused graph-classification head of fine-tuning (finetune_model.py:68-80, finetune.py:110-114) over one batch of
  * num_graphs graphs; graph b owns the rows ptr[b] .. ptr[b+1] of h (ptr: device int32 [num_graphs + 1]):
  *   pooled[b] = mean of the graph's rows, divisor max(count, 1) (gmp_segment_sum(mean = 1); an empty graph pools to zero),
