@@ -69,14 +69,6 @@ __global__ __launch_bounds__(THREADS) void emb_link_prep_kernel(const float* __r
     }
 }
 
-// acc[r] for a run-time r (a chain of selects: the accumulators stay in registers)
-__device__ __forceinline__ float pick(const f32x16& a, int r) {
-    float v = a[0];
-#pragma unroll
-    for (int i = 1; i < 16; ++i) v = r == i ? a[i] : v;
-    return v;
-}
-
 // the lane's share of row `node` of zn as Tile<DP>::product takes a query row (k in [half DP/2, (half + 1) DP/2)); zeros beyond dpad and
 // for a node outside [0, N)
 template <int DP>
@@ -281,9 +273,10 @@ extern "C" int gmp_emb_link_rank(const float* h, int64_t num_nodes, int dim, int
                                  gmp_stream_t stream) {
     if (int rc = args_ok("emb_link_rank", num_nodes, num_queries, dim, mode)) return rc;
     if (filter_nnz < 0) return gmp::fail(GMP_ERR_ARG, "emb_link_rank: filter_nnz=%lld", (long long)filter_nnz);
-    if (int rc = lpf::filter_ok("emb_link_rank", filter_rowptr, filter_col, filter_nnz)) return rc;
-    if (num_queries == 0) return GMP_OK;
-    if ((num_nodes && !h) || !src || !dst || !score_true || !n_greater || !n_equal) return gmp::fail(GMP_ERR_ARG, "emb_link_rank: null pointer");
+    bool done;                                                      // (the sign of num_queries is args_ok's)
+    if (int rc = lpf::rank_front("emb_link_rank", num_queries, filter_rowptr, filter_col, filter_nnz, src, dst, score_true, n_greater, n_equal, done); rc || done)
+        return rc;
+    if (num_nodes && !h) return gmp::fail(GMP_ERR_ARG, "emb_link_rank: null pointer");
     const Plan p = make_plan(num_queries, num_nodes, dim);
     if (p.tiles * std::max(p.chunks, 1) >= ROW_LIMIT)
         return gmp::fail(GMP_ERR_ARG, "emb_link_rank: %lld query tiles x %d candidate chunks exceed one grid", (long long)p.tiles, p.chunks);

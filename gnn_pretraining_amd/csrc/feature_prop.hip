@@ -192,11 +192,6 @@ bool sizes_ok(int64_t n, int d, int rounds) { return n >= 0 && n < LIMIT && d >=
 
 int buffers_of(int rounds) { return rounds - 1 < 2 ? rounds - 1 : 2; }
 
-bool overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a && b && a_bytes && b_bytes && x < y + b_bytes && y < x + a_bytes;
-}
-
 // the bytes from the first to the last element of an [n, d] matrix with leading dimension ld
 size_t span(int64_t n, int d, int64_t ld) { return n > 0 ? ((size_t)(n - 1) * (size_t)ld + (size_t)d) * sizeof(float) : 0; }
 
@@ -224,11 +219,11 @@ extern "C" int gmp_feature_propagate(const int32_t* rowptr, const int32_t* col, 
         return gmp::fail(GMP_ERR_ARG, "feature_propagate: x_nnz=%lld (0 <= x_nnz < 2^31) or a null x_rowptr / x_col / x_val", (long long)x_nnz);
     if (!rowptr || (!col && nnz > 0) || !out || !status) return gmp::fail(GMP_ERR_ARG, "feature_propagate: null pointer");
     const size_t out_bytes = span(n, d, ldo);
-    if ((dense && overlap(out, out_bytes, x, span(n, d, ldx))) || (sparse && overlap(out, out_bytes, x_val, (size_t)x_nnz * sizeof(float))))
+    if ((dense && gmp::overlap(out, out_bytes, x, span(n, d, ldx))) || (sparse && gmp::overlap(out, out_bytes, x_val, (size_t)x_nnz * sizeof(float))))
         return gmp::fail(GMP_ERR_ARG, "feature_propagate: out overlaps x");
     const size_t need = gmp_feature_propagate_workspace_bytes(n, d, rounds);
     if (need && (!ws || ws_bytes < need)) return gmp::fail(GMP_ERR_ARG, "feature_propagate: workspace %zu < %zu", ws ? ws_bytes : (size_t)0, need);
-    if (need && overlap(out, out_bytes, ws, ws_bytes)) return gmp::fail(GMP_ERR_ARG, "feature_propagate: out overlaps the workspace");
+    if (need && gmp::overlap(out, out_bytes, ws, ws_bytes)) return gmp::fail(GMP_ERR_ARG, "feature_propagate: out overlaps the workspace");
     hipStream_t st = (hipStream_t)stream;
     const int dpad = dpad_of(d);
     float* buf[2] = {nullptr, nullptr};

@@ -161,6 +161,12 @@ __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// the byte ranges [a, a + a_bytes) and [b, b + b_bytes) meet (a null pointer and an empty range meet nothing)
+inline bool overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return a && b && a_bytes && b_bytes && x < y + b_bytes && y < x + a_bytes;
+}
+
 // workspace slices start on 256 bytes
 inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
 

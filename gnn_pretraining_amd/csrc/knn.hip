@@ -74,14 +74,6 @@ __device__ __forceinline__ u64 read_lane(u64 v, int src) {
     return ((u64)hi << 32) | lo;
 }
 
-// acc[r] for a run-time r (a chain of selects: the accumulators stay in registers)
-__device__ __forceinline__ float pick(const f32x16& a, int r) {
-    float v = a[0];
-#pragma unroll
-    for (int i = 1; i < 16; ++i) v = r == i ? a[i] : v;
-    return v;
-}
-
 // rows [0, nq) of q into qn, rows [0, ndb) of db into dbn
 __global__ __launch_bounds__(THREADS) void knn_normalize_kernel(const float* __restrict__ q, int64_t nq, const float* __restrict__ db, int64_t ndb,
                                                                 int d, int dpad, float* __restrict__ qn, float* __restrict__ dbn) {

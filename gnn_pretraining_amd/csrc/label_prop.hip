@@ -113,11 +113,6 @@ int launch_round(const int32_t* rowptr, const int32_t* col, int n, int nnz, cons
 
 bool sizes_ok(int64_t n, int classes) { return n >= 0 && n < LIMIT && classes >= 1 && classes <= MAX_CLASSES; }
 
-bool overlap(const float* a, const float* b, size_t bytes) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a && b && x < y + bytes && y < x + bytes;
-}
-
 }  // namespace
 
 extern "C" size_t gmp_label_propagate_workspace_bytes(int64_t n, int classes) {
@@ -138,7 +133,7 @@ extern "C" int gmp_label_propagate(const int32_t* rowptr, const int32_t* col, in
     if (n == 0) return GMP_OK;
     if (!rowptr || (!col && nnz > 0) || !f0 || !out || !status) return gmp::fail(GMP_ERR_ARG, "label_propagate: null pointer");
     const size_t bytes = (size_t)n * classes * sizeof(float);
-    if (overlap(out, f0, bytes) || overlap(out, f_init, bytes)) return gmp::fail(GMP_ERR_ARG, "label_propagate: out aliases f0 or f_init");
+    if (gmp::overlap(out, bytes, f0, bytes) || gmp::overlap(out, bytes, f_init, bytes)) return gmp::fail(GMP_ERR_ARG, "label_propagate: out aliases f0 or f_init");
     const size_t need = gmp_label_propagate_workspace_bytes(n, classes);
     if (!workspace || workspace_bytes < need)
         return gmp::fail(GMP_ERR_WORKSPACE, "label_propagate: workspace %zu < %zu", workspace ? workspace_bytes : (size_t)0, need);

@@ -18,6 +18,7 @@
 //   simple_check_kernel  one wave per row
 // Every read of col is bounded by rowptr clamped to [0, nnz], every entry outside [0, N) is skipped and every LDS slot index is checked: a
 // CSR that breaks the assumptions gives wrong numbers, never an access outside the arrays.
+#include "csr_graph.h"
 #include "lp_filter.h"
 
 namespace {
@@ -27,14 +28,7 @@ constexpr int THREADS = 256;
 constexpr int WAVES = THREADS / GMP_WAVE;
 constexpr int MODE_SUM = 0, MODE_JACCARD = 1;
 
-struct Row { int64_t b, e; };
-
-// row v of the CSR, clamped to the col array; empty for v outside [0, N)
-__device__ __forceinline__ Row row_of(const int32_t* __restrict__ rowptr, int64_t nnz, int64_t N, int64_t v) {
-    if (v < 0 || v >= N) return Row{0, 0};
-    const int64_t b = min(max((int64_t)rowptr[v], (int64_t)0), nnz), e = min(max((int64_t)rowptr[v + 1], (int64_t)0), nnz);
-    return Row{b, max(b, e)};
-}
+using namespace csr;                // Row, row_of, graph_ok
 
 // the first i in [lo, hi) with col[i] >= key (hi if none)
 __device__ __forceinline__ int64_t lower_bound(const int32_t* __restrict__ col, int64_t lo, int64_t hi, int64_t key) {
@@ -209,13 +203,6 @@ __global__ __launch_bounds__(THREADS) void simple_check_kernel(const int32_t* __
     if (lane == 0 && bad) atomicAdd(&violations[0], bad);
 }
 
-int graph_ok(const char* who, const void* rowptr, const void* col, int64_t N, int64_t nnz) {
-    if (N < 0 || N >= ((int64_t)1 << 31) || nnz < 0 || nnz >= ((int64_t)1 << 31))
-        return gmp::fail(GMP_ERR_ARG, "%s: N=%lld nnz=%lld", who, (long long)N, (long long)nnz);
-    if (!rowptr || (nnz > 0 && !col)) return gmp::fail(GMP_ERR_ARG, "%s: null pointer", who);
-    return GMP_OK;
-}
-
 int scorer_ok(const char* who, const void* weight, int mode) {
     if (mode != MODE_SUM && mode != MODE_JACCARD) return gmp::fail(GMP_ERR_ARG, "%s: mode=%d (0 = weighted sum, 1 = Jaccard)", who, mode);
     if (weight && mode == MODE_JACCARD) return gmp::fail(GMP_ERR_ARG, "%s: Jaccard takes no weight array", who);
@@ -257,10 +244,9 @@ extern "C" int gmp_lp_cn_rank(const int32_t* rowptr, const int32_t* col, int64_t
     (void)workspace; (void)workspace_bytes;
     if (int rc = graph_ok("lp_cn_rank", rowptr, col, N, nnz)) return rc;
     if (int rc = scorer_ok("lp_cn_rank", weight, mode)) return rc;
-    if (Q < 0 || filter_nnz < 0) return gmp::fail(GMP_ERR_ARG, "lp_cn_rank: Q=%lld filter_nnz=%lld", (long long)Q, (long long)filter_nnz);
-    if (int rc = lpf::filter_ok("lp_cn_rank", filter_rowptr, filter_col, filter_nnz)) return rc;
-    if (Q == 0) return GMP_OK;
-    if (!src || !dst || !score_true || !n_greater || !n_equal) return gmp::fail(GMP_ERR_ARG, "lp_cn_rank: null pointer");
+    bool done;
+    if (int rc = lpf::rank_front("lp_cn_rank", Q, filter_rowptr, filter_col, filter_nnz, src, dst, score_true, n_greater, n_equal, done); rc || done)
+        return rc;
     const int64_t tiles = (N + TC - 1) / TC;
     if (int rc = lpf::grid_ok("lp_cn_rank", Q, tiles)) return rc;
     hipStream_t st = (hipStream_t)stream;

@@ -254,8 +254,9 @@ extern "C" int gmp_lp_rank(const float* h, const int64_t* src, const int64_t* ds
                            void* workspace, size_t workspace_bytes, gmp_stream_t stream) {
     (void)workspace; (void)workspace_bytes;
     if (int rc = common_ok("lp_rank", N, Q, feat, hidden, h, w0, b0, w3, b3, filter_rowptr, filter_col, filter_nnz)) return rc;
-    if (Q == 0) return GMP_OK;
-    if (!src || !dst || !logit_true || !n_greater || !n_equal) return gmp::fail(GMP_ERR_ARG, "lp_rank: null pointer");
+    bool done;                                                      // (common_ok has answered the front's first two checks: N and Q go together there)
+    if (int rc = lpf::rank_front("lp_rank", Q, filter_rowptr, filter_col, filter_nnz, src, dst, logit_true, n_greater, n_equal, done); rc || done)
+        return rc;
     const int64_t tiles = (N + BM - 1) / BM;
     if (int rc = lpf::grid_ok("lp_rank", Q, tiles)) return rc;
     static std::atomic<uint64_t> attr_true{0}, attr_count{0};

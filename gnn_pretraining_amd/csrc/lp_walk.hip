@@ -21,6 +21,7 @@
 // gives wrong numbers, never an access outside the arrays.
 #include <algorithm>
 
+#include "csr_graph.h"
 #include "lp_filter.h"
 
 namespace {
@@ -42,12 +43,18 @@ constexpr size_t lds_bytes(int64_t N) { return (size_t)(2 * N + words_of(N)) * 4
 static_assert(lds_bytes(LDS_NODES) + 64 <= 160 * 1024, "two vectors, the bitmap and the static counters fit one CU's LDS");
 static_assert(LARGE_THREADS * LARGE_REGS >= LDS_NODES && SMALL_NODES <= LDS_NODES, "every row of an LDS instance has its accumulator");
 
-struct Row { int64_t b, e; };
+using namespace csr;                // Row, row_of, graph_ok
 
-// row v of the CSR, clamped to the col array (v in [0, N))
-__device__ __forceinline__ Row row_of(const int32_t* __restrict__ rowptr, int64_t nnz, int64_t v) {
-    const int64_t b = min(max((int64_t)rowptr[v], (int64_t)0), nnz), e = min(max((int64_t)rowptr[v + 1], (int64_t)0), nnz);
-    return Row{b, max(b, e)};
+// lpf::mark over all candidates, written out: as a form of lpf::mark_each it changes walk_kernel's instruction schedule
+__device__ __forceinline__ void mark(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, int64_t nnz, int64_t s, int64_t N,
+                                     unsigned int* bits, int64_t words, int threads) {
+    if (rowptr && s >= 0 && s < N) {
+        const int64_t b = max((int64_t)rowptr[s], (int64_t)0), e = min((int64_t)rowptr[s + 1], nnz);
+        for (int64_t i = b + threadIdx.x; i < e; i += threads) {
+            const uint64_t off = (uint64_t)col[i];
+            if (off < (uint64_t)(32 * words)) atomicOr(&bits[off >> 5], 1u << (unsigned)(off & 31));
+        }
+    }
 }
 
 // one row of a round: a * (the fold of w[z] * prev[z] over the row in ascending z, one add each)
@@ -188,7 +195,7 @@ __global__ __launch_bounds__(T) void walk_kernel(const int32_t* __restrict__ row
         for (int64_t w = t; w < words; w += T) fbits[w] = 0u;
         if (t < 2) cnt[t] = 0;
         __syncthreads();
-        lpf::mark(frowptr, fcol, fnnz, s, N, 0, fbits, words, T);    // gmp_lp_rank's filter row
+        mark(frowptr, fcol, fnnz, s, N, fbits, words, T);            // gmp_lp_rank's filter row
         __syncthreads();
         int greater = 0, equal = 0;
         for (int64_t c = t; c < N; c += T) {
@@ -220,9 +227,7 @@ __global__ __launch_bounds__(T) void walk_kernel(const int32_t* __restrict__ row
 int64_t ws_stride(int64_t N) { return (int64_t)(gmp::al((size_t)N * 4) / 4); }
 
 int args_ok(const char* who, const void* rowptr, const void* col, int64_t N, int64_t nnz, const void* weight, float damping, int rounds, int mode) {
-    if (N < 0 || N >= ((int64_t)1 << 31) || nnz < 0 || nnz >= ((int64_t)1 << 31))
-        return gmp::fail(GMP_ERR_ARG, "%s: N=%lld nnz=%lld", who, (long long)N, (long long)nnz);
-    if (!rowptr || (nnz > 0 && !col)) return gmp::fail(GMP_ERR_ARG, "%s: null pointer", who);
+    if (int rc = graph_ok(who, rowptr, col, N, nnz)) return rc;
     if (mode != MODE_SUM && mode != MODE_HOPS) return gmp::fail(GMP_ERR_ARG, "%s: mode=%d (0 = walk sum, 1 = hops)", who, mode);
     if (rounds < 1 || rounds > MAX_ROUNDS) return gmp::fail(GMP_ERR_ARG, "%s: rounds=%d (1 <= rounds <= %d)", who, rounds, MAX_ROUNDS);
     if (weight && mode == MODE_HOPS) return gmp::fail(GMP_ERR_ARG, "%s: hops take no weight array", who);
@@ -287,10 +292,9 @@ extern "C" int gmp_lp_walk_rank(const int32_t* rowptr, const int32_t* col, int64
                                 const int32_t* filter_col, int64_t filter_nnz, float* score_true, int32_t* n_greater, int32_t* n_equal,
                                 void* workspace, size_t workspace_bytes, gmp_stream_t stream) {
     if (int rc = args_ok("lp_walk_rank", rowptr, col, N, nnz, weight, damping, rounds, mode)) return rc;
-    if (Q < 0 || filter_nnz < 0) return gmp::fail(GMP_ERR_ARG, "lp_walk_rank: Q=%lld filter_nnz=%lld", (long long)Q, (long long)filter_nnz);
-    if (int rc = lpf::filter_ok("lp_walk_rank", filter_rowptr, filter_col, filter_nnz)) return rc;
-    if (Q == 0) return GMP_OK;
-    if (!src || !dst || !score_true || !n_greater || !n_equal) return gmp::fail(GMP_ERR_ARG, "lp_walk_rank: null pointer");
+    bool done;
+    if (int rc = lpf::rank_front("lp_walk_rank", Q, filter_rowptr, filter_col, filter_nnz, src, dst, score_true, n_greater, n_equal, done); rc || done)
+        return rc;
     return launch("lp_walk_rank", rowptr, col, N, nnz, src, dst, Q, weight, damping, rounds, mode, filter_rowptr, filter_col, filter_nnz,
                   score_true, n_greater, n_equal, workspace, workspace_bytes, (hipStream_t)stream);
 }

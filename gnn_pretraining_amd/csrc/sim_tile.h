@@ -18,6 +18,14 @@ using gmp::acc_row;
 using gmp::f32x16;
 using gmp::u64;
 
+// acc[r] for a run-time r (a chain of selects: the accumulators stay in registers)
+__device__ __forceinline__ float pick(const f32x16& a, int r) {
+    float v = a[0];
+#pragma unroll
+    for (int i = 1; i < 16; ++i) v = r == i ? a[i] : v;
+    return v;
+}
+
 // the row stride of a normalised copy: the dimension padded to a multiple of 4
 constexpr int pad4(int64_t dim) { return (int)((dim + 3) / 4 * 4); }
 

@@ -22,6 +22,7 @@ from .. import operators as O, ops, repr_stats as RS
 from ..constants import NUM_CLASSES, TASK_TYPES
 from ..graph import SparseFeatures
 from ..models.finetune_model import FinetuneGNN, create_finetune_model
+from . import graph_baselines as GB, link_eval as LE, link_heuristics as LH, link_walks as LW, node_baselines as NB
 from .metrics import (compute_batch_metrics, compute_batch_metrics_device, compute_test_metrics, compute_training_metrics, compute_validation_metrics,
                       cluster_probe, knn_probe_accuracy, linear_eval_probe, ranking_metrics)
 
@@ -198,24 +199,12 @@ class FinetuneConfig:
                              "pass lp_engine (--lp-engine)")
         if self.lp_ranking and not self.lp_engine:
             raise ValueError("lp_ranking ranks with the link-prediction engine (gmp_lp_rank): pass lp_engine (--lp-engine)")
-        if self.lp_heuristics and TASK_TYPES[self.domain_name] != "link_prediction":
-            raise ValueError(f"lp_heuristics applies to the link-prediction domains (Cora_LP / CiteSeer_LP), not to {self.domain_name}")
-        if not 0 <= self.lp_walks <= ops.LP_WALK_MAX_ROUNDS:
-            raise ValueError(f"lp_walks={self.lp_walks} (the number of propagation rounds, 1 <= rounds <= {ops.LP_WALK_MAX_ROUNDS}; 0 switches the baselines off)")
-        if self.lp_walks and TASK_TYPES[self.domain_name] != "link_prediction":
-            raise ValueError(f"lp_walks applies to the link-prediction domains (Cora_LP / CiteSeer_LP), not to {self.domain_name}")
-        if not 0 <= self.wl_baseline <= ops.WL_MAX_ITERS:
-            raise ValueError(f"wl_baseline={self.wl_baseline} (the number of refinement rounds, 1 <= rounds <= {ops.WL_MAX_ITERS}; 0 switches the baseline off)")
-        if self.wl_baseline and TASK_TYPES[self.domain_name] != "graph_classification":
-            raise ValueError(f"wl_baseline applies to the graph-classification domains (ENZYMES / PTC_MR), not to {self.domain_name}")
-        if not 0 <= self.label_propagation <= ops.LABELPROP_MAX_ROUNDS:
-            raise ValueError(f"label_propagation={self.label_propagation} (the number of propagation rounds, 1 <= rounds <= {ops.LABELPROP_MAX_ROUNDS}; 0 switches the baselines off)")
-        if self.label_propagation and TASK_TYPES[self.domain_name] != "node_classification":
-            raise ValueError(f"label_propagation applies to the node-classification domains (Cora_NC / CiteSeer_NC), not to {self.domain_name}")
-        if not 0 <= self.sgc_baseline <= ops.FEATPROP_MAX_ROUNDS:
-            raise ValueError(f"sgc_baseline={self.sgc_baseline} (the number of propagation rounds, 1 <= rounds <= {ops.FEATPROP_MAX_ROUNDS}; 0 switches the baselines off)")
-        if self.sgc_baseline and TASK_TYPES[self.domain_name] != "node_classification":
-            raise ValueError(f"sgc_baseline applies to the node-classification domains (Cora_NC / CiteSeer_NC), not to {self.domain_name}")
+        for b in BASELINES:
+            value = getattr(self, b.field)
+            if b.max_value is not None and not 0 <= value <= b.max_value:
+                raise ValueError(f"{b.field}={value} ({b.bound.format(b.max_value)})")
+            if value and TASK_TYPES[self.domain_name] != b.task_type:
+                raise ValueError(f"{b.field} applies to the {b.task_type.replace('_', '-')} domains ({b.domains}), not to {self.domain_name}")
         self.exp_name = f"{self.domain_name}_{self.finetune_strategy}_{self.pretrained_scheme}"
         self.task_type = TASK_TYPES[self.domain_name]
         self.batch_size = BATCH_SIZES[self.domain_name]
@@ -449,36 +438,19 @@ def rank_test_edges(engine, train_loader, val_loader, test_loader, device) -> Di
     return {f"test/{k}": v for k, v in ranking_metrics(ranks).items()}
 
 
-def _structural_ranking_inputs(train_loader, val_loader, test_loader, device):
-    """(graph, num_nodes, true test edges, filter edges) of the model-free link baselines: the message-passing graph is the train
-    split's positive edges alone; the known positives of the three splits, in both directions, are the filter."""
+def rank_test_edges_baselines(family, extra: tuple, train_loader, val_loader, test_loader, device) -> Dict[str, float]:
+    """cfg.lp_heuristics, cfg.lp_walks: rank_test_edges with a family of model-free scorers in place of the trained one, one
+    link_eval.LinkScorer per kind: family.scorer(graph, num_nodes, kind, *extra) for family.KINDS -- the four neighbourhood baselines of
+    link_heuristics, or the three walk-based ones of link_walks with extra = (rounds,).  They see the message-passing graph alone -- the
+    train split's positive edges; validation and test edges enter the filter only.  Reads the datasets and nothing else: no model, no
+    generator, no dropout counter, no BatchNorm state."""
     data = train_loader.dataset
     graph = data.train_edges.to(device).contiguous()
     pos = test_loader.dataset.pos_edges.to(device).contiguous()
-    return graph, data.data.num_nodes, pos, _known_positives(train_loader, val_loader, test_loader, device)
-
-
-def rank_test_edges_heuristics(train_loader, val_loader, test_loader, device) -> Dict[str, float]:
-    """cfg.lp_heuristics: rank_test_edges with the four neighbourhood baselines (link_heuristics.KINDS) in place of the trained scorer.
-    They see the message-passing graph alone -- the train split's positive edges; validation and test edges enter the filter only.
-    Reads the datasets and nothing else: no model, no generator, no dropout counter, no BatchNorm state."""
-    from . import link_heuristics as LH
-    graph, num_nodes, pos, known = _structural_ranking_inputs(train_loader, val_loader, test_loader, device)
+    known = _known_positives(train_loader, val_loader, test_loader, device)
     out = {}
-    for kind in LH.KINDS:
-        ranks = LH.heuristic_ranks(graph, num_nodes, pos, kind, filter_edges=known).rank
-        out.update({f"test/{kind}_{k}": v for k, v in ranking_metrics(ranks).items()})
-    return out
-
-
-def rank_test_edges_walks(train_loader, val_loader, test_loader, device, rounds: int) -> Dict[str, float]:
-    """cfg.lp_walks: rank_test_edges_heuristics with the three walk-based baselines (link_walks.KINDS: Katz, rooted PageRank, hop
-    distance) at `rounds` rounds -- the same graph, the same filter, the same half-tie rank.  Reads the datasets and nothing else."""
-    from . import link_walks as LW
-    graph, num_nodes, pos, known = _structural_ranking_inputs(train_loader, val_loader, test_loader, device)
-    out = {}
-    for kind in LW.KINDS:
-        ranks = LW.walk_ranks(graph, num_nodes, pos, kind, rounds, filter_edges=known).rank
+    for kind, scorer in [(kind, family.scorer(graph, data.data.num_nodes, kind, *extra)) for kind in family.KINDS]:
+        ranks = LE.ranks(scorer, pos, known).rank
         out.update({f"test/{kind}_{k}": v for k, v in ranking_metrics(ranks).items()})
     return out
 
@@ -488,30 +460,62 @@ def wl_baseline_keys(train_loader, test_loader, device, cfg: FinetuneConfig) -> 
     features of the raw graphs with cfg.wl_baseline rounds, fitted on the train split and scored on the test split by a k-NN vote on the
     exact kernel and a softmax regression on the hashed histogram (graph_baselines.wl_baseline).  Reads the datasets and nothing else: no
     model, no generator, no dropout counter, no BatchNorm state."""
-    from . import graph_baselines as GB
     scores = GB.wl_baseline(train_loader.dataset, test_loader.dataset, NUM_CLASSES[cfg.domain_name], cfg.wl_baseline, device=device)
     return {f"test/wl_{k}": v for k, v in scores.items()}
 
 
-def label_baseline_keys(train_loader, test_loader, device, cfg: FinetuneConfig) -> Dict[str, float]:
-    """cfg.label_propagation: what test/accuracy has to beat on a node-classification domain -- label spreading and label propagation with
-    cfg.label_propagation rounds over the whole raw graph, seeded with the train split's labels and scored on the test split
-    (node_baselines.label_baselines).  Reads the datasets and nothing else: no model, no generator, no dropout counter, no BatchNorm state."""
-    from . import node_baselines as NB
+def node_baseline_keys(baselines: Callable, rounds: int, train_loader, test_loader, device, cfg: FinetuneConfig) -> Dict[str, float]:
+    """What test/accuracy has to beat on a node-classification domain, fitted on the train split and scored on the test split.
+    cfg.label_propagation (node_baselines.label_baselines): label spreading and label propagation with that many rounds over the whole raw
+    graph, seeded with the train split's labels.  cfg.sgc_baseline (node_baselines.feature_baselines), once the features are read: a
+    softmax regression on the raw features and SGC, the same regression on S^K X with K = cfg.sgc_baseline.  Reads the datasets and
+    nothing else: no model, no generator, no dropout counter, no BatchNorm state."""
     train, test = train_loader.dataset, test_loader.dataset
-    scores = NB.label_baselines(train.data, train.indices, test.indices, NUM_CLASSES[cfg.domain_name], cfg.label_propagation, device=device)
+    scores = baselines(train.data, train.indices, test.indices, NUM_CLASSES[cfg.domain_name], rounds, device=device)
     return {f"test/{k}": v for k, v in scores.items()}
 
 
-def feature_baseline_keys(train_loader, test_loader, device, cfg: FinetuneConfig) -> Dict[str, float]:
-    """cfg.sgc_baseline: what test/accuracy has to beat on a node-classification domain once the features are read -- a softmax regression
-    on the raw features and SGC, the same regression on S^K X with K = cfg.sgc_baseline, fitted on the train split's rows and scored on the
-    test split (node_baselines.feature_baselines).  Reads the datasets and nothing else: no model, no generator, no dropout counter, no
-    BatchNorm state."""
-    from . import node_baselines as NB
-    train, test = train_loader.dataset, test_loader.dataset
-    scores = NB.feature_baselines(train.data, train.indices, test.indices, NUM_CLASSES[cfg.domain_name], cfg.sgc_baseline, device=device)
-    return {f"test/{k}": v for k, v in scores.items()}
+@dataclass(frozen=True)
+class Baseline:
+    """One model-free baseline of the test record: a FinetuneConfig field (an integer, 0 = off, or a bool where max_value is None) with
+    its flag, the one task type it applies to, and keys(train_loader, val_loader, test_loader, device, cfg) -> the test/ keys it adds."""
+    field: str
+    flag: str
+    metavar: Optional[str]
+    max_value: Optional[int]
+    bound: Optional[str]                # what the integer is, for the bound's message ({} = max_value)
+    task_type: str
+    domains: str                        # the task type's domains, for the refusal elsewhere
+    keys: Callable
+    help: str
+
+
+ROUNDS = "the number of propagation rounds, 1 <= rounds <= {}; 0 switches the baselines off"
+LP, GC, NC = ("link_prediction", "Cora_LP / CiteSeer_LP"), ("graph_classification", "ENZYMES / PTC_MR"), ("node_classification", "Cora_NC / CiteSeer_NC")
+BASELINES = (
+    Baseline("lp_heuristics", "--lp-heuristics", None, None, None, *LP, lambda tr, va, te, dev, cfg: rank_test_edges_baselines(LH, (), tr, va, te, dev),
+             "Cora_LP / CiteSeer_LP: the test record also carries test/{cn,jaccard,aa,ra}_mrr and _hits@K, the common-neighbour, Jaccard, Adamic-Adar and resource-allocation baselines ranked like --lp-ranking on the training graph (needs neither --lp-engine nor --lp-ranking)"),
+    Baseline("lp_walks", "--lp-walks", "R", ops.LP_WALK_MAX_ROUNDS, ROUNDS, *LP, lambda tr, va, te, dev, cfg: rank_test_edges_baselines(LW, (cfg.lp_walks,), tr, va, te, dev),
+             "Cora_LP / CiteSeer_LP: the test record also carries test/{katz,ppr,hops}_mrr and _hits@K, the Katz index (beta 0.05), "
+             "rooted PageRank (alpha 0.15) and hop-distance baselines with R rounds (1..64), ranked like --lp-heuristics on the "
+             "training graph (needs neither --lp-engine nor --lp-ranking); 0 = off"),
+    Baseline("wl_baseline", "--wl-baseline", "H", ops.WL_MAX_ITERS, "the number of refinement rounds, 1 <= rounds <= {}; 0 switches the baseline off",
+             *GC, lambda tr, va, te, dev, cfg: wl_baseline_keys(tr, te, dev, cfg),
+             "ENZYMES / PTC_MR: the test record also carries test/wl_knn_accuracy and test/wl_logreg_accuracy, the Weisfeiler-Lehman "
+             "subtree baseline with H refinement rounds (1..7) on the raw graphs, fitted on the train split and scored on the test "
+             "split (needs neither --gc-engine nor a probe flag); 0 = off"),
+    Baseline("label_propagation", "--label-propagation", "T", ops.LABELPROP_MAX_ROUNDS, ROUNDS, *NC,
+             lambda tr, va, te, dev, cfg: node_baseline_keys(NB.label_baselines, cfg.label_propagation, tr, te, dev, cfg),
+             "Cora_NC / CiteSeer_NC: the test record also carries test/labelspread_accuracy, test/labelprop_accuracy and their "
+             "_unreached counts, label spreading (alpha 0.9) and label propagation with T rounds (1..10000) over the raw graph, "
+             "seeded with the train split's labels and scored on the test split (needs neither an engine nor a probe flag); 0 = off"),
+    Baseline("sgc_baseline", "--sgc-baseline", "K", ops.FEATPROP_MAX_ROUNDS, ROUNDS, *NC,
+             lambda tr, va, te, dev, cfg: node_baseline_keys(NB.feature_baselines, cfg.sgc_baseline, tr, te, dev, cfg),
+             "Cora_NC / CiteSeer_NC: the test record also carries test/rawfeat_accuracy and test/sgc_accuracy, a softmax regression "
+             "on the raw features and SGC (the same regression on S^K X, K rounds 1..64 of the degree-scaled propagation with "
+             "self-loops), fitted on the train split and scored on the test split (needs neither an engine nor a probe flag; "
+             "combines with --label-propagation and --sparse-features); 0 = off"),
+)
 
 
 def probe_embeddings(engine, datasets, device, cfg: FinetuneConfig):
@@ -683,16 +687,9 @@ def finetune(cfg: FinetuneConfig, epochs: Optional[int] = None, device: Optional
     test.update(run_probes(probe_engine, train_loader, test_loader, dev, cfg, "test", known))
     if cfg.lp_ranking:
         test.update(rank_test_edges(lp_engine, train_loader, val_loader, test_loader, dev))
-    if cfg.lp_heuristics:
-        test.update(rank_test_edges_heuristics(train_loader, val_loader, test_loader, dev))
-    if cfg.lp_walks:
-        test.update(rank_test_edges_walks(train_loader, val_loader, test_loader, dev, cfg.lp_walks))
-    if cfg.wl_baseline:
-        test.update(wl_baseline_keys(train_loader, test_loader, dev, cfg))
-    if cfg.label_propagation:
-        test.update(label_baseline_keys(train_loader, test_loader, dev, cfg))
-    if cfg.sgc_baseline:
-        test.update(feature_baseline_keys(train_loader, test_loader, dev, cfg))
+    for b in BASELINES:
+        if getattr(cfg, b.field):
+            test.update(b.keys(train_loader, val_loader, test_loader, dev, cfg))
     logger.log(test, global_step[0])
     print(f"{cfg.exp_name}: best {key} {best:.4f}, test/accuracy {test['test/accuracy']:.4f}, test/auc {test['test/auc']:.4f}, "
           f"training_time {test['test/training_time']:.2f}s, saved {path}")
@@ -701,6 +698,13 @@ def finetune(cfg: FinetuneConfig, epochs: Optional[int] = None, device: Optional
 
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser()
+
+    def add_baselines(task_types: Tuple[str, ...]) -> None:              # (--help lists the flags in the order they were added)
+        for b in BASELINES:
+            if b.task_type in task_types:
+                kind = {"action": "store_true"} if b.max_value is None else {"type": int, "default": 0, "metavar": b.metavar}
+                p.add_argument(b.flag, help=b.help, **kind)
+
     p.add_argument("--domain_name", required=True)
     p.add_argument("--finetune_strategy", required=True, choices=["full_finetune", "linear_probe"])
     p.add_argument("--pretrained_scheme", required=True)
@@ -715,11 +719,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--gc-engine", action="store_true", help="ENZYMES / PTC_MR: the explicit-kernel fine-tune step (GraphClassificationEngine)")
     p.add_argument("--engine-eval", action="store_true", help="validation / test through the active engine's predict (needs the node engine, --lp-engine or --gc-engine)")
     p.add_argument("--lp-ranking", action="store_true", help="with --lp-engine: the test pass also logs test/mrr and test/hits@K (true test edges ranked against all nodes, known positives filtered)")
-    p.add_argument("--lp-heuristics", action="store_true", help="Cora_LP / CiteSeer_LP: the test record also carries test/{cn,jaccard,aa,ra}_mrr and _hits@K, the common-neighbour, Jaccard, Adamic-Adar and resource-allocation baselines ranked like --lp-ranking on the training graph (needs neither --lp-engine nor --lp-ranking)")
-    p.add_argument("--lp-walks", type=int, default=0, metavar="R",
-                   help="Cora_LP / CiteSeer_LP: the test record also carries test/{katz,ppr,hops}_mrr and _hits@K, the Katz index (beta 0.05), "
-                        "rooted PageRank (alpha 0.15) and hop-distance baselines with R rounds (1..64), ranked like --lp-heuristics on the "
-                        "training graph (needs neither --lp-engine nor --lp-ranking); 0 = off")
+    add_baselines(("link_prediction",))
     p.add_argument("--link-probe", action="store_true",
                    help="with --lp-engine: also log val/embed_{cos,dot}_mrr and _auc (every epoch and once before training) and "
                         "test/embed_{cos,dot}_mrr, _hits@K and _auc, the parameter-free embedding link probe: pairs scored by the cosine / the "
@@ -728,19 +728,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--miner", choices=list(ops.MINER_IMPLS), default="matrix",
                    help="Cora_LP / CiteSeer_LP: the hard-negative miner's top-k kernel: matrix (n x n similarity in the workspace, n <= 65535), "
                         "stream (tiles recomputed, workspace O(n d + E), n <= 2^20), auto (stream beyond 65535 nodes)")
-    p.add_argument("--wl-baseline", type=int, default=0, metavar="H",
-                   help="ENZYMES / PTC_MR: the test record also carries test/wl_knn_accuracy and test/wl_logreg_accuracy, the Weisfeiler-Lehman "
-                        "subtree baseline with H refinement rounds (1..7) on the raw graphs, fitted on the train split and scored on the test "
-                        "split (needs neither --gc-engine nor a probe flag); 0 = off")
-    p.add_argument("--label-propagation", type=int, default=0, metavar="T",
-                   help="Cora_NC / CiteSeer_NC: the test record also carries test/labelspread_accuracy, test/labelprop_accuracy and their "
-                        "_unreached counts, label spreading (alpha 0.9) and label propagation with T rounds (1..10000) over the raw graph, "
-                        "seeded with the train split's labels and scored on the test split (needs neither an engine nor a probe flag); 0 = off")
-    p.add_argument("--sgc-baseline", type=int, default=0, metavar="K",
-                   help="Cora_NC / CiteSeer_NC: the test record also carries test/rawfeat_accuracy and test/sgc_accuracy, a softmax regression "
-                        "on the raw features and SGC (the same regression on S^K X, K rounds 1..64 of the degree-scaled propagation with "
-                        "self-loops), fitted on the train split and scored on the test split (needs neither an engine nor a probe flag; "
-                        "combines with --label-propagation and --sparse-features); 0 = off")
+    add_baselines(("graph_classification", "node_classification"))
     for probe in PROBES:
         p.add_argument(probe.flag, type=int, default=0, metavar=probe.metavar, help=probe.help)
     p.add_argument("--repr-stats", action="store_true",
@@ -754,8 +742,8 @@ def config_from_args(a: argparse.Namespace) -> FinetuneConfig:
                           lp_engine=getattr(a, "lp_engine", False), gc_engine=getattr(a, "gc_engine", False),
                           engine_eval=getattr(a, "engine_eval", False), lp_ranking=getattr(a, "lp_ranking", False),
                           device_metrics=getattr(a, "device_metrics", False), miner_impl=getattr(a, "miner", "matrix"),
-                          repr_stats=getattr(a, "repr_stats", False), lp_heuristics=getattr(a, "lp_heuristics", False), lp_walks=getattr(a, "lp_walks", 0), wl_baseline=getattr(a, "wl_baseline", 0),
-                          label_propagation=getattr(a, "label_propagation", 0), sgc_baseline=getattr(a, "sgc_baseline", 0), link_probe=getattr(a, "link_probe", False),
+                          repr_stats=getattr(a, "repr_stats", False), link_probe=getattr(a, "link_probe", False),
+                          **{b.field: getattr(a, b.field, False if b.max_value is None else 0) for b in BASELINES},
                           **{p.field: getattr(a, p.field, 0) for p in PROBES})
 
 

@@ -4,6 +4,7 @@ include/gnnmp.h).  They read a graph only: no model, no generator, no dropout co
 
     simple_graph(edge_index, num_nodes)      the simple undirected graph of an edge list as an int32 CSR, checked once, cached per tensor
     node_weights(deg, kind)                  the per-node weight of the sum (host float64, rounded once to fp32); None for cn / jaccard
+    scorer(edge_index, num_nodes, kind)                                           the LinkScorer of `kind` (link_eval.py)
     heuristic_scores(edge_index, num_nodes, pairs, kind)                          score [P]
     heuristic_ranks(edge_index, num_nodes, edges, kind, filter_edges=None)        LinkRanks, the score in the logit slot
 """
@@ -17,18 +18,13 @@ from torch import Tensor
 
 from .. import ops
 from .._lib import GnnmpError
-from ..operators import _lp_filter
+from . import link_eval as LE
 from .engine import LinkRanks
 
 KINDS = ("cn", "jaccard", "aa", "ra")
 
 _GRAPH_CACHE: Dict[int, Tuple[weakref.ref, int, int, Tuple[Tensor, Tensor], Dict[str, Optional[Tensor]]]] = {}
 _GRAPH_CACHE_MAX = 64
-
-
-def _check_kind(kind: str) -> None:
-    if kind not in KINDS:
-        raise ValueError(f"kind={kind!r} is not one of {KINDS}")
 
 
 def _build_simple_graph(edge_index: Tensor, num_nodes: int) -> Tuple[Tensor, Tensor]:
@@ -78,7 +74,7 @@ def node_weights(deg: Tensor, kind: str) -> Optional[Tensor]:
     """The weight vector of the common-neighbour sum for `kind`, fp32 on the host: aa 1 / ln(deg) where deg >= 2 else 0, ra 1 / deg where
     deg >= 1 else 0 -- float64 arithmetic on the integer degrees, rounded once to fp32 (the device's log never enters a score).  None for
     cn (every weight is 1) and jaccard."""
-    _check_kind(kind)
+    LE.check_kind(kind, KINDS)
     if kind in ("cn", "jaccard"):
         return None
     d = deg.detach().to("cpu", torch.float64)
@@ -89,8 +85,8 @@ def node_weights(deg: Tensor, kind: str) -> Optional[Tensor]:
     return w.to(torch.float32)
 
 
-def _scorer(edge_index: Tensor, num_nodes: int, kind: str):
-    _check_kind(kind)
+def _kernel_args(edge_index: Tensor, num_nodes: int, kind: str):
+    LE.check_kind(kind, KINDS)
     _, _, _, (rowptr, col), weights = _graph(edge_index, num_nodes)
     if kind not in weights:
         w = node_weights(rowptr[1:] - rowptr[:-1], kind)
@@ -98,25 +94,18 @@ def _scorer(edge_index: Tensor, num_nodes: int, kind: str):
     return rowptr, col, weights[kind], "jaccard" if kind == "jaccard" else "sum"
 
 
-def _pairs(who: str, pairs: Tensor) -> Tensor:
-    if pairs.dtype != torch.int64 or pairs.dim() != 2 or pairs.size(0) != 2:
-        raise GnnmpError(f"{who}: pairs must be an int64 [2, P] tensor, got {pairs.dtype} {tuple(pairs.shape)}")
-    return pairs.contiguous()
+def scorer(edge_index: Tensor, num_nodes: int, kind: str) -> LE.LinkScorer:
+    """`kind` on the simple graph of edge_index (cached) as link_eval scores and ranks with it."""
+    rowptr, col, weight, mode = _kernel_args(edge_index, num_nodes, kind)
+    return LE.LinkScorer("heuristic", num_nodes, lambda s, d: ops.lp_cn_score(rowptr, col, s, d, weight, mode),
+                         lambda s, d, frowptr, fcol: ops.lp_cn_rank(rowptr, col, s, d, weight, mode, frowptr, fcol))
 
 
 def heuristic_scores(edge_index: Tensor, num_nodes: int, pairs: Tensor, kind: str) -> Tensor:
     """score [P] (fp32) of the pairs [2, P] under `kind` on the simple graph of edge_index."""
-    rowptr, col, weight, mode = _scorer(edge_index, num_nodes, kind)
-    p = _pairs("heuristic_scores", pairs)
-    return ops.lp_cn_score(rowptr, col, p[0], p[1], weight, mode)
+    return LE.scores(scorer(edge_index, num_nodes, kind), pairs)
 
 
 def heuristic_ranks(edge_index: Tensor, num_nodes: int, edges: Tensor, kind: str, filter_edges: Optional[Tensor] = None) -> LinkRanks:
-    """Every true pair of edges [2, Q] ranked against all nodes as destinations under `kind` on the simple graph of edge_index, exactly
-    as LinkPredictionEngine.rank ranks with the trained scorer: the source, the destination and every c with (source, c) in filter_edges
-    [2, E] are no candidates; rank = 1 + n_greater + n_equal / 2.  The true pair's score stands in LinkRanks.logit."""
-    rowptr, col, weight, mode = _scorer(edge_index, num_nodes, kind)
-    e = _pairs("heuristic_ranks", edges)
-    frowptr, fcol = _lp_filter("heuristic_ranks", filter_edges, num_nodes)
-    score, n_greater, n_equal = ops.lp_cn_rank(rowptr, col, e[0], e[1], weight, mode, frowptr, fcol)
-    return LinkRanks.from_counts(n_greater, n_equal, score)
+    """link_eval.ranks under `kind` on the simple graph of edge_index, as LinkPredictionEngine.rank ranks with the trained scorer."""
+    return LE.ranks(scorer(edge_index, num_nodes, kind), edges, filter_edges)

@@ -8,6 +8,7 @@ first training step too.
     cos    the cosine of the two rows, rows normalised as the k-NN probe normalises them (a zero row scores 0)
     dot    the inner product of the raw rows (the GAE decoder without its sigmoid: the order is the same)
 
+    scorer(emb, kind)                                            the LinkScorer of `kind` (link_eval.py)
     embedding_scores(emb, pairs, kind)                           score [P]
     embedding_ranks(emb, edges, kind, filter_edges=None)         LinkRanks, the score in the logit slot
     pair_auc(scores, labels)                                     the area under the ROC curve, ties counted one half
@@ -21,35 +22,29 @@ import torch
 from torch import Tensor
 
 from .. import ops
-from ..operators import _lp_filter
+from . import link_eval as LE
 from .engine import LinkRanks
-from .link_heuristics import _pairs
 from .metrics import ranking_metrics
 
 KINDS = ("cos", "dot")
 
 
-def _check_kind(kind: str) -> None:
-    if kind not in KINDS:
-        raise ValueError(f"kind={kind!r} is not one of {KINDS}")
+def scorer(emb: Tensor, kind: str) -> LE.LinkScorer:
+    """`kind` on the rows of emb [N, d <= 256] as link_eval scores and ranks with it."""
+    LE.check_kind(kind, KINDS)
+    h = emb.detach().contiguous()
+    return LE.LinkScorer("embedding", emb.size(0), lambda s, d: ops.emb_link_score(h, s, d, kind),
+                         lambda s, d, frowptr, fcol: ops.emb_link_rank(h, s, d, kind, frowptr, fcol))
 
 
 def embedding_scores(emb: Tensor, pairs: Tensor, kind: str) -> Tensor:
     """score [P] (fp32) of the pairs [2, P] under `kind` from the rows of emb [N, d <= 256]."""
-    _check_kind(kind)
-    p = _pairs("embedding_scores", pairs)
-    return ops.emb_link_score(emb.detach().contiguous(), p[0], p[1], kind)
+    return LE.scores(scorer(emb, kind), pairs)
 
 
 def embedding_ranks(emb: Tensor, edges: Tensor, kind: str, filter_edges: Optional[Tensor] = None) -> LinkRanks:
-    """Every true pair of edges [2, Q] ranked against all nodes as destinations under `kind`, exactly as LinkPredictionEngine.rank ranks
-    with the trained scorer: the source, the destination and every c with (source, c) in filter_edges [2, E] are no candidates; rank =
-    1 + n_greater + n_equal / 2.  The true pair's score stands in LinkRanks.logit."""
-    _check_kind(kind)
-    e = _pairs("embedding_ranks", edges)
-    frowptr, fcol = _lp_filter("embedding_ranks", filter_edges, emb.size(0))
-    score, n_greater, n_equal = ops.emb_link_rank(emb.detach().contiguous(), e[0], e[1], kind, frowptr, fcol)
-    return LinkRanks.from_counts(n_greater, n_equal, score)
+    """link_eval.ranks under `kind` on the rows of emb [N, d <= 256], as LinkPredictionEngine.rank ranks with the trained scorer."""
+    return LE.ranks(scorer(emb, kind), edges, filter_edges)
 
 
 def pair_auc(scores: Tensor, labels: Tensor) -> float:

@@ -7,7 +7,7 @@ torch.  Autograd lives in operators.py.
 from __future__ import annotations
 
 import ctypes as C
-from typing import NamedTuple, Optional, Tuple
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import torch
 from torch import Tensor
@@ -1103,23 +1103,46 @@ def _lp_rank_args(who: str, h: Tensor, w0: Tensor, b0: Tensor, w3: Tensor, b3: T
     return _lp_filter_args(who, h.size(0), filter_rowptr, filter_col)
 
 
+def _rank_call(who: str, fn, lead, workspace_bytes, src: Tensor, dst: Tensor, num_nodes: int, filter_rowptr: Optional[Tensor],
+               filter_col: Optional[Tensor], anchor: Tensor, extra: tuple = ()) -> Tuple[Tensor, Tensor, Tensor]:
+    """The call of the all-candidate ranker fn = gmp_{who} behind its scorer's own checks: the pairs and the filter CSR checked, the three
+    outputs and the workspace (workspace_bytes(Q)) allocated where `anchor` lives.  lead(src, dst, Q) gives the C arguments up to the
+    filter, `extra` those between n_equal and the workspace.  Returns (score_true [Q], n_greater [Q] int32, n_equal [Q] int32)."""
+    fnnz = _lp_filter_args(who, num_nodes, filter_rowptr, filter_col)
+    _need(src, torch.int64, "src", 1); _need(dst, torch.int64, "dst", 1)
+    Q, dev = src.numel(), anchor.device
+    if dst.numel() != Q:
+        raise L.GnnmpError(f"{who}: src and dst differ in length")
+    score = torch.empty(Q, device=dev)
+    n_greater, n_equal = torch.empty(Q, dtype=torch.int32, device=dev), torch.empty(Q, dtype=torch.int32, device=dev)
+    ws = _ws(workspace_bytes(Q), dev)
+    L.check(fn(*lead(_ptr(src), _ptr(dst), Q), _ptr(filter_rowptr), _ptr(filter_col), fnnz, _ptr(score), _ptr(n_greater),
+                                           _ptr(n_equal), *extra, _ptr(ws), ws.numel(), _stream(anchor)), f"gmp_{who}")
+    return score, n_greater, n_equal
+
+
+def _score_call(who: str, fn, lead, workspace_bytes, src: Tensor, dst: Tensor, anchor: Tensor) -> Tensor:
+    """_rank_call for the pair scorer fn = gmp_{who}: score [P] of the pairs (src[p], dst[p]).  workspace_bytes None: it takes no workspace."""
+    _need(src, torch.int64, "src", 1); _need(dst, torch.int64, "dst", 1)
+    P, dev = src.numel(), anchor.device
+    if dst.numel() != P:
+        raise L.GnnmpError(f"{who}: src and dst differ in length")
+    score = torch.empty(P, device=dev)
+    ws = None if workspace_bytes is None else _ws(workspace_bytes(P), dev)
+    L.check(fn(*lead(_ptr(src), _ptr(dst), P), _ptr(score), *(() if ws is None else (_ptr(ws), ws.numel())),
+                                           _stream(anchor)), f"gmp_{who}")
+    return score
+
+
 def lp_rank(h: Tensor, src: Tensor, dst: Tensor, w0: Tensor, b0: Tensor, w3: Tensor, b3: Tensor, filter_rowptr: Optional[Tensor] = None,
             filter_col: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
     """Every true pair (src[q], dst[q]) ranked against all nodes of h [N, 256] (gnnmp.h gmp_lp_rank): returns (logit_true [Q],
     n_greater [Q] int32, n_equal [Q] int32) over the candidates c other than src[q], dst[q] and the entries of src[q]'s row of the
     optional filter CSR (int32 rowptr [N + 1] / col, row = source).  Logits are those of lp_score_fwd with p = 0, bit for bit."""
-    nnz = _lp_rank_args("lp_rank", h, w0, b0, w3, b3, filter_rowptr, filter_col)
-    _need(src, torch.int64, "src", 1); _need(dst, torch.int64, "dst", 1)
-    Q, N, dev, l = src.numel(), h.size(0), h.device, L.lib()
-    if dst.numel() != Q:
-        raise L.GnnmpError("lp_rank: src and dst differ in length")
-    logit = torch.empty(Q, device=dev)
-    n_greater, n_equal = torch.empty(Q, dtype=torch.int32, device=dev), torch.empty(Q, dtype=torch.int32, device=dev)
-    ws = _ws(l.gmp_lp_rank_workspace_bytes(Q, N), dev)
-    L.check(l.gmp_lp_rank(_ptr(h), _ptr(src), _ptr(dst), N, Q, h.size(1), w0.size(0), _ptr(w0), _ptr(b0), _ptr(w3), _ptr(b3),
-                          _ptr(filter_rowptr), _ptr(filter_col), nnz, _ptr(logit), _ptr(n_greater), _ptr(n_equal), _ptr(ws), ws.numel(),
-                          _stream(h)), "gmp_lp_rank")
-    return logit, n_greater, n_equal
+    _lp_rank_args("lp_rank", h, w0, b0, w3, b3, filter_rowptr, filter_col)
+    N = h.size(0)
+    return _rank_call("lp_rank", L.lib().gmp_lp_rank, lambda s, d, Q: (_ptr(h), s, d, N, Q, h.size(1), w0.size(0), _ptr(w0), _ptr(b0), _ptr(w3), _ptr(b3)),
+                      lambda Q: L.lib().gmp_lp_rank_workspace_bytes(Q, N), src, dst, N, filter_rowptr, filter_col, h)
 
 
 def lp_topk(h: Tensor, src: Tensor, k: int, w0: Tensor, b0: Tensor, w3: Tensor, b3: Tensor, filter_rowptr: Optional[Tensor] = None,
@@ -1142,21 +1165,23 @@ def lp_topk(h: Tensor, src: Tensor, k: int, w0: Tensor, b0: Tensor, w3: Tensor, 
 LP_CN_MODES = {"sum": 0, "jaccard": 1}                      # gmp_lp_cn_score / gmp_lp_cn_rank (gnnmp.h)
 
 
-def _lp_cn_args(who: str, rowptr: Tensor, col: Tensor, weight: Optional[Tensor], mode: str) -> Tuple[int, int, int]:
-    """(num_nodes, nnz, mode code) of a simple-graph CSR and its scorer (gnnmp.h gmp_lp_cn_score)."""
+def _simple_graph_args(who: str, rowptr: Tensor, col: Tensor, mode: str, modes: Dict[str, int]) -> Tuple[int, int, int]:
+    """(num_nodes, nnz, mode code) of a simple-graph CSR and its scorer's mode out of `modes` (gnnmp.h gmp_lp_cn_score, gmp_lp_walk_score)."""
     _need(rowptr, torch.int32, "rowptr", 1); _need(col, torch.int32, "col", 1)
     if rowptr.numel() < 1:
         raise L.GnnmpError(f"{who}: rowptr is empty (it has num_nodes + 1 entries)")
-    if mode not in LP_CN_MODES:
-        raise L.GnnmpError(f"{who}: mode={mode!r} is not one of {tuple(LP_CN_MODES)}")
-    N = rowptr.numel() - 1
+    if mode not in modes:
+        raise L.GnnmpError(f"{who}: mode={mode!r} is not one of {tuple(modes)}")
+    return rowptr.numel() - 1, col.numel(), modes[mode]
+
+
+def _node_weight_arg(who: str, weight: Optional[Tensor], num_nodes: int, refusal: Optional[str]) -> None:      # refusal: of a mode that takes none
     if weight is not None:
         _need(weight, torch.float32, "weight", 1)
-        if mode == "jaccard":
-            raise L.GnnmpError(f"{who}: Jaccard takes no weight array")
-        if weight.numel() != N:
-            raise L.GnnmpError(f"{who}: weight has {weight.numel()} entries for {N} nodes")
-    return N, col.numel(), LP_CN_MODES[mode]
+        if refusal:
+            raise L.GnnmpError(f"{who}: {refusal}")
+        if weight.numel() != num_nodes:
+            raise L.GnnmpError(f"{who}: weight has {weight.numel()} entries for {num_nodes} nodes")
 
 
 def lp_cn_score(rowptr: Tensor, col: Tensor, src: Tensor, dst: Tensor, weight: Optional[Tensor] = None, mode: str = "sum") -> Tensor:
@@ -1164,15 +1189,9 @@ def lp_cn_score(rowptr: Tensor, col: Tensor, src: Tensor, dst: Tensor, weight: O
     loops, rows strictly ascending; gnnmp.h gmp_lp_cn_score): mode "sum" the fp32 sum of weight[z] over the common neighbours z in
     ascending z (weight None: 1, the common-neighbour count), mode "jaccard" CN / (deg s + deg d - CN).  A pair with an endpoint outside
     the graph scores 0."""
-    N, nnz, code = _lp_cn_args("lp_cn_score", rowptr, col, weight, mode)
-    _need(src, torch.int64, "src", 1); _need(dst, torch.int64, "dst", 1)
-    P = src.numel()
-    if dst.numel() != P:
-        raise L.GnnmpError("lp_cn_score: src and dst differ in length")
-    score = torch.empty(P, device=rowptr.device)
-    L.check(L.lib().gmp_lp_cn_score(_ptr(rowptr), _ptr(col), N, nnz, _ptr(src), _ptr(dst), P, _ptr(weight), code, _ptr(score),
-                                    _stream(rowptr)), "gmp_lp_cn_score")
-    return score
+    N, nnz, code = _simple_graph_args("lp_cn_score", rowptr, col, mode, LP_CN_MODES)
+    _node_weight_arg("lp_cn_score", weight, N, "Jaccard takes no weight array" if mode == "jaccard" else None)
+    return _score_call("lp_cn_score", L.lib().gmp_lp_cn_score, lambda s, d, P: (_ptr(rowptr), _ptr(col), N, nnz, s, d, P, _ptr(weight), code), None, src, dst, rowptr)
 
 
 def lp_cn_rank(rowptr: Tensor, col: Tensor, src: Tensor, dst: Tensor, weight: Optional[Tensor] = None, mode: str = "sum",
@@ -1181,44 +1200,26 @@ def lp_cn_rank(rowptr: Tensor, col: Tensor, src: Tensor, dst: Tensor, weight: Op
     (score_true [Q], n_greater [Q] int32, n_equal [Q] int32) over the candidates c other than src[q], dst[q] and the entries of
     src[q]'s row of the optional filter CSR (lp_rank's).  A candidate's score has the bits lp_cn_score gives the pair; Jaccard is
     compared exactly in integers.  Nothing of size Q x N is allocated."""
-    N, nnz, code = _lp_cn_args("lp_cn_rank", rowptr, col, weight, mode)
-    fnnz = _lp_filter_args("lp_cn_rank", N, filter_rowptr, filter_col)
-    _need(src, torch.int64, "src", 1); _need(dst, torch.int64, "dst", 1)
-    Q, dev, l = src.numel(), rowptr.device, L.lib()
-    if dst.numel() != Q:
-        raise L.GnnmpError("lp_cn_rank: src and dst differ in length")
-    score = torch.empty(Q, device=dev)
-    n_greater, n_equal = torch.empty(Q, dtype=torch.int32, device=dev), torch.empty(Q, dtype=torch.int32, device=dev)
-    ws = _ws(l.gmp_lp_cn_rank_workspace_bytes(Q, N), dev)
-    L.check(l.gmp_lp_cn_rank(_ptr(rowptr), _ptr(col), N, nnz, _ptr(src), _ptr(dst), Q, _ptr(weight), code, _ptr(filter_rowptr),
-                             _ptr(filter_col), fnnz, _ptr(score), _ptr(n_greater), _ptr(n_equal), _ptr(ws), ws.numel(), _stream(rowptr)),
-            "gmp_lp_cn_rank")
-    return score, n_greater, n_equal
+    N, nnz, code = _simple_graph_args("lp_cn_rank", rowptr, col, mode, LP_CN_MODES)
+    _node_weight_arg("lp_cn_rank", weight, N, "Jaccard takes no weight array" if mode == "jaccard" else None)
+    return _rank_call("lp_cn_rank", L.lib().gmp_lp_cn_rank, lambda s, d, Q: (_ptr(rowptr), _ptr(col), N, nnz, s, d, Q, _ptr(weight), code),
+                      lambda Q: L.lib().gmp_lp_cn_rank_workspace_bytes(Q, N), src, dst, N, filter_rowptr, filter_col, rowptr)
 
 
 LP_WALK_MODES = {"sum": 0, "hops": 1}                       # gmp_lp_walk_score / gmp_lp_walk_rank (gnnmp.h)
 LP_WALK_MAX_ROUNDS = 64
 
 
-def _lp_walk_args(who: str, rowptr: Tensor, col: Tensor, rounds: int, damping: float, weight: Optional[Tensor], mode: str) -> Tuple[int, int, int]:
-    """(num_nodes, nnz, mode code) of a simple-graph CSR and its walk scorer (gnnmp.h gmp_lp_walk_score)."""
-    _need(rowptr, torch.int32, "rowptr", 1); _need(col, torch.int32, "col", 1)
-    if rowptr.numel() < 1:
-        raise L.GnnmpError(f"{who}: rowptr is empty (it has num_nodes + 1 entries)")
-    if mode not in LP_WALK_MODES:
-        raise L.GnnmpError(f"{who}: mode={mode!r} is not one of {tuple(LP_WALK_MODES)}")
+def _lp_walk_args(who: str, rowptr: Tensor, col: Tensor, rounds: int, damping: float, weight: Optional[Tensor], mode: str):
+    """_simple_graph_args and the walk's own two, as a function of (src, dst, count) that gives the C arguments up to the scorer's end."""
+    N, nnz, code = _simple_graph_args(who, rowptr, col, mode, LP_WALK_MODES)
     if not 1 <= int(rounds) <= LP_WALK_MAX_ROUNDS:
         raise L.GnnmpError(f"{who}: rounds={rounds} (1 <= rounds <= {LP_WALK_MAX_ROUNDS})")
     if mode == "sum" and not 0.0 < float(damping) <= 1.0:
         raise L.GnnmpError(f"{who}: damping={damping} (0 < damping <= 1)")
-    N = rowptr.numel() - 1
-    if weight is not None:
-        _need(weight, torch.float32, "weight", 1)
-        if mode == "hops":
-            raise L.GnnmpError(f"{who}: hops take no weight array")
-        if weight.numel() != N:
-            raise L.GnnmpError(f"{who}: weight has {weight.numel()} entries for {N} nodes")
-    return N, col.numel(), LP_WALK_MODES[mode]
+    _node_weight_arg(who, weight, N, "hops take no weight array" if mode == "hops" else None)
+    return (N, lambda s, d, n: (_ptr(rowptr), _ptr(col), N, nnz, s, d, n, _ptr(weight), float(damping), int(rounds), code),
+            lambda n: L.lib().gmp_lp_walk_workspace_bytes(n, N))
 
 
 def lp_walk_score(rowptr: Tensor, col: Tensor, src: Tensor, dst: Tensor, rounds: int, damping: float = 1.0, weight: Optional[Tensor] = None,
@@ -1228,16 +1229,8 @@ def lp_walk_score(rowptr: Tensor, col: Tensor, src: Tensor, dst: Tensor, rounds:
     e_src, every row folded in ascending neighbour order (weight None: 1); mode "hops" minus the BFS distance, -(rounds + 1) beyond
     `rounds` hops.  An endpoint outside the graph scores 0 / -(rounds + 1).  Pairs with equal sources next to each other share one
     propagation."""
-    N, nnz, code = _lp_walk_args("lp_walk_score", rowptr, col, rounds, damping, weight, mode)
-    _need(src, torch.int64, "src", 1); _need(dst, torch.int64, "dst", 1)
-    P, dev, l = src.numel(), rowptr.device, L.lib()
-    if dst.numel() != P:
-        raise L.GnnmpError("lp_walk_score: src and dst differ in length")
-    score = torch.empty(P, device=dev)
-    ws = _ws(l.gmp_lp_walk_workspace_bytes(P, N), dev)
-    L.check(l.gmp_lp_walk_score(_ptr(rowptr), _ptr(col), N, nnz, _ptr(src), _ptr(dst), P, _ptr(weight), float(damping), int(rounds), code,
-                                _ptr(score), _ptr(ws), ws.numel(), _stream(rowptr)), "gmp_lp_walk_score")
-    return score
+    _, lead, workspace_bytes = _lp_walk_args("lp_walk_score", rowptr, col, rounds, damping, weight, mode)
+    return _score_call("lp_walk_score", L.lib().gmp_lp_walk_score, lead, workspace_bytes, src, dst, rowptr)
 
 
 def lp_walk_rank(rowptr: Tensor, col: Tensor, src: Tensor, dst: Tensor, rounds: int, damping: float = 1.0, weight: Optional[Tensor] = None,
@@ -1246,19 +1239,8 @@ def lp_walk_rank(rowptr: Tensor, col: Tensor, src: Tensor, dst: Tensor, rounds: 
     (score_true [Q], n_greater [Q] int32, n_equal [Q] int32) over the candidates c other than src[q], dst[q] and the entries of
     src[q]'s row of the optional filter CSR (lp_rank's).  A candidate's score has the bits lp_walk_score gives the pair.  One workgroup
     per query keeps its vectors in LDS (num_nodes <= gmp_lp_walk_lds_nodes()) or in a bounded workspace: nothing of size Q x N."""
-    N, nnz, code = _lp_walk_args("lp_walk_rank", rowptr, col, rounds, damping, weight, mode)
-    fnnz = _lp_filter_args("lp_walk_rank", N, filter_rowptr, filter_col)
-    _need(src, torch.int64, "src", 1); _need(dst, torch.int64, "dst", 1)
-    Q, dev, l = src.numel(), rowptr.device, L.lib()
-    if dst.numel() != Q:
-        raise L.GnnmpError("lp_walk_rank: src and dst differ in length")
-    score = torch.empty(Q, device=dev)
-    n_greater, n_equal = torch.empty(Q, dtype=torch.int32, device=dev), torch.empty(Q, dtype=torch.int32, device=dev)
-    ws = _ws(l.gmp_lp_walk_workspace_bytes(Q, N), dev)
-    L.check(l.gmp_lp_walk_rank(_ptr(rowptr), _ptr(col), N, nnz, _ptr(src), _ptr(dst), Q, _ptr(weight), float(damping), int(rounds), code,
-                               _ptr(filter_rowptr), _ptr(filter_col), fnnz, _ptr(score), _ptr(n_greater), _ptr(n_equal), _ptr(ws), ws.numel(),
-                               _stream(rowptr)), "gmp_lp_walk_rank")
-    return score, n_greater, n_equal
+    N, lead, workspace_bytes = _lp_walk_args("lp_walk_rank", rowptr, col, rounds, damping, weight, mode)
+    return _rank_call("lp_walk_rank", L.lib().gmp_lp_walk_rank, lead, workspace_bytes, src, dst, N, filter_rowptr, filter_col, rowptr)
 
 
 EMB_LINK_MODES = {"cos": 0, "dot": 1}                       # gmp_emb_link_score / gmp_emb_link_rank (gnnmp.h)
@@ -1282,13 +1264,9 @@ def emb_link_score(h: Tensor, src: Tensor, dst: Tensor, mode: str = "cos") -> Te
     """The score of every pair (src[p], dst[p]) from the rows of h [N, d <= 256] alone (gnnmp.h gmp_emb_link_score; csrc/emb_link.hip):
     mode "cos" the cosine of the two rows, normalised as knn_topk normalises (a zero row scores 0), mode "dot" their inner product.  An
     endpoint outside [0, N) reads as a zero row.  Returns score [P]."""
-    N, P, code = _emb_link_args("emb_link_score", h, src, dst, mode)
-    dev, l = h.device, L.lib()
-    score = torch.empty(P, device=dev)
-    ws = _ws(l.gmp_emb_link_workspace_bytes(N, P, h.size(1)), dev)
-    L.check(l.gmp_emb_link_score(_ptr(h), N, h.size(1), code, _ptr(src), _ptr(dst), P, _ptr(score), _ptr(ws), ws.numel(), _stream(h)),
-            "gmp_emb_link_score")
-    return score
+    N, _, code = _emb_link_args("emb_link_score", h, src, dst, mode)
+    return _score_call("emb_link_score", L.lib().gmp_emb_link_score, lambda s, d, P: (_ptr(h), N, h.size(1), code, s, d, P),
+                       lambda P: L.lib().gmp_emb_link_workspace_bytes(N, P, h.size(1)), src, dst, h)
 
 
 def emb_link_rank(h: Tensor, src: Tensor, dst: Tensor, mode: str = "cos", filter_rowptr: Optional[Tensor] = None,
@@ -1304,15 +1282,10 @@ def emb_link_rank(h: Tensor, src: Tensor, dst: Tensor, mode: str = "cos", filter
             raise L.GnnmpError("emb_link_rank: pass the filter as a CSR or as filter_edges, not both")
         csr = csr_build(filter_edges, N)
         filter_rowptr, filter_col = csr.rowptr_t, csr.col_t
-    fnnz = _lp_filter_args("emb_link_rank", N, filter_rowptr, filter_col)
-    dev, l = h.device, L.lib()
-    score = torch.empty(Q, device=dev)
-    n_greater, n_equal = torch.empty(Q, dtype=torch.int32, device=dev), torch.empty(Q, dtype=torch.int32, device=dev)
-    mat = torch.empty(Q, N, device=dev) if return_matrix else None
-    ws = _ws(l.gmp_emb_link_workspace_bytes(N, Q, h.size(1)), dev)
-    L.check(l.gmp_emb_link_rank(_ptr(h), N, h.size(1), code, _ptr(src), _ptr(dst), Q, _ptr(filter_rowptr), _ptr(filter_col), fnnz, _ptr(score),
-                                _ptr(n_greater), _ptr(n_equal), _ptr(mat), _ptr(ws), ws.numel(), _stream(h)), "gmp_emb_link_rank")
-    return (score, n_greater, n_equal, mat) if return_matrix else (score, n_greater, n_equal)
+    mat = torch.empty(Q, N, device=h.device) if return_matrix else None
+    out = _rank_call("emb_link_rank", L.lib().gmp_emb_link_rank, lambda s, d, Q: (_ptr(h), N, h.size(1), code, s, d, Q),
+                     lambda Q: L.lib().gmp_emb_link_workspace_bytes(N, Q, h.size(1)), src, dst, N, filter_rowptr, filter_col, h, extra=(_ptr(mat),))
+    return (*out, mat) if return_matrix else out
 
 
 def graph_simple_check(rowptr: Tensor, col: Tensor) -> Tensor:

@@ -133,7 +133,7 @@ def attempt(fn):
 
 
 def bench_case(graph, N, pos, known, kind: str, rounds: int, a) -> dict:
-    rowptr, col, weight, damping, _ = LW._scorer(graph, N, kind)
+    rowptr, col, weight, damping, _ = LW._kernel_args(graph, N, kind)
     csr = csr_of(known, N)
     frp, fcl = csr.rowptr_t.to(torch.int64), csr.col_t.to(torch.int64)
     res = {"kind": kind, "rounds": rounds}

@@ -14,6 +14,9 @@
 plus the two exact-arithmetic row generators of knn_ref."""
 import numpy as np
 
+import link_rank_ref as P
+from link_rank_ref import rank_of  # noqa: F401  (re-exported)
+
 from knn_ref import four_ones, normalize, sixteen_signs  # noqa: F401  (the generators are re-exported)
 
 KINDS = ("cos", "dot")
@@ -45,25 +48,8 @@ def ranks(S, src, dst, filter_edges=None, similarity=None):
     per_query = similarity is not None
     M = np.asarray(similarity) if per_query else np.asarray(S)
     n = M.shape[1]
-    filt = {}
-    if filter_edges is not None:
-        for s, c in zip(*np.asarray(filter_edges)):
-            filt.setdefault(int(s), set()).add(int(c))
-    st, ng, ne = [], [], []
-    for q, (s, d) in enumerate(zip(src, dst)):
-        s, d = int(s), int(d)
-        row = _row(M, q, s, n, per_query)
-        true = row[d] if 0 <= d < n else row.dtype.type(0)
-        skip = filt.get(s, set()) if 0 <= s < n else set()
-        cand = np.array([c != s and c != d and c not in skip for c in range(n)], dtype=bool)
-        st.append(true)
-        ng.append(int((row[cand] > true).sum()))
-        ne.append(int((row[cand] == true).sum()))
-    return np.array(st), np.array(ng, dtype=np.int64), np.array(ne, dtype=np.int64)
-
-
-def rank_of(n_greater, n_equal):
-    return 1.0 + np.asarray(n_greater, dtype=np.float64) + 0.5 * np.asarray(n_equal, dtype=np.float64)
+    return P.ranks(n, src, dst, lambda q, s: _row(M, q, s, n, per_query), lambda q, s, d, row: row[d] if 0 <= d < n else row.dtype.type(0),
+                   P.filter_rows(filter_edges, n))
 
 
 def auc(scores_, labels):

@@ -5,6 +5,9 @@ import math
 
 import numpy as np
 
+import link_rank_ref as P
+from link_rank_ref import filter_rows, rank_of  # noqa: F401  (re-exported)
+
 KINDS = ("cn", "jaccard", "aa", "ra")
 
 
@@ -60,42 +63,19 @@ def pair_scores(rowptr, col, src, dst, w=None, mode="sum"):
     return np.asarray(out, dtype=np.float64), cns, unis
 
 
-def filter_rows(filter_edges, n):
-    """{source: destinations} of known edges [2, E]; entries outside [0, n) are dropped."""
-    rows = {}
-    if filter_edges is not None:
-        for s, d in np.asarray(filter_edges, dtype=np.int64).reshape(2, -1).T.tolist():
-            if 0 <= s < n and 0 <= d < n:
-                rows.setdefault(s, []).append(d)
-    return rows
-
-
 def ranks(rowptr, col, src, dst, w=None, mode="sum", filt=None):
     """(score_true [Q], n_greater [Q], n_equal [Q]) of the ranking query: candidates c in [0, n) except src, dst and filt[src]."""
     n = len(rowptr) - 1
     deg = np.diff(rowptr)
-    filt = filt or {}
-    st, ng, ne = pair_scores(rowptr, col, src, dst, w, mode)[0], [], []
+    st = pair_scores(rowptr, col, src, dst, w, mode)[0]
     _, tcn, tuni = pair_scores(rowptr, col, src, dst, None, "jaccard")
-    for q, (s, d) in enumerate(zip(np.asarray(src).tolist(), np.asarray(dst).tolist())):
-        acc = accumulate(rowptr, col, s, w)
-        valid = np.ones(n, dtype=bool)
-        for c in [s, d] + [c for c in filt.get(s, []) if 0 <= c < n]:
-            if 0 <= c < n:
-                valid[c] = False
-        if mode == "jaccard":
-            cn = acc.astype(np.int64).astype(object)
-            uni = (deg + (deg[s] if 0 <= s < n else 0)).astype(object) - cn
-            cn, uni = np.where(uni > 0, cn, 0), np.where(uni > 0, uni, 1)                       # an empty union scores 0 / 1
-            a, b = (tcn[q], tuni[q]) if tuni[q] > 0 else (0, 1)
-            left, right = cn * b, a * uni                                                       # Python integers
-            greater, equal = (left > right).astype(bool), (left == right).astype(bool)
-        else:
-            t = np.float32(st[q])
-            greater, equal = acc > t, acc == t
-        ng.append(int((greater & valid).sum())); ne.append(int((equal & valid).sum()))
-    return st, np.asarray(ng, dtype=np.int64), np.asarray(ne, dtype=np.int64)
 
+    def jaccard(q, s, acc):
+        cn = acc.astype(np.int64).astype(object)
+        uni = (deg + (deg[s] if 0 <= s < n else 0)).astype(object) - cn
+        cn, uni = np.where(uni > 0, cn, 0), np.where(uni > 0, uni, 1)                           # an empty union scores 0 / 1
+        a, b = (tcn[q], tuni[q]) if tuni[q] > 0 else (0, 1)
+        left, right = cn * b, a * uni                                                           # Python integers
+        return (left > right).astype(bool), (left == right).astype(bool)
 
-def rank_of(n_greater, n_equal):
-    return 1.0 + np.asarray(n_greater, dtype=np.float64) + 0.5 * np.asarray(n_equal, dtype=np.float64)
+    return P.ranks(n, src, dst, lambda q, s: accumulate(rowptr, col, s, w), lambda q, s, d, row: st[q], filt, jaccard if mode == "jaccard" else None)

@@ -5,6 +5,8 @@ one) and x86 keeps subnormals.  Vectorised over the rows (and the sources) with 
 row v's p-th entry is its p-th add.  The graph, the 1 / deg weights, the filter rows and the half-tie rank are lp_heur_ref's."""
 import numpy as np
 
+import link_rank_ref as P
+
 from lp_heur_ref import filter_rows, rank_of, simple_csr, weights  # noqa: F401  (re-exported for the tests)
 
 KINDS = ("katz", "ppr", "hops")
@@ -115,17 +117,8 @@ def pair_scores(rowptr, col, src, dst, rounds, damping=1.0, w=None, mode="sum"):
 
 def ranks(rowptr, col, src, dst, rounds, damping=1.0, w=None, mode="sum", filt=None):
     """(score_true float32 [Q], n_greater int64 [Q], n_equal int64 [Q]): candidates c in [0, n) except src, dst and filt[src]."""
-    n = len(rowptr) - 1
-    src, dst = np.asarray(src, dtype=np.int64).reshape(-1), np.asarray(dst, dtype=np.int64).reshape(-1)
-    filt = filt or {}
+    src = np.asarray(src, dtype=np.int64).reshape(-1)
     uniq, inv = np.unique(src, return_inverse=True)
     every = all_scores(rowptr, col, uniq, rounds, damping, w, mode)
-    st, ng, ne = pair_scores(rowptr, col, src, dst, rounds, damping, w, mode), [], []
-    for q, (s, d) in enumerate(zip(src.tolist(), dst.tolist())):
-        valid = np.ones(n, dtype=bool)
-        for c in [s, d] + list(filt.get(s, [])):
-            if 0 <= c < n:
-                valid[c] = False
-        row = every[inv[q]]
-        ng.append(int(((row > st[q]) & valid).sum())); ne.append(int(((row == st[q]) & valid).sum()))
-    return st, np.asarray(ng, dtype=np.int64), np.asarray(ne, dtype=np.int64)
+    st = pair_scores(rowptr, col, src, dst, rounds, damping, w, mode)
+    return P.ranks(len(rowptr) - 1, src, dst, lambda q, s: every[inv[q]], lambda q, s, d, row: st[q], filt)

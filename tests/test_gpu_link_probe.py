@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import link_probe_ref as R
+from link_rank_util import t as _t
 from gnn_pretraining_amd import _lib as L, ops
 from gnn_pretraining_amd.finetune import link_probe as LPR
 from gnn_pretraining_amd.finetune.metrics import ranking_metrics
@@ -18,10 +19,6 @@ from gnn_pretraining_amd.finetune.metrics import ranking_metrics
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 GMP_ERR_ARG, GMP_ERR_WORKSPACE = -1, -3
-
-
-def _t(a, dtype):
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).to(DEV)
 
 
 def _bits(t):

@@ -4,14 +4,13 @@ order and counts are integers, so everything is compared for EQUALITY; only Jacc
 one float32 ulp around the float64 quotient (IEEE division is within half an ulp; the margin allows one that is not correctly rounded)."""
 import ctypes as C
 import functools
-import json
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 import lp_heur_ref as R
+from link_rank_util import N_BIG, big as _big, filter_csr as _filter_csr, run_cli as _run_cli, t as _t
 from gnn_pretraining_amd import _lib as L, ops
 from gnn_pretraining_amd._lib import GnnmpError
 from gnn_pretraining_amd.finetune import link_heuristics as LH
@@ -22,21 +21,8 @@ DEV = "cuda"
 GMP_ERR_ARG = -1
 
 
-def _t(a, dtype):
-    return torch.as_tensor(np.ascontiguousarray(a)).to(dtype).to(DEV).contiguous()
-
-
 def _mode(kind):
     return "jaccard" if kind == "jaccard" else "sum"
-
-
-def _filter_csr(rows, n):
-    """The filter CSR (int32, on the device) with row s holding rows[s] verbatim: any order, duplicates, entries out of range."""
-    rowptr, col = [0], []
-    for s in range(n):
-        col += list(rows.get(s, []))
-        rowptr.append(len(col))
-    return _t(rowptr, torch.int32), _t(np.asarray(col, dtype=np.int64), torch.int32)
 
 
 def _gpu_rank(rowptr, col, src, dst, w=None, mode="sum", filt_rows=None):
@@ -67,48 +53,6 @@ def _assert_ranks(got, want, mode):
 
 
 # ---------------------------------------------------------------------------- 1. the four kinds on a seeded random graph
-N_BIG, HUB = 700, 0
-
-
-@functools.lru_cache(maxsize=None)
-def _big():
-    """700 nodes: node 0 a hub of degree 300 (longer than a 256-thread stride), 690 .. 694 of degree 1, 695 .. 699 isolated, about 2,100
-    random edges; 97 queries -- the hub and an isolated node as sources, an isolated destination, 48 destinations at distance two,
-    duplicates -- and known edges to filter."""
-    rng = np.random.RandomState(20240607)
-    hub = [(HUB, int(v)) for v in rng.choice(np.arange(1, 690), 300, replace=False)]
-    pend = [(690 + i, int(rng.randint(1, 690))) for i in range(5)]
-    rnd = rng.randint(1, 690, size=(1800, 2)).tolist()
-    edges = np.asarray(hub + pend + rnd, dtype=np.int64).T                       # one direction only, with the odd loop and duplicate
-    rowptr, col = R.simple_csr(edges, N_BIG)
-    deg = np.diff(rowptr)
-    assert deg[HUB] == 300 and bool((deg[690:695] == 1).all()) and bool((deg[695:] == 0).all())
-    src, dst = [], []
-    for _ in range(10):
-        src.append(HUB); dst.append(int(rng.randint(1, N_BIG)))
-    for _ in range(3):
-        src.append(695); dst.append(int(rng.randint(0, 690)))
-    for _ in range(2):
-        src.append(int(rng.randint(1, 690))); dst.append(697)
-    while len(src) < 63:                                                         # 48 at distance two
-        s = int(rng.randint(0, 690))
-        if deg[s] == 0:
-            continue
-        z = int(rng.choice(col[rowptr[s]:rowptr[s + 1]]))
-        d = int(rng.choice(col[rowptr[z]:rowptr[z + 1]]))
-        if d != s:
-            src.append(s); dst.append(d)
-    while len(src) < 92:
-        s, d = (int(v) for v in rng.randint(0, N_BIG, size=2))
-        if s != d:
-            src.append(s); dst.append(d)
-    src += src[:5]; dst += dst[:5]                                               # duplicates
-    assert len(src) == 97
-    half = edges[:, rng.rand(edges.shape[1]) < 0.5]
-    known = np.concatenate([half, half[::-1], rng.randint(0, N_BIG, size=(2, 300))], axis=1)
-    return edges, rowptr, col, np.asarray(src), np.asarray(dst), known
-
-
 @functools.lru_cache(maxsize=None)
 def _big_ref(kind, filtered):
     edges, rowptr, col, src, dst, known = _big()
@@ -175,40 +119,6 @@ def test_sums_add_in_ascending_z():
     assert (want[0].tolist(), want[1].tolist(), want[2].tolist()) == ([16777216.0, 0.0], [0, 2], [1, 3])
 
 
-# ---------------------------------------------------------------------------- 4. the filter row
-def test_filter_rows_unsorted_duplicated_out_of_range_empty_and_total():
-    edges, rowptr, col, _, _, _ = _big()
-    rng = np.random.RandomState(5)
-    src, dst = np.asarray([HUB, 17, 23, 40]), np.asarray([33, 90, 91, 92])
-    everyone = rng.permutation(N_BIG).tolist()
-    rows = {HUB: [650, 3, 3, 650, -5, N_BIG, N_BIG + 100, HUB, 33, 12, 2 ** 31 - 1, 3] + rng.randint(0, N_BIG, size=40).tolist(),
-            17: [],                                                              # an empty row
-            23: everyone + everyone[:7],                                         # every candidate filtered: 0 and 0
-            41: [1, 2, 3]}                                                       # another source's row is not read
-    for kind in ("cn", "ra", "jaccard"):
-        w = R.weights(rowptr, kind)
-        got = _gpu_rank(rowptr, col, src, dst, w, _mode(kind), rows)
-        _assert_ranks(got, R.ranks(rowptr, col, src, dst, w, _mode(kind), rows), _mode(kind))
-        assert got[1][2] == 0 and got[2][2] == 0
-        plain = _gpu_rank(rowptr, col, src[[1, 3]], dst[[1, 3]], w, _mode(kind))
-        assert np.array_equal(plain[1], got[1][[1, 3]]) and np.array_equal(plain[2], got[2][[1, 3]])
-
-
-# ---------------------------------------------------------------------------- 5. ranking agrees with scoring the explicit pair list
-@pytest.mark.parametrize("kind", ["cn", "aa", "ra"])
-def test_rank_counts_equal_counting_over_explicit_pairs(kind):
-    edges, rowptr, col, src, dst, _ = _big()
-    w = R.weights(rowptr, kind)
-    qs = [0, 10, 13, 15, 20, 40, 70, 91]
-    st, ng, ne = _gpu_rank(rowptr, col, src[qs], dst[qs], w)
-    cand = np.arange(N_BIG)
-    for i, q in enumerate(qs):
-        every = _gpu_score(rowptr, col, np.full(N_BIG, src[q]), cand, w)
-        valid = (cand != src[q]) & (cand != dst[q])
-        assert every[dst[q]] == st[i]
-        assert int(((every > st[i]) & valid).sum()) == ng[i] and int(((every == st[i]) & valid).sum()) == ne[i]
-
-
 # ---------------------------------------------------------------------------- 6. Jaccard is compared in integers
 def test_jaccard_equal_quotients_from_different_counts_tie():
     """J(0, 3) = 1 / 2 and J(0, 4) = 2 / 4."""
@@ -240,17 +150,6 @@ def test_jaccard_quotients_closer_than_float32_are_still_ordered():
     assert want[1].tolist() == [1, 0] and want[2].tolist() == [0, 0]             # 2 is above 1; nothing is above or level with 2
     got = _gpu_rank(rowptr, col, src, dst, None, "jaccard")
     _assert_ranks(got, want, "jaccard")
-
-
-# ---------------------------------------------------------------------------- 7. repeatability
-@pytest.mark.parametrize("kind", ["aa", "jaccard"])
-def test_two_calls_and_split_calls_are_bitwise_equal(kind):
-    edges, rowptr, col, src, dst, known = _big()
-    w, filt = R.weights(rowptr, kind), R.filter_rows(known, N_BIG)
-    one, two = (_gpu_rank(rowptr, col, src, dst, w, _mode(kind), filt) for _ in range(2))
-    head, tail = (_gpu_rank(rowptr, col, src[sl], dst[sl], w, _mode(kind), filt) for sl in (slice(0, 48), slice(48, None)))
-    for a, b, h, t in zip(one, two, head, tail):
-        assert a.tobytes() == b.tobytes() and a.tobytes() == np.concatenate([h, t]).tobytes()
 
 
 # ---------------------------------------------------------------------------- 8. what is accepted and what is refused
@@ -342,19 +241,6 @@ def test_argument_errors_and_empty_inputs():
 
 
 # ---------------------------------------------------------------------------- 9. the command-line path
-def _run_cli(tmp_path, monkeypatch, name, extra):
-    from gnn_pretraining_amd.finetune import finetune as FT
-    monkeypatch.setattr(FT, "OUTPUT_DIR", tmp_path / name)
-    log = tmp_path / f"{name}.jsonl"
-    monkeypatch.setattr(sys, "argv", ["finetune", "--domain_name", "Cora_LP", "--finetune_strategy", "full_finetune", "--pretrained_scheme", "b1",
-                                      "--seed", "5", "--epochs", "1", "--data-root", str(tmp_path / "data"), "--data-scale", "0.1",
-                                      "--log", str(log)] + extra)
-    FT.main()
-    rec = [json.loads(line) for line in log.read_text().splitlines()]
-    state = torch.load(next((tmp_path / name).glob("model_*.pt")), map_location="cpu", weights_only=True)["model_state_dict"]
-    return rec, state
-
-
 def test_cli_lp_heuristics_logs_the_sixteen_keys_and_leaves_training_alone(tmp_path, monkeypatch):
     """python -m gnn_pretraining_amd.finetune.finetune ... --lp-heuristics (no engine), in process: one epoch on the synthetic Cora_LP
     stand-in.  The test record carries the 16 baseline keys, each the ranking_metrics of the reference's ranks on the dataset's own

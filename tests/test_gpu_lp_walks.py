@@ -3,8 +3,6 @@ against the CPU reference of tests/lp_walk_ref.py.  Scores are float32 folds in 
 integers, so everything is compared for EQUALITY."""
 import ctypes as C
 import functools
-import json
-import sys
 
 import numpy as np
 import pytest
@@ -12,6 +10,7 @@ import torch
 
 import lp_heur_ref as R
 import lp_walk_ref as W
+from link_rank_util import HUB, N_BIG, big as _big, filter_csr as _filter_csr, run_cli as _run_cli, t as _t
 from gnn_pretraining_amd import _lib as L, ops
 from gnn_pretraining_amd._lib import GnnmpError
 from gnn_pretraining_amd.finetune import link_heuristics as LH, link_walks as LW
@@ -21,19 +20,6 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda"
 GMP_ERR_ARG = -1
 ROUNDS = {"katz": 4, "ppr": 10, "hops": 4}
-
-
-def _t(a, dtype):
-    return torch.as_tensor(np.ascontiguousarray(a)).to(dtype).to(DEV).contiguous()
-
-
-def _filter_csr(rows, n):
-    """The filter CSR (int32, on the device) with row s holding rows[s] verbatim: any order, duplicates, entries out of range."""
-    rowptr, col = [0], []
-    for s in range(n):
-        col += list(rows.get(s, []))
-        rowptr.append(len(col))
-    return _t(rowptr, torch.int32), _t(np.asarray(col, dtype=np.int64), torch.int32)
 
 
 def _gpu_rank(rowptr, col, src, dst, rounds, damping=1.0, w=None, mode="sum", filt_rows=None):
@@ -56,48 +42,6 @@ def _assert_ranks(got, want):
 
 
 # ---------------------------------------------------------------------------- 1. the three kinds on a seeded random graph
-N_BIG, HUB = 700, 0
-
-
-@functools.lru_cache(maxsize=None)
-def _big():
-    """The recipe of test_gpu_lp_heuristics._big: 700 nodes, node 0 a hub of degree 300, 690 .. 694 of degree 1, 695 .. 699 isolated,
-    about 2,100 random edges; 97 queries -- the hub and an isolated node as sources, an isolated destination, 48 destinations at
-    distance two, duplicates -- and known edges to filter."""
-    rng = np.random.RandomState(20240607)
-    hub = [(HUB, int(v)) for v in rng.choice(np.arange(1, 690), 300, replace=False)]
-    pend = [(690 + i, int(rng.randint(1, 690))) for i in range(5)]
-    rnd = rng.randint(1, 690, size=(1800, 2)).tolist()
-    edges = np.asarray(hub + pend + rnd, dtype=np.int64).T                       # one direction only, with the odd loop and duplicate
-    rowptr, col = R.simple_csr(edges, N_BIG)
-    deg = np.diff(rowptr)
-    assert deg[HUB] == 300 and bool((deg[690:695] == 1).all()) and bool((deg[695:] == 0).all())
-    src, dst = [], []
-    for _ in range(10):
-        src.append(HUB); dst.append(int(rng.randint(1, N_BIG)))
-    for _ in range(3):
-        src.append(695); dst.append(int(rng.randint(0, 690)))
-    for _ in range(2):
-        src.append(int(rng.randint(1, 690))); dst.append(697)
-    while len(src) < 63:                                                         # 48 at distance two
-        s = int(rng.randint(0, 690))
-        if deg[s] == 0:
-            continue
-        z = int(rng.choice(col[rowptr[s]:rowptr[s + 1]]))
-        d = int(rng.choice(col[rowptr[z]:rowptr[z + 1]]))
-        if d != s:
-            src.append(s); dst.append(d)
-    while len(src) < 92:
-        s, d = (int(v) for v in rng.randint(0, N_BIG, size=2))
-        if s != d:
-            src.append(s); dst.append(d)
-    src += src[:5]; dst += dst[:5]                                               # duplicates
-    assert len(src) == 97
-    half = edges[:, rng.rand(edges.shape[1]) < 0.5]
-    known = np.concatenate([half, half[::-1], rng.randint(0, N_BIG, size=(2, 300))], axis=1)
-    return edges, rowptr, col, np.asarray(src), np.asarray(dst), known
-
-
 @functools.lru_cache(maxsize=None)
 def _big_ref(kind, filtered):
     edges, rowptr, col, src, dst, known = _big()
@@ -206,43 +150,6 @@ def test_subnormals_are_kept_and_hops_do_not_read_them():
     assert hops.tolist() == [0.0, -1.0, -2.0, -3.0, -4.0, -5.0, -6.0, -6.0]
 
 
-# ---------------------------------------------------------------------------- 5. the filter row
-def test_filter_rows_unsorted_duplicated_out_of_range_empty_and_total():
-    edges, rowptr, col, _, _, _ = _big()
-    rng = np.random.RandomState(5)
-    src, dst = np.asarray([HUB, 17, 23, 40]), np.asarray([33, 90, 91, 92])
-    everyone = rng.permutation(N_BIG).tolist()
-    rows = {HUB: [650, 3, 3, 650, -5, N_BIG, N_BIG + 100, HUB, 33, 12, 2 ** 31 - 1, 3] + rng.randint(0, N_BIG, size=40).tolist(),
-            17: [],                                                              # an empty row
-            23: everyone + everyone[:7],                                         # every candidate filtered: 0 and 0
-            41: [1, 2, 3]}                                                       # another source's row is not read
-    for kind in W.KINDS:
-        w, a, mode = W.params(rowptr, kind)
-        got = _gpu_rank(rowptr, col, src, dst, ROUNDS[kind], a, w, mode, rows)
-        _assert_ranks(got, W.ranks(rowptr, col, src, dst, ROUNDS[kind], a, w, mode, rows))
-        assert got[1][2] == 0 and got[2][2] == 0
-        plain = _gpu_rank(rowptr, col, src[[1, 3]], dst[[1, 3]], ROUNDS[kind], a, w, mode)
-        assert np.array_equal(plain[1], got[1][[1, 3]]) and np.array_equal(plain[2], got[2][[1, 3]])
-
-
-# ---------------------------------------------------------------------------- 6. ranking agrees with scoring the explicit pair list
-@pytest.mark.parametrize("kind", W.KINDS)
-def test_rank_counts_equal_counting_over_explicit_pairs(kind):
-    edges, rowptr, col, src, dst, _ = _big()
-    w, a, mode = W.params(rowptr, kind)
-    qs = [0, 10, 13, 15, 20, 40, 70, 91]
-    st, ng, ne = _gpu_rank(rowptr, col, src[qs], dst[qs], ROUNDS[kind], a, w, mode)
-    cand = np.arange(N_BIG)
-    every = _gpu_score(rowptr, col, np.repeat(src[qs], N_BIG), np.tile(cand, len(qs)), ROUNDS[kind], a, w, mode).reshape(len(qs), N_BIG)
-    for i, q in enumerate(qs):
-        valid = (cand != src[q]) & (cand != dst[q])
-        assert every[i, dst[q]].tobytes() == st[i].tobytes()
-        assert int(((every[i] > st[i]) & valid).sum()) == ng[i] and int(((every[i] == st[i]) & valid).sum()) == ne[i]
-    # a pair on its own has the bits it has inside a run of equal sources
-    alone = _gpu_score(rowptr, col, src[qs], dst[qs], ROUNDS[kind], a, w, mode)
-    assert alone.tobytes() == st.tobytes()
-
-
 # ---------------------------------------------------------------------------- 7. the two modes agree on what is reached
 def test_walk_sum_is_positive_exactly_within_reach():
     """With damping 1/2 and four rounds nothing underflows: acc[c] > 0 exactly where dist(s, c) <= 4 (c != s: an isolated source does
@@ -259,17 +166,6 @@ def test_walk_sum_is_positive_exactly_within_reach():
     assert bool((hops[np.arange(len(sources)), sources] == 0.0).all()) and bool((hops[2][cand != 695] == -5.0).all())
     for i, src in enumerate(sources.tolist()):
         assert np.array_equal(-hops[i], W.cut_dist(W.hop_dist(rowptr, col, src), 4).astype(np.float32))
-
-
-# ---------------------------------------------------------------------------- 8. repeatability
-@pytest.mark.parametrize("kind", ["ppr", "hops"])
-def test_two_calls_and_split_calls_are_bitwise_equal(kind):
-    edges, rowptr, col, src, dst, known = _big()
-    (w, a, mode), filt = W.params(rowptr, kind), R.filter_rows(known, N_BIG)
-    one, two = (_gpu_rank(rowptr, col, src, dst, ROUNDS[kind], a, w, mode, filt) for _ in range(2))
-    head, tail = (_gpu_rank(rowptr, col, src[sl], dst[sl], ROUNDS[kind], a, w, mode, filt) for sl in (slice(0, 48), slice(48, None)))
-    for x, y, h, t in zip(one, two, head, tail):
-        assert x.tobytes() == y.tobytes() and x.tobytes() == np.concatenate([h, t]).tobytes()
 
 
 # ---------------------------------------------------------------------------- 9. what is accepted and what is refused
@@ -348,19 +244,6 @@ def test_argument_errors_and_empty_inputs():
 
 
 # ---------------------------------------------------------------------------- 10. the command-line path
-def _run_cli(tmp_path, monkeypatch, name, extra):
-    from gnn_pretraining_amd.finetune import finetune as FT
-    monkeypatch.setattr(FT, "OUTPUT_DIR", tmp_path / name)
-    log = tmp_path / f"{name}.jsonl"
-    monkeypatch.setattr(sys, "argv", ["finetune", "--domain_name", "Cora_LP", "--finetune_strategy", "full_finetune", "--pretrained_scheme", "b1",
-                                      "--seed", "5", "--epochs", "1", "--data-root", str(tmp_path / "data"), "--data-scale", "0.1",
-                                      "--log", str(log)] + extra)
-    FT.main()
-    rec = [json.loads(line) for line in log.read_text().splitlines()]
-    state = torch.load(next((tmp_path / name).glob("model_*.pt")), map_location="cpu", weights_only=True)["model_state_dict"]
-    return rec, state
-
-
 METRICS = ("mrr", "hits@1", "hits@10", "hits@50")
 WALK_KEYS = [f"test/{kind}_{m}" for kind in W.KINDS for m in METRICS]
 

@@ -1,9 +1,7 @@
 """What the label-propagation baselines rest on, without a GPU: the fp32 definition of tests/labelprop_ref.py (which the kernel is pinned to
 bit for bit in test_gpu_labelprop.py) against float64 and against the closed form, that it classifies a planted partition, that its
 subnormal case is one, and the flag, the config field and the bindings."""
-import ctypes
 import functools
-import re
 
 import numpy as np
 import pytest
@@ -13,8 +11,6 @@ import labelprop_ref as R
 from gnn_pretraining_amd import _lib as L, ops
 from gnn_pretraining_amd.finetune import finetune as FT
 
-BASE = ["--finetune_strategy", "full_finetune", "--pretrained_scheme", "b1", "--seed", "1"]
-NEW_SYMBOLS = ("gmp_label_propagate_workspace_bytes", "gmp_label_propagate")
 ALPHA, BETA = R.ALPHA, R.BETA
 
 
@@ -135,25 +131,6 @@ def test_chained_single_rounds_equal_one_call():
 
 
 # ---------------------------------------------------------------------------- 5. flag and config
-def test_flag_parses_into_the_config_and_is_off_by_default():
-    a = FT.build_parser().parse_args(["--domain_name", "Cora_NC", "--label-propagation", "5"] + BASE)
-    cfg = FT.config_from_args(a)
-    assert cfg.label_propagation == 5 and not any(getattr(cfg, p.field) for p in FT.PROBES)
-    assert FT.config_from_args(FT.build_parser().parse_args(["--domain_name", "Cora_NC"] + BASE)).label_propagation == 0
-    assert FT.FinetuneConfig("Cora_NC", "full_finetune", "b1", 1).label_propagation == 0
-    assert FT.FinetuneConfig("CiteSeer_NC", "full_finetune", "b1", 1, label_propagation=10000).label_propagation == 10000
-    assert "--label-propagation" in FT.__doc__ and len(FT.PROBES) == 3
-
-
-@pytest.mark.parametrize("domain", ["Cora_LP", "ENZYMES"])
-def test_flag_is_refused_off_node_classification(domain):
-    with pytest.raises(ValueError, match="label_propagation"):
-        FT.FinetuneConfig(domain_name=domain, finetune_strategy="full_finetune", pretrained_scheme="b1", seed=1, label_propagation=5)
-    a = FT.build_parser().parse_args(["--domain_name", domain, "--label-propagation", "5"] + BASE)
-    with pytest.raises(ValueError, match="label_propagation"):
-        FT.config_from_args(a)
-
-
 @pytest.mark.parametrize("bad", [-1, 10001])
 def test_rounds_are_bounded(bad):
     assert (ops.LABELPROP_MAX_CLASSES, ops.LABELPROP_MAX_ROUNDS) == (32, 10000)
@@ -182,18 +159,3 @@ def test_degree_scales_follow_the_host_rule():
     d = np.array([0, 3, 7, 16], np.int32)
     sym = NB.degree_scales(torch.from_numpy(np.concatenate([[0], np.cumsum(d)]).astype(np.int32)), "sym")[0].numpy()
     assert sym.tolist() == [0.0, np.float32(1 / np.sqrt(3.0)), np.float32(1 / np.sqrt(7.0)), 0.25]
-
-
-# ---------------------------------------------------------------------------- 6. the new symbols
-def test_symbols_are_declared_bound_and_exported():
-    declared = set(L.declared_symbols())
-    lib = ctypes.CDLL(L.LIB_PATH)
-    header = re.sub(r"/\*.*?\*/", "", open(L.HEADER_PATH).read(), flags=re.S)
-    for name in NEW_SYMBOLS:
-        assert name in declared, f"{name} missing from include/gnnmp.h"
-        assert name in L._SIGS, f"{name} missing from _lib.py's table"
-        assert hasattr(lib, name), f"{name} not exported by libgnnmp.so"
-        args = re.search(name + r"\s*\(([^;]*)\)\s*;", header).group(1)
-        assert len(args.split(",")) == len(L._SIGS[name][1]), f"{name}: the binding's argument count differs from the header's"
-    ws = L.lib().gmp_label_propagate_workspace_bytes
-    assert ws(2708, 7) >= 2 * 2708 * 7 * 4 and ws(2708, 0) == 0 and ws(2708, 33) == 0 and ws(-1, 7) == 0

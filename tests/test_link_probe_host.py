@@ -1,9 +1,7 @@
 """Host-side contract of the embedding link probe (csrc/emb_link.hip, finetune/link_probe.py, --link-probe): the CPU reference of
 tests/link_probe_ref.py on four nodes worked by hand -- every exclusion and the half tie -- the AUC with a tie, the flag and its
 refusals, the declaration / binding / export of the three C-ABI entry points, and the Python layer's refusals."""
-import ctypes
 import math
-import re
 
 import numpy as np
 import pytest
@@ -14,7 +12,6 @@ from gnn_pretraining_amd import _lib as L, ops
 from gnn_pretraining_amd._lib import GnnmpError
 from gnn_pretraining_amd.finetune import finetune as FT
 
-NEW_SYMBOLS = ["gmp_emb_link_workspace_bytes", "gmp_emb_link_score", "gmp_emb_link_rank"]
 BASE = ["--finetune_strategy", "full_finetune", "--pretrained_scheme", "b1", "--seed", "1"]
 
 # four nodes in the plane; inner products        cosines (r = sqrt(1/2))
@@ -114,19 +111,6 @@ def test_link_probe_is_refused_off_link_prediction(domain, engine):
     with pytest.raises(ValueError, match="link_probe applies to the link-prediction domains"):
         FT.FinetuneConfig(domain, "full_finetune", "b1", 1, link_probe=True, **engine)
     assert not FT.FinetuneConfig(domain, "full_finetune", "b1", 1, **engine).link_probe
-
-
-def test_emb_link_symbols_are_declared_bound_and_exported():
-    declared = set(L.declared_symbols())
-    lib = ctypes.CDLL(L.LIB_PATH)
-    header = re.sub(r"/\*.*?\*/", "", open(L.HEADER_PATH).read(), flags=re.S)
-    for name in NEW_SYMBOLS:
-        assert name in declared, f"{name} missing from include/gnnmp.h"
-        assert name in L._SIGS, f"{name} missing from _lib.py's table"
-        assert hasattr(lib, name), f"{name} not exported by libgnnmp.so"
-        args = re.search(name + r"\s*\(([^;]*)\)\s*;", header).group(1)
-        assert len(args.split(",")) == len(L._SIGS[name][1]), f"{name}: the binding's argument count differs from the header's"
-    assert [len(L._SIGS[n][1]) for n in NEW_SYMBOLS] == [3, 11, 17]
 
 
 def test_workspace_rule():

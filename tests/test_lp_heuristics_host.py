@@ -1,7 +1,6 @@
 """Host-side contract of the structural link baselines (csrc/lp_heuristics.hip, finetune/link_heuristics.py, --lp-heuristics): the CPU
 reference of tests/lp_heur_ref.py on a graph small enough to score by hand, the node weights, the flag and its precondition, the
 declaration / binding / export of the five C-ABI entry points, the workspace size, and a kernel source without float atomics."""
-import ctypes
 import math
 import re
 from pathlib import Path
@@ -12,11 +11,8 @@ import torch
 
 import lp_heur_ref as R
 from gnn_pretraining_amd import _lib as L
-from gnn_pretraining_amd.finetune import finetune as FT
 
 ROOT = Path(__file__).resolve().parents[1]
-NEW_SYMBOLS = ["gmp_lp_cn_tile_nodes", "gmp_lp_cn_rank_workspace_bytes", "gmp_lp_cn_score", "gmp_lp_cn_rank", "gmp_graph_simple_check"]
-BASE = ["--finetune_strategy", "full_finetune", "--pretrained_scheme", "b1", "--seed", "1"]
 
 # a triangle 0-1-2, the path 2-3-4 hanging off it (4 is a pendant node), 5 isolated.  Given one way round, once doubled, with a loop.
 EDGES = np.array([[0, 0, 1, 2, 3, 1, 5], [1, 2, 2, 3, 4, 0, 5]])
@@ -89,41 +85,6 @@ def test_node_weights_follow_the_float64_rule_rounded_once():
         node_weights(deg, "katz")
 
 
-def test_lp_heuristics_flag_parses_into_the_config():
-    a = FT.build_parser().parse_args(["--domain_name", "Cora_LP", "--lp-heuristics"] + BASE)
-    cfg = FT.config_from_args(a)
-    assert cfg.lp_heuristics is True and not cfg.lp_engine and not cfg.lp_ranking         # needs neither
-    a = FT.build_parser().parse_args(["--domain_name", "Cora_LP"] + BASE)
-    assert FT.config_from_args(a).lp_heuristics is False                                  # opt-in
-    assert FT.FinetuneConfig("CiteSeer_LP", "full_finetune", "b1", 1, lp_heuristics=True, lp_engine=True, lp_ranking=True).lp_heuristics
-
-
-@pytest.mark.parametrize("domain", ["Cora_NC", "ENZYMES"])
-def test_lp_heuristics_is_refused_off_link_prediction(domain):
-    a = FT.build_parser().parse_args(["--domain_name", domain, "--lp-heuristics"] + BASE)
-    with pytest.raises(ValueError, match="lp_heuristics"):
-        FT.config_from_args(a)
-    with pytest.raises(ValueError, match="lp_heuristics"):
-        FT.FinetuneConfig(domain, "full_finetune", "b1", 1, lp_heuristics=True)
-
-
-def test_the_probe_table_is_untouched():
-    assert len(FT.PROBES) == 3
-
-
-def test_heuristic_symbols_are_declared_bound_and_exported():
-    declared = set(L.declared_symbols())
-    lib = ctypes.CDLL(L.LIB_PATH)
-    header = re.sub(r"/\*.*?\*/", "", open(L.HEADER_PATH).read(), flags=re.S)
-    for name in NEW_SYMBOLS:
-        assert name in declared, f"{name} missing from include/gnnmp.h"
-        assert name in L._SIGS, f"{name} missing from _lib.py's table"
-        assert hasattr(lib, name), f"{name} not exported by libgnnmp.so"
-        args = re.search(name + r"\s*\(([^;]*)\)\s*;", header).group(1)
-        count = 0 if args.strip() == "void" else len(args.split(","))
-        assert count == len(L._SIGS[name][1]), f"{name}: the binding's argument count differs from the header's"
-
-
 def test_tile_size_is_exported_and_sane():
     tc = L.lib().gmp_lp_cn_tile_nodes()
     assert tc >= 64 and tc % 32 == 0 and tc * 4 <= 64 * 1024                               # a bitmap of whole words, an accumulator inside static LDS
@@ -139,7 +100,7 @@ def test_rank_workspace_is_linear_in_queries_plus_nodes():
 
 
 def test_heuristics_kernel_source_has_no_float_atomics():
-    src = (ROOT / "gnn_pretraining_amd" / "csrc" / "lp_heuristics.hip").read_text()
+    src = "".join((ROOT / "gnn_pretraining_amd" / "csrc" / f).read_text() for f in ("lp_heuristics.hip", "csr_graph.h"))     # the kernels and their row helper
     names = [m.group(1) for m in re.finditer(r"atomicAdd\(&(\w+)", src)]
     assert names and set(names) <= {"cnt", "n_greater", "n_equal", "violations"}, names    # integer counts only
     assert not re.search(r"__hip_atomic|unsafeAtomic|atomicAdd\([^&]|atomicExch|atomicCAS", src)

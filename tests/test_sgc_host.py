@@ -1,8 +1,6 @@
 """What the SGC and raw-feature baselines rest on, without a GPU: the fp32 definition of tests/sgc_ref.py (which the kernel is pinned to bit
 for bit in test_gpu_sgc.py) is consistent between its dense and its CSR form, the fixture of the fit has the margins the GPU test relies
 on, sgc_graph follows the host rule, and the flag, the config field and the bindings."""
-import ctypes
-import re
 
 import numpy as np
 import pytest
@@ -13,8 +11,6 @@ import sgc_ref as R
 from gnn_pretraining_amd import _lib as L, ops
 from gnn_pretraining_amd.finetune import finetune as FT, node_baselines as NB
 
-BASE = ["--finetune_strategy", "full_finetune", "--pretrained_scheme", "b1", "--seed", "1"]
-NEW_SYMBOLS = ("gmp_feature_propagate_workspace_bytes", "gmp_feature_propagate")
 
 
 def _bits(a):
@@ -136,28 +132,6 @@ def test_sgc_graph_adds_one_loop_per_row_in_its_place():
 
 
 # ---------------------------------------------------------------------------- 4. flag and config
-def test_flag_parses_into_the_config_and_is_off_by_default():
-    a = FT.build_parser().parse_args(["--domain_name", "Cora_NC", "--sgc-baseline", "2"] + BASE)
-    cfg = FT.config_from_args(a)
-    assert cfg.sgc_baseline == 2 and cfg.label_propagation == 0 and not any(getattr(cfg, p.field) for p in FT.PROBES)
-    assert FT.config_from_args(FT.build_parser().parse_args(["--domain_name", "Cora_NC"] + BASE)).sgc_baseline == 0
-    assert FT.FinetuneConfig("Cora_NC", "full_finetune", "b1", 1).sgc_baseline == 0
-    assert FT.FinetuneConfig("CiteSeer_NC", "full_finetune", "b1", 1, sgc_baseline=64).sgc_baseline == 64
-    both = FT.config_from_args(FT.build_parser().parse_args(["--domain_name", "CiteSeer_NC", "--sgc-baseline", "3", "--label-propagation", "10",
-                                                             "--sparse-features"] + BASE))
-    assert (both.sgc_baseline, both.label_propagation, both.sparse_features) == (3, 10, True)
-    assert "--sgc-baseline" in FT.__doc__
-
-
-@pytest.mark.parametrize("domain", ["Cora_LP", "ENZYMES"])
-def test_flag_is_refused_off_node_classification(domain):
-    with pytest.raises(ValueError, match="sgc_baseline"):
-        FT.FinetuneConfig(domain_name=domain, finetune_strategy="full_finetune", pretrained_scheme="b1", seed=1, sgc_baseline=2)
-    a = FT.build_parser().parse_args(["--domain_name", domain, "--sgc-baseline", "2"] + BASE)
-    with pytest.raises(ValueError, match="sgc_baseline"):
-        FT.config_from_args(a)
-
-
 @pytest.mark.parametrize("bad", [-1, 65])
 def test_rounds_are_bounded(bad):
     assert (ops.FEATPROP_MAX_DIM, ops.FEATPROP_MAX_ROUNDS) == (16384, 64)
@@ -175,21 +149,3 @@ def test_host_tensors_are_refused():
     with pytest.raises(L.GnnmpError, match="GPU"):
         NB.softmax_fit(torch.zeros(5, 2), torch.zeros(5, dtype=torch.int64), 2)
     assert ops.FeaturePropagation._fields == ("out", "status")
-
-
-# ---------------------------------------------------------------------------- 5. the new symbols
-def test_symbols_are_declared_bound_and_exported():
-    declared = set(L.declared_symbols())
-    lib = ctypes.CDLL(L.LIB_PATH)
-    header = re.sub(r"/\*.*?\*/", "", open(L.HEADER_PATH).read(), flags=re.S)
-    for name, count in zip(NEW_SYMBOLS, (3, 20)):
-        assert name in declared, f"{name} missing from include/gnnmp.h"
-        assert name in L._SIGS, f"{name} missing from _lib.py's table"
-        assert hasattr(lib, name), f"{name} not exported by libgnnmp.so"
-        args = re.search(name + r"\s*\(([^;]*)\)\s*;", header).group(1)
-        assert len(args.split(",")) == len(L._SIGS[name][1]) == count, f"{name}: the binding's argument count differs from the header's"
-    ws = L.lib().gmp_feature_propagate_workspace_bytes
-    assert ws(2708, 1433, 1) == 0                                                  # one round writes out directly
-    assert 2708 * 1436 * 4 <= ws(2708, 1433, 2) < 2 * 2708 * 1436 * 4              # one buffer of n x dpad
-    assert ws(2708, 1433, 3) >= 2 * 2708 * 1436 * 4 and ws(2708, 1433, 64) == ws(2708, 1433, 3)   # never more than two
-    assert ws(2708, 0, 2) == 0 and ws(2708, 16385, 2) == 0 and ws(2708, 7, 0) == 0 and ws(2708, 7, 65) == 0 and ws(-1, 7, 2) == 0
