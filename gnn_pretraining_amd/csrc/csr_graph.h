@@ -1,5 +1,6 @@
-// What the link baselines on a graph's own CSR share (lp_heuristics.hip, lp_walk.hip): the size / null check of the int32 CSR and a row
-// clamped to the col array, so that a CSR that breaks its contract gives wrong numbers, never an access outside the arrays.
+// What the baselines on a graph's own CSR share -- the link baselines (lp_heuristics.hip, lp_walk.hip) and, through csr_prop.h, the node
+// baselines (label_prop.hip, feature_prop.hip): the size / null check of the int32 CSR and a row clamped to the col array, so that a CSR
+// that breaks its contract gives wrong numbers, never an access outside the arrays.
 #pragma once
 #include "gnnmp_internal.h"
 

@@ -4,13 +4,11 @@
 // gmp_label_propagate with alpha = 1, beta = 0 and no clamp, with the same bits.
 //
 // Dense round.  One wave per (row, strip of 256 columns): lane l owns the columns strip * 256 + l + 64 q, q = 0 .. 3, so a neighbour's
-// row is read as four coalesced 256-byte segments.  All loads and stores are single dwords: a leading dimension such as CiteSeer's 3,703
-// puts no row but the first on 16 bytes, so this scalar path is the only one there is (a dwordx4 form would need base and leading
-// dimension to be multiples of 16 bytes and was not worth a second kernel: the round is a chain of dependent loads rowptr -> col -> H, not
-// a stream).  The row index is wave-uniform (readfirstlane), so rowptr, col and right travel through the scalar cache.  The loop takes
-// UNROLL entries at a time: UNROLL index loads, then UNROLL x 4 independent gathers, then the adds in order -- the order of the ADDS is
-// the contract, not that of the loads.  A hub row is walked sequentially by one wave per strip: that is the price of the fixed order;
-// scripts/bench_sgc.py measures it on a star graph.
+// row is read as four coalesced 256-byte segments, and the row's four sums per lane are prop::fold_row<4> (csr_prop.h).  All loads and
+// stores are single dwords: a leading dimension such as CiteSeer's 3,703 puts no row but the first on 16 bytes, so this scalar path is
+// the only one there is (a dwordx4 form would need base and leading dimension to be multiples of 16 bytes and was not worth a second
+// kernel).  The row index is wave-uniform (readfirstlane), so rowptr, col and right travel through the scalar cache, and a neighbour's
+// row address is a scalar.  A hub row is walked sequentially by one wave per strip; scripts/bench_sgc.py measures it on a star graph.
 //
 // Sparse first round (CSR features in, dense H_1 out).  One wave owns an output row and accumulates it in an LDS strip of dpad floats,
 // zeroed first; the workgroup holds as many waves (1 .. 4) as fit 64 KiB of strips, so the strip size follows d and nothing is assumed.
@@ -18,8 +16,7 @@
 // sum still sees its terms in neighbour order -- and a wave's LDS operations complete in program order, so consecutive neighbours need no
 // barrier.  The first 64 non-zeros of UNROLL_S neighbours are loaded together before their updates are applied in order.  Then the strip
 // is scaled by left and written out.
-// One launch per round, all enqueued at once; H ping-pongs between at most two workspace buffers and the last round writes `out`.
-#include "gnnmp_internal.h"
+#include "csr_prop.h"
 
 namespace {
 
@@ -27,7 +24,6 @@ constexpr int THREADS = 256;
 constexpr int WAVES = THREADS / GMP_WAVE;
 constexpr int STRIP = 256;                     // columns per wave of the dense round
 constexpr int PER_LANE = STRIP / GMP_WAVE;
-constexpr int UNROLL = 8;
 constexpr int UNROLL_S = 4;
 constexpr int MAX_DIM = 16384;
 constexpr int MAX_ROUNDS = 64;
@@ -44,58 +40,21 @@ __global__ __launch_bounds__(THREADS) void feature_prop_dense_kernel(const int32
     if (row >= n) return;
     const int c0 = (int)blockIdx.y * STRIP + lane;
     bool in[PER_LANE];
-#pragma unroll
-    for (int q = 0; q < PER_LANE; ++q) in[q] = c0 + q * GMP_WAVE < d;
-    // a rowptr that is no CSR offset reads nothing outside col
-    int beg = rowptr[row], end = rowptr[row + 1];
-    beg = min(max(beg, 0), nnz);
-    end = min(max(end, beg), nnz);
-    float acc[PER_LANE];
-#pragma unroll
-    for (int q = 0; q < PER_LANE; ++q) acc[q] = 0.f;
-    int bad = 0, k = beg;
-    for (; k + UNROLL <= end; k += UNROLL) {
-        int j[UNROLL];
-        float r[UNROLL], f[UNROLL][PER_LANE];
-#pragma unroll
-        for (int u = 0; u < UNROLL; ++u) j[u] = col[k + u];
-#pragma unroll
-        for (int u = 0; u < UNROLL; ++u) {
-            const bool ok = (unsigned)j[u] < (unsigned)n;
-            r[u] = ok ? (right ? right[j[u]] : 1.0f) : 0.f;
-            const float* src = hin + (int64_t)(ok ? j[u] : 0) * ldi + c0;
-#pragma unroll
-            for (int q = 0; q < PER_LANE; ++q) f[u][q] = (ok && in[q]) ? src[q * GMP_WAVE] : 0.f;
-        }
-#pragma unroll
-        for (int u = 0; u < UNROLL; ++u) {
-            const bool ok = (unsigned)j[u] < (unsigned)n;
-#pragma unroll
-            for (int q = 0; q < PER_LANE; ++q) {
-                const float s = __fadd_rn(acc[q], __fmul_rn(r[u], f[u][q]));
-                acc[q] = ok ? s : acc[q];                                   // an entry outside the graph is skipped, not added as zero
-            }
-            bad += ok ? 0 : 1;
-        }
+    int cq[PER_LANE];                                                       // a lane's column past the row's end reads the last one instead:
+#pragma unroll                                                              // no test in the loop, and its sum is never stored
+    for (int q = 0; q < PER_LANE; ++q) {
+        in[q] = c0 + q * GMP_WAVE < d;
+        cq[q] = in[q] ? c0 + q * GMP_WAVE : d - 1;
     }
-    for (; k < end; ++k) {
-        const int jj = col[k];
-        if ((unsigned)jj < (unsigned)n) {
-            const float rr = right ? right[jj] : 1.0f;
-            const float* src = hin + (int64_t)jj * ldi + c0;
-#pragma unroll
-            for (int q = 0; q < PER_LANE; ++q)
-                if (in[q]) acc[q] = __fadd_rn(acc[q], __fmul_rn(rr, src[q * GMP_WAVE]));
-        } else {
-            ++bad;
-        }
-    }
+    const auto sum = prop::fold_row<PER_LANE>(rowptr, col, n, nnz, row, right, [&](int j, int q) __attribute__((always_inline)) {
+        return (hin + (int64_t)j * ldi)[cq[q]];                             // a uniform 64-bit row address plus the lane's column
+    });
     const float l = left ? left[row] : 1.0f;
     float* dst = hout + row * ldo + c0;
 #pragma unroll
     for (int q = 0; q < PER_LANE; ++q)
-        if (in[q]) dst[q * GMP_WAVE] = __fmul_rn(l, acc[q]);
-    if (first && blockIdx.y == 0 && lane == 0 && bad) atomicAdd(status, bad);
+        if (in[q]) dst[q * GMP_WAVE] = __fmul_rn(l, sum.acc[q]);
+    if (first && blockIdx.y == 0 && lane == 0 && sum.bad) atomicAdd(status, sum.bad);
 }
 
 // One neighbour's entries e = from + lane, from + lane + 64, ... < xe added into the wave's strip: an entry whose column lies outside
@@ -123,9 +82,9 @@ __global__ __launch_bounds__(THREADS) void feature_prop_sparse_kernel(const int3
     float* const strip = strips + (size_t)wave * dpad;
     for (int c = lane; c < dpad; c += GMP_WAVE) strip[c] = 0.f;
     {
-        int xb = x_rowptr[row], xe = x_rowptr[row + 1], wrong = 0;
-        xb = min(max(xb, 0), x_nnz);
-        xe = min(max(xe, xb), x_nnz);
+        const csr::Row own = csr::row_of(x_rowptr, x_nnz, row);
+        const int xb = (int)own.b, xe = (int)own.e;
+        int wrong = 0;
         for (int e = xb + lane; e < xe; e += GMP_WAVE) {
             const int c = x_col[e], prev = e > xb ? x_col[e - 1] : -1;
             wrong += ((unsigned)c < (unsigned)d && c > prev) ? 0 : 1;
@@ -135,10 +94,9 @@ __global__ __launch_bounds__(THREADS) void feature_prop_sparse_kernel(const int3
         if (lane == 0 && wrong) atomicAdd(status + 1, wrong);
     }
     gmp::wave_sync();
-    int beg = rowptr[row], end = rowptr[row + 1];
-    beg = min(max(beg, 0), nnz);
-    end = min(max(end, beg), nnz);
-    int bad = 0, k = beg;
+    const csr::Row adj = csr::row_of(rowptr, nnz, row);                     // a rowptr that is no CSR offset reads nothing outside col
+    const int end = (int)adj.e;
+    int bad = 0, k = (int)adj.b;
     for (; k + UNROLL_S <= end; k += UNROLL_S) {
         int j[UNROLL_S], xb[UNROLL_S], xe[UNROLL_S], c[UNROLL_S], prev[UNROLL_S];
         float r[UNROLL_S], v[UNROLL_S];
@@ -146,11 +104,12 @@ __global__ __launch_bounds__(THREADS) void feature_prop_sparse_kernel(const int3
         for (int u = 0; u < UNROLL_S; ++u) j[u] = col[k + u];
 #pragma unroll
         for (int u = 0; u < UNROLL_S; ++u) {
-            const bool ok = (unsigned)j[u] < (unsigned)n;
-            r[u] = ok ? (right ? right[j[u]] : 1.0f) : 0.f;
-            const int b = ok ? x_rowptr[j[u]] : 0, e = ok ? x_rowptr[j[u] + 1] : 0;
-            xb[u] = min(max(b, 0), x_nnz);
-            xe[u] = min(max(e, xb[u]), x_nnz);
+            const bool ok = prop::inside(j[u], n);
+            const int js = ok ? j[u] : 0;                                           // a stray entry reads row 0 and takes none of it: no
+            r[u] = prop::right_of(right, js);                                       // branch, so the scalar loads of all four are in flight
+            const csr::Row xs = csr::row_of(x_rowptr, x_nnz, js);
+            xb[u] = (int)xs.b;
+            xe[u] = ok ? (int)xs.e : xb[u];
             bad += ok ? 0 : 1;
         }
 #pragma unroll
@@ -170,11 +129,9 @@ __global__ __launch_bounds__(THREADS) void feature_prop_sparse_kernel(const int3
     }
     for (; k < end; ++k) {
         const int jj = col[k];
-        if ((unsigned)jj < (unsigned)n) {
-            int xb = x_rowptr[jj], xe = x_rowptr[jj + 1];
-            xb = min(max(xb, 0), x_nnz);
-            xe = min(max(xe, xb), x_nnz);
-            add_entries(strip, x_col, x_val, xb, xb + lane, xe, d, right ? right[jj] : 1.0f);
+        if (prop::inside(jj, n)) {
+            const csr::Row xs = csr::row_of(x_rowptr, x_nnz, jj);
+            add_entries(strip, x_col, x_val, (int)xs.b, (int)xs.b + lane, (int)xs.e, d, prop::right_of(right, jj));
             gmp::wave_sync();
         } else {
             ++bad;
@@ -198,10 +155,8 @@ size_t span(int64_t n, int d, int64_t ld) { return n > 0 ? ((size_t)(n - 1) * (s
 }  // namespace
 
 extern "C" size_t gmp_feature_propagate_workspace_bytes(int64_t n, int32_t d, int32_t rounds) {
-    if (!sizes_ok(n, d, rounds) || rounds == 1) return 0;
-    gmp::Carver cv(nullptr, true);
-    for (int b = 0; b < buffers_of(rounds); ++b) cv.take<float>((size_t)n * dpad_of(d));
-    return cv.total();
+    float* buf[2];
+    return sizes_ok(n, d, rounds) && rounds > 1 ? prop::carve(nullptr, buffers_of(rounds), (size_t)n * dpad_of(d), buf) : 0;
 }
 
 extern "C" int gmp_feature_propagate(const int32_t* rowptr, const int32_t* col, int64_t n, int64_t nnz, const float* left, const float* right,
@@ -217,7 +172,8 @@ extern "C" int gmp_feature_propagate(const int32_t* rowptr, const int32_t* col, 
     if (ldo < d || (dense && ldx < d)) return gmp::fail(GMP_ERR_ARG, "feature_propagate: ldx=%lld ldo=%lld for d=%d (ld >= d)", (long long)ldx, (long long)ldo, d);
     if (sparse && (x_nnz < 0 || x_nnz >= LIMIT || !x_rowptr || (x_nnz > 0 && (!x_col || !x_val))))
         return gmp::fail(GMP_ERR_ARG, "feature_propagate: x_nnz=%lld (0 <= x_nnz < 2^31) or a null x_rowptr / x_col / x_val", (long long)x_nnz);
-    if (!rowptr || (!col && nnz > 0) || !out || !status) return gmp::fail(GMP_ERR_ARG, "feature_propagate: null pointer");
+    if (int rc = csr::graph_ok("feature_propagate", rowptr, col, n, nnz)) return rc;
+    if (!out || !status) return gmp::fail(GMP_ERR_ARG, "feature_propagate: null pointer");
     const size_t out_bytes = span(n, d, ldo);
     if ((dense && gmp::overlap(out, out_bytes, x, span(n, d, ldx))) || (sparse && gmp::overlap(out, out_bytes, x_val, (size_t)x_nnz * sizeof(float))))
         return gmp::fail(GMP_ERR_ARG, "feature_propagate: out overlaps x");
@@ -227,32 +183,20 @@ extern "C" int gmp_feature_propagate(const int32_t* rowptr, const int32_t* col, 
     hipStream_t st = (hipStream_t)stream;
     const int dpad = dpad_of(d);
     float* buf[2] = {nullptr, nullptr};
-    if (need) {
-        gmp::Carver cv(ws, true);
-        for (int b = 0; b < buffers_of(rounds); ++b) buf[b] = cv.take<float>((size_t)n * dpad);
-    }
+    if (need) prop::carve(ws, buffers_of(rounds), (size_t)n * dpad, buf);
     if (hipMemsetAsync(status, 0, 2 * sizeof(int32_t), st) != hipSuccess) return gmp::fail(GMP_ERR_LAUNCH, "feature_propagate: memset");
-    const float* hin = x;
-    int64_t ldi = ldx;
-    for (int t = 0; t < rounds; ++t) {
-        const bool last = t + 1 == rounds;
-        float* const hout = last ? out : buf[t & 1];
-        const int64_t ldh = last ? ldo : dpad;
-        if (t == 0 && sparse) {
+    return prop::run_rounds(rounds, x, ldx, out, ldo, buf, dpad, [&](int t, const float* hin, int64_t ldi, float* hout, int64_t ldh, bool first, bool) {
+        if (first && sparse) {
             // the strip size follows d: as many waves as fit the budget, one at least (d = 16384 is exactly 64 KiB)
             int waves = LDS_BUDGET / (dpad * (int)sizeof(float));
             waves = waves < 1 ? 1 : (waves > WAVES ? WAVES : waves);
             hipLaunchKernelGGL(feature_prop_sparse_kernel, dim3((unsigned)gmp::cdiv(n, waves)), dim3(waves * GMP_WAVE),
                                (size_t)waves * dpad * sizeof(float), st, rowptr, col, (int)n, (int)nnz, left, right, x_rowptr, x_col, x_val, (int)x_nnz, d,
                                dpad, waves, hout, ldh, status);
-            if (int rc = gmp::check_launch("feature_prop_sparse_kernel")) return rc;
-        } else {
-            hipLaunchKernelGGL(feature_prop_dense_kernel, dim3((unsigned)gmp::cdiv(n, WAVES), (unsigned)gmp::cdiv(d, STRIP)), dim3(THREADS), 0, st, rowptr,
-                               col, (int)n, (int)nnz, left, right, hin, ldi, d, hout, ldh, status, t == 0 ? 1 : 0);
-            if (int rc = gmp::check_launch("feature_prop_dense_kernel")) return rc;
+            return gmp::check_launch("feature_prop_sparse_kernel");
         }
-        hin = hout;
-        ldi = ldh;
-    }
-    return GMP_OK;
+        hipLaunchKernelGGL(feature_prop_dense_kernel, dim3((unsigned)gmp::cdiv(n, WAVES), (unsigned)gmp::cdiv(d, STRIP)), dim3(THREADS), 0, st, rowptr, col,
+                           (int)n, (int)nnz, left, right, hin, ldi, d, hout, ldh, status, (int)first);
+        return gmp::check_launch("feature_prop_dense_kernel");
+    });
 }

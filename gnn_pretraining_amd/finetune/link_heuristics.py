@@ -27,23 +27,32 @@ _GRAPH_CACHE: Dict[int, Tuple[weakref.ref, int, int, Tuple[Tensor, Tensor], Dict
 _GRAPH_CACHE_MAX = 64
 
 
-def _build_simple_graph(edge_index: Tensor, num_nodes: int) -> Tuple[Tensor, Tensor]:
+def symmetric_csr(who: str, edge_index: Tensor, num_nodes: int, self_loops: bool) -> Tuple[Tensor, Tensor]:
+    """(rowptr int32 [num_nodes + 1], col int32 [nnz]) of edge_index [2, E] (int64, any device) with both directions of every edge, rows
+    ascending, duplicates removed; self_loops False drops every loop, True leaves exactly one per node at its sorted position."""
+    n = int(num_nodes)
     if edge_index.dtype != torch.int64 or edge_index.dim() != 2 or edge_index.size(0) != 2:
-        raise GnnmpError(f"simple_graph: edge_index must be an int64 [2, E] tensor, got {edge_index.dtype} {tuple(edge_index.shape)}")
-    if not 0 <= num_nodes < 2 ** 31:
-        raise GnnmpError(f"simple_graph: num_nodes={num_nodes}")
-    if edge_index.numel() and (int(edge_index.min()) < 0 or int(edge_index.max()) >= num_nodes):
-        raise GnnmpError(f"simple_graph: an endpoint lies outside [0, {num_nodes})")
+        raise GnnmpError(f"{who}: edge_index must be an int64 [2, E] tensor, got {edge_index.dtype} {tuple(edge_index.shape)}")
+    if not 0 <= n < 2 ** 31:
+        raise GnnmpError(f"{who}: num_nodes={num_nodes}")
+    if edge_index.numel() and (int(edge_index.min()) < 0 or int(edge_index.max()) >= n):
+        raise GnnmpError(f"{who}: an endpoint lies outside [0, {n})")
     both = torch.cat([edge_index, edge_index.flip(0)], dim=1)                      # symmetrised
-    both = both[:, both[0] != both[1]]                                             # no loops
-    key = torch.unique(both[0] * num_nodes + both[1])                              # sorted by (row, col), no duplicates
+    if self_loops:
+        both = torch.cat([both, torch.arange(n, dtype=torch.int64, device=edge_index.device).expand(2, n)], dim=1)
+    else:
+        both = both[:, both[0] != both[1]]
+    key = torch.unique(both[0] * n + both[1])                                      # sorted by (row, col), no duplicates: a loop stands once
     if key.numel() >= 2 ** 31:
-        raise GnnmpError(f"simple_graph: {key.numel()} entries do not fit an int32 CSR")
-    row = torch.div(key, max(num_nodes, 1), rounding_mode="floor")
-    rowptr = torch.zeros(num_nodes + 1, dtype=torch.int64, device=edge_index.device)
-    rowptr[1:] = torch.cumsum(torch.bincount(row, minlength=num_nodes), dim=0)
-    col = key - row * num_nodes
-    rowptr, col = rowptr.to(torch.int32).contiguous(), col.to(torch.int32).contiguous()
+        raise GnnmpError(f"{who}: {key.numel()} entries do not fit an int32 CSR")
+    row = torch.div(key, max(n, 1), rounding_mode="floor")
+    rowptr = torch.zeros(n + 1, dtype=torch.int64, device=edge_index.device)
+    rowptr[1:] = torch.cumsum(torch.bincount(row, minlength=n), dim=0)
+    return rowptr.to(torch.int32).contiguous(), (key - row * n).to(torch.int32).contiguous()
+
+
+def _build_simple_graph(edge_index: Tensor, num_nodes: int) -> Tuple[Tensor, Tensor]:
+    rowptr, col = symmetric_csr("simple_graph", edge_index, num_nodes, self_loops=False)
     bad = int(ops.graph_simple_check(rowptr, col).item())
     if bad:
         raise GnnmpError(f"simple_graph: the CSR built from edge_index has {bad} entries that break the simple-graph contract")

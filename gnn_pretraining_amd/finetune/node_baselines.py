@@ -25,7 +25,7 @@ from torch import Tensor
 from .. import ops
 from .._lib import GnnmpError
 from ..graph import SparseFeatures
-from .link_heuristics import simple_graph
+from .link_heuristics import simple_graph, symmetric_csr
 
 KINDS = ("sym", "rw")
 
@@ -67,10 +67,14 @@ def _seeds(who: str, edge_index: Tensor, num_nodes: int, seeds: Tensor, seed_lab
     return f0, mask, graph
 
 
-def _checked(who: str, res: ops.LabelPropagation) -> ops.LabelPropagation:
-    skipped = int(res.status[0])
+def _checked(who: str, res):
+    """res (ops.LabelPropagation or ops.FeaturePropagation) when the kernel skipped nothing; status[1] counts skipped feature entries
+    only in the latter."""
+    skipped, second = (int(v) for v in res.status.tolist())
     if skipped:
         raise GnnmpError(f"{who}: {skipped} adjacency entries point outside the graph and were skipped")
+    if second and isinstance(res, ops.FeaturePropagation):
+        raise GnnmpError(f"{who}: {second} feature entries have a column outside the matrix or out of order and were skipped")
     return res
 
 
@@ -92,6 +96,19 @@ def label_propagation(edge_index: Tensor, num_nodes: int, seeds: Tensor, seed_la
     return _checked("label_propagation", ops.label_propagate(rowptr, col, f0, rounds, 1.0, 0.0, left=left, clamp=mask))
 
 
+def _splits(who: str, data, train_idx, eval_idx, device) -> Tuple[int, Tensor, Tensor, Tensor, Tensor]:
+    """(n, train_idx, eval_idx, edge_index, y) of a transductive split on `device`, int64: both splits non-empty (ValueError) and inside
+    [0, n) (GnnmpError)."""
+    n = int(data.num_nodes)
+    train_idx, eval_idx = torch.as_tensor(train_idx).to(device, torch.int64).reshape(-1), torch.as_tensor(eval_idx).to(device, torch.int64).reshape(-1)
+    if train_idx.numel() == 0 or eval_idx.numel() == 0:
+        raise ValueError(f"{who}: {train_idx.numel()} train and {eval_idx.numel()} evaluation nodes (both splits need one)")
+    for name, idx in (("train_idx", train_idx), ("eval_idx", eval_idx)):
+        if int(idx.min()) < 0 or int(idx.max()) >= n:
+            raise GnnmpError(f"{who}: {name} has an entry outside [0, {n})")
+    return n, train_idx, eval_idx, data.edge_index.to(device, torch.int64).contiguous(), data.y.to(device, torch.int64).reshape(-1)
+
+
 def label_baselines(data, train_idx: Tensor, eval_idx: Tensor, num_classes: int, rounds: int,
                     device: Union[str, torch.device] = "cuda") -> Dict[str, float]:
     """{"labelspread_accuracy", "labelprop_accuracy", "labelspread_unreached", "labelprop_unreached"} of the two baselines at their
@@ -101,15 +118,7 @@ def label_baselines(data, train_idx: Tensor, eval_idx: Tensor, num_classes: int,
     outside the graph and when the kernel skipped an adjacency entry."""
     if not 1 <= int(rounds) <= ops.LABELPROP_MAX_ROUNDS:
         raise ValueError(f"label_baselines: rounds={rounds} (1 <= rounds <= {ops.LABELPROP_MAX_ROUNDS})")
-    n = int(data.num_nodes)
-    train_idx, eval_idx = torch.as_tensor(train_idx).to(device, torch.int64).reshape(-1), torch.as_tensor(eval_idx).to(device, torch.int64).reshape(-1)
-    if train_idx.numel() == 0 or eval_idx.numel() == 0:
-        raise ValueError(f"label_baselines: {train_idx.numel()} train and {eval_idx.numel()} evaluation nodes (both splits need one)")
-    for name, idx in (("train_idx", train_idx), ("eval_idx", eval_idx)):
-        if int(idx.min()) < 0 or int(idx.max()) >= n:
-            raise GnnmpError(f"label_baselines: {name} has an entry outside [0, {n})")
-    edge_index = data.edge_index.to(device, torch.int64).contiguous()
-    y = data.y.to(device, torch.int64).reshape(-1)
+    n, train_idx, eval_idx, edge_index, y = _splits("label_baselines", data, train_idx, eval_idx, device)
     scores: Dict[str, float] = {}
     for name, run in (("labelspread", label_spreading), ("labelprop", label_propagation)):
         res = run(edge_index, n, train_idx, y[train_idx], num_classes, rounds=int(rounds))
@@ -129,34 +138,10 @@ def sgc_graph(edge_index: Tensor, num_nodes: int) -> Tuple[Tensor, Tensor, Tenso
     rows ascending -- plus ONE self-loop per node at its sorted position, and scale = 1 / sqrt(deg + 1) with deg the simple graph's
     degree, computed in float64 on the host and rounded once to fp32 (the rule of degree_scales: the device's rsqrt never enters a
     value).  S = diag(scale) (A + I) diag(scale): pass scale as both left and right of ops.feature_propagate."""
-    if edge_index.dtype != torch.int64 or edge_index.dim() != 2 or edge_index.size(0) != 2:
-        raise GnnmpError(f"sgc_graph: edge_index must be an int64 [2, E] tensor, got {edge_index.dtype} {tuple(edge_index.shape)}")
-    n = int(num_nodes)
-    if not 0 <= n < 2 ** 31:
-        raise GnnmpError(f"sgc_graph: num_nodes={num_nodes}")
-    if edge_index.numel() and (int(edge_index.min()) < 0 or int(edge_index.max()) >= n):
-        raise GnnmpError(f"sgc_graph: an endpoint lies outside [0, {n})")
-    loops = torch.arange(n, dtype=torch.int64, device=edge_index.device)
-    both = torch.cat([edge_index, edge_index.flip(0), torch.stack([loops, loops])], dim=1)
-    key = torch.unique(both[0] * n + both[1])                                      # sorted by (row, col): a loop stands once, in its place
-    if key.numel() >= 2 ** 31:
-        raise GnnmpError(f"sgc_graph: {key.numel()} entries do not fit an int32 CSR")
-    row = torch.div(key, max(n, 1), rounding_mode="floor")
-    rowptr = torch.zeros(n + 1, dtype=torch.int64, device=edge_index.device)
-    rowptr[1:] = torch.cumsum(torch.bincount(row, minlength=n), dim=0)
-    col = key - row * n
+    rowptr, col = symmetric_csr("sgc_graph", edge_index, num_nodes, self_loops=True)
     d = (rowptr[1:] - rowptr[:-1]).to("cpu", torch.float64)                       # deg + 1: the loop is counted
     scale = (1.0 / torch.sqrt(d)).to(torch.float32).to(edge_index.device)
-    return rowptr.to(torch.int32).contiguous(), col.to(torch.int32).contiguous(), scale
-
-
-def _propagated(who: str, res: ops.FeaturePropagation) -> Tensor:
-    skipped, malformed = (int(v) for v in res.status.tolist())
-    if skipped:
-        raise GnnmpError(f"{who}: {skipped} adjacency entries point outside the graph and were skipped")
-    if malformed:
-        raise GnnmpError(f"{who}: {malformed} feature entries have a column outside the matrix or out of order and were skipped")
-    return res.out
+    return rowptr, col, scale
 
 
 def sgc_features(x: Union[Tensor, SparseFeatures], edge_index: Tensor, num_nodes: int, rounds: int) -> Tensor:
@@ -172,7 +157,7 @@ def sgc_features(x: Union[Tensor, SparseFeatures], edge_index: Tensor, num_nodes
     if int(rounds) == 0:
         return x.to_dense() if isinstance(x, SparseFeatures) else x.to(torch.float32).contiguous()
     rowptr, col, scale = sgc_graph(edge_index, num_nodes)
-    return _propagated("sgc_features", ops.feature_propagate(rowptr, col, x, int(rounds), left=scale, right=scale))
+    return _checked("sgc_features", ops.feature_propagate(rowptr, col, x, int(rounds), left=scale, right=scale)).out
 
 
 def adam_step_(param: Tensor, grad: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, step: int, lr: float) -> None:
@@ -230,15 +215,7 @@ def feature_baselines(data, train_idx: Tensor, eval_idx: Tensor, num_classes: in
     GnnmpError on an index outside the graph and when the kernel skipped an adjacency or a feature entry."""
     if not 1 <= int(rounds) <= ops.FEATPROP_MAX_ROUNDS:
         raise ValueError(f"feature_baselines: rounds={rounds} (1 <= rounds <= {ops.FEATPROP_MAX_ROUNDS})")
-    n = int(data.num_nodes)
-    train_idx, eval_idx = torch.as_tensor(train_idx).to(device, torch.int64).reshape(-1), torch.as_tensor(eval_idx).to(device, torch.int64).reshape(-1)
-    if train_idx.numel() == 0 or eval_idx.numel() == 0:
-        raise ValueError(f"feature_baselines: {train_idx.numel()} train and {eval_idx.numel()} evaluation nodes (both splits need one)")
-    for name, idx in (("train_idx", train_idx), ("eval_idx", eval_idx)):
-        if int(idx.min()) < 0 or int(idx.max()) >= n:
-            raise GnnmpError(f"feature_baselines: {name} has an entry outside [0, {n})")
-    edge_index = data.edge_index.to(device, torch.int64).contiguous()
-    y = data.y.to(device, torch.int64).reshape(-1)
+    n, train_idx, eval_idx, edge_index, y = _splits("feature_baselines", data, train_idx, eval_idx, device)
     x = data.x.to(device)
     scores: Dict[str, float] = {}
     for name, k in (("rawfeat", 0), ("sgc", int(rounds))):

@@ -1704,6 +1704,23 @@ def wl_gram(sorted_a: Tensor, ptr_a: Tensor, sorted_b: Tensor, ptr_b: Tensor, it
     return K
 
 
+def _prop_args(who: str, rowptr: Tensor, col: Tensor, rows: int, what: str, left: Optional[Tensor], right: Optional[Tensor], others) -> int:
+    """n of the int32 CSR that label_propagate / feature_propagate walk: rowptr [n + 1] for the `rows` rows of the matrix `what`, left /
+    right fp32 [n] or None, and these and `others` on rowptr's device."""
+    _need(rowptr, torch.int32, "rowptr", 1); _need(col, torch.int32, "col", 1)
+    n = rowptr.numel() - 1
+    if n < 0 or rows != n:
+        raise L.GnnmpError(f"{who}: rowptr has {rowptr.numel()} entries for the {rows} rows of {what} (n + 1 entries)")
+    for t, name in ((left, "left"), (right, "right")):
+        if t is not None:
+            _need(t, torch.float32, name, 1)
+            if t.numel() != n:
+                raise L.GnnmpError(f"{who}: {name} has {t.numel()} entries for {n} nodes")
+    if any(t is not None and t.device != rowptr.device for t in (col, left, right) + tuple(others)):
+        raise L.GnnmpError(f"{who}: every input must be on one device")
+    return n
+
+
 LABELPROP_MAX_CLASSES, LABELPROP_MAX_ROUNDS = 32, 10000            # gmp_label_propagate (gnnmp.h)
 
 
@@ -1724,24 +1741,19 @@ def label_propagate(rowptr: Tensor, col: Tensor, f0: Tensor, rounds: int, alpha:
     [n, classes] with 1 <= classes <= 32, left / right fp32 [n] or None (ones), clamp uint8 [n] or None.  Every multiply and add is
     rounded on its own in a fixed order: the bits are reproducible, and `rounds` rounds equal `rounds` chained calls of one.  Returns
     LabelPropagation(out, pred, status[, residual]); status stays on the device."""
-    _need(rowptr, torch.int32, "rowptr", 1); _need(col, torch.int32, "col", 1); _need(f0, torch.float32, "f0", 2)
-    n, classes, dev = rowptr.numel() - 1, f0.size(1), rowptr.device
-    if n < 0 or f0.size(0) != n:
-        raise L.GnnmpError(f"label_propagate: rowptr has {rowptr.numel()} entries for the {f0.size(0)} rows of f0 (n + 1 entries)")
+    _need(f0, torch.float32, "f0", 2)
+    n, classes, dev = _prop_args("label_propagate", rowptr, col, f0.size(0), "f0", left, right, (f0, clamp, f_init)), f0.size(1), rowptr.device
     if not 1 <= classes <= LABELPROP_MAX_CLASSES or not 1 <= int(rounds) <= LABELPROP_MAX_ROUNDS:
         raise L.GnnmpError(f"label_propagate: classes={classes} rounds={rounds} (1 <= classes <= {LABELPROP_MAX_CLASSES}, "
                            f"1 <= rounds <= {LABELPROP_MAX_ROUNDS})")
-    for t, name, dtype in ((left, "left", torch.float32), (right, "right", torch.float32), (clamp, "clamp", torch.uint8)):
-        if t is not None:
-            _need(t, dtype, name, 1)
-            if t.numel() != n:
-                raise L.GnnmpError(f"label_propagate: {name} has {t.numel()} entries for {n} nodes")
+    if clamp is not None:
+        _need(clamp, torch.uint8, "clamp", 1)
+        if clamp.numel() != n:
+            raise L.GnnmpError(f"label_propagate: clamp has {clamp.numel()} entries for {n} nodes")
     if f_init is not None:
         _need(f_init, torch.float32, "f_init", 2)
         if f_init.shape != f0.shape:
             raise L.GnnmpError(f"label_propagate: f_init {tuple(f_init.shape)} against f0 {tuple(f0.shape)}")
-    if any(t is not None and t.device != dev for t in (col, f0, left, right, clamp, f_init)):
-        raise L.GnnmpError("label_propagate: every input must be on one device")
     rounds, l = int(rounds), L.lib()
     out = torch.empty(n, classes, device=dev)
     pred = torch.empty(n, dtype=torch.int64, device=dev)
@@ -1774,7 +1786,6 @@ def feature_propagate(rowptr: Tensor, col: Tensor, x, rounds: int, left: Optiona
     the CSR form gives the bits of the dense form on to_dense(), and `rounds` rounds equal `rounds` chained calls of one.  Returns
     FeaturePropagation(out, status); status stays on the device."""
     from .graph import SparseFeatures
-    _need(rowptr, torch.int32, "rowptr", 1); _need(col, torch.int32, "col", 1)
     sparse = isinstance(x, SparseFeatures)
     if sparse:
         _sparse_ok(x)
@@ -1782,25 +1793,16 @@ def feature_propagate(rowptr: Tensor, col: Tensor, x, rounds: int, left: Optiona
         _need_rows(x, "x")
     else:
         raise L.GnnmpError(f"feature_propagate: x must be a dense fp32 tensor or SparseFeatures, got {type(x).__name__}")
-    n, d, dev = rowptr.numel() - 1, int(x.shape[1]), rowptr.device
-    if n < 0 or x.shape[0] != n:
-        raise L.GnnmpError(f"feature_propagate: rowptr has {rowptr.numel()} entries for the {x.shape[0]} rows of x (n + 1 entries)")
+    rows, d, dev = int(x.shape[0]), int(x.shape[1]), rowptr.device
     if not 1 <= d <= FEATPROP_MAX_DIM or not 1 <= int(rounds) <= FEATPROP_MAX_ROUNDS:
         raise L.GnnmpError(f"feature_propagate: d={d} rounds={rounds} (1 <= d <= {FEATPROP_MAX_DIM}, 1 <= rounds <= {FEATPROP_MAX_ROUNDS})")
-    for t, name in ((left, "left"), (right, "right")):
-        if t is not None:
-            _need(t, torch.float32, name, 1)
-            if t.numel() != n:
-                raise L.GnnmpError(f"feature_propagate: {name} has {t.numel()} entries for {n} nodes")
     if out is None:
-        out = torch.empty(n, d, device=dev)
+        out = torch.empty(rows, d, device=dev)
     else:
         _need_rows(out, "out")
-        if tuple(out.shape) != (n, d):
-            raise L.GnnmpError(f"feature_propagate: out {tuple(out.shape)} against x {(n, d)}")
-    inputs = (col, left, right, out) + ((x.rowptr, x.col, x.val) if sparse else (x,))
-    if any(t is not None and t.device != dev for t in inputs):
-        raise L.GnnmpError("feature_propagate: every input must be on one device")
+        if tuple(out.shape) != (rows, d):
+            raise L.GnnmpError(f"feature_propagate: out {tuple(out.shape)} against x {(rows, d)}")
+    n = _prop_args("feature_propagate", rowptr, col, rows, "x", left, right, (out,) + ((x.rowptr, x.col, x.val) if sparse else (x,)))
     rounds, l = int(rounds), L.lib()
     status = torch.zeros(2, dtype=torch.int32, device=dev)
     ld = lambda t: t.stride(0) if t.size(0) > 1 else t.size(1)                     # noqa: E731

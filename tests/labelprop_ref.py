@@ -34,25 +34,32 @@ def argmax_rows(out: np.ndarray) -> np.ndarray:
     return (np.uint64(0xFFFFFFFF) - (best & np.uint64(0xFFFFFFFF))).astype(np.int64)
 
 
-def _propagate(dtype, rowptr, col, f0, rounds, alpha, beta, left, right, clamp, f_init) -> Result:
+def steps(rowptr, col, n):
+    """Per neighbour position p: the rows whose p-th entry lies inside the graph, and that entry -- the bookkeeping of the sequential row
+    sum, no arithmetic -- and the number of entries outside [0, n)."""
     rowptr, col = np.asarray(rowptr, dtype=np.int64), np.asarray(col, dtype=np.int64)
+    deg = rowptr[1:] - rowptr[:-1]
+    inside = (col >= 0) & (col < n)
+    out = []
+    for p in range(int(deg.max()) if n else 0):
+        rows = np.nonzero(deg > p)[0]
+        k = rowptr[rows] + p
+        out.append((rows[inside[k]], col[k][inside[k]]))
+    return out, int((~inside).sum())
+
+
+def _propagate(dtype, rowptr, col, f0, rounds, alpha, beta, left, right, clamp, f_init) -> Result:
     f0 = np.asarray(f0, dtype=dtype)
     n, classes = f0.shape
     alpha, beta = dtype(alpha), dtype(beta)
     left = np.ones(n, dtype) if left is None else np.asarray(left, dtype=dtype)
     right = np.ones(n, dtype) if right is None else np.asarray(right, dtype=dtype)
     F = f0.copy() if f_init is None else np.asarray(f_init, dtype=dtype).copy()
-    deg = rowptr[1:] - rowptr[:-1]
-    inside = (col >= 0) & (col < n)
-    steps = []                                                      # per neighbour position: the rows that have one inside the graph, and it
-    for p in range(int(deg.max()) if n else 0):
-        rows = np.nonzero(deg > p)[0]
-        k = rowptr[rows] + p
-        steps.append((rows[inside[k]], col[k][inside[k]]))
+    positions, stray = steps(rowptr, col, n)
     residual = np.zeros(rounds, dtype)
     for t in range(rounds):
         acc = np.zeros((n, classes), dtype)
-        for rows, j in steps:
+        for rows, j in positions:
             acc[rows] = acc[rows] + right[j][:, None] * F[j]        # an entry outside the graph is skipped, not added as zero
         v = left[:, None] * acc
         o = alpha * v + beta * f0
@@ -61,7 +68,7 @@ def _propagate(dtype, rowptr, col, f0, rounds, alpha, beta, left, right, clamp, 
         F = new
     pred = argmax_rows(F) if dtype is np.float32 else F.argmax(axis=1)
     top = F[np.arange(n), pred] if n else np.zeros(0, dtype)
-    status = np.array([int((~inside).sum()), int((~(top > 0)).sum())], dtype=np.int32)
+    status = np.array([stray, int((~(top > 0)).sum())], dtype=np.int32)
     return Result(F, pred.astype(np.int64), status, residual)
 
 
@@ -169,6 +176,22 @@ def with_stray_columns(g: Graph):
     rowptr[2:] += 1
     rowptr[g.n] += 1
     return Graph(g.n, rowptr.astype(np.int32), col.astype(np.int32), g.edges)
+
+
+LADDER_N = 24
+
+
+def degree_ladder(stray: bool = True) -> Graph:
+    """A raw CSR written by hand (not symmetric; `edges` is empty): row v holds v entries inside [0, n), ascending, so the degrees 0, 7, 8,
+    9, 15, 16 and 17 -- every remainder of a batch of 8 around one and two full batches -- all occur.  With `stray`, row 12 gets col = n
+    at position 3 (inside its full batch) and row 17 gets col = -1 as its last entry (in the tail after two full batches)."""
+    n = LADDER_N
+    rows = [sorted((v + 1 + p) % n for p in range(v)) for v in range(n)]          # the v nodes after v, cyclically
+    if stray:
+        rows[12].insert(3, n)
+        rows[17].append(-1)
+    rowptr = np.concatenate([[0], np.cumsum([len(r) for r in rows])])
+    return Graph(n, rowptr.astype(np.int32), np.array([c for r in rows for c in r], np.int32), np.zeros((2, 0), np.int64))
 
 
 def random_inputs(n: int, classes: int, seed: int):

@@ -20,19 +20,6 @@ class Result(NamedTuple):
     status: np.ndarray             # int32 [2]: adjacency entries outside [0, n), feature entries that break the CSR form
 
 
-def _steps(rowptr, col, n):
-    """Per neighbour position: the rows that have an entry inside the graph there, and that entry; and the number of entries outside."""
-    rowptr, col = np.asarray(rowptr, dtype=np.int64), np.asarray(col, dtype=np.int64)
-    deg = rowptr[1:] - rowptr[:-1]
-    inside = (col >= 0) & (col < n)
-    steps = []
-    for p in range(int(deg.max()) if n else 0):
-        rows = np.nonzero(deg > p)[0]
-        k = rowptr[rows] + p
-        steps.append((rows[inside[k]], col[k][inside[k]]))
-    return steps, int((~inside).sum())
-
-
 def _round(steps, H, left, right):
     acc = np.zeros(H.shape, np.float32)
     for rows, j in steps:
@@ -49,7 +36,7 @@ def propagate(rowptr, col, x, rounds, left=None, right=None) -> Result:
     H = np.asarray(x, dtype=np.float32).copy()
     n = H.shape[0]
     left, right = _scales(n, left, right)
-    steps, stray = _steps(rowptr, col, n)
+    steps, stray = LP.steps(rowptr, col, n)
     for _ in range(rounds):
         H = _round(steps, H, left, right)
     return Result(H, np.array([stray, 0], np.int32))
@@ -80,7 +67,7 @@ def propagate_csr(rowptr, col, x_rowptr, x_col, x_val, d, rounds, left=None, rig
                 if valid[e]:
                     acc[i, xc[e]] = acc[i, xc[e]] + right[j] * xv[e]
     H = left[:, None] * acc
-    steps, stray = _steps(rp, cl, n)
+    steps, stray = LP.steps(rp, cl, n)
     for _ in range(rounds - 1):
         H = _round(steps, H, left, right)
     return Result(H, np.array([stray, int((~valid).sum())], np.int32))

@@ -4,8 +4,6 @@ compared for BIT EQUALITY; pred, status and residual are compared exactly.  test
 the closed form."""
 import ctypes as C
 import functools
-import json
-import sys
 
 import numpy as np
 import pytest
@@ -15,23 +13,11 @@ import labelprop_ref as R
 from gnn_pretraining_amd import _lib as L, ops
 from gnn_pretraining_amd._lib import GnnmpError
 from gnn_pretraining_amd.finetune import node_baselines as NB
+from node_prop_util import DEV, SENTINEL, bits as _bits, run_cli as _run_cli, t as _t
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
 GMP_OK, GMP_ERR_ARG, GMP_ERR_WORKSPACE = 0, -1, -3
-SENTINEL = -7.0
 ALPHA, BETA = R.ALPHA, R.BETA
-
-
-def _t(a, dtype=None):
-    if a is None or isinstance(a, torch.Tensor):
-        return a
-    t = torch.as_tensor(np.ascontiguousarray(a))
-    return (t if dtype is None else t.to(dtype)).to(DEV).contiguous()
-
-
-def _bits(x):
-    return np.ascontiguousarray(x.cpu().numpy() if isinstance(x, torch.Tensor) else x, dtype=np.float32).view(np.uint32)
 
 
 def _gpu(g, f0, rounds, alpha, beta, left=None, right=None, clamp=None, f_init=None):
@@ -104,6 +90,17 @@ def test_star_with_a_long_row():
         _check(g, f0, 3, 0.75, 0.5, left, right, None, f_init)
     left, right = R.degree_scales(g.rowptr, "sym")
     _check(g, R.one_hot(g.n, 2, [0, 5], [0, 1]), 4, ALPHA, BETA, left, right)
+
+
+@pytest.mark.parametrize("rounds", [1, 3])
+@pytest.mark.parametrize("classes", [3, 32])
+def test_degree_ladder_with_strays_inside_a_batch_and_in_a_tail(classes, rounds):
+    """Degrees 0 .. 23 -- every remainder of the batch of 8 around one and two full batches -- with col = n at position 3 of row 12 (inside
+    its full batch) and col = -1 as the last entry of row 17 (its tail): skipped where they stand, counted once."""
+    s = R.degree_ladder()
+    f0, f_init, left, right, clamp = R.random_inputs(s.n, classes, 31)
+    got, want = _check(s, f0, rounds, 0.75, 0.5, left, right, clamp, f_init)
+    assert int(got.status[0]) == 2 == want.status[0]
 
 
 def test_graph_without_edges():
@@ -261,21 +258,6 @@ def test_label_baselines_refuse_indices_outside_the_graph():
 
 
 # ---------------------------------------------------------------------------- 8. the command-line path
-def _run_cli(root, monkeypatch, name, extra):
-    from gnn_pretraining_amd import operators as O
-    from gnn_pretraining_amd.finetune import finetune as FT
-    monkeypatch.setattr(FT, "OUTPUT_DIR", root / name)
-    monkeypatch.setattr(O.DROPOUT, "count", 0)                                    # the module path's dropout counter is process-wide
-    log = root / f"{name}.jsonl"
-    monkeypatch.setattr(sys, "argv", ["finetune", "--domain_name", "Cora_NC", "--finetune_strategy", "full_finetune", "--pretrained_scheme", "b1",
-                                      "--seed", "5", "--epochs", "1", "--data-root", str(root / "data"), "--data-scale", "0.1",
-                                      "--log", str(log)] + extra)
-    FT.main()
-    rec = [json.loads(line) for line in log.read_text().splitlines()]
-    state = torch.load(next((root / name).glob("model_*.pt")), map_location="cpu", weights_only=True)["model_state_dict"]
-    return rec, state
-
-
 def test_cli_logs_the_four_keys_and_leaves_training_alone(tmp_path, monkeypatch):
     """python -m gnn_pretraining_amd.finetune.finetune ... --label-propagation 10, in process: one epoch on the synthetic Cora_NC stand-in.
     The test record carries the four keys, equal to label_baselines called directly on the same splits; every other key but the timing

@@ -3,8 +3,6 @@ fp32 definition of tests/sgc_ref.py.  A row's sum is sequential and every operat
 propagation is compared for BIT EQUALITY and status exactly.  The fit is pinned to itself bit for bit and to the float64 reference by a
 bound taken from the reference's own margins.  test_sgc_host.py holds the preconditions of the fixture."""
 import ctypes as C
-import json
-import sys
 
 import numpy as np
 import pytest
@@ -16,22 +14,10 @@ from gnn_pretraining_amd import _lib as L, ops
 from gnn_pretraining_amd._lib import GnnmpError
 from gnn_pretraining_amd.finetune import node_baselines as NB
 from gnn_pretraining_amd.graph import SparseFeatures
+from node_prop_util import DEV, SENTINEL, bits as _bits, run_cli as _run_cli, t as _t
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
 GMP_OK, GMP_ERR_ARG = 0, -1
-SENTINEL = -7.0
-
-
-def _t(a, dtype=None):
-    if a is None or isinstance(a, (torch.Tensor, SparseFeatures)):
-        return a
-    t = torch.as_tensor(np.ascontiguousarray(a))
-    return (t if dtype is None else t.to(dtype)).to(DEV).contiguous()
-
-
-def _bits(x):
-    return np.ascontiguousarray(x.cpu().numpy() if isinstance(x, torch.Tensor) else x, dtype=np.float32).view(np.uint32)
 
 
 def _gpu(g, x, rounds, left=None, right=None, out=None):
@@ -115,6 +101,25 @@ def test_same_bits_as_label_propagate(d):
         got = ops.feature_propagate(rp, cl, _t(x), rounds, left=_t(left), right=_t(right))
         assert torch.equal(got.out.view(torch.int32), want.out.view(torch.int32))
         assert int(got.status[0]) == int(want.status[0]) == 0
+
+
+@pytest.mark.parametrize("rounds", [1, 3])
+@pytest.mark.parametrize("d", [5, 257])
+def test_degree_ladder_with_strays_inside_a_batch_and_in_a_tail(d, rounds):
+    """labelprop_ref.degree_ladder: degrees 0 .. 23 with col = n at position 3 of row 12 (inside its full batch of 8) and col = -1 as the
+    last entry of row 17 (its tail), on dense and on CSR features; at d = 5 the columns are label_propagate's with alpha 1, beta 0."""
+    s = LP.degree_ladder()
+    x, _, left, right, _ = LP.random_inputs(s.n, d, 31)
+    got = _check(s, x, rounds, left, right)
+    assert got.status.tolist() == [2, 0]
+    xr, xc, xv = R.sparse_features(s.n, d, 32, density=0.3)
+    sparse = _gpu(s, _sparse(xr, xc, xv, s.n, d), rounds, left, right)
+    want = R.propagate_csr(s.rowptr, s.col, xr, xc, xv, d, rounds, left, right)
+    assert np.array_equal(_bits(sparse.out), _bits(want.out)) and np.array_equal(sparse.status.cpu().numpy(), want.status)
+    assert want.status.tolist() == [2, 0]
+    if d == 5:
+        label = ops.label_propagate(_t(s.rowptr, torch.int32), _t(s.col, torch.int32), _t(x), rounds, 1.0, 0.0, left=_t(left), right=_t(right))
+        assert torch.equal(got.out.view(torch.int32), label.out.view(torch.int32)) and int(label.status[0]) == 2
 
 
 # ---------------------------------------------------------------------------- 2. CSR features
@@ -356,21 +361,6 @@ def test_feature_baselines_refuse_bad_indices_and_malformed_features():
 
 
 # ---------------------------------------------------------------------------- 8. the command-line path
-def _run_cli(root, monkeypatch, name, extra):
-    from gnn_pretraining_amd import operators as O
-    from gnn_pretraining_amd.finetune import finetune as FT
-    monkeypatch.setattr(FT, "OUTPUT_DIR", root / name)
-    monkeypatch.setattr(O.DROPOUT, "count", 0)                                    # the module path's dropout counter is process-wide
-    log = root / f"{name}.jsonl"
-    monkeypatch.setattr(sys, "argv", ["finetune", "--domain_name", "Cora_NC", "--finetune_strategy", "full_finetune", "--pretrained_scheme", "b1",
-                                      "--seed", "5", "--epochs", "1", "--data-root", str(root / "data"), "--data-scale", "0.1",
-                                      "--log", str(log)] + extra)
-    FT.main()
-    rec = [json.loads(line) for line in log.read_text().splitlines()]
-    state = torch.load(next((root / name).glob("model_*.pt")), map_location="cpu", weights_only=True)["model_state_dict"]
-    return rec, state
-
-
 def test_cli_logs_the_two_keys_and_leaves_training_alone(tmp_path, monkeypatch):
     """python -m gnn_pretraining_amd.finetune.finetune ... --sgc-baseline 2, in process: one epoch on the synthetic Cora_NC stand-in.  The
     test record carries the two keys, equal to feature_baselines called directly on the same splits; every other key but the timing ones,

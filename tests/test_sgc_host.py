@@ -56,6 +56,26 @@ def test_reference_is_label_propagation_per_column():
     assert stray.status.tolist() == [2, 0] and np.array_equal(_bits(stray.out), _bits(got.out))
 
 
+def test_degree_ladder_places_its_strays_and_both_references_skip_them():
+    """The case of the GPU ladder tests: every degree 0 .. 23 (so 0, 7, 8, 9, 15, 16, 17), one stray column inside a full batch of 8 and
+    one at the end of a tail.  Both references count the two and leave the bits of the same CSR without them."""
+    s, g = LP.degree_ladder(), LP.degree_ladder(stray=False)
+    n = LP.LADDER_N
+    assert n == 24 and np.diff(g.rowptr).tolist() == list(range(n)) and ((g.col >= 0) & (g.col < n)).all()
+    assert all((np.diff(g.col[g.rowptr[v]:g.rowptr[v + 1]]) > 0).all() for v in range(n))
+    assert s.col[s.rowptr[12] + 3] == n and s.rowptr[13] - s.rowptr[12] == 13             # position 3 of 13: inside the full batch
+    assert s.col[s.rowptr[18] - 1] == -1 and s.rowptr[18] - s.rowptr[17] == 18            # the last of 18: the tail after two batches
+    keep = (s.col >= 0) & (s.col < n)
+    assert (~keep).sum() == 2 and np.array_equal(s.col[keep], g.col)
+    f0, f_init, left, right, clamp = LP.random_inputs(n, 5, 31)
+    for rounds in (1, 3):
+        a = LP.propagate(s.rowptr, s.col, f0, rounds, 0.75, 0.5, left, right, clamp, f_init)
+        b = LP.propagate(g.rowptr, g.col, f0, rounds, 0.75, 0.5, left, right, clamp, f_init)
+        assert a.status[0] == 2 and b.status[0] == 0 and np.array_equal(_bits(a.out), _bits(b.out)) and np.array_equal(a.pred, b.pred)
+        a, b = R.propagate(s.rowptr, s.col, f0, rounds, left, right), R.propagate(g.rowptr, g.col, f0, rounds, left, right)
+        assert a.status.tolist() == [2, 0] and b.status.tolist() == [0, 0] and np.array_equal(_bits(a.out), _bits(b.out))
+
+
 # ---------------------------------------------------------------------------- 2. the fixture of the fit
 def test_fixture_has_the_margins_the_gpu_test_relies_on():
     """The GPU test asks the fp32 fit for the fp64 reference's predictions and bounds every logit by half of the reference's smallest
