@@ -158,6 +158,10 @@ _SIGS: Dict[str, tuple] = {
     "gmp_wl_workspace_bytes": (sz, [i32, i64, i32]),
     "gmp_wl_refine": (C.c_int, [p, i32, p, p, i64, i64, p, i32, i32, i64, p, p, p, p, p, sz, p]),
     "gmp_wl_gram": (C.c_int, [p, p, i64, i64, p, p, i64, i64, i32, p, p]),
+    "gmp_sp_workspace_bytes": (sz, [i32, i64]),
+    "gmp_sp_max_unique": (C.c_int, [i64]),
+    "gmp_sp_features": (C.c_int, [p, i32, p, p, i64, i64, p, i32, i32, i64, i32, p, p, p, p, p, p, sz, p]),
+    "gmp_sp_gram": (C.c_int, [p, p, p, i64, i32, p, p, p, i64, i32, p, p]),
     "gmp_label_propagate_workspace_bytes": (sz, [i64, i32]),
     "gmp_label_propagate": (C.c_int, [p, p, i64, i64, p, p, p, p, p, i32, i32, f32, f32, p, p, p, p, p, sz, p]),
     "gmp_feature_propagate_workspace_bytes": (sz, [i64, i32, i32]),

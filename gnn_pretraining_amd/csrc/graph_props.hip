@@ -29,7 +29,7 @@
 // leaving at once when its graph belongs to the other one.
 #include <algorithm>
 
-#include "gnnmp_internal.h"
+#include "bit_bfs.h"
 
 namespace {
 
@@ -38,49 +38,13 @@ typedef unsigned long long u64;
 constexpr int SMALL_N = 256, LARGE_N = 1024;
 constexpr int SLOTS = 16;
 
-__host__ __device__ inline int pow2_ceil(int v) {
-    int p = 1;
-    while (p < v) p <<= 1;
-    return p;
-}
+using gmp::Lanes;
+using gmp::pow2_ceil;
+using gmp::wave_bfs;                                                 // bit_bfs.h: the lane layout and the per-wave bit-set BFS
 
 // LDS of one block whose graphs have at most `cap` nodes: the bit matrix, the clustering terms (padded to a power of two), the degrees
 __host__ __device__ inline size_t lds_bytes(int cap) {
     return (size_t)cap * ((cap + 63) / 64) * 8 + (size_t)pow2_ceil(cap) * 8 + (size_t)cap * 4;
-}
-
-struct Lanes {
-    int w, wp, word, g0;      // row words, lanes per group, this lane's word, first lane of this lane's group
-    u64 stripe;               // the frontier bits this lane's group expands: b % (64 / wp) == group
-    u64 valid;                // node bits of word `word` that exist (node id < n)
-};
-
-// One BFS of a wave from the frontier F (word `word` of the bit set in every group's lane `word`); V = visited on return.
-// Returns the number of levels that found a new node (the eccentricity of a single source).
-__device__ __forceinline__ int wave_bfs(const u64* __restrict__ A, const Lanes& L, u64 F, u64& V) {
-    V = F;
-    int levels = -1;
-    const u64 group0 = (L.wp == 64) ? ~0ull : ((1ull << L.wp) - 1ull);
-    for (;;) {
-        u64 nz = __ballot(F != 0ull) & group0;                       // the frontier's non-empty words (wave-uniform)
-        if (!nz) break;
-        ++levels;
-        u64 acc = 0ull;
-        while (nz) {
-            const int j = __builtin_ctzll(nz);
-            nz &= nz - 1ull;
-            u64 m = __shfl(F, j, 64) & L.stripe;
-            while (m) {                                              // divergent between groups; no cross-lane operation inside
-                const int b = __builtin_ctzll(m);
-                m &= m - 1ull;
-                if (L.word < L.w) acc |= A[(j * 64 + b) * L.w + L.word];
-            }
-        }
-        for (int o = L.wp; o < 64; o <<= 1) acc |= __shfl_xor(acc, o, 64);
-        F = acc & ~V;
-        V |= F;
-    }
-    return levels < 0 ? 0 : levels;
 }
 
 template <int W, int T>
@@ -103,18 +67,8 @@ __global__ __launch_bounds__(T) void graph_props_kernel(const int64_t* __restric
     if (nn < n_min) return;                                          // the other instance's graph
 
     const int n = (int)nn;
-    Lanes L;
-    L.w = (n + 63) >> 6;
-    L.wp = pow2_ceil(L.w > 0 ? L.w : 1);
-    const int lane = t & 63, groups = 64 / L.wp, grp = lane / L.wp;
-    L.word = lane & (L.wp - 1);
-    L.g0 = lane - L.word;
-    L.stripe = 0ull;
-    for (int b = grp; b < 64; b += groups) L.stripe |= 1ull << b;
-    {
-        const int rem = n - L.word * 64;
-        L.valid = rem >= 64 ? ~0ull : (rem > 0 ? ((1ull << rem) - 1ull) : 0ull);
-    }
+    const Lanes L = gmp::make_lanes(n, t & 63);
+    const int lane = t & 63;
     const int w = L.w, wp = L.wp;
     const int P = pow2_ceil(n > 0 ? n : 1);
 

@@ -9,6 +9,14 @@ beat.  It reads the datasets only: no model, no generator, no dropout counter, n
     normalised_similarity(K_et, K_ee, K_tt)           K / sqrt(K_ee K_tt) in fp64
     wl_neighbours(sim, k)                             the k most similar columns per row, ties to the lower index
     wl_baseline(train_ds, eval_ds, num_classes, iters, k=20, device="cuda")    {"knn_accuracy", "logreg_accuracy"}
+
+Beside it the shortest-path kernel (Borgwardt & Kriegel, ICDM 2005; csrc/sp.hip, the definition is above gmp_sp_features): where WL sees
+rooted neighbourhoods, it compares graphs by their distributions of (label, label, hop distance) over node pairs.  Same protocol on top.
+
+    sp_features(batch, max_dist, dim=256, labels="auto")  SPFeatures: per graph the sorted distinct keys with their counts, and the hashed hist
+    sp_kernel(feat_a, feat_b)                             the int64 Gram of the shortest-path kernel between two SPFeatures
+    sp_self_similarity(feat)                              the Gram's diagonal from the counts alone
+    sp_baseline(train_ds, eval_ds, num_classes, max_dist, k=20, device="cuda") {"knn_accuracy", "logreg_accuracy"}
 """
 from __future__ import annotations
 
@@ -93,27 +101,100 @@ def _collate(ds, device):
     return ds.collate(torch.arange(len(ds))).to(device)
 
 
-def wl_baseline(train_ds, eval_ds, num_classes: int, iters: int, k: int = 20, device="cuda") -> Dict[str, float]:
-    """{"knn_accuracy", "logreg_accuracy"} of the WL subtree features with `iters` rounds, fitted on train_ds and scored on eval_ds (two
-    graph datasets with collate(); each split is collated into ONE batch, in dataset order).
+def _kernel_baseline(who: str, features, kernel, train_ds, eval_ds, num_classes: int, k: int, device) -> Dict[str, float]:
+    """The protocol the graph-kernel baselines share.  features(batch) -> a feature map with the hashed histogram in .hist, kernel(a, b) ->
+    the int64 Gram between two of them; each split is collated into ONE batch, in dataset order.
     knn: s = K[eval, train] / sqrt(K_ee K_tt) in fp64 (the self-similarities are the diagonals of the same Gram kernel, 0 where one is 0),
     the min(k, n_train) nearest by a stable descending sort (ties to the lower train index), then s in fp32 through ops.knn_vote at its
     default temperature.  The [n_eval, n_train] matrix IS the product here -- the kernel's Gram -- and is a few hundred squared on the TU
     datasets: there is nothing to stream.
     logreg: ops.logreg_fit on the train split's hashed histogram (as fp32, at its defaults: 100 iterations, lr 0.01), ops.logreg_predict
     on the evaluation split's."""
-    if not 1 <= int(iters) <= ops.WL_MAX_ITERS:
-        raise ValueError(f"wl_baseline: iters={iters} (1 <= iters <= {ops.WL_MAX_ITERS})")
     if not 1 <= int(k) <= ops.KNN_MAX_K:
-        raise ValueError(f"wl_baseline: k={k} (1 <= k <= {ops.KNN_MAX_K})")
+        raise ValueError(f"{who}: k={k} (1 <= k <= {ops.KNN_MAX_K})")
     if len(train_ds) == 0 or len(eval_ds) == 0:
-        raise ValueError(f"wl_baseline: {len(train_ds)} train and {len(eval_ds)} evaluation graphs (both splits need one)")
+        raise ValueError(f"{who}: {len(train_ds)} train and {len(eval_ds)} evaluation graphs (both splits need one)")
     tb, eb = _collate(train_ds, device), _collate(eval_ds, device)
-    ft, fe = wl_features(tb, iters), wl_features(eb, iters)
+    ft, fe = features(tb), features(eb)
     y_train, y_eval = tb.y.to(torch.int64).contiguous(), eb.y.to(torch.int64).contiguous()
-    sim = normalised_similarity(wl_kernel(fe, ft), wl_kernel(fe, fe).diagonal(), wl_kernel(ft, ft).diagonal())
+    sim = normalised_similarity(kernel(fe, ft), kernel(fe, fe).diagonal(), kernel(ft, ft).diagonal())
     idx, val = wl_neighbours(sim, k)
     _, knn_pred = ops.knn_vote(idx, val.to(torch.float32).contiguous(), y_train, num_classes)
     fit = ops.logreg_fit(ft.hist.to(torch.float32).contiguous(), y_train, num_classes)
     lr_pred = ops.logreg_predict(fe.hist.to(torch.float32).contiguous(), fit.state.weight, fit.state.bias)
     return {"knn_accuracy": float((knn_pred == y_eval).float().mean()), "logreg_accuracy": float((lr_pred == y_eval).float().mean())}
+
+
+def wl_baseline(train_ds, eval_ds, num_classes: int, iters: int, k: int = 20, device="cuda") -> Dict[str, float]:
+    """{"knn_accuracy", "logreg_accuracy"} of the WL subtree features with `iters` rounds, fitted on train_ds and scored on eval_ds (two
+    graph datasets with collate()) by the protocol of _kernel_baseline: a k-NN vote on the fp64-normalised exact kernel and a softmax
+    regression on the hashed histogram."""
+    if not 1 <= int(iters) <= ops.WL_MAX_ITERS:
+        raise ValueError(f"wl_baseline: iters={iters} (1 <= iters <= {ops.WL_MAX_ITERS})")
+    return _kernel_baseline("wl_baseline", lambda b: wl_features(b, iters), wl_kernel, train_ds, eval_ds, num_classes, k, device)
+
+
+class SPFeatures(NamedTuple):
+    keys: Tensor                   # int64 [G, cap]: per graph its distinct (label, label, distance) keys, ascending, in [:nuniq[g]]
+    counts: Tensor                 # int32 [G, cap]: the node pairs per key
+    nuniq: Tensor                  # int32 [G]
+    hist: Tensor                   # int32 [G, dim]
+    max_dist: int
+
+
+def sp_features(batch, max_dist: int, dim: int = ops.SP_MAX_DIM, labels: Union[str, None, Tensor] = "auto") -> SPFeatures:
+    """The shortest-path feature map of one collated Batch on the GPU (ops.sp_features on simple_graph(batch.edge_index)), distances up to
+    max_dist.  labels as for wl_features: "auto" = initial_labels(batch.x), None = degrees, or an int64 [N] tensor.  The row stride is
+    the most keys a graph of the batch can have -- its node pairs -- up to what the kernel takes.  Raises GnnmpError naming the first
+    graph the kernel refuses -- more than ops.SP_MAX_GRAPH_NODES nodes, more distinct keys than the row stride, a label outside
+    [0, ops.SP_MAX_LABEL) -- and when a CSR entry was skipped for leaving its graph (one read-back of the status words)."""
+    if not batch.x.is_cuda:
+        raise GnnmpError(f"sp_features: expected a batch on the GPU (the HIP path has no CPU fallback), got {batch.x.device}")
+    if isinstance(labels, str):
+        if labels != "auto":
+            raise ValueError(f"sp_features: labels={labels!r} (\"auto\", None or an int64 tensor)")
+        labels = initial_labels(batch.x)
+    rowptr, col = simple_graph(batch.edge_index.contiguous(), batch.num_nodes)
+    ptr = batch.ptr.to(torch.int64).contiguous()
+    n = int(batch.max_graph_nodes)
+    cap = max(1, min(ops.sp_max_unique(n), n * (n - 1) // 2))
+    out = ops.sp_features(ptr, rowptr, col, None if labels is None else labels.to(torch.int64).contiguous(), max_dist, dim,
+                          max_graph_nodes=n, cap=cap)
+    status = out.status.cpu()
+    if bool((status & 1).any()):
+        g = int((status & 1).nonzero()[0])
+        raise GnnmpError(f"sp_features: graph {g} has {batch.ptr_host[g + 1] - batch.ptr_host[g]} nodes, more than the "
+                         f"{ops.SP_MAX_GRAPH_NODES} the kernel takes (there is no host fallback)")
+    if bool((status & 2).any()):
+        g = int((status & 2).nonzero()[0])
+        raise GnnmpError(f"sp_features: graph {g} has more than {cap} distinct (label, label, distance) keys, the most the kernel takes "
+                         f"for graphs of up to {n} nodes (there is no host fallback)")
+    if bool((status & 4).any()):
+        g = int((status & 4).nonzero()[0])
+        raise GnnmpError(f"sp_features: graph {g} has a node label outside [0, {ops.SP_MAX_LABEL})")
+    if bool((status >> 8).any()):
+        g = int((status >> 8).nonzero()[0])
+        raise GnnmpError(f"sp_features: {int(status[g] >> 8)} adjacency entries of graph {g} point outside the graph and were skipped")
+    return SPFeatures(out.keys, out.counts, out.nuniq, out.hist, int(max_dist))
+
+
+def sp_kernel(feat_a: SPFeatures, feat_b: SPFeatures) -> Tensor:
+    """K int64 [Ga, Gb]: the shortest-path kernel between the graphs of two feature maps made with the same largest distance."""
+    if feat_a.max_dist != feat_b.max_dist:
+        raise GnnmpError(f"sp_kernel: the two feature maps count distances up to {feat_a.max_dist} and {feat_b.max_dist}")
+    return ops.sp_gram(feat_a.keys, feat_a.counts, feat_a.nuniq, feat_b.keys, feat_b.counts, feat_b.nuniq)
+
+
+def sp_self_similarity(feat: SPFeatures) -> Tensor:
+    """int64 [G]: K[g, g] = the sum of counts^2 over graph g's keys, without the Gram kernel."""
+    live = torch.arange(feat.counts.size(1), device=feat.counts.device)[None, :] < feat.nuniq[:, None]
+    c = torch.where(live, feat.counts, torch.zeros_like(feat.counts)).to(torch.int64)
+    return (c * c).sum(dim=1)
+
+
+def sp_baseline(train_ds, eval_ds, num_classes: int, max_dist: int, k: int = 20, device="cuda") -> Dict[str, float]:
+    """{"knn_accuracy", "logreg_accuracy"} of the shortest-path features with distances up to max_dist, fitted on train_ds and scored on
+    eval_ds (two graph datasets with collate()) by the protocol of _kernel_baseline, as wl_baseline."""
+    if not 1 <= int(max_dist) <= ops.SP_MAX_DIST:
+        raise ValueError(f"sp_baseline: max_dist={max_dist} (1 <= max_dist <= {ops.SP_MAX_DIST})")
+    return _kernel_baseline("sp_baseline", lambda b: sp_features(b, max_dist), sp_kernel, train_ds, eval_ds, num_classes, k, device)

@@ -1704,6 +1704,81 @@ def wl_gram(sorted_a: Tensor, ptr_a: Tensor, sorted_b: Tensor, ptr_b: Tensor, it
     return K
 
 
+SP_MAX_DIST, SP_MAX_GRAPH_NODES, SP_MAX_DIM, SP_MAX_LABEL = 1023, 1024, 256, 2 ** 24     # gmp_sp_features / gmp_sp_gram (gnnmp.h)
+
+
+class SPFeatureMap(NamedTuple):
+    """sp_features' outputs (gnnmp.h gmp_sp_features)."""
+    keys: Tensor                   # int64 [G, cap]: graph g's distinct keys (lo << 35 | hi << 11 | d), ascending, in [g, :nuniq[g]]
+    counts: Tensor                 # int32 [G, cap]: the pairs per key
+    nuniq: Tensor                  # int32 [G]: the distinct keys per graph (0 for a refused graph)
+    hist: Tensor                   # int32 [G, dim]: the hashed feature map
+    status: Tensor                 # int32 [G]: bit 0 = refused (too large), bit 1 = more than cap keys, bit 2 = a label outside [0, 2^24), bits 8.. = skipped CSR entries
+
+
+def sp_max_unique(max_graph_nodes: int) -> int:
+    """The largest row stride `cap` sp_features accepts for graphs of at most max_graph_nodes nodes (gnnmp.h gmp_sp_max_unique)."""
+    return int(L.lib().gmp_sp_max_unique(int(max_graph_nodes)))
+
+
+def sp_features(ptr: Tensor, rowptr: Tensor, col: Tensor, labels: Optional[Tensor] = None, max_dist: int = SP_MAX_DIST, dim: int = 256,
+                max_graph_nodes: Optional[int] = None, cap: Optional[int] = None, fill: int = 0) -> SPFeatureMap:
+    """The shortest-path feature map of a batch of graphs in one launch (gnnmp.h gmp_sp_features holds the definition; csrc/sp.hip): per
+    graph, the sorted distinct keys (label, label, hop distance <= max_dist) of its node pairs with their counts, and the counts hashed
+    into dim bins.  ptr int64 [G + 1] node offsets, (rowptr, col) the int32 CSR of the batch's simple undirected graph
+    (finetune.link_heuristics.simple_graph), labels int64 [N] in [0, SP_MAX_LABEL) or None (None: a node's degree inside its graph).
+    1 <= max_dist <= 1023, 1 <= dim <= 256, cap = the row stride of keys and counts, at most sp_max_unique(max_graph_nodes), which None
+    takes.  Returns SPFeatureMap(keys, counts, nuniq, hist, status); keys, counts and hist start as `fill`, which is what a refused graph
+    (status bits 0 - 2) and the tail of every row keep.  max_graph_nodes: the largest ptr[g + 1] - ptr[g] when the caller knows it (None
+    reads it back from ptr, one synchronisation).  No other read-back: status stays on the device."""
+    _need(ptr, torch.int64, "ptr", 1); _need(rowptr, torch.int32, "rowptr", 1); _need(col, torch.int32, "col", 1)
+    G, N, dev = ptr.numel() - 1, rowptr.numel() - 1, ptr.device
+    if G < 0 or N < 0:
+        raise L.GnnmpError(f"sp_features: ptr {tuple(ptr.shape)}, rowptr {tuple(rowptr.shape)} (G + 1 and N + 1 entries)")
+    if rowptr.device != dev or col.device != dev:
+        raise L.GnnmpError("sp_features: ptr, rowptr and col must be on one device")
+    if labels is not None:
+        _need(labels, torch.int64, "labels", 1)
+        if labels.numel() != N or labels.device != dev:
+            raise L.GnnmpError(f"sp_features: labels has {labels.numel()} entries on {labels.device} for {N} nodes on {dev}")
+    if not 1 <= int(max_dist) <= SP_MAX_DIST or not 1 <= int(dim) <= SP_MAX_DIM:
+        raise L.GnnmpError(f"sp_features: max_dist={max_dist} dim={dim} (1 <= max_dist <= {SP_MAX_DIST}, 1 <= dim <= {SP_MAX_DIM})")
+    if max_graph_nodes is None:
+        max_graph_nodes = max(int((ptr[1:] - ptr[:-1]).max()), 0) if G else 0
+    limit = sp_max_unique(max_graph_nodes)
+    cap = limit if cap is None else int(cap)
+    if not 1 <= cap <= limit:
+        raise L.GnnmpError(f"sp_features: cap={cap} (1 <= cap <= {limit} for graphs of up to {max_graph_nodes} nodes)")
+    keys = torch.full((G, cap), fill, dtype=torch.int64, device=dev)
+    counts = torch.full((G, cap), fill, dtype=torch.int32, device=dev)
+    hist = torch.full((G, int(dim)), fill, dtype=torch.int32, device=dev)
+    nuniq = torch.zeros(G, dtype=torch.int32, device=dev)
+    status = torch.zeros(G, dtype=torch.int32, device=dev)
+    if G:
+        L.check(L.lib().gmp_sp_features(_ptr(ptr), G, _ptr(rowptr), _ptr(col), N, col.numel(), _ptr(labels), int(max_dist), int(dim),
+                                        int(max_graph_nodes), cap, _ptr(keys), _ptr(counts), _ptr(nuniq), _ptr(hist), _ptr(status), None, 0,
+                                        _stream(ptr)), "gmp_sp_features")
+    return SPFeatureMap(keys, counts, nuniq, hist, status)
+
+
+def sp_gram(keys_a: Tensor, counts_a: Tensor, nuniq_a: Tensor, keys_b: Tensor, counts_b: Tensor, nuniq_b: Tensor) -> Tensor:
+    """K int64 [Ga, Gb], the shortest-path kernel between two batches of sp_features (gnnmp.h gmp_sp_gram): K[i, j] = the sum over the keys
+    that graph i of a and graph j of b share of the product of their counts (the two may be the same tensors; their row strides may
+    differ).  Exact integers."""
+    for k, c, n, s in ((keys_a, counts_a, nuniq_a, "a"), (keys_b, counts_b, nuniq_b, "b")):
+        _need(k, torch.int64, f"keys_{s}", 2); _need(c, torch.int32, f"counts_{s}", 2); _need(n, torch.int32, f"nuniq_{s}", 1)
+        if k.shape != c.shape or n.numel() != k.size(0) or k.size(1) < 1:
+            raise L.GnnmpError(f"sp_gram: keys_{s} {tuple(k.shape)}, counts_{s} {tuple(c.shape)}, nuniq_{s} {tuple(n.shape)} ([G, cap], [G, cap], [G])")
+    dev = keys_a.device
+    if any(t.device != dev for t in (counts_a, nuniq_a, keys_b, counts_b, nuniq_b)):
+        raise L.GnnmpError("sp_gram: the six inputs must be on one device")
+    Ga, Gb = keys_a.size(0), keys_b.size(0)
+    K = torch.zeros(Ga, Gb, dtype=torch.int64, device=dev)
+    L.check(L.lib().gmp_sp_gram(_ptr(keys_a), _ptr(counts_a), _ptr(nuniq_a), Ga, keys_a.size(1), _ptr(keys_b), _ptr(counts_b), _ptr(nuniq_b), Gb,
+                                keys_b.size(1), _ptr(K), _stream(keys_a)), "gmp_sp_gram")
+    return K
+
+
 def _prop_args(who: str, rowptr: Tensor, col: Tensor, rows: int, what: str, left: Optional[Tensor], right: Optional[Tensor], others) -> int:
     """n of the int32 CSR that label_propagate / feature_propagate walk: rowptr [n + 1] for the `rows` rows of the matrix `what`, left /
     right fp32 [n] or None, and these and `others` on rowptr's device."""

@@ -698,6 +698,51 @@ int gmp_wl_gram(const int64_t* sorted_a, const int64_t* ptr_a, int64_t num_graph
                 const int64_t* ptr_b, int64_t num_graphs_b, int64_t len_b, int iters, int64_t* K, gmp_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
+ * The shortest-path kernel baseline of graph classification (Borgwardt & Kriegel, ICDM 2005; csrc/sp.hip): the exact feature map of
+ * (label, label, hop distance) triples of a batch of graphs, one workgroup per graph, and the kernel between two batches -- a delta kernel
+ * on the two labels and on the distance.  Integer arithmetic only; mix and K1 are those of the Weisfeiler-Lehman block above.
+ * The batch is described as for gmp_wl_refine: ptr int64 [num_graphs + 1] node offsets, a simple undirected CSR over the batch's nodes,
+ * rowptr int32 [num_nodes + 1] and col int32 [nnz] (rowptr is clamped to [0, nnz]), and labels int64 [num_nodes] or NULL: with NULL a
+ * node's label is its degree in the CSR counted inside its own graph.  An entry of col outside its row's own graph [ptr[g], ptr[g+1]) is
+ * skipped, never dereferenced, and counted in the graph's status word.  The adjacency is the entries' symmetric closure without self
+ * loops, whatever their order and multiplicity.
+ * For every unordered pair {u, v} of nodes of one graph with hop distance 1 <= d <= max_dist (1 <= max_dist <= 1023; the search stops
+ * after max_dist levels, unreachable pairs count nowhere), with lo <= hi the two labels, both in [0, 2^24):
+ *   key = (lo << 35) | (hi << 11) | d          (exact: nothing is hashed)
+ * gmp_sp_features writes, with the caller's row stride cap (1 <= cap <= gmp_sp_max_unique(max_graph_nodes)) and 1 <= dim <= 256:
+ *   keys   int64 [num_graphs, cap]  the graph's distinct keys in ascending order;
+ *   counts int32 [num_graphs, cap]  the number of pairs per key;
+ *   nuniq  int32 [num_graphs]       the number of distinct keys;
+ *   hist   int32 [num_graphs, dim]  hist[g, b] = the sum of counts over the keys with b = (uint32(mix(key + K1) >> 32) * dim) >> 32 -- the
+ *     hashed feature map;
+ *   status int32 [num_graphs]  bit 0 = the graph is refused for its size: n_g > min(max_graph_nodes, 1024), ptr decreasing, or its node
+ *     range leaves [0, num_nodes]; bit 1 = it has more than cap distinct keys; bit 2 = a label lies outside [0, 2^24); bits 8.. = the
+ *     number of skipped entries (saturating at 2^23 - 1).
+ * A graph with any of bits 0 - 2 set gets its status and nuniq[g] = 0 written and nothing else: its rows of keys, counts and hist keep what
+ * the caller left there, as do the entries of every row at and beyond nuniq[g].  n_g = 0 and 1 are valid and have no pairs.  The result
+ * does not depend on node numbering, neighbour order or scheduling.
+ * max_graph_nodes is the caller's bound on ptr[g+1] - ptr[g]; it selects the launch (n <= 256: 256 threads; n <= 1024: 1024 threads, one
+ * workgroup per CU) and, with cap, sizes the LDS: the n x n bit matrix, the labels and a table of 2^k >= 2 cap slots of 12 bytes.
+ * gmp_sp_max_unique(max_graph_nodes) is the largest cap the launch accepts: 4096 up to 256 nodes, 1024 above.  No workspace
+ * (gmp_sp_workspace_bytes is 0; workspace may be NULL).
+ * gmp_sp_gram: K int64 [num_graphs_a, num_graphs_b], K[i, j] = the sum over the keys present in row i of a and in row j of b of
+ * count_a * count_b, between two outputs of gmp_sp_features with row strides cap_a and cap_b in [1, 4096] (they may be the same arrays).
+ * One wave per entry, the shorter row binary-searched in the longer, int64 products, no atomics.  nuniq is clamped to [0, cap]: on unsorted
+ * input the result is wrong, but nothing outside the rows is read.
+ * Both: asynchronous on `stream`, no allocation, no global state, no host read-back.  GMP_ERR_ARG before any launch on a null pointer
+ * (labels may be NULL), max_dist outside [1, 1023], dim outside [1, 256], cap outside its range, a negative size, num_nodes or nnz >= 2^31,
+ * or a Gram of more than 2^33 entries.  num_graphs == 0, num_graphs_a == 0 and num_graphs_b == 0 are no-ops.
+ * ------------------------------------------------------------------------- */
+size_t gmp_sp_workspace_bytes(int num_graphs, int64_t max_graph_nodes);
+int gmp_sp_max_unique(int64_t max_graph_nodes);
+int gmp_sp_features(const int64_t* ptr, int num_graphs, const int32_t* rowptr, const int32_t* col, int64_t num_nodes, int64_t nnz,
+                    const int64_t* labels, int max_dist, int dim, int64_t max_graph_nodes, int cap, int64_t* keys, int32_t* counts,
+                    int32_t* nuniq, int32_t* hist, int32_t* status, void* workspace, size_t workspace_bytes, gmp_stream_t stream);
+int gmp_sp_gram(const int64_t* keys_a, const int32_t* counts_a, const int32_t* nuniq_a, int64_t num_graphs_a, int cap_a,
+                const int64_t* keys_b, const int32_t* counts_b, const int32_t* nuniq_b, int64_t num_graphs_b, int cap_b, int64_t* K,
+                gmp_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
  * Degree-normalised propagation of a narrow matrix over a graph, iterated with a teleport term (csrc/label_prop.hip): label spreading
  * (Zhou et al. 2004), label propagation (Zhu & Ghahramani 2002), and the smoothing step of APPNP and Correct-and-Smooth.
  * The graph is a CSR, rowptr int32 [n + 1] and col int32 [nnz]; left and right are fp32 [n] scales, NULL = all ones; f0 and f_init are
