@@ -166,6 +166,7 @@ _SIGS: Dict[str, tuple] = {
     "gmp_label_propagate": (C.c_int, [p, p, i64, i64, p, p, p, p, p, i32, i32, f32, f32, p, p, p, p, p, sz, p]),
     "gmp_feature_propagate_workspace_bytes": (sz, [i64, i32, i32]),
     "gmp_feature_propagate": (C.c_int, [p, p, i64, i64, p, p, p, i64, p, p, p, i64, i32, i32, p, i64, p, p, sz, p]),
+    "gmp_graph_feature_map": (C.c_int, [p, i32, p, p, i64, i64, p, p, p, i64, i32, i32, i64, p, p, p]),
     "gmp_gc_head_fwd_workspace_bytes": (sz, [i64]),
     "gmp_gc_head_fwd": (C.c_int, [p, i64, p, i64, i64, i32, i32, i32, p, p, p, p, p, p, p, p, p, p, p, f32, C.c_uint64, C.c_uint32, p, sz, p]),
     "gmp_gc_head_bwd": (C.c_int, [p, i64, i64, i32, i32, i32, p, p, p, p, p, f32, C.c_uint64, C.c_uint32, p, p, p, p, p, i64, p]),

@@ -4,7 +4,7 @@ test metrics from the best checkpoint.  Data come from the loaders of gnn_pretra
 data/processed; synthetic stand-ins are generated when none were exported).  wandb is replaced by a JSONL logger with the
 same metric keys.  Build-only flags: --epochs, --device, --data-root, --data-scale, --log, --sparse-features, --lp-engine, --gc-engine,
 --engine-eval, --lp-ranking, --device-metrics, --miner, --knn-probe, --cluster-probe, --logreg-probe, --repr-stats, --lp-heuristics,
---wl-baseline, --label-propagation, --link-probe, --sgc-baseline, --sp-baseline."""
+--wl-baseline, --label-propagation, --link-probe, --sgc-baseline, --sp-baseline, --feat-baseline."""
 from __future__ import annotations
 
 import argparse
@@ -159,6 +159,7 @@ class FinetuneConfig:
     lp_walks: int = 0                   # link-prediction domains: rounds of the walk-based baselines; the test record also carries test/{katz,ppr,hops}_mrr / _hits@K, ranked like lp_heuristics on the message-passing graph (link_walks.py); needs no engine; 0 = off
     link_probe: bool = False            # link-prediction domains on the engine: the parameter-free embedding link probe (link_probe.py): val/embed_{cos,dot}_mrr / _auc every epoch and once before training, test/embed_{cos,dot}_mrr / _hits@K / _auc
     sgc_baseline: int = 0               # node-classification domains: K of the SGC baseline S^K X and, beside it, the raw-feature baseline, both a softmax regression fitted on the train split (node_baselines.py: test/rawfeat_accuracy, test/sgc_accuracy); needs no engine and no probe; 0 = off
+    feat_baseline: int = 0              # graph-classification domains: K of the pooled-feature baselines -- the sum / mean / max pools of the raw node features (no graph) and of S^t X, t = 0 .. K, each under a k-NN vote and a softmax regression fitted on the train split (graph_baselines.py: test/rawpool_{knn,logreg}_accuracy, test/sgcpool_{knn,logreg}_accuracy); needs no engine and no probe; 0 = off
     sp_baseline: int = 0                # graph-classification domains: the largest hop distance of the shortest-path kernel baseline on the raw graphs (graph_baselines.py: test/sp_knn_accuracy, test/sp_logreg_accuracy); needs no engine and no probe; 0 = off
     wl_baseline: int = 0                # graph-classification domains: rounds of the Weisfeiler-Lehman subtree baseline on the raw graphs (graph_baselines.py: test/wl_knn_accuracy, test/wl_logreg_accuracy); needs no engine and no probe; 0 = off
 
@@ -200,7 +201,7 @@ class FinetuneConfig:
                              "pass lp_engine (--lp-engine)")
         if self.lp_ranking and not self.lp_engine:
             raise ValueError("lp_ranking ranks with the link-prediction engine (gmp_lp_rank): pass lp_engine (--lp-engine)")
-        for b in BASELINES + EXTRA_BASELINES:
+        for b in ALL_BASELINES:
             value = getattr(self, b.field)
             if b.max_value is not None and not 0 <= value <= b.max_value:
                 raise ValueError(f"{b.field}={value} ({b.bound.format(b.max_value)})")
@@ -473,6 +474,15 @@ def sp_baseline_keys(train_loader, test_loader, device, cfg: FinetuneConfig) -> 
     return {f"test/sp_{k}": v for k, v in scores.items()}
 
 
+def feat_baseline_keys(train_loader, test_loader, device, cfg: FinetuneConfig) -> Dict[str, float]:
+    """cfg.feat_baseline: the baselines that read the node FEATURES, which the two kernels above never do on continuous ones -- the pooled
+    raw features (structure-blind, Errica et al. 2020) and the pooled S^t X, t = 0 .. cfg.feat_baseline (SGC, concatenated over the
+    scales), each under the k-NN vote and the softmax regression (graph_baselines.feature_baseline).  Reads the datasets and nothing
+    else, as wl_baseline_keys."""
+    scores = GB.feature_baseline(train_loader.dataset, test_loader.dataset, NUM_CLASSES[cfg.domain_name], cfg.feat_baseline, device=device)
+    return {f"test/{k}": v for k, v in scores.items()}
+
+
 def node_baseline_keys(baselines: Callable, rounds: int, train_loader, test_loader, device, cfg: FinetuneConfig) -> Dict[str, float]:
     """What test/accuracy has to beat on a node-classification domain, fitted on the train split and scored on the test split.
     cfg.label_propagation (node_baselines.label_baselines): label spreading and label propagation with that many rounds over the whole raw
@@ -534,6 +544,17 @@ EXTRA_BASELINES = (
              "kernel baseline over node pairs at hop distance 1..D (D up to 1023) on the raw graphs, fitted on the train split and "
              "scored on the test split (needs neither --gc-engine nor a probe flag; combines with --wl-baseline); 0 = off"),
 )
+# A further tuple for the same reason: tests/test_sp_host.py pins EXTRA_BASELINES to its one row.
+FEATURE_BASELINES = (
+    Baseline("feat_baseline", "--feat-baseline", "K", ops.GRAPH_FEAT_MAX_ROUNDS, ROUNDS, *GC, lambda tr, va, te, dev, cfg: feat_baseline_keys(tr, te, dev, cfg),
+             "ENZYMES / PTC_MR: the test record also carries test/rawpool_knn_accuracy, test/rawpool_logreg_accuracy, "
+             "test/sgcpool_knn_accuracy and test/sgcpool_logreg_accuracy: the sum, mean and max pools of the raw node features (no "
+             "graph: the structure-blind baseline) and of S^t X for t = 0..K (K rounds 1..16 of the degree-scaled propagation with "
+             "self-loops, concatenated), standardised by the train split, each under a 20-NN vote and a softmax regression fitted on "
+             "the train split and scored on the test split (needs neither --gc-engine nor a probe flag; combines with --wl-baseline "
+             "and --sp-baseline); 0 = off"),
+)
+ALL_BASELINES = BASELINES + EXTRA_BASELINES + FEATURE_BASELINES             # what the four loops walk (config check, test record, parser, config_from_args)
 
 
 def probe_embeddings(engine, datasets, device, cfg: FinetuneConfig):
@@ -705,7 +726,7 @@ def finetune(cfg: FinetuneConfig, epochs: Optional[int] = None, device: Optional
     test.update(run_probes(probe_engine, train_loader, test_loader, dev, cfg, "test", known))
     if cfg.lp_ranking:
         test.update(rank_test_edges(lp_engine, train_loader, val_loader, test_loader, dev))
-    for b in BASELINES + EXTRA_BASELINES:
+    for b in ALL_BASELINES:
         if getattr(cfg, b.field):
             test.update(b.keys(train_loader, val_loader, test_loader, dev, cfg))
     logger.log(test, global_step[0])
@@ -718,7 +739,7 @@ def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser()
 
     def add_baselines(task_types: Tuple[str, ...]) -> None:              # (--help lists the flags in the order they were added)
-        for b in BASELINES + EXTRA_BASELINES:
+        for b in ALL_BASELINES:
             if b.task_type in task_types:
                 kind = {"action": "store_true"} if b.max_value is None else {"type": int, "default": 0, "metavar": b.metavar}
                 p.add_argument(b.flag, help=b.help, **kind)
@@ -761,7 +782,7 @@ def config_from_args(a: argparse.Namespace) -> FinetuneConfig:
                           engine_eval=getattr(a, "engine_eval", False), lp_ranking=getattr(a, "lp_ranking", False),
                           device_metrics=getattr(a, "device_metrics", False), miner_impl=getattr(a, "miner", "matrix"),
                           repr_stats=getattr(a, "repr_stats", False), link_probe=getattr(a, "link_probe", False),
-                          **{b.field: getattr(a, b.field, False if b.max_value is None else 0) for b in BASELINES + EXTRA_BASELINES},
+                          **{b.field: getattr(a, b.field, False if b.max_value is None else 0) for b in ALL_BASELINES},
                           **{p.field: getattr(a, p.field, 0) for p in PROBES})
 
 

@@ -17,6 +17,16 @@ rooted neighbourhoods, it compares graphs by their distributions of (label, labe
     sp_kernel(feat_a, feat_b)                             the int64 Gram of the shortest-path kernel between two SPFeatures
     sp_self_similarity(feat)                              the Gram's diagonal from the counts alone
     sp_baseline(train_ds, eval_ds, num_classes, max_dist, k=20, device="cuda") {"knn_accuracy", "logreg_accuracy"}
+
+And the two baselines that read the FEATURES, which the kernels above never do on continuous ones: the structure-blind classifier on pooled
+raw features (Errica et al., ICLR 2020) and SGC's S^t X (Wu et al., ICML 2019) pooled per graph and concatenated over t = 0 .. K (the
+multi-scale concatenation of SIGN, Frasca et al. 2020), pooled on the GPU in one launch per batch (csrc/graph_feat.hip; the definition is
+above gmp_graph_feature_map) -- the graph-level pair of node_baselines' rawfeat / sgc.
+
+    pooled_features(batch, rounds)                        fp32 [G, (rounds + 1) * 3 * d]: per level t the sum, mean and max pool of S^t X
+    standardise(train, other)                             both by the train rows' column mean and population deviation (float64, rounded once)
+    feature_baseline(train_ds, eval_ds, num_classes, rounds, k=20, device="cuda")
+        {"rawpool_knn_accuracy", "rawpool_logreg_accuracy", "sgcpool_knn_accuracy", "sgcpool_logreg_accuracy"}
 """
 from __future__ import annotations
 
@@ -28,6 +38,7 @@ from torch import Tensor
 from .. import ops
 from .._lib import GnnmpError
 from .link_heuristics import simple_graph
+from .node_baselines import sgc_graph, softmax_fit
 
 
 class WLFeatures(NamedTuple):
@@ -198,3 +209,75 @@ def sp_baseline(train_ds, eval_ds, num_classes: int, max_dist: int, k: int = 20,
     if not 1 <= int(max_dist) <= ops.SP_MAX_DIST:
         raise ValueError(f"sp_baseline: max_dist={max_dist} (1 <= max_dist <= {ops.SP_MAX_DIST})")
     return _kernel_baseline("sp_baseline", lambda b: sp_features(b, max_dist), sp_kernel, train_ds, eval_ds, num_classes, k, device)
+
+
+def pooled_features(batch, rounds: int) -> Tensor:
+    """fp32 [G, (rounds + 1) * 3 * d] of one collated Batch on the GPU: for t = 0 .. rounds the sum, mean and max pool (in that order, d
+    columns each) over every graph's nodes of S^t X, S = D~^-1/2 (A + I) D~^-1/2 (ops.graph_feature_map on node_baselines.sgc_graph: the
+    simple graph plus one self-loop per node, the host-computed 1 / sqrt(deg + 1) as both scales).  The first 3 d columns are the pools of
+    the raw features: no graph.  Raises GnnmpError naming the first graph the kernel refuses (more than ops.GRAPH_FEAT_MAX_GRAPH_NODES
+    nodes), and when a CSR entry was skipped for leaving its graph (one read-back of the status words)."""
+    if not batch.x.is_cuda:
+        raise GnnmpError(f"pooled_features: expected a batch on the GPU (the HIP path has no CPU fallback), got {batch.x.device}")
+    rowptr, col, scale = sgc_graph(batch.edge_index.contiguous(), batch.num_nodes)
+    res = ops.graph_feature_map(batch.ptr.to(torch.int64).contiguous(), rowptr, col, batch.x.to(torch.float32), rounds, left=scale, right=scale,
+                                max_graph_nodes=batch.max_graph_nodes)
+    status = res.status.cpu()
+    if bool((status & 1).any()):
+        g = int((status & 1).nonzero()[0])
+        raise GnnmpError(f"pooled_features: graph {g} has {batch.ptr_host[g + 1] - batch.ptr_host[g]} nodes, more than the "
+                         f"{ops.GRAPH_FEAT_MAX_GRAPH_NODES} the kernel takes (there is no host fallback)")
+    if bool((status >> 8).any()):
+        g = int((status >> 8).nonzero()[0])
+        raise GnnmpError(f"pooled_features: {int(status[g] >> 8)} adjacency entries of graph {g} point outside the graph and were skipped")
+    return res.out.reshape(res.out.size(0), -1)
+
+
+def standardise(train: Tensor, other: Tensor) -> Tuple[Tensor, Tensor]:
+    """(train', other') fp32 on their devices: per column, minus the TRAIN rows' mean, divided by their population standard deviation;
+    a column whose deviation is 0 becomes all zeros in both.  Mean, deviation and the quotient are float64 on the host, rounded once to
+    fp32 (the rule of node_baselines.degree_scales: the device's arithmetic never enters a value)."""
+    t, o = train.detach().to("cpu", torch.float64), other.detach().to("cpu", torch.float64)
+    mean = t.mean(dim=0, keepdim=True)
+    std = ((t - mean) ** 2).mean(dim=0, keepdim=True).sqrt()
+    ok = std > 0
+    safe = torch.where(ok, std, torch.ones_like(std))
+    z = lambda m: torch.where(ok, (m - mean) / safe, torch.zeros_like(m)).to(torch.float32)          # noqa: E731
+    return z(t).to(train.device), z(o).to(other.device)
+
+
+FEATURE_KINDS = ("rawpool", "sgcpool")
+
+
+def feature_baseline(train_ds, eval_ds, num_classes: int, rounds: int, k: int = 20, device="cuda") -> Dict[str, float]:
+    """{"rawpool_knn_accuracy", "rawpool_logreg_accuracy", "sgcpool_knn_accuracy", "sgcpool_logreg_accuracy"}, fitted on train_ds and
+    scored on eval_ds (two graph datasets with collate()).  Each split is collated into ONE batch in dataset order and gets one
+    pooled_features call with `rounds` rounds.  rawpool is its t = 0 slice -- the 3 d pools of the raw features, no graph: the
+    structure-blind baseline -- and sgcpool all rounds + 1 slices; both are standardised by the train split.
+    knn, by the protocol of _kernel_baseline: the Gram Z_e Z_t^T and the two diagonals in torch fp64 (a few hundred squared), then
+    normalised_similarity, wl_neighbours(sim, k) and ops.knn_vote at its default temperature.
+    logreg: node_baselines.softmax_fit at its defaults on the train rows, prediction ops.gemm(NT, Z_e, W, bias).argmax, as
+    node_baselines.feature_baselines does for nodes."""
+    if not 1 <= int(rounds) <= ops.GRAPH_FEAT_MAX_ROUNDS:
+        raise ValueError(f"feature_baseline: rounds={rounds} (1 <= rounds <= {ops.GRAPH_FEAT_MAX_ROUNDS})")
+    if not 1 <= int(k) <= ops.KNN_MAX_K:
+        raise ValueError(f"feature_baseline: k={k} (1 <= k <= {ops.KNN_MAX_K})")
+    if len(train_ds) == 0 or len(eval_ds) == 0:
+        raise ValueError(f"feature_baseline: {len(train_ds)} train and {len(eval_ds)} evaluation graphs (both splits need one)")
+    tb, eb = _collate(train_ds, device), _collate(eval_ds, device)
+    pt, pe = pooled_features(tb, int(rounds)), pooled_features(eb, int(rounds))
+    y_train, y_eval = tb.y.to(torch.int64).contiguous(), eb.y.to(torch.int64).contiguous()
+    raw = pt.size(1) // (int(rounds) + 1)                                          # 3 d: the t = 0 slice
+    scores: Dict[str, float] = {}
+    for name, width in zip(FEATURE_KINDS, (raw, pt.size(1))):
+        zt, ze = standardise(pt[:, :width], pe[:, :width])
+        zt, ze = zt.contiguous(), ze.contiguous()
+        zt64, ze64 = zt.to(torch.float64), ze.to(torch.float64)
+        sim = normalised_similarity(ze64 @ zt64.T, (ze64 * ze64).sum(dim=1), (zt64 * zt64).sum(dim=1))
+        idx, val = wl_neighbours(sim, k)
+        _, knn_pred = ops.knn_vote(idx, val.to(torch.float32).contiguous(), y_train, num_classes)
+        weight, bias, _ = softmax_fit(zt, y_train, num_classes)
+        lr_pred = ops.gemm(ops.NT, ze, weight, bias=bias).argmax(dim=1)
+        scores[f"{name}_knn_accuracy"] = float((knn_pred == y_eval).float().mean())
+        scores[f"{name}_logreg_accuracy"] = float((lr_pred == y_eval).float().mean())
+    return scores

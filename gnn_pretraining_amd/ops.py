@@ -1888,6 +1888,48 @@ def feature_propagate(rowptr: Tensor, col: Tensor, x, rounds: int, left: Optiona
     return FeaturePropagation(out, status)
 
 
+GRAPH_FEAT_MAX_ROUNDS, GRAPH_FEAT_MAX_DIM, GRAPH_FEAT_MAX_GRAPH_NODES = 16, 256, 1024     # gmp_graph_feature_map (gnnmp.h)
+GRAPH_FEAT_POOLS = ("sum", "mean", "max")
+
+
+class GraphFeatureMap(NamedTuple):
+    """graph_feature_map's outputs (gnnmp.h gmp_graph_feature_map)."""
+    out: Tensor                    # fp32 [G, rounds + 1, 3, d]: per graph and level t the sum, mean and max pool of H(t) = S^t X
+    status: Tensor                 # int32 [G]: bit 0 = refused (too large, all its outputs +0), bits 8.. = skipped CSR entries
+
+
+def graph_feature_map(ptr: Tensor, rowptr: Tensor, col: Tensor, x: Tensor, rounds: int, left: Optional[Tensor] = None,
+                      right: Optional[Tensor] = None, max_graph_nodes: Optional[int] = None) -> GraphFeatureMap:
+    """The pooled-feature map of a batch of graphs in one launch (gnnmp.h gmp_graph_feature_map holds the definition; csrc/graph_feat.hip):
+    per graph the sum, mean and max pool (GRAPH_FEAT_POOLS) over its nodes of H(t), t = 0 .. rounds, with H(0) = x and H(t + 1) =
+    left[i] * (sum over the row's entries j inside the graph, in order, of right[j] * H(t)[j]) -- on a well-formed batch the bits of
+    feature_propagate.  ptr int64 [G + 1] node offsets, (rowptr, col) ONE int32 CSR over the batch's N nodes, x fp32 [N, d] with contiguous
+    rows (any leading dimension), 1 <= d <= 256, 0 <= rounds <= 16, left / right fp32 [N] or None (ones).  max_graph_nodes: the largest
+    ptr[g + 1] - ptr[g] when the caller knows it (None reads it back from ptr, one synchronisation); a graph above it, or above 1024
+    nodes, is refused with status bit 0 and zero outputs.  Returns GraphFeatureMap(out, status); no other read-back: status stays on the
+    device."""
+    _need(ptr, torch.int64, "ptr", 1)
+    _need_rows(x, "x")
+    G, d = ptr.numel() - 1, int(x.size(1))
+    N = _prop_args("graph_feature_map", rowptr, col, int(x.size(0)), "x", left, right, (ptr, x))
+    if G < 0:
+        raise L.GnnmpError(f"graph_feature_map: ptr {tuple(ptr.shape)} (G + 1 entries)")
+    if not 1 <= d <= GRAPH_FEAT_MAX_DIM or not 0 <= int(rounds) <= GRAPH_FEAT_MAX_ROUNDS:
+        raise L.GnnmpError(f"graph_feature_map: d={d} rounds={rounds} (1 <= d <= {GRAPH_FEAT_MAX_DIM}, 0 <= rounds <= {GRAPH_FEAT_MAX_ROUNDS})")
+    if max_graph_nodes is None:
+        max_graph_nodes = max(int((ptr[1:] - ptr[:-1]).max()), 0) if G else 0
+    if int(max_graph_nodes) < 0:
+        raise L.GnnmpError(f"graph_feature_map: max_graph_nodes={max_graph_nodes} (>= 0)")
+    rounds, dev = int(rounds), ptr.device
+    out = torch.empty(G, rounds + 1, len(GRAPH_FEAT_POOLS), d, device=dev)
+    status = torch.zeros(G, dtype=torch.int32, device=dev)
+    if G:
+        L.check(L.lib().gmp_graph_feature_map(_ptr(ptr), G, _ptr(rowptr), _ptr(col), N, col.numel(), _ptr(left), _ptr(right), _ptr(x),
+                                              x.stride(0) if x.size(0) > 1 else d, d, rounds, int(max_graph_nodes), _ptr(out), _ptr(status),
+                                              _stream(ptr)), "gmp_graph_feature_map")
+    return GraphFeatureMap(out, status)
+
+
 def gc_head_fwd(h: Tensor, ptr: Tensor, w0: Tensor, b0: Tensor, w3: Tensor, b3: Tensor, target: Tensor, g_scale: Tensor, p: float = 0.0,
                 seed: int = 0, site: int = 0) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
     """The fused graph-classification head up to the loss (gnnmp.h gmp_gc_head_fwd): h [N, 256] (rows contiguous, any leading dimension),

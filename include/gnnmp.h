@@ -816,6 +816,45 @@ int gmp_feature_propagate(const int32_t* rowptr, const int32_t* col, int64_t n, 
                           gmp_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
+ * The pooled-feature map of a batch of graphs (csrc/graph_feat.hip): the sum, mean and max pools of X, S X, .. S^rounds X per graph --
+ * what the structure-blind baseline of Errica et al. (ICLR 2020) reads at rounds = 0, and SGC's features (Wu et al. 2019) pooled and
+ * concatenated over the scales as in SIGN (Frasca et al. 2020) above it.  One launch per batch, one workgroup per (graph, strip of 16
+ * columns).
+ * The batch: ptr int64 [num_graphs + 1] node offsets (clamped to [0, num_nodes]); ONE CSR over all num_nodes nodes, rowptr int32
+ * [num_nodes + 1] (clamped to [0, nnz]) and col int32 [nnz]; left and right fp32 [num_nodes] scales, NULL = all ones; x fp32
+ * [num_nodes, d] with leading dimension ldx.  Self-loops are the caller's business, as for gmp_feature_propagate.
+ * All arithmetic is IEEE fp32, every multiply and every add rounded on its own (no fused multiply-add), subnormals kept.  H(0) = X.
+ * For round t = 0 .. rounds - 1, graph g with the window [b, e) = [ptr[g], ptr[g+1]), row i in the window, column c:
+ *   acc = +0;  for k = rowptr[i] .. rowptr[i+1] - 1, ASCENDING:  j = col[k]
+ *              if b <= j < e:  acc = acc + (right[j] * H(t)[j, c])      else: skipped by a select (not added as zero) and counted
+ *   H(t+1)[i, c] = left[i] * acc
+ * and for every t = 0 .. rounds the three pools over the graph's n_g = e - b rows:
+ *   sum [g, t, c]:  s = +0;  for i = b .. e - 1, ASCENDING:  s = s + H(t)[i, c]
+ *   mean[g, t, c]:  sum / (float)n_g      (one correctly rounded division; n_g = 0 gives +0)
+ *   max [g, t, c]:  the largest H(t)[i, c] under the integer order on the orderable bit pattern that gmp_label_propagate's argmax uses
+ *                   (so -0 < +0; n_g = 0 gives +0)
+ * out fp32, contiguous, [num_graphs, rounds + 1, 3, d], pool order sum, mean, max.
+ * On a well-formed batch no entry leaves its graph; H(t) then has the bits gmp_feature_propagate leaves over the whole batch.  Inputs are
+ * finite by contract: non-finite values give unspecified numbers, never an access out of range.
+ * status int32 [num_graphs], written inside the call.  Bit 0 = the graph has more nodes than the call takes -- more than 1024 or more
+ * than max_graph_nodes, the caller's bound on ptr[g+1] - ptr[g]: all its outputs are +0.  Bits 8 .. 30 = the number of skipped adjacency
+ * entries of the graph, each counted once (in round 1, by the workgroup of the first strip), saturating at 2^23 - 1; rounds == 0 reads no
+ * adjacency entry and counts none.  A malformed rowptr or ptr gives wrong numbers and reads nothing outside the arrays.
+ * max_graph_nodes selects the launch: graphs up to 256 nodes take a workgroup of 256 threads, graphs up to 1024 nodes one of 1024; a
+ * bound above 256 launches both and each workgroup leaves at once when its graph belongs to the other.  It also sizes the LDS, which holds
+ * the two ping-pong copies of the graph's strip of H and its left and right from the first load to the last pool: global memory sees x
+ * once, the CSR rows once per round, and the [rounds + 1, 3, 16] results.
+ * Determinism: every sum is sequential, there is no floating-point atomic (the skipped entries are counted by an integer atomic in LDS),
+ * so two calls leave the same bits.
+ * 0 <= num_graphs, 0 <= num_nodes, nnz < 2^31, 1 <= d <= 256, 0 <= rounds <= 16, 0 <= max_graph_nodes.  GMP_ERR_ARG, with nothing launched:
+ * a size outside those ranges, a null required pointer (ptr, rowptr, out, status; col when nnz > 0; x when num_nodes > 0), ldx < d, or out
+ * overlapping x.  num_graphs == 0 returns GMP_OK and writes nothing.  Asynchronous, no allocation, no global state, no workspace.
+ * ------------------------------------------------------------------------- */
+int gmp_graph_feature_map(const int64_t* ptr, int num_graphs, const int32_t* rowptr, const int32_t* col, int64_t num_nodes, int64_t nnz,
+                          const float* left, const float* right, const float* x, int64_t ldx, int32_t d, int32_t rounds,
+                          int64_t max_graph_nodes, float* out, int32_t* status, gmp_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
  * The fused graph-classification head of fine-tuning (finetune_model.py:68-80, finetune.py:110-114) over one batch of
  * num_graphs graphs; graph b owns the rows ptr[b] .. ptr[b+1] of h (ptr: device int32 [num_graphs + 1]):
  *   pooled[b] = mean of the graph's rows, divisor max(count, 1) (gmp_segment_sum(mean = 1); an empty graph pools to zero),

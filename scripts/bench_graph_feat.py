@@ -1,0 +1,166 @@
+"""The pooled-feature map (sum, mean and max pools of X, S X, .. S^K X per graph, S = D~^-1/2 (A + I) D~^-1/2) on the synthetic batches of
+ENZYMES, NCI1 and PROTEINS shape that scripts/bench_wl.py uses, with the feature widths of those datasets, three routes in one process:
+
+  kernel   ops.graph_feature_map (gmp_graph_feature_map: one launch per batch, a workgroup per graph and strip of 16 columns, H in LDS)
+  chain    the ops the library had before it: ops.feature_propagate once per round, and per level ops.segment_sum, ops.segment_sum(mean)
+           and ops.segment_max_fwd -- 4 K + 3 launches and every H(t) through global memory.  segment_max_fwd takes widths that are a
+           multiple of 4, so this route runs on x padded with zero columns (padded before the clock starts)
+  torch    torch.sparse.mm with the CSR (or, where that fails, COO) matrix S per round, and per level torch.segment_reduce sum / mean / max
+           (or, where that fails, scatter_reduce)
+
+    python scripts/bench_graph_feat.py [--rounds 3] [--reps 20] [--warmup 3] [--out profiles/graph_feat.json]
+
+The graph (node_baselines.sgc_graph), the padded x and the sparse matrix are built before the clock starts.  Routes run alternately and are
+timed per call by a host clock around work that ends in a synchronise and by device events; the figure reported is the median of the
+rounds of `reps` calls.  Peak memory is torch's allocator peak over a route's first call, above what was allocated before it (the inputs).
+What must agree: the chain walks its rows with the same row fold, so its max slice equals the kernel's bit for bit on the timed input.
+torch.sparse.mm multiplies by the products scale_i scale_j in an order of its own, so on the timed input its values differ in the last
+bits (the largest difference is recorded); all three routes are therefore ALSO run once on features in {-1, 0, 1} without scales, where
+every H(t) is a small integer and exact in any order, and there the three max slices must be equal exactly.  The script fails when one of
+these is not."""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import torch  # noqa: E402
+
+from bench_wl import DEV, SHAPES, attempt, peak_mb, synthetic_batch, timed  # noqa: E402
+from gnn_pretraining_amd import ops  # noqa: E402
+from gnn_pretraining_amd.finetune.node_baselines import sgc_graph  # noqa: E402
+
+WIDTHS = {"ENZYMES": 21, "NCI1": 37, "PROTEINS": 4}
+MAX = ops.GRAPH_FEAT_POOLS.index("max")
+
+
+def make_routes(ptr, rowptr, col, scale, x, rounds: int, mgn: int):
+    """{name: fn -> fp32 [G, rounds + 1, 3, d]} on one input; scale None = no scaling.  Setup (padding, the sparse matrix, the segment
+    ids) happens here, outside the clock."""
+    G, N, d = ptr.numel() - 1, x.size(0), x.size(1)
+    ptr32, sizes = ptr.to(torch.int32), ptr[1:] - ptr[:-1]
+    dpad = (d + 3) // 4 * 4
+    xpad = torch.zeros(N, dpad, device=DEV)
+    xpad[:, :d] = x
+
+    def kernel():
+        return ops.graph_feature_map(ptr, rowptr, col, x, rounds, left=scale, right=scale, max_graph_nodes=mgn).out
+
+    def chain():
+        H, out = xpad, torch.empty(G, rounds + 1, 3, dpad, device=DEV)
+        for t in range(rounds + 1):
+            out[:, t, 0].copy_(ops.segment_sum(H, ptr32, None))
+            out[:, t, 1].copy_(ops.segment_sum(H, ptr32, None, mean=True))
+            out[:, t, 2].copy_(ops.segment_max_fwd(H, ptr32))
+            if t < rounds:
+                H = ops.feature_propagate(rowptr, col, H, 1, left=scale, right=scale).out
+        return out[..., :d]
+
+    deg = (rowptr[1:] - rowptr[:-1]).to(torch.int64)
+    row = torch.repeat_interleave(torch.arange(N, device=DEV), deg)
+    cl = col.to(torch.int64)
+    val = torch.ones(cl.numel(), device=DEV) if scale is None else scale[row] * scale[cl]
+    S, err = attempt(lambda: torch.sparse_csr_tensor(rowptr.to(torch.int64), cl, val, size=(N, N)))
+    layout = "csr"
+    if err is None:
+        _, err = attempt(lambda: torch.sparse.mm(S, x))
+    if err is not None:
+        S, layout = torch.sparse_coo_tensor(torch.stack([row, cl]), val, size=(N, N)).coalesce(), "coo"
+    gid = torch.repeat_interleave(torch.arange(G, device=DEV), sizes)
+
+    def reduce_segment(H, how):
+        return torch.segment_reduce(H, how, lengths=sizes, axis=0)
+
+    def reduce_scatter(H, how):
+        index = gid[:, None].expand(-1, H.size(1))
+        return torch.zeros(G, H.size(1), device=DEV).scatter_reduce_(0, index, H, {"sum": "sum", "mean": "mean", "max": "amax"}[how], include_self=False)
+
+    _, err = attempt(lambda: [reduce_segment(x, how) for how in ("sum", "mean", "max")])
+    reduce, reducer = (reduce_segment, "segment_reduce") if err is None else (reduce_scatter, "scatter_reduce")
+
+    def torch_route():
+        H, out = x, torch.empty(G, rounds + 1, 3, d, device=DEV)
+        for t in range(rounds + 1):
+            for p, how in enumerate(("sum", "mean", "max")):
+                out[:, t, p] = reduce(H, how)
+            if t < rounds:
+                H = torch.sparse.mm(S, H)
+        return out
+
+    return {"kernel": kernel, "chain": chain, "torch": torch_route}, f"{layout} + {reducer}"
+
+
+def bench_shape(name: str, graphs: int, mean_nodes: float, mean_edges: float, big: int, num_labels: int, a) -> dict:
+    gen = torch.Generator().manual_seed(graphs)
+    ptr, edge_index, N, _ = synthetic_batch(graphs, mean_nodes, mean_edges, big, num_labels, gen)
+    rowptr, col, scale = sgc_graph(edge_index, N)
+    mgn, d = int((ptr[1:] - ptr[:-1]).max()), WIDTHS[name]
+    x = torch.randn(N, d, generator=gen).to(DEV)
+    res = {"name": name, "graphs": graphs, "nodes": N, "nnz": int(col.numel()), "max_graph_nodes": mgn, "d": d, "rounds": a.rounds}
+
+    # exact agreement where every order is exact: features in {-1, 0, 1}, no scales
+    xi = torch.randint(-1, 2, (N, d), generator=gen).to(torch.float32).to(DEV)
+    exact, res["torch_form"] = make_routes(ptr, rowptr, col, None, xi, a.rounds, mgn)
+    outs = {k: fn() for k, fn in exact.items()}
+    assert float(outs["kernel"].abs().max()) < 2 ** 24
+    res["max_equal_on_integers"] = {k: bool(torch.equal(outs[k][:, :, MAX], outs["kernel"][:, :, MAX])) for k in ("chain", "torch")}
+    res["all_pools_equal_on_integers"] = {k: bool(torch.equal(outs[k], outs["kernel"])) for k in ("chain", "torch")}
+    del outs, exact
+
+    routes, _ = make_routes(ptr, rowptr, col, scale, x, a.rounds, mgn)
+    status = ops.graph_feature_map(ptr, rowptr, col, x, a.rounds, left=scale, right=scale, max_graph_nodes=mgn).status
+    res["status_bits"] = {"too_large": int((status & 1).ne(0).sum()), "skipped_entries": int((status >> 8).sum())}
+    outs = {}
+    for k, fn in routes.items():
+        fn()
+        peak, outs[k] = peak_mb(fn)
+        res[f"{k}_peak_mb"] = round(peak, 3)
+    res["max_equal_chain"] = bool(torch.equal(outs["chain"][:, :, MAX], outs["kernel"][:, :, MAX]))
+    res["torch_max_abs_diff"] = float((outs["torch"] - outs["kernel"]).abs().max())
+    res["chain_max_abs_diff"] = float((outs["chain"] - outs["kernel"]).abs().max())
+    del outs
+    for _ in range(a.warmup):
+        for fn in routes.values():
+            fn()
+    times = {k: [] for k in routes}
+    for _ in range(5):                                                            # alternate the routes: the order does not decide the result
+        for k, fn in routes.items():
+            times[k].append(timed(fn, a.reps))
+    for k, ts in times.items():
+        res[f"{k}_ms"] = round(statistics.median(t[0] for t in ts), 4)
+        res[f"{k}_event_ms"] = round(statistics.median(t[1] for t in ts), 4)
+        res[f"{k}_event_ms_runs"] = [round(t[1], 4) for t in ts]
+    return res
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    res = {"what": "sum / mean / max pools per graph of X, S X, .. S^K X of one batch; kernel = gmp_graph_feature_map (one launch), chain = "
+                   "ops.feature_propagate per round + ops.segment_sum / segment_sum(mean) / segment_max_fwd per level on x padded to a multiple "
+                   "of 4 columns, torch = torch.sparse.mm per round + segment_reduce (or scatter_reduce) per level; *_ms = median over 5 "
+                   "alternating rounds of `reps` calls (host clock to a synchronise), *_event_ms = the same by device events",
+           "rounds": a.rounds, "reps": a.reps, "warmup": a.warmup, "device": torch.cuda.get_device_name(0),
+           "shapes": [bench_shape(*s, a) for s in SHAPES]}
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+    bad = [s["name"] for s in res["shapes"] if not s["max_equal_chain"] or not all(s["max_equal_on_integers"].values())]
+    if bad:
+        raise SystemExit(f"the routes disagree on the max slice on {bad}")
+
+
+if __name__ == "__main__":
+    main()

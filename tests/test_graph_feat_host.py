@@ -1,0 +1,167 @@
+"""Host-side checks of the pooled-feature baselines of graph classification (csrc/graph_feat.hip, finetune/graph_baselines.py,
+--feat-baseline): the preconditions of the separable fixture in tests/graph_feat_ref.py, the reference against itself, the flag and the
+config, the new symbol, and standardise against its float64 twin.  The kernel is compared against graph_feat_ref bit for bit in
+test_gpu_graph_feat.py."""
+import ctypes as C
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import graph_feat_ref as R
+from gnn_pretraining_amd import _lib as L, ops
+from gnn_pretraining_amd.finetune import finetune as FT, graph_baselines as GB
+
+BASE = ["--finetune_strategy", "full_finetune", "--pretrained_scheme", "b1", "--seed", "1"]
+MARGIN_FLOOR = 5.17                                                 # half of the 10.35 the float64 reference measures (see below)
+
+
+# ---------------------------------------------------------------------------- 1. the fixture's preconditions
+def test_raw_pools_are_constant_across_the_fixture():
+    graphs = R.fixture_graphs()
+    assert len(graphs) == R.N_TRAIN + R.N_EVAL and [c for _, _, _, c in graphs[:4]] == [0, 1, 0, 1]
+    assert sorted({n for n, _, _, _ in graphs}) == list(R.CYCLES)
+    raw = R.pooled(graphs, 0)
+    assert raw.shape == (60, 6) and (raw == raw[0]).all() and raw[0].tolist() == [0, 0, 0, 0, 1, 1]      # sum, mean, max of (v, -v)
+    ref = R.reference_baseline("rawpool")
+    assert ref.live_columns == 0 and not ref.z_train.any() and not ref.z_eval.any()
+    assert ref.logreg_accuracy == 0.5 and ref.knn_accuracy == 0.5                  # the majority share: nothing to read without the graph
+
+
+def test_two_rounds_separate_the_fixture_with_a_margin():
+    """The float64 reference on the fp32 features at K = 2: both accuracies are 1.0, and the smallest gap between the two largest logits
+    of an evaluation graph is 10.35 (measured on the CPU; 12 of the 18 columns vary over the train split).  The floor asserted here and
+    the bound of the GPU test are half of that."""
+    ref = R.reference_baseline("sgcpool")
+    print("smallest top-2 logit margin", ref.margin, "live columns", ref.live_columns)
+    assert ref.logreg_accuracy == 1.0 and ref.knn_accuracy == 1.0
+    assert ref.z_train.shape == (R.N_TRAIN, 18) and ref.live_columns == 12
+    assert ref.margin >= MARGIN_FLOOR
+    y_eval = np.arange(R.N_TRAIN, R.N_TRAIN + R.N_EVAL) % 2
+    assert np.array_equal(ref.logits.argmax(axis=1), y_eval)
+    mx = R.pooled(R.fixture_graphs(), 1).reshape(60, 2, 3, 2)[:, 1, 2, 0]          # the max pool of column 0 after one round
+    assert np.allclose(mx[0::2], 1.0, atol=1e-6) and np.allclose(mx[1::2], 1.0 / 3.0, atol=1e-6)
+
+
+# ---------------------------------------------------------------------------- 2. the reference against itself
+def test_reference_levels_pools_and_prefixes_agree():
+    b = R.make_batch(R.SMALL_SIZES, 3)
+    x = R.features(int(b.ptr[-1]), 5, 4)
+    full = R.feature_map(b.ptr, b.rowptr, b.col, x, 3, b.scale, b.scale)
+    assert full.out.shape == (len(R.SMALL_SIZES), 4, 3, 5) and not full.status.any()
+    for rounds in (0, 1):                                                          # fewer rounds: a prefix of the levels
+        assert np.array_equal(R.feature_map(b.ptr, b.rowptr, b.col, x, rounds, b.scale, b.scale).out, full.out[:, :rounds + 1])
+    H = R.levels(b.rowptr, b.col, x, 3, b.scale, b.scale)
+    for g, n in enumerate(R.SMALL_SIZES):
+        rows = slice(int(b.ptr[g]), int(b.ptr[g + 1]))
+        for t in range(4):
+            if n == 0:
+                assert not full.out[g, t].any() and not np.signbit(full.out[g, t]).any()
+                continue
+            assert np.array_equal(full.out[g, t, 2], H[t][rows].max(axis=0))
+            assert np.allclose(full.out[g, t, 0], H[t][rows].astype(np.float64).sum(axis=0), rtol=1e-4, atol=1e-4)
+            assert np.array_equal(full.out[g, t, 1], full.out[g, t, 0] / np.float32(n))
+    assert np.array_equal(full.out[1, 0, 0], x[0]) and np.array_equal(full.out[1, 0, 2], x[0])          # the one-node graph
+    bad, count = R.with_strays(b, 5, 4)
+    res = R.feature_map(bad.ptr, bad.rowptr, bad.col, x, 3, b.scale, b.scale)
+    assert res.status[5] == count << 8 and np.count_nonzero(res.status) == 1
+    assert not R.feature_map(bad.ptr, bad.rowptr, bad.col, x, 0, b.scale, b.scale).status.any()          # no round, no entry read
+    keep = [g for g in range(len(R.SMALL_SIZES)) if g != 5]
+    assert np.array_equal(res.out[keep], full.out[keep]) and not np.array_equal(res.out[5, 1:], full.out[5, 1:])
+    small = R.feature_map(b.ptr, b.rowptr, b.col, x, 3, b.scale, b.scale, max_graph_nodes=64)
+    assert np.array_equal(small.status == 1, np.array(R.SMALL_SIZES) > 64) and not small.out[small.status == 1].any()
+    zero = np.array([-0.0, 0.0, -1.0, np.float32(1e-40)], np.float32)
+    assert R.from_orderable(R.LP.orderable(zero)).view(np.uint32).tolist() == zero.view(np.uint32).tolist()
+
+
+# ---------------------------------------------------------------------------- 3. flag and config
+def _argv(domain, value):
+    return ["--domain_name", domain, "--feat-baseline", str(value)] + BASE
+
+
+def test_flag_parses_into_the_config_and_is_off_by_default():
+    assert (ops.GRAPH_FEAT_MAX_ROUNDS, ops.GRAPH_FEAT_MAX_DIM, ops.GRAPH_FEAT_MAX_GRAPH_NODES) == (16, 256, 1024)
+    assert ops.GRAPH_FEAT_POOLS == ("sum", "mean", "max") == R.POOLS
+    cfg = FT.config_from_args(FT.build_parser().parse_args(_argv("PTC_MR", 2)))
+    assert cfg.feat_baseline == 2 and type(cfg.feat_baseline) is int
+    assert not cfg.gc_engine and not cfg.wl_baseline and not cfg.sp_baseline and not any(getattr(cfg, p.field) for p in FT.PROBES)
+    assert FT.config_from_args(FT.build_parser().parse_args(["--domain_name", "PTC_MR"] + BASE)).feat_baseline == 0
+    assert FT.FinetuneConfig("ENZYMES", "full_finetune", "b1", 1).feat_baseline == 0
+    assert FT.FinetuneConfig("ENZYMES", "full_finetune", "b1", 1, feat_baseline=16).feat_baseline == 16
+    every = FT.config_from_args(FT.build_parser().parse_args(
+        ["--domain_name", "ENZYMES", "--gc-engine", "--feat-baseline", "3", "--sp-baseline", "8", "--wl-baseline", "3", "--knn-probe", "5"] + BASE))
+    assert (every.feat_baseline, every.sp_baseline, every.wl_baseline, every.knn_probe, every.gc_engine) == (3, 8, 3, 5, True)
+    assert "--feat-baseline" in FT.__doc__
+
+
+def test_flag_is_bounded():
+    for bad in (-1, 17):
+        with pytest.raises(ValueError, match=f"feat_baseline={bad} .*<= 16"):
+            FT.FinetuneConfig("PTC_MR", "full_finetune", "b1", 1, feat_baseline=bad)
+    for bad in (0, 17):                                                            # the API has no "off": 0 rounds is refused there
+        with pytest.raises(ValueError, match="rounds"):
+            GB.feature_baseline([], [], 2, bad)
+    with pytest.raises(ValueError, match="both splits need one"):
+        GB.feature_baseline([], [], 2, 2)
+
+
+@pytest.mark.parametrize("domain", ["Cora_NC", "Cora_LP"])
+def test_flag_is_refused_off_its_task_type_with_the_tables_message(domain):
+    with pytest.raises(ValueError, match="feat_baseline"):
+        FT.config_from_args(FT.build_parser().parse_args(_argv(domain, 2)))
+    with pytest.raises(ValueError, match=f"feat_baseline applies to the graph-classification domains \\(ENZYMES / PTC_MR\\), not to {domain}"):
+        FT.FinetuneConfig(domain_name=domain, finetune_strategy="full_finetune", pretrained_scheme="b1", seed=1, feat_baseline=2)
+    assert FT.FinetuneConfig(domain, "full_finetune", "b1", 1).feat_baseline == 0
+
+
+def test_the_row_stands_in_a_tuple_of_its_own_and_the_pinned_tables_are_unchanged():
+    assert [b.field for b in FT.FEATURE_BASELINES] == ["feat_baseline"] and isinstance(FT.FEATURE_BASELINES[0], FT.Baseline)
+    assert [b.field for b in FT.BASELINES] == ["lp_heuristics", "lp_walks", "wl_baseline", "label_propagation", "sgc_baseline"]
+    assert [b.field for b in FT.EXTRA_BASELINES] == ["sp_baseline"]
+    assert FT.ALL_BASELINES == FT.BASELINES + FT.EXTRA_BASELINES + FT.FEATURE_BASELINES
+    fields = list(FT.FinetuneConfig.__dataclass_fields__)
+    assert fields[-3:] == ["feat_baseline", "sp_baseline", "wl_baseline"]
+    assert "feat_baseline" not in {p.field for p in FT.PROBES}
+    row = FT.FEATURE_BASELINES[0]
+    assert (row.flag, row.max_value, row.task_type) == ("--feat-baseline", 16, "graph_classification")
+
+
+# ---------------------------------------------------------------------------- 4. the new symbol, the ops, standardise
+def test_symbol_is_declared_bound_and_exported():
+    lib = C.CDLL(L.LIB_PATH)
+    header = re.sub(r"/\*.*?\*/", "", open(L.HEADER_PATH).read(), flags=re.S)
+    name = "gmp_graph_feature_map"
+    assert name in set(L.declared_symbols()) and name in L._SIGS and hasattr(lib, name)
+    args = re.search(name + r"\s*\(([^;]*)\)\s*;", header).group(1)
+    assert len(args.split(",")) == 16 == len(L._SIGS[name][1])
+    assert L.lib().gmp_graph_feature_map(None, -1, None, None, 0, 0, None, None, None, 0, 1, 0, 0, None, None, None) == -1      # GMP_ERR_ARG
+    assert L.lib().gmp_graph_feature_map(None, 0, None, None, 0, 0, None, None, None, 0, 1, 0, 0, None, None, None) == 0        # no graph: nothing to do
+
+
+def test_ops_refuse_host_tensors():
+    b = R.make_batch((3, 4), 0)
+    ptr, rowptr, col = torch.from_numpy(b.ptr), torch.from_numpy(b.rowptr), torch.from_numpy(b.col)
+    with pytest.raises(L.GnnmpError, match="no CPU fallback"):
+        ops.graph_feature_map(ptr, rowptr, col, torch.zeros(7, 2), 1)
+
+    class HostBatch:
+        x = torch.zeros(7, 2)
+    with pytest.raises(L.GnnmpError, match="no CPU fallback"):
+        GB.pooled_features(HostBatch(), 1)
+
+
+def test_standardise_matches_the_float64_twin():
+    rng = np.random.default_rng(0)
+    train, other = rng.standard_normal((40, 7)).astype(np.float32) * 3 + 1, rng.standard_normal((20, 7)).astype(np.float32)
+    train[:, 2], other[:, 2] = 0.25, 5.0                                           # constant over the train rows: zeros in both
+    train[:, 5] = 1e-30 * np.arange(40)                                            # tiny but not constant: scaled like any other
+    zt, zo = GB.standardise(torch.from_numpy(train), torch.from_numpy(other))
+    wt, wo = R.standardise(train, other)
+    assert zt.dtype == zo.dtype == torch.float32 and tuple(zt.shape) == (40, 7) and tuple(zo.shape) == (20, 7)
+    for got, want in ((zt.numpy(), wt), (zo.numpy(), wo)):                         # two float64 routes (the sums' orders differ), each rounded
+        assert np.all(np.abs(got - want) <= 2.0 ** -23 * np.abs(want))             # once to fp32: one unit in the last place at the most
+    assert not zt[:, 2].any() and not zo[:, 2].any() and zt[:, 5].abs().max() > 1
+    assert np.allclose(wt.mean(axis=0), 0, atol=1e-6) and np.allclose(np.delete(wt.std(axis=0), 2), 1, atol=1e-5)
+    strided = torch.from_numpy(np.concatenate([train, train], axis=1))[:, :7]      # any layout in
+    assert torch.equal(GB.standardise(strided, torch.from_numpy(other))[0], zt)
