@@ -7,15 +7,9 @@
 // word a level walks is fetched with a shuffle.  One level = OR of the adjacency rows of the frontier into next & ~visited; the groups of
 // the wave split each frontier word's bits between them (bit b goes to group b % groups) and an xor-shuffle ORs the groups' partial rows.
 #pragma once
-#include "gnnmp_internal.h"
+#include "graph_block.h"
 
 namespace gmp {
-
-__host__ __device__ inline int pow2_ceil(int v) {
-    int p = 1;
-    while (p < v) p <<= 1;
-    return p;
-}
 
 struct Lanes {
     int w, wp, word, g0;      // row words, lanes per group, this lane's word, first lane of this lane's group

@@ -19,26 +19,25 @@
 //                       propagate, one workgroup barrier per round.  Only the pool of H(rounds) has the workgroup to itself.
 //   skipped entries     counted by the strip-0 workgroup in the first round: an integer atomicAdd on LDS, one per row that has any.
 //
-// Two instances by graph size, as in sp.hip and graph_props.hip (a batch whose max_graph_nodes is above 256 gets both launches, each block
-// leaving at once when its graph belongs to the other one).  Dynamic LDS of a block = 2 cn CS 4 bytes (H) + 2 cn 4 bytes (left, right),
-// cn = min(max_graph_nodes, the instance's limit), + 4 bytes static:
+// Two instances by graph size, planned by graph_block.h as for sp.hip and graph_props.hip (a batch whose max_graph_nodes is above 256 gets
+// both launches, each block leaving at once when its graph belongs to the other one).  Dynamic LDS of a block = 2 cn CS 4 bytes (H) +
+// 2 cn 4 bytes (left, right), cn = min(max_graph_nodes, the instance's limit), + 4 bytes static:
 //   <256 threads>   n <= 256: 3 waves (12 rows at a time) propagate.  At cn = 126 (ENZYMES' largest graph) 16.7 KiB, 9 workgroups per
 //                   CU by LDS and 8 by the 32 waves a CU takes at this register count; at the instance's worst (cn = 256) 34 KiB, 4 per CU.
 //   <1024 threads>  256 < n <= 1024: 15 waves (60 rows at a time) propagate.  Worst (cn = 1024): 128 + 8 = 136 KiB of the 160 KiB, one
 //                   workgroup per CU; at cn = 620 (PROTEINS' largest graph) 82 KiB, one per CU.
 // More than 64 KiB of dynamic LDS is reserved once per device, for the large instance only.
-#include <algorithm>
-
 #include "csr_prop.h"
+#include "graph_block.h"
 
 namespace {
 
+using gmp::LARGE_N, gmp::SMALL_N;                                   // graph_block.h: the two instances and their launch plan, the status word
+
 constexpr int CS = 16;                                              // columns per strip = lanes per row
 constexpr int POOL_GROUPS = GMP_WAVE / CS;                          // the groups of wave 0, which pools
-constexpr int SMALL_N = 256, LARGE_N = 1024;
 constexpr int MAX_DIM = 256, MAX_ROUNDS = 16;
 constexpr int64_t LIMIT = (int64_t)1 << 31;
-constexpr unsigned int SKIP_MAX = (1u << 23) - 1;                   // what bits 8 .. 30 of an int32 status word hold
 
 // dynamic LDS of one block whose graphs have at most `cn` nodes
 __host__ __device__ inline size_t lds_bytes(int cn) { return ((size_t)2 * cn * CS + (size_t)2 * cn) * sizeof(float); }
@@ -63,7 +62,7 @@ __global__ __launch_bounds__(T) void graph_feat_kernel(const int64_t* __restrict
         if (flag_large) {
             if (live)
                 for (int k = grp; k < (rounds + 1) * 3; k += GROUPS) dst[(int64_t)k * d] = 0.f;
-            if (blockIdx.y == 0 && t == 0) status[gidx] = 1;
+            if (blockIdx.y == 0 && t == 0) status[gidx] = gmp::STATUS_REFUSED;
         }
         return;
     }
@@ -113,7 +112,7 @@ __global__ __launch_bounds__(T) void graph_feat_kernel(const int64_t* __restrict
         }
         __syncthreads();
     }
-    if (counts && t == 0) status[gidx] = (int32_t)(min(skipped, SKIP_MAX) << 8);
+    if (counts && t == 0) status[gidx] = (int32_t)gmp::status_word(skipped, gmp::SKIP_MAX);
 }
 
 }  // namespace
@@ -135,17 +134,12 @@ extern "C" int gmp_graph_feature_map(const int64_t* ptr, int num_graphs, const i
         return gmp::fail(GMP_ERR_ARG, "graph_feature_map: out overlaps x");
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)num_graphs, (unsigned)gmp::cdiv(d, CS));
-    const bool two = max_graph_nodes > SMALL_N;
-    const int cn_s = (int)std::max<int64_t>(1, std::min<int64_t>(max_graph_nodes, SMALL_N));
-    static std::atomic<uint64_t> attr_large{0};                     // once per device, for the largest graph; before anything is launched
-    if (two)
-        if (int rc = gmp::reserve_lds(attr_large, (const void*)graph_feat_kernel<1024>, (int)lds_bytes(LARGE_N), "graph_feature_map")) return rc;
-    hipLaunchKernelGGL((graph_feat_kernel<256>), grid, dim3(256), lds_bytes(cn_s), st, ptr, rowptr, col, num_nodes, (int)nnz, left, right, x, ldx,
-                       d, rounds, 0, cn_s, two ? 0 : 1, out, status);
-    if (int rc = gmp::check_launch("graph_feat_kernel<256>")) return rc;
-    if (!two) return GMP_OK;
-    const int cn_l = (int)std::min<int64_t>(max_graph_nodes, LARGE_N);
-    hipLaunchKernelGGL((graph_feat_kernel<1024>), grid, dim3(1024), lds_bytes(cn_l), st, ptr, rowptr, col, num_nodes, (int)nnz, left, right, x,
-                       ldx, d, rounds, SMALL_N + 1, cn_l, 1, out, status);
-    return gmp::check_launch("graph_feat_kernel<1024>");
+    static std::atomic<uint64_t> done[2];                          // once per device and instance
+    return gmp::launch_by_size(                                     // the large instance reserves for the largest graph
+        "graph_feature_map", max_graph_nodes, done, graph_feat_kernel<SMALL_N>, 0, graph_feat_kernel<LARGE_N>, (int)lds_bytes(LARGE_N),
+        [&](auto kernel, int T, const gmp::Instance& in) {
+            hipLaunchKernelGGL(kernel, grid, dim3(T), lds_bytes(in.cap), st, ptr, rowptr, col, num_nodes, (int)nnz, left, right, x, ldx, d, rounds,
+                               in.n_min, in.cap, in.flag_large, out, status);
+            return gmp::check_launch(T == LARGE_N ? "graph_feat_kernel<1024>" : "graph_feat_kernel<256>");
+        });
 }

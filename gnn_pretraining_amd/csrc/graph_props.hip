@@ -26,18 +26,16 @@
 //
 // Two instances by row width: <4 words, 256 threads> for n <= 256 (<= 11 KB of LDS: several blocks per CU) and <16 words, 1024 threads>
 // for 256 < n <= 1024 (<= 140 KB: one block per CU).  A batch whose largest graph is above 256 nodes gets both launches, each block
-// leaving at once when its graph belongs to the other one.
-#include <algorithm>
-
+// leaving at once when its graph belongs to the other one (graph_block.h: the plan and the status word).
 #include "bit_bfs.h"
 
 namespace {
 
 typedef unsigned long long u64;
 
-constexpr int SMALL_N = 256, LARGE_N = 1024;
 constexpr int SLOTS = 16;
 
+using gmp::LARGE_N, gmp::SMALL_N;                                    // graph_block.h: the two instances and their launch plan, the status word
 using gmp::Lanes;
 using gmp::pow2_ceil;
 using gmp::wave_bfs;                                                 // bit_bfs.h: the lane layout and the per-wave bit-set BFS
@@ -60,8 +58,8 @@ __global__ __launch_bounds__(T) void graph_props_kernel(const int64_t* __restric
     const int64_t p0 = ptr[gidx], p1 = ptr[gidx + 1];
     const int64_t nn = p1 - p0;
     int64_t* out = counts + (int64_t)gidx * SLOTS;
-    if (nn < 0 || nn > cap) {                                        // block-uniform: nobody reaches a barrier
-        if (flag_large && t == 0) out[12] = 1;
+    if (nn < 0 || nn > cap) {                                        // block-uniform: nobody reaches a barrier (no num_nodes to hold ptr against)
+        if (flag_large && t == 0) out[12] = gmp::STATUS_REFUSED;
         return;
     }
     if (nn < n_min) return;                                          // the other instance's graph
@@ -221,7 +219,6 @@ __global__ __launch_bounds__(T) void graph_props_kernel(const int64_t* __restric
     __syncthreads();
 
     if (t == 0) {
-        const u64 kDropMax = (1ull << 54) - 1ull;
         out[0] = n;
         out[1] = (int64_t)(sums[0] >> 1);
         out[2] = max_deg;
@@ -234,7 +231,7 @@ __global__ __launch_bounds__(T) void graph_props_kernel(const int64_t* __restric
         out[9] = (int64_t)sums[5];
         out[10] = (int64_t)sums[1];
         out[11] = (int64_t)sums[2];
-        out[12] = (int64_t)((sums[6] > kDropMax ? kDropMax : sums[6]) << 8);
+        out[12] = (int64_t)gmp::status_word(sums[6], gmp::SKIP_MAX_WIDE);      // an int64 slot: 54 bits of dropped endpoints
         out[13] = 0;
         out[14] = 0;
         out[15] = 0;
@@ -262,16 +259,12 @@ extern "C" int gmp_graph_props(const int64_t* ptr, const int64_t* eptr, const in
     if (!ptr || !eptr || !counts || !clustering_sum || (num_edges > 0 && !edge_index)) return gmp::fail(GMP_ERR_ARG, "graph_props: null pointer");
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)num_graphs);
-    const bool two = max_graph_nodes > SMALL_N;
-    const int cap_s = (int)std::max<int64_t>(1, std::min<int64_t>(max_graph_nodes, SMALL_N));
-    hipLaunchKernelGGL((graph_props_kernel<SMALL_N / 64, 256>), grid, dim3(256), lds_bytes(cap_s), st, ptr, eptr, edge_index, num_edges, 0, cap_s,
-                       two ? 0 : 1, counts, clustering_sum);
-    if (int rc = gmp::check_launch("graph_props_kernel<4>")) return rc;
-    if (!two) return GMP_OK;
-    const int cap_l = (int)std::min<int64_t>(max_graph_nodes, LARGE_N);
-    static std::atomic<uint64_t> attr_set{0};                        // once per device, for the largest graph the instance takes
-    if (int rc = gmp::reserve_lds(attr_set, (const void*)graph_props_kernel<LARGE_N / 64, 1024>, (int)lds_bytes(LARGE_N), "graph_props")) return rc;
-    hipLaunchKernelGGL((graph_props_kernel<LARGE_N / 64, 1024>), grid, dim3(1024), lds_bytes(cap_l), st, ptr, eptr, edge_index, num_edges,
-                       SMALL_N + 1, cap_l, 1, counts, clustering_sum);
-    return gmp::check_launch("graph_props_kernel<16>");
+    static std::atomic<uint64_t> done[2];                          // once per device and instance
+    return gmp::launch_by_size(                                      // the large instance reserves for the largest graph it takes
+        "graph_props", max_graph_nodes, done, graph_props_kernel<SMALL_N / 64, SMALL_N>, 0, graph_props_kernel<LARGE_N / 64, LARGE_N>, (int)lds_bytes(LARGE_N),
+        [&](auto kernel, int T, const gmp::Instance& in) {
+            hipLaunchKernelGGL(kernel, grid, dim3(T), lds_bytes(in.cap), st, ptr, eptr, edge_index, num_edges, in.n_min, in.cap, in.flag_large, counts,
+                               clustering_sum);
+            return gmp::check_launch(T == LARGE_N ? "graph_props_kernel<16>" : "graph_props_kernel<4>");
+        });
 }

@@ -22,47 +22,32 @@
 //                       row stride: unsorted input gives a wrong sum, never a read outside.
 // Integer arithmetic only: no floating-point operation in this file, so every output is pinned bit for bit by tests/sp_ref.py.
 //
-// Two instances of sp_features_kernel by row width, as in graph_props.hip (a batch whose max_graph_nodes is above 256 gets both launches,
-// each block leaving at once when its graph belongs to the other one).  Dynamic LDS of a block = the bit matrix (cn ceil(cn / 64) 8 bytes,
-// cn = min(max_graph_nodes, the instance's limit)) + 12 bytes per table slot + 4 cn (labels); 1 KiB of static LDS holds the histogram.
+// Two instances of sp_features_kernel by row width, planned by graph_block.h as for the other per-graph kernels (a batch whose
+// max_graph_nodes is above 256 gets both launches, each block leaving at once when its graph belongs to the other one).  Dynamic LDS of a
+// block = the bit matrix (cn ceil(cn / 64) 8 bytes, cn = min(max_graph_nodes, the instance's limit)) + 12 bytes per table slot + 4 cn
+// (labels); 1 KiB of static LDS holds the histogram.
 //   <256 threads>   n <= 256, cap <= 4096.  At cn = 64, cap = 1024: 0.5 + 24 + 0.25 KiB, 6 workgroups per CU; at the instance's worst
 //                   (cn = 256, cap = 4096): 8 + 96 + 1 = 105 KiB, one per CU.
 //   <1024 threads>  256 < n <= 1024, cap <= 1024.  Worst: 128 + 24 + 4 = 156 KiB of the 160 KiB, one workgroup per CU.
 // More than 64 KiB of dynamic LDS is reserved once per device and instance.
-#include <algorithm>
-
 #include "bit_bfs.h"
 
 namespace {
 
 typedef unsigned long long u64;
-using gmp::Lanes;
-using gmp::pow2_ceil;
+using gmp::GRAM_THREADS, gmp::GRAM_WAVES, gmp::K1, gmp::LARGE_N, gmp::SMALL_N, gmp::mix, gmp::pow2_ceil;           // graph_block.h
+using gmp::Lanes;                                                   // bit_bfs.h
 
-constexpr int SMALL_N = 256, LARGE_N = 1024;
 constexpr int SMALL_CAP = 4096, LARGE_CAP = 1024;                   // the most distinct keys per graph, by instance
 constexpr int MAX_DIST = 1023, MAX_DIM = 256;
 constexpr int64_t MAX_LABEL = (int64_t)1 << 24;
-constexpr u64 K1 = 0x9E3779B97F4A7C15ull;
 constexpr u64 EMPTY = ~0ull;                                        // a free table slot: above every key (keys are below 2^59)
-constexpr int GRAM_THREADS = 256, GRAM_WAVES = GRAM_THREADS / GMP_WAVE;
-constexpr int64_t SKIP_MAX = (1ll << 23) - 1;                       // what bits 8 .. 30 of an int32 status word hold
 
 __host__ __device__ inline int table_slots(int cap) { return pow2_ceil(2 * cap); }
 
 // dynamic LDS of one block whose graphs have at most `cn` nodes and `cap` distinct keys
 __host__ __device__ inline size_t lds_bytes(int cn, int cap) {
     return (size_t)cn * ((cn + 63) / 64) * 8 + (size_t)table_slots(cap) * 12 + (size_t)cn * 4;
-}
-
-// the splitmix64 finaliser
-__device__ __forceinline__ u64 mix(u64 z) {
-    z ^= z >> 30;
-    z *= 0xBF58476D1CE4E5B9ull;
-    z ^= z >> 27;
-    z *= 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return z;
 }
 
 struct Table {
@@ -111,7 +96,7 @@ __global__ __launch_bounds__(T) void sp_features_kernel(const int64_t* __restric
     const int64_t nn = p1 - p0;
     if (nn < 0 || nn > cn || p0 < 0 || p1 > num_nodes) {            // block-uniform: nobody reaches a barrier
         if (flag_large && t == 0) {
-            status[gidx] = 1;
+            status[gidx] = gmp::STATUS_REFUSED;
             nuniq[gidx] = 0;
         }
         return;
@@ -152,21 +137,14 @@ __global__ __launch_bounds__(T) void sp_features_kernel(const int64_t* __restric
         unsigned int skip = 0u;
         for (int v = t; v < n; v += T) {
             const int64_t gv = p0 + v;
-            const int64_t rb = min(max((int64_t)rowptr[gv], (int64_t)0), nnz), re = min(max((int64_t)rowptr[gv + 1], rb), nnz);
             int64_t deg = 0;
-            for (int64_t i = rb; i < re; ++i) {
-                const int64_t gu = (int64_t)col[i] - p0;
-                if (gu < 0 || gu >= nn) {
-                    ++skip;
-                    continue;
-                }
+            skip += gmp::walk_row(rowptr, col, nnz, p0, nn, v, [&](int u) {
                 ++deg;
-                const int u = (int)gu;
                 if (u != v) {
                     atomicOr(&A[v * w + (u >> 6)], 1ull << (u & 63));
                     atomicOr(&A[u * w + (v >> 6)], 1ull << (v & 63));
                 }
-            }
+            });
             const int64_t l = labels ? labels[gv] : deg;
             if (l < 0 || l >= MAX_LABEL) bad_label = 1;
             lab[v] = (int)l;
@@ -210,7 +188,7 @@ __global__ __launch_bounds__(T) void sp_features_kernel(const int64_t* __restric
 
     if (bad_label || overflow) {                                    // block-uniform
         if (t == 0) {
-            status[gidx] = (int32_t)((min((int64_t)skipped, SKIP_MAX) << 8) | (overflow ? 2 : 0) | (bad_label ? 4 : 0));
+            status[gidx] = (int32_t)gmp::status_word(skipped, gmp::SKIP_MAX, (overflow ? gmp::STATUS_OVERFLOW : 0u) | (bad_label ? gmp::STATUS_BAD_LABEL : 0u));
             nuniq[gidx] = 0;
         }
         return;
@@ -242,17 +220,17 @@ __global__ __launch_bounds__(T) void sp_features_kernel(const int64_t* __restric
         const unsigned int c = tb.count[k];
         keys[(int64_t)gidx * cap + k] = (int64_t)key;
         counts[(int64_t)gidx * cap + k] = (int32_t)c;
-        const unsigned int b = (unsigned int)(((u64)(unsigned int)(mix(key + K1) >> 32) * (u64)(unsigned int)dim) >> 32);
-        atomicAdd(&bins[b], c);                                     // b < dim: (x * dim) >> 32 with x < 2^32
+        atomicAdd(&bins[gmp::hashed_bin(mix(key + K1), dim)], c);
     }
     __syncthreads();
     for (int b = t; b < dim; b += T) hist[(int64_t)gidx * dim + b] = (int32_t)bins[b];
     if (t == 0) {
-        status[gidx] = (int32_t)(min((int64_t)skipped, SKIP_MAX) << 8);
+        status[gidx] = (int32_t)gmp::status_word(skipped, gmp::SKIP_MAX);
         nuniq[gidx] = nk;
     }
 }
 
+// (the frame -- e -> (i, j), the shuffle sum, lane 0's write -- is written out: behind a shared helper hipcc reorders this kernel, graph_block.h)
 __global__ __launch_bounds__(GRAM_THREADS) void sp_gram_kernel(const int64_t* __restrict__ ka, const int32_t* __restrict__ ca,
                                                                const int32_t* __restrict__ na, int64_t Ga, int cap_a,
                                                                const int64_t* __restrict__ kb, const int32_t* __restrict__ cb,
@@ -295,7 +273,7 @@ extern "C" size_t gmp_sp_workspace_bytes(int num_graphs, int64_t max_graph_nodes
     return 0;                                                       // bit matrix, labels, table and histogram live in LDS
 }
 
-extern "C" int gmp_sp_max_unique(int64_t max_graph_nodes) { return max_graph_nodes > SMALL_N ? LARGE_CAP : SMALL_CAP; }
+extern "C" int gmp_sp_max_unique(int64_t max_graph_nodes) { return gmp::two_instances(max_graph_nodes) ? LARGE_CAP : SMALL_CAP; }
 
 extern "C" int gmp_sp_features(const int64_t* ptr, int num_graphs, const int32_t* rowptr, const int32_t* col, int64_t num_nodes, int64_t nnz,
                                const int64_t* labels, int max_dist, int dim, int64_t max_graph_nodes, int cap, int64_t* keys,
@@ -314,20 +292,14 @@ extern "C" int gmp_sp_features(const int64_t* ptr, int num_graphs, const int32_t
         return gmp::fail(GMP_ERR_ARG, "sp_features: null pointer");
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)num_graphs);
-    const bool two = max_graph_nodes > SMALL_N;
-    const int cn_s = (int)std::max<int64_t>(1, std::min<int64_t>(max_graph_nodes, SMALL_N));
-    static std::atomic<uint64_t> attr_small{0};                     // once per device, for the largest graph and the largest cap
-    if (int rc = gmp::reserve_lds(attr_small, (const void*)sp_features_kernel<256>, (int)lds_bytes(SMALL_N, SMALL_CAP), "sp_features")) return rc;
-    hipLaunchKernelGGL((sp_features_kernel<256>), grid, dim3(256), lds_bytes(cn_s, cap), st, ptr, rowptr, col, num_nodes, nnz, labels, max_dist,
-                       dim, 0, cn_s, two ? 0 : 1, cap, keys, counts, nuniq, hist, status);
-    if (int rc = gmp::check_launch("sp_features_kernel<256>")) return rc;
-    if (!two) return GMP_OK;
-    const int cn_l = (int)std::min<int64_t>(max_graph_nodes, LARGE_N);
-    static std::atomic<uint64_t> attr_large{0};
-    if (int rc = gmp::reserve_lds(attr_large, (const void*)sp_features_kernel<1024>, (int)lds_bytes(LARGE_N, LARGE_CAP), "sp_features")) return rc;
-    hipLaunchKernelGGL((sp_features_kernel<1024>), grid, dim3(1024), lds_bytes(cn_l, cap), st, ptr, rowptr, col, num_nodes, nnz, labels, max_dist,
-                       dim, SMALL_N + 1, cn_l, 1, cap, keys, counts, nuniq, hist, status);
-    return gmp::check_launch("sp_features_kernel<1024>");
+    static std::atomic<uint64_t> done[2];                          // once per device and instance
+    return gmp::launch_by_size(                                     // both reserve, for the largest graph and cap: the small one's worst is 105 KiB
+        "sp_features", max_graph_nodes, done, sp_features_kernel<SMALL_N>, (int)lds_bytes(SMALL_N, SMALL_CAP), sp_features_kernel<LARGE_N>,
+        (int)lds_bytes(LARGE_N, LARGE_CAP), [&](auto kernel, int T, const gmp::Instance& in) {
+            hipLaunchKernelGGL(kernel, grid, dim3(T), lds_bytes(in.cap, cap), st, ptr, rowptr, col, num_nodes, nnz, labels, max_dist, dim, in.n_min,
+                               in.cap, in.flag_large, cap, keys, counts, nuniq, hist, status);
+            return gmp::check_launch(T == LARGE_N ? "sp_features_kernel<1024>" : "sp_features_kernel<256>");
+        });
 }
 
 extern "C" int gmp_sp_gram(const int64_t* keys_a, const int32_t* counts_a, const int32_t* nuniq_a, int64_t num_graphs_a, int cap_a,
@@ -338,10 +310,8 @@ extern "C" int gmp_sp_gram(const int64_t* keys_a, const int32_t* counts_a, const
                          (long long)num_graphs_b, cap_a, cap_b, SMALL_CAP);
     if (num_graphs_a == 0 || num_graphs_b == 0) return GMP_OK;
     if (!keys_a || !counts_a || !nuniq_a || !keys_b || !counts_b || !nuniq_b || !K) return gmp::fail(GMP_ERR_ARG, "sp_gram: null pointer");
-    if (num_graphs_a >= ((int64_t)1 << 31) || num_graphs_b >= ((int64_t)1 << 31) ||
-        (num_graphs_a * num_graphs_b + GRAM_WAVES - 1) / GRAM_WAVES >= ((int64_t)1 << 31))
-        return gmp::fail(GMP_ERR_ARG, "sp_gram: %lld x %lld entries exceed one grid", (long long)num_graphs_a, (long long)num_graphs_b);
-    const int64_t blocks = (num_graphs_a * num_graphs_b + GRAM_WAVES - 1) / GRAM_WAVES;
+    int64_t blocks = 0;
+    if (int rc = gmp::gram_blocks("sp_gram", num_graphs_a, num_graphs_b, &blocks)) return rc;
     hipLaunchKernelGGL(sp_gram_kernel, dim3((unsigned)blocks), dim3(GRAM_THREADS), 0, (hipStream_t)stream, keys_a, counts_a, nuniq_a, num_graphs_a,
                        cap_a, keys_b, counts_b, nuniq_b, num_graphs_b, cap_b, K);
     return gmp::check_launch("sp_gram_kernel");

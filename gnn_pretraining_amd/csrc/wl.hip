@@ -24,47 +24,27 @@
 //                     arrays: unsorted input gives a wrong count, never a read outside.
 // Integer arithmetic only: no floating-point operation in this file, so every output is pinned bit for bit by tests/wl_ref.py.
 //
-// Two instances of wl_refine_kernel by graph size, as in graph_props.hip (a batch whose max_graph_nodes is above 256 gets both launches,
-// each block leaving at once when its graph belongs to the other one).  LDS of a block = 16 cap (colours) + 8 pow2((h + 1) cap) (list) +
-// 4 D (histogram), cap = min(max_graph_nodes, the instance's limit):
+// Two instances of wl_refine_kernel by graph size, planned by graph_block.h as for the other per-graph kernels (a batch whose
+// max_graph_nodes is above 256 gets both launches, each block leaving at once when its graph belongs to the other one).  LDS of a block =
+// 16 cap (colours) + 8 pow2((h + 1) cap) (list) + 4 D (histogram), cap = min(max_graph_nodes, the instance's limit):
 //   <256 threads>   n <= 256.  At cap = 39, h = 3, D = 256 (the TU datasets): 624 + 2,048 + 1,024 = 3.6 KiB -- 8 workgroups per CU, the
 //                   limit of 32 waves per CU, not LDS.  At the instance's worst (cap = 256, h = 7): 4 + 16 + 1 = 21 KiB, 7 per CU.
 //   <1024 threads>  256 < n <= 1024.  Worst (cap = 1024, h = 7): 16 + 64 + 1 = 81 KiB, one workgroup per CU (160 KiB); at h = 3, 49 KiB:
 //                   two by the wave limit.  More than 64 KiB of dynamic LDS is reserved once per device.
-#include <algorithm>
-
-#include "gnnmp_internal.h"
+#include "graph_block.h"
 
 namespace {
 
 typedef unsigned long long u64;
+using gmp::GRAM_THREADS, gmp::GRAM_WAVES, gmp::K1, gmp::LARGE_N, gmp::SMALL_N, gmp::mix, gmp::pow2_ceil;           // graph_block.h
 
-constexpr int SMALL_N = 256, LARGE_N = 1024;
 constexpr int MAX_ITERS = 7, MAX_DIM = 256;
-constexpr u64 K1 = 0x9E3779B97F4A7C15ull, K2 = 0xD1B54A32D192ED03ull;
-constexpr int GRAM_THREADS = 256, GRAM_WAVES = GRAM_THREADS / GMP_WAVE;
+constexpr u64 K2 = 0xD1B54A32D192ED03ull;
 constexpr int GRAM_STAGE = 512;                                     // words of a segment that a wave stages in LDS: 2 x 4 KiB per wave, 32 KiB per block
-constexpr int64_t SKIP_MAX = (1ll << 23) - 1;                       // what bits 8 .. 30 of an int32 status word hold
-
-__host__ __device__ inline int64_t pow2_ceil(int64_t v) {
-    int64_t p = 1;
-    while (p < v) p <<= 1;
-    return p;
-}
 
 // LDS of one block whose graphs have at most `cap` nodes
 __host__ __device__ inline size_t lds_bytes(int cap, int hp1, int dim) {
     return (size_t)cap * 16 + (size_t)pow2_ceil((int64_t)hp1 * cap) * 8 + (size_t)dim * 4;
-}
-
-// the splitmix64 finaliser
-__device__ __forceinline__ u64 mix(u64 z) {
-    z ^= z >> 30;
-    z *= 0xBF58476D1CE4E5B9ull;
-    z ^= z >> 27;
-    z *= 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return z;
 }
 
 template <int T>
@@ -80,7 +60,7 @@ __global__ __launch_bounds__(T) void wl_refine_kernel(const int64_t* __restrict_
     const int64_t p0 = ptr[gidx], p1 = ptr[gidx + 1];
     const int64_t nn = p1 - p0;
     if (nn < 0 || nn > cap || p0 < 0 || p1 > num_nodes) {           // block-uniform: nobody reaches a barrier
-        if (flag_large && t == 0) status[gidx] = 1;
+        if (flag_large && t == 0) status[gidx] = gmp::STATUS_REFUSED;
         return;
     }
     if (nn < n_min) return;                                         // the other instance's graph
@@ -101,12 +81,8 @@ __global__ __launch_bounds__(T) void wl_refine_kernel(const int64_t* __restrict_
         unsigned int skip = 0u;
         for (int v = t; v < n; v += T) {
             const int64_t gv = p0 + v;
-            const int64_t rb = min(max((int64_t)rowptr[gv], (int64_t)0), nnz), re = min(max((int64_t)rowptr[gv + 1], rb), nnz);
             int64_t deg = 0;
-            for (int64_t i = rb; i < re; ++i) {
-                const int64_t u = (int64_t)col[i] - p0;
-                if (u >= 0 && u < nn) ++deg; else ++skip;
-            }
+            skip += gmp::walk_row(rowptr, col, nnz, p0, nn, v, [&](int) { ++deg; });
             const u64 c = mix((u64)(labels ? labels[gv] : deg) + K1);
             cur[v] = c;
             list[v] = c;
@@ -120,12 +96,8 @@ __global__ __launch_bounds__(T) void wl_refine_kernel(const int64_t* __restrict_
     for (int r = 1; r <= h; ++r) {
         for (int v = t; v < n; v += T) {
             const int64_t gv = p0 + v;
-            const int64_t rb = min(max((int64_t)rowptr[gv], (int64_t)0), nnz), re = min(max((int64_t)rowptr[gv + 1], rb), nnz);
             u64 sum = 0ull;
-            for (int64_t i = rb; i < re; ++i) {
-                const int64_t u = (int64_t)col[i] - p0;
-                if (u >= 0 && u < nn) sum += mix(cur[u]);
-            }
+            (void)gmp::walk_row(rowptr, col, nnz, p0, nn, v, [&](int u) { sum += mix(cur[u]); });      // (round 0 counted the strays)
             const u64 c = mix(cur[v] * K1 + sum + (u64)r * K2);
             nxt[v] = c;
             list[r * n + v] = c;
@@ -138,10 +110,7 @@ __global__ __launch_bounds__(T) void wl_refine_kernel(const int64_t* __restrict_
     }
 
     // ---- histogram of all (h + 1) n colours
-    for (int k = t; k < len; k += T) {
-        const unsigned int b = (unsigned int)(((u64)(unsigned int)(list[k] >> 32) * (u64)(unsigned int)dim) >> 32);
-        atomicAdd(&bins[b], 1u);                                    // b < dim: (x * dim) >> 32 with x < 2^32
-    }
+    for (int k = t; k < len; k += T) atomicAdd(&bins[gmp::hashed_bin(list[k], dim)], 1u);
 
     // ---- sort list[0, len) ascending (unsigned).  Every step pairs i < j and leaves the smaller word at i; j >= len is "+infinity".
     const int P = (int)pow2_ceil(len > 0 ? len : 1);                // block-uniform trip counts: every thread reaches every barrier
@@ -178,7 +147,7 @@ __global__ __launch_bounds__(T) void wl_refine_kernel(const int64_t* __restrict_
     int64_t* out = sorted + (int64_t)hp1 * p0;
     for (int k = t; k < len; k += T) out[k] = (int64_t)list[k];
     for (int b = t; b < dim; b += T) hist[(int64_t)gidx * dim + b] = (int32_t)bins[b];
-    if (t == 0) status[gidx] = (int32_t)(min((int64_t)skipped, SKIP_MAX) << 8);
+    if (t == 0) status[gidx] = (int32_t)gmp::status_word(skipped, gmp::SKIP_MAX);
 }
 
 // the first i in [lo, hi) with s[i] >= key / > key (unsigned; hi if none)
@@ -225,6 +194,7 @@ __device__ __forceinline__ Seg seg_of(const int64_t* __restrict__ ptr, int64_t g
     return Seg{b, max(b, e)};
 }
 
+// (the frame -- e -> (i, j), the shuffle sum, lane 0's write -- is written out: behind a shared helper hipcc reorders this kernel, graph_block.h)
 __global__ __launch_bounds__(GRAM_THREADS) void wl_gram_kernel(const int64_t* __restrict__ sa, const int64_t* __restrict__ ptr_a, int64_t Ga,
                                                                int64_t len_a, const int64_t* __restrict__ sb,
                                                                const int64_t* __restrict__ ptr_b, int64_t Gb, int64_t len_b, int64_t hp1,
@@ -285,19 +255,14 @@ extern "C" int gmp_wl_refine(const int64_t* ptr, int num_graphs, const int32_t* 
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)num_graphs);
     const int hp1 = iters + 1;
-    const bool two = max_graph_nodes > SMALL_N;
-    const int cap_s = (int)std::max<int64_t>(1, std::min<int64_t>(max_graph_nodes, SMALL_N));
-    hipLaunchKernelGGL((wl_refine_kernel<256>), grid, dim3(256), lds_bytes(cap_s, hp1, dim), st, ptr, rowptr, col, num_nodes, nnz, labels, iters,
-                       dim, 0, cap_s, two ? 0 : 1, colors, sorted, hist, status);
-    if (int rc = gmp::check_launch("wl_refine_kernel<256>")) return rc;
-    if (!two) return GMP_OK;
-    const int cap_l = (int)std::min<int64_t>(max_graph_nodes, LARGE_N);
-    static std::atomic<uint64_t> attr_set{0};                       // once per device, for the largest graph and the most rounds
-    if (int rc = gmp::reserve_lds(attr_set, (const void*)wl_refine_kernel<1024>, (int)lds_bytes(LARGE_N, MAX_ITERS + 1, MAX_DIM), "wl_refine"))
-        return rc;
-    hipLaunchKernelGGL((wl_refine_kernel<1024>), grid, dim3(1024), lds_bytes(cap_l, hp1, dim), st, ptr, rowptr, col, num_nodes, nnz, labels, iters,
-                       dim, SMALL_N + 1, cap_l, 1, colors, sorted, hist, status);
-    return gmp::check_launch("wl_refine_kernel<1024>");
+    static std::atomic<uint64_t> done[2];                          // once per device and instance
+    return gmp::launch_by_size(                                     // the large instance reserves for the largest graph and the most rounds
+        "wl_refine", max_graph_nodes, done, wl_refine_kernel<SMALL_N>, 0, wl_refine_kernel<LARGE_N>, (int)lds_bytes(LARGE_N, MAX_ITERS + 1, MAX_DIM),
+        [&](auto kernel, int T, const gmp::Instance& in) {
+            hipLaunchKernelGGL(kernel, grid, dim3(T), lds_bytes(in.cap, hp1, dim), st, ptr, rowptr, col, num_nodes, nnz, labels, iters, dim, in.n_min,
+                               in.cap, in.flag_large, colors, sorted, hist, status);
+            return gmp::check_launch(T == LARGE_N ? "wl_refine_kernel<1024>" : "wl_refine_kernel<256>");
+        });
 }
 
 extern "C" int gmp_wl_gram(const int64_t* sorted_a, const int64_t* ptr_a, int64_t num_graphs_a, int64_t len_a, const int64_t* sorted_b,
@@ -307,10 +272,8 @@ extern "C" int gmp_wl_gram(const int64_t* sorted_a, const int64_t* ptr_a, int64_
                          (long long)num_graphs_a, (long long)num_graphs_b, (long long)len_a, (long long)len_b, iters, MAX_ITERS);
     if (num_graphs_a == 0 || num_graphs_b == 0) return GMP_OK;
     if (!ptr_a || !ptr_b || !K || (len_a > 0 && !sorted_a) || (len_b > 0 && !sorted_b)) return gmp::fail(GMP_ERR_ARG, "wl_gram: null pointer");
-    if (num_graphs_a >= ((int64_t)1 << 31) || num_graphs_b >= ((int64_t)1 << 31) ||
-        (num_graphs_a * num_graphs_b + GRAM_WAVES - 1) / GRAM_WAVES >= ((int64_t)1 << 31))
-        return gmp::fail(GMP_ERR_ARG, "wl_gram: %lld x %lld entries exceed one grid", (long long)num_graphs_a, (long long)num_graphs_b);
-    const int64_t blocks = (num_graphs_a * num_graphs_b + GRAM_WAVES - 1) / GRAM_WAVES;
+    int64_t blocks = 0;
+    if (int rc = gmp::gram_blocks("wl_gram", num_graphs_a, num_graphs_b, &blocks)) return rc;
     hipLaunchKernelGGL(wl_gram_kernel, dim3((unsigned)blocks), dim3(GRAM_THREADS), 0, (hipStream_t)stream, sorted_a, ptr_a, num_graphs_a, len_a,
                        sorted_b, ptr_b, num_graphs_b, len_b, (int64_t)(iters + 1), K);
     return gmp::check_launch("wl_gram_kernel");

@@ -201,7 +201,7 @@ class FinetuneConfig:
                              "pass lp_engine (--lp-engine)")
         if self.lp_ranking and not self.lp_engine:
             raise ValueError("lp_ranking ranks with the link-prediction engine (gmp_lp_rank): pass lp_engine (--lp-engine)")
-        for b in ALL_BASELINES:
+        for b in BASELINES:
             value = getattr(self, b.field)
             if b.max_value is not None and not 0 <= value <= b.max_value:
                 raise ValueError(f"{b.field}={value} ({b.bound.format(b.max_value)})")
@@ -457,30 +457,15 @@ def rank_test_edges_baselines(family, extra: tuple, train_loader, val_loader, te
     return out
 
 
-def wl_baseline_keys(train_loader, test_loader, device, cfg: FinetuneConfig) -> Dict[str, float]:
-    """cfg.wl_baseline: what test/accuracy and the probes have to beat on a graph-classification domain -- the Weisfeiler-Lehman subtree
-    features of the raw graphs with cfg.wl_baseline rounds, fitted on the train split and scored on the test split by a k-NN vote on the
-    exact kernel and a softmax regression on the hashed histogram (graph_baselines.wl_baseline).  Reads the datasets and nothing else: no
-    model, no generator, no dropout counter, no BatchNorm state."""
-    scores = GB.wl_baseline(train_loader.dataset, test_loader.dataset, NUM_CLASSES[cfg.domain_name], cfg.wl_baseline, device=device)
-    return {f"test/wl_{k}": v for k, v in scores.items()}
-
-
-def sp_baseline_keys(train_loader, test_loader, device, cfg: FinetuneConfig) -> Dict[str, float]:
-    """cfg.sp_baseline: the same protocol on the shortest-path kernel -- the (label, label, hop distance) counts of the raw graphs'
-    node pairs with distances up to cfg.sp_baseline (graph_baselines.sp_baseline).  Where the WL features are local, these are global.
-    Reads the datasets and nothing else, as wl_baseline_keys."""
-    scores = GB.sp_baseline(train_loader.dataset, test_loader.dataset, NUM_CLASSES[cfg.domain_name], cfg.sp_baseline, device=device)
-    return {f"test/sp_{k}": v for k, v in scores.items()}
-
-
-def feat_baseline_keys(train_loader, test_loader, device, cfg: FinetuneConfig) -> Dict[str, float]:
-    """cfg.feat_baseline: the baselines that read the node FEATURES, which the two kernels above never do on continuous ones -- the pooled
-    raw features (structure-blind, Errica et al. 2020) and the pooled S^t X, t = 0 .. cfg.feat_baseline (SGC, concatenated over the
-    scales), each under the k-NN vote and the softmax regression (graph_baselines.feature_baseline).  Reads the datasets and nothing
-    else, as wl_baseline_keys."""
-    scores = GB.feature_baseline(train_loader.dataset, test_loader.dataset, NUM_CLASSES[cfg.domain_name], cfg.feat_baseline, device=device)
-    return {f"test/{k}": v for k, v in scores.items()}
+def graph_baseline_keys(baseline: Callable, prefix: str, value: int, train_loader, test_loader, device, cfg: FinetuneConfig) -> Dict[str, float]:
+    """What test/accuracy and the probes have to beat on a graph-classification domain, fitted on the train split and scored on the test
+    split by a k-NN vote and a softmax regression, as test/{prefix}{key}.  cfg.wl_baseline (graph_baselines.wl_baseline): the
+    Weisfeiler-Lehman subtree features with that many rounds.  cfg.sp_baseline (sp_baseline): the shortest-path kernel's (label, label,
+    hop distance) counts up to that distance -- global where WL is local.  cfg.feat_baseline (feature_baseline): the two that read the
+    node FEATURES -- the pooled raw features (structure-blind, Errica et al. 2020) and the pooled S^t X, t = 0 .. cfg.feat_baseline
+    (SGC over the scales).  Reads the datasets and nothing else: no model, no generator, no dropout counter, no BatchNorm state."""
+    scores = baseline(train_loader.dataset, test_loader.dataset, NUM_CLASSES[cfg.domain_name], value, device=device)
+    return {f"test/{prefix}{k}": v for k, v in scores.items()}
 
 
 def node_baseline_keys(baselines: Callable, rounds: int, train_loader, test_loader, device, cfg: FinetuneConfig) -> Dict[str, float]:
@@ -519,7 +504,7 @@ BASELINES = (
              "rooted PageRank (alpha 0.15) and hop-distance baselines with R rounds (1..64), ranked like --lp-heuristics on the "
              "training graph (needs neither --lp-engine nor --lp-ranking); 0 = off"),
     Baseline("wl_baseline", "--wl-baseline", "H", ops.WL_MAX_ITERS, "the number of refinement rounds, 1 <= rounds <= {}; 0 switches the baseline off",
-             *GC, lambda tr, va, te, dev, cfg: wl_baseline_keys(tr, te, dev, cfg),
+             *GC, lambda tr, va, te, dev, cfg: graph_baseline_keys(GB.wl_baseline, "wl_", cfg.wl_baseline, tr, te, dev, cfg),
              "ENZYMES / PTC_MR: the test record also carries test/wl_knn_accuracy and test/wl_logreg_accuracy, the Weisfeiler-Lehman "
              "subtree baseline with H refinement rounds (1..7) on the raw graphs, fitted on the train split and scored on the test "
              "split (needs neither --gc-engine nor a probe flag); 0 = off"),
@@ -534,27 +519,20 @@ BASELINES = (
              "on the raw features and SGC (the same regression on S^K X, K rounds 1..64 of the degree-scaled propagation with "
              "self-loops), fitted on the train split and scored on the test split (needs neither an engine nor a probe flag; "
              "combines with --label-propagation and --sparse-features); 0 = off"),
-)
-# Rows like those of BASELINES, walked by the same four loops after them.  They stand apart only because tests/test_link_rankers_host.py
-# pins BASELINES to its five rows; merging the two tuples is a follow-up that edits that test.
-EXTRA_BASELINES = (
     Baseline("sp_baseline", "--sp-baseline", "D", ops.SP_MAX_DIST, "the largest hop distance counted, 1 <= distance <= {}; 0 switches the baseline off",
-             *GC, lambda tr, va, te, dev, cfg: sp_baseline_keys(tr, te, dev, cfg),
+             *GC, lambda tr, va, te, dev, cfg: graph_baseline_keys(GB.sp_baseline, "sp_", cfg.sp_baseline, tr, te, dev, cfg),
              "ENZYMES / PTC_MR: the test record also carries test/sp_knn_accuracy and test/sp_logreg_accuracy, the shortest-path "
              "kernel baseline over node pairs at hop distance 1..D (D up to 1023) on the raw graphs, fitted on the train split and "
              "scored on the test split (needs neither --gc-engine nor a probe flag; combines with --wl-baseline); 0 = off"),
-)
-# A further tuple for the same reason: tests/test_sp_host.py pins EXTRA_BASELINES to its one row.
-FEATURE_BASELINES = (
-    Baseline("feat_baseline", "--feat-baseline", "K", ops.GRAPH_FEAT_MAX_ROUNDS, ROUNDS, *GC, lambda tr, va, te, dev, cfg: feat_baseline_keys(tr, te, dev, cfg),
+    Baseline("feat_baseline", "--feat-baseline", "K", ops.GRAPH_FEAT_MAX_ROUNDS, ROUNDS, *GC,
+             lambda tr, va, te, dev, cfg: graph_baseline_keys(GB.feature_baseline, "", cfg.feat_baseline, tr, te, dev, cfg),
              "ENZYMES / PTC_MR: the test record also carries test/rawpool_knn_accuracy, test/rawpool_logreg_accuracy, "
              "test/sgcpool_knn_accuracy and test/sgcpool_logreg_accuracy: the sum, mean and max pools of the raw node features (no "
              "graph: the structure-blind baseline) and of S^t X for t = 0..K (K rounds 1..16 of the degree-scaled propagation with "
              "self-loops, concatenated), standardised by the train split, each under a 20-NN vote and a softmax regression fitted on "
              "the train split and scored on the test split (needs neither --gc-engine nor a probe flag; combines with --wl-baseline "
              "and --sp-baseline); 0 = off"),
-)
-ALL_BASELINES = BASELINES + EXTRA_BASELINES + FEATURE_BASELINES             # what the four loops walk (config check, test record, parser, config_from_args)
+)           # one table, walked by four loops: the config check, the test record, the parser, config_from_args
 
 
 def probe_embeddings(engine, datasets, device, cfg: FinetuneConfig):
@@ -726,7 +704,7 @@ def finetune(cfg: FinetuneConfig, epochs: Optional[int] = None, device: Optional
     test.update(run_probes(probe_engine, train_loader, test_loader, dev, cfg, "test", known))
     if cfg.lp_ranking:
         test.update(rank_test_edges(lp_engine, train_loader, val_loader, test_loader, dev))
-    for b in ALL_BASELINES:
+    for b in BASELINES:
         if getattr(cfg, b.field):
             test.update(b.keys(train_loader, val_loader, test_loader, dev, cfg))
     logger.log(test, global_step[0])
@@ -739,7 +717,7 @@ def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser()
 
     def add_baselines(task_types: Tuple[str, ...]) -> None:              # (--help lists the flags in the order they were added)
-        for b in ALL_BASELINES:
+        for b in BASELINES:
             if b.task_type in task_types:
                 kind = {"action": "store_true"} if b.max_value is None else {"type": int, "default": 0, "metavar": b.metavar}
                 p.add_argument(b.flag, help=b.help, **kind)
@@ -782,7 +760,7 @@ def config_from_args(a: argparse.Namespace) -> FinetuneConfig:
                           engine_eval=getattr(a, "engine_eval", False), lp_ranking=getattr(a, "lp_ranking", False),
                           device_metrics=getattr(a, "device_metrics", False), miner_impl=getattr(a, "miner", "matrix"),
                           repr_stats=getattr(a, "repr_stats", False), link_probe=getattr(a, "link_probe", False),
-                          **{b.field: getattr(a, b.field, False if b.max_value is None else 0) for b in ALL_BASELINES},
+                          **{b.field: getattr(a, b.field, False if b.max_value is None else 0) for b in BASELINES},
                           **{p.field: getattr(a, p.field, 0) for p in PROBES})
 
 

@@ -60,28 +60,46 @@ def initial_labels(x: Tensor) -> Optional[Tensor]:
     return nz.to(torch.int64).argmax(dim=1)
 
 
+def _gpu_batch(who: str, batch) -> None:
+    if not batch.x.is_cuda:
+        raise GnnmpError(f"{who}: expected a batch on the GPU (the HIP path has no CPU fallback), got {batch.x.device}")
+
+
+def _kernel_inputs(who: str, batch, labels: Union[str, None, Tensor]):
+    """(ptr, rowptr, col, labels) as ops.wl_refine / ops.sp_features take them: the batch's int64 ptr, its simple_graph, and the int64 [N]
+    start labels or None for degrees -- "auto" = initial_labels(batch.x), None, or a tensor."""
+    _gpu_batch(who, batch)
+    if isinstance(labels, str):
+        if labels != "auto":
+            raise ValueError(f"{who}: labels={labels!r} (\"auto\", None or an int64 tensor)")
+        labels = initial_labels(batch.x)
+    rowptr, col = simple_graph(batch.edge_index.contiguous(), batch.num_nodes)
+    return batch.ptr.to(torch.int64).contiguous(), rowptr, col, None if labels is None else labels.to(torch.int64).contiguous()
+
+
+def _check_status(who: str, status: Tensor, batch, node_limit: int, extra=()) -> None:
+    """One read-back of a per-graph kernel's status words (csrc/graph_block.h); GnnmpError naming the first graph with bit 0 (more than
+    node_limit nodes), then with a mask of `extra` -- rows (mask, what the graph has) -- then with skipped entries counted in bits 8 .."""
+    status = status.cpu()
+    if bool((status & 1).any()):
+        g = int((status & 1).nonzero()[0])
+        raise GnnmpError(f"{who}: graph {g} has {batch.ptr_host[g + 1] - batch.ptr_host[g]} nodes, more than the "
+                         f"{node_limit} the kernel takes (there is no host fallback)")
+    for mask, what in extra:
+        if bool((status & mask).any()):
+            raise GnnmpError(f"{who}: graph {int((status & mask).nonzero()[0])} has {what}")
+    if bool((status >> 8).any()):
+        g = int((status >> 8).nonzero()[0])
+        raise GnnmpError(f"{who}: {int(status[g] >> 8)} adjacency entries of graph {g} point outside the graph and were skipped")
+
+
 def wl_features(batch, iters: int, dim: int = ops.WL_MAX_DIM, labels: Union[str, None, Tensor] = "auto") -> WLFeatures:
     """`iters` rounds of WL refinement of one collated Batch on the GPU (ops.wl_refine on simple_graph(batch.edge_index)).  labels: "auto" =
     initial_labels(batch.x), None = degrees, or an int64 [N] tensor.  Raises GnnmpError naming the first graph the kernel refuses (more
     than ops.WL_MAX_GRAPH_NODES nodes), and when a CSR entry was skipped for leaving its graph (one read-back of the status words)."""
-    if not batch.x.is_cuda:
-        raise GnnmpError(f"wl_features: expected a batch on the GPU (the HIP path has no CPU fallback), got {batch.x.device}")
-    if isinstance(labels, str):
-        if labels != "auto":
-            raise ValueError(f"wl_features: labels={labels!r} (\"auto\", None or an int64 tensor)")
-        labels = initial_labels(batch.x)
-    rowptr, col = simple_graph(batch.edge_index.contiguous(), batch.num_nodes)
-    ptr = batch.ptr.to(torch.int64).contiguous()
-    out = ops.wl_refine(ptr, rowptr, col, None if labels is None else labels.to(torch.int64).contiguous(), iters, dim,
-                        max_graph_nodes=batch.max_graph_nodes)
-    status = out.status.cpu()
-    if bool((status & 1).any()):
-        g = int((status & 1).nonzero()[0])
-        raise GnnmpError(f"wl_features: graph {g} has {batch.ptr_host[g + 1] - batch.ptr_host[g]} nodes, more than the "
-                         f"{ops.WL_MAX_GRAPH_NODES} the kernel takes (there is no host fallback)")
-    if bool((status >> 8).any()):
-        g = int((status >> 8).nonzero()[0])
-        raise GnnmpError(f"wl_features: {int(status[g] >> 8)} adjacency entries of graph {g} point outside the graph and were skipped")
+    ptr, rowptr, col, labels = _kernel_inputs("wl_features", batch, labels)
+    out = ops.wl_refine(ptr, rowptr, col, labels, iters, dim, max_graph_nodes=batch.max_graph_nodes)
+    _check_status("wl_features", out.status, batch, ops.WL_MAX_GRAPH_NODES)
     return WLFeatures(out.sorted, out.hist, ptr, int(iters))
 
 
@@ -108,8 +126,22 @@ def wl_neighbours(sim: Tensor, k: int) -> Tuple[Tensor, Tensor]:
     return idx[:, :kk].contiguous(), val[:, :kk].contiguous()
 
 
-def _collate(ds, device):
-    return ds.collate(torch.arange(len(ds))).to(device)
+def _collated_splits(who: str, train_ds, eval_ds, k: int, device):
+    """The two splits as ONE batch each, in dataset order, after the checks every baseline makes: 1 <= k <= ops.KNN_MAX_K, no empty split."""
+    if not 1 <= int(k) <= ops.KNN_MAX_K:
+        raise ValueError(f"{who}: k={k} (1 <= k <= {ops.KNN_MAX_K})")
+    if len(train_ds) == 0 or len(eval_ds) == 0:
+        raise ValueError(f"{who}: {len(train_ds)} train and {len(eval_ds)} evaluation graphs (both splits need one)")
+    return tuple(ds.collate(torch.arange(len(ds))).to(device) for ds in (train_ds, eval_ds))
+
+
+def _accuracies(sim: Tensor, y_train: Tensor, y_eval: Tensor, num_classes: int, k: int, lr_pred: Tensor) -> Tuple[float, float]:
+    """(knn accuracy, accuracy of the caller's logreg predictions) on the evaluation split.  knn: wl_neighbours(sim, k) of sim (fp64
+    [n_eval, n_train]), their similarities in fp32 through ops.knn_vote at its default temperature.  (So the callers fit and predict
+    before the vote; the two share no state and no random draw.)"""
+    idx, val = wl_neighbours(sim, k)
+    _, knn_pred = ops.knn_vote(idx, val.to(torch.float32).contiguous(), y_train, num_classes)
+    return float((knn_pred == y_eval).float().mean()), float((lr_pred == y_eval).float().mean())
 
 
 def _kernel_baseline(who: str, features, kernel, train_ds, eval_ds, num_classes: int, k: int, device) -> Dict[str, float]:
@@ -121,19 +153,14 @@ def _kernel_baseline(who: str, features, kernel, train_ds, eval_ds, num_classes:
     datasets: there is nothing to stream.
     logreg: ops.logreg_fit on the train split's hashed histogram (as fp32, at its defaults: 100 iterations, lr 0.01), ops.logreg_predict
     on the evaluation split's."""
-    if not 1 <= int(k) <= ops.KNN_MAX_K:
-        raise ValueError(f"{who}: k={k} (1 <= k <= {ops.KNN_MAX_K})")
-    if len(train_ds) == 0 or len(eval_ds) == 0:
-        raise ValueError(f"{who}: {len(train_ds)} train and {len(eval_ds)} evaluation graphs (both splits need one)")
-    tb, eb = _collate(train_ds, device), _collate(eval_ds, device)
+    tb, eb = _collated_splits(who, train_ds, eval_ds, k, device)
     ft, fe = features(tb), features(eb)
     y_train, y_eval = tb.y.to(torch.int64).contiguous(), eb.y.to(torch.int64).contiguous()
     sim = normalised_similarity(kernel(fe, ft), kernel(fe, fe).diagonal(), kernel(ft, ft).diagonal())
-    idx, val = wl_neighbours(sim, k)
-    _, knn_pred = ops.knn_vote(idx, val.to(torch.float32).contiguous(), y_train, num_classes)
     fit = ops.logreg_fit(ft.hist.to(torch.float32).contiguous(), y_train, num_classes)
     lr_pred = ops.logreg_predict(fe.hist.to(torch.float32).contiguous(), fit.state.weight, fit.state.bias)
-    return {"knn_accuracy": float((knn_pred == y_eval).float().mean()), "logreg_accuracy": float((lr_pred == y_eval).float().mean())}
+    knn, logreg = _accuracies(sim, y_train, y_eval, num_classes, k, lr_pred)
+    return {"knn_accuracy": knn, "logreg_accuracy": logreg}
 
 
 def wl_baseline(train_ds, eval_ds, num_classes: int, iters: int, k: int = 20, device="cuda") -> Dict[str, float]:
@@ -159,33 +186,14 @@ def sp_features(batch, max_dist: int, dim: int = ops.SP_MAX_DIM, labels: Union[s
     the most keys a graph of the batch can have -- its node pairs -- up to what the kernel takes.  Raises GnnmpError naming the first
     graph the kernel refuses -- more than ops.SP_MAX_GRAPH_NODES nodes, more distinct keys than the row stride, a label outside
     [0, ops.SP_MAX_LABEL) -- and when a CSR entry was skipped for leaving its graph (one read-back of the status words)."""
-    if not batch.x.is_cuda:
-        raise GnnmpError(f"sp_features: expected a batch on the GPU (the HIP path has no CPU fallback), got {batch.x.device}")
-    if isinstance(labels, str):
-        if labels != "auto":
-            raise ValueError(f"sp_features: labels={labels!r} (\"auto\", None or an int64 tensor)")
-        labels = initial_labels(batch.x)
-    rowptr, col = simple_graph(batch.edge_index.contiguous(), batch.num_nodes)
-    ptr = batch.ptr.to(torch.int64).contiguous()
+    ptr, rowptr, col, labels = _kernel_inputs("sp_features", batch, labels)
     n = int(batch.max_graph_nodes)
     cap = max(1, min(ops.sp_max_unique(n), n * (n - 1) // 2))
-    out = ops.sp_features(ptr, rowptr, col, None if labels is None else labels.to(torch.int64).contiguous(), max_dist, dim,
-                          max_graph_nodes=n, cap=cap)
-    status = out.status.cpu()
-    if bool((status & 1).any()):
-        g = int((status & 1).nonzero()[0])
-        raise GnnmpError(f"sp_features: graph {g} has {batch.ptr_host[g + 1] - batch.ptr_host[g]} nodes, more than the "
-                         f"{ops.SP_MAX_GRAPH_NODES} the kernel takes (there is no host fallback)")
-    if bool((status & 2).any()):
-        g = int((status & 2).nonzero()[0])
-        raise GnnmpError(f"sp_features: graph {g} has more than {cap} distinct (label, label, distance) keys, the most the kernel takes "
-                         f"for graphs of up to {n} nodes (there is no host fallback)")
-    if bool((status & 4).any()):
-        g = int((status & 4).nonzero()[0])
-        raise GnnmpError(f"sp_features: graph {g} has a node label outside [0, {ops.SP_MAX_LABEL})")
-    if bool((status >> 8).any()):
-        g = int((status >> 8).nonzero()[0])
-        raise GnnmpError(f"sp_features: {int(status[g] >> 8)} adjacency entries of graph {g} point outside the graph and were skipped")
+    out = ops.sp_features(ptr, rowptr, col, labels, max_dist, dim, max_graph_nodes=n, cap=cap)
+    _check_status("sp_features", out.status, batch, ops.SP_MAX_GRAPH_NODES, extra=(
+        (2, f"more than {cap} distinct (label, label, distance) keys, the most the kernel takes for graphs of up to {n} nodes "
+            f"(there is no host fallback)"),
+        (4, f"a node label outside [0, {ops.SP_MAX_LABEL})")))
     return SPFeatures(out.keys, out.counts, out.nuniq, out.hist, int(max_dist))
 
 
@@ -217,19 +225,11 @@ def pooled_features(batch, rounds: int) -> Tensor:
     simple graph plus one self-loop per node, the host-computed 1 / sqrt(deg + 1) as both scales).  The first 3 d columns are the pools of
     the raw features: no graph.  Raises GnnmpError naming the first graph the kernel refuses (more than ops.GRAPH_FEAT_MAX_GRAPH_NODES
     nodes), and when a CSR entry was skipped for leaving its graph (one read-back of the status words)."""
-    if not batch.x.is_cuda:
-        raise GnnmpError(f"pooled_features: expected a batch on the GPU (the HIP path has no CPU fallback), got {batch.x.device}")
+    _gpu_batch("pooled_features", batch)
     rowptr, col, scale = sgc_graph(batch.edge_index.contiguous(), batch.num_nodes)
     res = ops.graph_feature_map(batch.ptr.to(torch.int64).contiguous(), rowptr, col, batch.x.to(torch.float32), rounds, left=scale, right=scale,
                                 max_graph_nodes=batch.max_graph_nodes)
-    status = res.status.cpu()
-    if bool((status & 1).any()):
-        g = int((status & 1).nonzero()[0])
-        raise GnnmpError(f"pooled_features: graph {g} has {batch.ptr_host[g + 1] - batch.ptr_host[g]} nodes, more than the "
-                         f"{ops.GRAPH_FEAT_MAX_GRAPH_NODES} the kernel takes (there is no host fallback)")
-    if bool((status >> 8).any()):
-        g = int((status >> 8).nonzero()[0])
-        raise GnnmpError(f"pooled_features: {int(status[g] >> 8)} adjacency entries of graph {g} point outside the graph and were skipped")
+    _check_status("pooled_features", res.status, batch, ops.GRAPH_FEAT_MAX_GRAPH_NODES)
     return res.out.reshape(res.out.size(0), -1)
 
 
@@ -260,11 +260,7 @@ def feature_baseline(train_ds, eval_ds, num_classes: int, rounds: int, k: int = 
     node_baselines.feature_baselines does for nodes."""
     if not 1 <= int(rounds) <= ops.GRAPH_FEAT_MAX_ROUNDS:
         raise ValueError(f"feature_baseline: rounds={rounds} (1 <= rounds <= {ops.GRAPH_FEAT_MAX_ROUNDS})")
-    if not 1 <= int(k) <= ops.KNN_MAX_K:
-        raise ValueError(f"feature_baseline: k={k} (1 <= k <= {ops.KNN_MAX_K})")
-    if len(train_ds) == 0 or len(eval_ds) == 0:
-        raise ValueError(f"feature_baseline: {len(train_ds)} train and {len(eval_ds)} evaluation graphs (both splits need one)")
-    tb, eb = _collate(train_ds, device), _collate(eval_ds, device)
+    tb, eb = _collated_splits("feature_baseline", train_ds, eval_ds, k, device)
     pt, pe = pooled_features(tb, int(rounds)), pooled_features(eb, int(rounds))
     y_train, y_eval = tb.y.to(torch.int64).contiguous(), eb.y.to(torch.int64).contiguous()
     raw = pt.size(1) // (int(rounds) + 1)                                          # 3 d: the t = 0 slice
@@ -274,10 +270,7 @@ def feature_baseline(train_ds, eval_ds, num_classes: int, rounds: int, k: int = 
         zt, ze = zt.contiguous(), ze.contiguous()
         zt64, ze64 = zt.to(torch.float64), ze.to(torch.float64)
         sim = normalised_similarity(ze64 @ zt64.T, (ze64 * ze64).sum(dim=1), (zt64 * zt64).sum(dim=1))
-        idx, val = wl_neighbours(sim, k)
-        _, knn_pred = ops.knn_vote(idx, val.to(torch.float32).contiguous(), y_train, num_classes)
         weight, bias, _ = softmax_fit(zt, y_train, num_classes)
         lr_pred = ops.gemm(ops.NT, ze, weight, bias=bias).argmax(dim=1)
-        scores[f"{name}_knn_accuracy"] = float((knn_pred == y_eval).float().mean())
-        scores[f"{name}_logreg_accuracy"] = float((lr_pred == y_eval).float().mean())
+        scores[f"{name}_knn_accuracy"], scores[f"{name}_logreg_accuracy"] = _accuracies(sim, y_train, y_eval, num_classes, k, lr_pred)
     return scores

@@ -1618,6 +1618,26 @@ def cls_counts(targets: Tensor, predictions: Tensor, probabilities: Tensor) -> T
 GRAPH_PROPS_SLOTS, GRAPH_PROPS_MAX_NODES = 16, 1024        # gmp_graph_props: counts per graph, largest graph the kernel takes (gnnmp.h)
 
 
+def _max_graph_nodes(ptr: Tensor, G: int) -> int:
+    """The largest ptr[g + 1] - ptr[g] of a batch of G graphs, read back from the device (one synchronisation); 0 without a graph."""
+    return max(int((ptr[1:] - ptr[:-1]).max()), 0) if G else 0
+
+
+def _batch_csr_args(who: str, ptr: Tensor, rowptr: Tensor, col: Tensor, labels: Optional[Tensor]) -> Tuple[int, int, torch.device]:
+    """(G, N, device) of ptr int64 [G + 1], the batch's int32 CSR (rowptr [N + 1], col) and labels int64 [N] or None, all on ptr's device."""
+    _need(ptr, torch.int64, "ptr", 1); _need(rowptr, torch.int32, "rowptr", 1); _need(col, torch.int32, "col", 1)
+    G, N, dev = ptr.numel() - 1, rowptr.numel() - 1, ptr.device
+    if G < 0 or N < 0:
+        raise L.GnnmpError(f"{who}: ptr {tuple(ptr.shape)}, rowptr {tuple(rowptr.shape)} (G + 1 and N + 1 entries)")
+    if rowptr.device != dev or col.device != dev:
+        raise L.GnnmpError(f"{who}: ptr, rowptr and col must be on one device")
+    if labels is not None:
+        _need(labels, torch.int64, "labels", 1)
+        if labels.numel() != N or labels.device != dev:
+            raise L.GnnmpError(f"{who}: labels has {labels.numel()} entries on {labels.device} for {N} nodes on {dev}")
+    return G, N, dev
+
+
 def graph_properties(ptr: Tensor, eptr: Tensor, edge_index: Tensor, max_graph_nodes: Optional[int] = None) -> Tuple[Tensor, Tensor]:
     """The integer counts behind the 12 graph-property targets of a batch (gnnmp.h gmp_graph_props; the slot table is there): ptr int64
     [B + 1] node offsets, eptr int64 [B + 1] edge offsets, edge_index int64 [2, E] batch-global ids grouped by graph.  Returns (counts
@@ -1635,7 +1655,7 @@ def graph_properties(ptr: Tensor, eptr: Tensor, edge_index: Tensor, max_graph_no
     if B == 0:
         return counts, csum
     if max_graph_nodes is None:
-        max_graph_nodes = max(int((ptr[1:] - ptr[:-1]).max()), 0)
+        max_graph_nodes = _max_graph_nodes(ptr, B)
     E = edge_index.size(1)
     L.check(L.lib().gmp_graph_props(_ptr(ptr), _ptr(eptr), _ptr(edge_index) if E else None, 0, E, B, int(max_graph_nodes), _ptr(counts),
                                     _ptr(csum), None, 0, _stream(ptr)), "gmp_graph_props")
@@ -1661,16 +1681,7 @@ def wl_refine(ptr: Tensor, rowptr: Tensor, col: Tensor, labels: Optional[Tensor]
     1 <= dim <= 256.  Returns WLRefinement(sorted, hist, status[, colors]); the outputs start as `fill`, which is what a refused graph
     (status bit 0: more than min(max_graph_nodes, WL_MAX_GRAPH_NODES) nodes) keeps.  max_graph_nodes: the largest ptr[g + 1] - ptr[g]
     when the caller knows it (None reads it back from ptr, one synchronisation).  No other read-back: status stays on the device."""
-    _need(ptr, torch.int64, "ptr", 1); _need(rowptr, torch.int32, "rowptr", 1); _need(col, torch.int32, "col", 1)
-    G, N, dev = ptr.numel() - 1, rowptr.numel() - 1, ptr.device
-    if G < 0 or N < 0:
-        raise L.GnnmpError(f"wl_refine: ptr {tuple(ptr.shape)}, rowptr {tuple(rowptr.shape)} (G + 1 and N + 1 entries)")
-    if rowptr.device != dev or col.device != dev:
-        raise L.GnnmpError("wl_refine: ptr, rowptr and col must be on one device")
-    if labels is not None:
-        _need(labels, torch.int64, "labels", 1)
-        if labels.numel() != N or labels.device != dev:
-            raise L.GnnmpError(f"wl_refine: labels has {labels.numel()} entries on {labels.device} for {N} nodes on {dev}")
+    G, N, dev = _batch_csr_args("wl_refine", ptr, rowptr, col, labels)
     if not 0 <= int(iters) <= WL_MAX_ITERS or not 1 <= int(dim) <= WL_MAX_DIM:
         raise L.GnnmpError(f"wl_refine: iters={iters} dim={dim} (0 <= iters <= {WL_MAX_ITERS}, 1 <= dim <= {WL_MAX_DIM})")
     iters, dim = int(iters), int(dim)
@@ -1680,7 +1691,7 @@ def wl_refine(ptr: Tensor, rowptr: Tensor, col: Tensor, labels: Optional[Tensor]
     colors = torch.full((iters + 1, N), fill, dtype=torch.int64, device=dev) if return_colors else None
     if G:
         if max_graph_nodes is None:
-            max_graph_nodes = max(int((ptr[1:] - ptr[:-1]).max()), 0)
+            max_graph_nodes = _max_graph_nodes(ptr, G)
         L.check(L.lib().gmp_wl_refine(_ptr(ptr), G, _ptr(rowptr), _ptr(col), N, col.numel(), _ptr(labels), iters, dim, int(max_graph_nodes),
                                       _ptr(colors), _ptr(srt), _ptr(hist), _ptr(status), None, 0, _stream(ptr)), "gmp_wl_refine")
     return WLRefinement(srt, hist, status, colors)
@@ -1731,20 +1742,11 @@ def sp_features(ptr: Tensor, rowptr: Tensor, col: Tensor, labels: Optional[Tenso
     takes.  Returns SPFeatureMap(keys, counts, nuniq, hist, status); keys, counts and hist start as `fill`, which is what a refused graph
     (status bits 0 - 2) and the tail of every row keep.  max_graph_nodes: the largest ptr[g + 1] - ptr[g] when the caller knows it (None
     reads it back from ptr, one synchronisation).  No other read-back: status stays on the device."""
-    _need(ptr, torch.int64, "ptr", 1); _need(rowptr, torch.int32, "rowptr", 1); _need(col, torch.int32, "col", 1)
-    G, N, dev = ptr.numel() - 1, rowptr.numel() - 1, ptr.device
-    if G < 0 or N < 0:
-        raise L.GnnmpError(f"sp_features: ptr {tuple(ptr.shape)}, rowptr {tuple(rowptr.shape)} (G + 1 and N + 1 entries)")
-    if rowptr.device != dev or col.device != dev:
-        raise L.GnnmpError("sp_features: ptr, rowptr and col must be on one device")
-    if labels is not None:
-        _need(labels, torch.int64, "labels", 1)
-        if labels.numel() != N or labels.device != dev:
-            raise L.GnnmpError(f"sp_features: labels has {labels.numel()} entries on {labels.device} for {N} nodes on {dev}")
+    G, N, dev = _batch_csr_args("sp_features", ptr, rowptr, col, labels)
     if not 1 <= int(max_dist) <= SP_MAX_DIST or not 1 <= int(dim) <= SP_MAX_DIM:
         raise L.GnnmpError(f"sp_features: max_dist={max_dist} dim={dim} (1 <= max_dist <= {SP_MAX_DIST}, 1 <= dim <= {SP_MAX_DIM})")
     if max_graph_nodes is None:
-        max_graph_nodes = max(int((ptr[1:] - ptr[:-1]).max()), 0) if G else 0
+        max_graph_nodes = _max_graph_nodes(ptr, G)
     limit = sp_max_unique(max_graph_nodes)
     cap = limit if cap is None else int(cap)
     if not 1 <= cap <= limit:
@@ -1917,7 +1919,7 @@ def graph_feature_map(ptr: Tensor, rowptr: Tensor, col: Tensor, x: Tensor, round
     if not 1 <= d <= GRAPH_FEAT_MAX_DIM or not 0 <= int(rounds) <= GRAPH_FEAT_MAX_ROUNDS:
         raise L.GnnmpError(f"graph_feature_map: d={d} rounds={rounds} (1 <= d <= {GRAPH_FEAT_MAX_DIM}, 0 <= rounds <= {GRAPH_FEAT_MAX_ROUNDS})")
     if max_graph_nodes is None:
-        max_graph_nodes = max(int((ptr[1:] - ptr[:-1]).max()), 0) if G else 0
+        max_graph_nodes = _max_graph_nodes(ptr, G)
     if int(max_graph_nodes) < 0:
         raise L.GnnmpError(f"graph_feature_map: max_graph_nodes={max_graph_nodes} (>= 0)")
     rounds, dev = int(rounds), ptr.device

@@ -115,15 +115,14 @@ def test_flag_is_refused_off_its_task_type_with_the_tables_message(domain):
     assert FT.FinetuneConfig(domain, "full_finetune", "b1", 1).feat_baseline == 0
 
 
-def test_the_row_stands_in_a_tuple_of_its_own_and_the_pinned_tables_are_unchanged():
-    assert [b.field for b in FT.FEATURE_BASELINES] == ["feat_baseline"] and isinstance(FT.FEATURE_BASELINES[0], FT.Baseline)
-    assert [b.field for b in FT.BASELINES] == ["lp_heuristics", "lp_walks", "wl_baseline", "label_propagation", "sgc_baseline"]
-    assert [b.field for b in FT.EXTRA_BASELINES] == ["sp_baseline"]
-    assert FT.ALL_BASELINES == FT.BASELINES + FT.EXTRA_BASELINES + FT.FEATURE_BASELINES
+def test_the_row_is_the_last_of_the_table_and_the_older_rows_are_unchanged():
+    assert [b.field for b in FT.BASELINES] == ["lp_heuristics", "lp_walks", "wl_baseline", "label_propagation", "sgc_baseline", "sp_baseline",
+                                               "feat_baseline"]
+    assert isinstance(FT.BASELINES[6], FT.Baseline)
     fields = list(FT.FinetuneConfig.__dataclass_fields__)
     assert fields[-3:] == ["feat_baseline", "sp_baseline", "wl_baseline"]
     assert "feat_baseline" not in {p.field for p in FT.PROBES}
-    row = FT.FEATURE_BASELINES[0]
+    row = FT.BASELINES[6]
     assert (row.flag, row.max_value, row.task_type) == ("--feat-baseline", 16, "graph_classification")
 
 

@@ -1,6 +1,6 @@
 """Host-side contract shared by the link rankers and the model-free baselines.  The four all-candidate rankers (gmp_lp_rank,
 gmp_lp_cn_rank, gmp_lp_walk_rank, gmp_emb_link_rank) and the three pair scorers beside them: what they refuse, with which code and which
-text (every call returns before anything is launched, so no GPU is needed).  The five rows of finetune.BASELINES: the flag parses into the
+text (every call returns before anything is launched, so no GPU is needed).  The seven rows of finetune.BASELINES: the flag parses into the
 config and is off by default, the row is refused off its task type, and its C symbols are declared, bound and exported."""
 import ctypes as C
 import re
@@ -130,6 +130,19 @@ ROWS = {
         combos=[(["--domain_name", "CiteSeer_NC", "--sgc-baseline", "3", "--label-propagation", "10", "--sparse-features"],
                  dict(sgc_baseline=3, label_propagation=10, sparse_features=True))],
         symbols=["gmp_feature_propagate_workspace_bytes", "gmp_feature_propagate"], counts=(3, 20), more=lambda lib: _sgc_workspace_rule(lib)),
+    "sp_baseline": dict(
+        on=("PTC_MR", 8), off=("Cora_NC", "Cora_LP"), top=("ENZYMES", ops.SP_MAX_DIST, {}), doc=True,
+        combos=[(["--domain_name", "ENZYMES", "--gc-engine", "--sp-baseline", "1023", "--wl-baseline", "3", "--knn-probe", "5"],
+                 dict(sp_baseline=1023, wl_baseline=3, knn_probe=5, gc_engine=True))],
+        symbols=["gmp_sp_workspace_bytes", "gmp_sp_max_unique", "gmp_sp_features", "gmp_sp_gram"], counts=(2, 1, 19, 12),
+        more=lambda lib: lib.gmp_sp_workspace_bytes(600, 1024) == 0 and lib.gmp_sp_max_unique(256) >= 4096 and lib.gmp_sp_max_unique(1024) >= 1024),
+    "feat_baseline": dict(
+        on=("PTC_MR", 2), off=("Cora_NC", "Cora_LP"), top=("ENZYMES", ops.GRAPH_FEAT_MAX_ROUNDS, {}), doc=True,
+        combos=[(["--domain_name", "ENZYMES", "--gc-engine", "--feat-baseline", "3", "--sp-baseline", "8", "--wl-baseline", "3", "--knn-probe", "5"],
+                 dict(feat_baseline=3, sp_baseline=8, wl_baseline=3, knn_probe=5, gc_engine=True))],
+        symbols=["gmp_graph_feature_map"], counts=(16,),
+        more=lambda lib: (lib.gmp_graph_feature_map(None, -1, None, None, 0, 0, None, None, None, 0, 1, 0, 0, None, None, None) == -1
+                          and lib.gmp_graph_feature_map(None, 0, None, None, 0, 0, None, None, None, 0, 1, 0, 0, None, None, None) == 0)),
 }
 ROW_IDS = [b.field for b in FT.BASELINES]
 
@@ -148,6 +161,8 @@ def _argv(b, domain, value):
 
 def test_the_tables():
     assert ROW_IDS == list(ROWS) and len(FT.PROBES) == 3                                   # the baselines are no probes: that table is untouched
+    assert ROW_IDS == ["lp_heuristics", "lp_walks", "wl_baseline", "label_propagation", "sgc_baseline", "sp_baseline", "feat_baseline"]
+    assert all(isinstance(b, FT.Baseline) for b in FT.BASELINES)                           # one table: no second tuple beside it
     assert not {b.field for b in FT.BASELINES} & {p.field for p in FT.PROBES}
     assert list(FT.FinetuneConfig.__dataclass_fields__)[-1] == "wl_baseline"              # appended, positional callers are undisturbed
 

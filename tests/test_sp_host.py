@@ -125,7 +125,7 @@ def test_flag_parses_into_the_config_and_is_off_by_default():
     cfg = FT.config_from_args(FT.build_parser().parse_args(_argv("PTC_MR", 8)))
     assert cfg.sp_baseline == 8 and type(cfg.sp_baseline) is int
     assert not cfg.gc_engine and not cfg.wl_baseline and not any(getattr(cfg, p.field) for p in FT.PROBES)
-    assert not any(getattr(cfg, b.field) for b in FT.BASELINES)
+    assert not any(getattr(cfg, b.field) for b in FT.BASELINES if b.field != "sp_baseline")
     assert FT.config_from_args(FT.build_parser().parse_args(["--domain_name", "PTC_MR"] + BASE)).sp_baseline == 0
     assert FT.FinetuneConfig("ENZYMES", "full_finetune", "b1", 1).sp_baseline == 0
     assert FT.FinetuneConfig("ENZYMES", "full_finetune", "b1", 1, sp_baseline=ops.SP_MAX_DIST).sp_baseline == 1023
@@ -153,12 +153,12 @@ def test_flag_is_refused_off_its_task_type_with_the_tables_message(domain):
     assert FT.FinetuneConfig(domain, "full_finetune", "b1", 1).sp_baseline == 0
 
 
-def test_the_row_stands_beside_the_table_and_the_field_before_wl_baseline():
-    assert [b.field for b in FT.EXTRA_BASELINES] == ["sp_baseline"] and isinstance(FT.EXTRA_BASELINES[0], FT.Baseline)
-    assert "sp_baseline" not in [b.field for b in FT.BASELINES]
+def test_the_row_is_in_the_table_and_the_field_before_wl_baseline():
+    assert [b.field for b in FT.BASELINES].index("sp_baseline") == 5 and isinstance(FT.BASELINES[5], FT.Baseline)   # after the five older rows
+    assert [b.field for b in FT.BASELINES].count("sp_baseline") == 1
     fields = list(FT.FinetuneConfig.__dataclass_fields__)
-    assert fields[-2:] == ["sp_baseline", "wl_baseline"]
-    assert not {b.field for b in FT.EXTRA_BASELINES} & {p.field for p in FT.PROBES}
+    assert fields[-3:] == ["feat_baseline", "sp_baseline", "wl_baseline"]
+    assert "sp_baseline" not in {p.field for p in FT.PROBES}
 
 
 # ---------------------------------------------------------------------------- 6. the new symbols
@@ -188,7 +188,8 @@ def test_ops_refuse_host_tensors():
 
 
 def test_sp_kernel_source_is_integer_only():
-    src = (ROOT / "gnn_pretraining_amd" / "csrc" / "sp.hip").read_text() + (ROOT / "gnn_pretraining_amd" / "csrc" / "bit_bfs.h").read_text()
+    csrc = ROOT / "gnn_pretraining_amd" / "csrc"
+    src = "".join((csrc / name).read_text() for name in ("sp.hip", "bit_bfs.h", "graph_block.h"))
     code = re.sub(r"//[^\n]*", "", src)
     assert not re.search(r"\b(float|double|__half)\b", code)
     assert not re.search(r"\basm\b", code)

@@ -145,9 +145,12 @@ def test_ops_refuse_host_tensors():
 
 # ---------------------------------------------------------------------------- 7. the new symbols
 def test_wl_kernel_source_is_integer_only():
-    src = (ROOT / "gnn_pretraining_amd" / "csrc" / "wl.hip").read_text()
+    csrc = ROOT / "gnn_pretraining_amd" / "csrc"
+    src = (csrc / "wl.hip").read_text() + (csrc / "graph_block.h").read_text()              # the header holds the row walk, the hash, the frames
     code = re.sub(r"//[^\n]*", "", src)
     assert not re.search(r"\b(float|double|__half)\b", code)
     assert not re.search(r"\basm\b|__builtin_amdgcn", code)
     names = [m.group(1) for m in re.finditer(r"atomicAdd\(&(\w+)", code)]
     assert names and set(names) <= {"bins", "skipped"}, names                             # integer LDS counters only
+    header = re.sub(r"//[^\n]*", "", (csrc / "graph_block.h").read_text())                 # the shared header on its own: no float, no atomic
+    assert not re.search(r"\b(float|double|__half)\b", header) and "atomic" not in header.replace("std::atomic", "")
