@@ -13,7 +13,6 @@ Then gmp_cls_counts alone at the row limit (device events), and the wall time of
 from __future__ import annotations
 
 import argparse
-import json
 import os
 import statistics
 import sys
@@ -26,11 +25,11 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
+from benchkit import DEV, emit, require_gpu  # noqa: E402
 from gnn_pretraining_amd import ops  # noqa: E402
 from gnn_pretraining_amd.constants import NUM_CLASSES  # noqa: E402
 from gnn_pretraining_amd.finetune import finetune as FT, metrics as M  # noqa: E402
 
-DEV = torch.device("cuda")
 SHAPES = [(500, "Cora_NC"), (1000, "Cora_NC"), (140, "Cora_NC"), (32, "ENZYMES"), (2110, "Cora_LP"), (64, "PTC_MR")]
 
 
@@ -103,8 +102,7 @@ def main() -> None:
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_cls_metrics.py needs a GPU")
+    require_gpu("bench_cls_metrics.py")
     res = {"per_batch": [bench_shape(n, d, a.reps, a.warmup) for n, d in SHAPES], "reps": a.reps, "warmup": a.warmup}
     res["row_limit"] = [limit_ms(c) for c in (2, 7, 32)]
     with tempfile.TemporaryDirectory() as tmp:
@@ -118,11 +116,7 @@ def main() -> None:
                                "host_metrics_wall_s_median": round(statistics.median(off), 4),
                                "device_metrics_wall_s_median": round(statistics.median(on), 4),
                                "what": "whole finetune() call: loaders, model, epochs x (one logged step + one validation batch), checkpoints, test"}
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    emit(res, a.out)
     if max(s["max_abs_difference"] for s in res["per_batch"]) > 1e-12:
         raise SystemExit("the two routes disagree")
 

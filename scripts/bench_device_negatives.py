@@ -14,7 +14,6 @@ No speed bar: the mode is opt-in whichever way the numbers fall."""
 from __future__ import annotations
 
 import argparse
-import json
 import os
 import random
 import statistics
@@ -34,8 +33,8 @@ def main() -> None:
     a = ap.parse_args()
     import bench as B                          # (first: it sets the process environment bench.py runs under)
     import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_device_negatives.py needs a GPU")
+    from benchkit import emit, require_gpu
+    require_gpu("bench_device_negatives.py")
     from gnn_pretraining_amd import _lib as L, ops
     from gnn_pretraining_amd._host import limit_host_threads
     from gnn_pretraining_amd.engine import StepEngine, StepPrefetcher, hostdraw
@@ -136,12 +135,7 @@ def main() -> None:
         ev.append(e0.elapsed_time(e1) * 1e3 / 400)
     res["kernel_us_per_ticket"] = {"median": statistics.median(ev), "runs": [round(x, 2) for x in ev],
                                    "note": "back-to-back tickets on an idle stream, two launches each: includes launch gaps"}
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    emit(res, a.out)
 
 
 if __name__ == "__main__":

@@ -13,38 +13,29 @@ device events.  Kernels per step: run it under `rocprofv3 --kernel-trace --stats
 from __future__ import annotations
 
 import argparse
-import json
+import itertools
 import os
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
+from benchkit import DEV, emit, require_gpu, timed  # noqa: E402
 from gnn_pretraining_amd import operators as O, ops, synthetic as S  # noqa: E402
 from gnn_pretraining_amd.finetune import finetune as FT  # noqa: E402
 from gnn_pretraining_amd.finetune.engine import GC_HEAD_SITE, GraphClassificationEngine  # noqa: E402
 from gnn_pretraining_amd.graph import Batch  # noqa: E402
 from gnn_pretraining_amd.models import FinetuneGNN  # noqa: E402
 
-DEV = torch.device("cuda")
 SHAPES = {"ENZYMES": (21, 33.0, 62.0, 6), "PTC_MR": (18, 14.0, 15.0, 2)}
 
 
-def timed(fn, steps: int, warmup: int):
-    for i in range(warmup):
-        fn(i)
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    t0 = time.perf_counter()
-    e0.record()
-    for i in range(steps):
-        fn(warmup + i)
-    e1.record()
-    torch.cuda.synchronize()
-    return 1e3 * (time.perf_counter() - t0) / steps, e0.elapsed_time(e1) / steps
+def counted(step):
+    """step(i) as a call without arguments, i counting the calls from 0: every timed run walks the batches from the first one."""
+    i = itertools.count()
+    return lambda: step(next(i))
 
 
 def bench_shape(domain: str, a) -> dict:
@@ -80,7 +71,7 @@ def bench_shape(domain: str, a) -> dict:
     for r in range(a.repeats):                                  # module, engine, module, engine, ...: the order of the legs does not decide the result
         for path, fn in (("module", module_step), ("engine", engine_step)):
             if path in a.paths:
-                w, g = timed(fn, a.steps, a.warmup if r == 0 else 5)
+                w, g = timed(counted(fn), a.steps, a.warmup if r == 0 else 5)
                 res[path + "_ms_per_step"].append(round(w, 4)); res[path + "_event_ms_per_step"].append(round(g, 4))
     if "engine" in a.paths:
         res["engine_loss_finite"] = bool(torch.isfinite(torch.tensor(eng.loss())).item())
@@ -109,8 +100,8 @@ def bench_shape(domain: str, a) -> dict:
             for q in head.parameters():
                 q.grad = None
 
-        fw, fg = timed(fused, a.head_reps, 10)
-        mw, mg = timed(module_head, a.head_reps, 10)
+        fw, fg = timed(counted(fused), a.head_reps, 10)
+        mw, mg = timed(counted(module_head), a.head_reps, 10)
         res["head_fused_event_ms"], res["head_fused_wall_ms"] = round(fg, 4), round(fw, 4)
         res["head_module_event_ms"], res["head_module_wall_ms"] = round(mg, 4), round(mw, 4)
     return res
@@ -129,15 +120,12 @@ def main() -> None:
     a = ap.parse_args()
     if a.batches < 8:
         ap.error("--batches: at least 8 different batches are cycled")
+    require_gpu("bench_gc_finetune.py")
     res = {"workload": "32 graphs per step, full_finetune, dropout 0.2, synthetic batches (public ENZYMES / PTC_MR size statistics)",
            "steps": a.steps, "warmup": a.warmup, "repeats": a.repeats, "batches": a.batches}
     for domain in a.shapes.split(","):
         res[domain] = bench_shape(domain, a)
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(json.dumps(res, indent=1) + "\n")
+    emit(res, a.out, indent=1)
 
 
 if __name__ == "__main__":

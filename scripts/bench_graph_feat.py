@@ -21,18 +21,16 @@ these is not."""
 from __future__ import annotations
 
 import argparse
-import json
 import os
 import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import torch  # noqa: E402
 
-from bench_wl import DEV, SHAPES, attempt, peak_mb, synthetic_batch, timed  # noqa: E402
+from benchkit import DEV, GRAPH_SHAPES, alternate, attempt, emit, peak, require_gpu, synthetic_batch  # noqa: E402
 from gnn_pretraining_amd import ops  # noqa: E402
 from gnn_pretraining_amd.finetune.node_baselines import sgc_graph  # noqa: E402
 
@@ -119,23 +117,17 @@ def bench_shape(name: str, graphs: int, mean_nodes: float, mean_edges: float, bi
     outs = {}
     for k, fn in routes.items():
         fn()
-        peak, outs[k] = peak_mb(fn)
-        res[f"{k}_peak_mb"] = round(peak, 3)
+        above, _, outs[k] = peak(fn)
+        res[f"{k}_peak_mb"] = round(above / 2 ** 20, 3)
     res["max_equal_chain"] = bool(torch.equal(outs["chain"][:, :, MAX], outs["kernel"][:, :, MAX]))
     res["torch_max_abs_diff"] = float((outs["torch"] - outs["kernel"]).abs().max())
     res["chain_max_abs_diff"] = float((outs["chain"] - outs["kernel"]).abs().max())
     del outs
-    for _ in range(a.warmup):
-        for fn in routes.values():
-            fn()
-    times = {k: [] for k in routes}
-    for _ in range(5):                                                            # alternate the routes: the order does not decide the result
-        for k, fn in routes.items():
-            times[k].append(timed(fn, a.reps))
-    for k, ts in times.items():
-        res[f"{k}_ms"] = round(statistics.median(t[0] for t in ts), 4)
-        res[f"{k}_event_ms"] = round(statistics.median(t[1] for t in ts), 4)
-        res[f"{k}_event_ms_runs"] = [round(t[1], 4) for t in ts]
+    times = alternate(routes, a.reps, rounds=5, warmup=a.warmup)                  # alternated: the order does not decide the result
+    for k, ts in times.items():                                                   # (the median and the event runs: this script's own record)
+        res[f"{k}_ms"] = round(statistics.median(t.host_ms for t in ts), 4)
+        res[f"{k}_event_ms"] = round(statistics.median(t.event_ms for t in ts), 4)
+        res[f"{k}_event_ms_runs"] = [round(t.event_ms, 4) for t in ts]
     return res
 
 
@@ -146,17 +138,14 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    require_gpu("bench_graph_feat.py")
     res = {"what": "sum / mean / max pools per graph of X, S X, .. S^K X of one batch; kernel = gmp_graph_feature_map (one launch), chain = "
                    "ops.feature_propagate per round + ops.segment_sum / segment_sum(mean) / segment_max_fwd per level on x padded to a multiple "
                    "of 4 columns, torch = torch.sparse.mm per round + segment_reduce (or scatter_reduce) per level; *_ms = median over 5 "
                    "alternating rounds of `reps` calls (host clock to a synchronise), *_event_ms = the same by device events",
            "rounds": a.rounds, "reps": a.reps, "warmup": a.warmup, "device": torch.cuda.get_device_name(0),
-           "shapes": [bench_shape(*s, a) for s in SHAPES]}
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+           "shapes": [bench_shape(*s, a) for s in GRAPH_SHAPES]}
+    emit(res, a.out)
     bad = [s["name"] for s in res["shapes"] if not s["max_equal_chain"] or not all(s["max_equal_on_integers"].values())]
     if bad:
         raise SystemExit(f"the routes disagree on the max slice on {bad}")

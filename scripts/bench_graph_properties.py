@@ -52,8 +52,6 @@ def run_case(name: str, count: int, reps: int) -> dict:
     import torch
     from gnn_pretraining_amd import ops
     from gnn_pretraining_amd.data.graph_properties import GraphPropertyCalculator
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_graph_properties.py needs a GPU")
     graphs, calc = case_graphs(name, count), GraphPropertyCalculator()
 
     def wall_ms(fn):
@@ -101,8 +99,10 @@ def main() -> None:
     ap.add_argument("--case", default=None, help="run one case in this process and print its JSON line (what the parent starts)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    from benchkit import emit, require_gpu                            # (brings torch: imported where this script imports torch)
     if a.case:
-        print(json.dumps(run_case(a.case, a.graphs, a.reps)))
+        require_gpu("bench_graph_properties.py")                      # in the case's process: the parent opens no device, it only starts them
+        emit(run_case(a.case, a.graphs, a.reps), None)
         return
     results = []
     for name in CASES:
@@ -115,11 +115,7 @@ def main() -> None:
             sys.stderr.write(done.stderr)
             raise SystemExit(f"case {name}: exit status {done.returncode}; stopping")
         results.append(json.loads(done.stdout.strip().splitlines()[-1]))
-    line = json.dumps({"cases": results})
-    print(line)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    emit({"cases": results}, a.out)
 
 
 if __name__ == "__main__":

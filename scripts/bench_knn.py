@@ -7,7 +7,6 @@ two routes return the same neighbours.  No speed bar is set: the condition is th
 lies below the torch route's (exit status 1 otherwise).
     python scripts/bench_knn.py --out profiles/knn.json"""
 import argparse
-import json
 import os
 import sys
 
@@ -15,6 +14,7 @@ import torch
 import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from benchkit import alternate, emit, peak, require_gpu                           # noqa: E402
 from gnn_pretraining_amd import ops                                               # noqa: E402
 
 CASES = [("leave_one_out", 2708, 2708), ("leave_one_out", 19717, 19717), ("leave_one_out", 65535, 65535), ("queries", 1000, 140)]
@@ -29,31 +29,6 @@ def torch_route(q, db, k, exclude_self):
     return idx, val
 
 
-def timed(fn, iters):
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(iters):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) / iters * 1e3          # us
-
-
-def peak_bytes(fn):
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
-    before = torch.cuda.memory_allocated()
-    torch.cuda.reset_peak_memory_stats()
-    out = fn()
-    torch.cuda.synchronize()
-    peak = torch.cuda.max_memory_allocated()
-    del out
-    return peak, peak - before
-
-
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--out", type=str, default=None, help="also write the rows to this JSON file")
@@ -62,8 +37,7 @@ def main():
     p.add_argument("--rounds", type=int, default=3, help="alternated rounds per case")
     p.add_argument("--iters", type=int, default=50, help="calls per round at fewer than 10,000 queries (a tenth of it above, at least 3)")
     a = p.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_knn.py measures on the GPU: no device found")
+    require_gpu("bench_knn.py")
     rows, ok = [], True
     for kind, nq, ndb in CASES:
         g = torch.Generator().manual_seed(0)
@@ -72,17 +46,15 @@ def main():
         q = db if loo else torch.randn(nq, a.d, generator=g).cuda()
         routes = {"knn_topk": lambda: ops.knn_topk(q, db, a.k, exclude_self=loo), "torch": lambda: torch_route(q, db, a.k, loo)}
         iters = a.iters if nq < 10000 else max(a.iters // 10, 3)
-        times = {r: [] for r in routes}
-        for _ in range(a.rounds):
-            for r, fn in routes.items():
-                times[r].append(timed(fn, iters))
+        times = {r: [1e3 * t.event_ms for t in ts] for r, ts in alternate(routes, iters, rounds=a.rounds, route_warmup=3).items()}      # us
         row = {"case": kind, "nq": nq, "ndb": ndb, "d": a.d, "k": a.k, "iters": iters, "rounds": a.rounds,
                "matrix_bytes": 4 * nq * ndb}
         for r, fn in routes.items():
             t = sorted(times[r])
             row[f"{r}_us"] = round(t[len(t) // 2], 1)
             row[f"{r}_us_rounds"] = [round(x, 1) for x in times[r]]
-            row[f"{r}_peak_bytes"], row[f"{r}_peak_bytes_above_inputs"] = peak_bytes(fn)
+            above, total = peak(fn)[:2]                                           # (the output dies here, before the next route's peak)
+            row[f"{r}_peak_bytes"], row[f"{r}_peak_bytes_above_inputs"] = total, above
         (ki, ks), (ti, ts) = routes["knn_topk"](), routes["torch"]()
         row["same_neighbours_share"] = round(float((ki == ti).float().mean()), 6)      # (torch.topk leaves the order of ties open)
         row["max_similarity_diff"] = float((ks - ts).abs().max())
@@ -91,14 +63,10 @@ def main():
         if nq in MEMORY_BAR_ROWS:
             row["memory_below_torch"] = row["knn_topk_peak_bytes"] < row["torch_peak_bytes"]
             ok = ok and row["memory_below_torch"]
-        print(json.dumps(row), flush=True)
+        emit(row, None)
         rows.append(row)
         del q, db, routes
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            json.dump({"device": torch.cuda.get_device_name(0), "memory_condition_met": ok, "rows": rows}, f, indent=1)
-            f.write("\n")
+    emit({"device": torch.cuda.get_device_name(0), "memory_condition_met": ok, "rows": rows}, a.out, indent=1)
     sys.exit(0 if ok else 1)
 
 

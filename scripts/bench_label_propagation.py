@@ -16,59 +16,20 @@ hub's row is walked by one lane group."""
 from __future__ import annotations
 
 import argparse
-import json
 import os
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
+from benchkit import DEV, alternate, attempt, emit, peak, random_graph, require_gpu  # noqa: E402
 from gnn_pretraining_amd import ops  # noqa: E402
 from gnn_pretraining_amd.finetune import link_heuristics as LH, node_baselines as NB  # noqa: E402
 
-DEV = torch.device("cuda")
 ALPHA = 0.9
 SHAPES = (("cora", 2708, 5429, 7, 0), ("pubmed", 19717, 44324, 3, 0), ("n65535", 65535, 200000, 32, 0), ("star", 20000, 40000, 7, 10000))
-
-
-def timed(fn, reps: int):
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    t0 = time.perf_counter()
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return 1e3 * (time.perf_counter() - t0) / reps, e0.elapsed_time(e1) / reps
-
-
-def peak_mb(fn):
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
-    base = torch.cuda.memory_allocated()
-    torch.cuda.reset_peak_memory_stats()
-    out = fn()
-    torch.cuda.synchronize()
-    return (torch.cuda.max_memory_allocated() - base) / 2 ** 20, out
-
-
-def attempt(fn):
-    try:
-        return fn(), None
-    except Exception as e:                                                          # noqa: BLE001  (recorded, not hidden)
-        torch.cuda.synchronize()
-        return None, f"{type(e).__name__}: {str(e).splitlines()[0][:160]}"
-
-
-def make_graph(N: int, E: int, hub: int, gen: torch.Generator):
-    edges = torch.randint(0, N, (2, E), generator=gen)
-    if hub:
-        edges = torch.cat([edges, torch.stack([torch.zeros(hub, dtype=torch.int64), torch.arange(1, hub + 1)])], dim=1)
-    return edges.to(DEV).contiguous()
 
 
 def torch_route(rowptr, col, left, right, f0, rounds: int):
@@ -88,7 +49,7 @@ def torch_route(rowptr, col, left, right, f0, rounds: int):
 
 def bench_shape(name: str, N: int, E: int, classes: int, hub: int, a) -> dict:
     gen = torch.Generator().manual_seed(N)
-    rowptr, col = LH.simple_graph(make_graph(N, E, hub, gen), N)
+    rowptr, col = LH.simple_graph(random_graph(N, E, hub, gen), N)
     left, right = NB.degree_scales(rowptr, "sym")
     seeds = torch.randperm(N, generator=gen)[: max(N // 20, 1)].to(DEV)
     f0 = torch.zeros(N, classes, device=DEV)
@@ -100,36 +61,30 @@ def bench_shape(name: str, N: int, E: int, classes: int, hub: int, a) -> dict:
         return ops.label_propagate(rowptr, col, f0, a.rounds, ALPHA, 1.0 - ALPHA, left=left, right=right).out
 
     kernel()
-    peak, got = peak_mb(kernel)
-    res["kernel_peak_mb"] = round(peak, 3)
+    above, _, got = peak(kernel)
+    res["kernel_peak_mb"] = round(above / 2 ** 20, 3)
     routes = {"kernel": kernel}
 
     def first():
         run = torch_route(rowptr, col, left, right, f0, a.rounds)
         run()
-        return (run,) + peak_mb(run)
+        return (run,) + peak(run)
     out, err = attempt(first)
     if err is not None:
         res["torch_error"] = err
         torch.cuda.empty_cache()
     else:
-        run, peak, want = out
+        run, above, _, want = out
         routes["torch"] = run
-        res["torch_peak_mb"] = round(peak, 3)
+        res["torch_peak_mb"] = round(above / 2 ** 20, 3)
         res["max_abs_diff"] = float((got - want).abs().max())
         res["max_abs_value"] = float(want.abs().max())
-    for _ in range(a.warmup):
-        for fn in routes.values():
-            fn()
-    times = {k: [] for k in routes}
-    for _ in range(3):                                                              # alternate the routes: the order does not decide the result
-        for k, fn in routes.items():
-            times[k].append(timed(fn, a.reps))
-    for k, ts in times.items():
-        res[f"{k}_ms"] = round(min(t[0] for t in ts), 4)
-        res[f"{k}_event_ms"] = round(min(t[1] for t in ts), 4)
-        res[f"{k}_us_per_round"] = round(1e3 * min(t[1] for t in ts) / a.rounds, 3)
-        res[f"{k}_ms_runs"] = [round(t[0], 4) for t in ts]
+    times = alternate(routes, a.reps, warmup=a.warmup)                              # alternated: the order does not decide the result
+    for k, ts in times.items():                                                     # (record_min's keys with *_us_per_round between them)
+        res[f"{k}_ms"] = round(min(t.host_ms for t in ts), 4)
+        res[f"{k}_event_ms"] = round(min(t.event_ms for t in ts), 4)
+        res[f"{k}_us_per_round"] = round(1e3 * min(t.event_ms for t in ts) / a.rounds, 3)
+        res[f"{k}_ms_runs"] = [round(t.host_ms, 4) for t in ts]
     return res
 
 
@@ -140,15 +95,12 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    require_gpu("bench_label_propagation.py")
     res = {"what": "label spreading (alpha 0.9, symmetric scaling) for `rounds` rounds; kernel = gmp_label_propagate (one launch per round, a "
                    "lane group per row, sequential row sums), torch = torch.sparse.mm on a CSR of S plus one axpy per round; *_us_per_round = "
                    "device-event time of a call over its rounds",
            "rounds": a.rounds, "reps": a.reps, "warmup": a.warmup, "shapes": [bench_shape(*s, a) for s in SHAPES]}
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    emit(res, a.out)
     bad = [s["graph"] for s in res["shapes"] if s.get("max_abs_diff", 0.0) > 1e-5]             # entries lie in [0, 1]: rounding leaves ~1e-7
     if bad:
         raise SystemExit(f"the kernel's result differs from the torch form's beyond rounding on {bad}")

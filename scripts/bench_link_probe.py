@@ -18,10 +18,8 @@ not required.  No time is a pass criterion."""
 from __future__ import annotations
 
 import argparse
-import json
 import os
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -29,49 +27,13 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
 
+from benchkit import DEV, alternate, attempt, emit, keep_mask, peak, record_min, require_gpu  # noqa: E402
 from gnn_pretraining_amd import _lib as L, operators as O  # noqa: E402
 from gnn_pretraining_amd.finetune import link_probe as LPR  # noqa: E402
 from gnn_pretraining_amd.operators import csr_of  # noqa: E402
 
-DEV = torch.device("cuda")
 SHAPES = ((2708, 5429), (19717, 44324), (65535, 200000))
 DIM = 256
-
-
-def timed(fn, reps: int):
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    t0 = time.perf_counter()
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return 1e3 * (time.perf_counter() - t0) / reps, e0.elapsed_time(e1) / reps
-
-
-def peak_mb(fn):
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
-    base = torch.cuda.memory_allocated()
-    torch.cuda.reset_peak_memory_stats()
-    out = fn()
-    torch.cuda.synchronize()
-    return (torch.cuda.max_memory_allocated() - base) / 2 ** 20, out
-
-
-def keep_mask(src, dst, frp, fcl, N):
-    """bool [len(src), N]: the candidates of every query -- all nodes but the source, the destination and the source's filter row."""
-    Q = src.numel()
-    qs = torch.arange(Q, device=src.device)
-    keep = torch.ones(Q, N, dtype=torch.bool, device=src.device)
-    keep[qs, src] = False
-    keep[qs, dst] = False
-    fd = frp[src + 1] - frp[src]
-    frow = torch.repeat_interleave(qs, fd)
-    fwithin = torch.arange(frow.numel(), device=src.device) - (torch.cumsum(fd, 0) - fd)[frow]
-    keep[frow, fcl[frp[src][frow] + fwithin]] = False
-    return keep
 
 
 def torch_route(h, pos, frp, fcl, kind):
@@ -88,14 +50,6 @@ def torch_route(h, pos, frp, fcl, kind):
     return run
 
 
-def attempt(fn):
-    try:
-        return fn(), None
-    except Exception as e:                                                          # noqa: BLE001  (recorded, not hidden: see the docstring)
-        torch.cuda.synchronize()
-        return None, f"{type(e).__name__}: {str(e).splitlines()[0][:160]}"
-
-
 def bench_kind(h, pos, known, frp, fcl, kind: str, scorer, a) -> dict:
     res = {"kind": kind}
 
@@ -104,37 +58,28 @@ def bench_kind(h, pos, known, frp, fcl, kind: str, scorer, a) -> dict:
         return r.n_greater, r.n_equal
 
     kernel()                                                                        # the cached filter CSR exists from here on
-    peak, got = peak_mb(kernel)
-    res["kernel_peak_mb"] = round(peak, 3)
+    above, _, got = peak(kernel)
+    res["kernel_peak_mb"] = round(above / 2 ** 20, 3)
     routes = {"kernel": kernel}
 
     def first():
         run = torch_route(h, pos, frp, fcl, kind)
-        return (run,) + peak_mb(run)
+        return (run,) + peak(run)
     out, err = attempt(first)
     if err is not None:
         res["torch_error"] = err
         torch.cuda.empty_cache()
     else:
-        run, peak, want = out
+        run, above, _, want = out
         routes["torch"] = run
-        res["torch_peak_mb"] = round(peak, 3)
+        res["torch_peak_mb"] = round(above / 2 ** 20, 3)
         res["torch_queries_with_other_counts"] = int(((got[0] != want[0]) | (got[1] != want[1])).sum())
         res["torch_max_rank_difference"] = float(((got[0] - want[0]).float() + 0.5 * (got[1] - want[1]).float()).abs().max())
     if scorer is not None:                                                          # once per shape: it does not depend on the kind
         routes["scorer"] = scorer
-        res["scorer_peak_mb"] = round(peak_mb(scorer)[0], 3)
-    for _ in range(a.warmup):
-        for fn in routes.values():
-            fn()
-    times = {k: [] for k in routes}
-    for _ in range(3):                                                              # alternate the routes: the order does not decide the result
-        for k, fn in routes.items():
-            times[k].append(timed(fn, max(a.reps // 5, 1) if k == "scorer" else a.reps))
-    for k, ts in times.items():
-        res[f"{k}_ms"] = round(min(t[0] for t in ts), 3)
-        res[f"{k}_event_ms"] = round(min(t[1] for t in ts), 3)
-        res[f"{k}_ms_runs"] = [round(t[0], 3) for t in ts]
+        res["scorer_peak_mb"] = round(peak(scorer).above_bytes / 2 ** 20, 3)
+    reps = {k: max(a.reps // 5, 1) if k == "scorer" else a.reps for k in routes}
+    record_min(res, alternate(routes, reps, warmup=a.warmup), 3)                    # alternated: the order does not decide the result
     return res
 
 
@@ -165,15 +110,12 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    require_gpu("bench_link_probe.py")
     res = {"what": "filtered ranking of true edges against all nodes by the cosine / the inner product of random d = 256 embeddings on uniform "
                    "random graphs; kernel = gmp_emb_link_rank (streaming, no Q x N array), torch = normalize + gather + Q x N matmul + dense "
                    "mask + compare and count, scorer = gmp_lp_rank with the 768 -> 256 -> 1 MLP on the same pairs (context, timed beside cos)",
            "reps": a.reps, "warmup": a.warmup, "shapes": [bench_shape(N, E, a) for N, E in SHAPES]}
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    emit(res, a.out)
 
 
 if __name__ == "__main__":

@@ -10,7 +10,6 @@ the four blob cases of tests/test_gpu_logreg.py against the float64 reference of
 train accuracy).  No bar on time or memory.
     python scripts/bench_logreg.py --out profiles/logreg.json"""
 import argparse
-import json
 import os
 import sys
 
@@ -21,6 +20,7 @@ import torch.nn.functional as F
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+from benchkit import alternate, emit, peak, require_gpu                           # noqa: E402
 from gnn_pretraining_amd import ops                                               # noqa: E402
 
 CASES = [(2708, 7), (19717, 3), (65535, 32)]
@@ -39,31 +39,6 @@ def torch_route(x, y, classes, iters, lr):
     return W.detach(), b.detach(), loss.detach()
 
 
-def timed(fn, reps):
-    for _ in range(2):
-        fn()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) / reps * 1e3          # us
-
-
-def peak_bytes(fn):
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
-    before = torch.cuda.memory_allocated()
-    torch.cuda.reset_peak_memory_stats()
-    out = fn()
-    torch.cuda.synchronize()
-    peak = torch.cuda.max_memory_allocated()
-    del out
-    return peak, peak - before
-
-
 def blob_rows():
     import logreg_ref as R
     rows = []
@@ -76,7 +51,7 @@ def blob_rows():
         rows.append({"n": n, "d": d, "classes": classes, "noise": noise, "iterations": 100, "final_loss": float(fit.loss_history[-1]),
                      "final_loss_fp64": float(hist[-1]), "max_abs_weight_minus_fp64": float(np.abs(fit.state.weight.cpu().numpy() - W64).max()),
                      "train_accuracy": float((pred == yd).float().mean())})
-        print(json.dumps(rows[-1]), flush=True)
+        emit(rows[-1], None)
     return rows
 
 
@@ -88,8 +63,7 @@ def main():
     p.add_argument("--rounds", type=int, default=3, help="alternated rounds per case")
     p.add_argument("--reps", type=int, default=5, help="calls per round at fewer than 10,000 rows (2 above)")
     a = p.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_logreg.py measures on the GPU: no device found")
+    require_gpu("bench_logreg.py")
     rows = []
     for n, classes in CASES:
         g = torch.Generator().manual_seed(0)
@@ -99,30 +73,24 @@ def main():
         routes = {"logreg_fit": lambda: ops.logreg_fit(x, y, classes, iters=a.iterations, lr=0.01),
                   "torch": lambda: torch_route(x, y, classes, a.iterations, 0.01)}
         reps = a.reps if n < 10000 else 2
-        times = {r: [] for r in routes}
-        for _ in range(a.rounds):
-            for r, fn in routes.items():
-                times[r].append(timed(fn, reps) / a.iterations)
+        times = {r: [1e3 * t.event_ms / a.iterations for t in ts]                   # us per iteration
+                 for r, ts in alternate(routes, reps, rounds=a.rounds, route_warmup=2).items()}
         row = {"n": n, "classes": classes, "d": a.d, "iterations": a.iterations, "reps": reps, "rounds": a.rounds, "logits_bytes": 4 * n * classes}
         for r, fn in routes.items():
             t = sorted(times[r])
             row[f"{r}_us_per_iteration"] = round(t[len(t) // 2], 1)
             row[f"{r}_us_per_iteration_rounds"] = [round(v, 1) for v in times[r]]
-            row[f"{r}_peak_bytes"], row[f"{r}_peak_bytes_above_inputs"] = peak_bytes(fn)
+            above, total = peak(fn)[:2]                                           # (the output dies here, before the next route's peak)
+            row[f"{r}_peak_bytes"], row[f"{r}_peak_bytes_above_inputs"] = total, above
         fit, (tw, tb, tl) = routes["logreg_fit"](), routes["torch"]()
         row["max_abs_weight_difference"] = float((fit.state.weight - tw).abs().max())
         row["last_loss_logreg_fit"], row["last_loss_torch"] = float(fit.loss_history[-1]), float(tl)
         row["logreg_over_torch_time"] = round(row["logreg_fit_us_per_iteration"] / row["torch_us_per_iteration"], 3)
         row["logreg_over_torch_peak_above_inputs"] = round(row["logreg_fit_peak_bytes_above_inputs"] / row["torch_peak_bytes_above_inputs"], 4)
-        print(json.dumps(row), flush=True)
+        emit(row, None)
         rows.append(row)
         del x, y, routes, fit
-    blobs = blob_rows()
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            json.dump({"device": torch.cuda.get_device_name(0), "rows": rows, "blob_fits": blobs}, f, indent=1)
-            f.write("\n")
+    emit({"device": torch.cuda.get_device_name(0), "rows": rows, "blob_fits": blob_rows()}, a.out, indent=1)
 
 
 if __name__ == "__main__":

@@ -10,37 +10,26 @@ under `rocprofv3 --kernel-trace --stats -- python scripts/bench_lp_finetune.py -
 from __future__ import annotations
 
 import argparse
-import json
+import itertools
 import os
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
+from benchkit import DEV, emit, require_gpu, timed  # noqa: E402
 from gnn_pretraining_amd import ops, synthetic as S  # noqa: E402
 from gnn_pretraining_amd.data.data_setup import create_link_prediction_splits  # noqa: E402
 from gnn_pretraining_amd.finetune import finetune as FT  # noqa: E402
 from gnn_pretraining_amd.finetune.engine import LinkPredictionEngine  # noqa: E402
 from gnn_pretraining_amd.models import FinetuneGNN  # noqa: E402
 
-DEV = torch.device("cuda")
-
-
-def timed(fn, steps: int, warmup: int):
-    for i in range(warmup):
-        fn(i)
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    t0 = time.perf_counter()
-    e0.record()
-    for i in range(steps):
-        fn(warmup + i)
-    e1.record()
-    torch.cuda.synchronize()
-    return 1e3 * (time.perf_counter() - t0) / steps, e0.elapsed_time(e1) / steps
+def counted(step):
+    """step(i) as a call without arguments, i counting the calls from 0: every timed run walks the batches from the first one."""
+    i = itertools.count()
+    return lambda: step(next(i))
 
 
 def main() -> None:
@@ -50,6 +39,7 @@ def main() -> None:
     ap.add_argument("--scorer-reps", type=int, default=50)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    require_gpu("bench_lp_finetune.py")
     gen = torch.Generator().manual_seed(0)
     torch.manual_seed(0)
     c = S.cora_like(gen)
@@ -80,9 +70,9 @@ def main() -> None:
         neg = eminer.mine_hard_negatives_for_edges(emb, pos, pos.size(1), mp)
         eng.step(pos, neg)
 
-    mod_wall, mod_gpu = timed(module_step, a.steps, a.warmup)
-    eng_wall, eng_gpu = timed(engine_step, a.steps, a.warmup)
-    mod_wall2, mod_gpu2 = timed(module_step, a.steps, 0)           # second module run: the order of the two legs does not decide the result
+    mod_wall, mod_gpu = timed(counted(module_step), a.steps, a.warmup)
+    eng_wall, eng_gpu = timed(counted(engine_step), a.steps, a.warmup)
+    mod_wall2, mod_gpu2 = timed(counted(module_step), a.steps, 0)  # second module run: the order of the two legs does not decide the result
 
     # the fused scorer alone at the step's K = 512
     h = torch.randn(c.num_nodes, 256, device=DEV)
@@ -92,8 +82,8 @@ def main() -> None:
     w0, b0, w3, b3 = p[hd + "0.weight"].detach(), p[hd + "0.bias"].detach(), p[hd + "3.weight"].detach(), p[hd + "3.bias"].detach()
     act, logit = ops.lp_score_fwd(h, src, dst, w0, b0, w3, b3, 0.2, 1, 40)
     g = torch.randn(512, device=DEV) / 512
-    fwd_wall, fwd_gpu = timed(lambda i: ops.lp_score_fwd(h, src, dst, w0, b0, w3, b3, 0.2, 1, 40), a.scorer_reps, 3)
-    bwd_wall, bwd_gpu = timed(lambda i: ops.lp_score_bwd(h, src, dst, w0, w3, act, g, 0.2, 1, 40), a.scorer_reps, 3)
+    fwd_wall, fwd_gpu = timed(lambda: ops.lp_score_fwd(h, src, dst, w0, b0, w3, b3, 0.2, 1, 40), a.scorer_reps, 3)
+    bwd_wall, bwd_gpu = timed(lambda: ops.lp_score_bwd(h, src, dst, w0, w3, act, g, 0.2, 1, 40), a.scorer_reps, 3)
 
     res = {"shape": "Cora_LP synthetic: 2708 x 1433, 256 positives + 256 mined negatives per step",
            "module_ms_per_step": round(min(mod_wall, mod_wall2), 3), "module_event_ms_per_step": round(min(mod_gpu, mod_gpu2), 3),
@@ -102,11 +92,7 @@ def main() -> None:
            "scorer_fwd_event_ms_K512": round(fwd_gpu, 4), "scorer_bwd_event_ms_K512": round(bwd_gpu, 4),
            "engine_loss_finite": bool(torch.isfinite(torch.tensor(eng.loss())).item()),
            "steps": a.steps, "warmup": a.warmup}
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    emit(res, a.out)
 
 
 if __name__ == "__main__":

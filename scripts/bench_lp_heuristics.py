@@ -16,43 +16,19 @@ counts may differ from the kernel's in ties; the cross-check that must hold is o
 from __future__ import annotations
 
 import argparse
-import json
 import os
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
+from benchkit import DEV, alternate, attempt, emit, peak, record_min, require_gpu  # noqa: E402
 from gnn_pretraining_amd.finetune import link_heuristics as LH  # noqa: E402
 from gnn_pretraining_amd.operators import csr_of  # noqa: E402
 
-DEV = torch.device("cuda")
 SHAPES = ((2708, 5429), (19717, 44324), (65535, 200000))
-
-
-def timed(fn, reps: int):
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    t0 = time.perf_counter()
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return 1e3 * (time.perf_counter() - t0) / reps, e0.elapsed_time(e1) / reps
-
-
-def peak_mb(fn):
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
-    base = torch.cuda.memory_allocated()
-    torch.cuda.reset_peak_memory_stats()
-    out = fn()
-    torch.cuda.synchronize()
-    return (torch.cuda.max_memory_allocated() - base) / 2 ** 20, out
 
 
 def torch_route(rowptr, col, weight, pos, known, N, dense: bool):
@@ -93,14 +69,6 @@ def torch_route(rowptr, col, weight, pos, known, N, dense: bool):
     return run
 
 
-def attempt(fn):
-    try:
-        return fn(), None
-    except Exception as e:                                                          # noqa: BLE001  (recorded, not hidden: see the docstring)
-        torch.cuda.synchronize()
-        return None, f"{type(e).__name__}: {str(e).splitlines()[0][:160]}"
-
-
 def bench_shape(N: int, E: int, a) -> dict:
     gen = torch.Generator().manual_seed(N)
     graph = torch.randint(0, N, (2, E), generator=gen).to(DEV).contiguous()
@@ -117,37 +85,28 @@ def bench_shape(N: int, E: int, a) -> dict:
         return r.n_greater, r.n_equal
 
     kernel()                                                                        # the cached graph, weights and filter CSR exist from here on
-    peak, got = peak_mb(kernel)
-    res["kernel_peak_mb"] = round(peak, 3)
+    above, _, got = peak(kernel)
+    res["kernel_peak_mb"] = round(above / 2 ** 20, 3)
     routes = {"kernel": kernel}
     for name, dense in (("torch_sparse", False), ("torch_dense", True)):
         def first(dense=dense):
             run = torch_route(rowptr, col, weight, pos, known, N, dense)
-            return (run,) + peak_mb(run)
+            return (run,) + peak(run)
         out, err = attempt(first)
         if err is not None:
             res[f"{name}_error"] = err
             torch.cuda.empty_cache()
             continue
-        run, peak, want = out
+        run, above, _, want = out
         routes[name] = run
-        res[f"{name}_peak_mb"] = round(peak, 3)
+        res[f"{name}_peak_mb"] = round(above / 2 ** 20, 3)
         res[f"{name}_aa_counts_equal"] = bool(torch.equal(got[0], want[0]) and torch.equal(got[1], want[1]))
         cn_run, err = attempt(lambda dense=dense: torch_route(rowptr, col, None, pos, known, N, dense)())
         if err is None:
             cn = kernel("cn")
             res[f"{name}_cn_counts_equal"] = bool(torch.equal(cn[0], cn_run[0]) and torch.equal(cn[1], cn_run[1]))
-    for _ in range(a.warmup):
-        for fn in routes.values():
-            fn()
-    times = {k: [] for k in routes}
-    for _ in range(3):                                                              # alternate the routes: the order does not decide the result
-        for k, fn in routes.items():
-            times[k].append(timed(fn, a.reps if k == "kernel" else max(a.reps // 5, 1)))
-    for k, ts in times.items():
-        res[f"{k}_ms"] = round(min(t[0] for t in ts), 3)
-        res[f"{k}_event_ms"] = round(min(t[1] for t in ts), 3)
-        res[f"{k}_ms_runs"] = [round(t[0], 3) for t in ts]
+    reps = {k: a.reps if k == "kernel" else max(a.reps // 5, 1) for k in routes}
+    record_min(res, alternate(routes, reps, warmup=a.warmup), 3)                    # alternated: the order does not decide the result
     return res
 
 
@@ -158,14 +117,11 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    require_gpu("bench_lp_heuristics.py")
     res = {"what": "Adamic-Adar filtered ranking of true edges against all nodes on uniform random graphs; kernel = gmp_lp_cn_rank (push form, "
                    "the only form built), torch = sparse A[src] times sparse / dense diag(w) A, then compare and count under a dense mask",
            "reps": a.reps, "warmup": a.warmup, "shapes": [bench_shape(N, E, a) for N, E in SHAPES]}
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    emit(res, a.out)
     bad = [s["nodes"] for s in res["shapes"] for k, v in s.items() if k.endswith("_cn_counts_equal") and not v]
     if bad:
         raise SystemExit(f"the kernel's common-neighbour counts differ from the torch form's at N = {bad}")

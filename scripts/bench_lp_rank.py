@@ -13,44 +13,19 @@ two routes' counts are compared and must be equal.  Also timed: top_k (k = 10) f
 from __future__ import annotations
 
 import argparse
-import json
 import os
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
+from benchkit import DEV, alternate, emit, peak, record_min, require_gpu, timed  # noqa: E402
 from gnn_pretraining_amd import synthetic as S  # noqa: E402
 from gnn_pretraining_amd.data.data_setup import create_link_prediction_splits  # noqa: E402
 from gnn_pretraining_amd.finetune.engine import LinkPredictionEngine  # noqa: E402
 from gnn_pretraining_amd.models import FinetuneGNN  # noqa: E402
-
-DEV = torch.device("cuda")
-
-
-def timed(fn, reps: int):
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    t0 = time.perf_counter()
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return 1e3 * (time.perf_counter() - t0) / reps, e0.elapsed_time(e1) / reps
-
-
-def peak_mb(fn):
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
-    base = torch.cuda.memory_allocated()
-    torch.cuda.reset_peak_memory_stats()
-    out = fn()
-    torch.cuda.synchronize()
-    return (torch.cuda.max_memory_allocated() - base) / 2 ** 20, out
 
 
 def main() -> None:
@@ -61,6 +36,7 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    require_gpu("bench_lp_rank.py")
     gen = torch.Generator().manual_seed(0)
     torch.manual_seed(0)
     c = S.cora_like(gen)
@@ -101,28 +77,19 @@ def main() -> None:
     route_topk = lambda: eng.top_k(sources, 10, filter_edges=known, embeddings=emb)
 
     # each route's first call: everything it makes the engine allocate counts (predict grows the engine's pair buffers to the chunk)
-    (rank_peak, got), (pred_peak, want) = peak_mb(route_rank), peak_mb(route_predict)
+    (rank_above, _, got), (pred_above, _, want) = peak(route_rank), peak(route_predict)
     for _ in range(a.warmup):
         route_rank(), route_predict(), route_topk()
     same = bool(torch.equal(got[0], want[0]) and torch.equal(got[1], want[1]))
-    rank_t, pred_t = [], []
-    for _ in range(3):                                          # alternate the routes: the order does not decide the result
-        rank_t.append(timed(route_rank, a.reps))
-        pred_t.append(timed(route_predict, max(a.reps // 5, 1)))
+    times = alternate({"rank": route_rank, "predict_route": route_predict}, {"rank": a.reps, "predict_route": max(a.reps // 5, 1)})
     topk_t = timed(route_topk, a.reps)
-    best = lambda ts, i: round(min(t[i] for t in ts), 3)
     res = {"shape": f"Cora-sized synthetic graph: N = {N}, Q = {Q} true edges, {known.size(1)} filter edges, predict route in chunks of {a.chunk} queries",
-           "counts_equal": same,
-           "rank_ms": best(rank_t, 0), "rank_event_ms": best(rank_t, 1), "rank_ms_runs": [round(t[0], 3) for t in rank_t],
-           "predict_route_ms": best(pred_t, 0), "predict_route_event_ms": best(pred_t, 1), "predict_route_ms_runs": [round(t[0], 3) for t in pred_t],
-           "rank_peak_mb": round(rank_peak, 2), "predict_route_peak_mb": round(pred_peak, 2),
-           "topk10_ms": round(topk_t[0], 3), "topk10_event_ms": round(topk_t[1], 3),
-           "pairs": Q * N, "reps": a.reps, "warmup": a.warmup}
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+           "counts_equal": same}
+    record_min(res, times, 3)                                   # alternated: the order does not decide the result
+    res.update({"rank_peak_mb": round(rank_above / 2 ** 20, 2), "predict_route_peak_mb": round(pred_above / 2 ** 20, 2),
+                "topk10_ms": round(topk_t.host_ms, 3), "topk10_event_ms": round(topk_t.event_ms, 3),
+                "pairs": Q * N, "reps": a.reps, "warmup": a.warmup})
+    emit(res, a.out)
     if not same:
         raise SystemExit("the two routes disagree")
 

@@ -18,60 +18,22 @@ must equal the kernel's; spmm adds in another order, so its counts may differ in
 from __future__ import annotations
 
 import argparse
-import json
 import os
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
+from benchkit import DEV, alternate, attempt, emit, keep_mask, peak, record_min, require_gpu  # noqa: E402
 from gnn_pretraining_amd import _lib as L, ops  # noqa: E402
 from gnn_pretraining_amd.finetune import link_heuristics as LH, link_walks as LW  # noqa: E402
 from gnn_pretraining_amd.operators import csr_of  # noqa: E402
 
-DEV = torch.device("cuda")
 SHAPES = ((2708, 5429), (19717, 44324), (65535, 200000))
 CASES = (("ppr", 20), ("katz", 6))
 CHUNK = ops.LABELPROP_MAX_CLASSES
-
-
-def timed(fn, reps: int):
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    t0 = time.perf_counter()
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return 1e3 * (time.perf_counter() - t0) / reps, e0.elapsed_time(e1) / reps
-
-
-def peak_mb(fn):
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
-    base = torch.cuda.memory_allocated()
-    torch.cuda.reset_peak_memory_stats()
-    out = fn()
-    torch.cuda.synchronize()
-    return (torch.cuda.max_memory_allocated() - base) / 2 ** 20, out
-
-
-def keep_mask(src, dst, frp, fcl, N):
-    """bool [len(src), N]: the candidates of every query -- all nodes but the source, the destination and the source's filter row."""
-    Q = src.numel()
-    qs = torch.arange(Q, device=DEV)
-    keep = torch.ones(Q, N, dtype=torch.bool, device=DEV)
-    keep[qs, src] = False
-    keep[qs, dst] = False
-    fd = frp[src + 1] - frp[src]
-    frow = torch.repeat_interleave(qs, fd)
-    fwithin = torch.arange(frow.numel(), device=DEV) - (torch.cumsum(fd, 0) - fd)[frow]
-    keep[frow, fcl[frp[src][frow] + fwithin]] = False
-    return keep
 
 
 def count(acc_t, src, dst, frp, fcl, N):
@@ -124,14 +86,6 @@ def labelprop_route(rowptr, col, weight, damping, rounds, pos, frp, fcl, N):
     return run
 
 
-def attempt(fn):
-    try:
-        return fn(), None
-    except Exception as e:                                                          # noqa: BLE001  (recorded, not hidden: see the docstring)
-        torch.cuda.synchronize()
-        return None, f"{type(e).__name__}: {str(e).splitlines()[0][:160]}"
-
-
 def bench_case(graph, N, pos, known, kind: str, rounds: int, a) -> dict:
     rowptr, col, weight, damping, _ = LW._kernel_args(graph, N, kind)
     csr = csr_of(known, N)
@@ -143,34 +97,25 @@ def bench_case(graph, N, pos, known, kind: str, rounds: int, a) -> dict:
         return r.n_greater, r.n_equal
 
     kernel()                                                                        # the cached graph, weights and filter CSR exist from here on
-    peak, got = peak_mb(kernel)
-    res["kernel_peak_mb"] = round(peak, 3)
+    above, _, got = peak(kernel)
+    res["kernel_peak_mb"] = round(above / 2 ** 20, 3)
     routes = {"kernel": kernel}
     for name, make in (("spmm", spmm_route), ("labelprop", labelprop_route)):
         def first(make=make):
             run = make(rowptr, col, weight, damping, rounds, pos, frp, fcl, N)
-            return (run,) + peak_mb(run)
+            return (run,) + peak(run)
         out, err = attempt(first)
         if err is not None:
             res[f"{name}_error"] = err
             torch.cuda.empty_cache()
             continue
-        run, peak, want = out
+        run, above, _, want = out
         routes[name] = run
-        res[f"{name}_peak_mb"] = round(peak, 3)
+        res[f"{name}_peak_mb"] = round(above / 2 ** 20, 3)
         res[f"{name}_counts_equal"] = bool(torch.equal(got[0], want[0]) and torch.equal(got[1], want[1]))
         res[f"{name}_queries_with_other_counts"] = int(((got[0] != want[0]) | (got[1] != want[1])).sum())
-    for _ in range(a.warmup):
-        for fn in routes.values():
-            fn()
-    times = {k: [] for k in routes}
-    for _ in range(3):                                                              # alternate the routes: the order does not decide the result
-        for k, fn in routes.items():
-            times[k].append(timed(fn, a.reps if k == "kernel" else max(a.reps // 5, 1)))
-    for k, ts in times.items():
-        res[f"{k}_ms"] = round(min(t[0] for t in ts), 3)
-        res[f"{k}_event_ms"] = round(min(t[1] for t in ts), 3)
-        res[f"{k}_ms_runs"] = [round(t[0], 3) for t in ts]
+    reps = {k: a.reps if k == "kernel" else max(a.reps // 5, 1) for k in routes}
+    record_min(res, alternate(routes, reps, warmup=a.warmup), 3)                    # alternated: the order does not decide the result
     return res
 
 
@@ -195,16 +140,13 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    require_gpu("bench_lp_walks.py")
     res = {"what": "filtered ranking of true edges against all nodes under rooted PageRank (20 rounds) and Katz (6 rounds) on uniform random "
                    "graphs; kernel = gmp_lp_walk_rank (one workgroup per query), spmm = torch.sparse.mm on an N x Q one-hot per round, "
                    "labelprop = ops.label_propagate on 32 columns at a time, both then compare and count under a dense mask",
            "reps": a.reps, "warmup": a.warmup, "lds_nodes": L.lib().gmp_lp_walk_lds_nodes(),
            "resident_blocks": L.lib().gmp_lp_walk_resident_blocks(), "shapes": [bench_shape(N, E, a) for N, E in SHAPES]}
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    emit(res, a.out)
     bad = [(s["nodes"], c["kind"]) for s in res["shapes"] for c in s["cases"] if c.get("labelprop_counts_equal") is False]
     if bad:
         raise SystemExit(f"the kernel's counts differ from the label_propagate route's at {bad}")

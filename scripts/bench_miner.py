@@ -9,7 +9,6 @@ streaming form ran (its device counter, read back after the timed loops).  At 65
 only the streaming form runs there.
     python scripts/bench_miner.py --impl both --out profiles/miner_stream.json"""
 import argparse
-import json
 import os
 import sys
 import time
@@ -17,6 +16,7 @@ import time
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from benchkit import alternate, emit, require_gpu, timed                          # noqa: E402
 from gnn_pretraining_amd import ops                                               # noqa: E402
 
 
@@ -34,19 +34,6 @@ def torch_sequence(emb, edges, k):
     idx = torch.where(pot)
     _, top = torch.topk(scores, k, largest=True)
     return torch.stack([idx[0][top], idx[1][top]])
-
-
-def timed(fn, iters):
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(iters):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) / iters * 1e3          # us
 
 
 SIZES = [(2708, 8446), (3327, 7283), (19717, 70918), (65535, 262140)]     # (nodes, directed training-edge entries: 80 % of the public counts; 4 n at 65,535)
@@ -78,10 +65,9 @@ def compare(a):
         edges = torch.randint(0, n, (2, E), generator=g).cuda()
         impls = [i for i in ("matrix", "stream") if a.impl in (i, "both") and (i == "stream" or n <= DENSE_MAX_N)]
         iters = a.iters if n < 10000 else max(a.iters // 5, 3)
-        times = {i: [] for i in impls}
-        for _ in range(a.rounds):                                            # alternated: matrix, stream, matrix, stream, ...
-            for i in impls:
-                times[i].append(timed(lambda: ops.hard_negative_topk(emb, edges, a.k, impl=i), iters))
+        routes = {i: lambda i=i: ops.hard_negative_topk(emb, edges, a.k, impl=i) for i in impls}
+        times = {i: [1e3 * t.event_ms for t in ts]                           # us; alternated: matrix, stream, matrix, stream, ...
+                 for i, ts in alternate(routes, iters, rounds=a.rounds, route_warmup=3).items()}
         row = {"n": n, "d": a.d, "E": E, "k": a.k, "iters": iters, "rounds": a.rounds}
         for i in impls:
             t = sorted(times[i])
@@ -100,13 +86,9 @@ def compare(a):
             row["same_pairs"] = bool(torch.equal(m, s))
             row["max_score_diff"] = float((ms - ss).abs().max())
             row["stream_over_matrix"] = round(row["stream_us"] / row["matrix_us"], 3)
-        print(json.dumps(row), flush=True)
+        emit(row, None)
         rows.append(row)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            json.dump({"device": torch.cuda.get_device_name(0), "rows": rows}, f, indent=1)
-            f.write("\n")
+    emit({"device": torch.cuda.get_device_name(0), "rows": rows}, a.out, indent=1)
 
 
 def main():
@@ -120,23 +102,24 @@ def main():
     p.add_argument("--k", type=int, default=256)
     p.add_argument("--iters", type=int, default=50)
     a = p.parse_args()
+    require_gpu("bench_miner.py")
     a.n_given = any(x == "--n" or x.startswith("--n=") for x in sys.argv[1:])
     if a.impl is not None:
         return compare(a)
     g = torch.Generator().manual_seed(0)
     emb = torch.randn(a.n, a.d, generator=g).cuda()
     edges = torch.randint(0, a.n, (2, a.edges), generator=g).cuda()
-    t_hip = timed(lambda: ops.hard_negative_topk(emb, edges, a.k), a.iters)
-    t_torch = timed(lambda: torch_sequence(emb, edges, a.k), max(a.iters // 5, 3))
+    t_hip = 1e3 * timed(lambda: ops.hard_negative_topk(emb, edges, a.k), a.iters, warmup=3).event_ms                  # us
+    t_torch = 1e3 * timed(lambda: torch_sequence(emb, edges, a.k), max(a.iters // 5, 3), warmup=3).event_ms
     from oracle import miner as OM
     t0 = time.time()
     OM.mine_hard_negatives_for_edges(emb.cpu(), edges[:, :a.k].cpu(), a.k, edges.cpu())
     t_cpu = (time.time() - t0) * 1e6
     # algorithmic traffic: write S once (n^2*4), read it 7 times (6 select passes + gather), read emb twice
     alg = a.n * a.n * 4 * 8 + 2 * a.n * a.d * 4
-    print(json.dumps({"n": a.n, "d": a.d, "k": a.k, "hip_us": round(t_hip, 1), "torch_gpu_us": round(t_torch, 1),
-                      "cpu_oracle_us": round(t_cpu, 1), "speedup_vs_torch_gpu": round(t_torch / t_hip, 2),
-                      "algorithmic_GBps": round(alg / t_hip / 1e3, 1), "gemm_TFLOPs_if_alone": round(2 * a.n * a.n * a.d / t_hip / 1e6, 2)}))
+    emit({"n": a.n, "d": a.d, "k": a.k, "hip_us": round(t_hip, 1), "torch_gpu_us": round(t_torch, 1),
+          "cpu_oracle_us": round(t_cpu, 1), "speedup_vs_torch_gpu": round(t_torch / t_hip, 2),
+          "algorithmic_GBps": round(alg / t_hip / 1e3, 1), "gemm_TFLOPs_if_alone": round(2 * a.n * a.n * a.d / t_hip / 1e6, 2)}, None)
 
 
 if __name__ == "__main__":

@@ -12,7 +12,6 @@ kernel's.  Per-kernel times: run under `rocprofv3 --kernel-trace --stats -- pyth
 from __future__ import annotations
 
 import argparse
-import json
 import os
 import statistics
 import sys
@@ -22,9 +21,9 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
+from benchkit import DEV, alternate, emit, require_gpu  # noqa: E402
 from gnn_pretraining_amd import _lib as L, ops  # noqa: E402
 
-DEV = torch.device("cuda")
 D, T = 128, 0.2
 PEAK_F32_MFMA = 157.3e12
 BOTH, STREAM_ONLY = (512, 2048, 8192), (16384, 32768)
@@ -48,16 +47,6 @@ def make_call(form: str, z1, z2, gs):
     return call, (loss, g1, g2), ws.numel()
 
 
-def time_ms(call, reps: int) -> float:
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        call()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / reps
-
-
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -65,8 +54,7 @@ def main() -> None:
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_ntxent.py measures on the GPU; none found")
+    require_gpu("bench_ntxent.py")
     gs = torch.full((1,), 0.25, device=DEV)
     rows = []
     for n in BOTH + STREAM_ONLY:
@@ -79,11 +67,7 @@ def main() -> None:
             calls[f], outs[f], row[f + "_workspace_bytes"] = make_call(f, z1, z2, gs)
             for _ in range(a.warmup):
                 calls[f]()
-        torch.cuda.synchronize()
-        times = {f: [] for f in forms}
-        for _ in range(a.rounds):
-            for f in forms:
-                times[f].append(time_ms(calls[f], reps))
+        times = {f: [t.event_ms for t in ts] for f, ts in alternate(calls, reps, rounds=a.rounds).items()}
         for f in forms:
             row[f + "_ms"] = statistics.median(times[f])
             row[f + "_ms_min_max"] = [min(times[f]), max(times[f])]
@@ -97,16 +81,12 @@ def main() -> None:
                                        "g_z1_rel_to_max": ((s1 - m1).abs().max() / m1.abs().max()).item(),
                                        "g_z2_rel_to_max": ((s2 - m2).abs().max() / m2.abs().max()).item()}
         rows.append(row)
-        print(json.dumps(row), flush=True)
+        emit(row, None)
         del calls, outs
         torch.cuda.empty_cache()
     res = {"bench": "nt_xent forward + backward, matrix form vs stream form", "device": torch.cuda.get_device_name(0),
            "warmup": a.warmup, "rounds": a.rounds, "peak_f32_mfma_flops": PEAK_F32_MFMA, "rows": rows}
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            json.dump(res, f, indent=1)
-            f.write("\n")
+    emit(res, a.out, indent=1)
 
 
 if __name__ == "__main__":

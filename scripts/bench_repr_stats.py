@@ -8,7 +8,6 @@ two routes' results lie apart.  No speed bar is set: the condition is the memory
 holds no n x n array (it stays below 4 n^2 bytes at 19,717 and 65,535 rows; exit status 1 otherwise).
     python scripts/bench_repr_stats.py --out profiles/repr_stats.json"""
 import argparse
-import json
 import os
 import sys
 
@@ -16,6 +15,7 @@ import torch
 import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from benchkit import alternate, emit, peak, require_gpu                           # noqa: E402
 from gnn_pretraining_amd import ops                                               # noqa: E402
 
 SIZES = (2708, 19717, 65535)
@@ -34,31 +34,6 @@ def torch_gram(z):
     return zd.t() @ zd, zd.sum(dim=0)
 
 
-def timed(fn, iters):
-    for _ in range(2):
-        fn()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(iters):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) / iters * 1e3          # us
-
-
-def peak_bytes(fn):
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
-    before = torch.cuda.memory_allocated()
-    torch.cuda.reset_peak_memory_stats()
-    out = fn()
-    torch.cuda.synchronize()
-    peak = torch.cuda.max_memory_allocated()
-    del out
-    return peak, peak - before
-
-
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--out", type=str, default=None, help="also write the rows to this JSON file")
@@ -67,8 +42,7 @@ def main():
     p.add_argument("--rounds", type=int, default=3, help="alternated rounds per case")
     p.add_argument("--iters", type=int, default=20, help="calls per round at fewer than 10,000 rows (a fifth of it above, at least 2)")
     a = p.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_repr_stats.py measures on the GPU: no device found")
+    require_gpu("bench_repr_stats.py")
     rows, ok = [], True
     for n in SIZES:
         z = torch.randn(n, a.d, generator=torch.Generator().manual_seed(0)).cuda()
@@ -77,16 +51,14 @@ def main():
             raise SystemExit(f"bench_repr_stats.py: the torch route needs about {5 * 4 * n * n >> 30} GiB of free device memory at n = {n}")
         for stat, routes in (("pair_stats", {"kernel": lambda: ops.repr_pair_stats(z, a.t), "torch": lambda: torch_pair_stats(z, a.t)}),
                              ("gram", {"kernel": lambda: ops.repr_gram(z), "torch": lambda: torch_gram(z)})):
-            times = {r: [] for r in routes}
-            for _ in range(a.rounds):
-                for r, fn in routes.items():
-                    times[r].append(timed(fn, iters))
+            times = {r: [1e3 * t.event_ms for t in ts] for r, ts in alternate(routes, iters, rounds=a.rounds, route_warmup=2).items()}      # us
             row = {"statistic": stat, "n": n, "d": a.d, "iters": iters, "rounds": a.rounds, "matrix_bytes": 4 * n * n}
             for r, fn in routes.items():
                 ts = sorted(times[r])
                 row[f"{r}_us"] = round(ts[len(ts) // 2], 1)
                 row[f"{r}_us_rounds"] = [round(x, 1) for x in times[r]]
-                row[f"{r}_peak_bytes"], row[f"{r}_peak_bytes_above_input"] = peak_bytes(fn)
+                above, total = peak(fn)[:2]                                       # (the output dies here, before the next route's peak)
+                row[f"{r}_peak_bytes"], row[f"{r}_peak_bytes_above_input"] = total, above
             k, ref = routes["kernel"](), routes["torch"]()
             if stat == "pair_stats":
                 pairs = n * (n - 1) / 2
@@ -98,15 +70,11 @@ def main():
             if n in MEMORY_BAR_ROWS:
                 row["no_n_by_n_array"] = row["kernel_peak_bytes_above_input"] < 4 * n * n
                 ok = ok and row["no_n_by_n_array"]
-            print(json.dumps(row), flush=True)
+            emit(row, None)
             rows.append(row)
             del routes, k, ref
         del z
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            json.dump({"device": torch.cuda.get_device_name(0), "memory_condition_met": ok, "rows": rows}, f, indent=1)
-            f.write("\n")
+    emit({"device": torch.cuda.get_device_name(0), "memory_condition_met": ok, "rows": rows}, a.out, indent=1)
     sys.exit(0 if ok else 1)
 
 

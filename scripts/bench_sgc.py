@@ -17,62 +17,23 @@ The star graph measures the accepted cost of the sequential row sum: the hub's r
 from __future__ import annotations
 
 import argparse
-import json
 import os
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
+from benchkit import DEV, alternate, attempt, emit, peak, random_graph, record_min, require_gpu  # noqa: E402
 from gnn_pretraining_amd import ops  # noqa: E402
 from gnn_pretraining_amd.finetune import node_baselines as NB  # noqa: E402
 from gnn_pretraining_amd.graph import SparseFeatures  # noqa: E402
 
-DEV = torch.device("cuda")
 ROUNDS = 2
 # name, nodes, random edges, features, density (0 = dense), hub neighbours
 SHAPES = (("cora", 2708, 5429, 1433, 0.0127, 0), ("citeseer", 3327, 4552, 3703, 0.0086, 0), ("pubmed", 19717, 44324, 500, 0.0, 0),
           ("star", 20000, 40000, 1433, 0.0127, 10000))
-
-
-def timed(fn, reps: int):
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    t0 = time.perf_counter()
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return 1e3 * (time.perf_counter() - t0) / reps, e0.elapsed_time(e1) / reps
-
-
-def peak_mb(fn):
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
-    base = torch.cuda.memory_allocated()
-    torch.cuda.reset_peak_memory_stats()
-    out = fn()
-    torch.cuda.synchronize()
-    return (torch.cuda.max_memory_allocated() - base) / 2 ** 20, out
-
-
-def attempt(fn):
-    try:
-        return fn(), None
-    except Exception as e:                                                          # noqa: BLE001  (recorded, not hidden)
-        torch.cuda.synchronize()
-        return None, f"{type(e).__name__}: {str(e).splitlines()[0][:160]}"
-
-
-def make_graph(N: int, E: int, hub: int, gen: torch.Generator):
-    edges = torch.randint(0, N, (2, E), generator=gen)
-    if hub:
-        edges = torch.cat([edges, torch.stack([torch.zeros(hub, dtype=torch.int64), torch.arange(1, hub + 1)])], dim=1)
-    return edges.to(DEV).contiguous()
 
 
 def make_features(N: int, d: int, density: float, gen: torch.Generator):
@@ -85,7 +46,7 @@ def make_features(N: int, d: int, density: float, gen: torch.Generator):
 
 def bench_shape(name: str, N: int, E: int, d: int, density: float, hub: int, a) -> dict:
     gen = torch.Generator().manual_seed(N)
-    rowptr, col, scale = NB.sgc_graph(make_graph(N, E, hub, gen), N)
+    rowptr, col, scale = NB.sgc_graph(random_graph(N, E, hub, gen), N)
     x, xs = make_features(N, d, density, gen)
     res = {"graph": name, "nodes": N, "edges": E + hub, "nnz": int(col.numel()), "features": d, "rounds": ROUNDS,
            "feature_nnz": int(xs.nnz) if xs is not None else N * d, "max_degree": int((rowptr[1:] - rowptr[:-1]).max())}
@@ -113,14 +74,14 @@ def bench_shape(name: str, N: int, E: int, d: int, density: float, hub: int, a) 
     for k, fn in candidates.items():
         def first(fn=fn):
             fn()
-            return peak_mb(fn)
+            return peak(fn)
         got, err = attempt(first)
         if err is not None:
             res[f"{k}_error"] = err
             torch.cuda.empty_cache()
             continue
-        routes[k], outs[k] = fn, got[1]
-        res[f"{k}_peak_mb"] = round(got[0], 3)
+        routes[k], outs[k] = fn, got.out
+        res[f"{k}_peak_mb"] = round(got.above_bytes / 2 ** 20, 3)
     want = outs["kernel_dense"]
     res["max_abs_value"] = float(want.abs().max())
     if "kernel_sparse" in outs:
@@ -129,17 +90,7 @@ def bench_shape(name: str, N: int, E: int, d: int, density: float, hub: int, a) 
         if k in outs:
             res[f"{k}_max_abs_diff"] = float((outs[k] - want).abs().max())
     outs.clear()
-    for _ in range(a.warmup):
-        for fn in routes.values():
-            fn()
-    times = {k: [] for k in routes}
-    for _ in range(3):                                                              # alternate the routes: the order does not decide the result
-        for k, fn in routes.items():
-            times[k].append(timed(fn, a.reps))
-    for k, ts in times.items():
-        res[f"{k}_ms"] = round(min(t[0] for t in ts), 4)
-        res[f"{k}_event_ms"] = round(min(t[1] for t in ts), 4)
-        res[f"{k}_ms_runs"] = [round(t[0], 4) for t in ts]
+    record_min(res, alternate(routes, a.reps, warmup=a.warmup), 4)                  # alternated: the order does not decide the result
     return res
 
 
@@ -149,15 +100,12 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    require_gpu("bench_sgc.py")
     res = {"what": "S^2 X, S = D~^-1/2 (A + I) D~^-1/2; kernel_* = gmp_feature_propagate (one launch per round, sequential row sums) on the "
                    "dense / the CSR X, torch_* = torch.sparse.mm on a CSR of S with the dense / the CSR X; *_event_ms = device-event time "
                    "of a call, *_peak_mb = allocator peak above the inputs",
            "rounds": ROUNDS, "reps": a.reps, "warmup": a.warmup, "shapes": [bench_shape(*s, a) for s in SHAPES]}
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    emit(res, a.out)
     bad = [s["graph"] for s in res["shapes"] if not s.get("kernel_sparse_equals_kernel_dense_bitwise", True)
            or any(s.get(f"{k}_max_abs_diff", 0.0) > 1e-5 * max(s["max_abs_value"], 1.0) for k in ("torch_dense", "torch_sparse"))]
     if bad:

@@ -19,17 +19,15 @@ script fails when they are not."""
 from __future__ import annotations
 
 import argparse
-import json
 import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import torch  # noqa: E402
 
-from bench_wl import DEV, SHAPES, attempt, peak_mb, synthetic_batch, timed  # noqa: E402
+from benchkit import DEV, GRAPH_SHAPES, alternate, attempt, emit, peak, record_min, require_gpu, synthetic_batch  # noqa: E402
 from gnn_pretraining_amd import ops  # noqa: E402
 from gnn_pretraining_amd.finetune.link_heuristics import simple_graph  # noqa: E402
 
@@ -104,8 +102,8 @@ def bench_shape(name: str, graphs: int, mean_nodes: float, mean_edges: float, bi
         return ops.sp_features(ptr, rowptr, col, labels, a.max_dist, a.dim, max_graph_nodes=mgn, cap=cap)
 
     k_features()
-    peak, feat = peak_mb(k_features)
-    res["features_kernel_peak_mb"] = round(peak, 3)
+    above, _, feat = peak(k_features)
+    res["features_kernel_peak_mb"] = round(above / 2 ** 20, 3)
     status = feat.status.cpu()
     res["status_bits"] = {"too_large": int((status & 1).ne(0).sum()), "key_overflow": int((status & 2).ne(0).sum()),
                           "label_range": int((status & 4).ne(0).sum()), "skipped_entries": int((status >> 8).sum())}
@@ -117,8 +115,8 @@ def bench_shape(name: str, graphs: int, mean_nodes: float, mean_edges: float, bi
     def k_gram():
         return ops.sp_gram(feat.keys, feat.counts, feat.nuniq, feat.keys, feat.counts, feat.nuniq)
 
-    peak, K = peak_mb(k_gram)
-    res["gram_kernel_peak_mb"] = round(peak, 3)
+    above, _, K = peak(k_gram)
+    res["gram_kernel_peak_mb"] = round(above / 2 ** 20, 3)
     routes = {"features_kernel": k_features, "gram_kernel": k_gram}
     kg, kk, kc = kernel_rows(feat)
 
@@ -127,37 +125,28 @@ def bench_shape(name: str, graphs: int, mean_nodes: float, mean_edges: float, bi
         res["features_torch_error"] = err
     else:
         t_features = torch_features(*out, a.max_dist)
-        out, err = attempt(lambda: peak_mb(t_features))
+        out, err = attempt(lambda: peak(t_features))
         if err is not None:
             res["features_torch_error"] = err
             torch.cuda.empty_cache()
         else:
-            res["features_torch_peak_mb"] = round(out[0], 3)
-            tg, tk, tc = out[1]
+            res["features_torch_peak_mb"] = round(out.above_bytes / 2 ** 20, 3)
+            tg, tk, tc = out.out
             keep = accepted[tg]                                                   # (a graph the kernel refused has no rows to compare)
             res["features_equal"] = bool(torch.equal(tg[keep], kg) and torch.equal(tk[keep], kk) and torch.equal(tc[keep], kc))
             routes["features_torch"] = t_features
     t_gram = torch_gram(kg, kk, kc, graphs)
-    out, err = attempt(lambda: peak_mb(t_gram))
+    out, err = attempt(lambda: peak(t_gram))
     if err is not None:
         res["gram_torch_error"] = err
         torch.cuda.empty_cache()
     else:
-        res["gram_torch_peak_mb"] = round(out[0], 3)
-        res["gram_equal"] = bool(torch.equal(out[1], K))
+        res["gram_torch_peak_mb"] = round(out.above_bytes / 2 ** 20, 3)
+        res["gram_equal"] = bool(torch.equal(out.out, K))
         routes["gram_torch"] = t_gram
     del out
-    for _ in range(a.warmup):
-        for fn in routes.values():
-            fn()
-    times = {k: [] for k in routes}
-    for _ in range(3):                                                            # alternate the routes: the order does not decide the result
-        for k, fn in routes.items():
-            times[k].append(timed(fn, a.reps if k.endswith("kernel") else max(a.reps // 5, 1)))
-    for k, ts in times.items():
-        res[f"{k}_ms"] = round(min(t[0] for t in ts), 3)
-        res[f"{k}_event_ms"] = round(min(t[1] for t in ts), 3)
-        res[f"{k}_ms_runs"] = [round(t[0], 3) for t in ts]
+    reps = {k: a.reps if k.endswith("kernel") else max(a.reps // 5, 1) for k in routes}
+    record_min(res, alternate(routes, reps, warmup=a.warmup), 3)                  # alternated: the order does not decide the result
     return res
 
 
@@ -169,15 +158,12 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    require_gpu("bench_sp.py")
     res = {"what": "shortest-path features (sorted distinct (label, label, distance) keys with counts, histograms) of one batch and the Gram of "
                    "the batch with itself; kernel = gmp_sp_features / gmp_sp_gram, torch = dense adjacency + one bmm per level + torch.unique, "
                    "torch.unique + dense fp64 count-matrix product",
-           "max_dist": a.max_dist, "dim": a.dim, "reps": a.reps, "warmup": a.warmup, "shapes": [bench_shape(*s, a) for s in SHAPES]}
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+           "max_dist": a.max_dist, "dim": a.dim, "reps": a.reps, "warmup": a.warmup, "shapes": [bench_shape(*s, a) for s in GRAPH_SHAPES]}
+    emit(res, a.out)
     bad = [s["name"] for s in res["shapes"] for k, v in s.items() if k.endswith("_equal") and not v]
     if bad:
         raise SystemExit(f"the kernel and the torch form disagree on {bad}")

@@ -11,7 +11,6 @@ Per-kernel times: run the script under `rocprofv3 --kernel-trace --stats -- pyth
 from __future__ import annotations
 
 import argparse
-import json
 import os
 import statistics
 import sys
@@ -22,6 +21,7 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
+from benchkit import alternate, emit, require_gpu  # noqa: E402
 from gnn_pretraining_amd import _lib as L, synthetic as S  # noqa: E402
 from gnn_pretraining_amd.finetune.engine import NodeClassificationEngine  # noqa: E402
 from gnn_pretraining_amd.graph import SparseFeatures  # noqa: E402
@@ -31,16 +31,6 @@ H = 256
 SHAPES = {"Cora_NC": dict(num_nodes=2708, undirected_edges=5278, dim=1433, density=0.0127, num_classes=7),
           "CiteSeer_NC": dict(num_nodes=3327, undirected_edges=4552, dim=3703, density=0.0085, num_classes=6)}
 HBM_TBS, MFMA_F32_TFLOPS = 8.0, 157.0          # MI355X: HBM3E peak, dense fp32 MFMA peak
-
-
-def timed(fn, reps: int) -> float:
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-    ev[0].record()
-    for _ in range(reps):
-        fn()
-    ev[1].record()
-    torch.cuda.synchronize()
-    return ev[0].elapsed_time(ev[1]) * 1e3 / reps        # us per call
 
 
 def encoder_legs(dense: NodeClassificationEngine, sparse: NodeClassificationEngine):
@@ -81,6 +71,7 @@ def main() -> None:
     ap.add_argument("--steps", type=int, default=100, help="engine steps per timed round")
     ap.add_argument("--out", type=str, default=None)
     a = ap.parse_args()
+    require_gpu("bench_sparse_encoder.py")
     dev = torch.device("cuda:0")
     report = {"device": torch.cuda.get_device_name(dev), "legs": {}}
     for domain, shp in SHAPES.items():
@@ -99,11 +90,8 @@ def main() -> None:
         for fn in legs.values():                              # warm-up: code objects, LDS attributes, caches
             for _ in range(10):
                 fn()
-        torch.cuda.synchronize()
-        samples = {k: [] for k in legs}
-        for _ in range(a.rounds):                             # the forms alternate within each round
-            for k, fn in legs.items():
-                samples[k].append(timed(fn, a.reps))
+        samples = {k: [1e3 * t.event_ms for t in ts]          # us per call; the forms alternate within each round
+                   for k, ts in alternate(legs, a.reps, rounds=a.rounds).items()}
         # engine step, eager default, dense and sparse alternating
         for e in engines.values():
             for _ in range(10):
@@ -140,12 +128,10 @@ def main() -> None:
             leg[f"step_ms_{k}"] = {"median": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4)}
         leg["loss_after"] = losses
         report["legs"][domain] = leg
-        print(json.dumps({domain: leg}), flush=True)
+        emit({domain: leg}, None)
         del engines
         torch.cuda.empty_cache()
-    if a.out:
-        with open(a.out, "w") as f:
-            json.dump(report, f, indent=1)
+    emit(report, a.out, indent=1)
 
 
 if __name__ == "__main__":

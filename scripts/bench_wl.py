@@ -14,22 +14,17 @@ arithmetic: the colours, the histograms and the Gram must be equal, and the scri
 from __future__ import annotations
 
 import argparse
-import json
 import os
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
+from benchkit import DEV, GRAPH_SHAPES, alternate, attempt, emit, peak, record_min, require_gpu, synthetic_batch  # noqa: E402
 from gnn_pretraining_amd import ops  # noqa: E402
 from gnn_pretraining_amd.finetune.link_heuristics import simple_graph  # noqa: E402
-
-DEV = torch.device("cuda")
-# name, graphs, mean nodes, mean edges, one graph of this many nodes (0: none), discrete labels (0: start from degrees)
-SHAPES = (("ENZYMES", 600, 32.6, 62.1, 0, 0), ("NCI1", 4110, 29.9, 32.3, 0, 37), ("PROTEINS", 1113, 39.1, 72.8, 620, 0))
 
 
 def _s64(v: int) -> int:
@@ -49,52 +44,6 @@ def mix(z):
     z = z ^ _lsr(z, 27)
     z = z * M2
     return z ^ _lsr(z, 31)
-
-
-def timed(fn, reps: int):
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    t0 = time.perf_counter()
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return 1e3 * (time.perf_counter() - t0) / reps, e0.elapsed_time(e1) / reps
-
-
-def peak_mb(fn):
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
-    base = torch.cuda.memory_allocated()
-    torch.cuda.reset_peak_memory_stats()
-    out = fn()
-    torch.cuda.synchronize()
-    return (torch.cuda.max_memory_allocated() - base) / 2 ** 20, out
-
-
-def attempt(fn):
-    try:
-        return fn(), None
-    except Exception as e:                                                        # noqa: BLE001  (recorded, not hidden: see the docstring)
-        torch.cuda.synchronize()
-        return None, f"{type(e).__name__}: {str(e).splitlines()[0][:160]}"
-
-
-def synthetic_batch(graphs: int, mean_nodes: float, mean_edges: float, big: int, num_labels: int, gen: torch.Generator):
-    sizes = torch.poisson(torch.full((graphs,), mean_nodes - 2.0), generator=gen).to(torch.int64) + 2
-    sizes = sizes.clamp(max=ops.WL_MAX_GRAPH_NODES)
-    if big:
-        sizes[graphs // 2] = big
-    ptr = torch.zeros(graphs + 1, dtype=torch.int64)
-    ptr[1:] = torch.cumsum(sizes, 0)
-    edges = torch.round(sizes.double() * (mean_edges / mean_nodes)).to(torch.int64)
-    owner = torch.repeat_interleave(torch.arange(graphs), edges)
-    u = (torch.rand(owner.numel(), generator=gen) * sizes[owner]).to(torch.int64) + ptr[owner]
-    v = (torch.rand(owner.numel(), generator=gen) * sizes[owner]).to(torch.int64) + ptr[owner]
-    N = int(ptr[-1])
-    labels = torch.randint(0, num_labels, (N,), generator=gen) if num_labels else None
-    return ptr.to(DEV), torch.stack([u, v]).to(DEV).contiguous(), N, None if labels is None else labels.to(DEV)
 
 
 def torch_refine(ptr, rowptr, col, labels, iters: int, dim: int):
@@ -142,46 +91,37 @@ def bench_shape(name: str, graphs: int, mean_nodes: float, mean_edges: float, bi
         return ops.wl_refine(ptr, rowptr, col, labels, a.iters, a.dim, max_graph_nodes=mgn, return_colors=True)
 
     k_refine()
-    peak, ref = peak_mb(lambda: ops.wl_refine(ptr, rowptr, col, labels, a.iters, a.dim, max_graph_nodes=mgn))
-    res["refine_kernel_peak_mb"] = round(peak, 3)
+    above, _, ref = peak(lambda: ops.wl_refine(ptr, rowptr, col, labels, a.iters, a.dim, max_graph_nodes=mgn))
+    res["refine_kernel_peak_mb"] = round(above / 2 ** 20, 3)
     ref = k_refine()
     assert not bool(ref.status.any())
 
     def k_gram():
         return ops.wl_gram(ref.sorted, ptr, ref.sorted, ptr, a.iters)
 
-    peak, K = peak_mb(k_gram)
-    res["gram_kernel_peak_mb"] = round(peak, 3)
+    above, _, K = peak(k_gram)
+    res["gram_kernel_peak_mb"] = round(above / 2 ** 20, 3)
     routes = {"refine_kernel": lambda: ops.wl_refine(ptr, rowptr, col, labels, a.iters, a.dim, max_graph_nodes=mgn), "gram_kernel": k_gram}
     t_refine, gid = torch_refine(ptr, rowptr, col, labels, a.iters, a.dim)
-    out, err = attempt(lambda: peak_mb(t_refine))
+    out, err = attempt(lambda: peak(t_refine))
     if err is not None:
         res["refine_torch_error"] = err
     else:
-        res["refine_torch_peak_mb"] = round(out[0], 3)
-        res["refine_equal"] = bool(torch.equal(out[1][0], ref.colors) and torch.equal(out[1][1], ref.hist))
+        res["refine_torch_peak_mb"] = round(out.above_bytes / 2 ** 20, 3)
+        res["refine_equal"] = bool(torch.equal(out.out[0], ref.colors) and torch.equal(out.out[1], ref.hist))
         routes["refine_torch"] = t_refine
     t_gram = torch_gram(ref.colors, gid, graphs)
-    out, err = attempt(lambda: peak_mb(t_gram))
+    out, err = attempt(lambda: peak(t_gram))
     if err is not None:
         res["gram_torch_error"] = err
         torch.cuda.empty_cache()
     else:
-        res["gram_torch_peak_mb"] = round(out[0], 3)
-        res["gram_equal"] = bool(torch.equal(out[1], K))
+        res["gram_torch_peak_mb"] = round(out.above_bytes / 2 ** 20, 3)
+        res["gram_equal"] = bool(torch.equal(out.out, K))
         routes["gram_torch"] = t_gram
     del out
-    for _ in range(a.warmup):
-        for fn in routes.values():
-            fn()
-    times = {k: [] for k in routes}
-    for _ in range(3):                                                            # alternate the routes: the order does not decide the result
-        for k, fn in routes.items():
-            times[k].append(timed(fn, a.reps if k.endswith("kernel") else max(a.reps // 5, 1)))
-    for k, ts in times.items():
-        res[f"{k}_ms"] = round(min(t[0] for t in ts), 3)
-        res[f"{k}_event_ms"] = round(min(t[1] for t in ts), 3)
-        res[f"{k}_ms_runs"] = [round(t[0], 3) for t in ts]
+    reps = {k: a.reps if k.endswith("kernel") else max(a.reps // 5, 1) for k in routes}
+    record_min(res, alternate(routes, reps, warmup=a.warmup), 3)                  # alternated: the order does not decide the result
     return res
 
 
@@ -193,14 +133,11 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    require_gpu("bench_wl.py")
     res = {"what": "WL subtree refinement (colours, sorted lists, histograms) of one batch and the Gram of the batch with itself; kernel = "
                    "gmp_wl_refine / gmp_wl_gram, torch = int64 mix + index_add_ per round, torch.unique + dense count-matrix product",
-           "iters": a.iters, "dim": a.dim, "reps": a.reps, "warmup": a.warmup, "shapes": [bench_shape(*s, a) for s in SHAPES]}
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+           "iters": a.iters, "dim": a.dim, "reps": a.reps, "warmup": a.warmup, "shapes": [bench_shape(*s, a) for s in GRAPH_SHAPES]}
+    emit(res, a.out)
     bad = [s["name"] for s in res["shapes"] for k, v in s.items() if k.endswith("_equal") and not v]
     if bad:
         raise SystemExit(f"the kernel and the torch form disagree on {bad}")
