@@ -1,4 +1,5 @@
-"""ctypes binding of libgnnmp.so (include/gnnmp.h).
+"""ctypes binding of libgnnmp.so.  Every prototype, struct and constant is read from include/gnnmp.h and
+include/gnnmp_step.h by _abi.py: to bind something new, declare it in the header.
 
 The product path has NO fallback: if the shared library is missing or a symbol
 is absent this module raises, and every operator in the package goes through it.
@@ -7,28 +8,27 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-import re
 from typing import Dict, List
+
+from ._abi import HEADER_PATH, STEP_HEADER_PATH, GnnmpError, load  # noqa: F401  (re-exported)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgnnmp.so")
-HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "gnnmp.h")
 
-OK = 0
+ABI = load()                    # constants, structs and prototypes of include/gnnmp.h and include/gnnmp_step.h
+K: Dict[str, int] = ABI.constants
+_SIGS: Dict[str, tuple] = ABI.functions     # name -> (restype, [argtypes])
 
-
-class GnnmpError(RuntimeError):
-    pass
-
-
-STEP_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "gnnmp_step.h")
+OK = K["GMP_OK"]
+p, i64, i32, f32, sz = C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_size_t
+BnConfig, AugMasksJob, AugViewsJob, AugNegJob = (ABI.structs["gmp_" + n] for n in ("bn_config", "aug_masks_job", "aug_views_job", "aug_neg_job"))
+SURGERY_RULES = {"reference": K["GMP_SURGERY_REFERENCE"], "pcgrad": K["GMP_SURGERY_PCGRAD"], "mean": K["GMP_SURGERY_MEAN"]}
+SURGERY_SCOPES = {"tensor": K["GMP_SURGERY_SCOPE_TENSOR"], "model": K["GMP_SURGERY_SCOPE_MODEL"]}
 
 
 def declared_symbols() -> List[str]:
     """Every function name declared in include/gnnmp.h and include/gnnmp_step.h (used by the export test)."""
-    text = open(HEADER_PATH).read() + open(STEP_HEADER_PATH).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(gmp_[a-z0-9_]+)\s*\(", text)))
+    return sorted(_SIGS)
 
 
 _lib = None
@@ -46,217 +46,18 @@ def lib() -> C.CDLL:
     return _lib
 
 
-p, i64, i32, f32, sz = C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_size_t
-
-
-class AugMasksJob(C.Structure):          # gmp_aug_masks_job (include/gnnmp.h)
-    _fields_ = [("ptr", C.c_void_p), ("out_ptr", C.c_void_p), ("num_graphs", C.c_int32), ("stream_id", C.c_uint32), ("out_idx", C.c_void_p)]
-
-
-class AugViewsJob(C.Structure):          # gmp_aug_views_job
-    _fields_ = [("ptr", C.c_void_p), ("eptr", C.c_void_p), ("edge_index", C.c_void_p), ("num_nodes", C.c_int64), ("num_edges", C.c_int64),
-                ("view_ptr", C.c_void_p), ("num_graphs", C.c_int32), ("num_features", C.c_int32), ("stream_id", C.c_uint32),
-                ("rows1", C.c_void_p), ("rows2", C.c_void_p), ("rowmask1", C.c_void_p), ("rowmask2", C.c_void_p), ("edges1", C.c_void_p),
-                ("edges2", C.c_void_p), ("edge_capacity", C.c_int64), ("common1", C.c_void_p), ("common2", C.c_void_p), ("counts", C.c_void_p),
-                ("totals_and_flags", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
-
-
-class AugNegJob(C.Structure):            # gmp_aug_neg_job
-    _fields_ = [("ptr", C.c_void_p), ("eptr", C.c_void_p), ("edge_index", C.c_void_p), ("num_nodes", C.c_int64), ("num_edges", C.c_int64),
-                ("num_graphs", C.c_int32), ("stream_id", C.c_uint32), ("num_neg", C.c_int64), ("neg_out", C.c_void_p), ("capacity", C.c_int64),
-                ("counts", C.c_void_p), ("total", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
-
-
-class BnConfig(C.Structure):
-    _fields_ = [("training", C.c_int), ("relu", C.c_int), ("eps", C.c_float), ("momentum", C.c_float),
-                ("dropout_p", C.c_float), ("seed", C.c_uint64), ("stream_id", C.c_uint32), ("seed_dev", C.c_void_p),
-                ("sync", C.c_void_p), ("sync_words", C.c_uint32)]
-
-
-_SIGS: Dict[str, tuple] = {
-    "gmp_version": (C.c_int, []),
-    "gmp_last_error_string": (C.c_char_p, []),
-    "gmp_csr_build_workspace_bytes": (sz, [i64, i64]),
-    "gmp_csr_build": (C.c_int, [p, i64, i64, p, p, p, p, p, p, p, p, sz, p]),
-    "gmp_csr_build_segmented": (C.c_int, [p, i64, i64, p, p, i32, i64, i64, p, p, p, p, p, p, p, p]),
-    "gmp_gin_aggregate_fwd": (C.c_int, [p, p, p, p, p, i64, i32, p]),
-    "gmp_gin_aggregate_fwd_rows": (C.c_int, [p, p, p, p, p, i64, i64, i32, p]),
-    "gmp_gin_aggregate_bwd_workspace_bytes": (sz, [i64, i32]),
-    "gmp_gin_aggregate_bwd": (C.c_int, [p, p, p, p, p, p, p, i64, i32, p, sz, p]),
-    "gmp_segment_sum": (C.c_int, [p, p, p, p, i64, i32, i32, i32, p]),
-    "gmp_row_gather": (C.c_int, [p, p, p, p, i64, i64, i32, p]),
-    "gmp_segment_max_fwd": (C.c_int, [p, p, p, i64, i32, p]),
-    "gmp_segment_max_bwd": (C.c_int, [p, p, p, p, p, i64, i32, i32, p]),
-    "gmp_gemm_f32_workspace_bytes": (sz, [i32, i64, i64, i64]),
-    "gmp_gemm_f32": (C.c_int, [i32, p, p, p, p, i64, i64, i64, i64, i64, i64, f32, i32, i32, p, sz, p]),
-    "gmp_gemm_f32_grouped": (C.c_int, [i32, p, p, p, p, i32, p, p, p, p, p, p, i64, i64, i64, i64, i64, i64, f32, i32, i32, p, sz, p]),
-    "gmp_gin_aggregate_bwd_ex": (C.c_int, [p, p, p, p, p, p, p, p, i64, i32, p]),
-    "gmp_group_sum_1d": (C.c_int, [p, i32, p, p, p, p]),
-    "gmp_colsum_workspace_bytes": (sz, [i64, i64]),
-    "gmp_colsum": (C.c_int, [p, p, i64, i64, i64, i32, p, sz, p]),
-    "gmp_sparse_linear_workspace_bytes": (sz, [i64, i32]),
-    "gmp_sparse_linear_fwd": (C.c_int, [p, p, p, i64, i64, p, i64, p, p, i32, i64, p, p, sz, p]),
-    "gmp_sparse_linear_wgrad": (C.c_int, [p, p, p, i64, i64, p, i32, p, i64, p, p]),
-    "gmp_sparse_csc_workspace_bytes": (sz, [i64, i64, i64]),
-    "gmp_sparse_csc_build": (C.c_int, [p, p, p, i64, i64, i64, p, p, p, p, p, sz, p]),
-    "gmp_bn_workspace_bytes": (sz, [i64, i32, i32, i64]),
-    "gmp_bn_sync_bytes": (sz, [i32, i32]),
-    "gmp_bn_fwd": (C.c_int, [p, p, p, p, i32, i64, i64, i32, p, p, p, p, p, p, p, C.POINTER(BnConfig), p, sz, p]),
-    "gmp_bn_param_grads": (C.c_int, [p, i32, i32, p, p, p, p, p, i32, p]),
-    "gmp_bn_running_update_batch": (C.c_int, [i32, p, i32, p, p, p, p, p, p, p, p]),
-    "gmp_bn_running_update": (C.c_int, [p, p, i32, i32, p, p, p, p, p, p]),
-    "gmp_bn_fold": (C.c_int, [i32, p, p, p, p, p, f32, p, p]),
-    "gmp_linear_affine_workspace_bytes": (sz, [i64, i64, i64]),
-    "gmp_linear_affine_fwd": (C.c_int, [p, p, p, p, p, p, p, i64, i64, i64, i64, i64, i64, i64, i32, p, sz, p]),
-    "gmp_bn_bwd": (C.c_int, [p, p, p, p, p, i32, i64, i64, i32, p, p, p, p, p, p, p, p, p, p, p, p, i32,
-                             C.POINTER(BnConfig), p, sz, p]),
-    "gmp_lp_edge_features_fwd": (C.c_int, [p, p, p, i64, i64, i32, p]),
-    "gmp_lp_edge_features_bwd": (C.c_int, [p, p, p, p, p, i64, i64, i32, p]),
-    "gmp_lp_feat_gemm_bwd_fold": (C.c_int, [p, p, p, p, p, p, i64, i64, i32, p]),
-    "gmp_lp_feat_gemm_fwd": (C.c_int, [p, p, p, p, p, i64, i64, i32, p]),
-    "gmp_lp_feat_gemm_wgrad": (C.c_int, [p, p, p, p, p, i64, i64, i32, p, sz, p]),
-    "gmp_lp_feat_gemm_launch_count": (C.c_uint64, []),
-    "gmp_lp_score_fwd_workspace_bytes": (sz, [i64]),
-    "gmp_lp_score_bwd_workspace_bytes": (sz, [i64]),
-    "gmp_lp_score_fwd": (C.c_int, [p, p, p, i64, i64, i32, i32, p, p, p, p, p, p, f32, C.c_uint64, C.c_uint32, p, sz, p]),
-    "gmp_lp_score_bwd": (C.c_int, [p, p, p, i64, i64, i32, i32, p, p, p, p, f32, C.c_uint64, C.c_uint32, p, p, p, p, i32, p, p, p, sz, p]),
-    "gmp_lp_rank_workspace_bytes": (sz, [i64, i64]),
-    "gmp_lp_topk_workspace_bytes": (sz, [i64, i64]),
-    "gmp_lp_rank": (C.c_int, [p, p, p, i64, i64, i32, i32, p, p, p, p, p, p, i64, p, p, p, p, sz, p]),
-    "gmp_lp_topk": (C.c_int, [p, p, i64, i64, i32, i32, i32, p, p, p, p, p, p, i64, p, p, p, sz, p]),
-    "gmp_lp_cn_tile_nodes": (C.c_int, []),
-    "gmp_lp_cn_rank_workspace_bytes": (sz, [i64, i64]),
-    "gmp_lp_cn_score": (C.c_int, [p, p, i64, i64, p, p, i64, p, i32, p, p]),
-    "gmp_lp_cn_rank": (C.c_int, [p, p, i64, i64, p, p, i64, p, i32, p, p, i64, p, p, p, p, sz, p]),
-    "gmp_lp_walk_lds_nodes": (C.c_int, []),
-    "gmp_lp_walk_resident_blocks": (C.c_int, []),
-    "gmp_lp_walk_workspace_bytes": (sz, [i64, i64]),
-    "gmp_lp_walk_score": (C.c_int, [p, p, i64, i64, p, p, i64, p, f32, i32, i32, p, p, sz, p]),
-    "gmp_lp_walk_rank": (C.c_int, [p, p, i64, i64, p, p, i64, p, f32, i32, i32, p, p, i64, p, p, p, p, sz, p]),
-    "gmp_emb_link_workspace_bytes": (sz, [i64, i64, i32]),
-    "gmp_emb_link_score": (C.c_int, [p, i64, i32, i32, p, p, i64, p, p, sz, p]),
-    "gmp_emb_link_rank": (C.c_int, [p, i64, i32, i32, p, p, i64, p, p, i64, p, p, p, p, p, sz, p]),
-    "gmp_graph_simple_check": (C.c_int, [p, p, i64, i64, p, p]),
-    "gmp_knn_workspace_bytes": (sz, [i64, i64, i32, i32]),
-    "gmp_knn_topk": (C.c_int, [p, i64, p, i64, i32, i32, i32, p, p, p, p, sz, p]),
-    "gmp_knn_vote": (C.c_int, [p, p, i64, i32, p, i64, i32, f32, p, p, p, p]),
-    "gmp_kmeans_workspace_bytes": (sz, [i64, i32, i32]),
-    "gmp_kmeans_assign": (C.c_int, [p, i64, p, i32, i32, p, p, p, p, sz, p]),
-    "gmp_kmeans_fit": (C.c_int, [p, i64, p, i32, i32, i32, p, p, p, p, p, sz, p]),
-    "gmp_contingency": (C.c_int, [p, p, i64, i32, i32, p, p, p]),
-    "gmp_logreg_workspace_bytes": (sz, [i64, i32, i32]),
-    "gmp_logreg_fit": (C.c_int, [p, p, i64, i32, i32, i32, f32, f32, p, p, p, p, p, p, p, p, p, p, sz, p]),
-    "gmp_logreg_predict": (C.c_int, [p, i64, p, p, i32, i32, p, p, p, sz, p]),
-    "gmp_repr_workspace_bytes": (sz, [i64, i32]),
-    "gmp_repr_pair_stats": (C.c_int, [p, i64, i32, f32, p, p, sz, p]),
-    "gmp_repr_alignment": (C.c_int, [p, p, i64, i32, f32, p, p, sz, p]),
-    "gmp_repr_gram": (C.c_int, [p, i64, i32, p, p, p, sz, p]),
-    "gmp_cls_counts_workspace_bytes": (sz, [i64, i32]),
-    "gmp_cls_counts": (C.c_int, [p, p, p, i64, i32, p, p, p, p, sz, p]),
-    "gmp_graph_props_workspace_bytes": (sz, [i32, i64]),
-    "gmp_graph_props": (C.c_int, [p, p, p, i64, i64, i32, i64, p, p, p, sz, p]),
-    "gmp_wl_workspace_bytes": (sz, [i32, i64, i32]),
-    "gmp_wl_refine": (C.c_int, [p, i32, p, p, i64, i64, p, i32, i32, i64, p, p, p, p, p, sz, p]),
-    "gmp_wl_gram": (C.c_int, [p, p, i64, i64, p, p, i64, i64, i32, p, p]),
-    "gmp_sp_workspace_bytes": (sz, [i32, i64]),
-    "gmp_sp_max_unique": (C.c_int, [i64]),
-    "gmp_sp_features": (C.c_int, [p, i32, p, p, i64, i64, p, i32, i32, i64, i32, p, p, p, p, p, p, sz, p]),
-    "gmp_sp_gram": (C.c_int, [p, p, p, i64, i32, p, p, p, i64, i32, p, p]),
-    "gmp_label_propagate_workspace_bytes": (sz, [i64, i32]),
-    "gmp_label_propagate": (C.c_int, [p, p, i64, i64, p, p, p, p, p, i32, i32, f32, f32, p, p, p, p, p, sz, p]),
-    "gmp_feature_propagate_workspace_bytes": (sz, [i64, i32, i32]),
-    "gmp_feature_propagate": (C.c_int, [p, p, i64, i64, p, p, p, i64, p, p, p, i64, i32, i32, p, i64, p, p, sz, p]),
-    "gmp_graph_feature_map": (C.c_int, [p, i32, p, p, i64, i64, p, p, p, i64, i32, i32, i64, p, p, p]),
-    "gmp_gc_head_fwd_workspace_bytes": (sz, [i64]),
-    "gmp_gc_head_fwd": (C.c_int, [p, i64, p, i64, i64, i32, i32, i32, p, p, p, p, p, p, p, p, p, p, p, f32, C.c_uint64, C.c_uint32, p, sz, p]),
-    "gmp_gc_head_bwd": (C.c_int, [p, i64, i64, i32, i32, i32, p, p, p, p, p, f32, C.c_uint64, C.c_uint32, p, p, p, p, p, i64, p]),
-    "gmp_nt_xent_workspace_bytes": (sz, [i64, i32]),
-    "gmp_nt_xent_fwd": (C.c_int, [p, p, i64, i32, f32, p, p, sz, p]),
-    "gmp_nt_xent_bwd": (C.c_int, [p, p, i64, i32, f32, p, p, p, p, sz, p]),
-    "gmp_nt_xent_stream_workspace_bytes": (sz, [i64, i32]),
-    "gmp_nt_xent_stream_fwd": (C.c_int, [p, p, i64, i32, f32, p, p, sz, p]),
-    "gmp_nt_xent_stream_bwd": (C.c_int, [p, p, i64, i32, f32, p, p, p, p, sz, p]),
-    "gmp_nt_xent_grouped_workspace_bytes": (sz, [i32, i64, i32]),
-    "gmp_nt_xent_grouped": (C.c_int, [p, p, i32, p, p, i32, f32, p, p, p, p, sz, p]),
-    "gmp_dropout_fwd": (C.c_int, [p, p, i64, f32, C.c_uint64, C.c_uint32, p]),
-    "gmp_relu_dropout_bwd": (C.c_int, [p, p, p, i64, f32, C.c_uint64, C.c_uint32, p]),
-    "gmp_dropout_rowdot_fwd": (C.c_int, [p, p, p, p, p, i64, i32, C.c_float, C.c_uint64, C.c_uint32, p]),
-    "gmp_outer_relu_dropout_bwd": (C.c_int, [p, p, p, p, i64, i32, C.c_float, C.c_uint64, C.c_uint32, p]),
-    "gmp_weighted_colsum_workspace_bytes": (sz, [i64, i32]),
-    "gmp_weighted_colsum": (C.c_int, [p, p, p, p, i64, i32, p, sz, p]),
-    "gmp_lp_pair_rowdot_fwd": (C.c_int, [p, p, p, p, p, i64, i32, C.c_float, C.c_uint64, C.c_uint32, p]),
-    "gmp_lp_pair_sigmoid_bce_fwd_bwd": (C.c_int, [p, p, p, i64, p, p, p, p, p, sz, p]),
-    "gmp_lp_pair_outer_bwd": (C.c_int, [p, p, p, p, p, i64, i32, C.c_float, C.c_uint64, C.c_uint32, p]),
-    "gmp_lp_pair_colsum_workspace_bytes": (sz, [i64, i32]),
-    "gmp_lp_pair_weighted_colsum": (C.c_int, [p, p, p, p, p, i64, i32, C.c_float, C.c_uint64, C.c_uint32, p, sz, p]),
-    "gmp_loss_workspace_bytes": (sz, [i64]),
-    "gmp_mse_sum_fwd": (C.c_int, [p, p, i64, p, p, sz, p]),
-    "gmp_mse_sum_bwd": (C.c_int, [p, p, p, p, i64, p]),
-    "gmp_sigmoid_fwd": (C.c_int, [p, p, i64, p]),
-    "gmp_sigmoid_bwd": (C.c_int, [p, p, p, i64, p]),
-    "gmp_bce_sum_fwd": (C.c_int, [p, p, i64, p, p, sz, p]),
-    "gmp_bce_sum_bwd": (C.c_int, [p, p, p, p, i64, p]),
-    "gmp_sigmoid_bce_sum_fwd_bwd": (C.c_int, [p, p, i64, p, p, p, p, p, sz, p]),
-    "gmp_sigmoid_bce_signed_sum_fwd_bwd": (C.c_int, [p, p, i64, p, p, p, p, p, sz, p]),
-    "gmp_cross_entropy_sum_fwd": (C.c_int, [p, p, i64, i32, p, p, sz, p]),
-    "gmp_cross_entropy_sum_bwd": (C.c_int, [p, p, i64, i32, p, p, p]),
-    "gmp_row_fill": (C.c_int, [p, p, p, i64, i64, i32, i32, p]),
-    "gmp_hard_negative_workspace_bytes": (sz, [i64, i64]),
-    "gmp_hard_negative_topk": (C.c_int, [p, i64, i64, p, i64, i64, p, p, p, p, sz, p]),
-    "gmp_hard_negative_stream_workspace_bytes": (sz, [i64, i64, i64]),
-    "gmp_hard_negative_topk_stream": (C.c_int, [p, i64, i64, p, i64, i64, p, p, p, p, sz, p]),
-    "gmp_streams_share_queue": (C.c_int, [p, p, p]),
-    "gmp_spin_us": (C.c_int, [i32, p]),
-    "gmp_gate_wait": (C.c_int, [p, C.c_uint64, i32, p, p]),
-    "gmp_gate_open": (C.c_int, [p, i32, p]),
-    "gmp_gate_open_by_next_gemm": (C.c_int, [p, i32]),
-    "gmp_gate_open_pending": (C.c_int, []),
-    "gmp_gate_set_timeout": (C.c_int, [C.c_double]),
-    "gmp_counter_add": (C.c_int, [p, C.c_uint64, p]),
-    "gmp_aug_workspace_bytes": (sz, [i64, i64, i32]),
-    "gmp_aug_node_masks": (C.c_int, [p, p, i32, i64, C.c_uint64, C.c_uint32, p, p]),
-    "gmp_aug_node_masks_batch": (C.c_int, [C.POINTER(AugMasksJob), i32, i64, C.c_uint64, p]),
-    "gmp_aug_two_views_batch": (C.c_int, [C.POINTER(AugViewsJob), i32, i64, i64, C.c_uint64, p]),
-    "gmp_aug_two_views": (C.c_int, [p, p, p, i64, i64, p, i32, i64, i64, i32, C.c_uint64, C.c_uint32, p, p, p, p, p, p, i64, p, p, p, p, p, sz, p]),
-    "gmp_aug_negative_edges_workspace_bytes": (sz, [i64, i64, i64]),
-    "gmp_aug_negative_edges": (C.c_int, [p, p, p, i64, i64, i32, i64, i64, C.c_uint64, C.c_uint32, p, i64, p, p, p, sz, p]),
-    "gmp_aug_negative_edges_batch": (C.c_int, [C.POINTER(AugNegJob), i32, i64, C.c_uint64, p]),
-    "gmp_upload": (C.c_int, [i32, p, p, p, p]),
-    "gmp_segments_pack": (C.c_int, [p, p, p, i32, i64, p]),
-    "gmp_segments_unpack": (C.c_int, [p, p, p, i32, i64, f32, p]),
-    "gmp_encoder_fwd": (C.c_int, [p, i64, i64, i32, p, p, p, p, p, i32, p, i32, p, p, p, i32, p, p]),
-    "gmp_encoder_bwd": (C.c_int, [p, i64, i64, i32, p, p, p, p, p, i32, p, i32, i32, p, p, p, p, p, sz, p]),
-    "gmp_step_desc_size": (sz, []),
-    "gmp_pretrain_step_fwd_bwd": (C.c_int, [p, p, p, p]),
-    "gmp_step_wait_grads": (C.c_int, [i32, p]),
-    "gmp_step_phase_ms": (C.c_int, [p]),
-    "gmp_step_phase_detail_ms": (C.c_int, [p]),
-    "gmp_step_head_ms": (C.c_int, [p, i32]),
-    "gmp_mt_workspace_bytes": (sz, [i32]),
-    "gmp_mt_pcgrad_clip_adamw": (C.c_int, [p, i64, i32, i32, p, p, p, p, i32, i32, i32, p, p, p, p, p, p, f32, f32, f32,
-                                           f32, p, p, p, p, p, sz, i32, p]),
-    "gmp_mt_pcgrad_clip_adamw_ex": (C.c_int, [p, i64, i32, i32, p, p, p, p, i32, i32, i32, p, p, p, p, p, p, f32, f32, f32,
-                                              f32, p, p, p, p, p, sz, i32, i32, i32, i32, p, p]),
-    "gmp_mt_surgery_clip_adamw": (C.c_int, [i32, i32, p, p, i64, i32, i32, p, p, p, p, i32, i32, i32, p, p, p, p, p, p, f32, f32, f32,
-                                            f32, p, p, p, p, p, sz, i32, i32, i32, i32, p, p]),
-}
-
-SURGERY_RULES = {"reference": 0, "pcgrad": 1, "mean": 2}      # GMP_SURGERY_* of include/gnnmp.h
-SURGERY_SCOPES = {"tensor": 0, "model": 1}
-
-
 def _declare(l: C.CDLL) -> None:
-    missing = [s for s in declared_symbols() if not hasattr(l, s)]
+    missing = [s for s in _SIGS if not hasattr(l, s)]
     if missing:
         raise GnnmpError(f"libgnnmp.so lacks symbols declared in gnnmp.h: {missing}")
     for name, (res, args) in _SIGS.items():
         fn = getattr(l, name)
         fn.restype = res
         fn.argtypes = args
-    from ._step_desc import StepDesc
-    if l.gmp_step_desc_size() != C.sizeof(StepDesc):
-        raise GnnmpError(f"gnnmp_step.h / _step_desc.py disagree: sizeof(gmp_step_desc) = {l.gmp_step_desc_size()} "
-                         f"but the ctypes mirror is {C.sizeof(StepDesc)} bytes")
+    desc = ABI.structs["gmp_step_desc"]
+    if l.gmp_step_desc_size() != C.sizeof(desc):
+        raise GnnmpError(f"gnnmp_step.h and libgnnmp.so disagree: sizeof(gmp_step_desc) = {l.gmp_step_desc_size()} in the library "
+                         f"but {C.sizeof(desc)} bytes by the header: rebuild the library")
 
 
 def check(rc: int, what: str) -> None:

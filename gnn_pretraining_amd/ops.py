@@ -234,7 +234,7 @@ def segment_max_bwd(g_out: Tensor, x: Tensor, out: Tensor, ptr: Tensor, g_x: Opt
     return g_x
 
 
-NT, NN, TN = 0, 1, 2
+NT, NN, TN = L.K["GMP_GEMM_NT"], L.K["GMP_GEMM_NN"], L.K["GMP_GEMM_TN"]
 
 
 def gemm(mode: int, A: Tensor, B: Tensor, bias: Optional[Tensor] = None, out: Optional[Tensor] = None,

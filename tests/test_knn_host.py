@@ -10,7 +10,6 @@ import knn_ref as R
 from gnn_pretraining_amd import _lib as L
 
 ERR_ARG, ERR_WORKSPACE = -1, -3
-SYMBOLS = ("gmp_knn_workspace_bytes", "gmp_knn_topk", "gmp_knn_vote")
 NINF = float("-inf")
 
 
@@ -59,12 +58,6 @@ def test_reference_vote_sums_in_order_skips_bad_labels_and_breaks_ties_to_the_lo
 
 
 # ---------------------------------------------------------------------------- the C ABI
-def test_symbols_are_declared_bound_and_exported():
-    declared = set(L.declared_symbols())
-    for s in SYMBOLS:
-        assert s in declared and s in L._SIGS and hasattr(L.lib(), s)
-
-
 def test_workspace_holds_no_matrix_and_grows_at_most_linearly():
     ws = L.lib().gmp_knn_workspace_bytes
     assert 0 < ws(1 << 20, 1 << 20, 256, 64) < 4 << 30                           # two normalised copies of 1 GiB + the lists
