@@ -199,8 +199,16 @@ extern "C" int gmp_encoder_bwd(const float* x_all, int64_t num_x_rows, int64_t n
     a.num_x_rows = (int)num_x_rows; a.num_rows = (int)num_rows; a.num_segs = num_segments;
     a.x_all = x_all; a.src_row = src_row; a.seg_ptr = seg_ptr; a.seg_dom = seg_dom;
     a.row_colmask = (const unsigned long long*)row_colmask; a.gz = g_z; a.dpad = dpad; a.groups = groups; a.out = grad_out;
-    for (int d = 0; d < num_domains; ++d) a.d_in[d] = d_in_host[d];
-    for (int g = 0; g <= groups; ++g) a.gseg[g] = group_seg_host[g];
+    for (int d = 0; d < num_domains; ++d) {
+        a.d_in[d] = d_in_host[d];
+        if (a.d_in[d] < 1 || a.d_in[d] > dpad) return gmp::fail(GMP_ERR_ARG, "encoder_bwd: d_in[%d]=%d exceeds dpad %d", d, a.d_in[d], dpad);
+    }
+    // the reduce kernel reads seg_dom[gseg[g]] of every non-empty group: ascending bounds inside [0, num_segments] keep that in range
+    for (int g = 0; g <= groups; ++g) {
+        a.gseg[g] = group_seg_host[g];
+        if (a.gseg[g] < 0 || a.gseg[g] > num_segments || (g > 0 && a.gseg[g] < a.gseg[g - 1]))
+            return gmp::fail(GMP_ERR_ARG, "encoder_bwd: group_seg[%d]=%d descends or leaves [0, %d]", g, a.gseg[g], num_segments);
+    }
     for (int g = 0; g < groups; ++g) { a.off_w[g] = off_w_host[g]; a.off_b[g] = off_b_host[g]; }
     hipStream_t st = (hipStream_t)stream;
     const int dp = dpad <= 8 ? 8 : (dpad <= 24 ? 24 : (dpad <= 40 ? 40 : 64));

@@ -1104,6 +1104,11 @@ int gmp_counter_add(uint64_t* word, uint64_t inc, gmp_stream_t stream);
  * 32 rows each; indices outside [0,num_x_rows) / [0,num_rows) / [0,num_segments) read as zero rows.
  * bwd: one gradient group per (task, domain) pair covering segments
  * group_seg_host[g]..[g+1]; dW lands at grad_out + off_w_host[g] ([256, d_in]), db at + off_b_host[g].
+ * An empty group (group_seg_host[g] == [g+1]) writes nothing; a group whose segments have no rows writes zeros.
+ * workspace (nullable): groups * 16 * 256 * (DP + 1) floats, DP = dpad rounded up to 8 / 24 / 40 / 64, splits each
+ * group's rows over 16 workgroups; without it (or with fewer bytes) one workgroup per group stores directly.
+ * Both entry points return GMP_ERR_ARG, before anything is launched, when a d_in_host[d] lies outside [1, dpad];
+ * gmp_encoder_bwd also when group_seg_host descends or leaves [0, num_segments].
  * ------------------------------------------------------------------------- */
 int gmp_encoder_fwd(const float* x_all, int64_t num_x_rows, int64_t num_rows, int num_segments, const int32_t* src_row, const int32_t* seg_ptr, const int32_t* seg_dom,
                     const uint64_t* row_colmask, const int32_t* tiles, int num_tiles, const float* params,
